@@ -2,13 +2,13 @@
 """bench.py -- DOF-updates/s and ms/RK-stage of the HiFiLES hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--cells CELLS] [--order P] [--mode split3|split|methods|dense]
-                    [--workload tgv|tets|prisms|mixed] [--tiles T]
+                    [--workload tgv|tets|prisms|mixed] [--tiles T] [--dump-outputs DIR] [--full]
 
 One "step" is one time step = 5 RK stages (RK45), each stage = CalcResidual + AdvanceSolution
 (/root/reference/src/HiFiLES.cpp:201-217) over the whole mesh.  Workload at N=1: BASELINE.json
 configs[1], the Taylor-Green vortex on a generated periodic 32^3 hexahedral mesh, P4, Navier-Stokes,
-HLLC + LDG, fixed dt; inputs are resident in HBM before the timed region.  The timed region (K steps between
-barriers + device synchronisation) is repeated 5 times and the MEDIAN is reported.
+HLLC + LDG, fixed dt; inputs are resident in HBM before the timed region.  The timed region is K steps between
+barriers + device synchronisation; with --reps R (default 1, 5 with --full) it is repeated R times and the MEDIAN is reported.
 For N>1 the periodic box is split into N blocks of 32^3 elements on a process grid (2: 2x1x1, 4: 2x2x1, 8: 2x2x2;
 weak scaling), one rank per GPU; every rank advances its block and exchanges partition-face solution and flux
 records with its neighbours twice per RK stage, as the reference's mpi_inters do -- by grouped ncclSend / ncclRecv
@@ -17,7 +17,15 @@ records with its neighbours twice per RK stage, as the reference's mpi_inters do
 `python bench.py --gpus N` it launches its N ranks itself as CHILD processes (before anything touches a GPU) and
 relays rank 0's line.
 
-Prints ONE JSON line (rank 0).  The oracle under oracle/ is used only for the `cpu_baseline` leg.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line; everything else it
+can measure -- the dominant kernel's roofline (per-kernel timing runs of their own), the mirrored CalcResidual +
+AdvanceSolution loop (`api_path`), the partitioned stage's per-phase times, the CPU baselines (`cpu_baseline`) and the short
+legs of the other configurations (`also`) -- runs only with --full.  The oracle under oracle/ is used only for the
+`cpu_baseline` leg.
+
+--dump-outputs DIR writes what the timed path leaves to its caller after its last step -- the solution at the solution
+points, disu_upts(0), of every element block -- as DIR/disu_upts[_<class>].npy in float64 (n_upts, n_eles, n_fields), rank
+0's block; above DUMP_BYTES in all, a fixed, seeded sample of the elements (the same in every run with the same arguments).
 """
 import argparse
 import ctypes as C
@@ -37,6 +45,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 DEFAULT_FUSED = "split3"  # which fused variant `--mode auto` runs
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP64_PEAK_TFLOPS = 78.6   # MI355X FP64 vector = matrix peak
+DUMP_BYTES = 48 << 20     # --dump-outputs writes at most this much in all (the 32^3 P4 state alone is 164 MB)
 
 METHOD_NAMES = ["extrapolate_solution", "calculate_gradient", "evaluate_invFlux", "common_invFlux", "correct_gradient",
                 "evaluate_viscFlux", "extrapolate_totalFlux", "calculate_divergence", "common_viscFlux",
@@ -132,6 +141,19 @@ def reference_baseline(order, n_cells=8, n_steps=8):
     n_upts = (order + 1) ** 3
     dofs = n_cells ** 3 * n_upts * 5 * int(m.group(2)) * int(m.group(1))
     return dict(value=dofs / secs, seconds=secs, n_cells=n_cells, steps=int(m.group(1)))
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every (n_pts, n_eles, n_fields) array of `arrays` as out_dir/<name>.npy in float64; an array above its
+    share of DUMP_BYTES is cut to a sample of its elements drawn with a fixed seed (sorted, so the element order is kept)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        n_eles = a.shape[1]
+        keep = min(n_eles, share // (a.nbytes // n_eles))
+        if keep < n_eles:
+            a = a[:, np.sort(np.random.default_rng(0).choice(n_eles, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def _min_over_ranks(dist, torch, v):
@@ -239,10 +261,14 @@ def general_workload(args):
     elapsed = float(np.median(samples))
     for c in classes:
         assert E[c].check_nan() == -1
+    if args.dump_outputs:
+        cname = {2: "tet", 3: "pri"}
+        dump_outputs(args.dump_outputs, {"disu_upts" + ("_" + cname[c] if len(classes) > 1 else ""): E[c].download(hfx.DISU_UPTS0)
+                                         for c in classes})
     dof = sum(E[c].n_eles * E[c].n_upts * E[c].n_fields for c in classes)
     value = dof * n_stages * args.steps / elapsed
     roof = None
-    if fused:
+    if fused and args.full:
         ea = (C.c_void_p * len(blocks))(*[e.h for e in blocks])
         fa = (C.c_void_p * max(1, len(F)))(*[f.h for f in F])
         ms = (C.c_double * 8)()
@@ -261,7 +287,7 @@ def general_workload(args):
                     kernel_ms_rocprof=k_prof, kernel_ms_rocprof_source=k_src, kernels_ms=times,
                     stage_algorithmic_bytes=sum(by[:4]), stage_hbm_frac=sum(by[:4]) / (1e-3 * sum(ms[:4])) / 1e9 / HBM_PEAK_GBS)
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         # the oracle on ONE tile (the reference is a serial code; the fixture was produced by the genuine reference itself)
         t0 = time.perf_counter()
         reps = 0
@@ -321,11 +347,12 @@ ALSO_LEGS = [
 
 
 def also_legs(args):
-    """Short legs of the other configurations as CHILD processes of the default run, after its timed region: each is this
-    script with --steps 4 --reps 3 --no-cpu --no-also and prints its own line, of which the summary goes into `also`."""
+    """Short legs of the other configurations as CHILD processes of the --full run, after its timed region: each is this
+    script with --full --steps 4 --reps 3 --no-cpu --no-also and prints its own line, of which the summary goes into `also`."""
     out = {}
     for name, what, extra in ALSO_LEGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--steps", "4", "--warmup", "1", "--reps", "3", "--no-cpu", "--no-also", "--no-api-path"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--steps", "4", "--warmup", "1", "--reps", "3", "--no-cpu", "--no-also",
+               "--no-api-path"] + extra
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=float(os.environ.get("HFX_BENCH_ALSO_TIMEOUT", "90")))
@@ -395,13 +422,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed region; the median is reported")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed region, the median is reported (default 1, "
+                    "5 with --full)")
     ap.add_argument("--cells", "--n", dest="n", type=int, default=32, help="cells per direction per GPU")
     ap.add_argument("--order", type=int, default=4)
     ap.add_argument("--mode", default="auto", choices=["auto", "split", "split3", "methods", "dense", "general"])
     ap.add_argument("--workload", default="tgv", choices=["tgv", "tets", "prisms", "mixed"],
                     help="tgv: BASELINE.json configs[1] (default); tets / prisms / mixed: configs[3]'s element classes, see general_workload")
     ap.add_argument("--tiles", type=int, default=2048, help="copies of the fixture mesh (workloads tets / prisms / mixed)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the roofline of the dominant kernel, the mirrored "
+                    "API path, the partitioned stage's phases, the CPU baselines and the short legs of the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state the timed path left after its last step "
+                    "as DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     # BASELINE.json configs[4]'s ingredients on the same mesh (not the default workload): polynomial de-aliasing of the
     # inviscid flux and shock capturing after every stage
@@ -413,10 +445,12 @@ def main():
                     help="hfx_ctx_set_option knob for A/B runs (split_grid_per_cu, xcd_order, dictionary_rows, flux_waves, "
                          "buffer_addressing, loader_wave, flux_stamps, tensor_ops); echoed into config.options")
     ap.add_argument("--no-api-path", action="store_true", help="skip the timing of the mirrored CalcResidual + AdvanceSolution loop")
-    ap.add_argument("--no-also", action="store_true", help="skip the short legs of the other workloads (the `also` block of the default run)")
+    ap.add_argument("--no-also", action="store_true", help="skip the short legs of the other workloads (the `also` block of the --full run)")
     ap.add_argument("--self-partition", action="store_true", help="N=1 only: the box's wrap-around faces become partition faces "
                     "to the rank itself, i.e. the partitioned stage with its RCCL exchanges priced on one GPU")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
 
     if args.workload != "tgv":
         if args.gpus != 1:
@@ -599,6 +633,10 @@ def main():
     bad = C.c_long(0)
     hfx.check(lib.hfx_eles_check_nan(e, C.byref(bad)))
     assert bad.value == -1, "NaN in the residual at flat index %d" % bad.value
+    if args.dump_outputs and rank == 0:
+        u = np.zeros((case.n_upts, case.n_eles, case.n_fields), order="F")
+        hfx.check(lib.hfx_eles_download(e, C.c_int(hfx.DISU_UPTS0), u.ctypes.data_as(C.POINTER(C.c_double))))
+        dump_outputs(args.dump_outputs, {"disu_upts": u})
 
     n_stages = case.n_stages
     dof_per_rank = case.n_eles * case.n_upts * case.n_fields
@@ -611,12 +649,6 @@ def main():
     rccl_info = None
     part_roof = None
     if partitioned and fused and transport == "rccl":
-        # per-phase and per-exchange times of the partitioned stage (HIP events on the compute / communication streams) in
-        # its SERIALISED schedule (every kernel on the compute stream so that the events bracket the phases; the timed run
-        # above puts the one-sided partition-face kernels on the communication stream); collective: every rank runs it,
-        # rank 0 reports its own
-        phases = case.time_partitioned(10)
-        phases["schedule"] = "serialised (all kernels on the compute stream); `value` is timed on the overlapped schedule"
         # what RCCL itself reports for every rank's communicator: N ranks on N different devices
         mine = case.comm_info()
         if dist is not None:
@@ -626,6 +658,13 @@ def main():
             allinfo = [mine]
         rccl_info = {"rccl_nranks": mine["nranks"], "ranks": allinfo,
                      "distinct_devices": len({i["pci_bus_id"] for i in allinfo})}
+    if partitioned and fused and transport == "rccl" and args.full:
+        # per-phase and per-exchange times of the partitioned stage (HIP events on the compute / communication streams) in
+        # its SERIALISED schedule (every kernel on the compute stream so that the events bracket the phases; the timed run
+        # above puts the one-sided partition-face kernels on the communication stream); collective: every rank runs it,
+        # rank 0 reports its own
+        phases = case.time_partitioned(10)
+        phases["schedule"] = "serialised (all kernels on the compute stream); `value` is timed on the overlapped schedule"
         if rank == 0 and phases.get("flux_kernel", 0.0) > 0.0:
             share = (C.c_double * 8)()
             hfx.check(lib.hfx_fused_kernel_bytes(e, share))
@@ -638,7 +677,7 @@ def main():
     # the seventeen method calls of src/solver.cpp:59-221 + src/HiFiLES.cpp:201-217 one by one through the C ABI), timed with
     # libhfx deferring them (whole stages run as the fused stage) and with every call launching its own kernels
     api_path = None
-    if not partitioned and fused and not args.no_api_path:
+    if args.full and not partitioned and fused and not args.no_api_path:
         api_path = {}
         for label, on, nsteps in (("deferred", True, args.steps), ("per_method", False, max(2, args.steps // 4))):
             case.set_deferred(on)
@@ -656,7 +695,7 @@ def main():
 
     roof = None
     cpu = None
-    if rank == 0 and not partitioned:
+    if args.full and rank == 0 and not partitioned:
         # ---- roofline of the dominant kernel, timed live with HIP events on the library's stream
         if fused:
             kt = (C.c_double * 8)()
@@ -731,8 +770,8 @@ def main():
                            sample=port_note, value_1core=cb["1core"]["value"])
 
     also = None
-    if (rank == 0 and world == 1 and not args.no_also and not partitioned and not extra and args.n == 32 and args.order == 4
-            and args.mode == "auto" and not args.opt):
+    if (args.full and rank == 0 and world == 1 and not args.no_also and not partitioned and not extra and args.n == 32
+            and args.order == 4 and args.mode == "auto" and not args.opt):
         also = also_legs(args)
 
     if rank == 0:

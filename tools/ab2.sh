@@ -5,8 +5,8 @@ line() { python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$1', 'stage %.4f ms' % d['ms_per_rk_stage'], {k: round(v, 4) for k, v in d['roofline']['kernels_ms'].items()})"; }
 for rep in 1 2; do
-  python bench.py --steps 20 --warmup 3 --no-cpu "$@" 2>/dev/null | line base
+  python bench.py --full --steps 20 --warmup 3 --no-cpu "$@" 2>/dev/null | line base
   for v in $dirs; do
-    HFX_LIB_DIR=$PWD/hifiles-solver_amd/$v python bench.py --steps 20 --warmup 3 --no-cpu "$@" 2>/dev/null | line $v
+    HFX_LIB_DIR=$PWD/hifiles-solver_amd/$v python bench.py --full --steps 20 --warmup 3 --no-cpu "$@" 2>/dev/null | line $v
   done
 done
