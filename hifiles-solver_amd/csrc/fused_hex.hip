@@ -15,7 +15,8 @@
 // Operator rows of the element kernels are either sum-factorised (1-D matrices through scalar registers, when the
 // registered operators are bit-exactly tensor products) or DICTIONARY-COMPRESSED sparse rows: a tensor-product
 // operator has only a handful of distinct values, so a row entry is 16 bits (value id, column), two per 32-bit
-// register, the values in a 2 kB LDS table.  The arithmetic is unchanged: the same non-zeros, multiplied in the same
+// register, the values in a 2 kB LDS table.  Hexes from P6 on have columns beyond 8 bits: their entries are 32 bits
+// (value id << 16 | column), one per register (Geo::WIDE); only variant 2 runs them (split_route).  The arithmetic is unchanged: the same non-zeros, multiplied in the same
 // ascending-column order as the reference dgemm (src/funcs.cpp:110-117).
 #include <vector>
 #include "fused_hex.hpp"
@@ -61,6 +62,17 @@ static int tensor_n(const hfx_eles *e)
   return 0;
 }
 
+// runtime form of split3_fits
+static bool split3_fits_rt(int nd, int N)
+{
+#define HFX_S3F(ND_, N_) \
+  if (nd == ND_ && N == N_) return split3_fits<ND_, N_>();
+  HFX_S3F(3, 2) HFX_S3F(3, 3) HFX_S3F(3, 4) HFX_S3F(3, 5) HFX_S3F(3, 6) HFX_S3F(3, 7) HFX_S3F(3, 8)
+  HFX_S3F(2, 2) HFX_S3F(2, 3) HFX_S3F(2, 4) HFX_S3F(2, 5) HFX_S3F(2, 6) HFX_S3F(2, 7) HFX_S3F(2, 8)
+#undef HFX_S3F
+  return false;
+}
+
 struct Dict
 {
   std::vector<double> vals;
@@ -74,17 +86,21 @@ struct Dict
   }
 };
 
-// pack `w` entries per row of an operator given in host ELL form (width hw) at word offset `off`
-static void pack_rows(std::vector<unsigned> &pk, size_t off, int m, int w, const double *hv, const int *hi, int hw, Dict &dict)
+// pack `w` entries per row of an operator given in host ELL form (width hw) at word offset `off`: `epw` = 2 entries of
+// 16 bits (value id << 8 | column) per word, or 1 wide entry (value id << 16 | column)
+static int pack_rows(std::vector<unsigned> &pk, size_t off, int m, int w, const double *hv, const int *hi, int hw, Dict &dict, int epw)
 {
+  const int cbits = epw == 2 ? 8 : 16;
   for (int r = 0; r < m; r++)
     for (int q = 0; q < w; q++)
     {
       const double v = (q < hw) ? hv[r + (size_t)m * q] : 0.0;
       const int c = (q < hw) ? hi[r + (size_t)m * q] : hi[r];
-      const unsigned ent = ((unsigned)dict.id(v) << 8) | (unsigned)c;
-      pk[off + (size_t)(q >> 1) * m + r] |= ent << (16 * (q & 1));
+      HFX_CHECK(c >= 0 && c < (1 << cbits), "fused path: column %d does not fit a %d-bit row entry", c, cbits);
+      const unsigned ent = ((unsigned)dict.id(v) << cbits) | (unsigned)c;
+      pk[off + (size_t)(q / epw) * m + r] |= ent << (16 * (q % epw));
     }
+  return 0;
 }
 
 static int upload(void **dst, const void *src, size_t bytes)
@@ -98,16 +114,16 @@ template <int ND, int N>
 static int build_packed(hfx_eles *e, FusedData *F, const std::vector<double> &o1v, const std::vector<int> &o1i)
 {
   using G = Geo<ND, N>;
-  constexpr int NU = G::NU, NFP = G::NFP, WN = G::WN;
+  constexpr int NU = G::NU, NFP = G::NFP, WN = G::WN, EPW = G::EPW;
   auto hw = [](const Operator &op) { return std::max(op.nnz_max, 1); };
   {
     Dict dict;
     std::vector<unsigned> pk(G::R_END, 0u);
     for (int d = 0; d < ND; d++)
-      pack_rows(pk, G::R_O2 + (size_t)d * WN * NU, NU, N, e->opp_2[d].h_val.data(), e->opp_2[d].h_idx.data(), hw(e->opp_2[d]), dict);
-    pack_rows(pk, G::R_O3, NU, 2 * ND, e->opp_3.h_val.data(), e->opp_3.h_idx.data(), hw(e->opp_3), dict);
-    pack_rows(pk, G::R_O0, NFP, N, e->opp_0.h_val.data(), e->opp_0.h_idx.data(), hw(e->opp_0), dict);
-    pack_rows(pk, G::R_O1, NFP, N, o1v.data(), o1i.data(), N, dict);
+      if (pack_rows(pk, G::R_O2 + (size_t)d * WN * NU, NU, N, e->opp_2[d].h_val.data(), e->opp_2[d].h_idx.data(), hw(e->opp_2[d]), dict, EPW)) return 1;
+    if (pack_rows(pk, G::R_O3, NU, 2 * ND, e->opp_3.h_val.data(), e->opp_3.h_idx.data(), hw(e->opp_3), dict, EPW)) return 1;
+    if (pack_rows(pk, G::R_O0, NFP, N, e->opp_0.h_val.data(), e->opp_0.h_idx.data(), hw(e->opp_0), dict, EPW)) return 1;
+    if (pack_rows(pk, G::R_O1, NFP, N, o1v.data(), o1i.data(), N, dict, EPW)) return 1;
     HFX_CHECK(dict.vals.size() <= MAX_TAB, "fused path: operators hold %zu distinct values (> %d)", dict.vals.size(), MAX_TAB);
     dict.vals.resize(MAX_TAB, 0.0);
     if (upload((void **)&F->pk_r, pk.data(), sizeof(unsigned) * pk.size())) return 1;
@@ -119,11 +135,11 @@ static int build_packed(hfx_eles *e, FusedData *F, const std::vector<double> &o1
     std::vector<unsigned> pk(G::G_END, 0u);
     for (int d = 0; d < ND; d++)
     {
-      pack_rows(pk, G::G_O4 + (size_t)d * WN * NU, NU, N, e->opp_4[d].h_val.data(), e->opp_4[d].h_idx.data(), hw(e->opp_4[d]), dict);
-      pack_rows(pk, G::G_O5 + (size_t)d * NU, NU, 2, e->opp_5[d].h_val.data(), e->opp_5[d].h_idx.data(), hw(e->opp_5[d]), dict);
+      if (pack_rows(pk, G::G_O4 + (size_t)d * WN * NU, NU, N, e->opp_4[d].h_val.data(), e->opp_4[d].h_idx.data(), hw(e->opp_4[d]), dict, EPW)) return 1;
+      if (pack_rows(pk, G::G_O5 + (size_t)d * G::W2 * NU, NU, 2, e->opp_5[d].h_val.data(), e->opp_5[d].h_idx.data(), hw(e->opp_5[d]), dict, EPW)) return 1;
     }
-    pack_rows(pk, G::G_O0, NFP, N, e->opp_0.h_val.data(), e->opp_0.h_idx.data(), hw(e->opp_0), dict);
-    pack_rows(pk, G::G_O6, NFP, N, e->opp_6.h_val.data(), e->opp_6.h_idx.data(), hw(e->opp_6), dict);
+    if (pack_rows(pk, G::G_O0, NFP, N, e->opp_0.h_val.data(), e->opp_0.h_idx.data(), hw(e->opp_0), dict, EPW)) return 1;
+    if (pack_rows(pk, G::G_O6, NFP, N, e->opp_6.h_val.data(), e->opp_6.h_idx.data(), hw(e->opp_6), dict, EPW)) return 1;
     HFX_CHECK(dict.vals.size() <= MAX_TAB, "fused path: operators hold %zu distinct values (> %d)", dict.vals.size(), MAX_TAB);
     dict.vals.resize(MAX_TAB, 0.0);
     if (upload((void **)&F->pk_g, pk.data(), sizeof(unsigned) * pk.size())) return 1;
@@ -143,6 +159,8 @@ static int dispatch_build_packed(hfx_eles *e, FusedData *F, int N, const std::ve
     case 4: return build_packed<3, 4>(e, F, o1v, o1i);
     case 5: return build_packed<3, 5>(e, F, o1v, o1i);
     case 6: return build_packed<3, 6>(e, F, o1v, o1i);
+    case 7: return build_packed<3, 7>(e, F, o1v, o1i);
+    case 8: return build_packed<3, 8>(e, F, o1v, o1i);
     }
   }
   else
@@ -373,7 +391,7 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
 {
   HFX_CHECK(e->ele_type == 4 || e->ele_type == 1, "fused path: tensor-product elements only (hexes, quads)");
   const int N = tensor_n(e);
-  HFX_CHECK(N >= 2 && N <= (e->n_dims == 2 ? 8 : 6), "fused path: built for orders 1..5 (quads: 1..7) (n_upts %d, n_fpts %d)", e->n_upts, e->n_fpts);
+  HFX_CHECK(N >= 2 && N <= 8, "fused path: built for orders 1..7 (n_upts %d, n_fpts %d)", e->n_upts, e->n_fpts);
   const int nd = e->n_dims, nfp = e->n_fpts;
   // the registered operators must have the collocated tensor-product sparsity the kernels are sized for
   HFX_CHECK(e->opp_0.nnz_max <= N && e->opp_3.nnz_max <= 2 * nd, "fused path: opp_0 / opp_3 are not tensor-product sparse");
@@ -385,7 +403,8 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
   }
   if (e->viscous_ops) HFX_CHECK(e->opp_6.nnz_max <= N, "fused path: opp_6 is not tensor-product sparse");
   HFX_CHECK(!e->ctx->params.viscous || e->viscous_ops, "fused path: viscous run but the block has no opp_4/5/6");
-  HFX_CHECK(e->n_upts <= 256 && e->n_fpts <= 256, "fused path: column indices must fit 8 bits");
+  // (the packed row entries: 8-bit columns up to 256 points per element, 16-bit ones above -- Geo::WIDE, checked in pack_rows)
+  HFX_CHECK(e->n_upts < 65536 && e->n_fpts < 65536, "fused path: column indices must fit 16 bits");
 
   if (!e->fused) e->fused = new FusedData();
   FusedData *F = e->fused;
@@ -421,7 +440,9 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
     }
     if (upload((void **)&F->o1m_dim, md.data(), sizeof(int) * md.size())) return 1;
     if (dispatch_build_packed(e, F, N, mv, mi)) return 1;
-    if (tensor_build(e, F, N, mv, mi, md)) return 1;
+    // (the sum-factorised tables serve variant 3 only: not built for the sizes it does not fit)
+    F->tensor_ok = false;
+    if (split3_fits_rt(nd, N) && tensor_build(e, F, N, mv, mi, md)) return 1;
   }
 
   const long plane_f = (long)e->n_fpts * e->n_eles;
@@ -598,6 +619,16 @@ bool les_in_flux_kernel(const hfx_eles *e)
   return plane_most * e->n_fields * e->n_dims * 8.0 < 4294967296.0;
 }
 
+// The variant a block runs when `variant` is asked for: variant 3 falls back to 2 where its kernels do not fit the element
+// size (split3_fits: hexes from P6 on) and where an LES closure cannot be evaluated in its flux kernel (les_in_flux_kernel).
+// (the LES part needs the block's fused tables: fused_build first)
+static int split_route(const hfx_eles *e, int variant)
+{
+  if (variant != 3) return variant;
+  if (!split3_fits_rt(e->n_dims, tensor_n(e))) return 2;
+  return (e->les_ready && !les_in_flux_kernel(e)) ? 2 : 3;
+}
+
 template <int ND, int N>
 static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, SplitEleArgs &ea, int which, int variant)
 {
@@ -610,6 +641,9 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
   const int per_cu = opt.split_grid_per_cu;
   const int flux_per_cu = opt.flux_grid_per_cu > 0 ? opt.flux_grid_per_cu : per_cu;
   constexpr int TB = SGeo<ND, N>::TB;
+  // variant 3's element kernels exist for the sizes they fit only (split3_fits); split_route sends the others to variant 2
+  constexpr bool V3 = split3_fits<ND, N>();
+  HFX_CHECK(V3 || variant == 2, "split variant 3 does not fit %d-D elements with %d points per direction: run variant 2", ND, N);
   auto face_args = [&](hfx_inters *f) {
     SplitFaceArgs a{};
     a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
@@ -700,112 +734,115 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
   // (variant 2 with an LES closure) alone, 8 = part 2 without them
   if (variant == 3)
   {
-    // Over-integration (src/solver.cpp:82-91).  With the loader-wave flux kernel the sum-factorised kernel hands over
-    // sum_l Dc[l] tdisf_l -- the de-aliased flux's whole contribution to (div_tdisf - opp_3 norm_tdisf), n_fields values per
-    // solution point (tensor_ops.hip) -- which that kernel adds to its divergence; otherwise tdisf_upts itself.
-    const bool lw_form = loader_wave_fits<ND, N>() && opt.loader_wave && opt.flux_waves == 2 && opt.buffer_addressing &&
-                         F->tensor_ok && !opt.dictionary_rows;
-    const bool oi_fold = e->over_int_ready && lw_form && oi_fold_ok;
-    auto run_over_int = [&]() -> int {
-      if (!oi_fold) return hfx_eles_evaluate_invFlux_over_int(e);
-      if (!tensor_over_int_folded(e))
-      {
-        // Dc[d] = D - c3[d][0] (L1 Lf)[d][0]^T - c3[d][1] (L1 Lf)[d][1]^T, as the flux kernel's prologue forms it (split3_kernels.hpp)
-        using T = TGeo<ND, N>;
-        const std::vector<double> &c = F->h_coef;
-        std::vector<double> Dc((size_t)ND * N * N);
-        for (int d = 0; d < ND; d++)
-          for (int mp = 0; mp < N; mp++)
-            for (int m = 0; m < N; m++)
-            {
-              const double ta = c[T::C_3 + (d * 2 + 0) * N + mp] * (c[T::C_L1 + (d * 2 + 0) * N] * c[T::C_LF + (d * 2 + 0) * N + m]);
-              const double tb = c[T::C_3 + (d * 2 + 1) * N + mp] * (c[T::C_L1 + (d * 2 + 1) * N] * c[T::C_LF + (d * 2 + 1) * N + m]);
-              Dc[((size_t)d * N + mp) * N + m] = c[T::C_D + mp * N + m] - ta - tb;
-            }
-        if (tensor_over_int_set_fold(e, Dc.data())) return 1;
-      }
-      return tensor_over_int_launch(e, true);
-    };
-    if (which == 5 && e->over_int_ready && run_over_int()) return 1;
-    // 21 / 22 / 23: the flux kernel on a part of the elements (partitioned blocks, hfx_run_steps_partitioned): the first half of
-    // the elements without partition-face points, those with, the second half -- the solution exchange runs beside the
-    // first launch, the exchange of the projected fluxes beside the third
-    const bool flux_part = which >= 21 && which <= 23;
-    e2.ele_list = nullptr;
-    e2.n_list = 0;
-    if (which == 21) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i1; }
-    if (which == 22) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
-    if (which == 23) { e2.ele_list = F->upd_list_i ? F->upd_list_i + F->n_list_i1 : nullptr; e2.n_list = F->n_list_i - F->n_list_i1; }
-    if (flux_part && e2.n_list == 0) return 0;
-    HFX_CHECK(!flux_part || (e2.ele_list != nullptr && !e->over_int_ready), "split flux kernel on element lists: no lists, or over-integration (which runs on all elements first)");
-    if (which == 0 || which == 2 || which == 7 || flux_part)
+    if constexpr (V3)
     {
-      e2.tdisf_in = nullptr;
-      if (e->over_int_ready)
+      // Over-integration (src/solver.cpp:82-91).  With the loader-wave flux kernel the sum-factorised kernel hands over
+      // sum_l Dc[l] tdisf_l -- the de-aliased flux's whole contribution to (div_tdisf - opp_3 norm_tdisf), n_fields values per
+      // solution point (tensor_ops.hip) -- which that kernel adds to its divergence; otherwise tdisf_upts itself.
+      const bool lw_form = loader_wave_fits<ND, N>() && opt.loader_wave && opt.flux_waves == 2 && opt.buffer_addressing &&
+                           F->tensor_ok && !opt.dictionary_rows;
+      const bool oi_fold = e->over_int_ready && lw_form && oi_fold_ok;
+      auto run_over_int = [&]() -> int {
+        if (!oi_fold) return hfx_eles_evaluate_invFlux_over_int(e);
+        if (!tensor_over_int_folded(e))
+        {
+          // Dc[d] = D - c3[d][0] (L1 Lf)[d][0]^T - c3[d][1] (L1 Lf)[d][1]^T, as the flux kernel's prologue forms it (split3_kernels.hpp)
+          using T = TGeo<ND, N>;
+          const std::vector<double> &c = F->h_coef;
+          std::vector<double> Dc((size_t)ND * N * N);
+          for (int d = 0; d < ND; d++)
+            for (int mp = 0; mp < N; mp++)
+              for (int m = 0; m < N; m++)
+              {
+                const double ta = c[T::C_3 + (d * 2 + 0) * N + mp] * (c[T::C_L1 + (d * 2 + 0) * N] * c[T::C_LF + (d * 2 + 0) * N + m]);
+                const double tb = c[T::C_3 + (d * 2 + 1) * N + mp] * (c[T::C_L1 + (d * 2 + 1) * N] * c[T::C_LF + (d * 2 + 1) * N + m]);
+                Dc[((size_t)d * N + mp) * N + m] = c[T::C_D + mp * N + m] - ta - tb;
+              }
+          if (tensor_over_int_set_fold(e, Dc.data())) return 1;
+        }
+        return tensor_over_int_launch(e, true);
+      };
+      if (which == 5 && e->over_int_ready && run_over_int()) return 1;
+      // 21 / 22 / 23: the flux kernel on a part of the elements (partitioned blocks, hfx_run_steps_partitioned): the first half of
+      // the elements without partition-face points, those with, the second half -- the solution exchange runs beside the
+      // first launch, the exchange of the projected fluxes beside the third
+      const bool flux_part = which >= 21 && which <= 23;
+      e2.ele_list = nullptr;
+      e2.n_list = 0;
+      if (which == 21) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i1; }
+      if (which == 22) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
+      if (which == 23) { e2.ele_list = F->upd_list_i ? F->upd_list_i + F->n_list_i1 : nullptr; e2.n_list = F->n_list_i - F->n_list_i1; }
+      if (flux_part && e2.n_list == 0) return 0;
+      HFX_CHECK(!flux_part || (e2.ele_list != nullptr && !e->over_int_ready), "split flux kernel on element lists: no lists, or over-integration (which runs on all elements first)");
+      if (which == 0 || which == 2 || which == 7 || flux_part)
       {
-        // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
-        if (which != 7 && run_over_int()) return 1;
-        e2.tdisf_in = e->arr[HFX_TDISF_UPTS];
-      }
-      const bool dict_only = opt.dictionary_rows != 0;
-      const int waves = opt.flux_waves;
-      // buffer-descriptor addressing needs 32-bit byte offsets into the largest array the kernel touches
-      const bool nobuf = !opt.buffer_addressing;
-      // (the largest array the launch really touches: the metric tensors at the flux points, and the n_fields * n_dims
-      // component arrays only when they are in use -- gradients at boundary points, the de-aliased flux)
-      // -- over BOTH point sets: quads with N >= 5 have more solution points than flux points
-      const double plane_most = (double)std::max<long>(plane_f, (long)e->n_upts * e->n_eles);
-      double most = plane_most * std::max(e->n_dims * e->n_dims, e->n_fields);
-      if (e2.grad_fpts || e2.grad_upts) most = std::max(most, plane_most * e->n_fields * e->n_dims);
-      if (e->over_int_ready) most = std::max(most, (double)e->n_upts * e->n_eles * e->n_fields * e->n_dims);
-      const bool buf = !nobuf && most * 8.0 < 4294967296.0;
-      const bool oi = e2.tdisf_in != nullptr;
-#define HFX_FLUX_LAUNCH(WV_, BUF_, OI_, LW_)                                                                                  \
-  hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, LW_>),                                                  \
-                     dim3(element_grid<split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, LW_>>(e, TB, per_cu)), dim3(TB), 0, st, \
-                     e2, F->t_coef, F->t_idx)
-      const bool no_lw = !opt.loader_wave;
-      constexpr bool lw_fits = loader_wave_fits<ND, N>();
-      // (a block whose de-aliased flux arrives whole -- dense over-integration -- takes the form without the loader wave)
-      const bool lw = lw_fits && buf && !no_lw && waves == 2 && (!oi || oi_fold);
-      HFX_CHECK(!oi_fold || (lw && F->tensor_ok && !dict_only), "over-integration: the folded form needs the loader-wave flux kernel");
-      bool launched = false;
-      // a closure with an SGS flux (every model but the spectral vanishing viscosity, which only filters the state)
-      const bool les = e->les_ready && e->les.sgs_model != 3;
-      HFX_CHECK(!les || (lw && F->tensor_ok && !dict_only && !oi && P.viscous),
-                "split variant 3 with an LES closure needs the loader-wave flux kernel (les_in_flux_kernel): run variant 2");
-      if (F->tensor_ok && !dict_only && lw)
-      {
-        const bool ga = e2.nbr != nullptr && P.viscous; // (the corrections formed in the kernel)
-        if (les && ga)
-          LoaderWaveLaunch<ND, N, false, true, true, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-        else if (les)
-          LoaderWaveLaunch<ND, N, false, false, true, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-        else if (oi && ga)
-          LoaderWaveLaunch<ND, N, true, true, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-        else if (oi)
-          LoaderWaveLaunch<ND, N, true, false, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-        else if (ga)
-          LoaderWaveLaunch<ND, N, false, true, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+        e2.tdisf_in = nullptr;
+        if (e->over_int_ready)
+        {
+          // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
+          if (which != 7 && run_over_int()) return 1;
+          e2.tdisf_in = e->arr[HFX_TDISF_UPTS];
+        }
+        const bool dict_only = opt.dictionary_rows != 0;
+        const int waves = opt.flux_waves;
+        // buffer-descriptor addressing needs 32-bit byte offsets into the largest array the kernel touches
+        const bool nobuf = !opt.buffer_addressing;
+        // (the largest array the launch really touches: the metric tensors at the flux points, and the n_fields * n_dims
+        // component arrays only when they are in use -- gradients at boundary points, the de-aliased flux)
+        // -- over BOTH point sets: quads with N >= 5 have more solution points than flux points
+        const double plane_most = (double)std::max<long>(plane_f, (long)e->n_upts * e->n_eles);
+        double most = plane_most * std::max(e->n_dims * e->n_dims, e->n_fields);
+        if (e2.grad_fpts || e2.grad_upts) most = std::max(most, plane_most * e->n_fields * e->n_dims);
+        if (e->over_int_ready) most = std::max(most, (double)e->n_upts * e->n_eles * e->n_fields * e->n_dims);
+        const bool buf = !nobuf && most * 8.0 < 4294967296.0;
+        const bool oi = e2.tdisf_in != nullptr;
+  #define HFX_FLUX_LAUNCH(WV_, BUF_, OI_, LW_)                                                                                  \
+    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, LW_>),                                                  \
+                       dim3(element_grid<split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, LW_>>(e, TB, per_cu)), dim3(TB), 0, st, \
+                       e2, F->t_coef, F->t_idx)
+        const bool no_lw = !opt.loader_wave;
+        constexpr bool lw_fits = loader_wave_fits<ND, N>();
+        // (a block whose de-aliased flux arrives whole -- dense over-integration -- takes the form without the loader wave)
+        const bool lw = lw_fits && buf && !no_lw && waves == 2 && (!oi || oi_fold);
+        HFX_CHECK(!oi_fold || (lw && F->tensor_ok && !dict_only), "over-integration: the folded form needs the loader-wave flux kernel");
+        bool launched = false;
+        // a closure with an SGS flux (every model but the spectral vanishing viscosity, which only filters the state)
+        const bool les = e->les_ready && e->les.sgs_model != 3;
+        HFX_CHECK(!les || (lw && F->tensor_ok && !dict_only && !oi && P.viscous),
+                  "split variant 3 with an LES closure needs the loader-wave flux kernel (les_in_flux_kernel): run variant 2");
+        if (F->tensor_ok && !dict_only && lw)
+        {
+          const bool ga = e2.nbr != nullptr && P.viscous; // (the corrections formed in the kernel)
+          if (les && ga)
+            LoaderWaveLaunch<ND, N, false, true, true, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+          else if (les)
+            LoaderWaveLaunch<ND, N, false, false, true, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+          else if (oi && ga)
+            LoaderWaveLaunch<ND, N, true, true, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+          else if (oi)
+            LoaderWaveLaunch<ND, N, true, false, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+          else if (ga)
+            LoaderWaveLaunch<ND, N, false, true, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+          else
+            LoaderWaveLaunch<ND, N, false, false, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+          launched = true;
+        }
+        if (launched)
+          ;
+        else if (F->tensor_ok && !dict_only && oi && buf)
+          HFX_FLUX_LAUNCH(2, true, true, false);
+        else if (F->tensor_ok && !dict_only && oi)
+          HFX_FLUX_LAUNCH(2, false, true, false);
+        else if (F->tensor_ok && !dict_only && waves == 2 && buf)
+          HFX_FLUX_LAUNCH(2, true, false, false);
+        else if (F->tensor_ok && !dict_only && buf)
+          HFX_FLUX_LAUNCH(3, true, false, false);
+        else if (F->tensor_ok && !dict_only)
+          HFX_FLUX_LAUNCH(2, false, false, false);
+  #undef HFX_FLUX_LAUNCH
         else
-          LoaderWaveLaunch<ND, N, false, false, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-        launched = true;
+          hipLaunchKernelGGL((split_flux_kernel<ND, N>), dim3(element_grid<split_flux_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, e2);
       }
-      if (launched)
-        ;
-      else if (F->tensor_ok && !dict_only && oi && buf)
-        HFX_FLUX_LAUNCH(2, true, true, false);
-      else if (F->tensor_ok && !dict_only && oi)
-        HFX_FLUX_LAUNCH(2, false, true, false);
-      else if (F->tensor_ok && !dict_only && waves == 2 && buf)
-        HFX_FLUX_LAUNCH(2, true, false, false);
-      else if (F->tensor_ok && !dict_only && buf)
-        HFX_FLUX_LAUNCH(3, true, false, false);
-      else if (F->tensor_ok && !dict_only)
-        HFX_FLUX_LAUNCH(2, false, false, false);
-#undef HFX_FLUX_LAUNCH
-      else
-        hipLaunchKernelGGL((split_flux_kernel<ND, N>), dim3(element_grid<split_flux_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, e2);
     }
   }
   else if (P.viscous && (which == 0 || which == 2 || which == 6 || which == 8))
@@ -864,28 +901,31 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
   {
     if (variant == 3)
     {
-      // 41 / 42: the update on the elements with partition-face points / on the others (two launches: the first one's
-      // flux-point solution leaves for the neighbours while the second runs); 42 comes behind the buffer swap of 41
-      e2.ele_list = nullptr;
-      e2.n_list = 0;
-      if (which == 41) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
-      if (which == 42) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i; e2.disu_next = e->arr[HFX_DISU_FPTS]; }
-      HFX_CHECK(which < 41 || e2.ele_list != nullptr || e2.n_list == 0, "split update: no element lists (the block was not built as a partitioned one)");
-      // buffer-descriptor addressing needs 32-bit byte offsets
-      const bool nobuf = !opt.buffer_addressing;
-      const bool small = (double)std::max<long>(plane_f, (long)e->n_upts * e->n_eles) * e->n_fields * 8.0 < 4294967296.0;
-      const long n_work = which >= 41 ? e2.n_list : (long)e->n_eles;
-      if (n_work > 0)
+      if constexpr (V3)
       {
-        if (small && !nobuf)
+        // 41 / 42: the update on the elements with partition-face points / on the others (two launches: the first one's
+        // flux-point solution leaves for the neighbours while the second runs); 42 comes behind the buffer swap of 41
+        e2.ele_list = nullptr;
+        e2.n_list = 0;
+        if (which == 41) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
+        if (which == 42) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i; e2.disu_next = e->arr[HFX_DISU_FPTS]; }
+        HFX_CHECK(which < 41 || e2.ele_list != nullptr || e2.n_list == 0, "split update: no element lists (the block was not built as a partitioned one)");
+        // buffer-descriptor addressing needs 32-bit byte offsets
+        const bool nobuf = !opt.buffer_addressing;
+        const bool small = (double)std::max<long>(plane_f, (long)e->n_upts * e->n_eles) * e->n_fields * 8.0 < 4294967296.0;
+        const long n_work = which >= 41 ? e2.n_list : (long)e->n_eles;
+        if (n_work > 0)
         {
-          const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, true>>(e, TB, per_cu, 3));
-          hipLaunchKernelGGL((split_update_kernel<ND, N, true>), dim3(g), dim3(TB), 0, st, e2);
-        }
-        else
-        {
-          const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, false>>(e, TB, per_cu, 3));
-          hipLaunchKernelGGL((split_update_kernel<ND, N, false>), dim3(g), dim3(TB), 0, st, e2);
+          if (small && !nobuf)
+          {
+            const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, true>>(e, TB, per_cu, 3));
+            hipLaunchKernelGGL((split_update_kernel<ND, N, true>), dim3(g), dim3(TB), 0, st, e2);
+          }
+          else
+          {
+            const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, false>>(e, TB, per_cu, 3));
+            hipLaunchKernelGGL((split_update_kernel<ND, N, false>), dim3(g), dim3(TB), 0, st, e2);
+          }
         }
       }
     }
@@ -929,7 +969,7 @@ static int split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_st
   int rc = 1;
 #define HFX_SPLIT_CASE(ND_, N_) \
   if (e->n_dims == ND_ && N == N_) rc = launch_split_stage<ND_, N_>(e, faces, nfb, a, which, variant);
-  HFX_SPLIT_CASE(3, 2) HFX_SPLIT_CASE(3, 3) HFX_SPLIT_CASE(3, 4) HFX_SPLIT_CASE(3, 5) HFX_SPLIT_CASE(3, 6)
+  HFX_SPLIT_CASE(3, 2) HFX_SPLIT_CASE(3, 3) HFX_SPLIT_CASE(3, 4) HFX_SPLIT_CASE(3, 5) HFX_SPLIT_CASE(3, 6) HFX_SPLIT_CASE(3, 7) HFX_SPLIT_CASE(3, 8)
   HFX_SPLIT_CASE(2, 2) HFX_SPLIT_CASE(2, 3) HFX_SPLIT_CASE(2, 4) HFX_SPLIT_CASE(2, 5) HFX_SPLIT_CASE(2, 6) HFX_SPLIT_CASE(2, 7) HFX_SPLIT_CASE(2, 8)
 #undef HFX_SPLIT_CASE
   if (rc) return 1;
@@ -970,8 +1010,9 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
   if (!e->fused || !e->fused->built)
     if (fused_build(e, faces, nfb)) return 1;
   // an LES closure reads the corrected gradient: variant 3 evaluates it in the flux kernel where that kernel's loader-wave form
-  // runs (les_in_flux_kernel); otherwise such a block runs variant 2, which keeps the gradient in HBM for a pointwise kernel
-  if (e->les_ready && variant == 3 && !les_in_flux_kernel(e)) variant = 2;
+  // runs (les_in_flux_kernel); otherwise such a block runs variant 2, which keeps the gradient in HBM for a pointwise kernel.
+  // Element sizes that variant 3 does not fit run variant 2 as well (split_route)
+  variant = split_route(e, variant);
   HFX_CHECK(!e->over_int_ready || variant == 3, "the split variant that keeps the gradients (fused 2, which LES without the in-kernel closure selects) has no over-integration");
   if (n_steps <= 0) return 0;
   const int adv = e->ctx->params.adv_type;
@@ -1006,7 +1047,7 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
 {
   if (!e->fused || !e->fused->built)
     if (fused_build(e, faces, nfb)) return 1;
-  if (e->les_ready && variant == 3 && !les_in_flux_kernel(e)) variant = 2;
+  variant = split_route(e, variant);
   const int adv = e->ctx->params.adv_type;
   const int nst = (adv == 0) ? 1 : (adv <= 2) ? 4 : (adv == 3) ? 5 : 14;
   hipStream_t st = e->ctx->stream;
@@ -1080,7 +1121,7 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
 
 void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant)
 {
-  if (e->les_ready && variant == 3 && !les_in_flux_kernel(e)) variant = 2;
+  variant = split_route(e, variant);
   // ALGORITHMIC HBM bytes per launch (doubles listed per element)
   const double nu = e->n_upts, nfp = e->n_fpts, nf = e->n_fields, nd = e->n_dims, ne = e->n_eles;
   for (int i = 0; i < 8; i++) bytes[i] = 0.0;

@@ -15,8 +15,8 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
                        int variant = 2);
 // algorithmic HBM bytes per launch of each kernel, same order
 void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant = 2);
-// which split variant a partitioned block runs: 2 (the reference's gradient arrays kept) when the context asks for it or the
-// block has an LES closure, else 3
+// which split variant a partitioned block runs: 2 (the reference's gradient arrays kept) when the context asks for it, the
+// block has an LES closure that variant 3 cannot evaluate, or variant 3 does not fit its element size (hexes from P6 on), else 3
 int split_variant(const hfx_eles *e);
 // an LES closure evaluated inside the flux kernel of variant 3 (needs the block's fused tables)
 bool les_in_flux_kernel(const hfx_eles *e);

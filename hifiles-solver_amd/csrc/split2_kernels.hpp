@@ -152,6 +152,12 @@ struct SGeo
 {
   using G = Geo<ND, N>;
   static constexpr int TB = 64 * (G::WU > G::WF ? G::WU : G::WF); // thread t: solution point t and flux point t
+  // minimum waves per SIMD of the residual kernel (second __launch_bounds__ argument).  The sizes with wide row entries
+  // (hexes from P6 on) are bound by LDS, tab + su + st + sc: as many workgroups as fit a CU's 160 KiB (P6: two of six waves,
+  // three per SIMD; P7: one of eight waves, two per SIMD) -- hipcc could not meet a higher target
+  static constexpr int RES_LDS = 8 * (MAX_TAB + (1 + ND) * G::NF * G::NU + G::NF * G::NFP);
+  static constexpr int RES_WAVES =
+      G::WIDE ? cmax(1, (160 * 1024 / RES_LDS) * (TB / 64) / 4) : HFX_SPLIT_WAVES_RES;
 };
 
 // ---- u, delta -> corrected gradient at solution points (physical) and flux points (physical)
@@ -159,7 +165,8 @@ template <int ND, int N>
 __global__ __launch_bounds__((SGeo<ND, N>::TB)) void split_gradient_kernel(const SplitEleArgs a)
 {
   using G = Geo<ND, N>;
-  constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, WN = G::WN, TB = SGeo<ND, N>::TB;
+  constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, WN = G::WN, W2 = G::W2, TB = SGeo<ND, N>::TB;
+  constexpr bool WD = G::WIDE;
   constexpr int PW = G::G_WU + WN; // opp_4[d] | opp_5[d] | opp_6
   __shared__ double tab[MAX_TAB];
   __shared__ double su[NF][NU];
@@ -176,7 +183,8 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB)) void split_gradient_kernel(const
   {
 #pragma unroll
     for (int i = 0; i < WN; i++) pw[d * WN + i] = a.pk[G::G_O4 + (d * WN + i) * NU + tu];
-    pw[ND * WN + d] = a.pk[G::G_O5 + d * NU + tu];
+#pragma unroll
+    for (int i = 0; i < W2; i++) pw[ND * WN + d * W2 + i] = a.pk[G::G_O5 + (d * W2 + i) * NU + tu];
   }
 #pragma unroll
   for (int i = 0; i < WN; i++) pw[G::G_WU + i] = a.pk[G::G_O6 + i * NFP + tf];
@@ -209,12 +217,12 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB)) void split_gradient_kernel(const
       for (int k = 0; k < NF; k++)
       {
         double tg[ND], cg[ND];
-        tg[0] = row_dot<N, 0, PW>(pw, tab, &su[k][0], 0.0);
-        tg[1] = row_dot<N, WN, PW>(pw, tab, &su[k][0], 0.0);
-        if (ND == 3) tg[ND - 1] = row_dot<N, (ND - 1) * WN, PW>(pw, tab, &su[k][0], 0.0);
-        tg[0] = row_dot<2, ND * WN + 0, PW>(pw, tab, &sd[k][0], tg[0]);
-        tg[1] = row_dot<2, ND * WN + 1, PW>(pw, tab, &sd[k][0], tg[1]);
-        if (ND == 3) tg[ND - 1] = row_dot<2, ND * WN + ND - 1, PW>(pw, tab, &sd[k][0], tg[ND - 1]);
+        tg[0] = row_dot<N, 0, PW, WD>(pw, tab, &su[k][0], 0.0);
+        tg[1] = row_dot<N, WN, PW, WD>(pw, tab, &su[k][0], 0.0);
+        if (ND == 3) tg[ND - 1] = row_dot<N, (ND - 1) * WN, PW, WD>(pw, tab, &su[k][0], 0.0);
+        tg[0] = row_dot<2, ND * WN + 0 * W2, PW, WD>(pw, tab, &sd[k][0], tg[0]);
+        tg[1] = row_dot<2, ND * WN + 1 * W2, PW, WD>(pw, tab, &sd[k][0], tg[1]);
+        if (ND == 3) tg[ND - 1] = row_dot<2, ND * WN + (ND - 1) * W2, PW, WD>(pw, tab, &sd[k][0], tg[ND - 1]);
 #pragma unroll
         for (int d = 0; d < ND; d++) sg[k + NF * d][tu] = tg[d];
         to_physical<ND>(inv_detjac, JG, tg, cg);
@@ -237,7 +245,7 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB)) void split_gradient_kernel(const
       {
         double tg[ND], cg[ND];
 #pragma unroll
-        for (int d = 0; d < ND; d++) tg[d] = row_dot<N, G::G_WU, PW>(pw, tab, &sg[k + NF * d][0], 0.0);
+        for (int d = 0; d < ND; d++) tg[d] = row_dot<N, G::G_WU, PW, WD>(pw, tab, &sg[k + NF * d][0], 0.0);
         to_physical<ND>(inv_detjac, JG, tg, cg);
 #pragma unroll
         for (int d = 0; d < ND; d++) a.grad_fpts[o + (k + NF * d) * plane_f] = cg[d];
@@ -251,11 +259,12 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB)) void split_gradient_kernel(const
 // Loads are placed right before their use: several workgroups are resident per CU and cover each
 // other's latency, and short live ranges keep the register count (= the occupancy) in check.
 template <int ND, int N>
-__global__ __launch_bounds__((SGeo<ND, N>::TB), HFX_SPLIT_WAVES_RES) void split_residual_kernel(const SplitEleArgs a)
+__global__ __launch_bounds__((SGeo<ND, N>::TB), (SGeo<ND, N>::RES_WAVES)) void split_residual_kernel(const SplitEleArgs a)
 {
   using G = Geo<ND, N>;
   constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, WN = G::WN, TB = SGeo<ND, N>::TB;
   constexpr int N3 = 2 * ND, NG = NF * ND;
+  constexpr bool WD = G::WIDE;
   constexpr int PW = G::R_WU + G::R_WF; // opp_2[d] | opp_3 | opp_0 | merged opp_1
   __shared__ double tab[MAX_TAB];
   __shared__ double su[NF][NU];
@@ -271,7 +280,7 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB), HFX_SPLIT_WAVES_RES) void split_
 #pragma unroll
   for (int i = 0; i < ND * WN; i++) pw[i] = a.pk[G::R_O2 + i * NU + tu];
 #pragma unroll
-  for (int i = 0; i < words_of(N3); i++) pw[ND * WN + i] = a.pk[G::R_O3 + i * NU + tu];
+  for (int i = 0; i < G::W3; i++) pw[ND * WN + i] = a.pk[G::R_O3 + i * NU + tu];
 #pragma unroll
   for (int i = 0; i < WN; i++)
   {
@@ -336,9 +345,9 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB), HFX_SPLIT_WAVES_RES) void split_
 #pragma unroll
       for (int k = 0; k < NF; k++)
       {
-        double s = row_dot<N, 0, PW>(pw, tab, &st[k][0], 0.0);
-        s = row_dot<N, WN, PW>(pw, tab, &st[k + NF][0], s);
-        if (ND == 3) s = row_dot<N, (ND - 1) * WN, PW>(pw, tab, &st[k + NF * (ND - 1)][0], s);
+        double s = row_dot<N, 0, PW, WD>(pw, tab, &st[k][0], 0.0);
+        s = row_dot<N, WN, PW, WD>(pw, tab, &st[k + NF][0], s);
+        if (ND == 3) s = row_dot<N, (ND - 1) * WN, PW, WD>(pw, tab, &st[k + NF * (ND - 1)][0], s);
         div[k] = s;
       }
     }
@@ -347,7 +356,7 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB), HFX_SPLIT_WAVES_RES) void split_
 #pragma unroll
       for (int k = 0; k < NF; k++)
       {
-        const double ntd = row_dot<N, G::R_WU + WN, PW>(pw, tab, &st[k + NF * d1][0], 0.0);
+        const double ntd = row_dot<N, G::R_WU + WN, PW, WD>(pw, tab, &st[k + NF * d1][0], 0.0);
         sc[k][tf] = a.tconf[o + k * plane_f] + -1.0 * ntd; // norm_tconf -= norm_tdisf (src/eles.cpp:1746)
       }
     }
@@ -359,7 +368,7 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB), HFX_SPLIT_WAVES_RES) void split_
 #pragma unroll
       for (int k = 0; k < NF; k++)
       {
-        const double dv = row_dot<N3, ND * WN, PW>(pw, tab, &sc[k][0], div[k]);
+        const double dv = row_dot<N3, ND * WN, PW, WD>(pw, tab, &sc[k][0], div[k]);
         const long q = p + k * plane_u;
         if (dv != dv) atomicMin(a.nan_flag, (unsigned long long)q);
         if (a.write_div) a.div_out[q] = dv;
@@ -406,7 +415,7 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB), HFX_SPLIT_WAVES_RES) void split_
     if (is_f)
     {
 #pragma unroll
-      for (int k = 0; k < NF; k++) a.disu_next[o + k * plane_f] = row_dot<N, G::R_WU, PW>(pw, tab, &su[k][0], 0.0);
+      for (int k = 0; k < NF; k++) a.disu_next[o + k * plane_f] = row_dot<N, G::R_WU, PW, WD>(pw, tab, &su[k][0], 0.0);
     }
     __syncthreads();
   }

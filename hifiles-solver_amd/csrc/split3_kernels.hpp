@@ -433,18 +433,36 @@ __device__ __forceinline__ void dma16_region(const GArr<BUF> &g, lds_dp lds_dst,
     }
 }
 
+// LDS bytes of one workgroup of the loader-wave form: input slots + metric slot + work regions
+template <int ND, int N>
+constexpr long loader_wave_lds()
+{
+  using G = Geo<ND, N>;
+  constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, NQ = ND * ND, NG = NF * ND;
+  return 8L * (cmax(NF * (NU + NFP), NG * NU) + NG * NU + 2 * NF * (NU + 1 + NFP) + NQ * (NU + NFP) + NU + (1 + ND) * NFP + 16);
+}
+
 // does the loader-wave form fit this element size?  (vmcnt counts at most 63 DMA instructions in flight; two workgroups
 // of input slots + metric slot + work regions must fit the CU's 160 KiB of LDS)
 template <int ND, int N>
 constexpr bool loader_wave_fits()
 {
   using G = Geo<ND, N>;
-  constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, NQ = ND * ND, NG = NF * ND;
+  constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, NQ = ND * ND;
   constexpr int UJ = NF * (((NU + 1) / 2 + 63) / 64), DJ = NF * (((NFP + 1) / 2 + 63) / 64);
   constexpr int L_JGU = (NQ * NU + 1) / 2, L_DJU = (NU + 1) / 2, L_JGF = (NQ * NFP + 1) / 2, L_DJF = (NFP + 1) / 2;
   constexpr int N_M = (L_JGU + 63) / 64 + (L_DJU + 63) / 64 + (L_JGF + 63) / 64 + (1 + ND) * ((L_DJF + 63) / 64);
-  constexpr long lds = 8L * (cmax(NF * (NU + NFP), NG * NU) + NG * NU + 2 * NF * (NU + 1 + NFP) + NQ * (NU + NFP) + NU + (1 + ND) * NFP + 16);
-  return UJ + DJ <= 63 && N_M <= 63 && 2 * lds <= 160 * 1024;
+  return UJ + DJ <= 63 && N_M <= 63 && 2 * loader_wave_lds<ND, N>() <= 160 * 1024;
+}
+
+// Does variant 3 fit this element size at all?  Its flux kernel holds one element's state, LDG corrections, gradient,
+// metrics and fluxes in LDS: the working set of ONE loader-wave workgroup must fit the CU's 160 KiB, and the dictionary
+// rows must be the 16-bit ones.  Hexes from P6 on (191 kB, P7 276 kB) do not: they run variant 2 (split_route), and no
+// variant-3 kernel is instantiated for them (launch_split_stage).
+template <int ND, int N>
+constexpr bool split3_fits()
+{
+  return !Geo<ND, N>::WIDE && loader_wave_lds<ND, N>() <= 160 * 1024;
 }
 
 // LW: a LOADER WAVE (one extra wave per workgroup) brings the next element's state and LDG corrections straight into

@@ -42,7 +42,8 @@ struct FusedData
 };
 
 constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
-constexpr int words_of(int w) { return (w + 1) / 2; }
+// 32-bit words that hold `w` packed row entries, `epw` entries per word
+constexpr int words_of(int w, int epw = 2) { return (w + epw - 1) / epw; }
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 
 template <int ND, int N>
@@ -57,46 +58,57 @@ struct Geo
   static constexpr int TB = 64 * (WU + WF);       // gradient kernel: roles U, F
   static constexpr int TBR = 64 * (WU + 2 * WF);  // residual kernel: roles U, A, B
   static constexpr int UNP = (NF * NU + TU - 1) / TU; // doubles of the next element's state per upt thread
-  static constexpr int WN = words_of(N);
+  // A packed row entry is 16 bits (8-bit value id | 8-bit column), two per word, while every column fits 8 bits.  Hexes
+  // from P6 on (343 / 512 solution points) take WIDE entries: value id << 16 | 16-bit column, one per word.
+  static constexpr bool WIDE = NU > 256 || NFP > 256;
+  static constexpr int EPW = WIDE ? 1 : 2;       // entries per word
+  static constexpr int WN = words_of(N, EPW);     // words of an N-entry row
+  static constexpr int W2 = words_of(2, EPW);     // words of an opp_5 row
+  static constexpr int W3 = words_of(2 * ND, EPW); // words of an opp_3 row
   // packed-row layout, gradient kernel: opp_4[d] | opp_5[d] (rows = upts) | opp_0 | opp_6 (rows = fpts)
   static constexpr int G_O4 = 0;
   static constexpr int G_O5 = G_O4 + ND * WN * NU;
-  static constexpr int G_O0 = G_O5 + ND * words_of(2) * NU;
+  static constexpr int G_O0 = G_O5 + ND * W2 * NU;
   static constexpr int G_O6 = G_O0 + WN * NFP;
   static constexpr int G_END = G_O6 + WN * NFP;
-  static constexpr int G_WU = ND * WN + ND * words_of(2); // words per upt thread
+  static constexpr int G_WU = ND * WN + ND * W2; // words per upt thread
   static constexpr int G_WF = 2 * WN;                     // words per fpt thread
   // residual kernel: opp_2[d] | opp_3 (upts) | opp_0 | merged opp_1 (fpts)
   static constexpr int R_O2 = 0;
   static constexpr int R_O3 = R_O2 + ND * WN * NU;
-  static constexpr int R_O0 = R_O3 + words_of(2 * ND) * NU;
+  static constexpr int R_O0 = R_O3 + W3 * NU;
   static constexpr int R_O1 = R_O0 + WN * NFP;
   static constexpr int R_END = R_O1 + WN * NFP;
-  static constexpr int R_WU = ND * WN + words_of(2 * ND);
+  static constexpr int R_WU = ND * WN + W3;
   static constexpr int R_WF = 2 * WN;
 };
 
 // acc += sum_q tab[vid_q] * data[col_q], ascending q (= ascending column).  `w` is a
-// register array subscripted with compile-time constants only.
-template <int W, int OFF, int PW>
+// register array subscripted with compile-time constants only.  WIDE: one 32-bit entry per word (Geo::WIDE).
+template <int W, int OFF, int PW, bool WIDE = false>
 __device__ __forceinline__ double row_dot(const unsigned (&w)[PW], const double *tab, const double *data, double acc)
 {
 #pragma unroll
-  for (int i = 0; i < words_of(W); i++)
+  for (int i = 0; i < words_of(W, WIDE ? 1 : 2); i++)
   {
     // The unpacked (value id, column) pairs are loop invariant; left alone the compiler hoists
     // all of them out of the persistent loop and the ~12 packed registers turn back into ~100
     // address registers.  The empty asm makes the word opaque so that it is unpacked at the use.
     unsigned word = w[OFF + i];
     asm volatile("" : "+v"(word));
+    if constexpr (WIDE)
+      acc += tab[word >> 16] * data[word & 0xffffu];
+    else
     {
-      const unsigned ent = word & 0xffffu;
-      acc += tab[ent >> 8] * data[ent & 0xffu];
-    }
-    if (2 * i + 1 < W)
-    {
-      const unsigned ent = word >> 16;
-      acc += tab[ent >> 8] * data[ent & 0xffu];
+      {
+        const unsigned ent = word & 0xffffu;
+        acc += tab[ent >> 8] * data[ent & 0xffu];
+      }
+      if (2 * i + 1 < W)
+      {
+        const unsigned ent = word >> 16;
+        acc += tab[ent >> 8] * data[ent & 0xffu];
+      }
     }
   }
   return acc;

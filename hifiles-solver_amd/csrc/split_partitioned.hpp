@@ -52,7 +52,7 @@ static int mpi_launch(hfx_eles *e, hfx_inters *f, int what, const double *fn_ove
 // the one-sided partition-face kernels for a block of the general fused stage (three-dimensional; fn: that block's projected flux)
 int mpi_launch_general(hfx_eles *e, hfx_inters *f, int what, const double *fn) { return mpi_launch<3>(e, f, what, fn); }
 
-int split_variant(const hfx_eles *e) { return (e->ctx->fused_mode == 2 || (e->les_ready && !les_in_flux_kernel(e))) ? 2 : 3; }
+int split_variant(const hfx_eles *e) { return split_route(e, e->ctx->fused_mode == 2 ? 2 : 3); }
 
 int split_stage_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi,
                             int phase, int in_step, int first)

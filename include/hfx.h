@@ -112,7 +112,9 @@ int hfx_ctx_set_params(hfx_ctx *ctx, const hfx_params *p);
 int hfx_ctx_set_contract_mode(hfx_ctx *ctx, int mode);
 /* which variant of the split fused stage (pairwise face kernels + element kernels, three or four launches per stage) the
  * measurement entry points describe and hfx_stage_partitioned / hfx_run_steps_partitioned run: 2 keeps the reference's
- * gradient arrays in HBM, 3 (default) evaluates the fluxes in the gradient kernel */
+ * gradient arrays in HBM, 3 (default) evaluates the fluxes in the gradient kernel.  Hexahedra of orders 6 and 7 (343 / 512
+ * solution points) run variant 2 whichever is asked for: variant 3 does not fit one such element in LDS.  Variant 2 has no
+ * over-integration, so such a block with over-integration stays on the per-method path (deferred execution replays it). */
 int hfx_ctx_set_fused_mode(hfx_ctx *ctx, int mode);
 /* run_input.CFL for dt_type 1 / 2 (src/input.cpp:141-158): hfx_run_steps and hfx_run_steps_partitioned then start every
  * time step with calc_time_step (src/HiFiLES.cpp:198, src/solver.cpp:484-549) */
