@@ -155,13 +155,42 @@ static int start_exchange(hfx_comm *c, hfx_inters *const *mpi_faces, int n_mpi, 
     HFX_NCCL(g_rccl.GroupEnd());
   }
   HFX_HIP(hipEventRecord(c->received[kind], cs));
+  c->posted[kind] += n_mpi;
+  if (kind == 0) c->in_flight += n_mpi;
   return 0;
 }
 
-static int wait_exchange(hfx_comm *c, int kind)
+// the compute stream waits for the exchange of `kind`; n: the partition-face blocks whose messages that consumes
+static int wait_exchange(hfx_comm *c, int kind, int n)
 {
   HFX_HIP(hipStreamWaitEvent(c->ctx->stream, c->received[kind], 0));
+  c->waited[kind] += n;
+  if (kind == 0) c->in_flight = std::max(0, c->in_flight - n);
   return 0;
+}
+
+// is e's flux-point solution of the current state on its way over c already?
+static bool sent_over(const hfx_eles *e, const hfx_comm *c) { return e->fpts_sent && e->sent_on == c->serial; }
+
+// a partitioned fused stage left e's new flux-point solution on its way (fpts_sent) and the state changes before a stage
+// consumes it: the compute stream waits for that message, which is then dropped (a stage after this one packs and posts again)
+int invalidate_fpts(hfx_eles *e)
+{
+  for (hfx_comm *c : e->ctx->comms)
+    if (sent_over(e, c) && c->in_flight > 0 && wait_exchange(c, 0, e->sent_blocks)) return 1;
+  e->fpts_valid = e->fpts_sent = false;
+  e->sent_on = 0;
+  return 0;
+}
+
+// what a partitioned loop leaves behind: it drained the message it posted last, nothing of these blocks is on its way
+static void mark_drained(hfx_eles *const *eles, int n)
+{
+  for (int i = 0; i < n; i++)
+  {
+    eles[i]->fpts_sent = false;
+    eles[i]->sent_on = 0;
+  }
 }
 
 static int n_rk_stages(const hfx_params &p) { return (p.adv_type == 0) ? 1 : (p.adv_type <= 2) ? 4 : (p.adv_type == 3) ? 5 : 14; }
@@ -264,7 +293,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
     // fluxes then leave beside the other half (and the interior common-flux kernel)
     const bool split_flux = ctx->opt.split_flux && !e->over_int_ready && n_mpi > 0;
     if (split_flux && phase(13, rk, 0)) return 1;
-    HFX_HIP(hipStreamWaitEvent(st, comm->received[0], 0));
+    if (wait_exchange(comm, 0, n_mpi)) return 1;
     if (split_flux ? phase(14, rk, 0) : phase(6, rk, 0)) return 1; // gradient + flux kernel
     HFX_HIP(hipEventRecord(comm->packed[1], st));
     HFX_HIP(hipStreamWaitEvent(cs, comm->packed[1], 0));
@@ -277,7 +306,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
     HFX_HIP(hipEventRecord(comm->received[1], cs));
     if (split_flux && phase(15, rk, 0)) return 1;
     if (phase(3, rk, 0)) return 1; // interior common fluxes                                  | compute stream
-    HFX_HIP(hipStreamWaitEvent(st, comm->received[1], 0));
+    if (wait_exchange(comm, 1, n_mpi)) return 1;
     // the update: first the elements with partition-face points, whose new flux-point solution is packed and sent (communication
     // stream) while the others are updated -- the exchange the next stage's flux kernel waits for is hidden behind them
     const bool split_update = ctx->opt.split_update && !e->shock_ready && n_mpi > 0;
@@ -294,7 +323,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
   if (T) HFX_HIP(hipEventRecord(T->ph[0], st));
   if (phase(1, rk, 0)) return 1;
   if (T) HFX_HIP(hipEventRecord(T->ph[1], st));
-  if (wait_exchange(comm, 0)) return 1;
+  if (wait_exchange(comm, 0, n_mpi)) return 1;
   const bool pieces = T && projected && visc; // phase 2 in its three pieces, the element kernel bracketed on its own
   if (pieces)
   {
@@ -316,8 +345,8 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
   if (T) HFX_HIP(hipEventRecord(T->ph[2], st));
   if (phase(3, rk, 0)) return 1;
   if (T) HFX_HIP(hipEventRecord(T->ph[3], st));
-  if (visc && wait_exchange(comm, 1)) return 1;
-  if (visc && les && wait_exchange(comm, 2)) return 1;
+  if (visc && wait_exchange(comm, 1, n_mpi)) return 1;
+  if (visc && les && wait_exchange(comm, 2, n_mpi)) return 1;
   if (phase(4, rk, 0)) return 1;
   if (T) HFX_HIP(hipEventRecord(T->x0[0], st));
   if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1;
@@ -402,7 +431,7 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
     if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1;
   }
   if (part(1)) return 1;
-  if (wait_exchange(comm, 0)) return 1;
+  if (wait_exchange(comm, 0, n_mpi)) return 1;
   if (visc && mpi_all(1)) return 1;
   if (part(2)) return 1;
   if (visc)
@@ -411,7 +440,7 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
     if (start_exchange(comm, mpi_faces, n_mpi, 1, true)) return 1;
   }
   if (part(3)) return 1;
-  if (visc && wait_exchange(comm, 1)) return 1;
+  if (visc && wait_exchange(comm, 1, n_mpi)) return 1;
   if (mpi_all(6)) return 1;
   if (part(4)) return 1;
   // eles::shock_capture (src/HiFiLES.cpp:214-216) before the new flux-point solution is packed: the filter, then the flux-point
@@ -428,7 +457,9 @@ static int run_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int,
   hfx_ctx *ctx = e->ctx;
   if (check_partition_blocks(e, mpi_faces, n_mpi, comm)) return 1;
   const int nst = n_rk_stages(ctx->params);
-  bool first = true;
+  // a partitioned fused stage of the deferred path may have left this state's flux-point solution on its way already: the
+  // first stage takes it instead of posting it again (the messages a rank posts follow its calls, not what ran deferred)
+  bool first = !sent_over(e, comm);
   int done = 0;
   for (int s = 0; n_stages_total >= 0 ? done < n_stages_total : s < n_steps; s++)
   {
@@ -442,7 +473,9 @@ static int run_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int,
   }
   // the exchange started after the last stage belongs to a stage that is not run: the compute stream waits for it so
   // that nothing is in flight when the caller reads or changes the state (a following call starts over with `first`)
-  return wait_exchange(comm, 0);
+  if (wait_exchange(comm, 0, n_mpi)) return 1;
+  mark_drained(&e, 1);
+  return 0;
 }
 
 } // namespace hfx
@@ -470,6 +503,8 @@ int hfx_comm_create(hfx_ctx *ctx, const char id[HFX_COMM_ID_BYTES], int nranks, 
   HFX_HIP(hipSetDevice(ctx->device));
   hfx_comm *c = new hfx_comm();
   c->ctx = ctx;
+  static unsigned long n_created = 0;
+  c->serial = ++n_created;
   c->nranks = nranks;
   c->rank = rank;
   ncclUniqueId u;
@@ -501,6 +536,7 @@ int hfx_comm_create(hfx_ctx *ctx, const char id[HFX_COMM_ID_BYTES], int nranks, 
     set_error("%s", msg.c_str());
     return 1;
   }
+  ctx->comms.push_back(c);
   *out = c;
   return 0;
 }
@@ -513,6 +549,8 @@ int hfx_comm_destroy(hfx_comm *c)
     // what has been recorded may name this communicator: run it, then forget the plans that do
     (void)defer_flush(c->ctx, 0);
     c->ctx->defer.plans.clear();
+    auto &v = c->ctx->comms;
+    v.erase(std::remove(v.begin(), v.end(), c), v.end());
   }
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->nccl) (void)g_rccl.CommDestroy((ncclComm_t)c->nccl);
@@ -589,6 +627,10 @@ int hfx_mpi_inters_send_solution(hfx_inters *f, hfx_comm *c)
   HFX_CHECK(f && f->is_mpi && c, "hfx_mpi_inters_send_solution: bad argument");
   if (f->n_inters == 0) return 0;
   HFX_DEFER(f->ctx, DM_MPI_SEND_SOLUTION, nullptr, f, c, 0, 0);
+  // the partitioned fused stage that produced this state has posted its flux-point solution already (a stage replayed after it,
+  // or calls made with the option "deferred" off): posting it again would send the neighbours one message more than the calls
+  // ask for, and packing it again would rewrite the buffer that message may still be reading.  receive_solution waits for it
+  if (sent_over(f->left, c)) return 0;
   if (hfx_mpi_inters_pack_solution(f)) return 1;
   return start_exchange(c, &f, 1, 0, false);
 }
@@ -598,7 +640,7 @@ int hfx_mpi_inters_receive_solution(hfx_inters *f, hfx_comm *c)
   HFX_CHECK(f && f->is_mpi && c, "hfx_mpi_inters_receive_solution: bad argument");
   if (f->n_inters == 0) return 0;
   HFX_DEFER(f->ctx, DM_MPI_RECEIVE_SOLUTION, nullptr, f, c, 0, 0);
-  return wait_exchange(c, 0);
+  return wait_exchange(c, 0, 1);
 }
 
 int hfx_mpi_inters_send_corrected_gradient(hfx_inters *f, hfx_comm *c)
@@ -615,7 +657,7 @@ int hfx_mpi_inters_receive_corrected_gradient(hfx_inters *f, hfx_comm *c)
   HFX_CHECK(f && f->is_mpi && c, "hfx_mpi_inters_receive_corrected_gradient: bad argument");
   if (f->n_inters == 0) return 0;
   HFX_DEFER(f->ctx, DM_MPI_RECEIVE_GRADIENT, nullptr, f, c, 0, 0);
-  return wait_exchange(c, 1);
+  return wait_exchange(c, 1, 1);
 }
 
 int hfx_mpi_inters_send_sgsf_fpts(hfx_inters *f, hfx_comm *c)
@@ -632,7 +674,7 @@ int hfx_mpi_inters_receive_sgsf_fpts(hfx_inters *f, hfx_comm *c)
   HFX_CHECK(f && f->is_mpi && c, "hfx_mpi_inters_receive_sgsf_fpts: bad argument");
   if (f->n_inters == 0) return 0;
   HFX_DEFER(f->ctx, DM_MPI_RECEIVE_SGSF, nullptr, f, c, 0, 0);
-  return wait_exchange(c, 2);
+  return wait_exchange(c, 2, 1);
 }
 
 int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi,
@@ -656,7 +698,9 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   const int nst = n_rk_stages(ctx->params);
   for (int i = 0; i < n_ele_blocks; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
-  bool start = true;
+  // (as run_partitioned: the solution a partitioned fused stage has posted for this state is not posted again)
+  bool start = false;
+  for (int i = 0; i < n_ele_blocks; i++) start = start || !sent_over(eles[i], comm);
   for (int s = 0; s < n_steps; s++)
   {
     for (int rk = 0; rk < nst; rk++)
@@ -671,7 +715,30 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
     advance_ramp_counters(int_faces, n_int);
   }
   // (nothing in flight when the caller reads or changes the state)
-  return n_steps > 0 ? wait_exchange(comm, 0) : 0;
+  if (n_steps > 0)
+  {
+    if (wait_exchange(comm, 0, n_mpi)) return 1;
+    mark_drained(eles, n_ele_blocks);
+  }
+  return 0;
+}
+
+int hfx_comm_exchange_stats(hfx_comm *c, long posted[3], long waited[3], int *in_flight, int *stream_busy)
+{
+  HFX_CHECK(c, "hfx_comm_exchange_stats: NULL communicator");
+  for (int k = 0; k < 3; k++)
+  {
+    if (posted) posted[k] = c->posted[k];
+    if (waited) waited[k] = c->waited[k];
+  }
+  if (in_flight) *in_flight = c->in_flight;
+  if (stream_busy)
+  {
+    const hipError_t q = hipStreamQuery(c->stream);
+    HFX_CHECK(q == hipSuccess || q == hipErrorNotReady, "hfx_comm_exchange_stats: hipStreamQuery failed: %s", hipGetErrorString(q));
+    *stream_busy = q == hipErrorNotReady;
+  }
+  return 0;
 }
 
 int hfx_time_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi,

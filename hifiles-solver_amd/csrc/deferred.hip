@@ -244,6 +244,8 @@ int replay_call(const DeferCall &c)
   {
   case DM_CALC_SGS_TERMS: return hfx_eles_calc_sgs_terms(c.e);
   case DM_EXTRAPOLATE_SOLUTION: return hfx_eles_extrapolate_solution(c.e);
+  // (posts nothing where a partitioned fused stage has already sent this state's flux-point solution: the record's
+  // receive_solution then waits for that message -- replaying never changes how many messages the neighbours get)
   case DM_MPI_SEND_SOLUTION: return hfx_mpi_inters_send_solution(c.f, c.c);
   case DM_CALCULATE_GRADIENT: return hfx_eles_calculate_gradient(c.e);
   case DM_EVALUATE_INVFLUX: return c.i0 ? hfx_eles_evaluate_invFlux_over_int(c.e) : hfx_eles_evaluate_invFlux(c.e);
@@ -285,7 +287,7 @@ static int run_fused(hfx_ctx *ctx, const DeferPlan &P, int in_step, bool write_d
   for (hfx_eles *e : P.eles)
   {
     if (!e->fpts_valid && hfx_eles_extrapolate_solution(e)) return 1;
-    start = start || !e->fpts_sent;
+    start = start || !(P.comm && e->fpts_sent && e->sent_on == P.comm->serial);
   }
   hfx_eles *e0 = P.eles[0];
   hfx_inters *const *faces = P.faces.data();
@@ -314,6 +316,9 @@ static int run_fused(hfx_ctx *ctx, const DeferPlan &P, int in_step, bool write_d
   {
     e->fpts_valid = true;
     e->fpts_sent = P.kind == 2 || P.kind == 4;
+    e->sent_on = e->fpts_sent ? P.comm->serial : 0;
+    e->sent_blocks = 0;
+    for (const hfx_inters *f : P.mpi_faces) e->sent_blocks += f->left == e;
     e->stale |= ~fresh & ((1u << HFX_N_ARRAYS) - 1u);
     e->stale &= ~fresh;
   }

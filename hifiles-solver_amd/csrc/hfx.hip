@@ -513,6 +513,10 @@ int hfx_ctx_synchronize(hfx_ctx *ctx)
   HFX_CHECK(ctx, "NULL ctx");
   HFX_IMMEDIATE(ctx, 0);
   HFX_HIP(hipStreamSynchronize(ctx->stream));
+  // a partitioned fused stage leaves the next state's exchange running on the communication stream (it is not waited for at
+  // the end of the stage, where it would serialise with the next one): wait for it here
+  for (hfx_comm *c : ctx->comms)
+    if (c->in_flight > 0) HFX_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -608,12 +612,11 @@ int hfx_eles_create(hfx_ctx *ctx, const hfx_eles_desc *d, hfx_eles **out)
 int hfx_eles_destroy(hfx_eles *e)
 {
   if (!e) return 0;
-  {
-    // (a record that still names this block cannot run any more: drop it with the plans that point here)
-    hfx::Deferred &d = e->ctx->defer;
-    d.log.clear();
-    d.plans.clear();
-  }
+  // what has been recorded runs first (a stage that RunSteps left pending behind its AdvanceSolution belongs to every block of
+  // the context, not only to this one); then the plans that point here go.  A failing flush is this call's error
+  const int rc = defer_flush(e->ctx, 0);
+  e->ctx->defer.log.clear();
+  e->ctx->defer.plans.clear();
   free_operator(e->opp_0); free_operator(e->opp_3); free_operator(e->opp_6);
   free_operator(e->inv_vandermonde); free_operator(e->exp_filter);
   free_operator(e->opp_over_int_cubpts); free_operator(e->over_int_filter);
@@ -647,7 +650,7 @@ int hfx_eles_destroy(hfx_eles *e)
   fused_destroy(e);
   general_destroy(e);
   delete e;
-  return 0;
+  return rc;
 }
 
 int hfx_eles_upload(hfx_eles *e, int id, const double *host)
@@ -655,7 +658,7 @@ int hfx_eles_upload(hfx_eles *e, int id, const double *host)
   HFX_CHECK(e && host, "hfx_eles_upload: NULL argument");
   HFX_CHECK(id >= 0 && id < HFX_N_ARRAYS, "hfx_eles_upload: bad array id %d", id);
   HFX_IMMEDIATE(e->ctx, 0);
-  if (id == HFX_DISU_UPTS0 || id == HFX_DISU_FPTS) invalidate_fpts(e);
+  if ((id == HFX_DISU_UPTS0 || id == HFX_DISU_FPTS) && invalidate_fpts(e)) return 1;
   e->stale &= ~(1u << id);
   if (!e->arr[id]) HFX_HIP(hipMalloc((void **)&e->arr[id], sizeof(double) * (size_t)std::max<long>(e->arr_len[id], 1)));
   HFX_HIP(hipStreamSynchronize(e->ctx->stream));
@@ -670,9 +673,10 @@ int hfx_eles_download(hfx_eles *e, int id, double *host)
   HFX_CHECK(id >= 0 && id < HFX_N_ARRAYS, "hfx_eles_download: bad array id %d", id);
   HFX_CHECK(e->arr[id] != nullptr, "hfx_eles_download: array %d was never uploaded", id);
   HFX_IMMEDIATE(e->ctx, 1u << id);
-  HFX_CHECK(!(e->ctx->defer.on && (e->stale & (1u << id))),
+  // (whether or not the context defers now: the option switched off after a fused stage does not make its arrays current)
+  HFX_CHECK(!(e->stale & (1u << id)),
             "hfx_eles_download: array %d was not materialised by the fused stage that ran last (deferred execution): read it before the "
-            "next stage begins, or switch the option \"deferred\" off", id);
+            "next stage begins", id);
   HFX_HIP(hipStreamSynchronize(e->ctx->stream));
   HFX_HIP(hipMemcpy(host, e->arr[id], sizeof(double) * (size_t)e->arr_len[id], hipMemcpyDeviceToHost));
   return 0;
@@ -684,7 +688,7 @@ int hfx_eles_is_current(hfx_eles *e, int id, int *current)
   HFX_CHECK(id >= 0 && id < HFX_N_ARRAYS, "hfx_eles_is_current: bad array id %d", id);
   // (a pending record is not run for this question)
   const hfx::Deferred &d = e->ctx->defer;
-  if (!(d.on && (e->stale & (1u << id))))
+  if (!(e->stale & (1u << id)))
     *current = 1;
   else
   {
@@ -701,7 +705,7 @@ int hfx_eles_device_ptr(hfx_eles *e, int id, double **dev)
   HFX_CHECK(e && dev, "hfx_eles_device_ptr: NULL argument");
   HFX_CHECK(id >= 0 && id < HFX_N_ARRAYS, "hfx_eles_device_ptr: bad array id %d", id);
   HFX_IMMEDIATE(e->ctx, 1u << id);
-  if (id == HFX_DISU_UPTS0 || id == HFX_DISU_FPTS) invalidate_fpts(e); // (the caller may write through the pointer)
+  if ((id == HFX_DISU_UPTS0 || id == HFX_DISU_FPTS) && invalidate_fpts(e)) return 1; // (the caller may write through the pointer)
   *dev = e->arr[id];
   return 0;
 }
@@ -872,7 +876,7 @@ int hfx_eles_AdvanceSolution(hfx_eles *e, int in_step, int adv_type)
   const int nst = (adv_type == 0) ? 1 : (adv_type <= 2) ? 4 : (adv_type == 3) ? 5 : 14;
   HFX_CHECK(in_step >= 0 && in_step < nst, "AdvanceSolution: stage %d out of range for adv_type %d", in_step, adv_type);
   HFX_DEFER(ctx, DM_ADVANCE_SOLUTION, e, nullptr, nullptr, in_step, adv_type);
-  invalidate_fpts(e);
+  if (invalidate_fpts(e)) return 1;
   AdvArgs a;
   a.n = (long)e->n_upts * e->n_eles * e->n_fields;
   a.plane = (long)e->n_upts * e->n_eles;
@@ -913,7 +917,7 @@ int hfx_eles_compute_res_upts(hfx_eles *e, int norm_type, int field, double *out
   HFX_CHECK(norm_type >= 0 && norm_type <= 2, "compute_res_upts: bad norm type");
   HFX_CHECK(field >= 0 && field < e->n_fields, "compute_res_upts: bad field");
   HFX_IMMEDIATE(e->ctx, 1u << HFX_DIV_TCONF_UPTS);
-  HFX_CHECK(!(e->ctx->defer.on && (e->stale & (1u << HFX_DIV_TCONF_UPTS))),
+  HFX_CHECK(!(e->stale & (1u << HFX_DIV_TCONF_UPTS)),
             "compute_res_upts: div_tconf_upts was not stored by the fused stage that ran last (deferred execution stores it at the last "
             "stage of a step, or when asked before the next stage begins)");
   const long plane = (long)e->n_upts * e->n_eles;
@@ -979,9 +983,16 @@ int hfx_int_inters_create(hfx_ctx *ctx, hfx_eles *left, hfx_eles *right, int n_i
 int hfx_inters_destroy(hfx_inters *f)
 {
   if (!f) return 0;
-  // (a record that still names this block cannot run any more: drop it with the plans that point here)
+  // what has been recorded runs first (as hfx_eles_destroy), then the plans that point here go
+  const int rc = defer_flush(f->ctx, 0);
   f->ctx->defer.log.clear();
   f->ctx->defer.plans.clear();
+  // a partition-face block's buffers may still be read or written by an exchange on the communication stream
+  if (f->is_mpi && f->left)
+  {
+    (void)invalidate_fpts(f->left);
+    (void)hipStreamSynchronize(f->ctx->stream);
+  }
   for (hfx_eles *e : {f->left, f->right})
     if (e)
     {
@@ -997,7 +1008,7 @@ int hfx_inters_destroy(hfx_inters *f)
   if (f->boundary_id) (void)hipFree(f->boundary_id);
   if (f->bcs) (void)hipFree(f->bcs);
   delete f;
-  return 0;
+  return rc;
 }
 
 // ---- LES closure ----------------------------------------------------------------------------
@@ -1063,7 +1074,7 @@ int hfx_eles_calc_sgs_terms(hfx_eles *e)
   HFX_CHECK(e->filter_upts.present(), "calc_sgs_terms: SGS model %d filters the solution: register filter_upts (hfx_eles_set_les_filter)", model);
   hfx_ctx *ctx = e->ctx;
   HFX_DEFER(ctx, DM_CALC_SGS_TERMS, e, nullptr, nullptr, 0, 0);
-  if (model == 3) invalidate_fpts(e); // (the filtered solution replaces the state)
+  if (model == 3 && invalidate_fpts(e)) return 1; // (the filtered solution replaces the state)
   e->stale &= ~((1u << HFX_DISUF_UPTS) | (1u << HFX_LU) | (1u << HFX_LE));
   hipStream_t st = ctx->stream;
   const long plane = (long)e->n_upts * e->n_eles;
@@ -1378,7 +1389,7 @@ int hfx_eles_shock_capture(hfx_eles *e)
   HFX_CHECK(e->shock_ready, "shock_capture: hfx_eles_set_shock_capture was not called");
   hfx_ctx *ctx = e->ctx;
   HFX_DEFER(ctx, DM_SHOCK_CAPTURE, e, nullptr, nullptr, 0, 0);
-  invalidate_fpts(e);
+  if (invalidate_fpts(e)) return 1;
   e->stale &= ~(1u << HFX_SENSOR);
   if (tensor_shock_available(e) && ctx->contract_mode != HFX_CONTRACT_DENSE) return tensor_shock_launch(e);
   const long plane = (long)e->n_upts * e->n_eles;

@@ -155,6 +155,7 @@ struct hfx_ctx
     int general_waves = 0;      // waves per workgroup of the general flux kernel: 0 by the LDS image (4 or 8), else 3, 4 or 8
   } opt;
   hfx::Deferred defer;
+  std::vector<hfx_comm *> comms; // the live communicators of this context (hfx_ctx_synchronize waits for their streams)
   double CFL = 0.0; // run_input.CFL (hfx_ctx_set_CFL); dt_type 1 / 2 only
   bool have_CFL = false;
   hfx::Phys phys() const
@@ -218,6 +219,8 @@ struct hfx_eles
   // else that changes the state clears it), and on a partitioned block that flux-point solution is already on its way to
   // the neighbours; stale: bit i = array i was not refreshed by the last fused stage (its contents are older)
   bool fpts_valid = false, fpts_sent = false;
+  unsigned long sent_on = 0; // fpts_sent: the serial number of the communicator that message travels on,
+  int sent_blocks = 0;       // and the partition-face blocks of this element block it carries
   unsigned stale = 0;
   unsigned long long *nan_flag = nullptr; // device: smallest flat index of a NaN in div_tconf, or ~0
   double *red_buf = nullptr;              // device partial sums for reductions
@@ -261,6 +264,12 @@ struct hfx_comm
   hipEvent_t packed[3] = {nullptr, nullptr, nullptr};   // compute -> comm: buffers of kind 0 / 1 / 2 are packed
   hipEvent_t received[3] = {nullptr, nullptr, nullptr}; // comm -> compute: exchange of kind 0 / 1 / 2 complete
   double *scratch = nullptr;                   // device scratch of the small all-reduces
+  // exchange accounting (hfx_comm_exchange_stats): messages of kind 0 / 1 / 2 posted and waited for, one per partition-face
+  // block -- what the per-method send_* / receive_* calls of those blocks would have posted -- and how many solution messages
+  // of partition-face blocks are posted and not consumed yet
+  long posted[3] = {0, 0, 0}, waited[3] = {0, 0, 0};
+  int in_flight = 0;
+  unsigned long serial = 0; // unique over the process (a block remembers the communicator of its message by it)
 };
 
 namespace hfx
@@ -286,7 +295,10 @@ struct DeferBusy
   explicit DeferBusy(hfx_ctx *ctx) : c(ctx), prev(ctx->defer.busy) { c->defer.busy = true; }
   ~DeferBusy() { c->defer.busy = prev; }
 };
-inline void invalidate_fpts(hfx_eles *e) { e->fpts_valid = e->fpts_sent = false; }
+// the state of e is about to change (or may be changed through a device pointer): disu_fpts no longer holds it.  A solution
+// message of e still on its way is taken off first -- the compute stream waits for it -- so that nothing the caller writes
+// next races the communication stream (comm.hip)
+int invalidate_fpts(hfx_eles *e);
 int side_stream_fork(hfx_ctx *ctx);
 int side_stream_join(hfx_ctx *ctx);
 int side_stream_wait(hfx_ctx *ctx);

@@ -433,6 +433,14 @@ class Comm:
         check(lib().hfx_comm_allreduce(self.h, a, C.c_int(len(values)), C.c_int({"min": 0, "max": 1, "sum": 2}[op])))
         return list(a)
 
+    def exchange_stats(self):
+        """-> {posted: [3], waited: [3], in_flight, stream_busy} (hfx_comm_exchange_stats): messages of kind 0 (solution),
+        1 (gradient / projected flux), 2 (SGS flux) counted per partition-face block"""
+        posted, waited = (C.c_long * 3)(), (C.c_long * 3)()
+        in_flight, busy = C.c_int(0), C.c_int(0)
+        check(lib().hfx_comm_exchange_stats(self.h, posted, waited, C.byref(in_flight), C.byref(busy)))
+        return {"posted": list(posted), "waited": list(waited), "in_flight": in_flight.value, "stream_busy": busy.value}
+
     def close(self):
         if self.h:
             lib().hfx_comm_destroy(self.h)

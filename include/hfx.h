@@ -157,12 +157,23 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value);
  * while a whole stage is pending makes that stage run call by call, so that the caller sees the reference's values (a
  * monitor that reads grad_disu_upts after a step, src/eles.cpp:5485, costs one per-method stage); once the next stage has
  * begun such an array is stale and its download FAILS rather than return older values.
- * An error in a recorded call surfaces at the entry point that makes the record run. */
+ * An error in a recorded call surfaces at the entry point that makes the record run.
+ * The stale marks hold whether or not the option is on: switching "deferred" off after a fused stage does not make the arrays it
+ * left stale readable.  hfx_eles_destroy / hfx_inters_destroy run what has been recorded before the block goes (a stage left
+ * pending behind its AdvanceSolution belongs to every block of the context); a failure of that run is their return value.
+ * Partition faces: a partitioned fused stage ends with the NEXT state's flux-point solution already posted.  Whatever follows
+ * -- that stage replayed call by call, calls made with the option off, hfx_run_steps_partitioned(_blocks) -- takes that message
+ * instead of posting it again (send_solution posts nothing, receive_solution waits for it), so replay and flush decisions,
+ * which are a rank's own, never change the number of messages a rank posts: that follows the partition-face calls alone
+ * (hfx_comm_exchange_stats counts them).  An upload of the state, a device pointer to it or a closure that filters it waits for
+ * such a message first and drops it; hfx_ctx_synchronize also waits for the communication streams that carry one. */
 int hfx_ctx_flush(hfx_ctx *ctx); /* run what has been recorded (asynchronously, on the context's stream); no-op otherwise */
 /* stages run fused / records replayed call by call since the context was created, and why the last replay was one */
 int hfx_ctx_deferred_stats(hfx_ctx *ctx, long *n_fused, long *n_replayed, const char **why_last_replay);
 /* run_input.dt as the last calc_time_step left it (dt_type 1), or as set (dt_type 0) */
 int hfx_ctx_get_dt(hfx_ctx *ctx, double *dt);
+/* runs what has been recorded and waits for the context's stream and for the communication stream of every hfx_comm of the
+ * context that has a solution message in flight */
 int hfx_ctx_synchronize(hfx_ctx *ctx);
 /* the HIP stream (hipStream_t) all kernels of this context are launched on */
 void *hfx_ctx_stream(hfx_ctx *ctx);
@@ -408,6 +419,13 @@ typedef struct hfx_comm hfx_comm;
 int hfx_comm_get_unique_id(char id[HFX_COMM_ID_BYTES]);
 int hfx_comm_create(hfx_ctx *ctx, const char id[HFX_COMM_ID_BYTES], int nranks, int rank, hfx_comm **out);
 int hfx_comm_destroy(hfx_comm *c);
+/* Exchange accounting of this communicator since its creation: posted[k] / waited[k] = messages of kind k (0 the flux-point
+ * solution, 1 the corrected gradient or projected viscous flux, 2 the SGS flux) posted / waited for, counted per partition-face
+ * block (a fused stage's grouped exchange over n blocks counts n, as n send_* calls would); *in_flight = solution messages
+ * posted and not yet consumed by a stage (a partitioned fused stage leaves the next state's one so); *stream_busy = 1 while the
+ * communication stream has work queued (hipStreamQuery).  posted[0] - *in_flight equals what the same partition-face calls post
+ * with the option "deferred" off, whatever the rank downloaded or flushed in between.  Any argument may be NULL. */
+int hfx_comm_exchange_stats(hfx_comm *c, long posted[3], long waited[3], int *in_flight, int *stream_busy);
 /* what RCCL reports for this communicator: ncclCommCount, ncclCommUserRank, ncclCommCuDevice, and that device's PCI bus id
  * (hipDeviceGetPCIBusId) -- evidence in a benchmark line that N ranks on N different devices took part */
 int hfx_comm_info(hfx_comm *c, int *nranks, int *rank, int *device, char pci_bus_id[32]);
