@@ -19,6 +19,7 @@
 
 #include "fused_hex.hpp"
 #include "general.hpp"
+#include "split_common.hpp"
 #include "hfx_internal.hpp"
 
 namespace hfx
@@ -193,8 +194,6 @@ static void mark_drained(hfx_eles *const *eles, int n)
   }
 }
 
-static int n_rk_stages(const hfx_params &p) { return (p.adv_type == 0) ? 1 : (p.adv_type <= 2) ? 4 : (p.adv_type == 3) ? 5 : 14; }
-
 // calc_time_step (src/solver.cpp:484-549): per-element CFL steps, minimum over the block and over the ranks
 int calc_time_step(hfx_eles *e, hfx_comm *comm)
 {
@@ -262,16 +261,16 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
 {
   hfx_ctx *ctx = e->ctx;
   const bool visc = ctx->params.viscous != 0;
-  if (split_deferred_prepare(e, int_faces, n_int, true)) return 1; // (the variant below depends on the block's fused tables)
-  const bool projected = split_variant(e) == 3; // variant 3 sends the projected viscous flux
+  if (split_deferred_prepare(e, int_faces, n_int, true)) return 1; // (the plan below depends on the block's fused tables)
+  const SplitPlan pl = split_plan(e, int_faces, n_int, ctx->fused_mode); // projected: variant 3 sends the projected viscous flux
   // third message: the SGS flux (src/solver.cpp:168-178,203-206) -- variant 2 only; in variant 3 it is part of the projected flux
-  const bool les = e->les_ready && !projected;
+  const bool les = e->les_ready && !pl.projected;
   hipStream_t st = ctx->stream, cs = comm->stream;
   auto phase = [&](int ph, int stage, int first) {
     return split_stage_partitioned(e, int_faces, n_int, mpi_faces, n_mpi, ph, stage, first);
   };
   // (the timed form keeps every kernel of a phase on the compute stream, so that its events bracket the phase)
-  const bool beside = ctx->opt.comm_stream_faces && projected && !les && visc && T == nullptr;
+  const bool beside = ctx->opt.comm_stream_faces && pl.projected && !les && visc && T == nullptr;
   if (start)
   {
     if (phase(0, rk, 1)) return 1;
@@ -291,7 +290,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
     // the flux kernel in three launches (option split_flux): half of the elements WITHOUT partition-face points first -- they
     // need nothing from the neighbours, so the solution exchange runs beside them --, then the elements with, whose projected
     // fluxes then leave beside the other half (and the interior common-flux kernel)
-    const bool split_flux = ctx->opt.split_flux && !e->over_int_ready && n_mpi > 0;
+    const bool split_flux = ctx->opt.split_flux && pl.split_flux && n_mpi > 0;
     if (split_flux && phase(13, rk, 0)) return 1;
     if (wait_exchange(comm, 0, n_mpi)) return 1;
     if (split_flux ? phase(14, rk, 0) : phase(6, rk, 0)) return 1; // gradient + flux kernel
@@ -309,7 +308,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
     if (wait_exchange(comm, 1, n_mpi)) return 1;
     // the update: first the elements with partition-face points, whose new flux-point solution is packed and sent (communication
     // stream) while the others are updated -- the exchange the next stage's flux kernel waits for is hidden behind them
-    const bool split_update = ctx->opt.split_update && !e->shock_ready && n_mpi > 0;
+    const bool split_update = ctx->opt.split_update && pl.split_update && n_mpi > 0;
     if (split_update ? phase(11, rk, 0) : phase(9, rk, 0)) return 1; // update (+ shock capturing)
     HFX_HIP(hipEventRecord(comm->packed[0], st));
     HFX_HIP(hipStreamWaitEvent(cs, comm->packed[0], 0));
@@ -324,7 +323,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
   if (phase(1, rk, 0)) return 1;
   if (T) HFX_HIP(hipEventRecord(T->ph[1], st));
   if (wait_exchange(comm, 0, n_mpi)) return 1;
-  const bool pieces = T && projected && visc; // phase 2 in its three pieces, the element kernel bracketed on its own
+  const bool pieces = T && pl.projected && visc; // phase 2 in its three pieces, the element kernel bracketed on its own
   if (pieces)
   {
     if (phase(5, rk, 0)) return 1;
@@ -338,7 +337,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
   if (visc)
   {
     if (T) HFX_HIP(hipEventRecord(T->x1[0], st));
-    if (start_exchange(comm, mpi_faces, n_mpi, 1, projected)) return 1;
+    if (start_exchange(comm, mpi_faces, n_mpi, 1, pl.projected)) return 1;
     if (les && start_exchange(comm, mpi_faces, n_mpi, 2, false)) return 1;
     if (T) HFX_HIP(hipEventRecord(T->x1[1], cs));
   }

@@ -24,6 +24,7 @@
 
 #include "fused_hex.hpp"
 #include "general.hpp"
+#include "split_common.hpp"
 #include "hfx_internal.hpp"
 
 namespace hfx
@@ -36,8 +37,6 @@ static const char *const method_names[DM_N_METHODS + 1] = {
     "calculate_divergence", "int calculate_common_viscFlux", "evaluate_boundaryConditions_viscFlux", "receive_corrected_gradient",
     "receive_sgsf_fpts", "mpi calculate_common_viscFlux", "calculate_corrected_divergence", "AdvanceSolution", "shock_capture",
     "set_ramp_counter"};
-
-static int n_rk_stages(const hfx_params &p) { return (p.adv_type == 0) ? 1 : (p.adv_type <= 2) ? 4 : (p.adv_type == 3) ? 5 : 14; }
 
 static bool same_call(const DeferCall &a, const DeferCall &b)
 {
@@ -212,7 +211,7 @@ static void make_plan(hfx_ctx *ctx, const std::vector<DeferCall> &log, DeferPlan
       P.why = hfx_last_error();
       return;
     }
-    if (e0->over_int_ready && split_variant(e0) != 3) { P.why = "the split variant that keeps the gradients (LES, fused mode 2) has no over-integration"; return; }
+    if (e0->over_int_ready && split_plan(e0, P.faces.data(), (int)P.faces.size(), ctx->fused_mode).variant != 3) { P.why = "the split variant that keeps the gradients (LES, fused mode 2) has no over-integration"; return; }
     P.kind = mpi ? 2 : 1;
     return;
   }

@@ -16,7 +16,7 @@
 // registered operators are bit-exactly tensor products) or DICTIONARY-COMPRESSED sparse rows: a tensor-product
 // operator has only a handful of distinct values, so a row entry is 16 bits (value id, column), two per 32-bit
 // register, the values in a 2 kB LDS table.  Hexes from P6 on have columns beyond 8 bits: their entries are 32 bits
-// (value id << 16 | column), one per register (Geo::WIDE); only variant 2 runs them (split_route).  The arithmetic is unchanged: the same non-zeros, multiplied in the same
+// (value id << 16 | column), one per register (Geo::WIDE); only variant 2 runs them (split_plan).  The arithmetic is unchanged: the same non-zeros, multiplied in the same
 // ascending-column order as the reference dgemm (src/funcs.cpp:110-117).
 #include <vector>
 #include "fused_hex.hpp"
@@ -604,33 +604,87 @@ static bool loader_wave_fits_rt(int nd, int N)
   return false;
 }
 
-// Can the LES closure of this block be evaluated inside the flux kernel of variant 3 (split_flux_tensor_kernel<..., LES>)?  It
-// is part of the loader-wave form of the sum-factorised kernel only; otherwise a block with a closure runs variant 2, which keeps
-// the corrected gradient in HBM for the pointwise closure kernel.  Needs the block's fused tables (fused_build).
-bool les_in_flux_kernel(const hfx_eles *e)
+// What the split stage runs on this block when `requested_variant` is asked for (SplitPlan): from the options, the block's fused
+// tables (fused_build; without them no sum-factorised form is planned), its flags and array sizes, its face blocks.
+SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int requested_variant)
 {
   const hfx_ctx::Options &opt = e->ctx->opt;
-  if (!e->les_ready || !e->ctx->params.viscous || e->over_int_ready || !opt.les_flux_kernel) return false;
-  if (!e->fused || !e->fused->built || !e->fused->tensor_ok) return false;
-  if (opt.dictionary_rows || !opt.loader_wave || !opt.buffer_addressing || opt.flux_waves != 2) return false;
-  if (!loader_wave_fits_rt(e->n_dims, tensor_n(e))) return false;
-  const double plane_most = (double)std::max<long>((long)e->n_fpts * e->n_eles, (long)e->n_upts * e->n_eles);
-  // every array the launch touches below 4 GiB (boundary blocks make it store the flux-point gradient array too)
-  return plane_most * e->n_fields * e->n_dims * 8.0 < 4294967296.0;
-}
+  const FusedData *F = (e->fused && e->fused->built) ? e->fused : nullptr;
+  const bool viscous = e->ctx->params.viscous != 0, oi = e->over_int_ready;
+  const int N = tensor_n(e);
+  // the sum-factorised kernels, and the options and element size of their loader-wave form
+  const bool tensor = F && F->tensor_ok && !opt.dictionary_rows;
+  const bool lw_form = tensor && loader_wave_fits_rt(e->n_dims, N) && opt.loader_wave && opt.buffer_addressing && opt.flux_waves == 2;
+  bool any_bdy = false;
+  for (int b = 0; b < nfb; b++) any_bdy = any_bdy || faces[b]->is_bdy;
+  SplitPlan p;
+  p.bdy_grad = any_bdy && viscous;
 
-// The variant a block runs when `variant` is asked for: variant 3 falls back to 2 where its kernels do not fit the element
-// size (split3_fits: hexes from P6 on) and where an LES closure cannot be evaluated in its flux kernel (les_in_flux_kernel).
-// (the LES part needs the block's fused tables: fused_build first)
-static int split_route(const hfx_eles *e, int variant)
-{
-  if (variant != 3) return variant;
-  if (!split3_fits_rt(e->n_dims, tensor_n(e))) return 2;
-  return (e->les_ready && !les_in_flux_kernel(e)) ? 2 : 3;
+  // Every array a launch touches below 4 GiB (32-bit byte offsets), each test with its own count of the largest array: the
+  // metric tensors, the n_fields * n_dims gradient-sized arrays when in use, the de-aliased flux -- over both point sets
+  // (quads with N >= 5 have more solution points than flux points).
+  auto below_4gib = [](double doubles) { return doubles * 8.0 < 4294967296.0; };
+  const double plane_most = (double)std::max<long>((long)e->n_fpts * e->n_eles, (long)e->n_upts * e->n_eles);
+  auto most = [&](bool grad) {
+    double m = plane_most * std::max(e->n_dims * e->n_dims, e->n_fields);
+    if (grad) m = std::max(m, plane_most * e->n_fields * e->n_dims);
+    if (oi) m = std::max(m, (double)e->n_upts * e->n_eles * e->n_fields * e->n_dims);
+    return m;
+  };
+  // LES in the flux kernel: the gradient-sized arrays always (a boundary block makes it store the flux-point gradient)
+  p.les_fits_4gib = below_4gib(plane_most * e->n_fields * e->n_dims);
+  // LDG corrections in the flux kernel: the gradient-sized arrays with any boundary face
+  p.gather_fits_4gib = below_4gib(most(any_bdy));
+  // buffer addressing of the flux kernel: the gradient-sized arrays with a boundary face on a viscous block
+  p.flux_buf_fits_4gib = below_4gib(most(p.bdy_grad));
+  // buffer addressing of the update kernel: the n_fields arrays
+  p.update_fits_4gib = below_4gib(plane_most * e->n_fields);
+
+  // The variant: 3 falls back to 2 where its kernels do not fit the element size (split3_fits: hexes from P6 on) and where an
+  // LES closure cannot be evaluated in its flux kernel (its loader-wave form only); variant 2 keeps the gradient in HBM.
+  p.les_in_flux = e->les_ready && viscous && !oi && opt.les_flux_kernel && lw_form && p.les_fits_4gib;
+  p.variant = requested_variant;
+  if (requested_variant == 3 && (!split3_fits_rt(e->n_dims, N) || (e->les_ready && !p.les_in_flux))) p.variant = 2;
+  const bool v3 = p.variant == 3;
+
+  // Over-integration (src/solver.cpp:82-91): the loader-wave flux kernel takes the sum-factorised kernel's result folded into
+  // the divergence; a de-aliased flux that arrives whole (unfolded, dense) goes to the register pipeline.
+  const bool oi_tensor = tensor_over_int_available(e) && e->ctx->contract_mode != HFX_CONTRACT_DENSE;
+  const bool oi_fold_ok = !oi || (opt.over_int_fold && oi_tensor);
+  p.oi_fold = v3 && oi && lw_form && oi_fold_ok;
+  if (v3 && oi) p.over_int = p.oi_fold ? OverInt::folded_tensor : oi_tensor ? OverInt::tensor : OverInt::dense;
+
+  // The LDG corrections of the interior points: formed by the loader-wave flux kernel itself, or by face_delta_kernel
+  p.gather = v3 && viscous && opt.gather_delta && F && F->nbr && lw_form && oi_fold_ok && p.gather_fits_4gib;
+  p.face_delta = viscous && !p.gather;
+
+  // The flux kernel.  (les: a closure with an SGS flux -- every model but the spectral vanishing viscosity, a filter)
+  p.flux = !tensor ? FluxForm::dictionary_rows
+           : (lw_form && oi_fold_ok && p.flux_buf_fits_4gib) ? FluxForm::loader_wave : FluxForm::register_pipeline;
+  p.oi = oi;
+  p.les = e->les_ready && e->les.sgs_model != 3;
+  p.buf = opt.buffer_addressing && p.flux_buf_fits_4gib;
+  p.wv = (p.flux == FluxForm::register_pipeline && !oi && p.buf && opt.flux_waves != 2) ? 3 : 2;
+  p.update_buf = opt.buffer_addressing && p.update_fits_4gib;
+
+  // a partitioned block: variant 3 sends the projected viscous flux; element lists for the flux kernel without over-integration
+  // (which runs on all elements first), for the update without shock capturing (whose filter follows the whole update)
+  p.projected = v3;
+  p.split_flux = v3 && !oi;
+  p.split_update = v3 && !e->shock_ready;
+
+  p.names = v3 ? (tensor ? "face_delta_kernel,split_flux_tensor_kernel,face_flux2_kernel,split_update_kernel"
+                         : "face_delta_kernel,split_flux_kernel,face_flux2_kernel,split_update_kernel")
+               : "face_delta_kernel,split_gradient_kernel,face_flux_kernel,split_residual_kernel";
+  if (p.over_int != OverInt::none)
+    p.extra_names = p.over_int == OverInt::dense ? ",evaluate_invFlux_over_int (dense)" : ",overint_tensor_kernel";
+  else if (p.variant == 2 && e->les_ready && viscous)
+    p.extra_names = ",sgsf_upts_kernel + ell_apply_kernel (SGS flux)";
+  return p;
 }
 
 template <int ND, int N>
-static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, SplitEleArgs &ea, int which, int variant)
+static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, SplitEleArgs &ea, Part part, const SplitPlan &pl)
 {
   FusedData *F = e->fused;
   hipStream_t st = e->ctx->stream;
@@ -641,22 +695,22 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
   const int per_cu = opt.split_grid_per_cu;
   const int flux_per_cu = opt.flux_grid_per_cu > 0 ? opt.flux_grid_per_cu : per_cu;
   constexpr int TB = SGeo<ND, N>::TB;
-  // variant 3's element kernels exist for the sizes they fit only (split3_fits); split_route sends the others to variant 2
+  // variant 3's element kernels exist for the sizes they fit only (split3_fits); split_plan sends the others to variant 2
   constexpr bool V3 = split3_fits<ND, N>();
-  HFX_CHECK(V3 || variant == 2, "split variant 3 does not fit %d-D elements with %d points per direction: run variant 2", ND, N);
+  HFX_CHECK(V3 || pl.variant == 2, "split variant 3 does not fit %d-D elements with %d points per direction: run variant 2", ND, N);
   auto face_args = [&](hfx_inters *f) {
     SplitFaceArgs a{};
     a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
     a.L = f->L; a.R = f->R; a.meta = F->meta; a.plane_f = plane_f;
     a.disu = e->arr[HFX_DISU_FPTS]; a.grad = e->arr[HFX_GRAD_DISU_FPTS]; a.fnorm = e->norm_fpts; a.tdA = e->tdA_fpts;
     a.delta = e->arr[HFX_DELTA_DISU_FPTS]; a.tconf = e->arr[HFX_NORM_TCONF_FPTS];
-    a.sgsf = (e->les_ready && variant == 2) ? e->arr[HFX_SGSF_FPTS] : nullptr;
+    a.sgsf = (e->les_ready && pl.variant == 2) ? e->arr[HFX_SGSF_FPTS] : nullptr;
     a.jac_fpts = e->Jacobian_fpts; a.detjac_fpts = e->detjac_fpts;
     a.P = P;
     return a;
   };
   Split2Args e2{};
-  if (variant == 3)
+  if (pl.variant == 3)
   {
     if (opt.flux_stamps && !F->stamps)
     {
@@ -671,12 +725,10 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
     e2.JGinv_fpts = ea.JGinv_fpts; e2.norm_fpts = e->norm_fpts;
     e2.u0 = ea.u0; e2.u1 = ea.u1; e2.delta = ea.delta; e2.tconf = ea.tconf;
     e2.fn_fpts = F->fn_fpts; e2.ntd_fpts = e->arr[HFX_NORM_TDISF_FPTS]; e2.div = ea.div_out;
-    e2.folded = (F->tensor_ok && !opt.dictionary_rows) ? 1 : 0;
+    e2.folded = pl.flux != FluxForm::dictionary_rows ? 1 : 0;
     e2.disu_next = ea.disu_next;
-    bool any_bdy = false;
-    for (int b = 0; b < nfb; b++) any_bdy = any_bdy || faces[b]->is_bdy;
     e2.grad_upts = nullptr;
-    e2.grad_fpts = (any_bdy && P.viscous) ? e->arr[HFX_GRAD_DISU_FPTS] : nullptr; // boundary points only
+    e2.grad_fpts = pl.bdy_grad ? e->arr[HFX_GRAD_DISU_FPTS] : nullptr; // boundary points only
     e2.meta = F->meta;
     e2.stamps = F->stamps;
     e2.stamp_it = std::max(2, opt.flux_stamps);
@@ -688,33 +740,12 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
     e2.adv_type = ea.adv_type; e2.in_step = ea.in_step; e2.dt_local_on = ea.dt_local_on; e2.write_div = ea.write_div;
     e2.need_u1 = ea.need_u1; e2.dt = ea.dt; e2.rk_a = ea.rk_a; e2.rk_b = ea.rk_b;
     e2.les = e->les; e2.tdA_fpts = e->tdA_fpts;
-    if (e->les_ready && e->les.sgs_model != 3 && les_len2_build(e)) return 1;
+    if (pl.les && les_len2_build(e)) return 1;
     e2.les_len2 = F->les_len2;
-  }
-  // Will the flux kernel form the LDG corrections of the interior points itself?  (the loader-wave form of the sum-factorised
-  // kernel only: same conditions as its selection below)
-  // (with over-integration the loader-wave form is taken when the over-integration kernel can hand over its folded result)
-  const bool oi_fold_ok = !e->over_int_ready ||
-                          (opt.over_int_fold && tensor_over_int_available(e) && e->ctx->contract_mode != HFX_CONTRACT_DENSE);
-  bool gather = false;
-  if (variant == 3 && P.viscous && opt.gather_delta && F->nbr && F->tensor_ok && !opt.dictionary_rows && opt.loader_wave &&
-      opt.buffer_addressing && opt.flux_waves == 2 && loader_wave_fits<ND, N>() && oi_fold_ok)
-  {
-    bool any_bdy = false;
-    for (int b = 0; b < nfb; b++) any_bdy = any_bdy || faces[b]->is_bdy;
-    const double plane_most = (double)std::max<long>(plane_f, (long)e->n_upts * e->n_eles);
-    double most = plane_most * std::max(e->n_dims * e->n_dims, e->n_fields);
-    if (any_bdy) most = std::max(most, plane_most * e->n_fields * e->n_dims);
-    if (e->over_int_ready) most = std::max(most, (double)e->n_upts * e->n_eles * e->n_fields * e->n_dims);
-    gather = most * 8.0 < 4294967296.0;
-  }
-  F->gather_on = gather;
-  if (variant == 3)
-  {
-    e2.nbr = gather ? F->nbr : nullptr;
+    e2.nbr = pl.gather ? F->nbr : nullptr;
     e2.disu = e->arr[HFX_DISU_FPTS];
   }
-  if (P.viscous && (which == 0 || which == 1))
+  if (P.viscous && (part == Part::stage || part == Part::ldg))
   {
     for (int b = 0; b < nfb; b++)
     {
@@ -724,26 +755,21 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
         if (hfx_bdy_launch_internal(faces[b], 0, 1)) return 1;
         continue;
       }
-      if (gather) continue; // (the flux kernel reads the partner's flux-point solution itself)
+      if (!pl.face_delta) continue; // (the flux kernel reads the partner's flux-point solution itself)
       const SplitFaceArgs a = face_args(faces[b]);
       if (a.npairs == 0) continue;
       hipLaunchKernelGGL((face_delta_kernel<ND>), dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, st, a);
     }
   }
-  // which (timing only): 5 = the over-integration kernel of part 2 alone, 7 = part 2 without it; 6 = the SGS kernels of part 2
-  // (variant 2 with an LES closure) alone, 8 = part 2 without them
-  if (variant == 3)
+  if (pl.variant == 3)
   {
     if constexpr (V3)
     {
       // Over-integration (src/solver.cpp:82-91).  With the loader-wave flux kernel the sum-factorised kernel hands over
       // sum_l Dc[l] tdisf_l -- the de-aliased flux's whole contribution to (div_tdisf - opp_3 norm_tdisf), n_fields values per
       // solution point (tensor_ops.hip) -- which that kernel adds to its divergence; otherwise tdisf_upts itself.
-      const bool lw_form = loader_wave_fits<ND, N>() && opt.loader_wave && opt.flux_waves == 2 && opt.buffer_addressing &&
-                           F->tensor_ok && !opt.dictionary_rows;
-      const bool oi_fold = e->over_int_ready && lw_form && oi_fold_ok;
       auto run_over_int = [&]() -> int {
-        if (!oi_fold) return hfx_eles_evaluate_invFlux_over_int(e);
+        if (!pl.oi_fold) return hfx_eles_evaluate_invFlux_over_int(e);
         if (!tensor_over_int_folded(e))
         {
           // Dc[d] = D - c3[d][0] (L1 Lf)[d][0]^T - c3[d][1] (L1 Lf)[d][1]^T, as the flux kernel's prologue forms it (split3_kernels.hpp)
@@ -762,96 +788,78 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
         }
         return tensor_over_int_launch(e, true);
       };
-      if (which == 5 && e->over_int_ready && run_over_int()) return 1;
-      // 21 / 22 / 23: the flux kernel on a part of the elements (partitioned blocks, hfx_run_steps_partitioned): the first half of
-      // the elements without partition-face points, those with, the second half -- the solution exchange runs beside the
-      // first launch, the exchange of the projected fluxes beside the third
-      const bool flux_part = which >= 21 && which <= 23;
+      if (part == Part::over_int_only && e->over_int_ready && run_over_int()) return 1;
+      // the flux kernel on a part of the elements (partitioned blocks, hfx_run_steps_partitioned): the first half of the elements
+      // without partition-face points, those with, the second half -- the solution exchange runs beside the first launch, the
+      // exchange of the projected fluxes beside the third
+      const bool flux_part = part == Part::flux_list_1 || part == Part::flux_list_b || part == Part::flux_list_2;
       e2.ele_list = nullptr;
       e2.n_list = 0;
-      if (which == 21) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i1; }
-      if (which == 22) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
-      if (which == 23) { e2.ele_list = F->upd_list_i ? F->upd_list_i + F->n_list_i1 : nullptr; e2.n_list = F->n_list_i - F->n_list_i1; }
+      if (part == Part::flux_list_1) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i1; }
+      if (part == Part::flux_list_b) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
+      if (part == Part::flux_list_2) { e2.ele_list = F->upd_list_i ? F->upd_list_i + F->n_list_i1 : nullptr; e2.n_list = F->n_list_i - F->n_list_i1; }
       if (flux_part && e2.n_list == 0) return 0;
       HFX_CHECK(!flux_part || (e2.ele_list != nullptr && !e->over_int_ready), "split flux kernel on element lists: no lists, or over-integration (which runs on all elements first)");
-      if (which == 0 || which == 2 || which == 7 || flux_part)
+      if (part == Part::stage || part == Part::flux || part == Part::flux_no_over_int || flux_part)
       {
         e2.tdisf_in = nullptr;
         if (e->over_int_ready)
         {
           // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
-          if (which != 7 && run_over_int()) return 1;
+          if (part != Part::flux_no_over_int && run_over_int()) return 1;
           e2.tdisf_in = e->arr[HFX_TDISF_UPTS];
         }
-        const bool dict_only = opt.dictionary_rows != 0;
-        const int waves = opt.flux_waves;
-        // buffer-descriptor addressing needs 32-bit byte offsets into the largest array the kernel touches
-        const bool nobuf = !opt.buffer_addressing;
-        // (the largest array the launch really touches: the metric tensors at the flux points, and the n_fields * n_dims
-        // component arrays only when they are in use -- gradients at boundary points, the de-aliased flux)
-        // -- over BOTH point sets: quads with N >= 5 have more solution points than flux points
-        const double plane_most = (double)std::max<long>(plane_f, (long)e->n_upts * e->n_eles);
-        double most = plane_most * std::max(e->n_dims * e->n_dims, e->n_fields);
-        if (e2.grad_fpts || e2.grad_upts) most = std::max(most, plane_most * e->n_fields * e->n_dims);
-        if (e->over_int_ready) most = std::max(most, (double)e->n_upts * e->n_eles * e->n_fields * e->n_dims);
-        const bool buf = !nobuf && most * 8.0 < 4294967296.0;
-        const bool oi = e2.tdisf_in != nullptr;
-  #define HFX_FLUX_LAUNCH(WV_, BUF_, OI_, LW_)                                                                                  \
-    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, LW_>),                                                  \
-                       dim3(element_grid<split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, LW_>>(e, TB, per_cu)), dim3(TB), 0, st, \
-                       e2, F->t_coef, F->t_idx)
-        const bool no_lw = !opt.loader_wave;
+        HFX_CHECK(!pl.oi_fold || pl.flux == FluxForm::loader_wave, "over-integration: the folded form needs the loader-wave flux kernel");
+        HFX_CHECK(!pl.les || (pl.flux == FluxForm::loader_wave && !pl.oi && P.viscous),
+                  "split variant 3 with an LES closure needs the loader-wave flux kernel (SplitPlan::les_in_flux): run variant 2");
         constexpr bool lw_fits = loader_wave_fits<ND, N>();
-        // (a block whose de-aliased flux arrives whole -- dense over-integration -- takes the form without the loader wave)
-        const bool lw = lw_fits && buf && !no_lw && waves == 2 && (!oi || oi_fold);
-        HFX_CHECK(!oi_fold || (lw && F->tensor_ok && !dict_only), "over-integration: the folded form needs the loader-wave flux kernel");
-        bool launched = false;
-        // a closure with an SGS flux (every model but the spectral vanishing viscosity, which only filters the state)
-        const bool les = e->les_ready && e->les.sgs_model != 3;
-        HFX_CHECK(!les || (lw && F->tensor_ok && !dict_only && !oi && P.viscous),
-                  "split variant 3 with an LES closure needs the loader-wave flux kernel (les_in_flux_kernel): run variant 2");
-        if (F->tensor_ok && !dict_only && lw)
-        {
-          const bool ga = e2.nbr != nullptr && P.viscous; // (the corrections formed in the kernel)
-          if (les && ga)
-            LoaderWaveLaunch<ND, N, false, true, true, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-          else if (les)
-            LoaderWaveLaunch<ND, N, false, false, true, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-          else if (oi && ga)
-            LoaderWaveLaunch<ND, N, true, true, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-          else if (oi)
-            LoaderWaveLaunch<ND, N, true, false, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-          else if (ga)
-            LoaderWaveLaunch<ND, N, false, true, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+        auto loader_wave = [&](auto OI, auto LES) {
+          if (pl.gather)
+            LoaderWaveLaunch<ND, N, decltype(OI)::value, true, decltype(LES)::value, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
           else
-            LoaderWaveLaunch<ND, N, false, false, false, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-          launched = true;
-        }
-        if (launched)
-          ;
-        else if (F->tensor_ok && !dict_only && oi && buf)
-          HFX_FLUX_LAUNCH(2, true, true, false);
-        else if (F->tensor_ok && !dict_only && oi)
-          HFX_FLUX_LAUNCH(2, false, true, false);
-        else if (F->tensor_ok && !dict_only && waves == 2 && buf)
-          HFX_FLUX_LAUNCH(2, true, false, false);
-        else if (F->tensor_ok && !dict_only && buf)
-          HFX_FLUX_LAUNCH(3, true, false, false);
-        else if (F->tensor_ok && !dict_only)
-          HFX_FLUX_LAUNCH(2, false, false, false);
-  #undef HFX_FLUX_LAUNCH
-        else
+            LoaderWaveLaunch<ND, N, decltype(OI)::value, false, decltype(LES)::value, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+        };
+  #define HFX_FLUX_LAUNCH(WV_, BUF_, OI_)                                                                                       \
+    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, false>),                                                 \
+                       dim3(element_grid<split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, false>>(e, TB, per_cu)), dim3(TB), 0, st, \
+                       e2, F->t_coef, F->t_idx)
+        switch (pl.flux)
+        {
+        case FluxForm::loader_wave:
+          if (pl.les)
+            loader_wave(std::false_type{}, std::true_type{});
+          else if (pl.oi)
+            loader_wave(std::true_type{}, std::false_type{});
+          else
+            loader_wave(std::false_type{}, std::false_type{});
+          break;
+        case FluxForm::register_pipeline:
+          if (pl.wv == 3)
+            HFX_FLUX_LAUNCH(3, true, false);
+          else if (pl.buf && pl.oi)
+            HFX_FLUX_LAUNCH(2, true, true);
+          else if (pl.oi)
+            HFX_FLUX_LAUNCH(2, false, true);
+          else if (pl.buf)
+            HFX_FLUX_LAUNCH(2, true, false);
+          else
+            HFX_FLUX_LAUNCH(2, false, false);
+          break;
+        case FluxForm::dictionary_rows:
           hipLaunchKernelGGL((split_flux_kernel<ND, N>), dim3(element_grid<split_flux_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, e2);
+          break;
+        }
+  #undef HFX_FLUX_LAUNCH
       }
     }
   }
-  else if (P.viscous && (which == 0 || which == 2 || which == 6 || which == 8))
+  else if (P.viscous && (part == Part::stage || part == Part::flux || part == Part::sgs_only || part == Part::flux_no_sgs))
   {
     ea.pk = F->pk_g;
     ea.tab = F->tab_g;
-    if (which != 6)
+    if (part != Part::sgs_only)
       hipLaunchKernelGGL((split_gradient_kernel<ND, N>), dim3(element_grid<split_gradient_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, ea);
-    if (e->les_ready && which != 8)
+    if (e->les_ready && part != Part::flux_no_sgs)
     {
       // LES (eddy-viscosity closures): SGS flux at the solution points from the corrected gradient, its extrapolation to
       // the flux points (src/solver.cpp:162-167); the face kernel adds it to each side, the residual kernel to the total
@@ -859,7 +867,7 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
       if (hfx_les_extrapolate_reference_internal(e)) return 1; // the back-transform happens in the face kernel
     }
   }
-  if (which == 0 || which == 3)
+  if (part == Part::stage || part == Part::faces)
   {
     // boundary faces on the side stream, beside the pairwise interior-face kernel: both need the flux kernel's results and
     // write norm_tconf at disjoint points
@@ -876,7 +884,7 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
       const SplitFaceArgs a = face_args(faces[b]);
       if (a.npairs == 0) continue;
       const unsigned nb = (unsigned)((a.npairs + 255) / 256);
-      if (variant == 3)
+      if (pl.variant == 3)
       {
         Split2FaceArgs a2{};
         a2.npairs = a.npairs; a2.L = a.L; a2.R = a.R; a2.meta = a.meta; a2.plane_f = plane_f;
@@ -897,26 +905,24 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
     }
     if (beside && side_stream_wait(e->ctx)) return 1;
   }
-  if (which == 0 || which == 4 || which == 41 || which == 42)
+  const bool update_part = part == Part::update_list_b || part == Part::update_list_i;
+  if (part == Part::stage || part == Part::update || update_part)
   {
-    if (variant == 3)
+    if (pl.variant == 3)
     {
       if constexpr (V3)
       {
-        // 41 / 42: the update on the elements with partition-face points / on the others (two launches: the first one's
-        // flux-point solution leaves for the neighbours while the second runs); 42 comes behind the buffer swap of 41
+        // the update on the elements with partition-face points / on the others (two launches: the first one's flux-point
+        // solution leaves for the neighbours while the second runs); update_list_i comes behind the buffer swap of update_list_b
         e2.ele_list = nullptr;
         e2.n_list = 0;
-        if (which == 41) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
-        if (which == 42) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i; e2.disu_next = e->arr[HFX_DISU_FPTS]; }
-        HFX_CHECK(which < 41 || e2.ele_list != nullptr || e2.n_list == 0, "split update: no element lists (the block was not built as a partitioned one)");
-        // buffer-descriptor addressing needs 32-bit byte offsets
-        const bool nobuf = !opt.buffer_addressing;
-        const bool small = (double)std::max<long>(plane_f, (long)e->n_upts * e->n_eles) * e->n_fields * 8.0 < 4294967296.0;
-        const long n_work = which >= 41 ? e2.n_list : (long)e->n_eles;
+        if (part == Part::update_list_b) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
+        if (part == Part::update_list_i) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i; e2.disu_next = e->arr[HFX_DISU_FPTS]; }
+        HFX_CHECK(!update_part || e2.ele_list != nullptr || e2.n_list == 0, "split update: no element lists (the block was not built as a partitioned one)");
+        const long n_work = update_part ? e2.n_list : (long)e->n_eles;
         if (n_work > 0)
         {
-          if (small && !nobuf)
+          if (pl.update_buf)
           {
             const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, true>>(e, TB, per_cu, 3));
             hipLaunchKernelGGL((split_update_kernel<ND, N, true>), dim3(g), dim3(TB), 0, st, e2);
@@ -940,8 +946,7 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
   return 0;
 }
 
-static int split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_step, bool last_stage, int which = 0,
-                       int variant = 2)
+static int split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_step, bool last_stage, Part part, const SplitPlan &pl)
 {
   FusedData *F = e->fused;
   const hfx_params &p = e->ctx->params;
@@ -955,7 +960,7 @@ static int split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_st
   a.disu_next = F->disu_alt;
   a.grad_upts = e->arr[HFX_GRAD_DISU_UPTS]; a.grad_fpts = e->arr[HFX_GRAD_DISU_FPTS];
   a.div_out = e->arr[HFX_DIV_TCONF_UPTS];
-  a.sgsf_upts = (e->les_ready && variant == 2) ? e->arr[HFX_SGSF_UPTS] : nullptr;
+  a.sgsf_upts = (e->les_ready && pl.variant == 2) ? e->arr[HFX_SGSF_UPTS] : nullptr;
   a.src = e->src_nonzero ? e->arr[HFX_SRC_UPTS] : nullptr;
   a.dt_local = e->arr[HFX_DT_LOCAL];
   a.nan_flag = e->nan_flag;
@@ -968,13 +973,13 @@ static int split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_st
   const int N = tensor_n(e);
   int rc = 1;
 #define HFX_SPLIT_CASE(ND_, N_) \
-  if (e->n_dims == ND_ && N == N_) rc = launch_split_stage<ND_, N_>(e, faces, nfb, a, which, variant);
+  if (e->n_dims == ND_ && N == N_) rc = launch_split_stage<ND_, N_>(e, faces, nfb, a, part, pl);
   HFX_SPLIT_CASE(3, 2) HFX_SPLIT_CASE(3, 3) HFX_SPLIT_CASE(3, 4) HFX_SPLIT_CASE(3, 5) HFX_SPLIT_CASE(3, 6) HFX_SPLIT_CASE(3, 7) HFX_SPLIT_CASE(3, 8)
   HFX_SPLIT_CASE(2, 2) HFX_SPLIT_CASE(2, 3) HFX_SPLIT_CASE(2, 4) HFX_SPLIT_CASE(2, 5) HFX_SPLIT_CASE(2, 6) HFX_SPLIT_CASE(2, 7) HFX_SPLIT_CASE(2, 8)
 #undef HFX_SPLIT_CASE
   if (rc) return 1;
   // (the buffer swap: behind the whole update, or behind its first part -- the second part then writes the new buffer by name)
-  if (which == 0 || which == 4 || which == 41) std::swap(e->arr[HFX_DISU_FPTS], e->fused->disu_alt);
+  if (part == Part::stage || part == Part::update || part == Part::update_list_b) std::swap(e->arr[HFX_DISU_FPTS], e->fused->disu_alt);
   return 0;
 }
 
@@ -997,9 +1002,9 @@ int split_deferred_prepare(hfx_eles *e, hfx_inters *const *faces, int nfb, bool 
 int split_deferred_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_step, bool write_div, bool shock)
 {
   if (split_deferred_prepare(e, faces, nfb, false)) return 1;
-  const int variant = split_variant(e);
-  HFX_CHECK(!e->over_int_ready || variant == 3, "the split variant that keeps the gradients (fused 2, which LES without the in-kernel closure selects) has no over-integration");
-  if (split_stage(e, faces, nfb, in_step, write_div, 0, variant)) return 1;
+  const SplitPlan pl = split_plan(e, faces, nfb, e->ctx->fused_mode);
+  HFX_CHECK(!e->over_int_ready || pl.variant == 3, "the split variant that keeps the gradients (fused 2, which LES without the in-kernel closure selects) has no over-integration");
+  if (split_stage(e, faces, nfb, in_step, write_div, Part::stage, pl)) return 1;
   // the filter changes disu_upts(0) after the stage: redo the flux-point solution of the new state
   return shock ? shock_capture_keep_fpts(e) : 0;
 }
@@ -1009,14 +1014,11 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
   HFX_CHECK(e->n_eles > 0, "fused path: empty element block");
   if (!e->fused || !e->fused->built)
     if (fused_build(e, faces, nfb)) return 1;
-  // an LES closure reads the corrected gradient: variant 3 evaluates it in the flux kernel where that kernel's loader-wave form
-  // runs (les_in_flux_kernel); otherwise such a block runs variant 2, which keeps the gradient in HBM for a pointwise kernel.
-  // Element sizes that variant 3 does not fit run variant 2 as well (split_route)
-  variant = split_route(e, variant);
-  HFX_CHECK(!e->over_int_ready || variant == 3, "the split variant that keeps the gradients (fused 2, which LES without the in-kernel closure selects) has no over-integration");
+  // (an LES closure that variant 3 cannot evaluate in its flux kernel, and element sizes it does not fit, run variant 2)
+  const SplitPlan pl = split_plan(e, faces, nfb, variant);
+  HFX_CHECK(!e->over_int_ready || pl.variant == 3, "the split variant that keeps the gradients (fused 2, which LES without the in-kernel closure selects) has no over-integration");
   if (n_steps <= 0) return 0;
-  const int adv = e->ctx->params.adv_type;
-  const int nst = (adv == 0) ? 1 : (adv <= 2) ? 4 : (adv == 3) ? 5 : 14;
+  const int nst = n_rk_stages(e->ctx->params);
   if (hfx_eles_extrapolate_solution(e)) return 1;
   for (int s = 0; s < n_steps; s++)
   {
@@ -1030,7 +1032,7 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
         if (hfx_eles_calc_sgs_terms(e)) return 1;
         if (e->les.sgs_model == 3 && hfx_eles_extrapolate_solution(e)) return 1;
       }
-      if (split_stage(e, faces, nfb, rk, rk == nst - 1, 0, variant)) return 1;
+      if (split_stage(e, faces, nfb, rk, rk == nst - 1, Part::stage, pl)) return 1;
       if (e->shock_ready)
       {
         // the filter changes disu_upts(0) after the stage: redo the flux-point solution of the new state
@@ -1047,21 +1049,20 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
 {
   if (!e->fused || !e->fused->built)
     if (fused_build(e, faces, nfb)) return 1;
-  variant = split_route(e, variant);
-  const int adv = e->ctx->params.adv_type;
-  const int nst = (adv == 0) ? 1 : (adv <= 2) ? 4 : (adv == 3) ? 5 : 14;
+  const SplitPlan pl = split_plan(e, faces, nfb, variant);
+  const int nst = n_rk_stages(e->ctx->params);
   hipStream_t st = e->ctx->stream;
   // one set of events per repetition and ONE synchronisation at the end: a host synchronisation per stage let the queue
   // run dry, and the first kernel after it (the flux kernel) then measured 10 % slower than in the running pipeline
   // the parts of a stage in launch order; part 2 in two pieces when the block de-aliases (variant 3: the over-integration kernel,
   // then the flux kernel) or carries an LES closure (variant 2: the gradient kernel, then the SGS kernels) -- slot 4 of `ms`
-  const bool oi = variant == 3 && e->over_int_ready, sgs = variant == 2 && e->les_ready && e->ctx->params.viscous;
-  std::vector<int> parts = {1};
-  if (oi) { parts.push_back(5); parts.push_back(7); }
-  else if (sgs) { parts.push_back(8); parts.push_back(6); }
-  else parts.push_back(2);
-  parts.push_back(3);
-  parts.push_back(4);
+  const bool oi = pl.over_int != OverInt::none, sgs = pl.variant == 2 && e->les_ready && e->ctx->params.viscous;
+  std::vector<Part> parts = {Part::ldg};
+  if (oi) { parts.push_back(Part::over_int_only); parts.push_back(Part::flux_no_over_int); }
+  else if (sgs) { parts.push_back(Part::flux_no_sgs); parts.push_back(Part::sgs_only); }
+  else parts.push_back(Part::flux);
+  parts.push_back(Part::faces);
+  parts.push_back(Part::update);
   const int np = (int)parts.size();
   std::vector<hipEvent_t> ev((size_t)reps * (np + 1));
   for (auto &x : ev) HFX_HIP(hipEventCreate(&x));
@@ -1073,7 +1074,7 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
     for (int q = 0; q < np; q++)
     {
       HFX_HIP(hipEventRecord(ev[(np + 1) * r + q], st));
-      if (split_stage(e, faces, nfb, rk, rk == nst - 1, parts[q], variant)) return 1;
+      if (split_stage(e, faces, nfb, rk, rk == nst - 1, parts[q], pl)) return 1;
     }
     HFX_HIP(hipEventRecord(ev[(np + 1) * r + np], st));
   }
@@ -1083,15 +1084,15 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
     {
       float t = 0;
       HFX_HIP(hipEventElapsedTime(&t, ev[(np + 1) * r + q], ev[(np + 1) * r + q + 1]));
-      acc[parts[q]] += t;
+      acc[(int)parts[q]] += t;
     }
   for (auto &x : ev) (void)hipEventDestroy(x);
   for (int i = 0; i < 8; i++) ms[i] = 0.0;
-  ms[0] = acc[1] / reps;
-  ms[1] = (acc[2] + acc[7] + acc[8]) / reps; // the element kernel of part 2 alone
-  ms[2] = acc[3] / reps;
-  ms[3] = acc[4] / reps;
-  ms[4] = (acc[5] + acc[6]) / reps;          // over-integration kernel | SGS kernels
+  ms[0] = acc[(int)Part::ldg] / reps;
+  ms[1] = (acc[(int)Part::flux] + acc[(int)Part::flux_no_over_int] + acc[(int)Part::flux_no_sgs]) / reps; // part 2's element kernel alone
+  ms[2] = acc[(int)Part::faces] / reps;
+  ms[3] = acc[(int)Part::update] / reps;
+  ms[4] = (acc[(int)Part::over_int_only] + acc[(int)Part::sgs_only]) / reps; // over-integration kernel | SGS kernels
   if (e->fused->stamps)
   {
     long long h[64];
@@ -1109,19 +1110,14 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
     for (int q = 1; q <= 7; q++) fprintf(stderr, "%s%lld", q > 1 ? " " : "", h[3 * 16 + q] - h[3 * 16 + q - 1]);
     fprintf(stderr, "   (wait state | bar1 | issue state, wait metrics | bar2 | bar3 | issue metrics | bar4)  total %lld\n", h[3 * 16 + 7] - h[3 * 16]);
   }
-  const bool tensor = e->fused->tensor_ok && !e->ctx->opt.dictionary_rows;
-  snprintf(names, names_len, "%s%s",
-           variant == 3 ? (tensor ? "face_delta_kernel,split_flux_tensor_kernel,face_flux2_kernel,split_update_kernel"
-                                  : "face_delta_kernel,split_flux_kernel,face_flux2_kernel,split_update_kernel")
-                        : "face_delta_kernel,split_gradient_kernel,face_flux_kernel,split_residual_kernel",
-           oi ? (tensor_over_int_available(e) && e->ctx->contract_mode != HFX_CONTRACT_DENSE ? ",overint_tensor_kernel" : ",evaluate_invFlux_over_int (dense)")
-              : sgs ? ",sgsf_upts_kernel + ell_apply_kernel (SGS flux)" : "");
+  snprintf(names, names_len, "%s%s", pl.names, pl.extra_names);
   return 0;
 }
 
 void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant)
 {
-  variant = split_route(e, variant);
+  // (the plan without the face blocks: their boundary faces change only which arrays must be below 4 GiB)
+  const SplitPlan pl = split_plan(e, nullptr, 0, variant);
   // ALGORITHMIC HBM bytes per launch (doubles listed per element)
   const double nu = e->n_upts, nfp = e->n_fpts, nf = e->n_fields, nd = e->n_dims, ne = e->n_eles;
   for (int i = 0; i < 8; i++) bytes[i] = 0.0;
@@ -1129,14 +1125,14 @@ void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant)
   bytes[1] = ne * 8.0 * (nu * nf + nfp * nf + nu * (nd * nd + 1) + nfp * (nd * nd + 1) + nfp * nf * nd); // + grad_fpts w
   bytes[2] = ne * (8.0 * (nfp * nf + nfp * nf * nd + 0.5 * nfp * nd + nfp + nfp * nf) + 4.0 * nfp);   // disu, grad, normal(left), tdA r; tconf w
   bytes[3] = ne * 8.0 * (nu * nf + nu * (nd * nd + 1) + nfp * nf + 3 * nu * nf + nfp * nf);           // u, metrics, tconf, u1 r; u0,u1,disu w
-  if (variant == 2 && e->les_ready)
+  if (pl.variant == 2 && e->les_ready)
     // SGS flux at the solution points (u, corrected gradient, metrics r; sgsf_upts w) and its extrapolation (sgsf_upts r, sgsf_fpts w)
     bytes[4] = ne * 8.0 * (nu * nf + nu * nf * nd + nu * (nd * nd + 1) + 2 * nu * nf * nd + nfp * nf * nd);
-  if (variant == 3)
+  if (pl.variant == 3)
   {
     // u, delta, volume + flux-point metrics, own normals r ; div, norm_tdisf, Fn w
     // (norm_tdisf: the dictionary-row form only; the sum-factorised kernel folds opp_3 . norm_tdisf into div)
-    const double ntd = (e->fused && e->fused->tensor_ok && !e->ctx->opt.dictionary_rows) ? 0.0 : nfp * nf;
+    const double ntd = pl.flux != FluxForm::dictionary_rows ? 0.0 : nfp * nf;
     bytes[1] = ne * 8.0 * (nu * nf + nfp * nf + nu * (nd * nd + 1) + nfp * (nd * nd + 1) + nfp * nd + nu * nf + nfp * nf + ntd);
     bytes[2] = ne * (8.0 * (nfp * nf + nfp * nf + 0.5 * nfp * nd + nfp + nfp * nf) + 4.0 * nfp); // disu, Fn, normal(left), tdA r; tconf w
     bytes[3] = ne * 8.0 * (3 * nu * nf + nu + nfp * nf + ntd + 2 * nu * nf + nfp * nf);          // u0,u1,div,detjac,tconf(,ntd) r; u0,u1,disu w
@@ -1149,10 +1145,12 @@ void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant)
     if (e->over_int_ready)
     {
       // the flux kernel reads the de-aliased flux too; the over-integration kernel: u, the metric tensors at the cubature points r, tdisf w
-      bytes[1] += ne * 8.0 * nu * nf * nd;
-      bytes[4] = ne * 8.0 * (nu * nf + nd * nd * e->n_cubpts + nu * nf * nd);
+      // (folded: its contribution to the divergence, n_fields values per solution point)
+      const double tdisf = pl.oi_fold ? nu * nf : nu * nf * nd;
+      bytes[1] += ne * 8.0 * tdisf;
+      bytes[4] = ne * 8.0 * (nu * nf + nd * nd * e->n_cubpts + tdisf);
     }
-    if (e->fused && e->fused->gather_on)
+    if (pl.gather)
     {
       // the flux kernel reads the partners' flux-point solution (as many doubles as the corrections it no longer reads) and
       // a partner word per point; the pairwise LDG kernel is not launched

@@ -15,11 +15,11 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
                        int variant = 2);
 // algorithmic HBM bytes per launch of each kernel, same order
 void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant = 2);
-// which split variant a partitioned block runs: 2 (the reference's gradient arrays kept) when the context asks for it, the
-// block has an LES closure that variant 3 cannot evaluate, or variant 3 does not fit its element size (hexes from P6 on), else 3
-int split_variant(const hfx_eles *e);
-// an LES closure evaluated inside the flux kernel of variant 3 (needs the block's fused tables)
-bool les_in_flux_kernel(const hfx_eles *e);
+// what the split stage runs on a block when `requested_variant` (2 or 3) is asked for (split_common.hpp): its .variant is 2
+// (the reference's gradient arrays kept) when asked for, when the block has an LES closure that variant 3 cannot evaluate,
+// or when variant 3 does not fit its element size (hexes from P6 on), else 3.  Needs the block's fused tables (fused_build)
+struct SplitPlan;
+SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int requested_variant);
 // one phase of a split-path stage on a partitioned block (see hfx_stage_partitioned)
 int split_stage_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi,
                             int phase, int in_step, int first);
@@ -30,8 +30,9 @@ int mpi_launch_general(hfx_eles *e, hfx_inters *f, int what, const double *fn);
 // builds the block's fused tables for these face blocks unless they exist; non-zero (message in hfx_last_error) when the
 // block does not qualify for the split fused stage.  partitioned: flux points without a registered face are partition-face points
 int split_deferred_prepare(hfx_eles *e, hfx_inters *const *faces, int nfb, bool partitioned);
-// ONE stage of the split fused path (the variant split_variant(e) names) on a block whose disu_fpts belongs to the current
-// state; write_div: store div_tconf_upts; shock: shock_capture follows AdvanceSolution (src/HiFiLES.cpp:214-216)
+// ONE stage of the split fused path (the variant that split_plan names for the context's fused mode) on a block whose
+// disu_fpts belongs to the current state; write_div: store div_tconf_upts; shock: shock_capture follows AdvanceSolution
+// (src/HiFiLES.cpp:214-216)
 int split_deferred_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_step, bool write_div, bool shock);
 // the same on a partitioned block with the library's transport (comm.hip); start: this state's flux-point solution has not
 // been sent yet

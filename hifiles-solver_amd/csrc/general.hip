@@ -1482,7 +1482,7 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
   if (n_steps <= 0) return 0;
   hfx_ctx *ctx = eles[0]->ctx;
   const int adv = ctx->params.adv_type;
-  const int nst = (adv == 0) ? 1 : (adv <= 2) ? 4 : (adv == 3) ? 5 : 14;
+  const int nst = n_rk_stages(adv);
   // disu_fpts of the current state (the caller may have changed disu_upts since the last call)
   for (int i = 0; i < neb; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
@@ -1522,7 +1522,7 @@ int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *face
   if (general_prepare(eles, neb, faces, nfb)) return 1;
   hfx_ctx *ctx = eles[0]->ctx;
   const int adv = ctx->params.adv_type;
-  const int nst = (adv == 0) ? 1 : (adv <= 2) ? 4 : (adv == 3) ? 5 : 14;
+  const int nst = n_rk_stages(adv);
   hipStream_t st = ctx->stream;
   // one set of events per repetition and ONE synchronisation at the end: a host synchronisation per stage let the queue
   // run dry, and the first kernel after it (the flux kernel) then measured 10 % slower than in the running pipeline

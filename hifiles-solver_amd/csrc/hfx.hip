@@ -873,7 +873,7 @@ int hfx_eles_AdvanceSolution(hfx_eles *e, int in_step, int adv_type)
   hfx_ctx *ctx = e->ctx;
   HFX_CHECK(ctx->have_params, "parameters not set");
   HFX_CHECK(adv_type >= 0 && adv_type <= 4, "ERROR: Time integration type not recognised ... ");
-  const int nst = (adv_type == 0) ? 1 : (adv_type <= 2) ? 4 : (adv_type == 3) ? 5 : 14;
+  const int nst = n_rk_stages(adv_type);
   HFX_CHECK(in_step >= 0 && in_step < nst, "AdvanceSolution: stage %d out of range for adv_type %d", in_step, adv_type);
   HFX_DEFER(ctx, DM_ADVANCE_SOLUTION, e, nullptr, nullptr, in_step, adv_type);
   if (invalidate_fpts(e)) return 1;
@@ -1800,7 +1800,7 @@ int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *face
   hfx_ctx *ctx = eles[0]->ctx;
   HFX_CHECK(ctx->have_params, "parameters not set");
   const int adv = ctx->params.adv_type;
-  const int nst = (adv == 0) ? 1 : (adv <= 2) ? 4 : (adv == 3) ? 5 : 14; /* src/HiFiLES.cpp:143-150 */
+  const int nst = n_rk_stages(adv); /* src/HiFiLES.cpp:143-150 */
   if (fused == 4) return general_run_steps(eles, neb, faces, nfb, n_steps);
   HFX_CHECK(fused == 0 || neb == 1, "hfx_run_steps_blocks: the split fused stage (fused %d) takes one tensor-product element block; "
                                     "several blocks run per method (0) or through the general fused stage (4)", fused);
@@ -1839,7 +1839,7 @@ int hfx_time_methods(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps, d
   HFX_CHECK(e->ctx->have_params, "parameters not set");
   hipStream_t st = e->ctx->stream;
   const int adv = e->ctx->params.adv_type;
-  const int nst = (adv == 0) ? 1 : (adv <= 2) ? 4 : (adv == 3) ? 5 : 14;
+  const int nst = n_rk_stages(adv);
   const int viscous = e->ctx->params.viscous;
   hipEvent_t ev[HFX_N_TIMED_METHODS + 1];
   for (auto &x : ev) HFX_HIP(hipEventCreate(&x));

@@ -279,6 +279,9 @@ namespace hfx
 int calc_time_step(hfx_eles *e, hfx_comm *comm);
 // run_input.ramp_counter++ after a time step for the boundary blocks with a ramping group (src/HiFiLES.cpp:224-225)
 void advance_ramp_counters(hfx_inters *const *faces, int nfb);
+// RK stages per time step of adv_type (src/HiFiLES.cpp:143-150)
+inline int n_rk_stages(int adv_type) { return (adv_type == 0) ? 1 : (adv_type <= 2) ? 4 : (adv_type == 3) ? 5 : 14; }
+inline int n_rk_stages(const hfx_params &p) { return n_rk_stages(p.adv_type); }
 } // namespace hfx
 
 namespace hfx

@@ -1,6 +1,6 @@
-// split_common.hpp -- tables, element geometry and device helpers shared by the split fused kernels
-// (device code of the split fused stage; included by fused_hex.hip only -- one translation unit, so that every kernel is
-// instantiated once)
+// split_common.hpp -- tables, element geometry and device helpers shared by the split fused kernels, and the plan of a split
+// stage (SplitPlan).  The kernels themselves (split2_kernels.hpp, split3_kernels.hpp) are included by fused_hex.hip only -- one
+// translation unit, so that every kernel is instantiated once; comm.hip and deferred.hip read the plan.
 #pragma once
 #include <vector>
 
@@ -37,8 +37,63 @@ struct FusedData
   long n_list_b = 0, n_list_i = 0;
   long n_list_i1 = 0; // the flux kernel takes the others in two parts: upd_list_i[0 .. n_list_i1) and the rest
   double *les_len2 = nullptr;                // (n_upts, n_eles) squared length scale of the LES closure evaluated in the flux kernel
-  bool gather_on = false;                    // the last stage formed the interior LDG corrections in the flux kernel (no face_delta launch)
   bool built = false;
+};
+
+// the flux kernel of variant 3: the loader-wave form of split_flux_tensor_kernel, its register-pipeline forms, or the
+// dictionary-row kernel split_flux_kernel
+enum class FluxForm { loader_wave, register_pipeline, dictionary_rows };
+// where the de-aliased flux of over-integration comes from: the sum-factorised kernel's result folded into the divergence, the
+// same kernel's tdisf_upts, or the dense contraction
+enum class OverInt { none, folded_tensor, tensor, dense };
+
+// What the split fused stage runs on one block for one request (split_plan, fused_hex.hip): every form decided once, from the
+// options, the block's fused tables, its flags and its array sizes.  Launch geometry (grids, element order, SIMD roles) is not
+// part of it.
+struct SplitPlan
+{
+  int variant = 2;              // the variant that runs (a request for 3 falls back to 2)
+  bool les_in_flux = false;     // the LES closure is evaluated in the flux kernel of variant 3
+  // the four "every array below 4 GiB" tests, each with its own count of the largest array
+  bool les_fits_4gib = false;
+  bool gather_fits_4gib = false;
+  bool flux_buf_fits_4gib = false;
+  bool update_fits_4gib = false;
+  // variant 3
+  FluxForm flux = FluxForm::dictionary_rows;
+  bool oi = false, les = false; // loader wave: the OI / LES flags (GA = gather); register pipeline: OI
+  int wv = 2;                   // register pipeline: WV
+  bool buf = false;             // register pipeline: BUF
+  bool gather = false;          // the flux kernel forms the interior LDG corrections itself (loader wave: GA)
+  bool face_delta = false;      // face_delta_kernel forms them (a viscous block without `gather`)
+  bool oi_fold = false;         // the over-integration kernel hands over its result folded into the divergence
+  OverInt over_int = OverInt::none;
+  bool update_buf = false;      // split_update_kernel with buffer addressing
+  bool bdy_grad = false;        // the flux kernel stores the gradient at the boundary points (a viscous block with boundary faces)
+  // a partitioned block: the projected viscous flux on the wire; the flux kernel / the update on element lists may run
+  bool projected = false, split_flux = false, split_update = false;
+  // hfx_time_fused_kernels: the stage's four kernels, and what part 2 adds (the over-integration kernel, the SGS kernels)
+  const char *names = "", *extra_names = "";
+};
+
+// The parts of a stage that split_stage runs: the whole stage, or one of its pieces (the phases of a partitioned block, the
+// launches timed on their own).  The timing parts index the accumulators of split_time_kernels.
+enum class Part
+{
+  stage,            // the whole stage
+  ldg,              // the LDG common solution at the boundary and interior faces
+  flux,             // the element kernel: over-integration + flux kernel (variant 3) | gradient kernel + SGS kernels (variant 2)
+  faces,            // the common fluxes at the boundary and interior faces
+  update,           // the update (variant 3) | residual (variant 2) kernel
+  over_int_only,    // timing: the over-integration kernel of `flux` alone
+  sgs_only,         // timing: the SGS kernels of `flux` (variant 2 with an LES closure) alone
+  flux_no_over_int, // timing: `flux` without the over-integration kernel
+  flux_no_sgs,      // timing: `flux` without the SGS kernels
+  flux_list_1,      // the flux kernel on the first half of the elements without partition-face points (upd_list_i)
+  flux_list_b,      // ... on the elements with partition-face points (upd_list_b)
+  flux_list_2,      // ... on the second half of upd_list_i
+  update_list_b,    // the update on the elements with partition-face points
+  update_list_i,    // the update on the others (behind the buffer swap of update_list_b)
 };
 
 constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }

@@ -211,6 +211,31 @@ def test_over_integration_folded_into_the_divergence(dims, order, viscous):
     assert np.isfinite(got[1]).all()
 
 
+def test_over_integration_kernel_bytes_follow_the_fold():
+    """hfx_fused_kernel_bytes prices the over-integration form the stage runs: folded (over_int_fold 1), the over-integration
+    kernel writes and the flux kernel reads n_fields doubles per solution point; unfolded (0), n_fields * n_dims, and the
+    pairwise LDG kernel runs again (the register-pipeline flux kernel does not form the corrections)"""
+    order, oi_order = 4, 6
+    c = H.Case([4, 4, 4], order=order, amp=0.1, viscous=1, over_int=1, over_int_order=oi_order)
+    c.to_device(0)
+    c.run_steps_lib(1, fused=3)  # builds the block's fused tables
+    ctx, e = c.handles()[0], c.handles()[1]
+    N = order + 1
+    nu, nfp, nf, nd, ne, ncub = N ** 3, 6 * N ** 2, 5, 3, 64, (oi_order + 1) ** 3
+    got = {}
+    for fold in (1, 0):
+        hfx.Context.set_option(_Ctx(ctx), "over_int_fold", fold)
+        b = (C.c_double * 8)()
+        hfx.check(hfx.lib().hfx_fused_kernel_bytes(e, b))
+        got[fold] = list(b)
+        tdisf = nu * nf if fold else nu * nf * nd
+        assert got[fold][4] == ne * 8.0 * (nu * nf + nd * nd * ncub + tdisf), fold
+    assert got[1][0] == 0.0 and got[0][0] == ne * (8.0 * (2 * nfp * nf) + 4.0 * nfp + nfp * 0.5)
+    # the flux kernel: the de-aliased flux it reads, and the partner words of the corrections it forms when folded
+    assert got[0][1] - got[1][1] == ne * 8.0 * (nu * nf * nd - nu * nf) - ne * 4.0 * nfp
+    c.close()
+
+
 def test_config5_ingredients_full_size_properties():
     """BASELINE.json configs[4]'s ingredients at bench size (tools/bench_config5.sh, the `config5_overint_shock` leg of bench.py):
     32^3 P4 hexes with over-integration (7 cubature points per direction) and shock capturing after every stage.  The split

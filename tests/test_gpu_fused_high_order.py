@@ -1,6 +1,6 @@
 """Hexahedra of orders 6 and 7 on the split fused stage: 343 / 512 solution points per element take the wide row entries of
 variant 2 (csrc/split_common.hpp, Geo::WIDE), and a request for variant 3 -- whose flux kernel does not fit one such element
-in LDS -- runs variant 2 (split_route, csrc/fused_hex.hip).  Against the per-method path, the genuine reference's fixtures,
+in LDS -- runs variant 2 (split_plan, csrc/fused_hex.hip).  Against the per-method path, the genuine reference's fixtures,
 the host mirror's unchanged loop and the undivided block of a self-partitioned run."""
 import ctypes as C
 import os
