@@ -235,13 +235,17 @@ struct StageTimers
   }
 };
 
-static int check_partition_blocks(hfx_eles *e, hfx_inters *const *mpi_faces, int n_mpi, hfx_comm *comm)
+// the partition-face blocks of a partitioned fused stage on these element blocks (split: one; general: several)
+static int check_partition_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *mpi_faces, int n_mpi, hfx_comm *comm)
 {
-  HFX_CHECK(comm && comm->ctx == e->ctx, "the communicator belongs to another context");
+  HFX_CHECK(comm && comm->ctx == eles[0]->ctx, "the communicator belongs to another context");
   for (int b = 0; b < n_mpi; b++)
   {
     const hfx_inters *f = mpi_faces[b];
-    HFX_CHECK(f->is_mpi && f->left == e, "bad partition-face block");
+    HFX_CHECK(f->is_mpi, "bad partition-face block");
+    bool mine = false;
+    for (int i = 0; i < neb; i++) mine = mine || f->left == eles[i];
+    HFX_CHECK(mine, "a partition-face block belongs to an element block that is not part of this call");
     int listed = 0;
     for (int c : f->seg_count) listed += c;
     HFX_CHECK(listed == f->n_inters, "partition-face block: %d of %d faces have a neighbour (hfx_mpi_inters_set_neighbours)", listed,
@@ -261,79 +265,66 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
 {
   hfx_ctx *ctx = e->ctx;
   const bool visc = ctx->params.viscous != 0;
-  if (split_deferred_prepare(e, int_faces, n_int, true)) return 1; // (the plan below depends on the block's fused tables)
-  const SplitPlan pl = split_plan(e, int_faces, n_int, ctx->fused_mode); // projected: variant 3 sends the projected viscous flux
+  PartitionedSplit s; // the steps of this stage, and its plan
+  if (s.init(e, int_faces, n_int, mpi_faces, n_mpi, rk)) return 1;
+  const SplitPlan &pl = s.pl; // projected: variant 3 sends the projected viscous flux
   // third message: the SGS flux (src/solver.cpp:168-178,203-206) -- variant 2 only; in variant 3 it is part of the projected flux
   const bool les = e->les_ready && !pl.projected;
   hipStream_t st = ctx->stream, cs = comm->stream;
-  auto phase = [&](int ph, int stage, int first) {
-    return split_stage_partitioned(e, int_faces, n_int, mpi_faces, n_mpi, ph, stage, first);
-  };
   // (the timed form keeps every kernel of a phase on the compute stream, so that its events bracket the phase)
   const bool beside = ctx->opt.comm_stream_faces && pl.projected && !les && visc && T == nullptr;
   if (start)
   {
-    if (phase(0, rk, 1)) return 1;
-    if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1; // later stages: started after phase 4 of the previous one
+    if (hfx_eles_extrapolate_solution(e)) return 1;
+    if (s.pack_solution(st)) return 1;
+    if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1; // later stages: started after the update of the previous one
   }
   if (beside)
   {
     // ---- partition-face kernels and exchanges on the communication stream, in its order; the compute stream meets it
     // at two events per stage: before the flux kernel (LDG corrections at the partition faces are in place) and before
     // the update kernel (common fluxes at the partition faces are in place)
-    if (phase(1, rk, 0)) return 1; // interior LDG pairs                                      | compute stream
-    ctx->mpi_stream = cs;
-    const int r5 = phase(5, rk, 0); // LDG corrections at the partition faces (behind the receive) | communication stream
-    ctx->mpi_stream = nullptr;
-    if (r5) return 1;
+    if (s.interior_ldg()) return 1;
+    if (s.partition_ldg(cs)) return 1; // (behind the receive)
     HFX_HIP(hipEventRecord(comm->received[0], cs));
     // the flux kernel in three launches (option split_flux): half of the elements WITHOUT partition-face points first -- they
     // need nothing from the neighbours, so the solution exchange runs beside them --, then the elements with, whose projected
     // fluxes then leave beside the other half (and the interior common-flux kernel)
     const bool split_flux = ctx->opt.split_flux && pl.split_flux && n_mpi > 0;
-    if (split_flux && phase(13, rk, 0)) return 1;
+    if (split_flux && s.element_kernel(Part::flux_list_1)) return 1;
     if (wait_exchange(comm, 0, n_mpi)) return 1;
-    if (split_flux ? phase(14, rk, 0) : phase(6, rk, 0)) return 1; // gradient + flux kernel
+    if (s.element_kernel(split_flux ? Part::flux_list_b : Part::flux)) return 1;
     HFX_HIP(hipEventRecord(comm->packed[1], st));
     HFX_HIP(hipStreamWaitEvent(cs, comm->packed[1], 0));
-    ctx->mpi_stream = cs;
-    int rc = phase(7, rk, 0); // pack the projected flux
-    if (!rc) rc = start_exchange(comm, mpi_faces, n_mpi, 1, true, true);
-    if (!rc) rc = phase(8, rk, 0); // common fluxes at the partition faces
-    ctx->mpi_stream = nullptr;
-    if (rc) return 1;
+    if (s.pack_projected_flux(cs)) return 1;
+    if (start_exchange(comm, mpi_faces, n_mpi, 1, true, true)) return 1;
+    if (s.partition_common_fluxes(cs)) return 1;
     HFX_HIP(hipEventRecord(comm->received[1], cs));
-    if (split_flux && phase(15, rk, 0)) return 1;
-    if (phase(3, rk, 0)) return 1; // interior common fluxes                                  | compute stream
+    if (split_flux && s.element_kernel(Part::flux_list_2)) return 1;
+    if (s.interior_common_fluxes()) return 1;
     if (wait_exchange(comm, 1, n_mpi)) return 1;
     // the update: first the elements with partition-face points, whose new flux-point solution is packed and sent (communication
     // stream) while the others are updated -- the exchange the next stage's flux kernel waits for is hidden behind them
     const bool split_update = ctx->opt.split_update && pl.split_update && n_mpi > 0;
-    if (split_update ? phase(11, rk, 0) : phase(9, rk, 0)) return 1; // update (+ shock capturing)
+    if (s.update(split_update ? Part::update_list_b : Part::update)) return 1; // (the whole update: + shock capturing)
     HFX_HIP(hipEventRecord(comm->packed[0], st));
     HFX_HIP(hipStreamWaitEvent(cs, comm->packed[0], 0));
-    ctx->mpi_stream = cs;
-    rc = phase(10, rk, 0); // pack the new flux-point solution
-    if (!rc) rc = start_exchange(comm, mpi_faces, n_mpi, 0, false, true);
-    ctx->mpi_stream = nullptr;
-    if (!rc && split_update) rc = phase(12, rk, 0);
-    return rc;
+    if (s.pack_solution(cs)) return 1;
+    if (start_exchange(comm, mpi_faces, n_mpi, 0, false, true)) return 1;
+    return split_update ? s.update(Part::update_list_i) : 0;
   }
+  // ---- everything on the compute stream (optionally timed): the five phases of hfx_stage_partitioned with the exchanges between
   if (T) HFX_HIP(hipEventRecord(T->ph[0], st));
-  if (phase(1, rk, 0)) return 1;
+  if (visc && s.interior_ldg()) return 1;
   if (T) HFX_HIP(hipEventRecord(T->ph[1], st));
   if (wait_exchange(comm, 0, n_mpi)) return 1;
-  const bool pieces = T && pl.projected && visc; // phase 2 in its three pieces, the element kernel bracketed on its own
-  if (pieces)
-  {
-    if (phase(5, rk, 0)) return 1;
-    HFX_HIP(hipEventRecord(T->fk[0], st));
-    if (phase(6, rk, 0)) return 1;
-    HFX_HIP(hipEventRecord(T->fk[1], st));
-    if (phase(7, rk, 0)) return 1;
-  }
-  else if (phase(2, rk, 0))
-    return 1;
+  const bool pieces = T && pl.projected && visc; // the element kernel bracketed on its own
+  if (visc && s.partition_ldg(st)) return 1;
+  if (pieces) HFX_HIP(hipEventRecord(T->fk[0], st));
+  if ((pl.projected || visc) && s.element_kernel()) return 1;
+  if (pieces) HFX_HIP(hipEventRecord(T->fk[1], st));
+  if (visc && (pl.projected ? s.pack_projected_flux(st) : s.pack_gradient(st))) return 1;
+  if (visc && les && s.pack_sgs_flux(st)) return 1;
   if (visc)
   {
     if (T) HFX_HIP(hipEventRecord(T->x1[0], st));
@@ -342,11 +333,14 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
     if (T) HFX_HIP(hipEventRecord(T->x1[1], cs));
   }
   if (T) HFX_HIP(hipEventRecord(T->ph[2], st));
-  if (phase(3, rk, 0)) return 1;
+  if (s.interior_common_fluxes()) return 1;
+  if (!pl.projected && s.partition_common_invflux(st)) return 1;
   if (T) HFX_HIP(hipEventRecord(T->ph[3], st));
   if (visc && wait_exchange(comm, 1, n_mpi)) return 1;
   if (visc && les && wait_exchange(comm, 2, n_mpi)) return 1;
-  if (phase(4, rk, 0)) return 1;
+  if (pl.projected ? s.partition_common_fluxes(st) : (visc && s.partition_common_viscflux(st))) return 1;
+  if (s.update()) return 1; // (+ shock capturing)
+  if (s.pack_solution(st)) return 1;
   if (T) HFX_HIP(hipEventRecord(T->x0[0], st));
   if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1;
   if (T)
@@ -383,7 +377,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
 int partitioned_stage_deferred(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi,
                                hfx_comm *comm, int rk, bool start)
 {
-  if (check_partition_blocks(e, mpi_faces, n_mpi, comm)) return 1;
+  if (check_partition_blocks(&e, 1, mpi_faces, n_mpi, comm)) return 1;
   return partitioned_stage(e, int_faces, n_int, mpi_faces, n_mpi, comm, rk, start, nullptr);
 }
 
@@ -400,52 +394,41 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
 {
   HFX_CHECK(neb > 0 && comm, "general partitioned stage: bad argument");
   hfx_ctx *ctx = eles[0]->ctx;
-  HFX_CHECK(comm->ctx == ctx, "the communicator belongs to another context");
+  if (check_partition_blocks(eles, neb, mpi_faces, n_mpi, comm)) return 1;
   const bool visc = ctx->params.viscous != 0;
   const int nst = n_rk_stages(ctx->params);
   // the blocks' tables are built with ALL face blocks (every flux point needs its face)
   std::vector<hfx_inters *> all(int_faces, int_faces + n_int);
-  for (int b = 0; b < n_mpi; b++)
-  {
-    const hfx_inters *f = mpi_faces[b];
-    HFX_CHECK(f->is_mpi, "bad partition-face block");
-    bool mine = false;
-    for (int i = 0; i < neb; i++) mine = mine || f->left == eles[i];
-    HFX_CHECK(mine, "a partition-face block belongs to an element block that is not part of this call");
-    int listed = 0;
-    for (int c : f->seg_count) listed += c;
-    HFX_CHECK(listed == f->n_inters, "partition-face block: %d of %d faces have a neighbour (hfx_mpi_inters_set_neighbours)", listed, f->n_inters);
-    all.push_back(mpi_faces[b]);
-  }
-  if (general_deferred_prepare(eles, neb, all.data(), (int)all.size())) return 1;
-  auto mpi_all = [&](int what) -> int {
+  all.insert(all.end(), mpi_faces, mpi_faces + n_mpi);
+  if (general_prepare(eles, neb, all.data(), (int)all.size())) return 1;
+  auto mpi_all = [&](MpiKernel k) -> int {
     for (int b = 0; b < n_mpi; b++)
-      if (mpi_launch_general(mpi_faces[b]->left, mpi_faces[b], what, general_fn_fpts(mpi_faces[b]->left))) return 1;
+      if (mpi_launch_general(mpi_faces[b]->left, mpi_faces[b], k, general_fn_fpts(mpi_faces[b]->left))) return 1;
     return 0;
   };
-  auto part = [&](int which) { return general_stage_part(eles, neb, all.data(), (int)all.size(), rk, rk == nst - 1, which); };
+  auto part = [&](GeneralPart which) { return general_stage(eles, neb, all.data(), (int)all.size(), rk, rk == nst - 1, which); };
   if (start)
   {
-    if (mpi_all(0)) return 1;
+    if (mpi_all(MpiKernel::pack_solution)) return 1;
     if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1;
   }
-  if (part(1)) return 1;
+  if (part(GeneralPart::ldg)) return 1;
   if (wait_exchange(comm, 0, n_mpi)) return 1;
-  if (visc && mpi_all(1)) return 1;
-  if (part(2)) return 1;
+  if (visc && mpi_all(MpiKernel::ldg_delta)) return 1;
+  if (part(GeneralPart::flux)) return 1;
   if (visc)
   {
-    if (mpi_all(5)) return 1;
+    if (mpi_all(MpiKernel::pack_projected_flux)) return 1;
     if (start_exchange(comm, mpi_faces, n_mpi, 1, true)) return 1;
   }
-  if (part(3)) return 1;
+  if (part(GeneralPart::faces)) return 1;
   if (visc && wait_exchange(comm, 1, n_mpi)) return 1;
-  if (mpi_all(6)) return 1;
-  if (part(4)) return 1;
+  if (mpi_all(MpiKernel::common_flux_projected)) return 1;
+  if (part(GeneralPart::update)) return 1;
   // eles::shock_capture (src/HiFiLES.cpp:214-216) before the new flux-point solution is packed: the filter, then the flux-point
   // values of the filtered state
   if (shock && general_shock_capture(eles, neb)) return 1;
-  if (mpi_all(0)) return 1;
+  if (mpi_all(MpiKernel::pack_solution)) return 1;
   return start_exchange(comm, mpi_faces, n_mpi, 0, false);
 }
 
@@ -454,7 +437,7 @@ static int run_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int,
                            hfx_comm *comm, int n_steps, int n_stages_total, StageTimers *T)
 {
   hfx_ctx *ctx = e->ctx;
-  if (check_partition_blocks(e, mpi_faces, n_mpi, comm)) return 1;
+  if (check_partition_blocks(&e, 1, mpi_faces, n_mpi, comm)) return 1;
   const int nst = n_rk_stages(ctx->params);
   // a partitioned fused stage of the deferred path may have left this state's flux-point solution on its way already: the
   // first stage takes it instead of posting it again (the messages a rank posts follow its calls, not what ran deferred)

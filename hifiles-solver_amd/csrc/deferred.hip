@@ -193,7 +193,7 @@ static bool match_stage(hfx_ctx *ctx, const std::vector<DeferCall> &log, DeferPl
 static void make_plan(hfx_ctx *ctx, const std::vector<DeferCall> &log, DeferPlan &P)
 {
   P.signature = log;
-  P.kind = 0;
+  P.kind = DeferPlan::Kind::replay;
   if (!match_stage(ctx, log, P)) return;
   const bool mpi = !P.mpi_faces.empty();
   hfx_eles *e0 = P.eles[0];
@@ -212,20 +212,20 @@ static void make_plan(hfx_ctx *ctx, const std::vector<DeferCall> &log, DeferPlan
       return;
     }
     if (e0->over_int_ready && split_plan(e0, P.faces.data(), (int)P.faces.size(), ctx->fused_mode).variant != 3) { P.why = "the split variant that keeps the gradients (LES, fused mode 2) has no over-integration"; return; }
-    P.kind = mpi ? 2 : 1;
+    P.kind = mpi ? DeferPlan::Kind::split_partitioned : DeferPlan::Kind::split;
     return;
   }
 
   {
     std::vector<hfx_inters *> all = P.faces;
     all.insert(all.end(), P.mpi_faces.begin(), P.mpi_faces.end());
-    if (general_deferred_prepare(P.eles.data(), (int)P.eles.size(), all.data(), (int)all.size()))
+    if (general_prepare(P.eles.data(), (int)P.eles.size(), all.data(), (int)all.size()))
     {
       P.why = hfx_last_error();
       return;
     }
   }
-  P.kind = mpi ? 4 : 3;
+  P.kind = mpi ? DeferPlan::Kind::general_partitioned : DeferPlan::Kind::general;
 }
 
 // arrays a fused stage of this kind leaves with the reference's values (given write_div)
@@ -293,28 +293,29 @@ static int run_fused(hfx_ctx *ctx, const DeferPlan &P, int in_step, bool write_d
   const int nfb = (int)P.faces.size();
   switch (P.kind)
   {
-  case 1:
+  case DeferPlan::Kind::split:
     if (split_deferred_stage(e0, faces, nfb, in_step, write_div, P.shock)) return 1;
     break;
-  case 2:
+  case DeferPlan::Kind::split_partitioned:
     if (partitioned_stage_deferred(e0, faces, nfb, P.mpi_faces.data(), (int)P.mpi_faces.size(), P.comm, in_step, start)) return 1;
     break;
-  case 3:
-    if (general_deferred_stage(P.eles.data(), (int)P.eles.size(), faces, nfb, in_step, write_div)) return 1;
+  case DeferPlan::Kind::general:
+    if (general_prepare(P.eles.data(), (int)P.eles.size(), faces, nfb)) return 1; // (no-op unless the registration changed)
+    if (general_stage(P.eles.data(), (int)P.eles.size(), faces, nfb, in_step, write_div, GeneralPart::stage)) return 1;
     if (P.shock && general_shock_capture(P.eles.data(), (int)P.eles.size())) return 1;
     break;
-  case 4:
+  case DeferPlan::Kind::general_partitioned:
     if (general_partitioned_stage(P.eles.data(), (int)P.eles.size(), faces, nfb, P.mpi_faces.data(), (int)P.mpi_faces.size(), P.comm, in_step, start, P.shock))
       return 1;
     break;
-  default:
-    HFX_CHECK(false, "deferred execution: plan of unknown kind %d", P.kind);
+  case DeferPlan::Kind::replay:
+    HFX_CHECK(false, "deferred execution: a record that replays has no fused stage");
   }
   const unsigned fresh = fresh_after(P, write_div);
   for (hfx_eles *e : P.eles)
   {
     e->fpts_valid = true;
-    e->fpts_sent = P.kind == 2 || P.kind == 4;
+    e->fpts_sent = P.partitioned();
     e->sent_on = e->fpts_sent ? P.comm->serial : 0;
     e->sent_blocks = 0;
     for (const hfx_inters *f : P.mpi_faces) e->sent_blocks += f->left == e;
@@ -374,14 +375,14 @@ int defer_flush(hfx_ctx *ctx, unsigned need)
     plan = &d.plans.back();
     make_plan(ctx, log, *plan);
   }
-  if (plan->kind != 0)
+  if (plan->kind != DeferPlan::Kind::replay)
   {
     int in_step = 0;
     for (const DeferCall &c : log)
       if (c.method == DM_ADVANCE_SOLUTION) in_step = c.i0;
     // div_tconf_upts is stored at the last stage of a step (where the monitors read it) or when this flush is for it
     // (the partitioned stage stores it at the last stage only)
-    const bool write_div = in_step == n_rk_stages(ctx->params) - 1 || (plan->kind != 2 && plan->kind != 4 && (need & (1u << HFX_DIV_TCONF_UPTS)) != 0);
+    const bool write_div = in_step == n_rk_stages(ctx->params) - 1 || (!plan->partitioned() && (need & (1u << HFX_DIV_TCONF_UPTS)) != 0);
     if ((need & ~fresh_after(*plan, write_div)) == 0)
     {
       d.n_fused++;

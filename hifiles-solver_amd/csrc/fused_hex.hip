@@ -1,6 +1,6 @@
 // fused_hex.hip -- the split fused stage for tensor-product elements (hexes, quads): table setup, launchers, RK loops.
 // Kernels: split_common.hpp (shared helpers), split2_kernels.hpp (variant 2), split3_kernels.hpp (variant 3, the default),
-// split_partitioned.hpp (the five phases of a partitioned block).
+// split_partitioned.hpp (the steps of a stage on a partitioned block).
 //
 // One RK stage = the 17 calls of CalcResidual + AdvanceSolution
 // (/root/reference/src/solver.cpp:50-223, src/HiFiLES.cpp:201-217).  Executed call by
@@ -873,7 +873,7 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
     // write norm_tconf at disjoint points
     bool any_bdy_faces = false;
     for (int b = 0; b < nfb; b++) any_bdy_faces = any_bdy_faces || (faces[b]->is_bdy && faces[b]->n_inters > 0);
-    const bool beside = any_bdy_faces && opt.bdy_beside && e->ctx->mpi_stream == nullptr;
+    const bool beside = any_bdy_faces && opt.bdy_beside;
     if (beside && side_stream_fork(e->ctx)) return 1;
     for (int b = 0; b < nfb; b++)
       if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], P.viscous ? 1 : 0, 1)) return 1;

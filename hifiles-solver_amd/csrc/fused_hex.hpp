@@ -20,12 +20,20 @@ void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant = 2);
 // or when variant 3 does not fit its element size (hexes from P6 on), else 3.  Needs the block's fused tables (fused_build)
 struct SplitPlan;
 SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int requested_variant);
-// one phase of a split-path stage on a partitioned block (see hfx_stage_partitioned)
-int split_stage_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi,
-                            int phase, int in_step, int first);
-// one of the one-sided partition-face kernels (kernels_mpi.hpp: 0 pack the solution, 1 LDG corrections, 5 pack Fn, 6 common flux
-// from u and Fn) on a block of the GENERAL fused stage, whose projected viscous flux is `fn`
-int mpi_launch_general(hfx_eles *e, hfx_inters *f, int what, const double *fn);
+// the one-sided partition-face kernels (kernels_mpi.hpp)
+enum class MpiKernel
+{
+  pack_solution,         // the flux-point solution into the send buffer
+  ldg_delta,             // LDG corrections from both sides' solution
+  pack_gradient,         // the corrected gradient into the send buffer
+  common_invflux,        // inviscid common flux
+  common_viscflux,       // viscous common flux from both sides' gradients
+  pack_projected_flux,   // each side's viscous flux projected on its own normal (Fn) into the send buffer
+  common_flux_projected, // common flux from both sides' solution and Fn
+  pack_sgs_flux,         // the physical SGS flux into the send buffer
+};
+// one of them on a block of the GENERAL fused stage, whose projected viscous flux is `fn` (compute stream)
+int mpi_launch_general(hfx_eles *e, hfx_inters *f, MpiKernel k, const double *fn);
 // ---- the deferred scheduler's pieces (deferred.hip) ----
 // builds the block's fused tables for these face blocks unless they exist; non-zero (message in hfx_last_error) when the
 // block does not qualify for the split fused stage.  partitioned: flux points without a registered face are partition-face points

@@ -1316,13 +1316,14 @@ static int launch_element_kernels(hfx_eles *e, const GenArgs &a, bool flux)
   return launch_element_kernels_t<W, 0, 0>(e, a, flux);
 }
 
-// which: 0 the whole stage, 1 .. 4 one of its four parts (for the per-kernel timing)
-static int general_stage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool last_stage, int which)
+// `faces` may hold partition-face blocks (they take part in the build -- every flux point needs its face -- and are skipped by
+// the pairwise loops)
+int general_stage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool last_stage, GeneralPart which)
 {
   hfx_ctx *ctx = eles[0]->ctx;
   const Phys P = ctx->phys();
   hipStream_t st = ctx->stream;
-  if (P.viscous && (which == 0 || which == 1))
+  if (P.viscous && (which == GeneralPart::stage || which == GeneralPart::ldg))
     for (int b = 0; b < nfb; b++)
     {
       if (faces[b]->is_bdy)
@@ -1342,7 +1343,7 @@ static int general_stage(hfx_eles *const *eles, int neb, hfx_inters *const *face
       if (a.npairs == 0) continue;
       hipLaunchKernelGGL(gface_delta_kernel, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, st, a);
     }
-  if (which == 0 || which == 2)
+  if (which == GeneralPart::stage || which == GeneralPart::flux)
     for (int i = 0; i < neb; i++)
     {
       // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
@@ -1355,7 +1356,7 @@ static int general_stage(hfx_eles *const *eles, int neb, hfx_inters *const *face
                                                                          : launch_element_kernels<8>(eles[i], a, true))
         return 1;
     }
-  if (which == 0 || which == 3)
+  if (which == GeneralPart::stage || which == GeneralPart::faces)
   {
     // boundary faces beside the interior ones: both need the flux kernels' results and write norm_tconf at disjoint points
     bool any_bdy = false;
@@ -1392,7 +1393,7 @@ static int general_stage(hfx_eles *const *eles, int neb, hfx_inters *const *face
     if (flush()) return 1;
     if (beside && side_stream_wait(ctx)) return 1;
   }
-  if (which == 0 || which == 4)
+  if (which == GeneralPart::stage || which == GeneralPart::update)
   {
     for (int i = 0; i < neb; i++)
     {
@@ -1411,7 +1412,7 @@ static int general_stage(hfx_eles *const *eles, int neb, hfx_inters *const *face
   return 0;
 }
 
-static int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb)
+int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb)
 {
   hfx_ctx *ctx = eles[0]->ctx;
   for (int i = 0; i < neb; i++)
@@ -1444,24 +1445,7 @@ static int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *fa
   return 0;
 }
 
-// the pieces of a stage for the partitioned driver (comm.hip): which = 1 .. 4 as in general_time_kernels; `faces` may hold
-// partition-face blocks (they take part in the build -- every flux point needs its face -- and are skipped by the pairwise loops)
-int general_stage_part(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool write_div, int which)
-{
-  return general_stage(eles, neb, faces, nfb, in_step, write_div, which);
-}
 const double *general_fn_fpts(const hfx_eles *e) { return e->general ? ((const GeneralData *)e->general)->fn_fpts : nullptr; }
-
-int general_deferred_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb)
-{
-  return general_prepare(eles, neb, faces, nfb);
-}
-
-int general_deferred_stage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool write_div)
-{
-  if (general_prepare(eles, neb, faces, nfb)) return 1; // (no-op unless the registration changed)
-  return general_stage(eles, neb, faces, nfb, in_step, write_div, 0);
-}
 
 // eles::shock_capture behind a general fused stage (src/HiFiLES.cpp:214-216): the modal filter changes the state of the elements
 // the sensor marks, so the flux-point values the update kernel left for the next stage are extrapolated again
@@ -1509,7 +1493,7 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
             if (hfx_eles_calc_sgs_terms(eles[i])) return 1;
             if (eles[i]->les.sgs_model == 3 && hfx_eles_extrapolate_solution(eles[i])) return 1;
           }
-      if (general_stage(eles, neb, faces, nfb, rk, rk == nst - 1, 0)) return 1;
+      if (general_stage(eles, neb, faces, nfb, rk, rk == nst - 1, GeneralPart::stage)) return 1;
       if (general_shock_capture(eles, neb)) return 1;
     }
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
@@ -1534,10 +1518,11 @@ int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *face
   for (int r = 0; r < reps; r++)
   {
     const int rk = r % nst;
-    for (int w = 1; w <= 4; w++)
+    const GeneralPart parts[4] = {GeneralPart::ldg, GeneralPart::flux, GeneralPart::faces, GeneralPart::update};
+    for (int w = 0; w < 4; w++)
     {
-      HFX_HIP(hipEventRecord(ev[5 * r + w - 1], st));
-      if (general_stage(eles, neb, faces, nfb, rk, rk == nst - 1, w)) return 1;
+      HFX_HIP(hipEventRecord(ev[5 * r + w], st));
+      if (general_stage(eles, neb, faces, nfb, rk, rk == nst - 1, parts[w])) return 1;
     }
     HFX_HIP(hipEventRecord(ev[5 * r + 4], st));
   }

@@ -15,13 +15,16 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
 int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int reps, double *ms);
 // algorithmic HBM bytes per launch group, same order
 void general_kernel_bytes(hfx_eles *const *eles, int neb, double *bytes);
-// ---- the deferred scheduler's pieces (deferred.hip): tables for these blocks (non-zero when a block does not qualify), and
-// ONE stage on blocks whose disu_fpts belong to the current state
-int general_deferred_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb);
-// pieces for the partitioned driver (comm.hip): one of the four parts of a stage; the projected viscous flux array of a block
-int general_stage_part(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool write_div, int which);
+// the whole stage, or one of its four launch groups (timed on their own; the partitioned driver puts the partition-face kernels
+// and the exchanges between them): boundary ghost states + LDG corrections of the interior pairs, the flux kernels of all blocks,
+// interior common fluxes + boundary viscous fluxes, the update kernels of all blocks
+enum class GeneralPart { stage, ldg, flux, faces, update };
+// tables for these blocks unless they exist (non-zero when a block does not qualify); `faces` may hold partition-face blocks
+int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb);
+// ONE stage, or one part of it, on prepared blocks whose disu_fpts belong to the current state
+int general_stage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool write_div, GeneralPart which);
+// the projected viscous flux array of a block
 const double *general_fn_fpts(const hfx_eles *e);
-int general_deferred_stage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool write_div);
 // eles::shock_capture of the blocks that registered it, and the flux-point values of the filtered state
 int general_shock_capture(hfx_eles *const *eles, int neb);
 } // namespace hfx

@@ -94,8 +94,10 @@ struct DeferCall
 struct DeferPlan
 {
   std::vector<DeferCall> signature; // the record this plan was made for (methods and objects; stage number excluded)
-  int kind = 0;                     // 0 replay, 1 split fused stage, 2 partitioned split stage, 3 general fused stage, 4 partitioned general stage
-  std::string why;                  // kind 0: why the record is not run as a fused stage
+  enum class Kind { replay, split, split_partitioned, general, general_partitioned }; // call by call, or as one of the fused stages
+  Kind kind = Kind::replay;
+  bool partitioned() const { return kind == Kind::split_partitioned || kind == Kind::general_partitioned; }
+  std::string why;                  // Kind::replay: why the record is not run as a fused stage
   std::vector<hfx_eles *> eles;
   std::vector<hfx_inters *> faces, mpi_faces; // interior + boundary blocks | partition-face blocks
   hfx_comm *comm = nullptr;
@@ -121,7 +123,6 @@ struct hfx_ctx
   // side_stream_join: launches go to the main stream again; side_stream_wait: the main stream waits for the side stream)
   hipStream_t side_stream = nullptr, bdy_stream = nullptr;
   hipEvent_t side_fork = nullptr, side_done = nullptr;
-  hipStream_t mpi_stream = nullptr; // when set: the one-sided partition-face kernels of the split path are launched here (hfx_run_steps_partitioned)
   hfx_params params{};
   bool have_params = false;
   int contract_mode = HFX_CONTRACT_AUTO;

@@ -96,6 +96,45 @@ enum class Part
   update_list_i,    // the update on the others (behind the buffer swap of update_list_b)
 };
 
+// ONE stage of the split fused path on a PARTITIONED block as named steps (split_partitioned.hpp).  init() does once what every
+// step relies on: argument checks, the block's fused tables, the plan, the stage range.  Which steps a stage takes is the caller's
+// choice from the plan (pl.variant, pl.projected, pl.split_flux, pl.split_update) and from `viscous`.  st: the stream of the
+// one-sided partition-face kernels; everything else runs on the context's compute stream.
+struct PartitionedSplit
+{
+  hfx_eles *e = nullptr;
+  hfx_inters *const *int_faces = nullptr, *const *mpi_faces = nullptr;
+  int n_int = 0, n_mpi = 0, in_step = 0;
+  bool last = false; // the last stage of a step (stores div_tconf_upts)
+  SplitPlan pl;
+  int init(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi, int in_step);
+  int pack_solution(hipStream_t st) const { return mpi_all(MpiKernel::pack_solution, st); }
+  // viscous: the LDG common solution at the boundary and interior faces (at the first stage behind the Leonard terms of an LES
+  // closure; the SVV closure is refused: it filters a state whose flux-point values have left already) | at the partition faces
+  int interior_ldg() const;
+  int partition_ldg(hipStream_t st) const { return mpi_all(MpiKernel::ldg_delta, st); }
+  // the element kernel (Part::flux; variant 3 allocates fn_fpts on first use), or with pl.split_flux one of its three launches:
+  // Part::flux_list_1 (needs nothing from the neighbours), Part::flux_list_b (behind partition_ldg), Part::flux_list_2
+  int element_kernel(Part part = Part::flux) const;
+  // the second message: variant 3 the projected viscous flux (behind the element kernel) | variant 2 the corrected gradient
+  // and, with an LES closure, a third message: the physical SGS flux (src/solver.cpp:168-178)
+  int pack_projected_flux(hipStream_t st) const { return mpi_all(MpiKernel::pack_projected_flux, st); }
+  int pack_gradient(hipStream_t st) const { return mpi_all(MpiKernel::pack_gradient, st); }
+  int pack_sgs_flux(hipStream_t st) const { return mpi_all(MpiKernel::pack_sgs_flux, st); }
+  // the common fluxes at the boundary and interior faces | at the partition faces: variant 3 from both sides' solution and
+  // projected flux; variant 2 the inviscid part (needs the solution only) and, viscous, the part from the gradients
+  int interior_common_fluxes() const;
+  int partition_common_fluxes(hipStream_t st) const { return mpi_all(MpiKernel::common_flux_projected, st); }
+  int partition_common_invflux(hipStream_t st) const { return mpi_all(MpiKernel::common_invflux, st); }
+  int partition_common_viscflux(hipStream_t st) const { return mpi_all(MpiKernel::common_viscflux, st); }
+  // the update (Part::update: residual, RK, the new flux-point solution, then shock capturing where the block has it), or with
+  // pl.split_update its two launches: Part::update_list_b (the elements with partition-face points, whose new flux-point
+  // solution can then leave) and Part::update_list_i (the others)
+  int update(Part part = Part::update) const;
+private:
+  int mpi_all(MpiKernel k, hipStream_t st) const; // kernel k on every partition-face block
+};
+
 constexpr int ipow(int b, int e) { return e == 0 ? 1 : b * ipow(b, e - 1); }
 // 32-bit words that hold `w` packed row entries, `epw` entries per word
 constexpr int words_of(int w, int epw = 2) { return (w + epw - 1) / epw; }
