@@ -393,10 +393,8 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
                               int n_mpi, hfx_comm *comm, int rk, bool start, bool shock)
 {
   HFX_CHECK(neb > 0 && comm, "general partitioned stage: bad argument");
-  hfx_ctx *ctx = eles[0]->ctx;
   if (check_partition_blocks(eles, neb, mpi_faces, n_mpi, comm)) return 1;
-  const bool visc = ctx->params.viscous != 0;
-  const int nst = n_rk_stages(ctx->params);
+  const bool visc = eles[0]->ctx->params.viscous != 0;
   // the blocks' tables are built with ALL face blocks (every flux point needs its face)
   std::vector<hfx_inters *> all(int_faces, int_faces + n_int);
   all.insert(all.end(), mpi_faces, mpi_faces + n_mpi);
@@ -406,25 +404,25 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
       if (mpi_launch_general(mpi_faces[b]->left, mpi_faces[b], k, general_fn_fpts(mpi_faces[b]->left))) return 1;
     return 0;
   };
-  auto part = [&](GeneralPart which) { return general_stage(eles, neb, all.data(), (int)all.size(), rk, rk == nst - 1, which); };
+  const GeneralStage stage(eles, neb, all.data(), (int)all.size(), rk);
   if (start)
   {
     if (mpi_all(MpiKernel::pack_solution)) return 1;
     if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1;
   }
-  if (part(GeneralPart::ldg)) return 1;
+  if (stage.interior_ldg()) return 1;
   if (wait_exchange(comm, 0, n_mpi)) return 1;
   if (visc && mpi_all(MpiKernel::ldg_delta)) return 1;
-  if (part(GeneralPart::flux)) return 1;
+  if (stage.flux_kernels()) return 1;
   if (visc)
   {
     if (mpi_all(MpiKernel::pack_projected_flux)) return 1;
     if (start_exchange(comm, mpi_faces, n_mpi, 1, true)) return 1;
   }
-  if (part(GeneralPart::faces)) return 1;
+  if (stage.common_fluxes()) return 1;
   if (visc && wait_exchange(comm, 1, n_mpi)) return 1;
   if (mpi_all(MpiKernel::common_flux_projected)) return 1;
-  if (part(GeneralPart::update)) return 1;
+  if (stage.update_kernels()) return 1;
   // eles::shock_capture (src/HiFiLES.cpp:214-216) before the new flux-point solution is packed: the filter, then the flux-point
   // values of the filtered state
   if (shock && general_shock_capture(eles, neb)) return 1;
@@ -687,10 +685,7 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   {
     for (int rk = 0; rk < nst; rk++)
     {
-      // closures that filter the solution do so at the first stage of a step (src/solver.cpp:55-62)
-      if (rk == 0)
-        for (int i = 0; i < n_ele_blocks; i++)
-          if (eles[i]->les_ready && eles[i]->les.sgs_model >= 2 && hfx_eles_calc_sgs_terms(eles[i])) return 1;
+      if (rk == 0 && first_stage_closure_filter(eles, n_ele_blocks, false)) return 1;
       if (general_partitioned_stage(eles, n_ele_blocks, int_faces, n_int, mpi_faces, n_mpi, comm, rk, start, true)) return 1;
       start = false;
     }

@@ -228,13 +228,11 @@ static void make_plan(hfx_ctx *ctx, const std::vector<DeferCall> &log, DeferPlan
   P.kind = mpi ? DeferPlan::Kind::general_partitioned : DeferPlan::Kind::general;
 }
 
-// arrays a fused stage of this kind leaves with the reference's values (given write_div)
-static unsigned fresh_after(const DeferPlan &P, bool write_div)
+// arrays a fused stage (of any kind) leaves with the reference's values (given write_div)
+static unsigned fresh_after(bool write_div)
 {
-  unsigned m = (1u << HFX_DISU_UPTS0) | (1u << HFX_DISU_UPTS1) | (1u << HFX_DISU_FPTS) | (1u << HFX_SRC_UPTS) | (1u << HFX_DT_LOCAL) |
-               (1u << HFX_SENSOR) | (1u << HFX_DISUF_UPTS) | (1u << HFX_LU) | (1u << HFX_LE);
-  if (write_div) m |= 1u << HFX_DIV_TCONF_UPTS;
-  return m;
+  return (1u << HFX_DISU_UPTS0) | (1u << HFX_DISU_UPTS1) | (1u << HFX_DISU_FPTS) | (1u << HFX_SRC_UPTS) | (1u << HFX_DT_LOCAL) |
+         (1u << HFX_SENSOR) | (1u << HFX_DISUF_UPTS) | (1u << HFX_LU) | (1u << HFX_LE) | (write_div ? 1u << HFX_DIV_TCONF_UPTS : 0u);
 }
 
 int replay_call(const DeferCall &c)
@@ -277,11 +275,8 @@ static int run_fused(hfx_ctx *ctx, const DeferPlan &P, int in_step, bool write_d
 {
   const int nst = n_rk_stages(ctx->params);
   HFX_CHECK(in_step >= 0 && in_step < nst, "AdvanceSolution: stage %d out of range for adv_type %d", in_step, ctx->params.adv_type);
-  // closures that filter the solution do so at the first stage of a step (src/solver.cpp:55-62); the SVV closure replaces the
-  // state, whose flux-point values are then recomputed below
-  if (P.sgs_terms)
-    for (hfx_eles *e : P.eles)
-      if (e->les_ready && e->les.sgs_model >= 2 && hfx_eles_calc_sgs_terms(e)) return 1;
+  // (the SVV closure replaces the state, whose flux-point values are recomputed below)
+  if (P.sgs_terms && first_stage_closure_filter(P.eles.data(), (int)P.eles.size(), false)) return 1;
   bool start = false; // partitioned: the flux-point solution of this state has not left yet
   for (hfx_eles *e : P.eles)
   {
@@ -301,7 +296,7 @@ static int run_fused(hfx_ctx *ctx, const DeferPlan &P, int in_step, bool write_d
     break;
   case DeferPlan::Kind::general:
     if (general_prepare(P.eles.data(), (int)P.eles.size(), faces, nfb)) return 1; // (no-op unless the registration changed)
-    if (general_stage(P.eles.data(), (int)P.eles.size(), faces, nfb, in_step, write_div, GeneralPart::stage)) return 1;
+    if (GeneralStage(P.eles.data(), (int)P.eles.size(), faces, nfb, in_step).run()) return 1; // (completes div_tconf_upts at every stage)
     if (P.shock && general_shock_capture(P.eles.data(), (int)P.eles.size())) return 1;
     break;
   case DeferPlan::Kind::general_partitioned:
@@ -311,7 +306,7 @@ static int run_fused(hfx_ctx *ctx, const DeferPlan &P, int in_step, bool write_d
   case DeferPlan::Kind::replay:
     HFX_CHECK(false, "deferred execution: a record that replays has no fused stage");
   }
-  const unsigned fresh = fresh_after(P, write_div);
+  const unsigned fresh = fresh_after(write_div);
   for (hfx_eles *e : P.eles)
   {
     e->fpts_valid = true;
@@ -383,7 +378,7 @@ int defer_flush(hfx_ctx *ctx, unsigned need)
     // div_tconf_upts is stored at the last stage of a step (where the monitors read it) or when this flush is for it
     // (the partitioned stage stores it at the last stage only)
     const bool write_div = in_step == n_rk_stages(ctx->params) - 1 || (!plan->partitioned() && (need & (1u << HFX_DIV_TCONF_UPTS)) != 0);
-    if ((need & ~fresh_after(*plan, write_div)) == 0)
+    if ((need & ~fresh_after(write_div)) == 0)
     {
       d.n_fused++;
       return run_fused(ctx, *plan, in_step, write_div);

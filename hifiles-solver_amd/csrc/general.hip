@@ -1,6 +1,6 @@
 // general.hip -- the fused RK stage for GENERAL (non-tensor-product) element classes: tetrahedra, triangular prisms.
 //
-// Reference side: the same 17 calls of CalcResidual + AdvanceSolution as everywhere (/root/reference/src/solver.cpp:50-223,
+// Reference side: the same 17 calls of CalcResidual + AdvanceSolution as everywhere (src/solver.cpp:50-223,
 // src/HiFiLES.cpp:201-217); on these classes the seven operators (src/eles.cpp:3074-3596, built by src/eles_tets.cpp and
 // src/eles_pris.cpp) are DENSE -- P3: 40 x 20 / 20 x 20 / 20 x 40 doubles on tetrahedra, 68 x 40 / 40 x 40 / 40 x 68 on
 // prisms -- so the per-method path is a stream of 15+ dense GEMM and point kernels per stage (820 B per DOF-update).
@@ -25,22 +25,15 @@
 // and stay cache resident.  Element data sits in LDS as [operator column k][16 elements] planes (one per field /
 // field x dimension) with the element index XOR-swizzled by the row: operand reads, accumulator writes and the
 // point-wise passes are all bank-conflict free.
-#include <vector>
-#include "general.hpp"
-
+#include <algorithm>
 #include <type_traits>
 
-#include <algorithm>
-#include <cstring>
-
-#include "physics.hpp"
+#include "general.hpp"
 
 namespace hfx
 {
 
 typedef double g_f64x4 __attribute__((ext_vector_type(4)));
-
-constexpr int GB = 16; // elements per batch = MFMA tile edge
 
 struct GeneralData
 {
@@ -62,13 +55,13 @@ struct GeneralData
 
 void general_invalidate(hfx_eles *e)
 {
-  if (e && e->general) ((GeneralData *)e->general)->built = false;
+  if (e && e->general) e->general->built = false;
 }
 
 void general_destroy(hfx_eles *e)
 {
   if (!e || !e->general) return;
-  GeneralData *g = (GeneralData *)e->general;
+  GeneralData *g = e->general;
   void *p[] = {g->o0, g->o1[0], g->o1[1], g->o1[2], g->o2[0], g->o2[1], g->o2[2], g->o3, g->o4[0], g->o4[1], g->o4[2],
                g->o5[0], g->o5[1], g->o5[2], g->o6, g->meta, g->disu_alt, g->fn_fpts, g->stamps, g->nbr, g->o2f[0], g->o2f[1], g->o2f[2], g->les_len2};
   for (void *q : p)
@@ -93,42 +86,6 @@ __device__ __forceinline__ void g_to_physical(const double inv_detjac, const dou
     for (int d = 0; d < 3; d++) cg[d] += temp * JG[l + 3 * d];
   }
 }
-
-struct GenArgs
-{
-  int n_eles, nu, nfp, KU, KF, MU, MF;
-  unsigned inv_nu, inv_nfp; // floor(2^32 / n) + 1: q / n == __umulhi(q, inv) for the q < 2^16 of the staging loops
-  const double *o0, *o1[3], *o2[3], *o3, *o4[3], *o5[3], *o6;
-  const double *u0, *delta, *disu;
-  // fold != 0: o2[d] holds opp_2[d] - opp_3 opp_1[d], so that P4 leaves div_tdisf - opp_3 norm_tdisf in `div` and norm_tdisf is
-  // neither formed nor stored; the update kernel then adds opp_3 norm_tconf alone (as split3's folded correction)
-  int fold;
-  // the LDG correction of a flux point whose partner lies in the SAME element block is formed in the flux kernel from the
-  // partner's flux-point solution: (partner offset << 4) | partner's block << 2 | beta sign flipped << 1 | this point is the right
-  // side; -1: a boundary point (its correction is in `delta`).  NULL: `delta` holds all of them.
-  const int *nbr;
-  const double *disu_b[4]; // flux-point solution of the blocks a partner word may name (its bits 3:2), and their plane strides
-  long plane_b[4];
-  const double *detjac_upts, *JGinv_upts, *detjac_fpts, *JGinv_fpts, *norm_fpts;
-  const unsigned char *meta;
-  double *div, *ntd, *fn, *grad_fpts; // grad_fpts: boundary points only (NULL: no boundary faces / inviscid)
-  Phys P;
-  // update kernel
-  double *u0w, *u1;
-  const double *tconf, *div_in, *src, *dt_local;
-  double *disu_next;
-  unsigned long long *nan_flag;
-  int adv_type, in_step, dt_local_on, write_div, need_u1;
-  double dt, rk_a, rk_b;
-  long long *stamps; // diagnostics (option flux_stamps): cycle counter of every wave of ONE workgroup at the phase boundaries
-  // LES closure evaluated in the flux kernel (LESG form): parameters (with the Leonard terms of the similarity models), the wall
-  // distance of the Smagorinsky damping, and tdA at the flux points (F_sgs . n = (F~_sgs . n~) / tdA)
-  LesParams les;
-  const double *les_len2, *tdA_fpts;
-  // over-integration: the de-aliased transformed inviscid flux (eles::evaluate_invFlux_over_int, formed by the dense contractions
-  // before this launch), taken in P3 instead of the collocated one; NULL: none
-  const double *tdisf_in;
-};
 
 // NA output tiles at once, sharing the operator fragments: acc[j] += op[rt*16 + (0..15)][0 .. 4 ksteps) . plane_j[k][16 elements],
 // plane_j = plane + j * pstride.  op: zero-padded operator, leading dimension M; lane: li = lane & 15, lk = lane >> 4.
@@ -239,8 +196,8 @@ __global__ __launch_bounds__(64 * W, 2) void general_flux_kernel(const GenArgs a
   // ALL loads of a thread are requested before the first one is used (one memory latency for the batch instead of one per
   // trip of the staging loop: the stamps showed 21 000 - 48 000 of a batch's 100 000 cycles here)
   {
-    constexpr int MAXQ_U = NUc ? (((NUc + 3) & ~3) * GB + T - 1) / T : 0, MAXQ_D = NFPc ? (((NFPc + 3) & ~3) * GB + T - 1) / T : 0;
-    if constexpr (NUc != 0 && NFPc != 0 && (MAXQ_U + MAXQ_D) * NF <= 30) // (more would not fit the registers)
+    constexpr int MAXQ_U = general_staged((NUc + 3) & ~3, W), MAXQ_D = general_staged((NFPc + 3) & ~3, W);
+    if constexpr (NUc != 0 && NFPc != 0 && general_flux_batched(NUc, NFPc, W)) // (more would not fit the registers)
     {
       double ru[NF][MAXQ_U], rd[NF][MAXQ_D];
 #pragma unroll
@@ -722,8 +679,8 @@ __global__ __launch_bounds__(64 * W) void general_update_kernel(const GenArgs a)
 
   // every load of a thread is requested before the first one is used (one memory latency per staging step, as in the
   // flux kernel's P0)
-  constexpr int MAXQ_D = NFPc ? (((NFPc + 3) & ~3) * GB + T - 1) / T : 0, MAXQ_U = NUc ? (NUc * GB + T - 1) / T : 0;
-  constexpr bool BATCH = NUc != 0 && NFPc != 0 && MAXQ_D * NF <= 20 && MAXQ_U * NF <= 15;
+  constexpr int MAXQ_D = general_staged((NFPc + 3) & ~3, W), MAXQ_U = general_staged(NUc, W);
+  constexpr bool BATCH = NUc != 0 && NFPc != 0 && general_update_batched(NUc, NFPc, W);
   if constexpr (BATCH)
   {
     double rt_[NF][MAXQ_D], rn_[NF][MAXQ_D];
@@ -1031,8 +988,13 @@ static int padded_operator(double **dst, const Operator &op, int M, int K)
   return 0;
 }
 
-static size_t flux_lds_bytes(const GeneralData *g) { return sizeof(double) * GB * (5 * g->KU + 5 * g->KF + 15 * g->KU); }
-static size_t update_lds_bytes(const GeneralData *g) { return sizeof(double) * GB * (5 * g->KF + 5 * g->KU); }
+// the block's index in GENERAL_SIZES, or -1
+static int general_size_class(const hfx_eles *e)
+{
+  for (int i = 0; i < N_GENERAL_SIZES; i++)
+    if (e->n_upts == GENERAL_SIZES[i][0] && e->n_fpts == GENERAL_SIZES[i][1]) return i;
+  return -1;
+}
 
 static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_eles *const *eles, int neb)
 {
@@ -1042,24 +1004,20 @@ static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_ele
   HFX_CHECK(!(e->les_ready && e->over_int_ready), "general fused stage: an LES closure together with over-integration runs per method");
   if (e->les_ready)
   {
-    static const int sizes[][2] = {{4, 12}, {10, 24}, {20, 40}, {6, 18}, {18, 39}, {40, 68}};
-    bool known = false;
-    for (const auto &sz : sizes) known = known || (e->n_upts == sz[0] && e->n_fpts == sz[1]);
-    HFX_CHECK(known && e->ctx->params.viscous, "general fused stage: the LES closure is built for tetrahedra / prisms of orders 1..3 on a viscous run");
+    HFX_CHECK(general_size_class(e) >= 0 && e->ctx->params.viscous, "general fused stage: the LES closure is built for tetrahedra / prisms of orders 1..3 on a viscous run");
     // (partitioned blocks: the projected flux a partition face sends already contains F_sgs . n -- no third message; the
     // SVV closure filters the state after its flux-point values have left for the neighbours)
     for (int b = 0; b < nfb; b++)
       HFX_CHECK(!faces[b]->is_mpi || e->les.sgs_model != 3, "general fused stage: the SVV closure on partitioned blocks runs per method");
   }
   if (!e->general) e->general = new GeneralData();
-  if (e->les_ready && e->les.sgs_model != 3 && les_len2_upload(e, &((GeneralData *)e->general)->les_len2)) return 1;
+  GeneralData *g = e->general;
+  if (e->les_ready && e->les.sgs_model != 3 && les_len2_upload(e, &g->les_len2)) return 1;
   const bool visc = e->ctx->params.viscous != 0;
   HFX_CHECK(!visc || e->viscous_ops, "general fused stage: viscous run but the block has no opp_4/5/6");
-  if (!e->general) e->general = new GeneralData();
-  GeneralData *g = (GeneralData *)e->general;
   const int nu = e->n_upts, nfp = e->n_fpts;
   g->KU = (nu + 3) & ~3; g->KF = (nfp + 3) & ~3; g->MU = (nu + 15) & ~15; g->MF = (nfp + 15) & ~15;
-  HFX_CHECK(flux_lds_bytes(g) <= 160 * 1024, "general fused stage: a batch of this element class (%d solution, %d flux points) does not fit LDS", nu, nfp);
+  HFX_CHECK(general_flux_lds_bytes(nu, nfp) <= 160 * 1024, "general fused stage: a batch of this element class (%d solution, %d flux points) does not fit LDS", nu, nfp);
   if (padded_operator(&g->o0, e->opp_0, g->MF, g->KU) || padded_operator(&g->o3, e->opp_3, g->MU, g->KF)) return 1;
   for (int d = 0; d < 3; d++)
     if (padded_operator(&g->o1[d], e->opp_1[d], g->MF, g->KU) || padded_operator(&g->o2[d], e->opp_2[d], g->MU, g->KU)) return 1;
@@ -1187,36 +1145,36 @@ static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_ele
   return 0;
 }
 
-// does the flux kernel of this block stage its inputs with all loads requested up front (the form that can also form the
-// LDG corrections itself)?  -- an instantiated element size whose staging registers fit (general_flux_kernel, P0)
-static bool general_batched(const hfx_eles *e)
+GeneralPlan general_plan(const hfx_eles *e)
 {
-  const GeneralData *g = (const GeneralData *)e->general;
-  if (!g) return false;
-  static const int sizes[][2] = {{4, 12}, {10, 24}, {20, 40}, {6, 18}, {18, 39}, {40, 68}};
-  bool known = false;
-  for (const auto &sz : sizes) known = known || (e->n_upts == sz[0] && e->n_fpts == sz[1]);
-  if (!known) return false;
-  int w = e->ctx->opt.general_waves;
-  if (w == 0) w = flux_lds_bytes(g) <= 80 * 1024 ? 4 : 8;
-  const int T = 64 * w, mq_u = (g->KU * GB + T - 1) / T, mq_d = (g->KF * GB + T - 1) / T;
-  return (mq_u + mq_d) * 5 <= 30;
+  const hfx_ctx::Options &opt = e->ctx->opt;
+  const int nu = e->n_upts, nfp = e->n_fpts, viscous = e->ctx->params.viscous;
+  GeneralPlan pl;
+  pl.size_class = general_size_class(e);
+  pl.flux_waves = opt.general_waves ? opt.general_waves : general_flux_default_waves(nu, nfp);
+  pl.flux_batched = pl.size_class >= 0 && general_flux_batched(nu, nfp, pl.flux_waves);
+  pl.gather = opt.gather_delta && viscous && pl.flux_batched && e->general && e->general->nbr;
+  pl.les = e->les_ready && e->les.sgs_model != 3 && viscous;
+  pl.update_waves = opt.general_update_waves ? opt.general_update_waves : general_update_batched(nu, nfp, 4) ? 4 : 8;
+  pl.flux_lds = general_flux_lds_bytes(nu, nfp); pl.update_lds = general_update_lds_bytes(nu, nfp);
+  pl.fold = opt.fold_general != 0;
+  return pl;
 }
 
-static GenArgs gen_args(hfx_eles *e, int in_step, bool last_stage)
+static GenArgs gen_args(hfx_eles *e, const GeneralPlan &pl, int in_step)
 {
-  GeneralData *g = (GeneralData *)e->general;
+  GeneralData *g = e->general;
   const hfx_params &p = e->ctx->params;
   GenArgs a{};
   a.inv_nu = (unsigned)(4294967296ull / (unsigned)e->n_upts) + 1u; a.inv_nfp = (unsigned)(4294967296ull / (unsigned)e->n_fpts) + 1u;
   a.n_eles = e->n_eles; a.nu = e->n_upts; a.nfp = e->n_fpts; a.KU = g->KU; a.KF = g->KF; a.MU = g->MU; a.MF = g->MF;
   a.o0 = g->o0; a.o3 = g->o3; a.o6 = g->o6;
-  a.fold = e->ctx->opt.fold_general ? 1 : 0;
+  a.fold = pl.fold ? 1 : 0;
   for (int d = 0; d < 3; d++) { a.o1[d] = g->o1[d]; a.o2[d] = a.fold ? g->o2f[d] : g->o2[d]; a.o4[d] = g->o4[d]; a.o5[d] = g->o5[d]; }
   a.u0 = e->arr[HFX_DISU_UPTS0]; a.delta = e->arr[HFX_DELTA_DISU_FPTS]; a.disu = e->arr[HFX_DISU_FPTS];
   a.detjac_upts = e->detjac_upts; a.JGinv_upts = e->JGinv_upts; a.detjac_fpts = e->detjac_fpts; a.JGinv_fpts = e->JGinv_fpts;
   a.norm_fpts = e->norm_fpts; a.meta = g->meta;
-  a.nbr = (e->ctx->opt.gather_delta && p.viscous && general_batched(e)) ? g->nbr : nullptr;
+  a.nbr = pl.gather ? g->nbr : nullptr;
   for (int i = 0; i < 4; i++)
   {
     a.disu_b[i] = (i < g->n_blocks) ? g->blocks[i]->arr[HFX_DISU_FPTS] : nullptr;
@@ -1243,14 +1201,13 @@ static GenArgs gen_args(hfx_eles *e, int in_step, bool last_stage)
   a.les = e->les; a.les_len2 = g->les_len2; a.tdA_fpts = e->tdA_fpts;
   a.tdisf_in = e->over_int_ready ? e->arr[HFX_TDISF_UPTS] : nullptr;
   a.write_div = 1; // the flux kernel left the discontinuous part there: always complete it (the monitors read it)
-  (void)last_stage;
   return a;
 }
 
 static GFaceArgs gface_args(hfx_inters *f)
 {
   hfx_eles *l = f->left, *r = f->right;
-  GeneralData *gl = (GeneralData *)l->general, *gr = (GeneralData *)r->general;
+  GeneralData *gl = l->general, *gr = r->general;
   GFaceArgs a{};
   a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
   a.L = f->L; a.R = f->R; a.meta_l = gl->meta;
@@ -1265,150 +1222,115 @@ static GFaceArgs gface_args(hfx_inters *f)
 }
 
 template <int W, int NUc, int NFPc>
-static int launch_element_kernels_t(hfx_eles *e, const GenArgs &a, bool flux)
+static int launch_element_kernels_t(hfx_eles *e, const GenArgs &a, const GeneralPlan &pl, bool flux)
 {
-  GeneralData *g = (GeneralData *)e->general;
-  const unsigned grid = (unsigned)((e->n_eles + GB - 1) / GB);
-  hipStream_t st = e->ctx->stream;
-  if (flux)
-  {
-    const size_t lds = flux_lds_bytes(g);
-    // (function attributes are per device: set whenever the image exceeds the default, as launch_dense does -- a cached
-    // "configured" size would be wrong for a second context on another GPU of the same process)
-    // a closure with an SGS flux (every model but the spectral vanishing viscosity, which only filters the state)
-    const bool les = e->les_ready && e->les.sgs_model != 3 && e->ctx->params.viscous;
-    if constexpr (NUc != 0)
-    {
-      if (les)
-      {
-        if (lds > 48 * 1024)
-          HFX_HIP(hipFuncSetAttribute((const void *)general_flux_kernel<W, NUc, NFPc, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((general_flux_kernel<W, NUc, NFPc, true>), dim3(grid), dim3(64 * W), lds, st, a);
-        HFX_HIP(hipGetLastError());
-        return 0;
-      }
-    }
-    HFX_CHECK(!les, "general fused stage: the LES closure is built for the element classes with compile-time sizes");
-    if (lds > 48 * 1024)
-      HFX_HIP(hipFuncSetAttribute((const void *)general_flux_kernel<W, NUc, NFPc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((general_flux_kernel<W, NUc, NFPc>), dim3(grid), dim3(64 * W), lds, st, a);
-  }
+  const dim3 grid((unsigned)((e->n_eles + GB - 1) / GB)), block(64 * W);
+  // (function attributes are per device: set whenever the image exceeds the default, as launch_dense does -- a cached
+  // "configured" size would be wrong for a second context on another GPU of the same process)
+  auto launch = [&](auto kernel, size_t lds) -> int {
+    if (lds > 48 * 1024) HFX_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, grid, block, lds, e->ctx->stream, a);
+    HFX_HIP(hipGetLastError());
+    return 0;
+  };
+  if (!flux) return launch(general_update_kernel<W, NUc, NFPc>, pl.update_lds);
+  if constexpr (NUc != 0)
+    if (pl.les) return launch(general_flux_kernel<W, NUc, NFPc, true>, pl.flux_lds);
+  HFX_CHECK(!pl.les, "general fused stage: the LES closure is built for the element classes with compile-time sizes");
+  return launch(general_flux_kernel<W, NUc, NFPc>, pl.flux_lds);
+}
+
+// the instantiation of the plan's size class (GENERAL_SIZES[I], I counting up), else the size-generic one
+template <int W, int I = 0>
+static int launch_element_kernels(hfx_eles *e, const GenArgs &a, const GeneralPlan &pl, bool flux)
+{
+  if constexpr (I == N_GENERAL_SIZES)
+    return launch_element_kernels_t<W, 0, 0>(e, a, pl, flux);
   else
+    return pl.size_class == I ? launch_element_kernels_t<W, GENERAL_SIZES[I][0], GENERAL_SIZES[I][1]>(e, a, pl, flux)
+                              : launch_element_kernels<W, I + 1>(e, a, pl, flux);
+}
+
+static int launch_element_kernels(int waves, hfx_eles *e, const GenArgs &a, const GeneralPlan &pl, bool flux)
+{
+  return waves == 3 ? launch_element_kernels<3>(e, a, pl, flux) : waves == 4 ? launch_element_kernels<4>(e, a, pl, flux)
+                                                                              : launch_element_kernels<8>(e, a, pl, flux);
+}
+
+GeneralStage::GeneralStage(hfx_eles *const *eles_, int neb_, hfx_inters *const *faces_, int nfb_, int in_step_)
+    : eles(eles_), faces(faces_), neb(neb_), nfb(nfb_)
+{
+  for (int i = 0; i < neb; i++) args.push_back(gen_args(eles[i], plans.emplace_back(general_plan(eles[i])), in_step_));
+}
+
+int GeneralStage::interior_ldg() const
+{
+  hfx_ctx *ctx = eles[0]->ctx;
+  if (!ctx->params.viscous) return 0;
+  auto gathers = [&](const hfx_eles *x) { return plans[std::find(eles, eles + neb - 1, x) - eles].gather; }; // (x is a block of the call)
+  for (int b = 0; b < nfb; b++)
   {
-    const size_t lds = update_lds_bytes(g);
-    if (lds > 48 * 1024)
-      HFX_HIP(hipFuncSetAttribute((const void *)general_update_kernel<W, NUc, NFPc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((general_update_kernel<W, NUc, NFPc>), dim3(grid), dim3(64 * W), lds, st, a);
+    if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], 0, 1)) return 1; // ghost state -> inviscid common flux, LDG common solution
+    if (faces[b]->is_bdy || faces[b]->is_mpi) continue;
+    if (gathers(faces[b]->left) && gathers(faces[b]->right)) continue; // both sides' flux kernels form these corrections themselves
+    const GFaceArgs a = gface_args(faces[b]);
+    if (a.npairs == 0) continue;
+    hipLaunchKernelGGL(gface_delta_kernel, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, ctx->stream, a);
   }
   HFX_HIP(hipGetLastError());
   return 0;
 }
 
-// the element classes of the reference's orders 1..3 (tetrahedra 4/12, 10/24, 20/40; prisms 6/18, 18/39, 40/68 solution /
-// flux points) get instantiations with compile-time sizes; anything else runs the size-generic form
-template <int W>
-static int launch_element_kernels(hfx_eles *e, const GenArgs &a, bool flux)
+int GeneralStage::flux_kernels() const
 {
-#define HFX_GEN_CASE(NU_, NFP_) \
-  if (a.nu == NU_ && a.nfp == NFP_) return launch_element_kernels_t<W, NU_, NFP_>(e, a, flux);
-  HFX_GEN_CASE(4, 12) HFX_GEN_CASE(10, 24) HFX_GEN_CASE(20, 40) HFX_GEN_CASE(6, 18) HFX_GEN_CASE(18, 39) HFX_GEN_CASE(40, 68)
-#undef HFX_GEN_CASE
-  return launch_element_kernels_t<W, 0, 0>(e, a, flux);
+  for (int i = 0; i < neb; i++)
+  {
+    // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
+    if (eles[i]->over_int_ready && hfx_eles_evaluate_invFlux_over_int(eles[i])) return 1;
+    if (launch_element_kernels(plans[i].flux_waves, eles[i], args[i], plans[i], true)) return 1;
+  }
+  return 0;
 }
 
-// `faces` may hold partition-face blocks (they take part in the build -- every flux point needs its face -- and are skipped by
-// the pairwise loops)
-int general_stage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool last_stage, GeneralPart which)
+int GeneralStage::common_fluxes() const
 {
   hfx_ctx *ctx = eles[0]->ctx;
   const Phys P = ctx->phys();
-  hipStream_t st = ctx->stream;
-  if (P.viscous && (which == GeneralPart::stage || which == GeneralPart::ldg))
-    for (int b = 0; b < nfb; b++)
-    {
-      if (faces[b]->is_bdy)
-      {
-        if (hfx_bdy_launch_internal(faces[b], 0, 1)) return 1; // ghost state -> inviscid common flux, LDG common solution
-        continue;
-      }
-      if (faces[b]->is_mpi) continue;
-      {
-        // both sides' flux kernels form these corrections themselves?
-        auto own = [&](hfx_eles *x) {
-          return x->general && ((GeneralData *)x->general)->nbr && ((GeneralData *)x->general)->n_blocks && general_batched(x);
-        };
-        if (ctx->opt.gather_delta && own(faces[b]->left) && own(faces[b]->right)) continue;
-      }
-      const GFaceArgs a = gface_args(faces[b]);
-      if (a.npairs == 0) continue;
-      hipLaunchKernelGGL(gface_delta_kernel, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, st, a);
-    }
-  if (which == GeneralPart::stage || which == GeneralPart::flux)
-    for (int i = 0; i < neb; i++)
-    {
-      // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
-      if (eles[i]->over_int_ready && hfx_eles_evaluate_invFlux_over_int(eles[i])) return 1;
-      const GenArgs a = gen_args(eles[i], in_step, last_stage);
-      // two workgroups per CU where the batch's LDS image allows it (4 waves each), otherwise one of 8 waves
-      int w = ctx->opt.general_waves;
-      if (w == 0) w = flux_lds_bytes((GeneralData *)eles[i]->general) <= 80 * 1024 ? 4 : 8;
-      if (w == 3 ? launch_element_kernels<3>(eles[i], a, true) : w == 4 ? launch_element_kernels<4>(eles[i], a, true)
-                                                                         : launch_element_kernels<8>(eles[i], a, true))
-        return 1;
-    }
-  if (which == GeneralPart::stage || which == GeneralPart::faces)
+  // boundary faces beside the interior ones: both need the flux kernels' results and write norm_tconf at disjoint points
+  bool any_bdy = false;
+  for (int b = 0; b < nfb; b++) any_bdy = any_bdy || (faces[b]->is_bdy && faces[b]->n_inters > 0);
+  const bool beside = any_bdy && ctx->opt.bdy_beside;
+  if (beside && side_stream_fork(ctx)) return 1;
+  for (int b = 0; b < nfb; b++)
+    if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], P.viscous ? 1 : 0, 1)) return 1;
+  if (beside && side_stream_join(ctx)) return 1;
+  // all interior-face blocks in one launch (groups of GFACE_MAX_BLOCKS)
+  GFaceMulti m{};
+  const auto kernel = P.riemann == 0 ? gface_flux_multi_kernel<0> : P.riemann == 2 ? gface_flux_multi_kernel<2> : gface_flux_multi_kernel<3>;
+  auto flush = [&]() {
+    if (m.nb > 0) hipLaunchKernelGGL(kernel, dim3(m.wg_start[m.nb]), dim3(256), 0, ctx->stream, m);
+    m.nb = 0;
+  };
+  for (int b = 0; b < nfb; b++)
   {
-    // boundary faces beside the interior ones: both need the flux kernels' results and write norm_tconf at disjoint points
-    bool any_bdy = false;
-    for (int b = 0; b < nfb; b++) any_bdy = any_bdy || (faces[b]->is_bdy && faces[b]->n_inters > 0);
-    const bool beside = any_bdy && ctx->opt.bdy_beside;
-    if (beside && side_stream_fork(ctx)) return 1;
-    for (int b = 0; b < nfb; b++)
-      if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], P.viscous ? 1 : 0, 1)) return 1;
-    if (beside && side_stream_join(ctx)) return 1;
-    // all interior-face blocks in one launch (groups of GFACE_MAX_BLOCKS)
-    GFaceMulti m{};
-    auto flush = [&]() -> int {
-      if (m.nb == 0) return 0;
-      const dim3 grid(m.wg_start[m.nb]);
-      if (P.riemann == 0)
-        hipLaunchKernelGGL(gface_flux_multi_kernel<0>, grid, dim3(256), 0, st, m);
-      else if (P.riemann == 2)
-        hipLaunchKernelGGL(gface_flux_multi_kernel<2>, grid, dim3(256), 0, st, m);
-      else
-        hipLaunchKernelGGL(gface_flux_multi_kernel<3>, grid, dim3(256), 0, st, m);
-      m.nb = 0;
-      return 0;
-    };
-    for (int b = 0; b < nfb; b++)
-    {
-      if (faces[b]->is_bdy || faces[b]->is_mpi) continue;
-      const GFaceArgs a = gface_args(faces[b]);
-      if (a.npairs == 0) continue;
-      if (m.nb == 0) m.wg_start[0] = 0;
-      m.blk[m.nb] = a;
-      m.wg_start[m.nb + 1] = m.wg_start[m.nb] + (unsigned)((a.npairs + 255) / 256);
-      if (++m.nb == GFACE_MAX_BLOCKS && flush()) return 1;
-    }
-    if (flush()) return 1;
-    if (beside && side_stream_wait(ctx)) return 1;
+    if (faces[b]->is_bdy || faces[b]->is_mpi) continue;
+    const GFaceArgs a = gface_args(faces[b]);
+    if (a.npairs == 0) continue;
+    m.blk[m.nb] = a;
+    m.wg_start[m.nb + 1] = m.wg_start[m.nb] + (unsigned)((a.npairs + 255) / 256);
+    if (++m.nb == GFACE_MAX_BLOCKS) flush();
   }
-  if (which == GeneralPart::stage || which == GeneralPart::update)
-  {
-    for (int i = 0; i < neb; i++)
-    {
-      const GenArgs a = gen_args(eles[i], in_step, last_stage);
-      // four waves where all of a thread's staging loads fit its registers at once (general_update_kernel, BATCH), else eight:
-      // P3 prisms stage 5 + 3 doubles per field and thread on four waves -- past the limit, every trip of the staging loops then
-      // waited for its own loads (0.233 ms for 451 MB)
-      const int w_opt = ctx->opt.general_update_waves;
-      const int mq_d = (a.KF * GB + 255) / 256, mq_u = (a.nu * GB + 255) / 256;
-      const bool eight = w_opt ? w_opt == 8 : (mq_d * 5 > 20 || mq_u * 5 > 15);
-      if (eight ? launch_element_kernels<8>(eles[i], a, false) : launch_element_kernels<4>(eles[i], a, false)) return 1;
-    }
-    for (int i = 0; i < neb; i++) std::swap(eles[i]->arr[HFX_DISU_FPTS], ((GeneralData *)eles[i]->general)->disu_alt);
-  }
+  flush();
+  if (beside && side_stream_wait(ctx)) return 1;
   HFX_HIP(hipGetLastError());
+  return 0;
+}
+
+int GeneralStage::update_kernels() const
+{
+  for (int i = 0; i < neb; i++)
+    if (launch_element_kernels(plans[i].update_waves, eles[i], args[i], plans[i], false)) return 1;
+  for (int i = 0; i < neb; i++) std::swap(eles[i]->arr[HFX_DISU_FPTS], eles[i]->general->disu_alt);
   return 0;
 }
 
@@ -1432,7 +1354,7 @@ int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, in
   }
   for (int i = 0; i < neb; i++)
   {
-    GeneralData *g = (GeneralData *)eles[i]->general;
+    GeneralData *g = eles[i]->general;
     bool same = g && g->built;
     if (same && g->n_blocks)
     {
@@ -1445,7 +1367,7 @@ int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, in
   return 0;
 }
 
-const double *general_fn_fpts(const hfx_eles *e) { return e->general ? ((const GeneralData *)e->general)->fn_fpts : nullptr; }
+const double *general_fn_fpts(const hfx_eles *e) { return e->general ? e->general->fn_fpts : nullptr; }
 
 // eles::shock_capture behind a general fused stage (src/HiFiLES.cpp:214-216): the modal filter changes the state of the elements
 // the sensor marks, so the flux-point values the update kernel left for the next stage are extrapolated again
@@ -1464,36 +1386,17 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
 {
   if (general_prepare(eles, neb, faces, nfb)) return 1;
   if (n_steps <= 0) return 0;
-  hfx_ctx *ctx = eles[0]->ctx;
-  const int adv = ctx->params.adv_type;
-  const int nst = n_rk_stages(adv);
+  const int nst = n_rk_stages(eles[0]->ctx->params);
   // disu_fpts of the current state (the caller may have changed disu_upts since the last call)
   for (int i = 0; i < neb; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
   for (int s = 0; s < n_steps; s++)
   {
-    if (ctx->params.dt_type != 0)
-    {
-      double dt_min = 1e12;
-      for (int i = 0; i < neb; i++)
-      {
-        if (calc_time_step(eles[i], nullptr)) return 1; /* src/HiFiLES.cpp:198 */
-        dt_min = std::min(dt_min, ctx->params.dt);
-      }
-      ctx->params.dt = dt_min;
-    }
+    if (calc_time_step_blocks(eles, neb)) return 1; /* src/HiFiLES.cpp:198 */
     for (int rk = 0; rk < nst; rk++)
     {
-      // closures that filter the solution do so at the first stage of a step (src/solver.cpp:55-62); the SVV closure replaces the
-      // state, whose flux-point values are then recomputed
-      if (rk == 0)
-        for (int i = 0; i < neb; i++)
-          if (eles[i]->les_ready && eles[i]->les.sgs_model >= 2)
-          {
-            if (hfx_eles_calc_sgs_terms(eles[i])) return 1;
-            if (eles[i]->les.sgs_model == 3 && hfx_eles_extrapolate_solution(eles[i])) return 1;
-          }
-      if (general_stage(eles, neb, faces, nfb, rk, rk == nst - 1, GeneralPart::stage)) return 1;
+      if (rk == 0 && first_stage_closure_filter(eles, neb, true)) return 1;
+      if (GeneralStage(eles, neb, faces, nfb, rk).run()) return 1;
       if (general_shock_capture(eles, neb)) return 1;
     }
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
@@ -1504,10 +1407,8 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
 int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int reps, double *ms)
 {
   if (general_prepare(eles, neb, faces, nfb)) return 1;
-  hfx_ctx *ctx = eles[0]->ctx;
-  const int adv = ctx->params.adv_type;
-  const int nst = n_rk_stages(adv);
-  hipStream_t st = ctx->stream;
+  const int nst = n_rk_stages(eles[0]->ctx->params);
+  hipStream_t st = eles[0]->ctx->stream;
   // one set of events per repetition and ONE synchronisation at the end: a host synchronisation per stage let the queue
   // run dry, and the first kernel after it (the flux kernel) then measured 10 % slower than in the running pipeline
   std::vector<hipEvent_t> ev((size_t)reps * 5);
@@ -1517,13 +1418,15 @@ int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *face
   double acc[4] = {0, 0, 0, 0};
   for (int r = 0; r < reps; r++)
   {
-    const int rk = r % nst;
-    const GeneralPart parts[4] = {GeneralPart::ldg, GeneralPart::flux, GeneralPart::faces, GeneralPart::update};
-    for (int w = 0; w < 4; w++)
-    {
-      HFX_HIP(hipEventRecord(ev[5 * r + w], st));
-      if (general_stage(eles, neb, faces, nfb, rk, rk == nst - 1, parts[w])) return 1;
-    }
+    const GeneralStage stage(eles, neb, faces, nfb, r % nst);
+    HFX_HIP(hipEventRecord(ev[5 * r], st));
+    if (stage.interior_ldg()) return 1;
+    HFX_HIP(hipEventRecord(ev[5 * r + 1], st));
+    if (stage.flux_kernels()) return 1;
+    HFX_HIP(hipEventRecord(ev[5 * r + 2], st));
+    if (stage.common_fluxes()) return 1;
+    HFX_HIP(hipEventRecord(ev[5 * r + 3], st));
+    if (stage.update_kernels()) return 1;
     HFX_HIP(hipEventRecord(ev[5 * r + 4], st));
   }
   HFX_HIP(hipStreamSynchronize(st));
@@ -1538,7 +1441,7 @@ int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *face
   for (int i = 0; i < 8; i++) ms[i] = (i < 4) ? acc[i] / reps : 0.0;
   for (int i = 0; i < neb; i++)
   {
-    GeneralData *g = (GeneralData *)eles[i]->general;
+    GeneralData *g = eles[i]->general;
     if (!g || !g->stamps) continue;
     long long h[16 * 16];
     HFX_HIP(hipMemcpy(h, g->stamps, sizeof h, hipMemcpyDeviceToHost));
@@ -1565,14 +1468,14 @@ void general_kernel_bytes(hfx_eles *const *eles, int neb, double *bytes)
                             + nu * nf + 2 * nfp * nf);                                                       // div, norm_tdisf, Fn w
     bytes[2] += ne * (8.0 * (nfp * nf + nfp * nf + 0.5 * nfp * nd + nfp + nfp * nf) + 4.0 * nfp);            // disu, Fn, normal(left), tdA r; tconf w
     bytes[3] += ne * 8.0 * (3 * nu * nf + nu + 2 * nfp * nf + 3 * nu * nf + nfp * nf);                       // u0,u1,div,detjac,tconf,ntd r; u0,u1,div,disu w
-    if (e->ctx->opt.fold_general)
+    const GeneralPlan pl = general_plan(e);
+    if (pl.fold)
     {
       // folded correction: norm_tdisf is neither written (flux kernel) nor read (update kernel)
       bytes[1] -= ne * 8.0 * nfp * nf;
       bytes[3] -= ne * 8.0 * nfp * nf;
     }
-    const GeneralData *g = (const GeneralData *)e->general;
-    if (g && g->nbr && e->ctx->opt.gather_delta && e->ctx->params.viscous && general_batched(e))
+    if (pl.gather)
     {
       // LDG corrections formed in the flux kernel: the pairwise kernel is not launched for the pairs inside the block (the
       // partner values it reads are as many doubles as the corrections it no longer reads) + a partner word per point

@@ -383,6 +383,28 @@ int les_len2_upload(hfx_eles *e, double **dst)
   return 0;
 }
 
+int calc_time_step_blocks(hfx_eles *const *eles, int neb)
+{
+  hfx_ctx *ctx = eles[0]->ctx;
+  if (ctx->params.dt_type != 1 && ctx->params.dt_type != 2) return 0;
+  double dt_min = 1e12;
+  for (int i = 0; i < neb; i++)
+  {
+    if (calc_time_step(eles[i], nullptr)) return 1;
+    dt_min = std::min(dt_min, ctx->params.dt);
+  }
+  ctx->params.dt = dt_min;
+  return 0;
+}
+
+int first_stage_closure_filter(hfx_eles *const *eles, int neb, bool refresh_svv)
+{
+  for (int i = 0; i < neb; i++)
+    if (eles[i]->les_ready && eles[i]->les.sgs_model >= 2 &&
+        (hfx_eles_calc_sgs_terms(eles[i]) || (refresh_svv && eles[i]->les.sgs_model == 3 && hfx_eles_extrapolate_solution(eles[i]))))
+      return 1;
+  return 0;
+}
 } // namespace hfx
 
 using namespace hfx;
@@ -1801,21 +1823,6 @@ int hfx_CalcResidual(hfx_eles *e, hfx_inters *const *faces, int nfb)
 {
   HFX_CHECK(e, "NULL eles");
   return hfx_CalcResidual_blocks(&e, 1, faces, nfb);
-}
-
-// calc_time_step over several blocks: the minimum over the blocks (src/solver.cpp:498-505)
-static int calc_time_step_blocks(hfx_eles *const *eles, int neb)
-{
-  hfx_ctx *ctx = eles[0]->ctx;
-  if (ctx->params.dt_type != 1 && ctx->params.dt_type != 2) return 0;
-  double dt_min = 1e12;
-  for (int i = 0; i < neb; i++)
-  {
-    if (calc_time_step(eles[i], nullptr)) return 1;
-    dt_min = std::min(dt_min, ctx->params.dt);
-  }
-  ctx->params.dt = dt_min;
-  return 0;
 }
 
 int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int n_steps, int fused)

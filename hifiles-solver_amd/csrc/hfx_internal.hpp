@@ -15,6 +15,7 @@ namespace hfx
 
 void set_error(const char *fmt, ...);
 struct FusedData;
+struct GeneralData;
 
 #define HFX_HIP(call)                                                                          \
   do                                                                                           \
@@ -229,7 +230,7 @@ struct hfx_eles
   void *tensor_ops = nullptr; // hfx::TensorOps: 1-D factors of the over-integration / shock-capturing matrices
   // fused-path private data (built lazily)
   hfx::FusedData *fused = nullptr;
-  void *general = nullptr; // hfx::GeneralData: the general (non-tensor-product) fused stage (general.hip)
+  hfx::GeneralData *general = nullptr; // the general (non-tensor-product) fused stage (general.hip)
   std::vector<hfx_inters *> faces_attached;
 };
 
@@ -276,8 +277,13 @@ struct hfx_comm
 namespace hfx
 {
 // calc_time_step (src/solver.cpp:484-549) for one block: dt_type 1 sets params.dt to the minimum CFL step (over the ranks
-// of `comm` when given), dt_type 2 refreshes HFX_DT_LOCAL; dt_type 0: nothing (comm.hip)
+// of `comm` when given), dt_type 2 refreshes HFX_DT_LOCAL; dt_type 0: nothing (comm.hip).  _blocks: the minimum over several
+// blocks of one rank (src/solver.cpp:498-505; hfx.hip)
 int calc_time_step(hfx_eles *e, hfx_comm *comm);
+int calc_time_step_blocks(hfx_eles *const *eles, int neb);
+// first stage of a step (src/solver.cpp:55-62): calc_sgs_terms of every block with a filtering closure (hfx.hip).  SVV replaces the state;
+// refresh_svv: extrapolate it again at once (general_run_steps; deferred does so through fpts_valid, partitioned blocks refuse SVV: false)
+int first_stage_closure_filter(hfx_eles *const *eles, int neb, bool refresh_svv);
 // run_input.ramp_counter++ after a time step for the boundary blocks with a ramping group (src/HiFiLES.cpp:224-225)
 void advance_ramp_counters(hfx_inters *const *faces, int nfb);
 // RK stages per time step of adv_type (src/HiFiLES.cpp:143-150)
