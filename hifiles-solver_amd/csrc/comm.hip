@@ -267,7 +267,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
   const bool visc = ctx->params.viscous != 0;
   PartitionedSplit s; // the steps of this stage, and its plan
   if (s.init(e, int_faces, n_int, mpi_faces, n_mpi, rk)) return 1;
-  const SplitPlan &pl = s.pl; // projected: variant 3 sends the projected viscous flux
+  const SplitPlan &pl = s.stage->pl; // projected: variant 3 sends the projected viscous flux
   // third message: the SGS flux (src/solver.cpp:168-178,203-206) -- variant 2 only; in variant 3 it is part of the projected flux
   const bool les = e->les_ready && !pl.projected;
   hipStream_t st = ctx->stream, cs = comm->stream;
@@ -291,27 +291,27 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
     // need nothing from the neighbours, so the solution exchange runs beside them --, then the elements with, whose projected
     // fluxes then leave beside the other half (and the interior common-flux kernel)
     const bool split_flux = ctx->opt.split_flux && pl.split_flux && n_mpi > 0;
-    if (split_flux && s.element_kernel(Part::flux_list_1)) return 1;
+    if (split_flux && s.stage->flux_kernel(EleList::interior_1)) return 1;
     if (wait_exchange(comm, 0, n_mpi)) return 1;
-    if (s.element_kernel(split_flux ? Part::flux_list_b : Part::flux)) return 1;
+    if (s.stage->element_kernels(split_flux ? EleList::partition : EleList::all)) return 1;
     HFX_HIP(hipEventRecord(comm->packed[1], st));
     HFX_HIP(hipStreamWaitEvent(cs, comm->packed[1], 0));
     if (s.pack_projected_flux(cs)) return 1;
     if (start_exchange(comm, mpi_faces, n_mpi, 1, true, true)) return 1;
     if (s.partition_common_fluxes(cs)) return 1;
     HFX_HIP(hipEventRecord(comm->received[1], cs));
-    if (split_flux && s.element_kernel(Part::flux_list_2)) return 1;
-    if (s.interior_common_fluxes()) return 1;
+    if (split_flux && s.stage->flux_kernel(EleList::interior_2)) return 1;
+    if (s.stage->common_fluxes()) return 1;
     if (wait_exchange(comm, 1, n_mpi)) return 1;
     // the update: first the elements with partition-face points, whose new flux-point solution is packed and sent (communication
     // stream) while the others are updated -- the exchange the next stage's flux kernel waits for is hidden behind them
     const bool split_update = ctx->opt.split_update && pl.split_update && n_mpi > 0;
-    if (s.update(split_update ? Part::update_list_b : Part::update)) return 1; // (the whole update: + shock capturing)
+    if (s.update(split_update ? EleList::partition : EleList::all)) return 1; // (the whole update: + shock capturing)
     HFX_HIP(hipEventRecord(comm->packed[0], st));
     HFX_HIP(hipStreamWaitEvent(cs, comm->packed[0], 0));
     if (s.pack_solution(cs)) return 1;
     if (start_exchange(comm, mpi_faces, n_mpi, 0, false, true)) return 1;
-    return split_update ? s.update(Part::update_list_i) : 0;
+    return split_update ? s.update(EleList::interior) : 0;
   }
   // ---- everything on the compute stream (optionally timed): the five phases of hfx_stage_partitioned with the exchanges between
   if (T) HFX_HIP(hipEventRecord(T->ph[0], st));
@@ -321,7 +321,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
   const bool pieces = T && pl.projected && visc; // the element kernel bracketed on its own
   if (visc && s.partition_ldg(st)) return 1;
   if (pieces) HFX_HIP(hipEventRecord(T->fk[0], st));
-  if ((pl.projected || visc) && s.element_kernel()) return 1;
+  if ((pl.projected || visc) && s.stage->element_kernels()) return 1;
   if (pieces) HFX_HIP(hipEventRecord(T->fk[1], st));
   if (visc && (pl.projected ? s.pack_projected_flux(st) : s.pack_gradient(st))) return 1;
   if (visc && les && s.pack_sgs_flux(st)) return 1;
@@ -333,7 +333,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
     if (T) HFX_HIP(hipEventRecord(T->x1[1], cs));
   }
   if (T) HFX_HIP(hipEventRecord(T->ph[2], st));
-  if (s.interior_common_fluxes()) return 1;
+  if (s.stage->common_fluxes()) return 1;
   if (!pl.projected && s.partition_common_invflux(st)) return 1;
   if (T) HFX_HIP(hipEventRecord(T->ph[3], st));
   if (visc && wait_exchange(comm, 1, n_mpi)) return 1;

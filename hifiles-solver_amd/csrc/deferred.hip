@@ -206,12 +206,12 @@ static void make_plan(hfx_ctx *ctx, const std::vector<DeferCall> &log, DeferPlan
   }
   if (tensor)
   {
-    if (split_deferred_prepare(e0, P.faces.data(), (int)P.faces.size(), mpi))
+    SplitPlan pl;
+    if (ensure_fused_tables(e0, P.faces.data(), (int)P.faces.size(), mpi) || split_stage_plan(e0, P.faces.data(), (int)P.faces.size(), ctx->fused_mode, &pl))
     {
       P.why = hfx_last_error();
       return;
     }
-    if (e0->over_int_ready && split_plan(e0, P.faces.data(), (int)P.faces.size(), ctx->fused_mode).variant != 3) { P.why = "the split variant that keeps the gradients (LES, fused mode 2) has no over-integration"; return; }
     P.kind = mpi ? DeferPlan::Kind::split_partitioned : DeferPlan::Kind::split;
     return;
   }

@@ -1,4 +1,5 @@
-// fused_hex.hip -- the split fused stage for tensor-product elements (hexes, quads): table setup, launchers, RK loops.
+// fused_hex.hip -- the split fused stage for tensor-product elements (hexes, quads): table setup (fused_build), the plan
+// (split_plan), one stage as named steps (SplitStage::make and SplitStageT, one instantiation per element size), RK loops.
 // Kernels: split_common.hpp (shared helpers), split2_kernels.hpp (variant 2), split3_kernels.hpp (variant 3, the default),
 // split_partitioned.hpp (the steps of a stage on a partitioned block).
 //
@@ -62,14 +63,25 @@ static int tensor_n(const hfx_eles *e)
   return 0;
 }
 
-// runtime form of split3_fits
+// The element sizes (n_dims, points per direction) the split stage is instantiated for: every dispatch on the element size
+// applies a macro X(ND, N) to this list
+#define HFX_SPLIT_SIZES(X) X(3, 2) X(3, 3) X(3, 4) X(3, 5) X(3, 6) X(3, 7) X(3, 8) X(2, 2) X(2, 3) X(2, 4) X(2, 5) X(2, 6) X(2, 7) X(2, 8)
+
+// runtime forms of split3_fits and loader_wave_fits
 static bool split3_fits_rt(int nd, int N)
 {
-#define HFX_S3F(ND_, N_) \
+#define HFX_X(ND_, N_) \
   if (nd == ND_ && N == N_) return split3_fits<ND_, N_>();
-  HFX_S3F(3, 2) HFX_S3F(3, 3) HFX_S3F(3, 4) HFX_S3F(3, 5) HFX_S3F(3, 6) HFX_S3F(3, 7) HFX_S3F(3, 8)
-  HFX_S3F(2, 2) HFX_S3F(2, 3) HFX_S3F(2, 4) HFX_S3F(2, 5) HFX_S3F(2, 6) HFX_S3F(2, 7) HFX_S3F(2, 8)
-#undef HFX_S3F
+  HFX_SPLIT_SIZES(HFX_X)
+#undef HFX_X
+  return false;
+}
+static bool loader_wave_fits_rt(int nd, int N)
+{
+#define HFX_X(ND_, N_) \
+  if (nd == ND_ && N == N_) return loader_wave_fits<ND_, N_>();
+  HFX_SPLIT_SIZES(HFX_X)
+#undef HFX_X
   return false;
 }
 
@@ -150,32 +162,10 @@ static int build_packed(hfx_eles *e, FusedData *F, const std::vector<double> &o1
 
 static int dispatch_build_packed(hfx_eles *e, FusedData *F, int N, const std::vector<double> &o1v, const std::vector<int> &o1i)
 {
-  if (e->n_dims == 3)
-  {
-    switch (N)
-    {
-    case 2: return build_packed<3, 2>(e, F, o1v, o1i);
-    case 3: return build_packed<3, 3>(e, F, o1v, o1i);
-    case 4: return build_packed<3, 4>(e, F, o1v, o1i);
-    case 5: return build_packed<3, 5>(e, F, o1v, o1i);
-    case 6: return build_packed<3, 6>(e, F, o1v, o1i);
-    case 7: return build_packed<3, 7>(e, F, o1v, o1i);
-    case 8: return build_packed<3, 8>(e, F, o1v, o1i);
-    }
-  }
-  else
-  {
-    switch (N)
-    {
-    case 2: return build_packed<2, 2>(e, F, o1v, o1i);
-    case 3: return build_packed<2, 3>(e, F, o1v, o1i);
-    case 4: return build_packed<2, 4>(e, F, o1v, o1i);
-    case 5: return build_packed<2, 5>(e, F, o1v, o1i);
-    case 6: return build_packed<2, 6>(e, F, o1v, o1i);
-    case 7: return build_packed<2, 7>(e, F, o1v, o1i);
-    case 8: return build_packed<2, 8>(e, F, o1v, o1i);
-    }
-  }
+#define HFX_X(ND_, N_) \
+  if (e->n_dims == ND_ && N == N_) return build_packed<ND_, N_>(e, F, o1v, o1i);
+  HFX_SPLIT_SIZES(HFX_X)
+#undef HFX_X
   set_error("fused path: no kernel for N = %d, n_dims = %d", N, e->n_dims);
   return 1;
 }
@@ -594,16 +584,6 @@ static int les_len2_build(hfx_eles *e)
   return les_len2_upload(e, &F->les_len2);
 }
 
-// runtime form of loader_wave_fits
-static bool loader_wave_fits_rt(int nd, int N)
-{
-#define HFX_LWF(ND_, N_) \
-  if (nd == ND_ && N == N_) return loader_wave_fits<ND_, N_>();
-  HFX_LWF(3, 2) HFX_LWF(3, 3) HFX_LWF(3, 4) HFX_LWF(3, 5) HFX_LWF(3, 6) HFX_LWF(2, 2) HFX_LWF(2, 3) HFX_LWF(2, 4) HFX_LWF(2, 5) HFX_LWF(2, 6) HFX_LWF(2, 7) HFX_LWF(2, 8)
-#undef HFX_LWF
-  return false;
-}
-
 // What the split stage runs on this block when `requested_variant` is asked for (SplitPlan): from the options, the block's fused
 // tables (fused_build; without them no sum-factorised form is planned), its flags and array sizes, its face blocks.
 SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int requested_variant)
@@ -683,52 +663,134 @@ SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int r
   return p;
 }
 
-template <int ND, int N>
-static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, SplitEleArgs &ea, Part part, const SplitPlan &pl)
+int split_stage_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int requested_variant, SplitPlan *pl)
 {
-  FusedData *F = e->fused;
-  hipStream_t st = e->ctx->stream;
-  const Phys P = e->ctx->phys();
-  const long plane_f = (long)e->n_fpts * e->n_eles;
-  const hfx_ctx::Options &opt = e->ctx->opt;
-  // persistent grids: split_grid_per_cu workgroups per CU, 0 = as many as are resident (element_grid)
-  const int per_cu = opt.split_grid_per_cu;
-  const int flux_per_cu = opt.flux_grid_per_cu > 0 ? opt.flux_grid_per_cu : per_cu;
-  constexpr int TB = SGeo<ND, N>::TB;
+  *pl = split_plan(e, faces, nfb, requested_variant);
+  HFX_CHECK(!e->over_int_ready || pl->variant == 3,
+            "the split variant that keeps the gradients (fused 2, which LES without the in-kernel closure selects) has no over-integration");
+  return 0;
+}
+
+// what the element kernels of both variants take alike: geometry, state, the RK coefficients of this stage
+template <class Args>
+static void stage_args(Args &a, const hfx_eles *e, int in_step, bool write_div)
+{
+  const hfx_params &p = e->ctx->params;
+  a.n_eles = e->n_eles;
+  a.o1m_dim = e->fused->o1m_dim;
+  a.detjac_upts = e->detjac_upts; a.JGinv_upts = e->JGinv_upts;
+  a.detjac_fpts = e->detjac_fpts; a.JGinv_fpts = e->JGinv_fpts;
+  a.u0 = e->arr[HFX_DISU_UPTS0]; a.u1 = e->arr[HFX_DISU_UPTS1];
+  a.delta = e->arr[HFX_DELTA_DISU_FPTS]; a.tconf = e->arr[HFX_NORM_TCONF_FPTS];
+  a.disu_next = e->fused->disu_alt;
+  a.src = e->src_nonzero ? e->arr[HFX_SRC_UPTS] : nullptr;
+  a.dt_local = e->arr[HFX_DT_LOCAL];
+  a.nan_flag = e->nan_flag;
+  a.P = e->ctx->phys();
+  a.adv_type = p.adv_type; a.in_step = in_step; a.dt_local_on = p.dt_type == 2; a.dt = p.dt;
+  a.rk_a = (p.adv_type >= 3) ? p.RK_a[in_step] : 0.0;
+  a.rk_b = (p.adv_type >= 3) ? p.RK_b[in_step] : 0.0;
+  a.need_u1 = (p.adv_type >= 3) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
+  a.write_div = write_div ? 1 : 0;
+}
+
+// the pairs of one interior-face block for a pairwise kernel; false: none
+template <class Args>
+static bool face_pairs(Args &a, const hfx_inters *f)
+{
+  a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
+  a.L = f->L; a.R = f->R;
+  return a.npairs > 0;
+}
+
+// f(RS) with the Riemann solver of a pairwise common-flux kernel (face_flux_kernel, face_flux2_kernel) as a constant
+template <class F>
+static void with_riemann_solver(int riemann, F f)
+{
+  if (riemann == 0)
+    f(std::integral_constant<int, 0>{});
+  else if (riemann == 2)
+    f(std::integral_constant<int, 2>{});
+  else
+    f(std::integral_constant<int, 3>{});
+}
+
+// Over-integration folded into the divergence (src/solver.cpp:82-91): the sum-factorised kernel hands the loader-wave flux kernel
+// sum_l Dc[l] tdisf_l -- the de-aliased flux's whole contribution to (div_tdisf - opp_3 norm_tdisf), n_fields values per solution
+// point (tensor_ops.hip).  Dc[d] = D - c3[d][0] (L1 Lf)[d][0]^T - c3[d][1] (L1 Lf)[d][1]^T, as the flux kernel's prologue forms
+// it (split3_kernels.hpp), from the host copy of the tensor-product tables
+template <int ND, int N>
+static std::vector<double> over_int_fold_matrices(const std::vector<double> &c)
+{
+  using T = TGeo<ND, N>;
+  std::vector<double> Dc((size_t)ND * N * N);
+  for (int d = 0; d < ND; d++)
+    for (int mp = 0; mp < N; mp++)
+      for (int m = 0; m < N; m++)
+      {
+        const double ta = c[T::C_3 + (d * 2 + 0) * N + mp] * (c[T::C_L1 + (d * 2 + 0) * N] * c[T::C_LF + (d * 2 + 0) * N + m]);
+        const double tb = c[T::C_3 + (d * 2 + 1) * N + mp] * (c[T::C_L1 + (d * 2 + 1) * N] * c[T::C_LF + (d * 2 + 1) * N + m]);
+        Dc[((size_t)d * N + mp) * N + m] = c[T::C_D + mp * N + m] - ta - tb;
+      }
+  return Dc;
+}
+
+// SplitStage for one element size: the arguments and the launches
+template <int ND, int N>
+struct SplitStageT final : SplitStage
+{
+  static constexpr int TB = SGeo<ND, N>::TB;
   // variant 3's element kernels exist for the sizes they fit only (split3_fits); split_plan sends the others to variant 2
-  constexpr bool V3 = split3_fits<ND, N>();
-  HFX_CHECK(V3 || pl.variant == 2, "split variant 3 does not fit %d-D elements with %d points per direction: run variant 2", ND, N);
-  auto face_args = [&](hfx_inters *f) {
-    SplitFaceArgs a{};
-    a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
-    a.L = f->L; a.R = f->R; a.meta = F->meta; a.plane_f = plane_f;
-    a.disu = e->arr[HFX_DISU_FPTS]; a.grad = e->arr[HFX_GRAD_DISU_FPTS]; a.fnorm = e->norm_fpts; a.tdA = e->tdA_fpts;
-    a.delta = e->arr[HFX_DELTA_DISU_FPTS]; a.tconf = e->arr[HFX_NORM_TCONF_FPTS];
-    a.sgsf = (e->les_ready && pl.variant == 2) ? e->arr[HFX_SGSF_FPTS] : nullptr;
-    a.jac_fpts = e->Jacobian_fpts; a.detjac_fpts = e->detjac_fpts;
-    a.P = P;
-    return a;
-  };
-  Split2Args e2{};
-  if (pl.variant == 3)
+  static constexpr bool V3 = split3_fits<ND, N>();
+  FusedData *const F = e->fused;
+  const hipStream_t st = e->ctx->stream;
+  const Phys P = e->ctx->phys();
+  // persistent grids: split_grid_per_cu workgroups per CU, 0 = as many as are resident (element_grid)
+  const int per_cu = e->ctx->opt.split_grid_per_cu;
+  const int flux_per_cu = e->ctx->opt.flux_grid_per_cu > 0 ? e->ctx->opt.flux_grid_per_cu : per_cu;
+  Split2Args e2{};      // variant 3
+  SplitEleArgs ea{};    // variant 2
+  SplitFaceArgs fa{};   // face_delta_kernel, face_flux_kernel: all but the block's pairs (face_pairs)
+  Split2FaceArgs fa2{}; // face_flux2_kernel: likewise
+  SplitStageT(hfx_eles *e_, hfx_inters *const *faces_, int nfb_, const SplitPlan &pl_) : SplitStage(e_, faces_, nfb_, pl_) {}
+
+  int init(int in_step, bool write_div) override
   {
+    HFX_CHECK(V3 || pl.variant == 2, "split variant 3 does not fit %d-D elements with %d points per direction: run variant 2", ND, N);
+    const long plane_f = (long)e->n_fpts * e->n_eles;
+    fa.meta = F->meta; fa.plane_f = plane_f;
+    fa.disu = e->arr[HFX_DISU_FPTS]; fa.grad = e->arr[HFX_GRAD_DISU_FPTS]; fa.fnorm = e->norm_fpts; fa.tdA = e->tdA_fpts;
+    fa.delta = e->arr[HFX_DELTA_DISU_FPTS]; fa.tconf = e->arr[HFX_NORM_TCONF_FPTS];
+    fa.sgsf = (e->les_ready && pl.variant == 2) ? e->arr[HFX_SGSF_FPTS] : nullptr;
+    fa.jac_fpts = e->Jacobian_fpts; fa.detjac_fpts = e->detjac_fpts;
+    fa.P = P;
+    if (pl.variant == 2)
+    {
+      stage_args(ea, e, in_step, write_div);
+      ea.grad_upts = e->arr[HFX_GRAD_DISU_UPTS]; ea.grad_fpts = e->arr[HFX_GRAD_DISU_FPTS];
+      ea.div_out = e->arr[HFX_DIV_TCONF_UPTS];
+      ea.sgsf_upts = e->les_ready ? e->arr[HFX_SGSF_UPTS] : nullptr;
+      return 0;
+    }
+    const hfx_ctx::Options &opt = e->ctx->opt;
     if (opt.flux_stamps && !F->stamps)
     {
       HFX_HIP(hipMalloc((void **)&F->stamps, sizeof(long long) * 64));
       HFX_HIP(hipMemset(F->stamps, 0, sizeof(long long) * 64));
     }
     if (!F->fn_fpts) HFX_HIP(hipMalloc((void **)&F->fn_fpts, sizeof(double) * (size_t)plane_f * e->n_fields));
-    e2.n_eles = ea.n_eles;
+    if (pl.les && les_len2_build(e)) return 1;
+    if (pl.oi_fold && !tensor_over_int_folded(e) && tensor_over_int_set_fold(e, over_int_fold_matrices<ND, N>(F->h_coef).data())) return 1;
+    stage_args(e2, e, in_step, write_div);
     e2.xcd_order = opt.xcd_order ? 1 : 0;
-    e2.pk_g = F->pk_g; e2.pk_r = F->pk_r; e2.tab_g = F->tab_g; e2.tab_r = F->tab_r; e2.o1m_dim = F->o1m_dim;
-    e2.detjac_upts = ea.detjac_upts; e2.JGinv_upts = ea.JGinv_upts; e2.detjac_fpts = ea.detjac_fpts;
-    e2.JGinv_fpts = ea.JGinv_fpts; e2.norm_fpts = e->norm_fpts;
-    e2.u0 = ea.u0; e2.u1 = ea.u1; e2.delta = ea.delta; e2.tconf = ea.tconf;
-    e2.fn_fpts = F->fn_fpts; e2.ntd_fpts = e->arr[HFX_NORM_TDISF_FPTS]; e2.div = ea.div_out;
+    e2.pk_g = F->pk_g; e2.pk_r = F->pk_r; e2.tab_g = F->tab_g; e2.tab_r = F->tab_r;
+    e2.norm_fpts = e->norm_fpts;
+    e2.fn_fpts = F->fn_fpts; e2.ntd_fpts = e->arr[HFX_NORM_TDISF_FPTS]; e2.div = e->arr[HFX_DIV_TCONF_UPTS];
     e2.folded = pl.flux != FluxForm::dictionary_rows ? 1 : 0;
-    e2.disu_next = ea.disu_next;
     e2.grad_upts = nullptr;
     e2.grad_fpts = pl.bdy_grad ? e->arr[HFX_GRAD_DISU_FPTS] : nullptr; // boundary points only
+    // polynomial de-aliasing: tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u), or its folded form (over_int)
+    e2.tdisf_in = e->over_int_ready ? e->arr[HFX_TDISF_UPTS] : nullptr;
     e2.meta = F->meta;
     e2.stamps = F->stamps;
     e2.stamp_it = std::max(2, opt.flux_stamps);
@@ -736,17 +798,18 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
     e2.light_short = opt.light_wave_short ? 1 : 0;
     e2.o3v = e->opp_3.ell_val; e2.o3i = e->opp_3.ell_idx; e2.o3w = std::max(e->opp_3.nnz_max, 1);
     e2.o0v = e->opp_0.ell_val; e2.o0i = e->opp_0.ell_idx; e2.o0w = std::max(e->opp_0.nnz_max, 1);
-    e2.src = ea.src; e2.dt_local = ea.dt_local; e2.nan_flag = ea.nan_flag; e2.P = ea.P;
-    e2.adv_type = ea.adv_type; e2.in_step = ea.in_step; e2.dt_local_on = ea.dt_local_on; e2.write_div = ea.write_div;
-    e2.need_u1 = ea.need_u1; e2.dt = ea.dt; e2.rk_a = ea.rk_a; e2.rk_b = ea.rk_b;
     e2.les = e->les; e2.tdA_fpts = e->tdA_fpts;
-    if (pl.les && les_len2_build(e)) return 1;
     e2.les_len2 = F->les_len2;
     e2.nbr = pl.gather ? F->nbr : nullptr;
     e2.disu = e->arr[HFX_DISU_FPTS];
+    fa2.meta = F->meta; fa2.plane_f = plane_f;
+    fa2.disu = fa.disu; fa2.fn = F->fn_fpts; fa2.fnorm = fa.fnorm; fa2.tdA = fa.tdA; fa2.tconf = fa.tconf; fa2.P = P;
+    return 0;
   }
-  if (P.viscous && (part == Part::stage || part == Part::ldg))
+
+  int ldg() override
   {
+    if (!P.viscous) return 0;
     for (int b = 0; b < nfb; b++)
     {
       if (faces[b]->is_bdy)
@@ -756,231 +819,185 @@ static int launch_split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, Sp
         continue;
       }
       if (!pl.face_delta) continue; // (the flux kernel reads the partner's flux-point solution itself)
-      const SplitFaceArgs a = face_args(faces[b]);
-      if (a.npairs == 0) continue;
-      hipLaunchKernelGGL((face_delta_kernel<ND>), dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, st, a);
+      if (!face_pairs(fa, faces[b])) continue;
+      hipLaunchKernelGGL((face_delta_kernel<ND>), dim3((unsigned)((fa.npairs + 255) / 256)), dim3(256), 0, st, fa);
     }
+    HFX_HIP(hipGetLastError());
+    return 0;
   }
-  if (pl.variant == 3)
+
+  // the loader-wave form with the plan's flags (instantiated only for the sizes it fits)
+  template <bool OI, bool LES>
+  void loader_wave()
   {
+    constexpr bool fits = loader_wave_fits<ND, N>();
+    if (pl.gather)
+      LoaderWaveLaunch<ND, N, OI, true, LES, fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+    else
+      LoaderWaveLaunch<ND, N, OI, false, LES, fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+  }
+  template <int WV, bool BUF, bool OI>
+  void register_pipeline()
+  {
+    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, WV, BUF, OI, false>),
+                       dim3(element_grid<split_flux_tensor_kernel<ND, N, WV, BUF, OI, false>>(e, TB, per_cu)), dim3(TB), 0, st, e2, F->t_coef, F->t_idx);
+  }
+
+  // (partitioned blocks: the solution exchange runs beside the launch on interior_1, the exchange of the projected fluxes
+  // beside the one on interior_2)
+  int flux_kernel(EleList list) override
+  {
+    HFX_CHECK(pl.variant == 3, "split stage: the flux kernel is a step of variant 3");
     if constexpr (V3)
     {
-      // Over-integration (src/solver.cpp:82-91).  With the loader-wave flux kernel the sum-factorised kernel hands over
-      // sum_l Dc[l] tdisf_l -- the de-aliased flux's whole contribution to (div_tdisf - opp_3 norm_tdisf), n_fields values per
-      // solution point (tensor_ops.hip) -- which that kernel adds to its divergence; otherwise tdisf_upts itself.
-      auto run_over_int = [&]() -> int {
-        if (!pl.oi_fold) return hfx_eles_evaluate_invFlux_over_int(e);
-        if (!tensor_over_int_folded(e))
-        {
-          // Dc[d] = D - c3[d][0] (L1 Lf)[d][0]^T - c3[d][1] (L1 Lf)[d][1]^T, as the flux kernel's prologue forms it (split3_kernels.hpp)
-          using T = TGeo<ND, N>;
-          const std::vector<double> &c = F->h_coef;
-          std::vector<double> Dc((size_t)ND * N * N);
-          for (int d = 0; d < ND; d++)
-            for (int mp = 0; mp < N; mp++)
-              for (int m = 0; m < N; m++)
-              {
-                const double ta = c[T::C_3 + (d * 2 + 0) * N + mp] * (c[T::C_L1 + (d * 2 + 0) * N] * c[T::C_LF + (d * 2 + 0) * N + m]);
-                const double tb = c[T::C_3 + (d * 2 + 1) * N + mp] * (c[T::C_L1 + (d * 2 + 1) * N] * c[T::C_LF + (d * 2 + 1) * N + m]);
-                Dc[((size_t)d * N + mp) * N + m] = c[T::C_D + mp * N + m] - ta - tb;
-              }
-          if (tensor_over_int_set_fold(e, Dc.data())) return 1;
-        }
-        return tensor_over_int_launch(e, true);
-      };
-      if (part == Part::over_int_only && e->over_int_ready && run_over_int()) return 1;
-      // the flux kernel on a part of the elements (partitioned blocks, hfx_run_steps_partitioned): the first half of the elements
-      // without partition-face points, those with, the second half -- the solution exchange runs beside the first launch, the
-      // exchange of the projected fluxes beside the third
-      const bool flux_part = part == Part::flux_list_1 || part == Part::flux_list_b || part == Part::flux_list_2;
-      e2.ele_list = nullptr;
-      e2.n_list = 0;
-      if (part == Part::flux_list_1) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i1; }
-      if (part == Part::flux_list_b) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
-      if (part == Part::flux_list_2) { e2.ele_list = F->upd_list_i ? F->upd_list_i + F->n_list_i1 : nullptr; e2.n_list = F->n_list_i - F->n_list_i1; }
-      if (flux_part && e2.n_list == 0) return 0;
-      HFX_CHECK(!flux_part || (e2.ele_list != nullptr && !e->over_int_ready), "split flux kernel on element lists: no lists, or over-integration (which runs on all elements first)");
-      if (part == Part::stage || part == Part::flux || part == Part::flux_no_over_int || flux_part)
+      const bool listed = elements(list, e2.ele_list, e2.n_list);
+      if (listed && e2.n_list == 0) return 0;
+      HFX_CHECK(!listed || (e2.ele_list != nullptr && !e->over_int_ready), "split flux kernel on element lists: no lists, or over-integration (which runs on all elements first)");
+      HFX_CHECK(!pl.oi_fold || pl.flux == FluxForm::loader_wave, "over-integration: the folded form needs the loader-wave flux kernel");
+      HFX_CHECK(!pl.les || (pl.flux == FluxForm::loader_wave && !pl.oi && P.viscous),
+                "split variant 3 with an LES closure needs the loader-wave flux kernel (SplitPlan::les_in_flux): run variant 2");
+      switch (pl.flux)
       {
-        e2.tdisf_in = nullptr;
-        if (e->over_int_ready)
-        {
-          // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
-          if (part != Part::flux_no_over_int && run_over_int()) return 1;
-          e2.tdisf_in = e->arr[HFX_TDISF_UPTS];
-        }
-        HFX_CHECK(!pl.oi_fold || pl.flux == FluxForm::loader_wave, "over-integration: the folded form needs the loader-wave flux kernel");
-        HFX_CHECK(!pl.les || (pl.flux == FluxForm::loader_wave && !pl.oi && P.viscous),
-                  "split variant 3 with an LES closure needs the loader-wave flux kernel (SplitPlan::les_in_flux): run variant 2");
-        constexpr bool lw_fits = loader_wave_fits<ND, N>();
-        auto loader_wave = [&](auto OI, auto LES) {
-          if (pl.gather)
-            LoaderWaveLaunch<ND, N, decltype(OI)::value, true, decltype(LES)::value, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-          else
-            LoaderWaveLaunch<ND, N, decltype(OI)::value, false, decltype(LES)::value, lw_fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
-        };
-  #define HFX_FLUX_LAUNCH(WV_, BUF_, OI_)                                                                                       \
-    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, false>),                                                 \
-                       dim3(element_grid<split_flux_tensor_kernel<ND, N, WV_, BUF_, OI_, false>>(e, TB, per_cu)), dim3(TB), 0, st, \
-                       e2, F->t_coef, F->t_idx)
-        switch (pl.flux)
-        {
-        case FluxForm::loader_wave:
-          if (pl.les)
-            loader_wave(std::false_type{}, std::true_type{});
-          else if (pl.oi)
-            loader_wave(std::true_type{}, std::false_type{});
-          else
-            loader_wave(std::false_type{}, std::false_type{});
-          break;
-        case FluxForm::register_pipeline:
-          if (pl.wv == 3)
-            HFX_FLUX_LAUNCH(3, true, false);
-          else if (pl.buf && pl.oi)
-            HFX_FLUX_LAUNCH(2, true, true);
-          else if (pl.oi)
-            HFX_FLUX_LAUNCH(2, false, true);
-          else if (pl.buf)
-            HFX_FLUX_LAUNCH(2, true, false);
-          else
-            HFX_FLUX_LAUNCH(2, false, false);
-          break;
-        case FluxForm::dictionary_rows:
-          hipLaunchKernelGGL((split_flux_kernel<ND, N>), dim3(element_grid<split_flux_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, e2);
-          break;
-        }
-  #undef HFX_FLUX_LAUNCH
+      case FluxForm::loader_wave:
+        if (pl.les)
+          loader_wave<false, true>();
+        else if (pl.oi)
+          loader_wave<true, false>();
+        else
+          loader_wave<false, false>();
+        break;
+      case FluxForm::register_pipeline:
+        if (pl.wv == 3)
+          register_pipeline<3, true, false>();
+        else if (pl.buf && pl.oi)
+          register_pipeline<2, true, true>();
+        else if (pl.oi)
+          register_pipeline<2, false, true>();
+        else if (pl.buf)
+          register_pipeline<2, true, false>();
+        else
+          register_pipeline<2, false, false>();
+        break;
+      case FluxForm::dictionary_rows:
+        hipLaunchKernelGGL((split_flux_kernel<ND, N>), dim3(element_grid<split_flux_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, e2);
+        break;
       }
+      HFX_HIP(hipGetLastError());
     }
+    return 0;
   }
-  else if (P.viscous && (part == Part::stage || part == Part::flux || part == Part::sgs_only || part == Part::flux_no_sgs))
+
+  int gradient_kernel() override
   {
+    HFX_CHECK(pl.variant == 2, "split stage: the gradient kernel is a step of variant 2");
+    if (!P.viscous) return 0;
     ea.pk = F->pk_g;
     ea.tab = F->tab_g;
-    if (part != Part::sgs_only)
-      hipLaunchKernelGGL((split_gradient_kernel<ND, N>), dim3(element_grid<split_gradient_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, ea);
-    if (e->les_ready && part != Part::flux_no_sgs)
-    {
-      // LES (eddy-viscosity closures): SGS flux at the solution points from the corrected gradient, its extrapolation to
-      // the flux points (src/solver.cpp:162-167); the face kernel adds it to each side, the residual kernel to the total
-      if (hfx_les_sgsf_upts_internal(e)) return 1;
-      if (hfx_les_extrapolate_reference_internal(e)) return 1; // the back-transform happens in the face kernel
-    }
+    hipLaunchKernelGGL((split_gradient_kernel<ND, N>), dim3(element_grid<split_gradient_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, ea);
+    HFX_HIP(hipGetLastError());
+    return 0;
   }
-  if (part == Part::stage || part == Part::faces)
+
+  int common_fluxes() override
   {
     // boundary faces on the side stream, beside the pairwise interior-face kernel: both need the flux kernel's results and
     // write norm_tconf at disjoint points
     bool any_bdy_faces = false;
     for (int b = 0; b < nfb; b++) any_bdy_faces = any_bdy_faces || (faces[b]->is_bdy && faces[b]->n_inters > 0);
-    const bool beside = any_bdy_faces && opt.bdy_beside;
+    const bool beside = any_bdy_faces && e->ctx->opt.bdy_beside;
     if (beside && side_stream_fork(e->ctx)) return 1;
     for (int b = 0; b < nfb; b++)
       if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], P.viscous ? 1 : 0, 1)) return 1;
     if (beside && side_stream_join(e->ctx)) return 1;
     for (int b = 0; b < nfb; b++)
     {
-      if (faces[b]->is_bdy) continue;
-      const SplitFaceArgs a = face_args(faces[b]);
-      if (a.npairs == 0) continue;
-      const unsigned nb = (unsigned)((a.npairs + 255) / 256);
+      if (faces[b]->is_bdy || !face_pairs(fa, faces[b])) continue;
+      const dim3 nb((unsigned)((fa.npairs + 255) / 256));
       if (pl.variant == 3)
       {
-        Split2FaceArgs a2{};
-        a2.npairs = a.npairs; a2.L = a.L; a2.R = a.R; a2.meta = a.meta; a2.plane_f = plane_f;
-        a2.disu = a.disu; a2.fn = F->fn_fpts; a2.fnorm = a.fnorm; a2.tdA = a.tdA; a2.tconf = a.tconf; a2.P = P;
-        if (P.riemann == 0)
-          hipLaunchKernelGGL((face_flux2_kernel<ND, 0>), dim3(nb), dim3(256), 0, st, a2);
-        else if (P.riemann == 2)
-          hipLaunchKernelGGL((face_flux2_kernel<ND, 2>), dim3(nb), dim3(256), 0, st, a2);
-        else
-          hipLaunchKernelGGL((face_flux2_kernel<ND, 3>), dim3(nb), dim3(256), 0, st, a2);
+        face_pairs(fa2, faces[b]);
+        with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL((face_flux2_kernel<ND, decltype(RS)::value>), nb, dim3(256), 0, st, fa2); });
       }
-      else if (P.riemann == 0)
-        hipLaunchKernelGGL((face_flux_kernel<ND, 0>), dim3(nb), dim3(256), 0, st, a);
-      else if (P.riemann == 2)
-        hipLaunchKernelGGL((face_flux_kernel<ND, 2>), dim3(nb), dim3(256), 0, st, a);
       else
-        hipLaunchKernelGGL((face_flux_kernel<ND, 3>), dim3(nb), dim3(256), 0, st, a);
+        with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL((face_flux_kernel<ND, decltype(RS)::value>), nb, dim3(256), 0, st, fa); });
     }
     if (beside && side_stream_wait(e->ctx)) return 1;
+    HFX_HIP(hipGetLastError());
+    return 0;
   }
-  const bool update_part = part == Part::update_list_b || part == Part::update_list_i;
-  if (part == Part::stage || part == Part::update || update_part)
+
+  template <bool BUF>
+  void update_launch(long n_work)
   {
-    if (pl.variant == 3)
-    {
-      if constexpr (V3)
-      {
-        // the update on the elements with partition-face points / on the others (two launches: the first one's flux-point
-        // solution leaves for the neighbours while the second runs); update_list_i comes behind the buffer swap of update_list_b
-        e2.ele_list = nullptr;
-        e2.n_list = 0;
-        if (part == Part::update_list_b) { e2.ele_list = F->upd_list_b; e2.n_list = F->n_list_b; }
-        if (part == Part::update_list_i) { e2.ele_list = F->upd_list_i; e2.n_list = F->n_list_i; e2.disu_next = e->arr[HFX_DISU_FPTS]; }
-        HFX_CHECK(!update_part || e2.ele_list != nullptr || e2.n_list == 0, "split update: no element lists (the block was not built as a partitioned one)");
-        const long n_work = update_part ? e2.n_list : (long)e->n_eles;
-        if (n_work > 0)
-        {
-          if (pl.update_buf)
-          {
-            const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, true>>(e, TB, per_cu, 3));
-            hipLaunchKernelGGL((split_update_kernel<ND, N, true>), dim3(g), dim3(TB), 0, st, e2);
-          }
-          else
-          {
-            const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, false>>(e, TB, per_cu, 3));
-            hipLaunchKernelGGL((split_update_kernel<ND, N, false>), dim3(g), dim3(TB), 0, st, e2);
-          }
-        }
-      }
-    }
-    else
+    // (the streaming update kernel is fastest at three workgroups per CU: element_grid)
+    const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, BUF>>(e, TB, per_cu, 3));
+    hipLaunchKernelGGL((split_update_kernel<ND, N, BUF>), dim3(g), dim3(TB), 0, st, e2);
+  }
+
+  // The buffers of disu_fpts change places behind the first update launch of a stage (all | partition): `interior`, which
+  // follows `partition` (whose flux-point solution leaves for the neighbours meanwhile), writes the buffer that is disu_fpts by then
+  int update(EleList list) override
+  {
+    if (pl.variant == 2)
     {
       ea.pk = F->pk_r;
       ea.tab = F->tab_r;
       hipLaunchKernelGGL((split_residual_kernel<ND, N>), dim3(element_grid<split_residual_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, ea);
     }
+    else if constexpr (V3)
+    {
+      const bool listed = elements(list, e2.ele_list, e2.n_list);
+      HFX_CHECK(!listed || e2.ele_list != nullptr || e2.n_list == 0, "split update: no element lists (the block was not built as a partitioned one)");
+      const long n_work = listed ? e2.n_list : (long)e->n_eles;
+      if (n_work > 0) pl.update_buf ? update_launch<true>(n_work) : update_launch<false>(n_work);
+    }
+    HFX_HIP(hipGetLastError());
+    if (list == EleList::all || list == EleList::partition) std::swap(e->arr[HFX_DISU_FPTS], F->disu_alt);
+    return 0;
   }
-  HFX_HIP(hipGetLastError());
-  return 0;
+};
+
+std::unique_ptr<SplitStage> SplitStage::make(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_step, bool write_div, const SplitPlan &pl)
+{
+  const int N = tensor_n(e); // (one of the sizes: the block has fused tables)
+  std::unique_ptr<SplitStage> s;
+#define HFX_X(ND_, N_) \
+  if (e->n_dims == ND_ && N == N_) s = std::make_unique<SplitStageT<ND_, N_>>(e, faces, nfb, pl);
+  HFX_SPLIT_SIZES(HFX_X)
+#undef HFX_X
+  if (!s || s->init(in_step, write_div)) s.reset();
+  return s;
 }
 
-static int split_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_step, bool last_stage, Part part, const SplitPlan &pl)
+bool SplitStage::elements(EleList list, const int *&ele_list, long &n_list) const
 {
-  FusedData *F = e->fused;
-  const hfx_params &p = e->ctx->params;
-  SplitEleArgs a{};
-  a.n_eles = e->n_eles;
-  a.o1m_dim = F->o1m_dim;
-  a.detjac_upts = e->detjac_upts; a.JGinv_upts = e->JGinv_upts;
-  a.detjac_fpts = e->detjac_fpts; a.JGinv_fpts = e->JGinv_fpts;
-  a.u0 = e->arr[HFX_DISU_UPTS0]; a.u1 = e->arr[HFX_DISU_UPTS1];
-  a.delta = e->arr[HFX_DELTA_DISU_FPTS]; a.tconf = e->arr[HFX_NORM_TCONF_FPTS];
-  a.disu_next = F->disu_alt;
-  a.grad_upts = e->arr[HFX_GRAD_DISU_UPTS]; a.grad_fpts = e->arr[HFX_GRAD_DISU_FPTS];
-  a.div_out = e->arr[HFX_DIV_TCONF_UPTS];
-  a.sgsf_upts = (e->les_ready && pl.variant == 2) ? e->arr[HFX_SGSF_UPTS] : nullptr;
-  a.src = e->src_nonzero ? e->arr[HFX_SRC_UPTS] : nullptr;
-  a.dt_local = e->arr[HFX_DT_LOCAL];
-  a.nan_flag = e->nan_flag;
-  a.P = e->ctx->phys();
-  a.adv_type = p.adv_type; a.in_step = in_step; a.dt_local_on = p.dt_type == 2; a.dt = p.dt;
-  a.rk_a = (p.adv_type >= 3) ? p.RK_a[in_step] : 0.0;
-  a.rk_b = (p.adv_type >= 3) ? p.RK_b[in_step] : 0.0;
-  a.need_u1 = (p.adv_type >= 3) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
-  a.write_div = last_stage ? 1 : 0;
-  const int N = tensor_n(e);
-  int rc = 1;
-#define HFX_SPLIT_CASE(ND_, N_) \
-  if (e->n_dims == ND_ && N == N_) rc = launch_split_stage<ND_, N_>(e, faces, nfb, a, part, pl);
-  HFX_SPLIT_CASE(3, 2) HFX_SPLIT_CASE(3, 3) HFX_SPLIT_CASE(3, 4) HFX_SPLIT_CASE(3, 5) HFX_SPLIT_CASE(3, 6) HFX_SPLIT_CASE(3, 7) HFX_SPLIT_CASE(3, 8)
-  HFX_SPLIT_CASE(2, 2) HFX_SPLIT_CASE(2, 3) HFX_SPLIT_CASE(2, 4) HFX_SPLIT_CASE(2, 5) HFX_SPLIT_CASE(2, 6) HFX_SPLIT_CASE(2, 7) HFX_SPLIT_CASE(2, 8)
-#undef HFX_SPLIT_CASE
-  if (rc) return 1;
-  // (the buffer swap: behind the whole update, or behind its first part -- the second part then writes the new buffer by name)
-  if (part == Part::stage || part == Part::update || part == Part::update_list_b) std::swap(e->arr[HFX_DISU_FPTS], e->fused->disu_alt);
-  return 0;
+  const FusedData *F = e->fused;
+  switch (list)
+  {
+  case EleList::all: ele_list = nullptr; n_list = 0; break;
+  case EleList::interior_1: ele_list = F->upd_list_i; n_list = F->n_list_i1; break;
+  case EleList::partition: ele_list = F->upd_list_b; n_list = F->n_list_b; break;
+  case EleList::interior_2: ele_list = F->upd_list_i ? F->upd_list_i + F->n_list_i1 : nullptr; n_list = F->n_list_i - F->n_list_i1; break;
+  case EleList::interior: ele_list = F->upd_list_i; n_list = F->n_list_i; break;
+  }
+  return list != EleList::all;
+}
+
+int SplitStage::over_int()
+{
+  HFX_CHECK(pl.variant == 3, "split stage: over-integration is a step of variant 3");
+  if (!e->over_int_ready) return 0;
+  return pl.oi_fold ? tensor_over_int_launch(e, true) : hfx_eles_evaluate_invFlux_over_int(e);
+}
+
+int SplitStage::sgs_kernels()
+{
+  // LES (eddy-viscosity closures): SGS flux at the solution points from the corrected gradient, its extrapolation to
+  // the flux points (src/solver.cpp:162-167); the face kernel adds it to each side, the residual kernel to the total
+  // (the back-transform of the extrapolated flux happens in the face kernel)
+  HFX_CHECK(pl.variant == 2, "split stage: the SGS kernels are a step of variant 2");
+  if (!e->ctx->params.viscous || !e->les_ready) return 0;
+  return hfx_les_sgsf_upts_internal(e) || hfx_les_extrapolate_reference_internal(e);
 }
 
 // shock capturing inside a split-path stage: disu_fpts must follow the filtered state.  The sum-factorised kernel
@@ -992,7 +1009,7 @@ static int shock_capture_keep_fpts(hfx_eles *e)
   return hfx_eles_extrapolate_solution(e);
 }
 
-int split_deferred_prepare(hfx_eles *e, hfx_inters *const *faces, int nfb, bool partitioned)
+int ensure_fused_tables(hfx_eles *e, hfx_inters *const *faces, int nfb, bool partitioned)
 {
   HFX_CHECK(e->n_eles > 0, "fused path: empty element block");
   if (e->fused && e->fused->built) return 0;
@@ -1001,22 +1018,19 @@ int split_deferred_prepare(hfx_eles *e, hfx_inters *const *faces, int nfb, bool 
 
 int split_deferred_stage(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_step, bool write_div, bool shock)
 {
-  if (split_deferred_prepare(e, faces, nfb, false)) return 1;
-  const SplitPlan pl = split_plan(e, faces, nfb, e->ctx->fused_mode);
-  HFX_CHECK(!e->over_int_ready || pl.variant == 3, "the split variant that keeps the gradients (fused 2, which LES without the in-kernel closure selects) has no over-integration");
-  if (split_stage(e, faces, nfb, in_step, write_div, Part::stage, pl)) return 1;
+  SplitPlan pl;
+  if (ensure_fused_tables(e, faces, nfb, false) || split_stage_plan(e, faces, nfb, e->ctx->fused_mode, &pl)) return 1;
+  const auto stage = SplitStage::make(e, faces, nfb, in_step, write_div, pl);
+  if (!stage || stage->run()) return 1;
   // the filter changes disu_upts(0) after the stage: redo the flux-point solution of the new state
   return shock ? shock_capture_keep_fpts(e) : 0;
 }
 
 int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps, int variant)
 {
-  HFX_CHECK(e->n_eles > 0, "fused path: empty element block");
-  if (!e->fused || !e->fused->built)
-    if (fused_build(e, faces, nfb)) return 1;
   // (an LES closure that variant 3 cannot evaluate in its flux kernel, and element sizes it does not fit, run variant 2)
-  const SplitPlan pl = split_plan(e, faces, nfb, variant);
-  HFX_CHECK(!e->over_int_ready || pl.variant == 3, "the split variant that keeps the gradients (fused 2, which LES without the in-kernel closure selects) has no over-integration");
+  SplitPlan pl;
+  if (ensure_fused_tables(e, faces, nfb, false) || split_stage_plan(e, faces, nfb, variant, &pl)) return 1;
   if (n_steps <= 0) return 0;
   const int nst = n_rk_stages(e->ctx->params);
   if (hfx_eles_extrapolate_solution(e)) return 1;
@@ -1025,19 +1039,12 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
     if (calc_time_step(e, nullptr)) return 1; /* src/HiFiLES.cpp:198 */
     for (int rk = 0; rk < nst; rk++)
     {
-      if (rk == 0 && e->les_ready && e->les.sgs_model >= 2)
-      {
-        // first stage of a step: filtered solution / Leonard terms (src/solver.cpp:55-62); the SVV closure replaces the
-        // state, whose flux-point values the previous stage's update kernel has already written: redo them
-        if (hfx_eles_calc_sgs_terms(e)) return 1;
-        if (e->les.sgs_model == 3 && hfx_eles_extrapolate_solution(e)) return 1;
-      }
-      if (split_stage(e, faces, nfb, rk, rk == nst - 1, Part::stage, pl)) return 1;
-      if (e->shock_ready)
-      {
-        // the filter changes disu_upts(0) after the stage: redo the flux-point solution of the new state
-        if (shock_capture_keep_fpts(e)) return 1;
-      }
+      // (the SVV closure replaces the state, whose flux-point values the previous stage's update kernel has already written)
+      if (rk == 0 && first_stage_closure_filter(&e, 1, true)) return 1;
+      const auto stage = SplitStage::make(e, faces, nfb, rk, rk == nst - 1, pl);
+      if (!stage || stage->run()) return 1;
+      // the filter changes disu_upts(0) after the stage: redo the flux-point solution of the new state
+      if (e->shock_ready && shock_capture_keep_fpts(e)) return 1;
     }
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
   }
@@ -1047,52 +1054,59 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
 int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps, double *ms, char *names, int names_len,
                        int variant)
 {
-  if (!e->fused || !e->fused->built)
-    if (fused_build(e, faces, nfb)) return 1;
+  if (ensure_fused_tables(e, faces, nfb, false)) return 1;
   const SplitPlan pl = split_plan(e, faces, nfb, variant);
   const int nst = n_rk_stages(e->ctx->params);
   hipStream_t st = e->ctx->stream;
+  // The steps of a stage in launch order, each with its slot of `ms`; the element kernels in two pieces when the block
+  // de-aliases (variant 3: the over-integration kernel, then the flux kernel) or carries an LES closure (variant 2: the gradient
+  // kernel, then the SGS kernels) -- the second kernel's time goes to slot 4
+  struct Timed { int slot; int (*step)(SplitStage &); };
+  const bool oi = pl.over_int != OverInt::none, sgs = pl.variant == 2 && e->les_ready && e->ctx->params.viscous;
+  std::vector<Timed> steps = {{0, [](SplitStage &s) { return s.ldg(); }}};
+  if (oi)
+  {
+    steps.push_back({4, [](SplitStage &s) { return s.over_int(); }});
+    steps.push_back({1, [](SplitStage &s) { return s.flux_kernel(); }});
+  }
+  else if (sgs)
+  {
+    steps.push_back({1, [](SplitStage &s) { return s.gradient_kernel(); }});
+    steps.push_back({4, [](SplitStage &s) { return s.sgs_kernels(); }});
+  }
+  else
+    steps.push_back({1, [](SplitStage &s) { return s.element_kernels(); }});
+  steps.push_back({2, [](SplitStage &s) { return s.common_fluxes(); }});
+  steps.push_back({3, [](SplitStage &s) { return s.update(); }});
+  const int np = (int)steps.size();
   // one set of events per repetition and ONE synchronisation at the end: a host synchronisation per stage let the queue
   // run dry, and the first kernel after it (the flux kernel) then measured 10 % slower than in the running pipeline
-  // the parts of a stage in launch order; part 2 in two pieces when the block de-aliases (variant 3: the over-integration kernel,
-  // then the flux kernel) or carries an LES closure (variant 2: the gradient kernel, then the SGS kernels) -- slot 4 of `ms`
-  const bool oi = pl.over_int != OverInt::none, sgs = pl.variant == 2 && e->les_ready && e->ctx->params.viscous;
-  std::vector<Part> parts = {Part::ldg};
-  if (oi) { parts.push_back(Part::over_int_only); parts.push_back(Part::flux_no_over_int); }
-  else if (sgs) { parts.push_back(Part::flux_no_sgs); parts.push_back(Part::sgs_only); }
-  else parts.push_back(Part::flux);
-  parts.push_back(Part::faces);
-  parts.push_back(Part::update);
-  const int np = (int)parts.size();
   std::vector<hipEvent_t> ev((size_t)reps * (np + 1));
   for (auto &x : ev) HFX_HIP(hipEventCreate(&x));
   if (hfx_eles_extrapolate_solution(e)) return 1;
-  double acc[9] = {};
   for (int r = 0; r < reps; r++)
   {
     const int rk = r % nst;
+    const auto stage = SplitStage::make(e, faces, nfb, rk, rk == nst - 1, pl);
+    if (!stage) return 1;
     for (int q = 0; q < np; q++)
     {
       HFX_HIP(hipEventRecord(ev[(np + 1) * r + q], st));
-      if (split_stage(e, faces, nfb, rk, rk == nst - 1, parts[q], pl)) return 1;
+      if (steps[q].step(*stage)) return 1;
     }
     HFX_HIP(hipEventRecord(ev[(np + 1) * r + np], st));
   }
   HFX_HIP(hipStreamSynchronize(st));
+  double acc[8] = {};
   for (int r = 0; r < reps; r++)
     for (int q = 0; q < np; q++)
     {
       float t = 0;
       HFX_HIP(hipEventElapsedTime(&t, ev[(np + 1) * r + q], ev[(np + 1) * r + q + 1]));
-      acc[(int)parts[q]] += t;
+      acc[steps[q].slot] += t;
     }
   for (auto &x : ev) (void)hipEventDestroy(x);
-  for (int i = 0; i < 8; i++) ms[i] = 0.0;
-  ms[0] = acc[(int)Part::ldg] / reps;
-  ms[1] = (acc[(int)Part::flux] + acc[(int)Part::flux_no_over_int] + acc[(int)Part::flux_no_sgs]) / reps; // part 2's element kernel alone
-  ms[2] = acc[(int)Part::faces] / reps;
-  ms[3] = acc[(int)Part::update] / reps;
-  ms[4] = (acc[(int)Part::over_int_only] + acc[(int)Part::sgs_only]) / reps; // over-integration kernel | SGS kernels
+  for (int i = 0; i < 8; i++) ms[i] = acc[i] / reps;
   if (e->fused->stamps)
   {
     long long h[64];

@@ -20,6 +20,12 @@ void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant = 2);
 // or when variant 3 does not fit its element size (hexes from P6 on), else 3.  Needs the block's fused tables (fused_build)
 struct SplitPlan;
 SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int requested_variant);
+// the plan of a stage that is about to run: split_plan, and the one refusal of what no variant of the split stage computes
+// (over-integration where variant 2 runs).  Non-zero: refused, message in hfx_last_error
+int split_stage_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int requested_variant, SplitPlan *pl);
+// builds the block's fused tables for these face blocks unless they exist; non-zero (message in hfx_last_error) when the
+// block does not qualify for the split fused stage.  partitioned: flux points without a registered face are partition-face points
+int ensure_fused_tables(hfx_eles *e, hfx_inters *const *faces, int nfb, bool partitioned);
 // the one-sided partition-face kernels (kernels_mpi.hpp)
 enum class MpiKernel
 {
@@ -35,9 +41,6 @@ enum class MpiKernel
 // one of them on a block of the GENERAL fused stage, whose projected viscous flux is `fn` (compute stream)
 int mpi_launch_general(hfx_eles *e, hfx_inters *f, MpiKernel k, const double *fn);
 // ---- the deferred scheduler's pieces (deferred.hip) ----
-// builds the block's fused tables for these face blocks unless they exist; non-zero (message in hfx_last_error) when the
-// block does not qualify for the split fused stage.  partitioned: flux points without a registered face are partition-face points
-int split_deferred_prepare(hfx_eles *e, hfx_inters *const *faces, int nfb, bool partitioned);
 // ONE stage of the split fused path (the variant that split_plan names for the context's fused mode) on a block whose
 // disu_fpts belongs to the current state; write_div: store div_tconf_upts; shock: shock_capture follows AdvanceSolution
 // (src/HiFiLES.cpp:214-216)

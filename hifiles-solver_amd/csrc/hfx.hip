@@ -1690,7 +1690,7 @@ int hfx_stage_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, 
   hipStream_t st = e->ctx->stream;
   PartitionedSplit s;
   if (s.init(e, int_faces, n_int, mpi_faces, n_mpi, in_step)) return 1;
-  const bool v3 = s.pl.variant == 3; // fluxes in the element kernel, the projected flux on the wire; else the gradients kept and sent
+  const bool v3 = s.stage->pl.variant == 3; // fluxes in the element kernel, the projected flux on the wire; else the gradients kept and sent
   switch (phase)
   {
   case 0:
@@ -1698,14 +1698,14 @@ int hfx_stage_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, 
     return first ? s.pack_solution(st) : 0;
   case 1: return viscous ? s.interior_ldg() : 0;
   case 2:
-    if (!viscous) return v3 ? s.element_kernel() : 0;
+    if (!viscous) return v3 ? s.stage->element_kernels() : 0;
     if (s.partition_ldg(st)) return 1;
-    if (s.element_kernel()) return 1;
+    if (s.stage->element_kernels()) return 1;
     if (v3) return s.pack_projected_flux(st);
     if (s.pack_gradient(st)) return 1;
     return e->les_ready ? s.pack_sgs_flux(st) : 0;
   case 3:
-    if (s.interior_common_fluxes()) return 1;
+    if (s.stage->common_fluxes()) return 1;
     return v3 ? 0 : s.partition_common_invflux(st);
   default:
     if (v3 ? s.partition_common_fluxes(st) : (viscous && s.partition_common_viscflux(st))) return 1;

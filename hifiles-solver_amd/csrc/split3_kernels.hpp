@@ -458,7 +458,7 @@ constexpr bool loader_wave_fits()
 // Does variant 3 fit this element size at all?  Its flux kernel holds one element's state, LDG corrections, gradient,
 // metrics and fluxes in LDS: the working set of ONE loader-wave workgroup must fit the CU's 160 KiB, and the dictionary
 // rows must be the 16-bit ones.  Hexes from P6 on (191 kB, P7 276 kB) do not: they run variant 2 (split_plan), and no
-// variant-3 kernel is instantiated for them (launch_split_stage).
+// variant-3 kernel is instantiated for them (SplitStageT).
 template <int ND, int N>
 constexpr bool split3_fits()
 {

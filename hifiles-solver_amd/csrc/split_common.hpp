@@ -2,6 +2,7 @@
 // stage (SplitPlan).  The kernels themselves (split2_kernels.hpp, split3_kernels.hpp) are included by fused_hex.hip only -- one
 // translation unit, so that every kernel is instantiated once; comm.hip and deferred.hip read the plan.
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "fused_hex.hpp"
@@ -76,61 +77,89 @@ struct SplitPlan
   const char *names = "", *extra_names = "";
 };
 
-// The parts of a stage that split_stage runs: the whole stage, or one of its pieces (the phases of a partitioned block, the
-// launches timed on their own).  The timing parts index the accumulators of split_time_kernels.
-enum class Part
+// The elements a launch of the flux or update kernel works on: all, or one of a partitioned block's lists (FusedData)
+enum class EleList
 {
-  stage,            // the whole stage
-  ldg,              // the LDG common solution at the boundary and interior faces
-  flux,             // the element kernel: over-integration + flux kernel (variant 3) | gradient kernel + SGS kernels (variant 2)
-  faces,            // the common fluxes at the boundary and interior faces
-  update,           // the update (variant 3) | residual (variant 2) kernel
-  over_int_only,    // timing: the over-integration kernel of `flux` alone
-  sgs_only,         // timing: the SGS kernels of `flux` (variant 2 with an LES closure) alone
-  flux_no_over_int, // timing: `flux` without the over-integration kernel
-  flux_no_sgs,      // timing: `flux` without the SGS kernels
-  flux_list_1,      // the flux kernel on the first half of the elements without partition-face points (upd_list_i)
-  flux_list_b,      // ... on the elements with partition-face points (upd_list_b)
-  flux_list_2,      // ... on the second half of upd_list_i
-  update_list_b,    // the update on the elements with partition-face points
-  update_list_i,    // the update on the others (behind the buffer swap of update_list_b)
+  all,
+  interior_1, // the first part of the elements without partition-face points: upd_list_i[0 .. n_list_i1)
+  partition,  // the elements with partition-face points: upd_list_b
+  interior_2, // the rest of upd_list_i
+  interior,   // upd_list_i
 };
 
-// ONE stage of the split fused path on a PARTITIONED block as named steps (split_partitioned.hpp).  init() does once what every
-// step relies on: argument checks, the block's fused tables, the plan, the stage range.  Which steps a stage takes is the caller's
-// choice from the plan (pl.variant, pl.projected, pl.split_flux, pl.split_update) and from `viscous`.  st: the stream of the
-// one-sided partition-face kernels; everything else runs on the context's compute stream.
+// ONE RK stage of the split path on one block whose fused tables exist (ensure_fused_tables), as named steps on the compute
+// stream.  make() does once what every step relies on: the element size's implementation (fused_hex.hip), the kernel arguments
+// of the variant that runs, the face arguments, the allocations of variant 3 (fn_fpts, stamps, les_len2) and the folded
+// over-integration matrices.  The arguments name the disu_fpts buffers as they are when the stage is made, and update()
+// exchanges them: a SplitStage is made before the stage's first launch and does not outlive the stage.
+struct SplitStage
+{
+  hfx_eles *const e;
+  hfx_inters *const *const faces;
+  const int nfb;
+  const SplitPlan pl;
+  // write_div: store div_tconf_upts (the last stage of a step).  Null: error (message in hfx_last_error)
+  static std::unique_ptr<SplitStage> make(hfx_eles *e, hfx_inters *const *faces, int nfb, int in_step, bool write_div, const SplitPlan &pl);
+  virtual ~SplitStage() = default;
+  // viscous: the ghost states of the boundary faces (-> inviscid common flux, LDG common solution); face_delta_kernel where
+  // the plan says so (pl.face_delta)
+  virtual int ldg() = 0;
+  // variant 3: the over-integration kernel where the block de-aliases; the flux kernel, on a partitioned block in up to three
+  // launches (interior_1 needs nothing from the neighbours; an empty list launches nothing)
+  int over_int();
+  virtual int flux_kernel(EleList list = EleList::all) = 0;
+  // variant 2, viscous: the gradient kernel; with an LES closure the SGS flux at the solution points and its extrapolation
+  virtual int gradient_kernel() = 0;
+  int sgs_kernels();
+  // everything element-local between the two cuts of the stage, for the variant that runs
+  // (over-integration works on all elements: a list with it is refused by flux_kernel, before anything is launched)
+  int element_kernels(EleList list = EleList::all) { return pl.variant == 3 ? (list == EleList::all && over_int()) || flux_kernel(list) : gradient_kernel() || sgs_kernels(); }
+  // the viscous fluxes of the boundary faces (option bdy_beside: on the side stream) and the pairwise common-flux kernel
+  virtual int common_fluxes() = 0;
+  // the update (variant 3) | residual (variant 2) kernel: RK update and the NEW state's flux-point solution, written to the
+  // second disu_fpts buffer.  The buffers change places behind the first update launch of a stage (all | partition), so
+  // `interior`, which follows `partition`, writes the buffer that is disu_fpts by then.  An empty list launches nothing.
+  virtual int update(EleList list = EleList::all) = 0;
+  int run() { return ldg() || element_kernels() || common_fluxes() || update(); }
+protected:
+  SplitStage(hfx_eles *e_, hfx_inters *const *faces_, int nfb_, const SplitPlan &pl_) : e(e_), faces(faces_), nfb(nfb_), pl(pl_) {}
+  virtual int init(int in_step, bool write_div) = 0;
+  // the list's elements (false: `all`)
+  bool elements(EleList list, const int *&ele_list, long &n_list) const;
+};
+
+// ONE stage of the split fused path on a PARTITIONED block (split_partitioned.hpp): a SplitStage for the elements and the
+// interior and boundary faces, and the steps at the partition faces.  init() does once what every step relies on: argument
+// checks, the block's fused tables, the plan, the stage range, the stage.  Which steps a stage takes is the caller's choice from
+// the plan (stage->pl: variant, projected, split_flux, split_update) and from `viscous`.  st: the stream of the one-sided
+// partition-face kernels; everything else runs on the context's compute stream.  The steps of a viscous stage, in order:
+//   [pack_solution]  interior_ldg  partition_ldg  stage->element_kernels  pack_projected_flux | pack_gradient [pack_sgs_flux]
+//   stage->common_fluxes  partition_common_fluxes | partition_common_invflux, partition_common_viscflux  update  pack_solution
 struct PartitionedSplit
 {
   hfx_eles *e = nullptr;
-  hfx_inters *const *int_faces = nullptr, *const *mpi_faces = nullptr;
-  int n_int = 0, n_mpi = 0, in_step = 0;
-  bool last = false; // the last stage of a step (stores div_tconf_upts)
-  SplitPlan pl;
+  hfx_inters *const *mpi_faces = nullptr;
+  int n_mpi = 0, in_step = 0;
+  std::unique_ptr<SplitStage> stage;
   int init(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi, int in_step);
   int pack_solution(hipStream_t st) const { return mpi_all(MpiKernel::pack_solution, st); }
   // viscous: the LDG common solution at the boundary and interior faces (at the first stage behind the Leonard terms of an LES
   // closure; the SVV closure is refused: it filters a state whose flux-point values have left already) | at the partition faces
   int interior_ldg() const;
   int partition_ldg(hipStream_t st) const { return mpi_all(MpiKernel::ldg_delta, st); }
-  // the element kernel (Part::flux; variant 3 allocates fn_fpts on first use), or with pl.split_flux one of its three launches:
-  // Part::flux_list_1 (needs nothing from the neighbours), Part::flux_list_b (behind partition_ldg), Part::flux_list_2
-  int element_kernel(Part part = Part::flux) const;
   // the second message: variant 3 the projected viscous flux (behind the element kernel) | variant 2 the corrected gradient
   // and, with an LES closure, a third message: the physical SGS flux (src/solver.cpp:168-178)
   int pack_projected_flux(hipStream_t st) const { return mpi_all(MpiKernel::pack_projected_flux, st); }
   int pack_gradient(hipStream_t st) const { return mpi_all(MpiKernel::pack_gradient, st); }
   int pack_sgs_flux(hipStream_t st) const { return mpi_all(MpiKernel::pack_sgs_flux, st); }
-  // the common fluxes at the boundary and interior faces | at the partition faces: variant 3 from both sides' solution and
-  // projected flux; variant 2 the inviscid part (needs the solution only) and, viscous, the part from the gradients
-  int interior_common_fluxes() const;
+  // the common fluxes at the partition faces: variant 3 from both sides' solution and projected flux; variant 2 the inviscid
+  // part (needs the solution only) and, viscous, the part from the gradients
   int partition_common_fluxes(hipStream_t st) const { return mpi_all(MpiKernel::common_flux_projected, st); }
   int partition_common_invflux(hipStream_t st) const { return mpi_all(MpiKernel::common_invflux, st); }
   int partition_common_viscflux(hipStream_t st) const { return mpi_all(MpiKernel::common_viscflux, st); }
-  // the update (Part::update: residual, RK, the new flux-point solution, then shock capturing where the block has it), or with
-  // pl.split_update its two launches: Part::update_list_b (the elements with partition-face points, whose new flux-point
-  // solution can then leave) and Part::update_list_i (the others)
-  int update(Part part = Part::update) const;
+  // the stage's update, whole (then shock capturing where the block has it) or with pl.split_update in two launches: `partition`
+  // (whose new flux-point solution can then leave) and `interior`
+  int update(EleList list = EleList::all) const;
 private:
   int mpi_all(MpiKernel k, hipStream_t st) const; // kernel k on every partition-face block
 };

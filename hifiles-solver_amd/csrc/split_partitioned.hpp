@@ -4,10 +4,12 @@
 // file's launchers).
 #pragma once
 
-// one of the one-sided partition-face kernels on one block, on stream `st`.  variant: the split variant of the block (split_plan).
-// (the arguments are filled at every launch: fn_fpts exists only once the element kernel of variant 3 has run)
+// one of the one-sided partition-face kernels on one block, on stream `st`.  sgs_ref: the SGS flux at the flux points is in
+// reference space (the split variant 2 keeps sgsf_fpts so: the kernels take it to physical space; variant 3: the SGS flux is part
+// of the projected flux Fn the kernels move anyway).  The arguments are filled at every launch: pack_solution behind the update
+// packs the NEW state, e->arr[HFX_DISU_FPTS] as it is then
 template <int ND>
-static int mpi_launch(hfx_eles *e, hfx_inters *f, MpiKernel k, int variant, hipStream_t st, const double *fn_override = nullptr)
+static int mpi_launch(hfx_eles *e, hfx_inters *f, MpiKernel k, bool sgs_ref, hipStream_t st, const double *fn_override = nullptr)
 {
   if (f->n_inters == 0) return 0;
   MpiArgs a{};
@@ -22,10 +24,8 @@ static int mpi_launch(hfx_eles *e, hfx_inters *f, MpiKernel k, int variant, hipS
   a.out_disu = f->out_disu; a.out_grad = f->out_grad; a.in_disu = f->in_disu; a.in_grad = f->in_grad;
   a.fn = fn_override ? fn_override : (e->fused ? e->fused->fn_fpts : nullptr);
   a.P = e->ctx->phys();
-  if (e->les_ready && variant == 2)
+  if (e->les_ready && sgs_ref)
   {
-    // the split path (variant 2) keeps sgsf_fpts in reference space: the partition-face kernels take it to physical space
-    // (variant 3: the SGS flux is part of the projected flux Fn the kernels move anyway)
     if (hfx_mpi_sgsf_buffers_internal(f)) return 1;
     a.sgsf = e->arr[HFX_SGSF_FPTS]; a.jac_fpts = e->Jacobian_fpts; a.detjac_fpts = e->detjac_fpts;
     a.out_sgsf = f->out_sgsf; a.in_sgsf = f->in_sgsf; a.sgs_ref = 1;
@@ -46,32 +46,32 @@ static int mpi_launch(hfx_eles *e, hfx_inters *f, MpiKernel k, int variant, hipS
   return 0;
 }
 
-// the one-sided partition-face kernels for a block of the general fused stage (three-dimensional; fn: that block's projected flux)
+// the one-sided partition-face kernels for a block of the general fused stage (three-dimensional; fn: that block's projected flux).
+// (sgs_ref as the SPLIT plan of the block's fused mode would have it: it decides whether a block with a closure gets SGS buffers)
 int mpi_launch_general(hfx_eles *e, hfx_inters *f, MpiKernel k, const double *fn)
 {
-  return mpi_launch<3>(e, f, k, split_plan(e, nullptr, 0, e->ctx->fused_mode).variant, e->ctx->stream, fn);
+  return mpi_launch<3>(e, f, k, split_plan(e, nullptr, 0, e->ctx->fused_mode).variant == 2, e->ctx->stream, fn);
 }
 
-int PartitionedSplit::init(hfx_eles *e_, hfx_inters *const *int_faces_, int n_int_, hfx_inters *const *mpi_faces_, int n_mpi_, int in_step_)
+int PartitionedSplit::init(hfx_eles *e_, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces_, int n_mpi_, int in_step_)
 {
-  e = e_; int_faces = int_faces_; n_int = n_int_; mpi_faces = mpi_faces_; n_mpi = n_mpi_; in_step = in_step_;
-  HFX_CHECK(e->n_eles > 0, "fused path: empty element block");
+  e = e_; mpi_faces = mpi_faces_; n_mpi = n_mpi_; in_step = in_step_;
   for (int b = 0; b < n_mpi; b++) HFX_CHECK(mpi_faces[b]->is_mpi && mpi_faces[b]->left == e, "bad partition-face block");
-  if (!e->fused || !e->fused->built)
-    if (fused_build(e, int_faces, n_int, true)) return 1;
+  if (ensure_fused_tables(e, int_faces, n_int, true)) return 1;
   const int nst = n_rk_stages(e->ctx->params);
   HFX_CHECK(in_step >= 0 && in_step < nst, "hfx_stage_partitioned: stage %d out of range", in_step);
-  last = in_step == nst - 1;
   // variant 3: fluxes in the gradient kernel, Fn on the wire; 2 with an LES closure
-  pl = split_plan(e, int_faces, n_int, e->ctx->fused_mode);
-  HFX_CHECK(!e->over_int_ready || pl.variant == 3, "the split variant that keeps the gradients (fused 2, which LES selects) has no over-integration");
-  return 0;
+  SplitPlan pl;
+  if (split_stage_plan(e, int_faces, n_int, e->ctx->fused_mode, &pl)) return 1;
+  stage = SplitStage::make(e, int_faces, n_int, in_step, in_step == nst - 1, pl);
+  return stage ? 0 : 1;
 }
 
 int PartitionedSplit::mpi_all(MpiKernel k, hipStream_t st) const
 {
+  const bool sgs_ref = stage->pl.variant == 2;
   for (int b = 0; b < n_mpi; b++)
-    if ((e->n_dims == 2 ? mpi_launch<2>(e, mpi_faces[b], k, pl.variant, st) : mpi_launch<3>(e, mpi_faces[b], k, pl.variant, st))) return 1;
+    if ((e->n_dims == 2 ? mpi_launch<2>(e, mpi_faces[b], k, sgs_ref, st) : mpi_launch<3>(e, mpi_faces[b], k, sgs_ref, st))) return 1;
   return 0;
 }
 
@@ -83,17 +83,13 @@ int PartitionedSplit::interior_ldg() const
                                      "values have left for the neighbours: run it per method");
     if (hfx_eles_calc_sgs_terms(e)) return 1; // Leonard terms of this step (src/solver.cpp:55-62)
   }
-  return split_stage(e, int_faces, n_int, in_step, false, Part::ldg, pl);
+  return stage->ldg();
 }
 
-int PartitionedSplit::element_kernel(Part part) const { return split_stage(e, int_faces, n_int, in_step, false, part, pl); }
-
-int PartitionedSplit::interior_common_fluxes() const { return split_stage(e, int_faces, n_int, in_step, last, Part::faces, pl); }
-
-int PartitionedSplit::update(Part part) const
+int PartitionedSplit::update(EleList list) const
 {
-  if (split_stage(e, int_faces, n_int, in_step, last, part, pl)) return 1; // residual, RK, new disu_fpts (swaps)
+  if (stage->update(list)) return 1; // residual, RK, new disu_fpts
   // src/HiFiLES.cpp:214-216: the filter changes disu_upts(0) after the WHOLE update (no element lists then: pl.split_update) --
   // redo the flux-point solution
-  return (part == Part::update && e->shock_ready) ? shock_capture_keep_fpts(e) : 0;
+  return (list == EleList::all && e->shock_ready) ? shock_capture_keep_fpts(e) : 0;
 }
