@@ -506,8 +506,7 @@ int hfx_comm_create(hfx_ctx *ctx, const char id[HFX_COMM_ID_BYTES], int nranks, 
       HFX_HIP(hipEventCreateWithFlags(&c->packed[k], hipEventDisableTiming));
       HFX_HIP(hipEventCreateWithFlags(&c->received[k], hipEventDisableTiming));
     }
-    HFX_HIP(hipMalloc((void **)&c->scratch, sizeof(double) * 64));
-    return 0;
+    return c->scratch.alloc(64);
   };
   if (rest())
   {
@@ -539,7 +538,6 @@ int hfx_comm_destroy(hfx_comm *c)
     if (c->packed[k]) (void)hipEventDestroy(c->packed[k]);
     if (c->received[k]) (void)hipEventDestroy(c->received[k]);
   }
-  if (c->scratch) (void)hipFree(c->scratch);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return 0;

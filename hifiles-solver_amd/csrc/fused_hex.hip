@@ -37,20 +37,10 @@ void fused_invalidate(hfx_eles *e)
 {
   if (!e || !e->fused) return;
   e->fused->built = false;
-  if (e->fused->les_len2) { (void)hipFree(e->fused->les_len2); e->fused->les_len2 = nullptr; } // (follows the registered closure)
+  e->fused->les_len2.reset(); // (follows the registered closure)
 }
 
-void fused_destroy(hfx_eles *e)
-{
-  if (!e || !e->fused) return;
-  FusedData *f = e->fused;
-  void *p[] = {f->meta, f->disu_alt, f->fn_fpts, f->t_coef, f->t_idx, f->pk_g, f->pk_r, f->tab_g, f->tab_r, f->o1m_dim, f->nbr, f->les_len2,
-               f->upd_list_b, f->upd_list_i};
-  for (void *q : p)
-    if (q) (void)hipFree(q);
-  delete f;
-  e->fused = nullptr;
-}
+void FusedDelete::operator()(FusedData *p) const { delete p; }
 
 // ---------------------------------------------------------------------------------------
 // host side
@@ -115,13 +105,6 @@ static int pack_rows(std::vector<unsigned> &pk, size_t off, int m, int w, const 
   return 0;
 }
 
-static int upload(void **dst, const void *src, size_t bytes)
-{
-  if (!*dst) HFX_HIP(hipMalloc(dst, std::max<size_t>(bytes, 8)));
-  HFX_HIP(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-
 template <int ND, int N>
 static int build_packed(hfx_eles *e, FusedData *F, const std::vector<double> &o1v, const std::vector<int> &o1i)
 {
@@ -138,8 +121,7 @@ static int build_packed(hfx_eles *e, FusedData *F, const std::vector<double> &o1
     if (pack_rows(pk, G::R_O1, NFP, N, o1v.data(), o1i.data(), N, dict, EPW)) return 1;
     HFX_CHECK(dict.vals.size() <= MAX_TAB, "fused path: operators hold %zu distinct values (> %d)", dict.vals.size(), MAX_TAB);
     dict.vals.resize(MAX_TAB, 0.0);
-    if (upload((void **)&F->pk_r, pk.data(), sizeof(unsigned) * pk.size())) return 1;
-    if (upload((void **)&F->tab_r, dict.vals.data(), sizeof(double) * MAX_TAB)) return 1;
+    if (F->pk_r.upload(pk) || F->tab_r.upload(dict.vals)) return 1;
   }
   if (e->viscous_ops)
   {
@@ -154,8 +136,7 @@ static int build_packed(hfx_eles *e, FusedData *F, const std::vector<double> &o1
     if (pack_rows(pk, G::G_O6, NFP, N, e->opp_6.h_val.data(), e->opp_6.h_idx.data(), hw(e->opp_6), dict, EPW)) return 1;
     HFX_CHECK(dict.vals.size() <= MAX_TAB, "fused path: operators hold %zu distinct values (> %d)", dict.vals.size(), MAX_TAB);
     dict.vals.resize(MAX_TAB, 0.0);
-    if (upload((void **)&F->pk_g, pk.data(), sizeof(unsigned) * pk.size())) return 1;
-    if (upload((void **)&F->tab_g, dict.vals.data(), sizeof(double) * MAX_TAB)) return 1;
+    if (F->pk_g.upload(pk) || F->tab_g.upload(dict.vals)) return 1;
   }
   return 0;
 }
@@ -368,11 +349,9 @@ static int tensor_build(hfx_eles *e, FusedData *F, int N, const std::vector<doub
   idx.insert(idx.end(), pf.begin(), pf.end());
   idx.insert(idx.end(), fdq.begin(), fdq.end());
   idx.insert(idx.end(), fbase.begin(), fbase.end());
-  if (F->t_coef) { (void)hipFree(F->t_coef); F->t_coef = nullptr; }
-  if (F->t_idx) { (void)hipFree(F->t_idx); F->t_idx = nullptr; }
-  if (upload((void **)&F->t_coef, coef.data(), sizeof(double) * coef.size())) return 1;
+  if (F->t_coef.upload(coef)) return 1;
   F->h_coef = coef;
-  if (upload((void **)&F->t_idx, idx.data(), sizeof(int) * idx.size())) return 1;
+  if (F->t_idx.upload(idx)) return 1;
   F->tensor_ok = true;
   return 0;
 }
@@ -396,8 +375,8 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
   // (the packed row entries: 8-bit columns up to 256 points per element, 16-bit ones above -- Geo::WIDE, checked in pack_rows)
   HFX_CHECK(e->n_upts < 65536 && e->n_fpts < 65536, "fused path: column indices must fit 16 bits");
 
-  if (!e->fused) e->fused = new FusedData();
-  FusedData *F = e->fused;
+  if (!e->fused) e->fused.reset(new FusedData());
+  FusedData *F = e->fused.get();
 
   // opp_1 merged over the dimension slabs (row k of opp_1[d] is l_j(fpt_k) * tnorm(d,k): one d per row)
   {
@@ -428,7 +407,7 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
         mi[r + (size_t)nfp * q] = (q < w) ? op.h_idx[r + (size_t)nfp * q] : op.h_idx[r];
       }
     }
-    if (upload((void **)&F->o1m_dim, md.data(), sizeof(int) * md.size())) return 1;
+    if (F->o1m_dim.upload(md)) return 1;
     if (dispatch_build_packed(e, F, N, mv, mi)) return 1;
     // (the sum-factorised tables serve variant 3 only: not built for the sizes it does not fit)
     F->tensor_ok = false;
@@ -484,8 +463,8 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
     for (long o = 0; o < plane_f; o++)
       HFX_CHECK(paired[o], "fused path: flux point %ld belongs to no registered face (partition faces need "
                            "hfx_stage_partitioned / hfx_run_steps_partitioned)", o);
-  for (int **q : {&F->upd_list_b, &F->upd_list_i})
-    if (*q) { (void)hipFree(*q); *q = nullptr; }
+  F->upd_list_b.reset();
+  F->upd_list_i.reset();
   F->n_list_b = F->n_list_i = 0;
   if (allow_unpaired)
   {
@@ -500,10 +479,10 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
     F->n_list_b = (long)lb.size();
     F->n_list_i = (long)li.size();
     F->n_list_i1 = F->n_list_i / 2;
-    if (!lb.empty() && upload((void **)&F->upd_list_b, lb.data(), sizeof(int) * lb.size())) return 1;
-    if (!li.empty() && upload((void **)&F->upd_list_i, li.data(), sizeof(int) * li.size())) return 1;
+    if (!lb.empty() && F->upd_list_b.upload(lb)) return 1;
+    if (!li.empty() && F->upd_list_i.upload(li)) return 1;
   }
-  if (upload((void **)&F->meta, meta.data(), plane_f)) return 1;
+  if (F->meta.upload(meta)) return 1;
   {
     // partner of every interior flux point for the flux kernel that forms the LDG corrections itself:
     // (partner offset << 2) | beta-sign flipped << 1 | this point is the right side;  -1: boundary or partition-face point
@@ -521,10 +500,10 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
         nbr[ir] = (il << 2) | (meta[il] & 2) | 1;
       }
     }
-    if (F->nbr) { (void)hipFree(F->nbr); F->nbr = nullptr; }
-    if (fits && upload((void **)&F->nbr, nbr.data(), sizeof(int) * nbr.size())) return 1;
+    F->nbr.reset();
+    if (fits && F->nbr.upload(nbr)) return 1;
   }
-  if (!F->disu_alt) HFX_HIP(hipMalloc((void **)&F->disu_alt, sizeof(double) * plane_f * e->n_fields));
+  if (F->disu_alt.ensure((size_t)plane_f * e->n_fields)) return 1;
   F->built = true;
   return 0;
 }
@@ -579,9 +558,9 @@ struct LoaderWaveLaunch<ND, N, OI, GA, LES, true>
 // reads it instead of evaluating a cube root per point and stage.
 static int les_len2_build(hfx_eles *e)
 {
-  FusedData *F = e->fused;
+  FusedData *F = e->fused.get();
   if (F->les_len2) return 0;
-  return les_len2_upload(e, &F->les_len2);
+  return les_len2_upload(e, F->les_len2);
 }
 
 // What the split stage runs on this block when `requested_variant` is asked for (SplitPlan): from the options, the block's fused
@@ -589,7 +568,7 @@ static int les_len2_build(hfx_eles *e)
 SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int requested_variant)
 {
   const hfx_ctx::Options &opt = e->ctx->opt;
-  const FusedData *F = (e->fused && e->fused->built) ? e->fused : nullptr;
+  const FusedData *F = (e->fused && e->fused->built) ? e->fused.get() : nullptr;
   const bool viscous = e->ctx->params.viscous != 0, oi = e->over_int_ready;
   const int N = tensor_n(e);
   // the sum-factorised kernels, and the options and element size of their loader-wave form
@@ -742,7 +721,7 @@ struct SplitStageT final : SplitStage
   static constexpr int TB = SGeo<ND, N>::TB;
   // variant 3's element kernels exist for the sizes they fit only (split3_fits); split_plan sends the others to variant 2
   static constexpr bool V3 = split3_fits<ND, N>();
-  FusedData *const F = e->fused;
+  FusedData *const F = e->fused.get();
   const hipStream_t st = e->ctx->stream;
   const Phys P = e->ctx->phys();
   // persistent grids: split_grid_per_cu workgroups per CU, 0 = as many as are resident (element_grid)
@@ -769,16 +748,12 @@ struct SplitStageT final : SplitStage
       stage_args(ea, e, in_step, write_div);
       ea.grad_upts = e->arr[HFX_GRAD_DISU_UPTS]; ea.grad_fpts = e->arr[HFX_GRAD_DISU_FPTS];
       ea.div_out = e->arr[HFX_DIV_TCONF_UPTS];
-      ea.sgsf_upts = e->les_ready ? e->arr[HFX_SGSF_UPTS] : nullptr;
+      ea.sgsf_upts = e->les_ready ? e->arr[HFX_SGSF_UPTS].get() : nullptr;
       return 0;
     }
     const hfx_ctx::Options &opt = e->ctx->opt;
-    if (opt.flux_stamps && !F->stamps)
-    {
-      HFX_HIP(hipMalloc((void **)&F->stamps, sizeof(long long) * 64));
-      HFX_HIP(hipMemset(F->stamps, 0, sizeof(long long) * 64));
-    }
-    if (!F->fn_fpts) HFX_HIP(hipMalloc((void **)&F->fn_fpts, sizeof(double) * (size_t)plane_f * e->n_fields));
+    if (opt.flux_stamps && F->stamps.ensure_zeroed(16 * 16)) return 1; // (a row of 16 per wave: room for every workgroup size)
+    if (F->fn_fpts.ensure((size_t)plane_f * e->n_fields)) return 1;
     if (pl.les && les_len2_build(e)) return 1;
     if (pl.oi_fold && !tensor_over_int_folded(e) && tensor_over_int_set_fold(e, over_int_fold_matrices<ND, N>(F->h_coef).data())) return 1;
     stage_args(e2, e, in_step, write_div);
@@ -800,7 +775,7 @@ struct SplitStageT final : SplitStage
     e2.o0v = e->opp_0.ell_val; e2.o0i = e->opp_0.ell_idx; e2.o0w = std::max(e->opp_0.nnz_max, 1);
     e2.les = e->les; e2.tdA_fpts = e->tdA_fpts;
     e2.les_len2 = F->les_len2;
-    e2.nbr = pl.gather ? F->nbr : nullptr;
+    e2.nbr = pl.gather ? F->nbr.get() : nullptr;
     e2.disu = e->arr[HFX_DISU_FPTS];
     fa2.meta = F->meta; fa2.plane_f = plane_f;
     fa2.disu = fa.disu; fa2.fn = F->fn_fpts; fa2.fnorm = fa.fnorm; fa2.tdA = fa.tdA; fa2.tconf = fa.tconf; fa2.P = P;
@@ -971,7 +946,7 @@ std::unique_ptr<SplitStage> SplitStage::make(hfx_eles *e, hfx_inters *const *fac
 
 bool SplitStage::elements(EleList list, const int *&ele_list, long &n_list) const
 {
-  const FusedData *F = e->fused;
+  const FusedData *F = e->fused.get();
   switch (list)
   {
   case EleList::all: ele_list = nullptr; n_list = 0; break;

@@ -39,18 +39,18 @@ struct GeneralData
 {
   int KU = 0, KF = 0, MU = 0, MF = 0; // n_upts / n_fpts padded to 4 (contraction length) and to 16 (output rows)
   // zero-padded operators, column-major with leading dimension M*: o4/o5/o2 (MU rows), o6/o1/o0 (MF rows), o3 (MU rows)
-  double *o0 = nullptr, *o1[3] = {}, *o2[3] = {}, *o3 = nullptr, *o4[3] = {}, *o5[3] = {}, *o6 = nullptr;
-  unsigned char *meta = nullptr; // (n_fpts, n_eles): bit1 beta sign flipped (LEFT point of a pair), bit2 boundary point
-  double *disu_alt = nullptr;    // second disu_fpts buffer (the update kernel writes the new state's flux-point solution)
-  double *fn_fpts = nullptr;     // (n_fpts, n_eles, n_fields) viscous flux projected on the point's own normal
-  int *nbr = nullptr;            // (n_fpts, n_eles) partner word of every flux point whose pair lies inside this block (GenArgs::nbr)
-  double *o2f[3] = {};           // opp_2[d] - opp_3 opp_1[d], padded like o2: the folded correction (GenArgs::fold)
-  hfx_eles *blocks[4] = {};      // the element blocks the partner words refer to (bits 3:2 of a word), captured at build
+  DevBuf<double> o0, o1[3], o2[3], o3, o4[3], o5[3], o6;
+  DevBuf<unsigned char> meta; // (n_fpts, n_eles): bit1 beta sign flipped (LEFT point of a pair), bit2 boundary point
+  DevBuf<double> disu_alt;    // second disu_fpts buffer (the update kernel writes the new state's flux-point solution)
+  DevBuf<double> fn_fpts;     // (n_fpts, n_eles, n_fields) viscous flux projected on the point's own normal
+  DevBuf<int> nbr;            // (n_fpts, n_eles) partner word of every flux point whose pair lies inside this block (GenArgs::nbr)
+  DevBuf<double> o2f[3];      // opp_2[d] - opp_3 opp_1[d], padded like o2: the folded correction (GenArgs::fold)
+  hfx_eles *blocks[4] = {};   // the element blocks the partner words refer to (bits 3:2 of a word), captured at build
   int n_blocks = 0;
   bool any_bdy = false;
   bool built = false;
-  long long *stamps = nullptr;
-  double *les_len2 = nullptr; // (n_upts, n_eles) squared length scale of an LES closure (les_len2_upload)
+  DevBuf<long long> stamps;
+  DevBuf<double> les_len2; // (n_upts, n_eles) squared length scale of an LES closure (les_len2_upload)
 };
 
 void general_invalidate(hfx_eles *e)
@@ -58,17 +58,7 @@ void general_invalidate(hfx_eles *e)
   if (e && e->general) e->general->built = false;
 }
 
-void general_destroy(hfx_eles *e)
-{
-  if (!e || !e->general) return;
-  GeneralData *g = e->general;
-  void *p[] = {g->o0, g->o1[0], g->o1[1], g->o1[2], g->o2[0], g->o2[1], g->o2[2], g->o3, g->o4[0], g->o4[1], g->o4[2],
-               g->o5[0], g->o5[1], g->o5[2], g->o6, g->meta, g->disu_alt, g->fn_fpts, g->stamps, g->nbr, g->o2f[0], g->o2f[1], g->o2f[2], g->les_len2};
-  for (void *q : p)
-    if (q) (void)hipFree(q);
-  delete g;
-  e->general = nullptr;
-}
+void GeneralDelete::operator()(GeneralData *p) const { delete p; }
 
 // LDS plane [row][16 elements], the element index swizzled by the row
 __device__ __forceinline__ int sw(int row, int col) { return row * GB + (col ^ (row & 15)); }
@@ -975,17 +965,14 @@ static double ldg_switch_host(double beta, const double (&n)[3])
   return beta;
 }
 
-static int padded_operator(double **dst, const Operator &op, int M, int K)
+static int padded_operator(DevBuf<double> &dst, const Operator &op, int M, int K)
 {
   HFX_CHECK(op.present(), "general fused stage: an operator is missing");
   std::vector<double> h((size_t)op.m * op.k), p((size_t)M * K, 0.0);
   HFX_HIP(hipMemcpy(h.data(), op.dense, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
   for (int c = 0; c < op.k; c++)
     for (int r = 0; r < op.m; r++) p[r + (size_t)M * c] = h[r + (size_t)op.m * c];
-  if (*dst) (void)hipFree(*dst);
-  HFX_HIP(hipMalloc((void **)dst, sizeof(double) * p.size()));
-  HFX_HIP(hipMemcpy(*dst, p.data(), sizeof(double) * p.size(), hipMemcpyHostToDevice));
-  return 0;
+  return dst.upload(p);
 }
 
 // the block's index in GENERAL_SIZES, or -1
@@ -1010,17 +997,17 @@ static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_ele
     for (int b = 0; b < nfb; b++)
       HFX_CHECK(!faces[b]->is_mpi || e->les.sgs_model != 3, "general fused stage: the SVV closure on partitioned blocks runs per method");
   }
-  if (!e->general) e->general = new GeneralData();
-  GeneralData *g = e->general;
-  if (e->les_ready && e->les.sgs_model != 3 && les_len2_upload(e, &g->les_len2)) return 1;
+  if (!e->general) e->general.reset(new GeneralData());
+  GeneralData *g = e->general.get();
+  if (e->les_ready && e->les.sgs_model != 3 && les_len2_upload(e, g->les_len2)) return 1;
   const bool visc = e->ctx->params.viscous != 0;
   HFX_CHECK(!visc || e->viscous_ops, "general fused stage: viscous run but the block has no opp_4/5/6");
   const int nu = e->n_upts, nfp = e->n_fpts;
   g->KU = (nu + 3) & ~3; g->KF = (nfp + 3) & ~3; g->MU = (nu + 15) & ~15; g->MF = (nfp + 15) & ~15;
   HFX_CHECK(general_flux_lds_bytes(nu, nfp) <= 160 * 1024, "general fused stage: a batch of this element class (%d solution, %d flux points) does not fit LDS", nu, nfp);
-  if (padded_operator(&g->o0, e->opp_0, g->MF, g->KU) || padded_operator(&g->o3, e->opp_3, g->MU, g->KF)) return 1;
+  if (padded_operator(g->o0, e->opp_0, g->MF, g->KU) || padded_operator(g->o3, e->opp_3, g->MU, g->KF)) return 1;
   for (int d = 0; d < 3; d++)
-    if (padded_operator(&g->o1[d], e->opp_1[d], g->MF, g->KU) || padded_operator(&g->o2[d], e->opp_2[d], g->MU, g->KU)) return 1;
+    if (padded_operator(g->o1[d], e->opp_1[d], g->MF, g->KU) || padded_operator(g->o2[d], e->opp_2[d], g->MU, g->KU)) return 1;
   {
     // the folded operators: O2f[d] = opp_2[d] - opp_3 . opp_1[d] (sum over the flux points in ascending order)
     std::vector<double> o3((size_t)nu * nfp), o1((size_t)nfp * nu), o2((size_t)nu * nu), pad((size_t)g->MU * g->KU);
@@ -1037,17 +1024,14 @@ static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_ele
           for (int j = 0; j < nfp; j++) t += o3[r + (size_t)nu * j] * o1[j + (size_t)nfp * c];
           pad[r + (size_t)g->MU * c] = o2[r + (size_t)nu * c] - t;
         }
-      if (g->o2f[d]) (void)hipFree(g->o2f[d]);
-      g->o2f[d] = nullptr;
-      HFX_HIP(hipMalloc((void **)&g->o2f[d], sizeof(double) * pad.size()));
-      HFX_HIP(hipMemcpy(g->o2f[d], pad.data(), sizeof(double) * pad.size(), hipMemcpyHostToDevice));
+      if (g->o2f[d].upload(pad)) return 1;
     }
   }
   if (visc)
   {
-    if (padded_operator(&g->o6, e->opp_6, g->MF, g->KU)) return 1;
+    if (padded_operator(g->o6, e->opp_6, g->MF, g->KU)) return 1;
     for (int d = 0; d < 3; d++)
-      if (padded_operator(&g->o4[d], e->opp_4[d], g->MU, g->KU) || padded_operator(&g->o5[d], e->opp_5[d], g->MU, g->KF)) return 1;
+      if (padded_operator(g->o4[d], e->opp_4[d], g->MU, g->KU) || padded_operator(g->o5[d], e->opp_5[d], g->MU, g->KF)) return 1;
   }
   // per flux point: the LDG switch of the pair it is the LEFT point of (exact tests on the left normal, decided once),
   // and whether a boundary face owns it; every flux point must belong to exactly one registered face
@@ -1126,21 +1110,17 @@ static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_ele
         any = true;
       }
     }
-    if (g->nbr) { (void)hipFree(g->nbr); g->nbr = nullptr; }
+    g->nbr.reset();
     g->n_blocks = 0;
     if (fits && any)
     {
-      HFX_HIP(hipMalloc((void **)&g->nbr, sizeof(int) * (size_t)plane_f));
-      HFX_HIP(hipMemcpy(g->nbr, nbr.data(), sizeof(int) * (size_t)plane_f, hipMemcpyHostToDevice));
+      if (g->nbr.upload(nbr)) return 1;
       g->n_blocks = neb;
       for (int i = 0; i < neb; i++) g->blocks[i] = eles[i];
     }
   }
-  if (g->meta) (void)hipFree(g->meta);
-  HFX_HIP(hipMalloc((void **)&g->meta, (size_t)plane_f));
-  HFX_HIP(hipMemcpy(g->meta, meta.data(), (size_t)plane_f, hipMemcpyHostToDevice));
-  if (!g->disu_alt) HFX_HIP(hipMalloc((void **)&g->disu_alt, sizeof(double) * plane_f * e->n_fields));
-  if (!g->fn_fpts) HFX_HIP(hipMalloc((void **)&g->fn_fpts, sizeof(double) * plane_f * e->n_fields));
+  if (g->meta.upload(meta)) return 1;
+  if (g->disu_alt.ensure((size_t)plane_f * e->n_fields) || g->fn_fpts.ensure((size_t)plane_f * e->n_fields)) return 1;
   g->built = true;
   return 0;
 }
@@ -1163,7 +1143,7 @@ GeneralPlan general_plan(const hfx_eles *e)
 
 static GenArgs gen_args(hfx_eles *e, const GeneralPlan &pl, int in_step)
 {
-  GeneralData *g = e->general;
+  GeneralData *g = e->general.get();
   const hfx_params &p = e->ctx->params;
   GenArgs a{};
   a.inv_nu = (unsigned)(4294967296ull / (unsigned)e->n_upts) + 1u; a.inv_nfp = (unsigned)(4294967296ull / (unsigned)e->n_fpts) + 1u;
@@ -1193,10 +1173,7 @@ static GenArgs gen_args(hfx_eles *e, const GeneralPlan &pl, int in_step)
   a.rk_a = (p.adv_type >= 3) ? p.RK_a[in_step] : 0.0;
   a.rk_b = (p.adv_type >= 3) ? p.RK_b[in_step] : 0.0;
   a.need_u1 = (p.adv_type >= 3) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
-  if (e->ctx->opt.flux_stamps && !g->stamps)
-  {
-    if (hipMalloc((void **)&g->stamps, sizeof(long long) * 16 * 16) == hipSuccess) (void)hipMemset(g->stamps, 0, sizeof(long long) * 16 * 16);
-  }
+  if (e->ctx->opt.flux_stamps) (void)g->stamps.ensure_zeroed(16 * 16); // (diagnostics: without the buffer the kernel takes none)
   a.stamps = g->stamps;
   a.les = e->les; a.les_len2 = g->les_len2; a.tdA_fpts = e->tdA_fpts;
   a.tdisf_in = e->over_int_ready ? e->arr[HFX_TDISF_UPTS] : nullptr;
@@ -1207,7 +1184,7 @@ static GenArgs gen_args(hfx_eles *e, const GeneralPlan &pl, int in_step)
 static GFaceArgs gface_args(hfx_inters *f)
 {
   hfx_eles *l = f->left, *r = f->right;
-  GeneralData *gl = l->general, *gr = r->general;
+  GeneralData *gl = l->general.get(), *gr = r->general.get();
   GFaceArgs a{};
   a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
   a.L = f->L; a.R = f->R; a.meta_l = gl->meta;
@@ -1354,7 +1331,7 @@ int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, in
   }
   for (int i = 0; i < neb; i++)
   {
-    GeneralData *g = eles[i]->general;
+    GeneralData *g = eles[i]->general.get();
     bool same = g && g->built;
     if (same && g->n_blocks)
     {
@@ -1441,7 +1418,7 @@ int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *face
   for (int i = 0; i < 8; i++) ms[i] = (i < 4) ? acc[i] / reps : 0.0;
   for (int i = 0; i < neb; i++)
   {
-    GeneralData *g = eles[i]->general;
+    GeneralData *g = eles[i]->general.get();
     if (!g || !g->stamps) continue;
     long long h[16 * 16];
     HFX_HIP(hipMemcpy(h, g->stamps, sizeof h, hipMemcpyDeviceToHost));

@@ -104,7 +104,6 @@ struct GeneralStage
 
 // drop / release the tables derived from the block's operators and face registration
 void general_invalidate(hfx_eles *e);
-void general_destroy(hfx_eles *e);
 // n_steps time steps over several element blocks (a mixed mesh) and the face blocks between them; fails loudly when a block does not
 // qualify (2-D; an LES closure without an instantiated size or with over-integration); shock capturing follows every stage
 int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int n_steps);

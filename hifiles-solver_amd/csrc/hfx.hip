@@ -28,26 +28,21 @@ void set_error(const char *fmt, ...)
   g_err = buf;
 }
 
-static int dev_alloc_copy(double **dst, const double *src, long n)
-{
-  HFX_HIP(hipMalloc((void **)dst, sizeof(double) * (size_t)std::max<long>(n, 1)));
-  if (src) HFX_HIP(hipMemcpy(*dst, src, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  return 0;
-}
-
 // ---- operator registration -------------------------------------------------
-static int make_operator(Operator &op, const double *host, int m, int k)
+// (a failure leaves `dst` as it was)
+static int make_operator(Operator &dst, const double *host, int m, int k)
 {
+  Operator op;
   op.m = m;
   op.k = k;
-  if (dev_alloc_copy(&op.dense, host, (long)m * k)) return 1;
+  if (op.dense.upload(host, (size_t)m * k)) return 1;
   {
     op.mpad = (m + 15) & ~15;
     op.kpad = (k + 3) & ~3;
     std::vector<double> pad((size_t)op.mpad * op.kpad, 0.0);
     for (int c = 0; c < k; c++)
       for (int r = 0; r < m; r++) pad[r + (size_t)op.mpad * c] = host[r + (long)m * c];
-    if (dev_alloc_copy(&op.dense_pad, pad.data(), (long)pad.size())) return 1;
+    if (op.dense_pad.upload(pad)) return 1;
   }
   // ELL: exact non-zeros, ascending column
   int nnz_max = 0;
@@ -82,22 +77,11 @@ static int make_operator(Operator &op, const double *host, int m, int k)
       idx[r + (size_t)m * q] = first;
     }
   }
-  HFX_HIP(hipMalloc((void **)&op.ell_val, sizeof(double) * val.size()));
-  HFX_HIP(hipMalloc((void **)&op.ell_idx, sizeof(int) * idx.size()));
-  HFX_HIP(hipMemcpy(op.ell_val, val.data(), sizeof(double) * val.size(), hipMemcpyHostToDevice));
-  HFX_HIP(hipMemcpy(op.ell_idx, idx.data(), sizeof(int) * idx.size(), hipMemcpyHostToDevice));
-  op.h_val = val;
-  op.h_idx = idx;
+  if (op.ell_val.upload(val) || op.ell_idx.upload(idx)) return 1;
+  op.h_val = std::move(val);
+  op.h_idx = std::move(idx);
+  dst = std::move(op);
   return 0;
-}
-
-static void free_operator(Operator &op)
-{
-  if (op.dense) (void)hipFree(op.dense);
-  if (op.dense_pad) (void)hipFree(op.dense_pad);
-  if (op.ell_val) (void)hipFree(op.ell_val);
-  if (op.ell_idx) (void)hipFree(op.ell_idx);
-  op = Operator();
 }
 
 constexpr int ELL_MAX_NNZ = 8;
@@ -316,6 +300,23 @@ static int contract_multi_out(hfx_ctx *ctx, const Operator *const *ops, int no, 
 
 static inline unsigned nblocks(long n, int b) { return (unsigned)((n + b - 1) / b); }
 
+// f(std::integral_constant<int, n_dims>): the one place that turns a block's dimension into a template argument
+template <class F>
+static void with_dims(int n_dims, F f)
+{
+  if (n_dims == 2)
+    f(std::integral_constant<int, 2>{});
+  else
+    f(std::integral_constant<int, 3>{});
+}
+
+// one thread per point: workgroups of PT_BLOCK threads, as many as cover n
+template <class... P, class... A>
+static void launch_points(void (*kernel)(P...), long n, hipStream_t st, const A &...args)
+{
+  hipLaunchKernelGGL(kernel, dim3(nblocks(n, PT_BLOCK)), dim3(PT_BLOCK), 0, st, args...);
+}
+
 // ---- the side stream of the boundary-face kernels (hfx_ctx::side_stream) ----
 int side_stream_fork(hfx_ctx *ctx)
 {
@@ -350,8 +351,8 @@ namespace hfx
 // Smagorinsky model and C_s^2 Delta^2 for WALE (src/eles.cpp:2436-2520, Delta = filter_ratio vol^(1/n_dims) / (order + 1) with
 // vol = detjac * the reference element's volume): it depends on the metrics and the wall distance only, so the fused stages' flux
 // kernels read it (calc_sgsf_fast) instead of evaluating a cube root per point and stage.  Evaluated once on the host with the
-// reference's own expression; *dst: a new device array (n_upts, n_eles).
-int les_len2_upload(hfx_eles *e, double **dst)
+// reference's own expression; dst: the device array (n_upts, n_eles) it fills.
+int les_len2_upload(hfx_eles *e, DevBuf<double> &dst)
 {
   const long plane = (long)e->n_upts * e->n_eles;
   std::vector<double> dj(plane), len2(plane), wd;
@@ -377,10 +378,7 @@ int les_len2_upload(hfx_eles *e, double **dst)
     }
     len2[p] = l2;
   }
-  if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-  HFX_HIP(hipMalloc((void **)dst, sizeof(double) * std::max<long>(plane, 1)));
-  HFX_HIP(hipMemcpy(*dst, len2.data(), sizeof(double) * plane, hipMemcpyHostToDevice));
-  return 0;
+  return dst.upload(len2);
 }
 
 int calc_time_step_blocks(hfx_eles *const *eles, int neb)
@@ -414,6 +412,7 @@ extern "C" {
 
 const char *hfx_last_error(void) { return g_err.c_str(); }
 int hfx_version(void) { return 1; }
+long hfx_live_device_bytes_internal(void) { return g_live_device_bytes.load(); }
 
 int hfx_ctx_create(int device, hfx_ctx **out)
 {
@@ -571,7 +570,7 @@ int hfx_eles_create(hfx_ctx *ctx, const hfx_eles_desc *d, hfx_eles **out)
   HFX_IMMEDIATE(ctx, 0);
   ctx->defer.plans.clear();
   HFX_HIP(hipSetDevice(ctx->device));
-  hfx_eles *e = new hfx_eles();
+  auto e = std::make_unique<hfx_eles>();
   e->ctx = ctx;
   e->n_eles = d->n_eles; e->n_upts = d->n_upts; e->n_fpts = d->n_fpts; e->n_fields = d->n_fields;
   e->n_dims = d->n_dims; e->ele_type = d->ele_type; e->order = d->order;
@@ -597,12 +596,12 @@ int hfx_eles_create(hfx_ctx *ctx, const hfx_eles_desc *d, hfx_eles **out)
     HFX_CHECK(d->detjac_fpts && d->JGinv_fpts, "hfx_eles_create: missing flux-point metrics");
     if (make_operator(e->opp_6, d->opp_6, nfp, nu)) return 1;
   }
-  if (dev_alloc_copy(&e->detjac_upts, d->detjac_upts, nu * ne)) return 1;
-  if (dev_alloc_copy(&e->JGinv_upts, d->JGinv_upts, (long)nd * nd * nu * ne)) return 1;
-  if (d->detjac_fpts && dev_alloc_copy(&e->detjac_fpts, d->detjac_fpts, nfp * ne)) return 1;
-  if (d->JGinv_fpts && dev_alloc_copy(&e->JGinv_fpts, d->JGinv_fpts, (long)nd * nd * nfp * ne)) return 1;
-  if (dev_alloc_copy(&e->tdA_fpts, d->tdA_fpts, nfp * ne)) return 1;
-  if (dev_alloc_copy(&e->norm_fpts, d->norm_fpts, (long)nfp * ne * nd)) return 1;
+  if (e->detjac_upts.upload(d->detjac_upts, nu * ne)) return 1;
+  if (e->JGinv_upts.upload(d->JGinv_upts, (long)nd * nd * nu * ne)) return 1;
+  if (d->detjac_fpts && e->detjac_fpts.upload(d->detjac_fpts, nfp * ne)) return 1;
+  if (d->JGinv_fpts && e->JGinv_fpts.upload(d->JGinv_fpts, (long)nd * nd * nfp * ne)) return 1;
+  if (e->tdA_fpts.upload(d->tdA_fpts, nfp * ne)) return 1;
+  if (e->norm_fpts.upload(d->norm_fpts, (long)nfp * ne * nd)) return 1;
 
   const long pu = nu * ne, pf = nfp * ne;
   long len[HFX_N_ARRAYS];
@@ -619,15 +618,14 @@ int hfx_eles_create(hfx_ctx *ctx, const hfx_eles_desc *d, hfx_eles **out)
     if (i == HFX_SRC_UPTS || i == HFX_DT_LOCAL) continue;       // allocated on first upload
     if (i == HFX_SGSF_UPTS || i == HFX_SGSF_FPTS) continue;     // allocated by hfx_eles_set_les
     if (i == HFX_DISUF_UPTS || i == HFX_LU || i == HFX_LE) continue; // allocated by hfx_eles_set_les_filter
-    HFX_HIP(hipMalloc((void **)&e->arr[i], sizeof(double) * (size_t)std::max<long>(len[i], 1)));
     // the reference zero-initialises its arrays (hf_array::setup + initialize_to_zero, src/eles.cpp:100-215)
-    HFX_HIP(hipMemset(e->arr[i], 0, sizeof(double) * (size_t)std::max<long>(len[i], 1)));
+    if (e->arr[i].alloc_zeroed(len[i])) return 1;
   }
-  HFX_HIP(hipMalloc((void **)&e->nan_flag, sizeof(unsigned long long)));
+  if (e->nan_flag.alloc(1)) return 1;
   HFX_HIP(hipMemset(e->nan_flag, 0xff, sizeof(unsigned long long)));
   e->red_blocks = 1024;
-  HFX_HIP(hipMalloc((void **)&e->red_buf, sizeof(double) * e->red_blocks));
-  *out = e;
+  if (e->red_buf.alloc(e->red_blocks)) return 1;
+  *out = e.release();
   return 0;
 }
 
@@ -639,38 +637,6 @@ int hfx_eles_destroy(hfx_eles *e)
   const int rc = defer_flush(e->ctx, 0);
   e->ctx->defer.log.clear();
   e->ctx->defer.plans.clear();
-  free_operator(e->opp_0); free_operator(e->opp_3); free_operator(e->opp_6);
-  free_operator(e->inv_vandermonde); free_operator(e->exp_filter);
-  free_operator(e->opp_over_int_cubpts); free_operator(e->over_int_filter);
-  free_operator(e->opp_volume_cubpts);
-  free_operator(e->opp_p);
-  free_operator(e->filter_upts);
-  for (double *p : {e->sgs_uu, e->sgs_ue})
-    if (p) (void)hipFree(p);
-  if (e->disu_ppts) (void)hipFree(e->disu_ppts);
-  for (double *p : {e->weight_volume_cubpts, e->vol_detjac_vol_cubpts, e->iq_u, e->iq_g})
-    if (p) (void)hipFree(p);
-  for (double *p : {e->JGinv_over_int_cubpts, e->u_cub, e->t_cub})
-    if (p) (void)hipFree(p);
-  if (e->persson_num) (void)hipFree(e->persson_num);
-  if (e->persson_den) (void)hipFree(e->persson_den);
-  tensor_ops_destroy(e);
-  for (int i = 0; i < 3; i++)
-  {
-    free_operator(e->opp_1[i]); free_operator(e->opp_2[i]); free_operator(e->opp_4[i]); free_operator(e->opp_5[i]);
-  }
-  double *m[] = {e->detjac_upts, e->JGinv_upts, e->detjac_fpts, e->JGinv_fpts, e->tdA_fpts, e->norm_fpts};
-  for (double *p : m)
-    if (p) (void)hipFree(p);
-  for (int i = 0; i < HFX_N_ARRAYS; i++)
-    if (e->arr[i]) (void)hipFree(e->arr[i]);
-  if (e->h_ref) (void)hipFree(e->h_ref);
-  if (e->wall_distance) (void)hipFree(e->wall_distance);
-  if (e->Jacobian_fpts) (void)hipFree(e->Jacobian_fpts);
-  if (e->nan_flag) (void)hipFree(e->nan_flag);
-  if (e->red_buf) (void)hipFree(e->red_buf);
-  fused_destroy(e);
-  general_destroy(e);
   delete e;
   return rc;
 }
@@ -682,7 +648,7 @@ int hfx_eles_upload(hfx_eles *e, int id, const double *host)
   HFX_IMMEDIATE(e->ctx, 0);
   if ((id == HFX_DISU_UPTS0 || id == HFX_DISU_FPTS) && invalidate_fpts(e)) return 1;
   e->stale &= ~(1u << id);
-  if (!e->arr[id]) HFX_HIP(hipMalloc((void **)&e->arr[id], sizeof(double) * (size_t)std::max<long>(e->arr_len[id], 1)));
+  if (e->arr[id].ensure(e->arr_len[id])) return 1;
   HFX_HIP(hipStreamSynchronize(e->ctx->stream));
   HFX_HIP(hipMemcpy(e->arr[id], host, sizeof(double) * (size_t)e->arr_len[id], hipMemcpyHostToDevice));
   if (id == HFX_SRC_UPTS) e->src_nonzero = true;
@@ -693,7 +659,7 @@ int hfx_eles_download(hfx_eles *e, int id, double *host)
 {
   HFX_CHECK(e && host, "hfx_eles_download: NULL argument");
   HFX_CHECK(id >= 0 && id < HFX_N_ARRAYS, "hfx_eles_download: bad array id %d", id);
-  HFX_CHECK(e->arr[id] != nullptr, "hfx_eles_download: array %d was never uploaded", id);
+  HFX_CHECK(e->arr[id], "hfx_eles_download: array %d was never uploaded", id);
   HFX_IMMEDIATE(e->ctx, 1u << id);
   // (whether or not the context defers now: the option switched off after a fused stage does not make its arrays current)
   HFX_CHECK(!(e->stale & (1u << id)),
@@ -766,12 +732,10 @@ int hfx_eles_evaluate_invFlux(hfx_eles *e)
   HFX_DEFER(e->ctx, DM_EVALUATE_INVFLUX, e, nullptr, nullptr, 0, 0);
   e->stale &= ~(1u << HFX_TDISF_UPTS);
   const long plane = (long)e->n_upts * e->n_eles;
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(invflux_kernel<2>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, e->ctx->stream, plane,
-                       e->ctx->params.gamma, e->arr[HFX_DISU_UPTS0], e->JGinv_upts, e->arr[HFX_TDISF_UPTS]);
-  else
-    hipLaunchKernelGGL(invflux_kernel<3>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, e->ctx->stream, plane,
-                       e->ctx->params.gamma, e->arr[HFX_DISU_UPTS0], e->JGinv_upts, e->arr[HFX_TDISF_UPTS]);
+  with_dims(e->n_dims, [&](auto ND) {
+    launch_points(invflux_kernel<ND()>, plane, e->ctx->stream, plane, e->ctx->params.gamma, e->arr[HFX_DISU_UPTS0],
+                  e->JGinv_upts, e->arr[HFX_TDISF_UPTS]);
+  });
   HFX_HIP(hipGetLastError());
   return 0;
 }
@@ -800,20 +764,10 @@ int hfx_eles_correct_gradient(hfx_eles *e)
   }
   // (iii) reference -> physical, in place, at solution and flux points
   const long pu = (long)e->n_upts * e->n_eles, pf = (long)e->n_fpts * e->n_eles;
-  if (e->n_dims == 2)
-  {
-    hipLaunchKernelGGL(grad_transform_kernel<2>, dim3(nblocks(pu, PT_BLOCK)), dim3(PT_BLOCK), 0, ctx->stream, pu,
-                       e->detjac_upts, e->JGinv_upts, e->arr[HFX_GRAD_DISU_UPTS]);
-    hipLaunchKernelGGL(grad_transform_kernel<2>, dim3(nblocks(pf, PT_BLOCK)), dim3(PT_BLOCK), 0, ctx->stream, pf,
-                       e->detjac_fpts, e->JGinv_fpts, e->arr[HFX_GRAD_DISU_FPTS]);
-  }
-  else
-  {
-    hipLaunchKernelGGL(grad_transform_kernel<3>, dim3(nblocks(pu, PT_BLOCK)), dim3(PT_BLOCK), 0, ctx->stream, pu,
-                       e->detjac_upts, e->JGinv_upts, e->arr[HFX_GRAD_DISU_UPTS]);
-    hipLaunchKernelGGL(grad_transform_kernel<3>, dim3(nblocks(pf, PT_BLOCK)), dim3(PT_BLOCK), 0, ctx->stream, pf,
-                       e->detjac_fpts, e->JGinv_fpts, e->arr[HFX_GRAD_DISU_FPTS]);
-  }
+  with_dims(e->n_dims, [&](auto ND) {
+    launch_points(grad_transform_kernel<ND()>, pu, ctx->stream, pu, e->detjac_upts, e->JGinv_upts, e->arr[HFX_GRAD_DISU_UPTS]);
+    launch_points(grad_transform_kernel<ND()>, pf, ctx->stream, pf, e->detjac_fpts, e->JGinv_fpts, e->arr[HFX_GRAD_DISU_FPTS]);
+  });
   HFX_HIP(hipGetLastError());
   return 0;
 }
@@ -827,25 +781,15 @@ int hfx_eles_evaluate_viscFlux(hfx_eles *e)
   e->stale &= ~((1u << HFX_TDISF_UPTS) | (1u << HFX_SGSF_UPTS));
   const long plane = (long)e->n_upts * e->n_eles;
   const Phys P = e->ctx->phys();
-  if (e->les_ready)
-  {
-    if (e->n_dims == 2)
-      hipLaunchKernelGGL(viscflux_les_kernel<2>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, e->ctx->stream, plane, P,
-                         e->les, e->arr[HFX_DISU_UPTS0], e->arr[HFX_GRAD_DISU_UPTS], e->JGinv_upts, e->detjac_upts,
-                         e->wall_distance, e->arr[HFX_TDISF_UPTS], e->arr[HFX_SGSF_UPTS]);
+  with_dims(e->n_dims, [&](auto ND) {
+    if (e->les_ready)
+      launch_points(viscflux_les_kernel<ND()>, plane, e->ctx->stream, plane, P, e->les, e->arr[HFX_DISU_UPTS0],
+                    e->arr[HFX_GRAD_DISU_UPTS], e->JGinv_upts, e->detjac_upts, e->wall_distance, e->arr[HFX_TDISF_UPTS],
+                    e->arr[HFX_SGSF_UPTS]);
     else
-      hipLaunchKernelGGL(viscflux_les_kernel<3>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, e->ctx->stream, plane, P,
-                         e->les, e->arr[HFX_DISU_UPTS0], e->arr[HFX_GRAD_DISU_UPTS], e->JGinv_upts, e->detjac_upts,
-                         e->wall_distance, e->arr[HFX_TDISF_UPTS], e->arr[HFX_SGSF_UPTS]);
-    HFX_HIP(hipGetLastError());
-    return 0;
-  }
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(viscflux_kernel<2>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, e->ctx->stream, plane, P,
-                       e->arr[HFX_DISU_UPTS0], e->arr[HFX_GRAD_DISU_UPTS], e->JGinv_upts, e->arr[HFX_TDISF_UPTS]);
-  else
-    hipLaunchKernelGGL(viscflux_kernel<3>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, e->ctx->stream, plane, P,
-                       e->arr[HFX_DISU_UPTS0], e->arr[HFX_GRAD_DISU_UPTS], e->JGinv_upts, e->arr[HFX_TDISF_UPTS]);
+      launch_points(viscflux_kernel<ND()>, plane, e->ctx->stream, plane, P, e->arr[HFX_DISU_UPTS0], e->arr[HFX_GRAD_DISU_UPTS],
+                    e->JGinv_upts, e->arr[HFX_TDISF_UPTS]);
+  });
   HFX_HIP(hipGetLastError());
   return 0;
 }
@@ -984,21 +928,18 @@ int hfx_int_inters_create(hfx_ctx *ctx, hfx_eles *left, hfx_eles *right, int n_i
       sr[R[q]] = 1;
     }
   }
-  hfx_inters *f = new hfx_inters();
+  auto f = std::make_unique<hfx_inters>();
   f->ctx = ctx; f->left = left; f->right = right; f->n_inters = n_inters; f->n_fpts_per_inter = nfpi;
   f->hL.assign(L, L + np);
   f->hR.assign(R, R + np);
-  HFX_HIP(hipMalloc((void **)&f->L, sizeof(int) * (size_t)std::max<long>(np, 1)));
-  HFX_HIP(hipMalloc((void **)&f->R, sizeof(int) * (size_t)std::max<long>(np, 1)));
-  HFX_HIP(hipMemcpy(f->L, L, sizeof(int) * (size_t)np, hipMemcpyHostToDevice));
-  HFX_HIP(hipMemcpy(f->R, R, sizeof(int) * (size_t)np, hipMemcpyHostToDevice));
-  left->faces_attached.push_back(f);
-  if (right != left) right->faces_attached.push_back(f);
+  if (f->L.upload(f->hL) || f->R.upload(f->hR)) return 1;
+  left->faces_attached.push_back(f.get());
+  if (right != left) right->faces_attached.push_back(f.get());
   fused_invalidate(left);
   fused_invalidate(right);
   general_invalidate(left);
   general_invalidate(right);
-  *out = f;
+  *out = f.release();
   return 0;
 }
 
@@ -1023,12 +964,6 @@ int hfx_inters_destroy(hfx_inters *f)
       fused_invalidate(e);
       general_invalidate(e);
     }
-  if (f->L) (void)hipFree(f->L);
-  if (f->R) (void)hipFree(f->R);
-  for (double *b : {f->out_disu, f->in_disu, f->out_grad, f->in_grad, f->out_sgsf, f->in_sgsf})
-    if (b) (void)hipFree(b);
-  if (f->boundary_id) (void)hipFree(f->boundary_id);
-  if (f->bcs) (void)hipFree(f->bcs);
   delete f;
   return rc;
 }
@@ -1050,16 +985,11 @@ int hfx_eles_set_les(hfx_eles *e, const hfx_les *les, const double *wall_distanc
   }
   e->les.C_s = les->C_s; e->les.filter_ratio = les->filter_ratio; e->les.Kappa = les->Kappa; e->les.prandtl_t = les->prandtl_t;
   e->les.Lu = e->arr[HFX_LU]; e->les.Le = e->arr[HFX_LE]; // NULL until hfx_eles_set_les_filter
-  for (double **p : {&e->wall_distance, &e->Jacobian_fpts})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-  if (wall_distance && dev_alloc_copy(&e->wall_distance, wall_distance, (long)e->n_upts * e->n_eles * e->n_dims)) return 1;
-  if (dev_alloc_copy(&e->Jacobian_fpts, Jacobian_fpts, (long)e->n_dims * e->n_dims * e->n_fpts * e->n_eles)) return 1;
+  e->wall_distance.reset();
+  if (wall_distance && e->wall_distance.upload(wall_distance, (size_t)e->n_upts * e->n_eles * e->n_dims)) return 1;
+  if (e->Jacobian_fpts.upload(Jacobian_fpts, (size_t)e->n_dims * e->n_dims * e->n_fpts * e->n_eles)) return 1;
   for (int id : {HFX_SGSF_UPTS, HFX_SGSF_FPTS})
-    if (!e->arr[id])
-    {
-      HFX_HIP(hipMalloc((void **)&e->arr[id], sizeof(double) * (size_t)std::max<long>(e->arr_len[id], 1)));
-      HFX_HIP(hipMemset(e->arr[id], 0, sizeof(double) * (size_t)std::max<long>(e->arr_len[id], 1)));
-    }
+    if (e->arr[id].ensure_zeroed(e->arr_len[id])) return 1;
   e->les_ready = true;
   fused_invalidate(e);
   general_invalidate(e); // (the general stage takes the closure / the de-aliased flux from the registration too)
@@ -1071,16 +1001,10 @@ int hfx_eles_set_les_filter(hfx_eles *e, const double *filter_upts)
   HFX_CHECK(e && filter_upts, "hfx_eles_set_les_filter: NULL argument");
   HFX_IMMEDIATE(e->ctx, 0);
   e->ctx->defer.plans.clear();
-  free_operator(e->filter_upts);
   if (make_operator(e->filter_upts, filter_upts, e->n_upts, e->n_upts)) return 1;
   for (int id : {HFX_DISUF_UPTS, HFX_LU, HFX_LE})
-    if (!e->arr[id])
-    {
-      HFX_HIP(hipMalloc((void **)&e->arr[id], sizeof(double) * (size_t)std::max<long>(e->arr_len[id], 1)));
-      HFX_HIP(hipMemset(e->arr[id], 0, sizeof(double) * (size_t)std::max<long>(e->arr_len[id], 1)));
-    }
-  if (!e->sgs_uu) HFX_HIP(hipMalloc((void **)&e->sgs_uu, sizeof(double) * (size_t)std::max<long>(e->arr_len[HFX_LU], 1)));
-  if (!e->sgs_ue) HFX_HIP(hipMalloc((void **)&e->sgs_ue, sizeof(double) * (size_t)std::max<long>(e->arr_len[HFX_LE], 1)));
+    if (e->arr[id].ensure_zeroed(e->arr_len[id])) return 1;
+  if (e->sgs_uu.ensure(e->arr_len[HFX_LU]) || e->sgs_ue.ensure(e->arr_len[HFX_LE])) return 1;
   e->les.Lu = e->arr[HFX_LU];
   e->les.Le = e->arr[HFX_LE];
   return 0;
@@ -1105,12 +1029,10 @@ int hfx_eles_calc_sgs_terms(hfx_eles *e)
   if (contract_multi_in(ctx, ops, 1, in_u, e->arr[HFX_DISUF_UPTS], (long)e->n_eles * e->n_fields, 0)) return 1;
   const bool sim = model == 2 || model == 4;
   // products of the unfiltered solution (similarity models) and the NaN scan of the filtered one
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(sgs_products_kernel<2>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, st, plane, e->arr[HFX_DISU_UPTS0],
-                       e->arr[HFX_DISUF_UPTS], sim ? e->sgs_uu : nullptr, sim ? e->sgs_ue : nullptr, e->nan_flag);
-  else
-    hipLaunchKernelGGL(sgs_products_kernel<3>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, st, plane, e->arr[HFX_DISU_UPTS0],
-                       e->arr[HFX_DISUF_UPTS], sim ? e->sgs_uu : nullptr, sim ? e->sgs_ue : nullptr, e->nan_flag);
+  with_dims(e->n_dims, [&](auto ND) {
+    launch_points(sgs_products_kernel<ND()>, plane, st, plane, e->arr[HFX_DISU_UPTS0], e->arr[HFX_DISUF_UPTS],
+                  sim ? e->sgs_uu.get() : nullptr, sim ? e->sgs_ue.get() : nullptr, e->nan_flag);
+  });
   HFX_HIP(hipGetLastError());
   if (model == 3)
   {
@@ -1122,12 +1044,9 @@ int hfx_eles_calc_sgs_terms(hfx_eles *e)
   const double *in_uu[1] = {e->sgs_uu}, *in_ue[1] = {e->sgs_ue};
   if (contract_multi_in(ctx, ops, 1, in_uu, e->arr[HFX_LU], (long)e->n_eles * (e->n_dims == 2 ? 3 : 6), 0)) return 1;
   if (contract_multi_in(ctx, ops, 1, in_ue, e->arr[HFX_LE], (long)e->n_eles * e->n_dims, 0)) return 1;
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(sgs_leonard_kernel<2>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, st, plane, e->arr[HFX_DISUF_UPTS],
-                       e->arr[HFX_LU], e->arr[HFX_LE]);
-  else
-    hipLaunchKernelGGL(sgs_leonard_kernel<3>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, st, plane, e->arr[HFX_DISUF_UPTS],
-                       e->arr[HFX_LU], e->arr[HFX_LE]);
+  with_dims(e->n_dims, [&](auto ND) {
+    launch_points(sgs_leonard_kernel<ND()>, plane, st, plane, e->arr[HFX_DISUF_UPTS], e->arr[HFX_LU], e->arr[HFX_LE]);
+  });
   HFX_HIP(hipGetLastError());
   return 0;
 }
@@ -1138,14 +1057,10 @@ extern "C" int hfx_les_sgsf_upts_internal(hfx_eles *e)
   HFX_CHECK(e && e->les_ready, "LES closure not set");
   hfx_ctx *ctx = e->ctx;
   const long plane = (long)e->n_upts * e->n_eles;
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(sgsf_upts_kernel<2>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, ctx->stream, plane, ctx->phys(), e->les,
-                       e->arr[HFX_DISU_UPTS0], e->arr[HFX_GRAD_DISU_UPTS], e->JGinv_upts, e->detjac_upts, e->wall_distance,
-                       e->arr[HFX_SGSF_UPTS]);
-  else
-    hipLaunchKernelGGL(sgsf_upts_kernel<3>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, ctx->stream, plane, ctx->phys(), e->les,
-                       e->arr[HFX_DISU_UPTS0], e->arr[HFX_GRAD_DISU_UPTS], e->JGinv_upts, e->detjac_upts, e->wall_distance,
-                       e->arr[HFX_SGSF_UPTS]);
+  with_dims(e->n_dims, [&](auto ND) {
+    launch_points(sgsf_upts_kernel<ND()>, plane, ctx->stream, plane, ctx->phys(), e->les, e->arr[HFX_DISU_UPTS0],
+                  e->arr[HFX_GRAD_DISU_UPTS], e->JGinv_upts, e->detjac_upts, e->wall_distance, e->arr[HFX_SGSF_UPTS]);
+  });
   HFX_HIP(hipGetLastError());
   return 0;
 }
@@ -1174,12 +1089,10 @@ int hfx_eles_extrapolate_sgsFlux(hfx_eles *e)
     if (contract_multi_in(e->ctx, ops, 1, in, e->arr[HFX_SGSF_FPTS], (long)e->n_eles * e->n_fields * e->n_dims, 0)) return 1;
   }
   const long plane = (long)e->n_fpts * e->n_eles;
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(sgsf_to_physical_kernel<2>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, e->ctx->stream, plane,
-                       e->detjac_fpts, e->Jacobian_fpts, e->arr[HFX_SGSF_FPTS]);
-  else
-    hipLaunchKernelGGL(sgsf_to_physical_kernel<3>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, e->ctx->stream, plane,
-                       e->detjac_fpts, e->Jacobian_fpts, e->arr[HFX_SGSF_FPTS]);
+  with_dims(e->n_dims, [&](auto ND) {
+    launch_points(sgsf_to_physical_kernel<ND()>, plane, e->ctx->stream, plane, e->detjac_fpts, e->Jacobian_fpts,
+                  e->arr[HFX_SGSF_FPTS]);
+  });
   HFX_HIP(hipGetLastError());
   return 0;
 }
@@ -1191,14 +1104,12 @@ int hfx_eles_set_volume_cubpts(hfx_eles *e, int n_cubpts, const double *opp_volu
   HFX_CHECK(e && opp_volume_cubpts && weight_volume_cubpts && vol_detjac_vol_cubpts && n_cubpts > 0,
             "hfx_eles_set_volume_cubpts: bad argument");
   HFX_IMMEDIATE(e->ctx, 0);
-  free_operator(e->opp_volume_cubpts);
-  for (double **p : {&e->weight_volume_cubpts, &e->vol_detjac_vol_cubpts, &e->iq_u, &e->iq_g})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
+  e->iq_u.reset(); // (sized by n_cubpts: allocated again by the next CalcIntegralQuantities)
+  e->iq_g.reset();
   e->n_vol_cubpts = n_cubpts;
   if (make_operator(e->opp_volume_cubpts, opp_volume_cubpts, n_cubpts, e->n_upts)) return 1;
-  if (dev_alloc_copy(&e->weight_volume_cubpts, weight_volume_cubpts, n_cubpts)) return 1;
-  if (dev_alloc_copy(&e->vol_detjac_vol_cubpts, vol_detjac_vol_cubpts, (long)n_cubpts * e->n_eles)) return 1;
-  return 0;
+  if (e->weight_volume_cubpts.upload(weight_volume_cubpts, n_cubpts)) return 1;
+  return e->vol_detjac_vol_cubpts.upload(vol_detjac_vol_cubpts, (size_t)n_cubpts * e->n_eles);
 }
 
 int hfx_eles_CalcIntegralQuantities(hfx_eles *e, int n_q, const int *quantity_ids, double *integral_quantities)
@@ -1215,8 +1126,7 @@ int hfx_eles_CalcIntegralQuantities(hfx_eles *e, int n_q, const int *quantity_id
   hipStream_t st = ctx->stream;
   const int nc = e->n_vol_cubpts;
   const long pc = (long)nc * e->n_eles;
-  if (!e->iq_u) HFX_HIP(hipMalloc((void **)&e->iq_u, sizeof(double) * (size_t)pc * e->n_fields));
-  if (!e->iq_g) HFX_HIP(hipMalloc((void **)&e->iq_g, sizeof(double) * (size_t)pc * e->n_fields * e->n_dims));
+  if (e->iq_u.ensure((size_t)pc * e->n_fields) || e->iq_g.ensure((size_t)pc * e->n_fields * e->n_dims)) return 1;
   // state and corrected gradient at the cubature points: dense contractions
   {
     const Operator *ops[1] = {&e->opp_volume_cubpts};
@@ -1226,20 +1136,17 @@ int hfx_eles_CalcIntegralQuantities(hfx_eles *e, int n_q, const int *quantity_id
     if (contract_multi_in(ctx, ops, 1, in, e->iq_g, (long)e->n_eles * e->n_fields * e->n_dims, 0)) return 1;
   }
   const int nblk = (int)std::min<long>(e->red_blocks / IQ_MAX, nblocks(pc, PT_BLOCK));
-  int *d_ids = nullptr;
-  HFX_HIP(hipMalloc((void **)&d_ids, sizeof(int) * IQ_MAX));
-  HFX_HIP(hipMemcpyAsync(d_ids, quantity_ids, sizeof(int) * n_q, hipMemcpyHostToDevice, st));
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(integral_quantities_kernel<2>, dim3(nblk), dim3(PT_BLOCK), 0, st, nc, (long)e->n_eles, e->iq_u, e->iq_g,
-                       e->weight_volume_cubpts, e->vol_detjac_vol_cubpts, ctx->params.gamma, n_q, d_ids, e->red_buf);
-  else
-    hipLaunchKernelGGL(integral_quantities_kernel<3>, dim3(nblk), dim3(PT_BLOCK), 0, st, nc, (long)e->n_eles, e->iq_u, e->iq_g,
-                       e->weight_volume_cubpts, e->vol_detjac_vol_cubpts, ctx->params.gamma, n_q, d_ids, e->red_buf);
+  if (e->iq_ids.ensure(IQ_MAX)) return 1; // (free again: every call waits for the stream before it returns)
+  HFX_HIP(hipMemcpyAsync(e->iq_ids, quantity_ids, sizeof(int) * n_q, hipMemcpyHostToDevice, st));
+  with_dims(e->n_dims, [&](auto ND) {
+    hipLaunchKernelGGL(integral_quantities_kernel<ND()>, dim3(nblk), dim3(PT_BLOCK), 0, st, nc, (long)e->n_eles, e->iq_u.get(),
+                       e->iq_g.get(), e->weight_volume_cubpts.get(), e->vol_detjac_vol_cubpts.get(), ctx->params.gamma, n_q,
+                       e->iq_ids.get(), e->red_buf.get());
+  });
   HFX_HIP(hipGetLastError());
   std::vector<double> part((size_t)nblk * n_q);
   HFX_HIP(hipMemcpyAsync(part.data(), e->red_buf, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
   HFX_HIP(hipStreamSynchronize(st));
-  (void)hipFree(d_ids);
   for (int m = 0; m < n_q; m++)
   {
     double s = 0.0;
@@ -1254,11 +1161,7 @@ int hfx_eles_set_h_ref(hfx_eles *e, const double *h_ref)
 {
   HFX_CHECK(e && h_ref, "hfx_eles_set_h_ref: NULL argument");
   HFX_IMMEDIATE(e->ctx, 0);
-  if (e->h_ref) (void)hipFree(e->h_ref);
-  if (e->wall_distance) (void)hipFree(e->wall_distance);
-  if (e->Jacobian_fpts) (void)hipFree(e->Jacobian_fpts);
-  e->h_ref = nullptr;
-  return dev_alloc_copy(&e->h_ref, h_ref, e->n_eles);
+  return e->h_ref.upload(h_ref, e->n_eles);
 }
 
 int hfx_eles_calc_dt_local(hfx_eles *e, double CFL, double *dt_min)
@@ -1270,16 +1173,15 @@ int hfx_eles_calc_dt_local(hfx_eles *e, double CFL, double *dt_min)
   if (e->n_eles == 0) return 0;
   HFX_CHECK(e->h_ref, "calc_dt_local: hfx_eles_set_h_ref was not called");
   hipStream_t st = e->ctx->stream;
-  if (!e->arr[HFX_DT_LOCAL]) HFX_HIP(hipMalloc((void **)&e->arr[HFX_DT_LOCAL], sizeof(double) * (size_t)e->n_eles));
+  if (e->arr[HFX_DT_LOCAL].ensure(e->n_eles)) return 1;
   const double big = 1e12;
   HFX_HIP(hipMemcpyAsync(e->red_buf, &big, sizeof(double), hipMemcpyHostToDevice, st));
   const Phys P = e->ctx->phys();
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(dt_local_kernel<2>, dim3((unsigned)e->n_eles), dim3(64), 0, st, e->n_upts, (long)e->n_eles,
-                       e->arr[HFX_DISU_UPTS0], e->h_ref, P, CFL, e->order, e->arr[HFX_DT_LOCAL], (unsigned long long *)e->red_buf);
-  else
-    hipLaunchKernelGGL(dt_local_kernel<3>, dim3((unsigned)e->n_eles), dim3(64), 0, st, e->n_upts, (long)e->n_eles,
-                       e->arr[HFX_DISU_UPTS0], e->h_ref, P, CFL, e->order, e->arr[HFX_DT_LOCAL], (unsigned long long *)e->red_buf);
+  with_dims(e->n_dims, [&](auto ND) {
+    hipLaunchKernelGGL(dt_local_kernel<ND()>, dim3((unsigned)e->n_eles), dim3(64), 0, st, e->n_upts, (long)e->n_eles,
+                       e->arr[HFX_DISU_UPTS0].get(), e->h_ref.get(), P, CFL, e->order, e->arr[HFX_DT_LOCAL].get(),
+                       (unsigned long long *)e->red_buf.get());
+  });
   HFX_HIP(hipGetLastError());
   HFX_HIP(hipMemcpyAsync(dt_min, e->red_buf, sizeof(double), hipMemcpyDeviceToHost, st));
   HFX_HIP(hipStreamSynchronize(st));
@@ -1291,10 +1193,8 @@ int hfx_eles_set_opp_p(hfx_eles *e, int n_ppts, const double *opp_p)
 {
   HFX_CHECK(e && opp_p && n_ppts > 0, "hfx_eles_set_opp_p: bad argument");
   HFX_IMMEDIATE(e->ctx, 0);
-  free_operator(e->opp_p);
-  if (e->disu_ppts) { (void)hipFree(e->disu_ppts); e->disu_ppts = nullptr; }
   if (make_operator(e->opp_p, opp_p, n_ppts, e->n_upts)) return 1;
-  if (dev_alloc_copy(&e->disu_ppts, nullptr, (long)n_ppts * e->n_eles * e->n_fields)) return 1;
+  if (e->disu_ppts.alloc((size_t)n_ppts * e->n_eles * e->n_fields)) return 1;
   e->n_ppts = n_ppts;
   return 0;
 }
@@ -1323,17 +1223,12 @@ int hfx_eles_set_over_int(hfx_eles *e, int n_cubpts, const double *opp_over_int_
             "hfx_eles_set_over_int: bad argument");
   HFX_IMMEDIATE(e->ctx, 0);
   e->ctx->defer.plans.clear();
-  free_operator(e->opp_over_int_cubpts);
-  free_operator(e->over_int_filter);
-  for (double **p : {&e->JGinv_over_int_cubpts, &e->u_cub, &e->t_cub})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
   e->n_cubpts = n_cubpts;
   if (make_operator(e->opp_over_int_cubpts, opp_over_int_cubpts, n_cubpts, e->n_upts)) return 1;
   if (make_operator(e->over_int_filter, over_int_filter, e->n_upts, n_cubpts)) return 1;
   const long pc = (long)n_cubpts * e->n_eles;
-  if (dev_alloc_copy(&e->JGinv_over_int_cubpts, JGinv_over_int_cubpts, pc * e->n_dims * e->n_dims)) return 1;
-  if (dev_alloc_copy(&e->u_cub, nullptr, pc * e->n_fields)) return 1;
-  if (dev_alloc_copy(&e->t_cub, nullptr, pc * e->n_fields * e->n_dims)) return 1;
+  if (e->JGinv_over_int_cubpts.upload(JGinv_over_int_cubpts, pc * e->n_dims * e->n_dims)) return 1;
+  if (e->u_cub.alloc(pc * e->n_fields) || e->t_cub.alloc(pc * e->n_fields * e->n_dims)) return 1;
   e->over_int_ready = true;
   fused_invalidate(e);
   general_invalidate(e); // (the general stage takes the closure / the de-aliased flux from the registration too)
@@ -1359,12 +1254,9 @@ int hfx_eles_evaluate_invFlux_over_int(hfx_eles *e)
   }
   // flux + transform there
   const long plane = (long)e->n_cubpts * e->n_eles;
-  if (e->n_dims == 2)
-    hipLaunchKernelGGL(invflux_kernel<2>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, ctx->stream, plane,
-                       ctx->params.gamma, e->u_cub, e->JGinv_over_int_cubpts, e->t_cub);
-  else
-    hipLaunchKernelGGL(invflux_kernel<3>, dim3(nblocks(plane, PT_BLOCK)), dim3(PT_BLOCK), 0, ctx->stream, plane,
-                       ctx->params.gamma, e->u_cub, e->JGinv_over_int_cubpts, e->t_cub);
+  with_dims(e->n_dims, [&](auto ND) {
+    launch_points(invflux_kernel<ND()>, plane, ctx->stream, plane, ctx->params.gamma, e->u_cub, e->JGinv_over_int_cubpts, e->t_cub);
+  });
   HFX_HIP(hipGetLastError());
   // project back to the solution points (the over-integration filter)
   {
@@ -1383,8 +1275,6 @@ int hfx_eles_set_shock_capture(hfx_eles *e, const double *inv_vandermonde, const
   HFX_IMMEDIATE(e->ctx, 0);
   e->ctx->defer.plans.clear();
   HFX_CHECK(shock_det_field == 0 || shock_det_field == 1, "Unsupported shock capturing field."); /* src/eles_hexas.cpp:1034 */
-  free_operator(e->inv_vandermonde);
-  free_operator(e->exp_filter);
   if (make_operator(e->inv_vandermonde, inv_vandermonde, e->n_upts, e->n_upts)) return 1;
   if (make_operator(e->exp_filter, exp_filter, e->n_upts, e->n_upts)) return 1;
   std::vector<double> num(e->n_upts), den(e->n_upts);
@@ -1393,11 +1283,7 @@ int hfx_eles_set_shock_capture(hfx_eles *e, const double *inv_vandermonde, const
     den[j] = norm_basis_persson[j];
     num[j] = high_modes[j] ? norm_basis_persson[j] : 0.0;
   }
-  if (e->persson_num) (void)hipFree(e->persson_num);
-  if (e->persson_den) (void)hipFree(e->persson_den);
-  e->persson_num = e->persson_den = nullptr;
-  if (dev_alloc_copy(&e->persson_num, num.data(), e->n_upts)) return 1;
-  if (dev_alloc_copy(&e->persson_den, den.data(), e->n_upts)) return 1;
+  if (e->persson_num.upload(num) || e->persson_den.upload(den)) return 1;
   e->s0 = s0;
   e->shock_det_field = shock_det_field;
   e->shock_ready = true;
@@ -1461,24 +1347,18 @@ int hfx_bdy_inters_create(hfx_ctx *ctx, hfx_eles *left, int n_inters, int nfpi, 
     HFX_CHECK(b.flag != HFX_BC_ADIABAT_WALL || ctx->params.viscous || !ctx->have_params,
               "Adiabatic wall boundary only available to viscous simulation"); /* src/input.cpp:427 */
   }
-  hfx_inters *f = new hfx_inters();
+  auto f = std::make_unique<hfx_inters>();
   f->ctx = ctx; f->left = left; f->right = nullptr; f->n_inters = n_inters; f->n_fpts_per_inter = nfpi;
   f->is_bdy = true;
   f->n_bcs = n_bcs;
   for (int b = 0; b < n_bcs; b++) f->any_ramp = f->any_ramp || (bcs[b].flag == HFX_BC_SUB_IN_CHAR && bcs[b].pressure_ramp);
   f->R_ref = R_ref;
   f->hL.assign(L, L + np);
-  const size_t ni = (size_t)std::max<long>(np, 1);
-  HFX_HIP(hipMalloc((void **)&f->L, sizeof(int) * ni));
-  HFX_HIP(hipMemcpy(f->L, L, sizeof(int) * (size_t)np, hipMemcpyHostToDevice));
-  HFX_HIP(hipMalloc((void **)&f->boundary_id, sizeof(int) * (size_t)std::max(n_inters, 1)));
-  HFX_HIP(hipMemcpy(f->boundary_id, boundary_id, sizeof(int) * (size_t)n_inters, hipMemcpyHostToDevice));
-  HFX_HIP(hipMalloc((void **)&f->bcs, sizeof(hfx_bc) * (size_t)std::max(n_bcs, 1)));
-  HFX_HIP(hipMemcpy(f->bcs, bcs, sizeof(hfx_bc) * (size_t)n_bcs, hipMemcpyHostToDevice));
-  left->faces_attached.push_back(f);
+  if (f->L.upload(f->hL) || f->boundary_id.upload(boundary_id, n_inters) || f->bcs.upload(bcs, n_bcs)) return 1;
+  left->faces_attached.push_back(f.get());
   fused_invalidate(left);
   general_invalidate(left);
-  *out = f;
+  *out = f.release();
   return 0;
 }
 
@@ -1520,23 +1400,16 @@ int hfx_bdy_launch_internal(hfx_inters *f, int visc, int fast)
   HFX_CHECK(f->ctx->have_params, "parameters not set");
   if (f->n_inters == 0) return 0;
   const BdyArgs a = bdy_args(f);
-  const dim3 g((unsigned)((a.npts + 255) / 256)), b(256);
   hipStream_t st = f->ctx->bdy_stream ? f->ctx->bdy_stream : f->ctx->stream;
-  const int nd = f->left->n_dims;
-#define HFX_BDY(K)                                                             \
-  if (nd == 2 && fast) hipLaunchKernelGGL((K<2, true>), g, b, 0, st, a);       \
-  else if (nd == 2) hipLaunchKernelGGL((K<2, false>), g, b, 0, st, a);         \
-  else if (fast) hipLaunchKernelGGL((K<3, true>), g, b, 0, st, a);             \
-  else hipLaunchKernelGGL((K<3, false>), g, b, 0, st, a);
-  if (visc)
-  {
-    HFX_BDY(bdy_viscflux_kernel)
-  }
-  else
-  {
-    HFX_BDY(bdy_invflux_kernel)
-  }
-#undef HFX_BDY
+  with_dims(f->left->n_dims, [&](auto ND) {
+    auto launch = [&](auto FAST) {
+      launch_points(visc ? bdy_viscflux_kernel<ND(), FAST()> : bdy_invflux_kernel<ND(), FAST()>, a.npts, st, a);
+    };
+    if (fast)
+      launch(std::true_type{});
+    else
+      launch(std::false_type{});
+  });
   HFX_HIP(hipGetLastError());
   return 0;
 }
@@ -1573,24 +1446,15 @@ int hfx_mpi_inters_create(hfx_ctx *ctx, hfx_eles *left, int n_inters, int nfpi, 
     HFX_CHECK(L[q] >= 0 && L[q] < pl, "partition face table L[%ld] = %d out of range", q, L[q]);
     HFX_CHECK(Rlut[q] >= 0 && Rlut[q] < nfpi, "partition face table Rlut[%ld] = %d out of range", q, Rlut[q]);
   }
-  hfx_inters *f = new hfx_inters();
+  auto f = std::make_unique<hfx_inters>();
   f->ctx = ctx; f->left = left; f->right = nullptr; f->n_inters = n_inters; f->n_fpts_per_inter = nfpi;
   f->is_mpi = true;
   f->hL.assign(L, L + np);
   f->hR.assign(Rlut, Rlut + np);
-  const size_t ni = (size_t)std::max<long>(np, 1);
-  HFX_HIP(hipMalloc((void **)&f->L, sizeof(int) * ni));
-  HFX_HIP(hipMalloc((void **)&f->R, sizeof(int) * ni));
-  HFX_HIP(hipMemcpy(f->L, L, sizeof(int) * (size_t)np, hipMemcpyHostToDevice));
-  HFX_HIP(hipMemcpy(f->R, Rlut, sizeof(int) * (size_t)np, hipMemcpyHostToDevice));
-  const size_t nd = ni * left->n_fields, ng = nd * left->n_dims;
-  HFX_HIP(hipMalloc((void **)&f->out_disu, sizeof(double) * nd));
-  HFX_HIP(hipMalloc((void **)&f->in_disu, sizeof(double) * nd));
-  HFX_HIP(hipMalloc((void **)&f->out_grad, sizeof(double) * ng));
-  HFX_HIP(hipMalloc((void **)&f->in_grad, sizeof(double) * ng));
-  HFX_HIP(hipMemset(f->in_disu, 0, sizeof(double) * nd));
-  HFX_HIP(hipMemset(f->in_grad, 0, sizeof(double) * ng));
-  *out = f;
+  if (f->L.upload(f->hL) || f->R.upload(f->hR)) return 1;
+  const size_t nd = (size_t)std::max<long>(np, 1) * left->n_fields, ng = nd * left->n_dims;
+  if (f->out_disu.alloc(nd) || f->in_disu.alloc_zeroed(nd) || f->out_grad.alloc(ng) || f->in_grad.alloc_zeroed(ng)) return 1;
+  *out = f.release();
   return 0;
 }
 
@@ -1620,46 +1484,48 @@ extern "C" int hfx_mpi_sgsf_buffers_internal(hfx_inters *f)
 {
   if (f->out_sgsf || !f->left->les_ready) return 0;
   const size_t ng = (size_t)std::max<long>((long)f->n_inters * f->n_fpts_per_inter, 1) * f->left->n_fields * f->left->n_dims;
-  HFX_HIP(hipMalloc((void **)&f->out_sgsf, sizeof(double) * ng));
-  HFX_HIP(hipMalloc((void **)&f->in_sgsf, sizeof(double) * ng));
-  HFX_HIP(hipMemset(f->in_sgsf, 0, sizeof(double) * ng));
-  return 0;
+  return f->out_sgsf.alloc(ng) || f->in_sgsf.alloc_zeroed(ng);
 }
 
-// METHOD: the DeferMethod of a recordable call, or -1 for the packing halves (not part of the reference's call sequence:
-// what has been recorded runs first)
-#define HFX_MPI_LAUNCH(METHOD, KERNEL2, KERNEL3)                                                            \
-  do                                                                                                        \
-  {                                                                                                         \
-    HFX_CHECK(f && f->is_mpi, "not a partition-face block");                                                \
-    if (f->n_inters == 0) return 0;                                                                         \
-    HFX_CHECK(f->ctx->have_params, "parameters not set");                                                   \
-    if ((METHOD) >= 0) { HFX_DEFER(f->ctx, METHOD, nullptr, f, nullptr, 0, 0); }                            \
-    HFX_IMMEDIATE(f->ctx, 0);                                                                               \
-    if (hfx_mpi_sgsf_buffers_internal(f)) return 1;                                                         \
-    const MpiArgs a = mpi_args(f);                                                                          \
-    if (f->left->n_dims == 2)                                                                               \
-      hipLaunchKernelGGL(KERNEL2, dim3(nblocks(a.npairs, 256)), dim3(256), 0, f->ctx->stream, a);           \
-    else                                                                                                    \
-      hipLaunchKernelGGL(KERNEL3, dim3(nblocks(a.npairs, 256)), dim3(256), 0, f->ctx->stream, a);           \
-    HFX_HIP(hipGetLastError());                                                                             \
-    return 0;                                                                                               \
-  } while (0)
+// The partition-face launchers.  method: the DeferMethod of a recordable call, or -1 for the packing halves (not part of the
+// reference's call sequence: what has been recorded runs first)
+extern "C++" {
+template <class Launch>
+static int mpi_launch_method(hfx_inters *f, int method, Launch launch)
+{
+  HFX_CHECK(f && f->is_mpi, "not a partition-face block");
+  if (f->n_inters == 0) return 0;
+  HFX_CHECK(f->ctx->have_params, "parameters not set");
+  if (method >= 0) { HFX_DEFER(f->ctx, method, nullptr, f, nullptr, 0, 0); }
+  HFX_IMMEDIATE(f->ctx, 0);
+  if (hfx_mpi_sgsf_buffers_internal(f)) return 1;
+  const MpiArgs a = mpi_args(f);
+  with_dims(f->left->n_dims, [&](auto ND) { launch_points(launch(ND), a.npairs, f->ctx->stream, a); });
+  HFX_HIP(hipGetLastError());
+  return 0;
+}
+}
 
-int hfx_mpi_inters_pack_solution(hfx_inters *f) { HFX_MPI_LAUNCH(-1, mpi_pack_disu_kernel<2>, mpi_pack_disu_kernel<3>); }
-int hfx_mpi_inters_pack_corrected_gradient(hfx_inters *f) { HFX_MPI_LAUNCH(-1, mpi_pack_grad_kernel<2>, mpi_pack_grad_kernel<3>); }
+int hfx_mpi_inters_pack_solution(hfx_inters *f)
+{
+  return mpi_launch_method(f, -1, [](auto ND) { return mpi_pack_disu_kernel<ND()>; });
+}
+int hfx_mpi_inters_pack_corrected_gradient(hfx_inters *f)
+{
+  return mpi_launch_method(f, -1, [](auto ND) { return mpi_pack_grad_kernel<ND()>; });
+}
 int hfx_mpi_inters_pack_sgsf(hfx_inters *f)
 {
   HFX_CHECK(f && f->is_mpi && f->left->les_ready, "hfx_mpi_inters_pack_sgsf: the left block has no LES closure (hfx_eles_set_les)");
-  HFX_MPI_LAUNCH(-1, mpi_pack_sgsf_kernel<2>, mpi_pack_sgsf_kernel<3>);
+  return mpi_launch_method(f, -1, [](auto ND) { return mpi_pack_sgsf_kernel<ND()>; });
 }
 int hfx_mpi_inters_calculate_common_invFlux(hfx_inters *f)
 {
-  HFX_MPI_LAUNCH(DM_MPI_COMMON_INVFLUX, (mpi_common_invflux_kernel<2, false>), (mpi_common_invflux_kernel<3, false>));
+  return mpi_launch_method(f, DM_MPI_COMMON_INVFLUX, [](auto ND) { return mpi_common_invflux_kernel<ND(), false>; });
 }
 int hfx_mpi_inters_calculate_common_viscFlux(hfx_inters *f)
 {
-  HFX_MPI_LAUNCH(DM_MPI_COMMON_VISCFLUX, (mpi_common_viscflux_kernel<2, false>), (mpi_common_viscflux_kernel<3, false>));
+  return mpi_launch_method(f, DM_MPI_COMMON_VISCFLUX, [](auto ND) { return mpi_common_viscflux_kernel<ND(), false>; });
 }
 
 int hfx_mpi_inters_buffer(hfx_inters *f, int which, double **dev, long *n)
@@ -1742,10 +1608,7 @@ int hfx_int_inters_calculate_common_invFlux(hfx_inters *f)
   for (hfx_eles *x : {f->left, f->right}) x->stale &= ~((1u << HFX_NORM_TCONF_FPTS) | (1u << HFX_DELTA_DISU_FPTS));
   const FaceArgs a = face_args(f);
   const Phys P = f->ctx->phys();
-  if (f->left->n_dims == 2)
-    hipLaunchKernelGGL(common_invflux_kernel<2>, dim3(nblocks(a.npairs, PT_BLOCK)), dim3(PT_BLOCK), 0, f->ctx->stream, a, P);
-  else
-    hipLaunchKernelGGL(common_invflux_kernel<3>, dim3(nblocks(a.npairs, PT_BLOCK)), dim3(PT_BLOCK), 0, f->ctx->stream, a, P);
+  with_dims(f->left->n_dims, [&](auto ND) { launch_points(common_invflux_kernel<ND()>, a.npairs, f->ctx->stream, a, P); });
   HFX_HIP(hipGetLastError());
   return 0;
 }
@@ -1758,10 +1621,7 @@ int hfx_int_inters_calculate_common_viscFlux(hfx_inters *f)
   HFX_DEFER(f->ctx, DM_INT_COMMON_VISCFLUX, nullptr, f, nullptr, 0, 0);
   const FaceArgs a = face_args(f);
   const Phys P = f->ctx->phys();
-  if (f->left->n_dims == 2)
-    hipLaunchKernelGGL(common_viscflux_kernel<2>, dim3(nblocks(a.npairs, PT_BLOCK)), dim3(PT_BLOCK), 0, f->ctx->stream, a, P);
-  else
-    hipLaunchKernelGGL(common_viscflux_kernel<3>, dim3(nblocks(a.npairs, PT_BLOCK)), dim3(PT_BLOCK), 0, f->ctx->stream, a, P);
+  with_dims(f->left->n_dims, [&](auto ND) { launch_points(common_viscflux_kernel<ND()>, a.npairs, f->ctx->stream, a, P); });
   HFX_HIP(hipGetLastError());
   return 0;
 }

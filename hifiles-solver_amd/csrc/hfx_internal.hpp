@@ -2,8 +2,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -16,6 +19,11 @@ namespace hfx
 void set_error(const char *fmt, ...);
 struct FusedData;
 struct GeneralData;
+struct TensorOps;
+// (the three are complete in their own translation units only: fused_hex.hip, general.hip, tensor_ops.hip)
+struct FusedDelete { void operator()(FusedData *p) const; };
+struct GeneralDelete { void operator()(GeneralData *p) const; };
+struct TensorOpsDelete { void operator()(TensorOps *p) const; };
 
 #define HFX_HIP(call)                                                                          \
   do                                                                                           \
@@ -38,27 +46,97 @@ struct GeneralData;
     }                              \
   } while (0)
 
+// the bytes all live DevBufs of the process hold (hfx_live_device_bytes_internal)
+inline std::atomic<long> g_live_device_bytes{0};
+
+// One device allocation and its owner (move-only): the only place of the library that allocates or frees device memory.
+// At least one element is allocated, so a buffer of an empty block still has an address.  Converts to T*: kernel argument
+// structs and the launchers read it as the plain pointer it holds.
+template <class T>
+class DevBuf
+{
+  T *p_ = nullptr;
+  size_t n_ = 0; // elements allocated
+
+public:
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept
+  {
+    if (this != &o)
+    {
+      reset();
+      std::swap(p_, o.p_);
+      std::swap(n_, o.n_);
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+
+  void reset()
+  {
+    if (!p_) return;
+    (void)hipFree(p_);
+    g_live_device_bytes -= (long)(sizeof(T) * n_);
+    p_ = nullptr;
+    n_ = 0;
+  }
+  // what it held goes; a failed allocation leaves the buffer empty
+  int alloc(size_t n)
+  {
+    reset();
+    n = std::max<size_t>(n, 1);
+    void *q = nullptr;
+    HFX_HIP(hipMalloc(&q, sizeof(T) * n));
+    p_ = (T *)q;
+    n_ = n;
+    g_live_device_bytes += (long)(sizeof(T) * n_);
+    return 0;
+  }
+  int alloc_zeroed(size_t n)
+  {
+    if (alloc(n)) return 1;
+    HFX_HIP(hipMemset(p_, 0, sizeof(T) * n_));
+    return 0;
+  }
+  // allocated on first use
+  int ensure(size_t n) { return p_ ? 0 : alloc(n); }
+  int ensure_zeroed(size_t n) { return p_ ? 0 : alloc_zeroed(n); }
+  int upload(const T *src, size_t n)
+  {
+    if ((!p_ || n_ != std::max<size_t>(n, 1)) && alloc(n)) return 1;
+    if (n) HFX_HIP(hipMemcpy(p_, src, sizeof(T) * n, hipMemcpyHostToDevice));
+    return 0;
+  }
+  int upload(const std::vector<T> &v) { return upload(v.data(), v.size()); }
+
+  T *get() const { return p_; }
+  size_t size() const { return n_; }
+  explicit operator bool() const { return p_ != nullptr; }
+  operator T *() const { return p_; }
+};
+
 // One registered operator matrix (m x k, column-major) on the device, in the
 // forms the contraction kernels consume.
 struct Operator
 {
   int m = 0, k = 0;
-  double *dense = nullptr; // (m,k) column-major
+  DevBuf<double> dense; // (m,k) column-major
   // the same zero-padded to whole MFMA tiles, (mpad, kpad) column-major with mpad = 16 ceil(m/16), kpad = 4 ceil(k/4): the
   // dense contraction kernels read operator fragments from it without bounds checks
-  double *dense_pad = nullptr;
+  DevBuf<double> dense_pad;
   int mpad = 0, kpad = 0;
   // ELL form: exact non-zeros of every row in ASCENDING column order (the
   // reference dgemm sums l ascending, src/funcs.cpp:110-117), padded with
   // (val 0, col = first column of the row).  Row-interleaved: entry q of row r
   // at [r + m*q].
   int nnz_max = 0;
-  double *ell_val = nullptr;
-  int *ell_idx = nullptr;
+  DevBuf<double> ell_val;
+  DevBuf<int> ell_idx;
   long nnz_total = 0;
   std::vector<double> h_val; // host copy of the ELL arrays (width max(nnz_max,1), row-interleaved)
   std::vector<int> h_idx;
-  bool present() const { return dense != nullptr; }
+  bool present() const { return (bool)dense; }
 };
 
 } // namespace hfx
@@ -182,39 +260,39 @@ struct hfx_eles
   hfx_ctx *ctx = nullptr;
   int n_eles = 0, n_upts = 0, n_fpts = 0, n_fields = 0, n_dims = 0, ele_type = 0, order = 0;
   bool viscous_ops = false;
-  double *h_ref = nullptr; // (n_eles) eles::h_ref for calc_dt_local
+  hfx::DevBuf<double> h_ref; // (n_eles) eles::h_ref for calc_dt_local
   // LES closure (hfx_eles_set_les)
   bool les_ready = false;
   hfx::LesParams les{};
-  double *wall_distance = nullptr, *Jacobian_fpts = nullptr;
+  hfx::DevBuf<double> wall_distance, Jacobian_fpts;
   // similarity-type closures (sgs_model 2, 3, 4): the filter matrix and the work arrays of calc_sgs_terms
   hfx::Operator filter_upts;
-  double *sgs_uu = nullptr, *sgs_ue = nullptr;
+  hfx::DevBuf<double> sgs_uu, sgs_ue;
   // integral diagnostics (hfx_eles_set_volume_cubpts)
   int n_vol_cubpts = 0;
   hfx::Operator opp_volume_cubpts;
-  double *weight_volume_cubpts = nullptr, *vol_detjac_vol_cubpts = nullptr, *iq_u = nullptr, *iq_g = nullptr;
+  hfx::DevBuf<double> weight_volume_cubpts, vol_detjac_vol_cubpts, iq_u, iq_g;
+  hfx::DevBuf<int> iq_ids; // the quantity ids of the call that runs
   // plot-point interpolation (hfx_eles_set_opp_p)
   int n_ppts = 0;
   hfx::Operator opp_p;
-  double *disu_ppts = nullptr;
+  hfx::DevBuf<double> disu_ppts;
   // over-integration (hfx_eles_set_over_int)
   bool over_int_ready = false;
   int n_cubpts = 0;
   hfx::Operator opp_over_int_cubpts, over_int_filter;
-  double *JGinv_over_int_cubpts = nullptr, *u_cub = nullptr, *t_cub = nullptr;
+  hfx::DevBuf<double> JGinv_over_int_cubpts, u_cub, t_cub;
   // shock capturing (hfx_eles_set_shock_capture)
   bool shock_ready = false;
   hfx::Operator inv_vandermonde, exp_filter;
-  double *persson_num = nullptr, *persson_den = nullptr; // (n_upts) weights of the sensor's two sums
+  hfx::DevBuf<double> persson_num, persson_den; // (n_upts) weights of the sensor's two sums
   double s0 = 0.0;
   int shock_det_field = 0;
   hfx::Operator opp_0, opp_1[3], opp_2[3], opp_3, opp_4[3], opp_5[3], opp_6;
   // metrics
-  double *detjac_upts = nullptr, *JGinv_upts = nullptr, *detjac_fpts = nullptr, *JGinv_fpts = nullptr,
-         *tdA_fpts = nullptr, *norm_fpts = nullptr;
+  hfx::DevBuf<double> detjac_upts, JGinv_upts, detjac_fpts, JGinv_fpts, tdA_fpts, norm_fpts;
   // state / work arrays, indexed by hfx_array_id
-  double *arr[HFX_N_ARRAYS] = {};
+  hfx::DevBuf<double> arr[HFX_N_ARRAYS];
   long arr_len[HFX_N_ARRAYS] = {};
   bool src_nonzero = false;
   // deferred execution: disu_fpts holds opp_0 . disu_upts(0) of the CURRENT state (the fused stages leave it so; anything
@@ -224,13 +302,13 @@ struct hfx_eles
   unsigned long sent_on = 0; // fpts_sent: the serial number of the communicator that message travels on,
   int sent_blocks = 0;       // and the partition-face blocks of this element block it carries
   unsigned stale = 0;
-  unsigned long long *nan_flag = nullptr; // device: smallest flat index of a NaN in div_tconf, or ~0
-  double *red_buf = nullptr;              // device partial sums for reductions
+  hfx::DevBuf<unsigned long long> nan_flag; // device: smallest flat index of a NaN in div_tconf, or ~0
+  hfx::DevBuf<double> red_buf;            // device partial sums for reductions
   int red_blocks = 0;
-  void *tensor_ops = nullptr; // hfx::TensorOps: 1-D factors of the over-integration / shock-capturing matrices
+  std::unique_ptr<hfx::TensorOps, hfx::TensorOpsDelete> tensor_ops; // 1-D factors of the over-integration / shock-capturing matrices
   // fused-path private data (built lazily)
-  hfx::FusedData *fused = nullptr;
-  hfx::GeneralData *general = nullptr; // the general (non-tensor-product) fused stage (general.hip)
+  std::unique_ptr<hfx::FusedData, hfx::FusedDelete> fused;
+  std::unique_ptr<hfx::GeneralData, hfx::GeneralDelete> general; // the general (non-tensor-product) fused stage (general.hip)
   std::vector<hfx_inters *> faces_attached;
 };
 
@@ -239,18 +317,18 @@ struct hfx_inters
   hfx_ctx *ctx = nullptr;
   hfx_eles *left = nullptr, *right = nullptr;
   int n_inters = 0, n_fpts_per_inter = 0;
-  int *L = nullptr, *R = nullptr; // device (n_fpts_per_inter, n_inters)
+  hfx::DevBuf<int> L, R;          // device (n_fpts_per_inter, n_inters)
   std::vector<int> hL, hR;        // host copies (for building per-element tables)
   // partition faces (is_mpi): R holds the received-record slot lut(j); buffers are owned here
   bool is_mpi = false;
-  double *out_disu = nullptr, *in_disu = nullptr, *out_grad = nullptr, *in_grad = nullptr;
-  double *out_sgsf = nullptr, *in_sgsf = nullptr; // LES: physical SGS flux records (allocated when the left block has a closure)
+  hfx::DevBuf<double> out_disu, in_disu, out_grad, in_grad;
+  hfx::DevBuf<double> out_sgsf, in_sgsf; // LES: physical SGS flux records (allocated when the left block has a closure)
   // neighbour segments (hfx_mpi_inters_set_neighbours): faces [send[s], send[s]+count[s]) go to peer[s], its faces arrive at recv[s]
   std::vector<int> seg_peer, seg_send, seg_recv, seg_count;
   // boundary faces (is_bdy): left side only
   bool is_bdy = false;
-  int *boundary_id = nullptr; // device (n_inters)
-  hfx_bc *bcs = nullptr;      // device (n_bcs)
+  hfx::DevBuf<int> boundary_id; // device (n_inters)
+  hfx::DevBuf<hfx_bc> bcs;      // device (n_bcs)
   int n_bcs = 0, ramp_counter = 0;
   bool any_ramp = false; // a group of this block ramps its total pressure: run_input.pressure_ramp (src/input.cpp:374-377)
   double R_ref = 0.0;
@@ -265,7 +343,7 @@ struct hfx_comm
   int nranks = 1, rank = 0;
   hipEvent_t packed[3] = {nullptr, nullptr, nullptr};   // compute -> comm: buffers of kind 0 / 1 / 2 are packed
   hipEvent_t received[3] = {nullptr, nullptr, nullptr}; // comm -> compute: exchange of kind 0 / 1 / 2 complete
-  double *scratch = nullptr;                   // device scratch of the small all-reduces
+  hfx::DevBuf<double> scratch;                 // device scratch of the small all-reduces
   // exchange accounting (hfx_comm_exchange_stats): messages of kind 0 / 1 / 2 posted and waited for, one per partition-face
   // block -- what the per-method send_* / receive_* calls of those blocks would have posted -- and how many solution messages
   // of partition-face blocks are posted and not consumed yet
@@ -313,7 +391,7 @@ int side_stream_fork(hfx_ctx *ctx);
 int side_stream_join(hfx_ctx *ctx);
 int side_stream_wait(hfx_ctx *ctx);
 // (hfx.hip) the squared length scale of the eddy-viscosity closures at every solution point, for the fused stages' flux kernels
-int les_len2_upload(hfx_eles *e, double **dst);
+int les_len2_upload(hfx_eles *e, DevBuf<double> &dst);
 } // namespace hfx
 // a per-method entry point: recorded while the context defers (and is not replaying)
 #define HFX_DEFER(ctx_, method_, e_, f_, c_, i0_, i1_)  \
@@ -330,3 +408,5 @@ extern "C" int hfx_bdy_launch_internal(hfx_inters *f, int visc, int fast);
 extern "C" int hfx_mpi_sgsf_buffers_internal(hfx_inters *f); // allocates out / in_sgsf when the left block has a closure
 extern "C" int hfx_les_sgsf_upts_internal(hfx_eles *e);
 extern "C" int hfx_les_extrapolate_reference_internal(hfx_eles *e); // sgsf_fpts = opp_0 * sgsf_upts, not yet back-transformed
+// the bytes of device memory the library holds now (all contexts of the process): what a create / destroy cycle must give back
+extern "C" long hfx_live_device_bytes_internal(void);

@@ -20,24 +20,24 @@ constexpr int MAX_TAB = 256;
 
 struct FusedData
 {
-  unsigned char *meta = nullptr; // bit0: this point is the RIGHT side, bit1: beta sign flipped, bit2: boundary point
-  double *disu_alt = nullptr;    // second disu_fpts buffer
-  double *fn_fpts = nullptr;     // split variant 3: projected viscous flux per flux point (n_fpts,n_eles,n_fields)
+  DevBuf<unsigned char> meta; // bit0: this point is the RIGHT side, bit1: beta sign flipped, bit2: boundary point
+  DevBuf<double> disu_alt;    // second disu_fpts buffer
+  DevBuf<double> fn_fpts;     // split variant 3: projected viscous flux per flux point (n_fpts,n_eles,n_fields)
   // tensor-product tables of the sum-factorised flux kernel (valid when tensor_ok)
-  long long *stamps = nullptr; // diagnostics buffer (HFX_FLUX_STAMPS=1)
+  DevBuf<long long> stamps; // diagnostics buffer (HFX_FLUX_STAMPS=1)
   bool tensor_ok = false;
-  double *t_coef = nullptr; // Dm[N][N] | c5[ND][2][N] | Lf[ND][2][N] | L1[ND][2][N] | c3[ND][2][N]
+  DevBuf<double> t_coef; // Dm[N][N] | c5[ND][2][N] | Lf[ND][2][N] | L1[ND][2][N] | c3[ND][2][N]
   std::vector<double> h_coef; // host copy
-  int *t_idx = nullptr;     // pf[ND][L][2] | fdq[NFP] | fbase[NFP]
-  unsigned *pk_g = nullptr, *pk_r = nullptr; // packed operator rows of the gradient / residual kernel
-  double *tab_g = nullptr, *tab_r = nullptr; // value tables (MAX_TAB doubles)
-  int *o1m_dim = nullptr;                    // (n_fpts) dimension slab of the merged opp_1 row
-  int *nbr = nullptr;                        // (n_fpts, n_eles) partner of every interior flux point (split3_kernels.hpp, Split2Args::nbr)
+  DevBuf<int> t_idx;     // pf[ND][L][2] | fdq[NFP] | fbase[NFP]
+  DevBuf<unsigned> pk_g, pk_r; // packed operator rows of the gradient / residual kernel
+  DevBuf<double> tab_g, tab_r; // value tables (MAX_TAB doubles)
+  DevBuf<int> o1m_dim;                       // (n_fpts) dimension slab of the merged opp_1 row
+  DevBuf<int> nbr;                           // (n_fpts, n_eles) partner of every interior flux point (split3_kernels.hpp, Split2Args::nbr)
   // partitioned blocks: the elements that own a flux point without a registered face (= a partition-face point), and the rest
-  int *upd_list_b = nullptr, *upd_list_i = nullptr;
+  DevBuf<int> upd_list_b, upd_list_i;
   long n_list_b = 0, n_list_i = 0;
   long n_list_i1 = 0; // the flux kernel takes the others in two parts: upd_list_i[0 .. n_list_i1) and the rest
-  double *les_len2 = nullptr;                // (n_upts, n_eles) squared length scale of the LES closure evaluated in the flux kernel
+  DevBuf<double> les_len2;                   // (n_upts, n_eles) squared length scale of the LES closure evaluated in the flux kernel
   bool built = false;
 };
 

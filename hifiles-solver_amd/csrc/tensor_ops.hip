@@ -119,35 +119,21 @@ struct TensorOps
   // over-integration
   bool over_int = false;
   int N = 0, Nc = 0;
-  double *I1 = nullptr, *F1 = nullptr; // device: (Nc x N) interpolation, (N x Nc) projection
+  DevBuf<double> I1, F1;               // device: (Nc x N) interpolation, (N x Nc) projection
   std::vector<double> hF1;             // host copy of F1
-  double *F1f = nullptr;               // device: n_dims matrices (N x Nc): the projection followed by a 1-D operator of the caller
+  DevBuf<double> F1f;                  // device: n_dims matrices (N x Nc): the projection followed by a 1-D operator of the caller
   bool folded = false;
   // shock capturing
   bool shock = false;
-  double *W1 = nullptr, *E1 = nullptr;         // device: (N x N) modal transform, (N x N) filter
-  double *wnum = nullptr, *wden = nullptr;     // device: sensor weights per TENSOR mode
+  DevBuf<double> W1, E1;     // device: (N x N) modal transform, (N x N) filter
+  DevBuf<double> wnum, wden; // device: sensor weights per TENSOR mode
 };
-
-static void free_dev(double *&p)
-{
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-void tensor_ops_destroy(hfx_eles *e)
-{
-  TensorOps *T = (TensorOps *)e->tensor_ops;
-  if (!T) return;
-  for (double **p : {&T->I1, &T->F1, &T->F1f, &T->W1, &T->E1, &T->wnum, &T->wden}) free_dev(*p);
-  delete T;
-  e->tensor_ops = nullptr;
-}
+void TensorOpsDelete::operator()(TensorOps *p) const { delete p; }
 
 static TensorOps *ops_of(hfx_eles *e)
 {
-  if (!e->tensor_ops) e->tensor_ops = new TensorOps();
-  return (TensorOps *)e->tensor_ops;
+  if (!e->tensor_ops) e->tensor_ops.reset(new TensorOps());
+  return e->tensor_ops.get();
 }
 
 static int tensor_n1(const hfx_eles *e)
@@ -155,14 +141,6 @@ static int tensor_n1(const hfx_eles *e)
   if (e->ele_type != 4 && e->ele_type != 1) return 0;
   const int N = e->order + 1;
   return ipow_i(N, e->n_dims) == e->n_upts ? N : 0;
-}
-
-static int upload_d(double **dst, const std::vector<double> &v)
-{
-  free_dev(*dst);
-  HFX_HIP(hipMalloc((void **)dst, sizeof(double) * std::max<size_t>(v.size(), 1)));
-  HFX_HIP(hipMemcpy(*dst, v.data(), sizeof(double) * v.size(), hipMemcpyHostToDevice));
-  return 0;
 }
 
 static const double KRON_TOL = 1e-12;
@@ -183,7 +161,7 @@ int tensor_over_int_setup(hfx_eles *e, int n_cubpts, const double *opp_cub, cons
   std::vector<double> I1, F1;
   if (!kron_factor(opp_cub, e->n_dims, Nc, N, I1, KRON_TOL)) return 0;
   if (!kron_factor(filter, e->n_dims, N, Nc, F1, KRON_TOL)) return 0;
-  if (upload_d(&T->I1, I1) || upload_d(&T->F1, F1)) return 1;
+  if (T->I1.upload(I1) || T->F1.upload(F1)) return 1;
   T->hF1 = F1;
   T->folded = false;
   T->N = N;
@@ -199,7 +177,7 @@ int tensor_over_int_setup(hfx_eles *e, int n_cubpts, const double *opp_cub, cons
 // n_fields values per solution point instead of n_fields * n_dims.
 int tensor_over_int_set_fold(hfx_eles *e, const double *Dc)
 {
-  TensorOps *T = (TensorOps *)e->tensor_ops;
+  TensorOps *T = e->tensor_ops.get();
   HFX_CHECK(T && T->over_int, "over-integration: no tensor factors");
   const int N = T->N, Nc = T->Nc, nd = e->n_dims;
   std::vector<double> M((size_t)nd * N * Nc, 0.0);
@@ -211,11 +189,11 @@ int tensor_over_int_set_fold(hfx_eles *e, const double *Dc)
         for (int m = 0; m < N; m++) s += Dc[((size_t)d * N + mp) * N + m] * T->hF1[m + (size_t)N * c];
         M[(size_t)d * N * Nc + mp + (size_t)N * c] = s;
       }
-  if (upload_d(&T->F1f, M)) return 1;
+  if (T->F1f.upload(M)) return 1;
   T->folded = true;
   return 0;
 }
-bool tensor_over_int_folded(const hfx_eles *e) { return tensor_over_int_available(e) && ((TensorOps *)e->tensor_ops)->folded; }
+bool tensor_over_int_folded(const hfx_eles *e) { return tensor_over_int_available(e) && e->tensor_ops->folded; }
 
 int tensor_shock_setup(hfx_eles *e, const double *inv_vandermonde, const double *exp_filter, const double *norm_basis,
                        const int *high_modes)
@@ -239,14 +217,14 @@ int tensor_shock_setup(hfx_eles *e, const double *inv_vandermonde, const double 
   }
   if (!kron_factor(Wt.data(), nd, N, N, W1, KRON_TOL)) return 0;
   if (!kron_factor(exp_filter, nd, N, N, E1, KRON_TOL)) return 0;
-  if (upload_d(&T->W1, W1) || upload_d(&T->E1, E1) || upload_d(&T->wnum, wn) || upload_d(&T->wden, wd)) return 1;
+  if (T->W1.upload(W1) || T->E1.upload(E1) || T->wnum.upload(wn) || T->wden.upload(wd)) return 1;
   T->N = N;
   T->shock = true;
   return 0;
 }
 
-bool tensor_over_int_available(const hfx_eles *e) { return e->ctx->opt.tensor_ops && e->tensor_ops && ((TensorOps *)e->tensor_ops)->over_int; }
-bool tensor_shock_available(const hfx_eles *e) { return e->ctx->opt.tensor_ops && e->tensor_ops && ((TensorOps *)e->tensor_ops)->shock; }
+bool tensor_over_int_available(const hfx_eles *e) { return e->ctx->opt.tensor_ops && e->tensor_ops && e->tensor_ops->over_int; }
+bool tensor_shock_available(const hfx_eles *e) { return e->ctx->opt.tensor_ops && e->tensor_ops && e->tensor_ops->shock; }
 
 // ---- device ---------------------------------------------------------------------------------------------------
 
@@ -540,13 +518,13 @@ static int oi_pick_n(hfx_eles *e, const OverIntArgs &a, size_t lds, int grid, in
 
 int tensor_over_int_launch(hfx_eles *e, bool folded)
 {
-  TensorOps *T = (TensorOps *)e->tensor_ops;
+  TensorOps *T = e->tensor_ops.get();
   HFX_CHECK(T && T->over_int, "over-integration: no tensor factors");
   HFX_CHECK(!folded || T->folded, "over-integration: the folded form was not set up");
   OverIntArgs a{};
   a.n_eles = e->n_eles;
   a.u = e->arr[HFX_DISU_UPTS0]; a.JGc = e->JGinv_over_int_cubpts; a.I1 = T->I1; a.F1 = T->F1;
-  a.F1f = folded ? T->F1f : nullptr;
+  a.F1f = folded ? T->F1f.get() : nullptr;
   // (folded: n_fields values per solution point, in the first n_fields planes of tdisf_upts)
   a.tdisf = e->arr[HFX_TDISF_UPTS];
   a.gamma = e->ctx->params.gamma;
@@ -705,7 +683,7 @@ static int shock_pick_n(hfx_eles *e, const ShockArgs &a, int grid, int n)
 
 int tensor_shock_launch(hfx_eles *e, bool refresh_disu_fpts)
 {
-  TensorOps *T = (TensorOps *)e->tensor_ops;
+  TensorOps *T = e->tensor_ops.get();
   HFX_CHECK(T && T->shock, "shock capturing: no tensor factors");
   ShockArgs a{};
   a.n_eles = e->n_eles;

@@ -23,5 +23,4 @@ int tensor_over_int_set_fold(hfx_eles *e, const double *Dc);
 bool tensor_over_int_folded(const hfx_eles *e);
 // sensor, and the filtered state where sensor >= s0; refresh_disu_fpts: also the flux-point solution of those elements
 int tensor_shock_launch(hfx_eles *e, bool refresh_disu_fpts = false);
-void tensor_ops_destroy(hfx_eles *e);
 } // namespace hfx
