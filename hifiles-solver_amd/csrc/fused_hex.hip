@@ -24,6 +24,7 @@
 #include "tensor_ops.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "kernels_mpi.hpp"
@@ -356,6 +357,104 @@ static int tensor_build(hfx_eles *e, FusedData *F, int N, const std::vector<doub
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------
+// Affine blocks.  On a parallelepiped the map from the reference element is affine: JGinv and detjac are the same at every point
+// of the element, the normal and tdA the same at every point of a face.  The registered arrays hold them evaluated point by
+// point from the eight-node shape derivatives and the vertex coordinates, so they agree to the rounding of that arithmetic
+// only.  A block is AFFINE when every element's metrics agree with the element's representative (the first solution point; on
+// a face: the face's first flux point) within
+//     tol = AFFINE_C * eps * (1 + R),   R = (block volume / element volume)^(1/n_dims),
+// relative to the element's own max |JGinv|, |detjac| and tdA (normals: absolute, they are unit vectors).  Derivation
+// ("Affine blocks"): a Jacobian entry is a sum of eight products dN_i x_i with sum |dN_i| <= 1, so its error
+// is below 11 eps max|x| on an entry of size h / 2; JGinv entries (differences of two products of Jacobian entries) carry 4
+// such relative errors, detjac (six triple products) up to 18, and two points are compared: 2 * 18 * 11 * 2 = 792 <= 1024
+// times eps max|x| / h.  The block knows no coordinates: R, its own extent in element sizes, stands for max|x| / h.  One
+// element outside the bound makes the block general.  The result: one AffRec per element (FusedData::aff_rec).
+// ---------------------------------------------------------------------------------------
+constexpr double AFFINE_C = 1024.0;
+
+static int affine_detect(hfx_eles *e, FusedData *F)
+{
+  F->affine = false;
+  F->affine_tol = F->affine_spread = 0.0;
+  F->aff_rec.reset();
+  const int nd = e->n_dims, nq = nd * nd, nu = e->n_upts, nfp = e->n_fpts, npf = nfp / (2 * nd);
+  const long ne = e->n_eles, plane_f = (long)nfp * ne;
+  if (!e->JGinv_upts || !e->detjac_upts || !e->JGinv_fpts || !e->detjac_fpts || !e->tdA_fpts || !e->norm_fpts) return 0;
+  std::vector<double> dju((size_t)nu * ne);
+  HFX_HIP(hipMemcpy(dju.data(), e->detjac_upts, sizeof(double) * dju.size(), hipMemcpyDeviceToHost));
+  double vol = 0.0;
+  for (long el = 0; el < ne; el++) vol += std::fabs(dju[(size_t)nu * el]);
+  const double eps = 2.220446049250313e-16;
+  std::vector<double> recs((size_t)AffRec::SIZE * ne, 0.0);
+  // the per-point arrays in chunks of elements (an element's values are contiguous in each; the normal has a plane per dimension)
+  const long chunk = 2048;
+  std::vector<double> jgu, jgf, djf, tda, nrm;
+  double spread = 0.0, tol_max = 0.0;
+  bool ok = true;
+  for (long e0 = 0; e0 < ne; e0 += chunk)
+  {
+    const long nc = std::min(chunk, ne - e0);
+    jgu.resize((size_t)nq * nu * nc); jgf.resize((size_t)nq * nfp * nc); djf.resize((size_t)nfp * nc);
+    tda.resize((size_t)nfp * nc); nrm.resize((size_t)nfp * nc * nd);
+    HFX_HIP(hipMemcpy(jgu.data(), e->JGinv_upts + (size_t)nq * nu * e0, sizeof(double) * jgu.size(), hipMemcpyDeviceToHost));
+    HFX_HIP(hipMemcpy(jgf.data(), e->JGinv_fpts + (size_t)nq * nfp * e0, sizeof(double) * jgf.size(), hipMemcpyDeviceToHost));
+    HFX_HIP(hipMemcpy(djf.data(), e->detjac_fpts + (size_t)nfp * e0, sizeof(double) * djf.size(), hipMemcpyDeviceToHost));
+    HFX_HIP(hipMemcpy(tda.data(), e->tdA_fpts + (size_t)nfp * e0, sizeof(double) * tda.size(), hipMemcpyDeviceToHost));
+    for (int m = 0; m < nd; m++)
+      HFX_HIP(hipMemcpy(nrm.data() + (size_t)nfp * nc * m, e->norm_fpts + (size_t)nfp * e0 + m * plane_f, sizeof(double) * nfp * nc, hipMemcpyDeviceToHost));
+    for (long c = 0; c < nc; c++)
+    {
+      const long el = e0 + c;
+      double *r = &recs[(size_t)AffRec::SIZE * el];
+      const double *ju = &jgu[(size_t)nq * nu * c], *jf = &jgf[(size_t)nq * nfp * c];
+      const double dj = dju[(size_t)nu * el];
+      double sj = 0.0;
+      for (int q = 0; q < nq; q++)
+      {
+        r[AffRec::JG + q] = ju[q];
+        sj = std::max(sj, std::fabs(ju[q]));
+      }
+      r[AffRec::DJ] = dj;
+      if (!(std::fabs(dj) > 0.0) || !(sj > 0.0) || !(vol > 0.0)) { ok = false; continue; }
+      const double tol = AFFINE_C * eps * (1.0 + std::pow(vol / std::fabs(dj), 1.0 / nd));
+      tol_max = std::max(tol_max, tol);
+      double worst = 0.0; // largest difference from the representative, in units of its scale
+      auto see = [&](double diff, double scale) { worst = std::max(worst, std::fabs(diff) / scale); };
+      for (int p = 0; p < nu; p++)
+      {
+        for (int q = 0; q < nq; q++) see(ju[(size_t)nq * p + q] - ju[q], sj);
+        see(dju[(size_t)nu * el + p] - dj, std::fabs(dj));
+      }
+      for (int j = 0; j < nfp; j++)
+      {
+        for (int q = 0; q < nq; q++) see(jf[(size_t)nq * j + q] - ju[q], sj);
+        see(djf[(size_t)nfp * c + j] - dj, std::fabs(dj));
+        const int f = j / npf, j0 = f * npf;
+        double *rf = r + AffRec::FACE + AffRec::FACE_W * f;
+        const double t0 = tda[(size_t)nfp * c + j0];
+        if (!(t0 > 0.0)) { worst = 1.0; continue; }
+        for (int m = 0; m < nd; m++)
+        {
+          const double n0 = nrm[(size_t)nfp * nc * m + (size_t)nfp * c + j0];
+          rf[m] = n0;
+          see(nrm[(size_t)nfp * nc * m + (size_t)nfp * c + j] - n0, 1.0);
+        }
+        rf[AffRec::TDA] = t0;
+        see(tda[(size_t)nfp * c + j] - t0, t0);
+      }
+      spread = std::max(spread, worst);
+      if (!(worst <= tol)) ok = false; // (NaN included)
+    }
+  }
+  F->affine_tol = tol_max;
+  F->affine_spread = spread;
+  if (!ok) return 0;
+  if (F->aff_rec.upload(recs)) return 1;
+  F->affine = true;
+  return 0;
+}
+
 static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allow_unpaired = false)
 {
   HFX_CHECK(e->ele_type == 4 || e->ele_type == 1, "fused path: tensor-product elements only (hexes, quads)");
@@ -413,6 +512,8 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
     F->tensor_ok = false;
     if (split3_fits_rt(nd, N) && tensor_build(e, F, N, mv, mi, md)) return 1;
   }
+  // (whatever kernels the block runs: split_plan decides which of them read the record)
+  if (affine_detect(e, F)) return 1;
 
   const long plane_f = (long)e->n_fpts * e->n_eles;
   std::vector<char> paired(plane_f, 0);
@@ -535,22 +636,22 @@ static int element_grid(const hfx_eles *e, int threads, int per_cu, int cap = 1 
 }
 
 // launch of the loader-wave form, instantiated only for element sizes it fits (loader_wave_fits)
-template <int ND, int N, bool OI, bool GA, bool LES, bool FITS>
+template <int ND, int N, bool OI, bool GA, bool LES, bool FITS, bool AFF = false>
 struct LoaderWaveLaunch
 {
   static void go(const hfx_eles *, int, hipStream_t, const Split2Args &, const double *, const int *) {}
 };
-template <int ND, int N, bool OI, bool GA, bool LES>
-struct LoaderWaveLaunch<ND, N, OI, GA, LES, true>
+template <int ND, int N, bool OI, bool GA, bool LES, bool AFF>
+struct LoaderWaveLaunch<ND, N, OI, GA, LES, true, AFF>
 {
   static void go(const hfx_eles *e, int per_cu, hipStream_t st, const Split2Args &e2, const double *coef, const int *idx)
   {
     constexpr int TB = SGeo<ND, N>::TB + 64;
     // (the over-integration form measured 3 % faster at sixteen workgroups per CU than at the two that are resident)
     if (OI && per_cu == 0) per_cu = 16;
-    int grid = element_grid<split_flux_tensor_kernel<ND, N, 2, true, OI, true, GA, LES>>(e, TB, per_cu);
+    int grid = element_grid<split_flux_tensor_kernel<ND, N, 2, true, OI, true, GA, LES, AFF>>(e, TB, per_cu);
     if (e2.ele_list != nullptr) grid = (int)std::max<long>(1, std::min<long>(grid, e2.n_list));
-    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, 2, true, OI, true, GA, LES>), dim3(grid), dim3(TB), 0, st, e2, coef, idx);
+    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, 2, true, OI, true, GA, LES, AFF>), dim3(grid), dim3(TB), 0, st, e2, coef, idx);
   }
 };
 
@@ -625,6 +726,10 @@ SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int r
   p.buf = opt.buffer_addressing && p.flux_buf_fits_4gib;
   p.wv = (p.flux == FluxForm::register_pipeline && !oi && p.buf && opt.flux_waves != 2) ? 3 : 2;
   p.update_buf = opt.buffer_addressing && p.update_fits_4gib;
+  // An affine block: the default form of the flux kernel (loader wave, corrections formed in the kernel, no over-integration, no
+  // LES closure) has an AFF instantiation for every element size the loader wave fits; the update kernel follows it.
+  // Every other form keeps the per-point metrics.
+  p.affine = v3 && F && F->affine && opt.affine_metrics && p.flux == FluxForm::loader_wave && p.gather && !oi && !p.les;
 
   // a partitioned block: variant 3 sends the projected viscous flux; element lists for the flux kernel without over-integration
   // (which runs on all elements first), for the update without shock capturing (whose filter follows the whole update)
@@ -639,6 +744,10 @@ SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int r
     p.extra_names = p.over_int == OverInt::dense ? ",evaluate_invFlux_over_int (dense)" : ",overint_tensor_kernel";
   else if (p.variant == 2 && e->les_ready && viscous)
     p.extra_names = ",sgsf_upts_kernel + ell_apply_kernel (SGS flux)";
+  else if (F && F->affine)
+    // (no launch of its own: the flux and update kernels read the per-element metric record | the block was found affine, but the form
+    // that runs keeps the per-point metrics)
+    p.extra_names = p.affine ? ",affine_metrics" : ",affine_block";
   return p;
 }
 
@@ -777,6 +886,7 @@ struct SplitStageT final : SplitStage
     e2.les_len2 = F->les_len2;
     e2.nbr = pl.gather ? F->nbr.get() : nullptr;
     e2.disu = e->arr[HFX_DISU_FPTS];
+    e2.aff_rec = pl.affine ? F->aff_rec.get() : nullptr;
     fa2.meta = F->meta; fa2.plane_f = plane_f;
     fa2.disu = fa.disu; fa2.fn = F->fn_fpts; fa2.fnorm = fa.fnorm; fa2.tdA = fa.tdA; fa2.tconf = fa.tconf; fa2.P = P;
     return 0;
@@ -806,7 +916,12 @@ struct SplitStageT final : SplitStage
   void loader_wave()
   {
     constexpr bool fits = loader_wave_fits<ND, N>();
-    if (pl.gather)
+    static_assert(!fits || loader_wave_fits<ND, N, true>(), "the affine form fits wherever the loader wave does");
+    if (pl.affine)
+    {
+      if constexpr (!OI && !LES) LoaderWaveLaunch<ND, N, false, true, false, fits, true>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
+    }
+    else if (pl.gather)
       LoaderWaveLaunch<ND, N, OI, true, LES, fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
     else
       LoaderWaveLaunch<ND, N, OI, false, LES, fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
@@ -829,6 +944,8 @@ struct SplitStageT final : SplitStage
       if (listed && e2.n_list == 0) return 0;
       HFX_CHECK(!listed || (e2.ele_list != nullptr && !e->over_int_ready), "split flux kernel on element lists: no lists, or over-integration (which runs on all elements first)");
       HFX_CHECK(!pl.oi_fold || pl.flux == FluxForm::loader_wave, "over-integration: the folded form needs the loader-wave flux kernel");
+      HFX_CHECK(!pl.affine || (e2.aff_rec != nullptr && pl.flux == FluxForm::loader_wave && pl.gather && !pl.oi && !pl.les),
+                "split stage: the affine-metric form needs the block's metric records and the default loader-wave flux kernel");
       HFX_CHECK(!pl.les || (pl.flux == FluxForm::loader_wave && !pl.oi && P.viscous),
                 "split variant 3 with an LES closure needs the loader-wave flux kernel (SplitPlan::les_in_flux): run variant 2");
       switch (pl.flux)
@@ -1145,6 +1262,14 @@ void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant)
       // a partner word per point; the pairwise LDG kernel is not launched
       bytes[0] = 0.0;
       bytes[1] += ne * 4.0 * nfp;
+    }
+    if (pl.affine)
+    {
+      // the element's metric record in place of the per-point metrics: the flux kernel reads its 34 doubles and JGinv at the
+      // solution points (which transforms the total flux) instead of JGinv / detjac at both point sets and the own normals; the
+      // update kernel the record's detjac.  The face kernel keeps the per-point normal and tdA (they multiply the pressure).
+      bytes[1] += ne * 8.0 * (AffRec::SIZE + nu * nd * nd - (nu * (nd * nd + 1) + nfp * (nd * nd + 1) + nfp * nd));
+      bytes[3] += ne * 8.0 * (1.0 - nu);
     }
   }
 }

@@ -515,6 +515,7 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value)
   else if (n == "bdy_beside") o.bdy_beside = value != 0;
   else if (n == "light_wave_short") o.light_wave_short = value != 0;
   else if (n == "tensor_ops") o.tensor_ops = value != 0;
+  else if (n == "affine_metrics") o.affine_metrics = value != 0;
   else if (n == "dense_waves") { HFX_CHECK(value == 0 || value == 4 || value == 8, "dense_waves must be 0, 4 or 8"); o.dense_waves = value; }
   else if (n == "dense_split") { HFX_CHECK(value == 0 || value == 1 || value == 2 || value == 4, "dense_split must be 0, 1, 2 or 4"); o.dense_split = value; }
   else if (n == "general_waves") { HFX_CHECK(value == 0 || value == 3 || value == 4 || value == 8, "general_waves must be 0, 3, 4 or 8"); o.general_waves = value; }

@@ -74,6 +74,9 @@ struct Split2Args
   long n_list;
   LesParams les;
   const double *les_len2, *tdA_fpts; // les_len2 (n_upts,n_eles): the closure's squared length scale (calc_sgsf_fast)
+  // an affine block (SplitPlan::affine): the per-element metric record (AffRec) the flux kernel's AFF form and the update kernel
+  // read in place of the per-point metric arrays; NULL: per-point metrics
+  const double *aff_rec;
 };
 
 template <int ND, int N>
@@ -433,26 +436,29 @@ __device__ __forceinline__ void dma16_region(const GArr<BUF> &g, lds_dp lds_dst,
     }
 }
 
-// LDS bytes of one workgroup of the loader-wave form: input slots + metric slot + work regions
-template <int ND, int N>
+// LDS bytes of one workgroup of the loader-wave form: input slots + metric slot + work regions.  AFF (affine blocks): no metric
+// slot, an AffRec behind each input slot
+template <int ND, int N, bool AFF = false>
 constexpr long loader_wave_lds()
 {
   using G = Geo<ND, N>;
   constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, NQ = ND * ND, NG = NF * ND;
-  return 8L * (cmax(NF * (NU + NFP), NG * NU) + NG * NU + 2 * NF * (NU + 1 + NFP) + NQ * (NU + NFP) + NU + (1 + ND) * NFP + 16);
+  constexpr int metrics = AFF ? 2 * AffRec::SIZE : NQ * (NU + NFP) + NU + (1 + ND) * NFP + 16;
+  return 8L * (cmax(NF * (NU + NFP), NG * NU) + NG * NU + 2 * NF * (NU + 1 + NFP) + metrics);
 }
 
 // does the loader-wave form fit this element size?  (vmcnt counts at most 63 DMA instructions in flight; two workgroups
 // of input slots + metric slot + work regions must fit the CU's 160 KiB of LDS)
-template <int ND, int N>
+// (AFF: the record is one more instruction beside the state and the corrections, and there are no metric instructions)
+template <int ND, int N, bool AFF = false>
 constexpr bool loader_wave_fits()
 {
   using G = Geo<ND, N>;
   constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, NQ = ND * ND;
   constexpr int UJ = NF * (((NU + 1) / 2 + 63) / 64), DJ = NF * (((NFP + 1) / 2 + 63) / 64);
   constexpr int L_JGU = (NQ * NU + 1) / 2, L_DJU = (NU + 1) / 2, L_JGF = (NQ * NFP + 1) / 2, L_DJF = (NFP + 1) / 2;
-  constexpr int N_M = (L_JGU + 63) / 64 + (L_DJU + 63) / 64 + (L_JGF + 63) / 64 + (1 + ND) * ((L_DJF + 63) / 64);
-  return UJ + DJ <= 63 && N_M <= 63 && 2 * loader_wave_lds<ND, N>() <= 160 * 1024;
+  constexpr int N_M = AFF ? 0 : (L_JGU + 63) / 64 + (L_DJU + 63) / 64 + (L_JGF + 63) / 64 + (1 + ND) * ((L_DJF + 63) / 64);
+  return UJ + DJ + (AFF ? 1 : 0) <= 63 && N_M <= 63 && 2 * loader_wave_lds<ND, N, AFF>() <= 160 * 1024;
 }
 
 // Does variant 3 fit this element size at all?  Its flux kernel holds one element's state, LDG corrections, gradient,
@@ -479,7 +485,11 @@ constexpr bool split3_fits()
 //     a second, short pencil pass (two more barriers) over the transformed SGS flux the solution-point threads kept in
 //     registers, whose result joins Fn before it is stored.
 // So an LES stage moves the bytes of a plain one (+ tdA, the Leonard terms of the similarity models) in the same three launches.
-template <int ND, int N, int WV, bool BUF, bool OI, bool LW, bool GA = false, bool LES = false>
+// AFF: an AFFINE block (SplitPlan::affine).  The metrics of an element are 34 numbers (AffRec), which the loader wave brings with
+// the input slot in ONE more DMA instruction (17 lanes): no metric slot, no metric requests, no barrier 2b; the compute waves read
+// the record by LDS broadcast where they use it and hold nothing of it across the point physics.  One per-point metric stays: a
+// solution point's own JGinv, read by its thread for the transform of the total flux (see phase B).
+template <int ND, int N, int WV, bool BUF, bool OI, bool LW, bool GA = false, bool LES = false, bool AFF = false>
 __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_flux_tensor_kernel(const Split2Args a,
                                                                                                const double *coef_g,
                                                                                                const int *tidx)
@@ -494,17 +504,21 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
   constexpr int U_DW = 2 * NF * NUS, D_DW = 2 * NF * NFP, SLOT = (U_DW + D_DW) / 2;
   static_assert(!LW || BUF, "the loader wave addresses through buffer descriptors");
   static_assert(!LES || (LW && !OI), "the in-kernel LES closure belongs to the loader-wave form without over-integration");
+  static_assert(!AFF || (LW && !LES), "the affine-metric form belongs to the loader-wave form without the LES closure");
+  // AFF: the element's metric record lies behind its input slot
+  constexpr int SLOTA = SLOT + (AFF ? AffRec::SIZE : 0), NPF = NFP / (2 * ND);
   __shared__ double sA[R1];      // su | sd, later st
   __shared__ double sB[NG * NU]; // sg, later the per-direction parts of the divergence
-  __shared__ double s_in[LW ? 2 * SLOT : 1];
+  __shared__ double s_in[LW ? 2 * SLOTA : 1];
   // LW: ONE metric slot (volume metrics, flux-point metrics, own normals of the element); it is free from the end of
   // phase B (barrier 3) on, which is when the loader refills it for the next element.  Regions start on 16-byte
   // boundaries (the loader moves 16 bytes per lane).
   constexpr int NQ = ND * ND;
   constexpr int O_JGU = 0, O_DJU = O_JGU + ((NQ * NU + 1) & ~1), O_JGF = O_DJU + ((NU + 1) & ~1), O_DJF = O_JGF + ((NQ * NFP + 1) & ~1),
                 NFPP = (NFP + 1) & ~1, O_NRM = O_DJF + NFPP, MET = O_NRM + ND * NFPP;
-  __shared__ double s_met[LW ? MET : 1];
+  __shared__ double s_met[(LW && !AFF) ? MET : 1];
   double *su = sA, *sd = sA + NF * NU;
+  [[maybe_unused]] const double *rec = s_in; // AFF: the record of the current element
   double *const st = sA, *const sg = sB, *const sp = sB;
   const cdptr coef = (cdptr)(uintptr_t)coef_g;
   // ---- which wave plays which part.  With 4 waves (P4 hexes: two HEAVY waves that own solution points and flux points,
@@ -630,6 +644,9 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
   const GArr<BUF> g_JGf(a.JGinv_fpts, plane_f * (ND * ND)), g_djf(a.detjac_fpts, plane_f), g_nrm(a.norm_fpts, plane_f * ND);
   const GArr<BUF> g_gu(a.grad_upts, plane_u * NG), g_gf(a.grad_fpts, plane_f * NG), g_fn(a.fn_fpts, tot_f),
       g_div(a.div, tot_u), g_td(a.tdisf_in, plane_u * NG);
+  [[maybe_unused]] const GArr<BUF> g_rec(AFF ? a.aff_rec : nullptr, (long)AffRec::SIZE * ne);
+  // AFF: this flux point's face in the record (faces are runs of NPF flux points: affine_detect)
+  [[maybe_unused]] const int fo = AffRec::FACE + AffRec::FACE_W * (tf / NPF);
   const unsigned lu = tu, lf = tf;
   unsigned lo_u[UNP], lo_d[DNP]; // lane offsets of the state / delta prefetch: (field plane + point)
 #pragma unroll
@@ -667,7 +684,18 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
   double JF[ND * ND], nrm[ND], djf_raw = 1.0;
   long ef_cur = 0;
   auto fetch_fmetrics = [&]() {
-    if constexpr (LW)
+    if constexpr (AFF)
+    {
+      if (viscous && is_f)
+      {
+#pragma unroll
+        for (int q = 0; q < ND * ND; q++) JF[q] = ldsv(&rec[AffRec::JG + q]);
+        djf_raw = ldsv(&rec[AffRec::DJ]);
+#pragma unroll
+        for (int m = 0; m < ND; m++) nrm[m] = ldsv(&rec[fo + m]);
+      }
+    }
+    else if constexpr (LW)
     {
       if (viscous && is_f)
       {
@@ -701,7 +729,8 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
       constexpr int L_U = (NU + 1) / 2, L_D = (NFP + 1) / 2; // lanes per field run
       constexpr int UJ = NF * ((L_U + 63) / 64), DJ = NF * ((L_D + 63) / 64);
       auto issue = [&](long e, int which) {
-        const lds_dp base = (lds_dp)s_in + which * SLOT;
+        const lds_dp base = (lds_dp)s_in + which * SLOTA;
+        if constexpr (AFF) dma16_region(g_rec, base + SLOT, AffRec::SIZE / 2, lane, (unsigned)((long)AffRec::SIZE * e) * 8u);
 #pragma unroll
         for (int k = 0; k < NF; k++) dma16_region(g_u0, base + k * NUS, L_U, lane, (unsigned)((long)NU * e + k * plane_u) * 8u);
         if (dma_delta)
@@ -711,6 +740,37 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
             dma16_region(g_delta, base + (U_DW / 2 + k * NFP), L_D, lane, (unsigned)((long)NFP * e + k * plane_f) * 8u);
         }
       };
+#define HFX_VMCNT(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
+      auto lstamp = [&](long kk, int slot) {
+        if (a.stamps != nullptr && blockIdx.x == 0 && kk == a.stamp_it && lane == 0) a.stamps[3 * 16 + slot] = clock64();
+      };
+      if constexpr (AFF)
+      {
+        // ---- affine block: the record travels with the input slot, so the only requests in flight at the top of element k
+        // are those of element k itself -- vmcnt(0), and no metric slot to hand over (no barrier 2b)
+        static_assert(UJ + DJ + 1 <= 63, "loader wave: more DMA instructions in flight than vmcnt can count");
+        if (order.at(0) >= 0) issue(order.at(0), 0);
+        for (long kk = 0, e = order.at(0), e_next; e >= 0; kk++, e = e_next)
+        {
+          e_next = order.at(kk + 1);
+          lstamp(kk, 0);
+          HFX_VMCNT(0);
+          lstamp(kk, 1);
+          lds_barrier(); // 1: the compute waves may read the input slot and the record
+          if (gather) lds_barrier(); // 1b
+          lstamp(kk, 2);
+          if (e_next >= 0) issue(e_next, (int)((kk + 1) & 1));
+          lstamp(kk, 3);
+          lds_barrier(); // 2
+          lstamp(kk, 4);
+          lds_barrier(); // 3
+          lstamp(kk, 5);
+          lstamp(kk, 6);
+          lds_barrier(); // 4
+          lstamp(kk, 7);
+        }
+        return;
+      }
       // metrics: 16 bytes per lane, partial last wave-instruction masked (an inactive lane writes nothing)
       constexpr int L_JGU = (NQ * NU + 1) / 2, L_DJU = (NU + 1) / 2, L_JGF = (NQ * NFP + 1) / 2, L_DJF = (NFP + 1) / 2; // lanes
       constexpr int N_MU = (L_JGU + 63) / 64 + (L_DJU + 63) / 64;                          // volume metrics
@@ -729,15 +789,11 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
             dma16_region(g_nrm, (lds_dp)s_met + (O_NRM + m * NFPP), L_DJF, lane, (unsigned)((long)NFP * e + m * plane_f) * 8u);
         }
       };
-#define HFX_VMCNT(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
       if (order.at(0) >= 0)
       {
         issue(order.at(0), 0);
         issue_met(order.at(0));
       }
-      auto lstamp = [&](long kk, int slot) {
-        if (a.stamps != nullptr && blockIdx.x == 0 && kk == a.stamp_it && lane == 0) a.stamps[3 * 16 + slot] = clock64();
-      };
       for (long kk = 0, e = order.at(0), e_next; e >= 0; kk++, e = e_next)
       {
         e_next = order.at(kk + 1);
@@ -836,8 +892,9 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
     }
     if constexpr (LW)
     {
-      su = s_in + (kk & 1) * SLOT;
+      su = s_in + (kk & 1) * SLOTA;
       sd = su + U_DW / 2;
+      rec = su + SLOT;
     }
     else
     {
@@ -1058,27 +1115,47 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
       // else would fill the gaps).  Lanes beyond the last point of a kind repeat that point's arithmetic on clamped
       // numbers and do not store.  The inviscid and the viscous flux are summed BEFORE the one transform to reference space
       // (the reference transforms them separately, src/eles.cpp:1439-1470 and :2360-2387: a re-association).
+      // (AFF: both points share the element's JGinv and detjac -- row PF of jg2 / inv2 is row 0)
+      constexpr int PF = AFF ? 0 : 1;
       double jg2[2][NQ], inv2[2], u2[2][NF], g2[2][NG], f2[2][NG];
-#pragma unroll
-      for (int q = 0; q < NQ; q++)
-      {
-        jg2[0][q] = ldsv(&s_met[O_JGU + tu * NQ + q]);
-        jg2[1][q] = ldsv(&s_met[O_JGF + tf * NQ + q]);
-      }
       double nr2[ND];
+      // AFF: the solution point's OWN JGinv for the transform of the total flux to reference space, requested here and used
+      // behind the point physics.  That transform multiplies the free-stream pressure: where the exact flux is constant its
+      // divergence is the divergence of the metrics' rounding noise, and the reference's arrays hold that noise point by
+      // point (1e-14 of the pressure is 1e-10 of the smallest momentum component of the full-size case,
+      // tests/test_fullsize_vs_reference.py) -- the record stands for every metric that multiplies gradients and viscous
+      // fluxes only, where its perturbation stays relative.
+      [[maybe_unused]] double jgp[AFF ? NQ : 1];
+      if constexpr (AFF)
+      {
 #pragma unroll
-      for (int l = 0; l < ND; l++) nr2[l] = ldsv(&s_met[O_NRM + l * NFPP + tf]);
-      inv2[0] = ldsv(&s_met[O_DJU + tu]);
-      inv2[1] = ldsv(&s_met[O_DJF + tf]);
+        for (int q = 0; q < NQ; q++) jgp[q] = g_JGu.ld(eu * NQ, lu * NQ + q);
+#pragma unroll
+        for (int q = 0; q < NQ; q++) jg2[0][q] = ldsv(&rec[AffRec::JG + q]);
+        inv2[0] = ldsv(&rec[AffRec::DJ]);
+      }
+      else
+      {
+#pragma unroll
+        for (int q = 0; q < NQ; q++)
+        {
+          jg2[0][q] = ldsv(&s_met[O_JGU + tu * NQ + q]);
+          jg2[1][q] = ldsv(&s_met[O_JGF + tf * NQ + q]);
+        }
+#pragma unroll
+        for (int l = 0; l < ND; l++) nr2[l] = ldsv(&s_met[O_NRM + l * NFPP + tf]);
+        inv2[0] = ldsv(&s_met[O_DJU + tu]);
+        inv2[1] = ldsv(&s_met[O_DJF + tf]);
+      }
       if constexpr (LES)
       {
         // requested here, used behind the paired physics
         tdA_f = a.tdA_fpts[ef + tf];
         len2 = a.les_len2[eu + tu];
       }
-      lds_barrier(); // 2b: the metric slot is free, the loader requests the next element's metrics
+      if constexpr (!AFF) lds_barrier(); // 2b: the metric slot is free, the loader requests the next element's metrics
       inv2[0] = 1.0 / inv2[0];
-      inv2[1] = 1.0 / inv2[1];
+      if constexpr (!AFF) inv2[1] = 1.0 / inv2[1];
 #pragma unroll
       for (int k = 0; k < NF; k++)
       {
@@ -1112,11 +1189,11 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
         for (int l = 0; l < ND; l++)
         {
 #pragma unroll
-          for (int p = 0; p < 2; p++) tmp[p] = inv2[p] * g2[p][k + NF * l];
+          for (int p = 0; p < 2; p++) tmp[p] = inv2[p * PF] * g2[p][k + NF * l];
 #pragma unroll
           for (int d = 0; d < ND; d++)
 #pragma unroll
-            for (int p = 0; p < 2; p++) cg[p][d] += tmp[p] * jg2[p][l + ND * d];
+            for (int p = 0; p < 2; p++) cg[p][d] += tmp[p] * jg2[p * PF][l + ND * d];
         }
 #pragma unroll
         for (int d = 0; d < ND; d++)
@@ -1127,6 +1204,15 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
 #pragma unroll
         for (int q = 0; q < NG; q++) g_gf.st(ef + q * plane_f, lf, g2[1][q]);
       calc_visf_pair<ND>(a.P, u2, g2, f2);
+      if constexpr (AFF)
+      {
+        // the face's normal for the projection: the record again, where it is used (a broadcast read; nothing of the record was
+        // held through the point physics); the transform to reference space takes the point's own JGinv (above)
+#pragma unroll
+        for (int l = 0; l < ND; l++) nr2[l] = ldsv(&rec[fo + l]);
+#pragma unroll
+        for (int q = 0; q < NQ; q++) jg2[0][q] = jgp[q];
+      }
       // flux point: this side's viscous flux on its own normal
       if constexpr (LES)
       {
@@ -1212,13 +1298,23 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
     {
       // ---- a wave without solution points: the flux-point physics alone, metrics from the slot into registers first (2b)
       double JFl[NQ], nl[ND], grf[NG], fq[NG];
+      double inv_df;
+      if constexpr (AFF)
+      {
 #pragma unroll
-      for (int q = 0; q < NQ; q++) JFl[q] = ldsv(&s_met[O_JGF + tf * NQ + q]);
+        for (int q = 0; q < NQ; q++) JFl[q] = ldsv(&rec[AffRec::JG + q]);
+        inv_df = ldsv(&rec[AffRec::DJ]);
+      }
+      else
+      {
 #pragma unroll
-      for (int l = 0; l < ND; l++) nl[l] = ldsv(&s_met[O_NRM + l * NFPP + tf]);
-      double inv_df = ldsv(&s_met[O_DJF + tf]);
+        for (int q = 0; q < NQ; q++) JFl[q] = ldsv(&s_met[O_JGF + tf * NQ + q]);
+#pragma unroll
+        for (int l = 0; l < ND; l++) nl[l] = ldsv(&s_met[O_NRM + l * NFPP + tf]);
+        inv_df = ldsv(&s_met[O_DJF + tf]);
+      }
       if constexpr (LES) tdA_f = a.tdA_fpts[ef + tf];
-      lds_barrier(); // 2b
+      if constexpr (!AFF) lds_barrier(); // 2b
       inv_df = 1.0 / inv_df;
 #pragma unroll
       for (int q = 0; q < NG; q++) grf[q] = 0.0;
@@ -1245,6 +1341,11 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
 #pragma unroll
         for (int q = 0; q < NG; q++) g_gf.st(ef + q * plane_f, lf, grf[q]);
       calc_visf<ND, true>(a.P, uf, grf, fq);
+      if constexpr (AFF)
+      {
+#pragma unroll
+        for (int l = 0; l < ND; l++) nl[l] = ldsv(&rec[fo + l]);
+      }
 #pragma unroll
       for (int k = 0; k < NF; k++)
       {
@@ -1263,7 +1364,14 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
     {
     if (is_u)
     {
-      if constexpr (LW)
+      if constexpr (AFF)
+      {
+        // (the point's own JGinv: it transforms the inviscid flux -- see the paired form)
+#pragma unroll
+        for (int q = 0; q < NQ; q++) JG[q] = g_JGu.ld(eu * NQ, lu * NQ + q);
+        if (viscous) inv_detjac = 1.0 / ldsv(&rec[AffRec::DJ]);
+      }
+      else if constexpr (LW)
       {
         // volume metrics of this point from the slot the loader wave filled
 #pragma unroll
@@ -1678,7 +1786,8 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB), HFX_UPD_WAVES) void split_update
 #pragma unroll
     for (int k = 0; k < NF; k++) tcv[k] = g_tc.ld(ef + k * plane_f, lf);
     const double dt = a.dt_local_on ? a.dt_local[e] : a.dt;
-    const double dj = g_dj.ld(eu, lu);
+    // (an affine block: the element's detjac, one uniform 8-byte read of its record)
+    const double dj = a.aff_rec != nullptr ? a.aff_rec[(long)AffRec::SIZE * e + AffRec::DJ] : g_dj.ld(eu, lu);
 #pragma unroll
     for (int k = 0; k < NF; k++)
     {

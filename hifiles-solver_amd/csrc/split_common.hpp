@@ -38,7 +38,20 @@ struct FusedData
   long n_list_b = 0, n_list_i = 0;
   long n_list_i1 = 0; // the flux kernel takes the others in two parts: upd_list_i[0 .. n_list_i1) and the rest
   DevBuf<double> les_len2;                   // (n_upts, n_eles) squared length scale of the LES closure evaluated in the flux kernel
+  // an AFFINE block (every element a parallelepiped: metrics constant inside an element up to the rounding of their own
+  // evaluation -- affine_detect, fused_hex.hip): one AffRec per element in place of the per-point metric arrays
+  bool affine = false;
+  double affine_tol = 0.0, affine_spread = 0.0; // the relative bound of the test and the largest spread it met (diagnostics)
+  DevBuf<double> aff_rec;                       // (AffRec::SIZE, n_eles)
   bool built = false;
+};
+
+// The metric record of one element of an affine block (the face's tdA is recorded, no kernel reads it yet), 34 doubles (quads use the first 26): JGinv (n_dims^2, as in JGinv_upts),
+// detjac, then per local face the own normal (n_dims of 3 slots) and tdA.  Element stride 272 bytes and face offset 80 + 32 f:
+// a record is 17 16-byte lanes of the loader wave's LDS-DMA, a face is one aligned 32-byte read.
+struct AffRec
+{
+  static constexpr int JG = 0, DJ = 9, FACE = 10, FACE_W = 4, TDA = 3, SIZE = 34;
 };
 
 // the flux kernel of variant 3: the loader-wave form of split_flux_tensor_kernel, its register-pipeline forms, or the
@@ -66,6 +79,7 @@ struct SplitPlan
   int wv = 2;                   // register pipeline: WV
   bool buf = false;             // register pipeline: BUF
   bool gather = false;          // the flux kernel forms the interior LDG corrections itself (loader wave: GA)
+  bool affine = false;          // an affine block: the flux kernel (loader wave: AFF) and the update kernel read the per-element metric record
   bool face_delta = false;      // face_delta_kernel forms them (a viscous block without `gather`)
   bool oi_fold = false;         // the over-integration kernel hands over its result folded into the divergence
   OverInt over_int = OverInt::none;
