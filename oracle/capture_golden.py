@@ -261,6 +261,50 @@ CASES = [
     # a total-pressure ramp over several time steps: run_input.ramp_counter advances after every step (src/HiFiLES.cpp:224-225)
     case("quad_p3_ramp", dims=2, n=4, amp=0.1, level=1, order=3, steps=3,
          bcs={"y-": "WallT", "y+": "Slip", "x-": "InR", "x+": "Out"}, **BC_KEYS),
+    # supersonic face states: every other case above (but the Rusanov vortex) stays below Mach 0.1, where HLLC only ever
+    # takes its two star-state branches and RoeM's wave-speed clips never clip.  The Taylor-Green start is isothermal,
+    # so the local Mach number is |v|/a with constant a and the pressure stays positive while 1/(gamma M^2) > 0.375 in
+    # 3-D (M < 1.38) and > 0.5 in 2-D (M < 1.19).  tests/test_branch_census.py counts the branches taken.
+    # (a 3 x 3 x 2 box: with every intermediate of a residual, 27 P2 hexes no longer fit a file of 1 MiB)
+    case("hex_p2_transonic", n=[3, 3, 2], amp=0.15, level=2, order=2, steps=2, Mach_c_ic=1.2),
+    case("hex_p2_transonic_roem", n=[3, 3, 2], amp=0.15, level=2, order=2, steps=2, Mach_c_ic=1.2, riemann_solve_type=2),
+    # Sutherland's law on a temperature field that is not uniform: T leaves the isothermal start within the first
+    # stages; over the last stored state (step 2, stage 4) T / T_ref runs from 0.99398 to 1.00731 (298.2 K to 302.2 K).
+    # Mach 1.1: at 1.2 the P1 extrapolation to the flux points of this mesh gives a negative pressure in the first residual
+    case("hex_p1_transonic_sutherland", amp=0.1, level=1, order=1, steps=3, fix_vis=0, Mach_c_ic=1.1),
+    case("quad_p3_transonic", dims=2, n=4, amp=0.1, level=1, order=3, steps=2, Mach_c_ic=1.15),
+    # three cells along x: with two, every x face of the box lies where the Taylor-Green u vanishes and no face of a
+    # tetrahedron or prism sees a normal Mach number above 0.85.  Mach 1.25 on the tetrahedra: at 1.2 six flux-point pairs
+    # take S_L >= 0, at 1.3 the first residual has a negative pressure
+    case("tet_p2_transonic", n=[3, 2, 2], amp=0.1, level=1, order=2, steps=1, tets=True, Mach_c_ic=1.25,
+         upts_type_tet=0, fpts_type_tet=0, vcjh_scheme_tet=1, eta_tet=0.0),
+    case("pri_p2_transonic", n=[3, 2, 2], amp=0.1, level=1, order=2, steps=1, tets="prisms", Mach_c_ic=1.2,
+         upts_type_pri_tri=0, upts_type_pri_1d=0, vcjh_scheme_pri_1d=1, eta_pri=0.0, upts_type_tri=0,
+         vcjh_scheme_tri=1, c_tri=0.0),
+    # boundary states at supersonic normal Mach numbers: uniform oblique flow (a 343.8, Mach 1.22 along y, 1.31 along z),
+    # periodic in x.  "char" with supersonic inflow (z-) and supersonic outflow (z+); "sub_out_simp" with machn >= 1 (y+)
+    # and with reverse flow, u.n < 0 (y-: its ghost state comes from T_total)
+    case("hex_p1_bdy_supersonic", amp=0.1, level=2, order=1, steps=2, viscous=0, ic_form=1, riemann_solve_type=3,
+         rho_c_ic=1.2, u_c_ic=100.0, v_c_ic=420.0, w_c_ic=450.0, p_c_ic=101325.0,
+         bcs={"z-": "FarS", "z+": "FarS", "y-": "OutS2", "y+": "OutS2"},
+         bc_FarS_type="char", bc_FarS_p_static=101325.0, bc_FarS_mach=1.8, bc_FarS_T_static=294.0, bc_FarS_nx=0.16,
+         bc_FarS_ny=0.67, bc_FarS_nz=0.725,
+         bc_OutS2_type="sub_out_simp", bc_OutS2_p_static=101000.0, bc_OutS2_T_total=480.0, **BC_KEYS),
+    # the subsonic branches with u.n well away from zero: viscous uniform flow at Mach 0.6 along (0.55, 0.6, 0.58), so
+    # the normal Mach number is about 0.33 on every side.  "char" inflow (x-) and outflow (x+), "sub_in_char" (y-),
+    # "sub_out_char" (y+), an isothermal wall (z+), and on z- a "sub_in_char" inlet whose total temperature (600 K
+    # against the interior's 322 K) asks for more than sonic speed: the ghost Mach number is clamped to 1 (M2 >= 1 needs
+    # u.n + 5 c <= 4 sqrt(2 / (gamma + 1)) c0, here T_total >= 487 K)
+    case("hex_p2_bdy_transonic", amp=0.1, level=2, order=2, steps=1, ic_form=1, Mach_c_ic=0.6, nx_c_ic=0.55, ny_c_ic=0.6,
+         nz_c_ic=0.58,
+         bcs={"x-": "FarT", "x+": "FarT", "y-": "InT", "y+": "OutT", "z-": "InC", "z+": "WallT"},
+         bc_FarT_type="char", bc_FarT_p_static=P_TGV, bc_FarT_mach=0.55, bc_FarT_T_static=295.0, bc_FarT_nx=0.55,
+         bc_FarT_ny=0.6, bc_FarT_nz=0.58,
+         bc_InT_type="sub_in_char", bc_InT_p_total=P_TGV * 1.28, bc_InT_T_total=322.0, bc_InT_nx=0.0, bc_InT_ny=1.0,
+         bc_InT_nz=0.0,
+         bc_OutT_type="sub_out_char", bc_OutT_p_static=P_TGV * 0.98,
+         bc_InC_type="sub_in_char", bc_InC_p_total=P_TGV * 1.9, bc_InC_T_total=600.0, bc_InC_nx=0.0, bc_InC_ny=0.0,
+         bc_InC_nz=1.0, **BC_KEYS),
 ]
 
 

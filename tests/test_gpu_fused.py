@@ -127,6 +127,27 @@ def test_split_paths_every_order_vs_methods(dims, order):
         c.close()
 
 
+def test_split_paths_p4_supersonic_faces_vs_methods():
+    """The headline order (the loader-wave face kernel) at Mach 1.2: face states on all four branches of HLLC, split fused
+    kernels against the per-method path."""
+    n, kw = [3, 3, 3], dict(order=4, amp=0.1, Mach_c_ic=1.2)
+    ref = H.Case(n, **kw)
+    start = ref.array("disu_upts0").copy()
+    ref.to_device(0)
+    ref.run_steps_lib(1, fused=False)
+    ref.sync_host()
+    want = ref.array("disu_upts0").copy()
+    ref.close()
+    assert np.isfinite(want).all() and relerr(want, start) > 1e-8
+    for mode in (2, 3):
+        c = H.Case(n, **kw)
+        c.to_device(0)
+        c.run_steps_lib(1, fused=mode)
+        c.sync_host()
+        assert relerr(c.array("disu_upts0"), want) < 1e-12, mode
+        c.close()
+
+
 @pytest.mark.parametrize("knob,value,exact", [("simd_roles", 0, True), ("light_wave_short", 0, False), ("gather_delta", 0, False), ("loader_wave", 0, False), ("dictionary_rows", 1, False),
                                               ("buffer_addressing", 0, False), ("xcd_order", 0, True), ("split_grid_per_cu", 2, True), ("split_grid_per_cu", 16, True)])
 def test_split3_variant_knobs_agree(knob, value, exact):

@@ -72,8 +72,10 @@ def build(ctx, d, mode=hfx.CONTRACT_AUTO):
 
 
 @pytest.mark.parametrize("mode", [hfx.CONTRACT_SPARSE, hfx.CONTRACT_DENSE])
-def test_every_intermediate(ctx, mode):
-    d = dict(np.load(os.path.join(GOLDEN, "hex_p2_n3_deformed.npz")))
+@pytest.mark.parametrize("name", ["hex_p2_n3_deformed", "hex_p2_transonic"])
+def test_every_intermediate(ctx, name, mode):
+    """hex_p2_transonic: the common fluxes at face states on all four branches of HLLC (tests/test_branch_census.py)"""
+    d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
     e, faces = build(ctx, d, mode)
     e.extrapolate_solution()
     assert relerr(e.download(hfx.DISU_FPTS), d["s0_disu_fpts"]) < RTOL1
@@ -254,7 +256,7 @@ def test_stage_states_vs_reference(ctx, name):
 
 
 @pytest.mark.parametrize("name", ["hex_p4_n3_deformed", "hex_p3_n3_deformed", "hex_p1_roem", "hex_p4_jet", "hex_p3_shock",
-                                  "quad_p3_shock", "quad_p3_overint"])
+                                  "quad_p3_shock", "quad_p3_overint", "hex_p2_transonic", "hex_p2_transonic_roem"])
 def test_dense_mfma_path_vs_reference(ctx, name):
     d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
     e, faces = build(ctx, d, hfx.CONTRACT_DENSE)

@@ -24,6 +24,11 @@ def rel(a, b):
     ([2, 4, 4], [2, 1, 1], dict(riemann_solve_type=3)),
     ([4, 4, 2], [1, 1, 2], dict(riemann_solve_type=0, order=3)),
     ([2, 2, 4], [2, 2, 1], dict(riemann_solve_type=3)),
+    # supersonic face states: the two ranks of a partition face must pick the same branch of HLLC / clip of RoeM.  Three
+    # ranks along x: the Taylor-Green u vanishes at x = 0 and pi, where a two-rank split puts its partition faces
+    # (test_partition_gloo.py counts the supersonic points on the partition faces)
+    ([2, 4, 4], [3, 1, 1], dict(riemann_solve_type=3, Mach_c_ic=1.2)),
+    ([2, 4, 4], [3, 1, 1], dict(riemann_solve_type=2, Mach_c_ic=1.2)),
 ])
 def test_gpu_partition_invariance(tmp_path, mode, n_local, pgrid, kw):
     cfg = dict(CFG)
@@ -121,6 +126,8 @@ def test_gpu_partition_invariance_8_ranks(mode):
 @pytest.mark.parametrize("n_local,kw", [
     ([3, 4, 3], dict(riemann_solve_type=3, self_partition=[1, 0, 1])),
     ([4, 3, 3], dict(riemann_solve_type=0, order=3, self_partition=[0, 1, 0])),
+    # (wrap-around faces lie at x = 0 and z = 0, where u.n vanishes: supersonic interior faces beside subsonic partition faces)
+    ([3, 4, 3], dict(riemann_solve_type=3, Mach_c_ic=1.2, self_partition=[1, 0, 1])),
 ])
 def test_gpu_rccl_transport_self_partition(tmp_path, mode, n_local, kw):
     """libhfx's own transport (hfx_comm_*: grouped ncclSend / ncclRecv on the library's communication stream, ordered

@@ -95,8 +95,9 @@ def test_stage_states(oracle, name):
             bd, nbd = c.c_bdy()
 
 
-def test_every_intermediate(oracle):
-    d = dict(np.load(os.path.join(GOLDEN, "hex_p2_n3_deformed.npz")))
+@pytest.mark.parametrize("name", ["hex_p2_n3_deformed", "hex_p2_transonic"])
+def test_every_intermediate(oracle, name):
+    d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
     c = O.Case(d)
     e = c.c_eles()
     f, nfb = c.c_faces()

@@ -29,6 +29,10 @@ def rel(a, b):
     ([2, 4, 4], [2, 1, 1], dict(riemann_solve_type=3, LES=1, SGS_model=4, C_s=0.325, filter_ratio=2.0, filter_type=1)),
     ([2, 4, 4], [2, 1, 1], dict(riemann_solve_type=0, viscous=0, ic_form=1, u_c_ic=30.0, v_c_ic=10.0, w_c_ic=5.0,
                                 p_c_ic=101325.0, rho_c_ic=1.2)),          # inviscid: solution exchange only
+    # supersonic face states: the two ranks of a partition face must pick the same branch of HLLC / clip of RoeM.  Three
+    # ranks along x: the Taylor-Green u vanishes at x = 0 and pi, where every two-rank split puts its partition faces
+    ([2, 4, 4], [3, 1, 1], dict(riemann_solve_type=3, Mach_c_ic=1.2)),
+    ([2, 4, 4], [3, 1, 1], dict(riemann_solve_type=2, Mach_c_ic=1.2)),
 ])
 def test_partition_invariance_oracle(tmp_path, n_local, pgrid, kw):
     cfg = dict(CFG)
@@ -48,6 +52,27 @@ def test_partition_invariance_oracle(tmp_path, n_local, pgrid, kw):
         # scale of the state
         assert np.abs(div - div1).max() < 1e-12 * np.abs(u1).max()
     assert rel(u, u1) < 1e-12
+
+
+def test_supersonic_rows_put_supersonic_points_on_partition_faces():
+    """A condition on the inputs of the Mach 1.2 rows above (and of test_gpu_partition.py's): the one-sided kernels of
+    the partition faces see normal Mach numbers above one -- S_L >= 0 on one rank, S_R < 0 on its neighbour."""
+    import hfx_host as H
+    n_local, pgrid = [2, 4, 4], [3, 1, 1]
+    count = 0
+    for r in range(3):
+        c = H.Case(n_local, rank=r, pgrid=pgrid, Mach_c_ic=1.2, **CFG)
+        d = c.registration()
+        u = np.einsum("fu,uek->fek", d["opp_0"], c.array("disu_upts0"))
+        plane = u.shape[0] * u.shape[1]
+        idx = np.ravel(c.mpi_faces()[0], order="F")
+        u = u.reshape(plane, 5, order="F")[idx]
+        n = d["norm_fpts"].reshape(plane, 3, order="F")[idx]
+        v = u[:, 1:4] / u[:, :1]
+        p = 0.4 * (u[:, 4] - 0.5 * u[:, 0] * (v * v).sum(axis=1))
+        count += int((np.abs((v * n).sum(axis=1)) >= np.sqrt(1.4 * p / u[:, 0])).sum())
+        c.close()
+    assert count >= 3 * 8, count
 
 
 def test_partition_quads(tmp_path):
