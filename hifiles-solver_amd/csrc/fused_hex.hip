@@ -625,7 +625,8 @@ static int resident_per_cu(int threads)
   return n;
 }
 
-// grid of a persistent element kernel: the resident workgroups, or `per_cu` of them per CU when the option asks.  `cap`:
+// workgroups of a persistent element kernel: the resident ones, or `per_cu` of them per CU when the option asks -- what a
+// launcher hands to persistent_grid (hfx_internal.hpp), which every launch's grid comes from.  `cap`:
 // the streaming update kernel is fastest at three workgroups per CU (0.27 ms; 0.35 ms at the four that are resident, 0.29 ms
 // at sixteen)
 template <auto KERNEL>
@@ -651,6 +652,7 @@ struct LoaderWaveLaunch<ND, N, OI, GA, LES, true, AFF>
     if (OI && per_cu == 0) per_cu = 16;
     int grid = element_grid<split_flux_tensor_kernel<ND, N, 2, true, OI, true, GA, LES, AFF>>(e, TB, per_cu);
     if (e2.ele_list != nullptr) grid = (int)std::max<long>(1, std::min<long>(grid, e2.n_list));
+    grid = persistent_grid(e, SLOT_ELEMENT, e2.ele_list != nullptr ? e2.n_list : (long)e->n_eles, grid);
     hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, 2, true, OI, true, GA, LES, AFF>), dim3(grid), dim3(TB), 0, st, e2, coef, idx);
   }
 };
@@ -911,6 +913,13 @@ struct SplitStageT final : SplitStage
     return 0;
   }
 
+  // grid of the element kernel KERNEL on all elements, or on the list the step was given (the workgroups past its end find no work)
+  template <auto KERNEL>
+  int flux_grid() const
+  {
+    return persistent_grid(e, SLOT_ELEMENT, e2.ele_list != nullptr ? e2.n_list : (long)e->n_eles, element_grid<KERNEL>(e, TB, per_cu));
+  }
+
   // the loader-wave form with the plan's flags (instantiated only for the sizes it fits)
   template <bool OI, bool LES>
   void loader_wave()
@@ -929,8 +938,8 @@ struct SplitStageT final : SplitStage
   template <int WV, bool BUF, bool OI>
   void register_pipeline()
   {
-    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, WV, BUF, OI, false>),
-                       dim3(element_grid<split_flux_tensor_kernel<ND, N, WV, BUF, OI, false>>(e, TB, per_cu)), dim3(TB), 0, st, e2, F->t_coef, F->t_idx);
+    hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, WV, BUF, OI, false>), dim3(flux_grid<split_flux_tensor_kernel<ND, N, WV, BUF, OI, false>>()),
+                       dim3(TB), 0, st, e2, F->t_coef, F->t_idx);
   }
 
   // (partitioned blocks: the solution exchange runs beside the launch on interior_1, the exchange of the projected fluxes
@@ -971,7 +980,7 @@ struct SplitStageT final : SplitStage
           register_pipeline<2, false, false>();
         break;
       case FluxForm::dictionary_rows:
-        hipLaunchKernelGGL((split_flux_kernel<ND, N>), dim3(element_grid<split_flux_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, e2);
+        hipLaunchKernelGGL((split_flux_kernel<ND, N>), dim3(flux_grid<split_flux_kernel<ND, N>>()), dim3(TB), 0, st, e2);
         break;
       }
       HFX_HIP(hipGetLastError());
@@ -985,7 +994,7 @@ struct SplitStageT final : SplitStage
     if (!P.viscous) return 0;
     ea.pk = F->pk_g;
     ea.tab = F->tab_g;
-    hipLaunchKernelGGL((split_gradient_kernel<ND, N>), dim3(element_grid<split_gradient_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, ea);
+    hipLaunchKernelGGL((split_gradient_kernel<ND, N>), dim3(persistent_grid(e, SLOT_ELEMENT, e->n_eles, element_grid<split_gradient_kernel<ND, N>>(e, TB, per_cu))), dim3(TB), 0, st, ea);
     HFX_HIP(hipGetLastError());
     return 0;
   }
@@ -1022,7 +1031,7 @@ struct SplitStageT final : SplitStage
   void update_launch(long n_work)
   {
     // (the streaming update kernel is fastest at three workgroups per CU: element_grid)
-    const int g = (int)std::min<long>(n_work, element_grid<split_update_kernel<ND, N, BUF>>(e, TB, per_cu, 3));
+    const int g = persistent_grid(e, SLOT_UPDATE, n_work, std::min<long>(n_work, element_grid<split_update_kernel<ND, N, BUF>>(e, TB, per_cu, 3)));
     hipLaunchKernelGGL((split_update_kernel<ND, N, BUF>), dim3(g), dim3(TB), 0, st, e2);
   }
 
@@ -1034,7 +1043,7 @@ struct SplitStageT final : SplitStage
     {
       ea.pk = F->pk_r;
       ea.tab = F->tab_r;
-      hipLaunchKernelGGL((split_residual_kernel<ND, N>), dim3(element_grid<split_residual_kernel<ND, N>>(e, TB, per_cu)), dim3(TB), 0, st, ea);
+      hipLaunchKernelGGL((split_residual_kernel<ND, N>), dim3(persistent_grid(e, SLOT_UPDATE, e->n_eles, element_grid<split_residual_kernel<ND, N>>(e, TB, per_cu))), dim3(TB), 0, st, ea);
     }
     else if constexpr (V3)
     {

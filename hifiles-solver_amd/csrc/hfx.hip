@@ -497,6 +497,7 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value)
   if (n == "deferred") ctx->defer.on = value != 0;
   else if (n == "split_grid_per_cu") { HFX_CHECK(value >= 0, "split_grid_per_cu must be >= 0"); o.split_grid_per_cu = value; }
   else if (n == "flux_grid_per_cu") { HFX_CHECK(value >= 0, "flux_grid_per_cu must be >= 0"); o.flux_grid_per_cu = value; }
+  else if (n == "persistent_grid_cap") { HFX_CHECK(value >= 0, "persistent_grid_cap must be >= 0"); o.persistent_grid_cap = value; }
   else if (n == "xcd_order") o.xcd_order = value != 0;
   else if (n == "over_int_fold") o.over_int_fold = value != 0;
   else if (n == "general_update_waves") { HFX_CHECK(value == 0 || value == 4 || value == 8, "general_update_waves must be 0, 4 or 8"); o.general_update_waves = value; }
@@ -1807,6 +1808,19 @@ int hfx_fused_kernel_bytes(hfx_eles *e, double bytes[8])
 {
   HFX_CHECK(e && bytes, "hfx_fused_kernel_bytes: bad argument");
   split_kernel_bytes(e, bytes, e->ctx->fused_mode);
+  return 0;
+}
+
+int hfx_fused_launch_grids(hfx_eles *e, int max_launches, int *slot, int *grid, long *work, int *n_launches)
+{
+  HFX_CHECK(e && slot && grid && work && n_launches && max_launches >= 0, "hfx_fused_launch_grids: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  const hfx::LaunchLog &g = e->launch_log;
+  *n_launches = g.n;
+  for (int i = 0; i < g.n && i < max_launches; i++)
+  {
+    slot[i] = g.slot[i]; grid[i] = g.grid[i]; work[i] = g.work[i];
+  }
   return 0;
 }
 

@@ -212,6 +212,7 @@ struct hfx_ctx
   {
     int split_grid_per_cu = 0;  // persistent workgroups per CU of the split element kernels; 0: as many as are resident
     int flux_grid_per_cu = 0;   // the same for the loader-wave flux kernel alone (0: split_grid_per_cu)
+    int persistent_grid_cap = 0; // n > 0: no persistent element kernel is launched with more than n workgroups (persistent_grid); tests make small meshes loop with it
     int xcd_order = 1;          // workgroups of one XCD walk one contiguous eighth of the elements
     int dictionary_rows = 0;    // 1: the dictionary-row flux kernel even when the operators are tensor products
     int flux_waves = 2;         // waves per SIMD the sum-factorised flux kernel is launched for (2 or 3)
@@ -256,9 +257,23 @@ struct hfx_ctx
   }
 };
 
+namespace hfx
+{
+// The launches of the persistent element kernels since the block's last fused stage began (persistent_grid), in launch order
+// (hfx_fused_launch_grids): the slot of hfx_time_fused_kernels, the grid, the elements or list entries the launch walks
+struct LaunchLog
+{
+  static constexpr int MAX = 16;
+  int n = 0;
+  int slot[MAX] = {}, grid[MAX] = {};
+  long work[MAX] = {};
+};
+} // namespace hfx
+
 struct hfx_eles
 {
   hfx_ctx *ctx = nullptr;
+  mutable hfx::LaunchLog launch_log;
   int n_eles = 0, n_upts = 0, n_fpts = 0, n_fields = 0, n_dims = 0, ele_type = 0, order = 0;
   bool viscous_ops = false;
   hfx::DevBuf<double> h_ref; // (n_eles) eles::h_ref for calc_dt_local
@@ -312,6 +327,32 @@ struct hfx_eles
   std::unique_ptr<hfx::GeneralData, hfx::GeneralDelete> general; // the general (non-tensor-product) fused stage (general.hip)
   std::vector<hfx_inters *> faces_attached;
 };
+
+namespace hfx
+{
+// Slots of the persistent element kernels in hfx_fused_launch_grids: those of hfx_time_fused_kernels, and one each for the
+// over-integration and the shock-capturing kernel
+enum : int { SLOT_ELEMENT = 1, SLOT_UPDATE = 3, SLOT_OVER_INT = 4, SLOT_SHOCK = 5 };
+
+// The grid of EVERY persistent element kernel: `most`, the workgroups its launcher would start for `work` elements (or list
+// entries), and no more than the persistent_grid_cap option when that is set.  Notes the launch in the block's log.
+inline int persistent_grid(const hfx_eles *e, int slot, long work, long most)
+{
+  const int cap = e->ctx->opt.persistent_grid_cap;
+  const int grid = (int)(cap > 0 ? std::min<long>(most, cap) : most);
+  hfx::LaunchLog &g = e->launch_log;
+  // a stage launches its over-integration and flux (gradient) kernels, then its update (residual) kernels, then the shock filter: the
+  // first of the former behind one of the latter begins the next stage (a partitioned stage is driven step by step, each its own call)
+  const bool opens = slot == SLOT_OVER_INT || slot == SLOT_ELEMENT;
+  if (opens && g.n > 0 && (g.slot[g.n - 1] == SLOT_UPDATE || g.slot[g.n - 1] == SLOT_SHOCK)) g.n = 0;
+  if (g.n < hfx::LaunchLog::MAX)
+  {
+    g.slot[g.n] = slot; g.grid[g.n] = grid; g.work[g.n] = work;
+    g.n++;
+  }
+  return grid;
+}
+} // namespace hfx
 
 struct hfx_inters
 {

@@ -478,7 +478,7 @@ static int oi_launch_form(hfx_eles *e, const OverIntArgs &a, size_t lds, int gri
   // waits for a slot while the others are half way through their elements
   int per_cu = 0;
   HFX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, overint_tensor_kernel<ND, N, NC, FOLD>, oi_threads(cpow(NC, ND)), lds));
-  grid = (int)std::min<long>(e->n_eles, (long)e->ctx->n_cu * std::max(per_cu, 1));
+  grid = persistent_grid(e, SLOT_OVER_INT, e->n_eles, std::min<long>(e->n_eles, (long)e->ctx->n_cu * std::max(per_cu, 1)));
   hipLaunchKernelGGL((overint_tensor_kernel<ND, N, NC, FOLD>), dim3(grid), dim3(oi_threads(cpow(NC, ND))), lds, e->ctx->stream, a);
   HFX_HIP(hipGetLastError());
   return 0;
@@ -667,7 +667,7 @@ static int shock_pick_n(hfx_eles *e, const ShockArgs &a, int grid, int n)
     // persistent grid: the workgroups resident at once, or all of a small mesh
     int per_cu = 0;
     HFX_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, shock_tensor_kernel<ND, N>, 256, 0));
-    grid = (int)std::min<long>(grid, (long)e->ctx->n_cu * std::max(per_cu, 1));
+    grid = persistent_grid(e, SLOT_SHOCK, e->n_eles, std::min<long>(grid, (long)e->ctx->n_cu * std::max(per_cu, 1)));
     hipLaunchKernelGGL((shock_tensor_kernel<ND, N>), dim3(grid), dim3(256), 0, e->ctx->stream, a);
     HFX_HIP(hipGetLastError());
     return 0;

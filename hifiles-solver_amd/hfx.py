@@ -116,6 +116,14 @@ def deferred_stats(ctx_handle):
     return nf.value, nr.value, (why.value or b"").decode()
 
 
+def fused_launch_grids(eles_handle):
+    """[(slot, grid, work)] of the persistent element kernels since the block's last split fused stage began, in launch order
+    (hfx_fused_launch_grids: slot 1 flux / gradient, 3 update / residual, 4 over-integration, 5 shock capturing)"""
+    n, slot, grid, work = C.c_int(0), (C.c_int * 16)(), (C.c_int * 16)(), (C.c_long * 16)()
+    check(lib().hfx_fused_launch_grids(eles_handle, C.c_int(16), slot, grid, work, C.byref(n)))
+    return [(slot[i], grid[i], work[i]) for i in range(min(n.value, 16))]
+
+
 class Context:
     def __init__(self, device=0):
         self.h = C.c_void_p()

@@ -120,7 +120,10 @@ int hfx_ctx_set_fused_mode(hfx_ctx *ctx, int mode);
  * time step with calc_time_step (src/HiFiLES.cpp:198, src/solver.cpp:484-549) */
 int hfx_ctx_set_CFL(hfx_ctx *ctx, double CFL);
 /* Measurement knobs: kernel variants with the same results (A/B runs; defaults are the product path).  name:
- * "split_grid_per_cu" (0 = the workgroups resident at once | n), "xcd_order" (1), "dictionary_rows" (0), "flux_waves" (2 | 3), "buffer_addressing" (1),
+ * "split_grid_per_cu" (0 = the workgroups resident at once | n), "persistent_grid_cap" (0 = off | n: every persistent element kernel -- the
+ * split stage's flux, gradient, update and residual kernels, the sum-factorised over-integration and shock-capturing kernels -- is launched with
+ * min(its usual grid, n) workgroups, so that a mesh of a few elements runs their element loops past the first iteration; results do not change,
+ * hfx_fused_launch_grids reports the grids), "xcd_order" (1), "dictionary_rows" (0), "flux_waves" (2 | 3), "buffer_addressing" (1),
  * "loader_wave" (1), "fold_general" (1: the general fused stage applies opp_2 - opp_3 opp_1 and never forms norm_tdisf), "gather_delta" (1: the loader-wave flux kernel forms the interior LDG corrections itself, no pairwise
  * LDG launch), "simd_roles" (1: the flux kernel deals its waves' parts by SIMD), "comm_stream_faces" (1:
  * hfx_run_steps_partitioned launches the one-sided partition-face kernels on the communication stream), "flux_stamps" (0; n >= 1: cycle
@@ -496,6 +499,11 @@ int hfx_time_methods(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, i
 int hfx_time_fused_kernels(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int reps, double ms[8], char names[256]);
 /* ALGORITHMIC HBM bytes per launch of each fused kernel (same order), see DESIGN.md */
 int hfx_fused_kernel_bytes(hfx_eles *e, double bytes[8]);
+/* The launches of the persistent element kernels since the block's last split fused stage began, in launch order: slot[i] is the
+ * kernel's entry in hfx_time_fused_kernels (1 flux / gradient kernel, 3 update / residual kernel, 4 over-integration kernel) or 5 for the
+ * shock-capturing kernel, grid[i] its workgroups, work[i] the elements -- on a partitioned block the entries of the element list -- it walks.
+ * Writes min(*n_launches, max_launches) entries; at most 16 launches are kept. */
+int hfx_fused_launch_grids(hfx_eles *e, int max_launches, int *slot, int *grid, long *work, int *n_launches);
 /* The same for the general fused stage (hfx_run_steps_blocks(..., fused = 4)): ms[0..3] = pairwise LDG kernels, flux
  * kernels of all element blocks, pairwise common-flux kernels, update kernels of all blocks */
 int hfx_time_general_kernels(hfx_eles *const *eles, int n_ele_blocks, hfx_inters *const *faces, int n_face_blocks, int reps,

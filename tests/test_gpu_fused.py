@@ -149,29 +149,42 @@ def test_split_paths_p4_supersonic_faces_vs_methods():
 
 
 @pytest.mark.parametrize("knob,value,exact", [("simd_roles", 0, True), ("light_wave_short", 0, False), ("gather_delta", 0, False), ("loader_wave", 0, False), ("dictionary_rows", 1, False),
-                                              ("buffer_addressing", 0, False), ("xcd_order", 0, True), ("split_grid_per_cu", 2, True), ("split_grid_per_cu", 16, True)])
+                                              ("buffer_addressing", 0, False), ("xcd_order", 0, True), ("split_grid_per_cu", 2, True), ("split_grid_per_cu", 16, True),
+                                              ("persistent_grid_cap", 3, True), ("persistent_grid_cap", 8, True)])
 def test_split3_variant_knobs_agree(knob, value, exact):
     """hfx_ctx_set_option selects between forms of the split3 kernels (wave parts dealt by SIMD or by wave number, loader
     wave or register pipeline, sum-factorised or dictionary rows, buffer or flat addressing, element order, grid size).
-    Forms that only move work between waves or change addressing give the SAME bits; the others the same state to rounding."""
+    Forms that only move work between waves or change addressing give the SAME bits; the others the same state to rounding.
+    The 64 elements get a workgroup each whatever the element order and the grid options say: persistent_grid_cap makes them
+    loop (test_gpu_persistent_loops.py), and the xcd_order row runs a second time under a cap of 8 workgroups, where the order
+    it switches off is on in the baseline."""
     n = [4, 4, 4]
-    ref = H.Case(n, order=4, amp=0.1)
-    ref.to_device(0)
-    ref.run_steps_lib(2, fused=3)
-    ref.sync_host()
-    want = ref.array("disu_upts0").copy()
-    ref.close()
-    c = H.Case(n, order=4, amp=0.1)
-    c.to_device(0)
-    hfx.Context.set_option(_Ctx(c.handles()[0]), knob, value)
-    c.run_steps_lib(2, fused=3)
-    c.sync_host()
-    got = c.array("disu_upts0")
+
+    def state(opts):
+        c = H.Case(n, order=4, amp=0.1)
+        c.to_device(0)
+        for k, v in opts:
+            hfx.Context.set_option(_Ctx(c.handles()[0]), k, v)
+        c.run_steps_lib(2, fused=3)
+        c.sync_host()
+        u = c.array("disu_upts0").copy()
+        grids = hfx.fused_launch_grids(c.handles()[1])
+        c.close()
+        return u, grids
+
+    want, _ = state([])
+    got, grids = state([(knob, value)])
     if exact:
         assert np.array_equal(got, want), knob
     else:
         assert relerr(got, want) < 1e-12, knob
-    c.close()
+    if knob == "persistent_grid_cap":
+        assert [g[1:] for g in grids] == [(value, 64)] * 2, grids
+    if knob == "xcd_order":
+        capped, g1 = state([("persistent_grid_cap", 8)])
+        got, g2 = state([("persistent_grid_cap", 8), (knob, value)])
+        assert [g[1:] for g in g1] == [(8, 64)] * 2 and g2 == g1, (g1, g2)
+        assert np.array_equal(capped, want) and np.array_equal(got, capped), knob
 
 
 class _Ctx:
