@@ -450,6 +450,9 @@ static int run_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int,
       first = false;
     }
     advance_ramp_counters(int_faces, n_int);
+    // the clock and the time averages (src/HiFiLES.cpp:221-245; not for hfx_time_partitioned).  The update kernel reads disu_upts(0)
+    // alone, on the compute stream: the solution exchange the stage left in flight reads the packed flux-point values
+    if (n_stages_total < 0 && end_of_step(&e, 1)) return 1;
   }
   // the exchange started after the last stage belongs to a stage that is not run: the compute stream waits for it so
   // that nothing is in flight when the caller reads or changes the state (a following call starts over with `first`)
@@ -688,6 +691,7 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
       start = false;
     }
     advance_ramp_counters(int_faces, n_int);
+    if (end_of_step(eles, n_ele_blocks)) return 1; /* src/HiFiLES.cpp:221-245 */
   }
   // (nothing in flight when the caller reads or changes the state)
   if (n_steps > 0)

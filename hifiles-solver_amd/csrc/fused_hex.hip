@@ -1148,6 +1148,7 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
       if (e->shock_ready && shock_capture_keep_fpts(e)) return 1;
     }
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
+    if (end_of_step(&e, 1)) return 1; /* src/HiFiLES.cpp:221-245 */
   }
   return 0;
 }

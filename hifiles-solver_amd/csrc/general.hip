@@ -1377,6 +1377,7 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
       if (general_shock_capture(eles, neb)) return 1;
     }
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
+    if (end_of_step(eles, neb)) return 1; /* src/HiFiLES.cpp:221-245 */
   }
   return 0;
 }

@@ -1217,6 +1217,25 @@ int hfx_eles_calc_disu_ppts(hfx_eles *e, double *host)
   return 0;
 }
 
+// eles::calc_time_average_ppts (src/eles.cpp:3820-3846): the same contraction over the planes of disu_average_upts
+int hfx_eles_calc_time_average_ppts(hfx_eles *e, double *host)
+{
+  HFX_CHECK(e && host, "hfx_eles_calc_time_average_ppts: NULL argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  if (e->n_eles == 0) return 0;
+  HFX_CHECK(e->n_ppts > 0, "calc_time_average_ppts: hfx_eles_set_opp_p was not called");
+  HFX_CHECK(e->n_average_fields > 0, "calc_time_average_ppts: no average fields (hfx_eles_set_average_fields)");
+  hfx_ctx *ctx = e->ctx;
+  const size_t n_out = (size_t)e->n_ppts * e->n_eles * e->n_average_fields;
+  if (e->disu_average_ppts.size() != n_out && e->disu_average_ppts.alloc(n_out)) return 1;
+  const Operator *ops[1] = {&e->opp_p};
+  const double *in[1] = {e->disu_average_upts};
+  if (contract_multi_in(ctx, ops, 1, in, e->disu_average_ppts, (long)e->n_eles * e->n_average_fields, 0)) return 1;
+  HFX_HIP(hipMemcpyAsync(host, e->disu_average_ppts, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream));
+  HFX_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
 // ---- over-integration (polynomial de-aliasing of the inviscid flux) ------------------------
 int hfx_eles_set_over_int(hfx_eles *e, int n_cubpts, const double *opp_over_int_cubpts, const double *over_int_filter,
                           const double *JGinv_over_int_cubpts)
@@ -1716,6 +1735,7 @@ int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *face
         if (eles[i]->shock_ready && hfx_eles_shock_capture(eles[i])) return 1; /* src/HiFiLES.cpp:214-216 */
     }
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
+    if (end_of_step(eles, neb)) return 1; /* src/HiFiLES.cpp:221-245 */
   }
   return 0;
 }

@@ -240,6 +240,11 @@ struct hfx_ctx
   std::vector<hfx_comm *> comms; // the live communicators of this context (hfx_ctx_synchronize waits for their streams)
   double CFL = 0.0; // run_input.CFL (hfx_ctx_set_CFL); dt_type 1 / 2 only
   bool have_CFL = false;
+  // the clock of the step loops (hfx_ctx_set_clock): FlowSol.time, i_steps and run_input.spinup_time of src/HiFiLES.cpp:221-243.
+  // have_clock: the loops advance it and update the time averages after every step (hfx::end_of_step)
+  double time = 0.0, spinup_time = 0.0;
+  int i_steps = 0;
+  bool have_clock = false;
   hfx::Phys phys() const
   {
     hfx::Phys P;
@@ -293,6 +298,10 @@ struct hfx_eles
   int n_ppts = 0;
   hfx::Operator opp_p;
   hfx::DevBuf<double> disu_ppts;
+  // time-averaged fields (hfx_eles_set_average_fields): disu_average_upts (n_upts, n_eles, n_average_fields)
+  int n_average_fields = 0;
+  int average_codes[HFX_MAX_AVERAGE_FIELDS] = {};
+  hfx::DevBuf<double> disu_average_upts, disu_average_ppts;
   // over-integration (hfx_eles_set_over_int)
   bool over_int_ready = false;
   int n_cubpts = 0;
@@ -406,6 +415,10 @@ int calc_time_step_blocks(hfx_eles *const *eles, int neb);
 int first_stage_closure_filter(hfx_eles *const *eles, int neb, bool refresh_svv);
 // run_input.ramp_counter++ after a time step for the boundary blocks with a ramping group (src/HiFiLES.cpp:224-225)
 void advance_ramp_counters(hfx_inters *const *faces, int nfb);
+// what the reference's main loop does between the last RK stage and the outputs (src/HiFiLES.cpp:221-245), for a context whose
+// clock is the library's: time += dt, i_steps++, spinup_time at step 1, then the time averages of every block that has average
+// fields (averages.hip).  Nothing for a context without a clock; no launch for a block without average fields
+int end_of_step(hfx_eles *const *eles, int neb);
 // RK stages per time step of adv_type (src/HiFiLES.cpp:143-150)
 inline int n_rk_stages(int adv_type) { return (adv_type == 0) ? 1 : (adv_type <= 2) ? 4 : (adv_type == 3) ? 5 : 14; }
 inline int n_rk_stages(const hfx_params &p) { return n_rk_stages(p.adv_type); }

@@ -369,6 +369,55 @@ extern "C" int hfxh_case_calc_disu_ppts(hfxh_case *c, const double **out, int di
   return 0;
 }
 
+// ---- time-averaged fields ----------------------------------------------------------------------------------------------
+extern "C" int hfxh_case_set_average_fields(hfxh_case *c, int n, const char *const *names)
+{
+  if (!c || n < 0 || (n > 0 && !names)) { g_err = "hfxh_case_set_average_fields: bad argument"; return 1; }
+  std::vector<std::string> v;
+  for (int i = 0; i < n; i++) v.push_back(names[i] ? names[i] : "");
+  if (c->S.run_input.set_average_fields(v, c->S.n_dims, g_err)) return 1;
+  eles *E = the_eles(c);
+  if (E->register_average_fields()) { g_err = E->last_error(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_get_average_fields(hfxh_case *c, int *n, const char *names[HFX_MAX_AVERAGE_FIELDS])
+{
+  const input &in = c->S.run_input;
+  *n = in.n_average_fields;
+  if (names)
+    for (int i = 0; i < in.n_average_fields; i++) names[i] = in.average_fields[i].c_str();
+  return 0;
+}
+
+extern "C" int hfxh_case_get_averages(hfxh_case *c, const double **out, int dims[3])
+{
+  eles *E = the_eles(c);
+  if (c->S.run_input.n_average_fields == 0) { g_err = "hfxh_case_get_averages: the case has no average_fields"; return 1; }
+  if (E->cp_disu_average_upts_gpu_cpu()) { g_err = E->last_error(); return 1; }
+  *out = E->disu_average_upts.get_ptr_cpu();
+  dims[0] = E->n_upts_per_ele; dims[1] = E->n_eles; dims[2] = c->S.run_input.n_average_fields;
+  return 0;
+}
+
+extern "C" int hfxh_case_calc_time_average_ppts(hfxh_case *c, const double **out, int dims[3])
+{
+  eles *E = the_eles(c);
+  if (c->S.run_input.n_average_fields == 0) { g_err = "hfxh_case_calc_time_average_ppts: the case has no average_fields"; return 1; }
+  if (E->calc_time_average_ppts_all()) { g_err = E->last_error(); return 1; }
+  *out = E->disu_average_ppts.get_ptr_cpu();
+  dims[0] = E->n_ppts_per_ele; dims[1] = E->n_eles; dims[2] = c->S.run_input.n_average_fields;
+  return 0;
+}
+
+extern "C" int hfxh_case_get_clock(hfxh_case *c, double *time, int *i_steps, double *spinup_time)
+{
+  if (time) *time = c->S.time;
+  if (i_steps) *i_steps = c->S.i_steps;
+  if (spinup_time) *spinup_time = c->S.run_input.spinup_time;
+  return 0;
+}
+
 
 // ---- tetrahedra / prisms as producers of operators and metrics -------------------------------------------------------
 struct hfxh_simplex

@@ -457,6 +457,7 @@ int eles::mv_all_cpu_gpu(hfx_ctx *ctx)
     fail(hfx_last_error());
     return 1;
   }
+  if (run_input->n_average_fields && register_average_fields()) return 1;
   if (run_input->over_int &&
       hfx_eles_set_over_int(dev, loc_over_int_cubpts.get_dim(1), opp_over_int_cubpts.get_ptr_cpu(), over_int_filter.get_ptr_cpu(),
                             JGinv_over_int_cubpts.get_ptr_cpu()))
@@ -515,6 +516,40 @@ void eles::extrapolate_totalFlux() { HFX_CALL(hfx_eles_extrapolate_totalFlux(dev
 void eles::calculate_divergence() { HFX_CALL(hfx_eles_calculate_divergence(dev)); }
 void eles::calculate_corrected_divergence() { HFX_CALL(hfx_eles_calculate_corrected_divergence(dev)); }
 void eles::AdvanceSolution(int in_step, int adv_type) { HFX_CALL(hfx_eles_AdvanceSolution(dev, in_step, adv_type)); }
+void eles::CalcTimeAverageQuantities(double &time) { HFX_CALL(hfx_eles_CalcTimeAverageQuantities(dev, time, run_input->spinup_time)); }
+
+int eles::register_average_fields()
+{
+  if (!dev) return 0; // (mv_all_cpu_gpu registers them)
+  int codes[HFX_MAX_AVERAGE_FIELDS];
+  for (int i = 0; i < run_input->n_average_fields; i++) codes[i] = run_input->average_code(i);
+  if (hfx_eles_set_average_fields(dev, run_input->n_average_fields, codes)) { fail(hfx_last_error()); return 1; }
+  return 0;
+}
+
+int eles::cp_disu_average_upts_gpu_cpu()
+{
+  if (!dev) { fail("element block is not on the device"); return 1; }
+  disu_average_upts.setup(n_upts_per_ele, n_eles, run_input->n_average_fields);
+  if (hfx_eles_download_average(dev, disu_average_upts.get_ptr_cpu())) { fail(hfx_last_error()); return 1; }
+  return 0;
+}
+
+int eles::calc_time_average_ppts_all()
+{
+  if (!dev) { fail("element block is not on the device"); return 1; }
+  disu_average_ppts.setup(n_ppts_per_ele, n_eles, run_input->n_average_fields);
+  if (hfx_eles_calc_time_average_ppts(dev, disu_average_ppts.get_ptr_cpu())) { fail(hfx_last_error()); return 1; }
+  return 0;
+}
+
+void eles::calc_time_average_ppts(int in_ele, hf_array<double> &out_disu_average_ppts)
+{
+  // (as calc_disu_ppts: the whole block is interpolated once and read per element)
+  if (disu_average_ppts.get_dim(0) != n_ppts_per_ele && calc_time_average_ppts_all()) return;
+  for (int k = 0; k < run_input->n_average_fields; k++)
+    for (int j = 0; j < n_ppts_per_ele; j++) out_disu_average_ppts(j, k) = disu_average_ppts(j, in_ele, k);
+}
 
 double eles::compute_res_upts(int in_norm_type, int in_field)
 {

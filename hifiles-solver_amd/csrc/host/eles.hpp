@@ -52,6 +52,13 @@ public:
   void calculate_corrected_divergence();
   void AdvanceSolution(int in_step, int adv_type);
   double calc_dt_local(int in_ele); // host evaluation on the host copy of disu_upts(0), src/eles.cpp:1267
+  // ---- time-averaged fields (run_input->average_fields; registered by mv_all_cpu_gpu)
+  void CalcTimeAverageQuantities(double &time); // src/eles.cpp:5630: one update on the device, spin-up time from run_input
+  int register_average_fields();                // run_input->average_fields -> the device block (zeroed averages)
+  int cp_disu_average_upts_gpu_cpu();           // -> disu_average_upts (n_upts, n_eles, n_average_fields)
+  int calc_time_average_ppts_all();             // every element at once, on the device -> disu_average_ppts
+  void calc_time_average_ppts(int in_ele, hf_array<double> &out_disu_average_ppts); // src/eles.cpp:3820, the per-element accessor
+  hf_array<double> disu_average_upts, disu_average_ppts;
   double compute_res_upts(int in_norm_type, int in_field);
 
   // ---- getters used by face wiring (src/eles.cpp:4638-4949 return pointers; here: offsets)

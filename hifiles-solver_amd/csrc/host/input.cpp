@@ -1,5 +1,7 @@
 #include "input.hpp"
 
+#include <algorithm>
+#include <cctype>
 #include <cmath>
 
 // Low-storage RK tableaux.  Values: Carpenter & Kennedy, "Fourth-order 2N-storage
@@ -83,6 +85,29 @@ int input::setup_params(std::string &err)
     T_ref = L_ref = rho_ref = uvw_ref = p_ref = mu_ref = time_ref = R_ref = NAN;
   }
   return 0;
+}
+
+static const char *const AVERAGE_NAMES[5] = {"rho_average", "u_average", "v_average", "w_average", "e_average"}; // HFX_AVG_*
+
+int input::set_average_fields(const std::vector<std::string> &names, int n_dims, std::string &err)
+{
+  std::vector<std::string> lower(names);
+  for (std::string &s : lower)
+  {
+    std::transform(s.begin(), s.end(), s.begin(), [](unsigned char c) { return (char)std::tolower(c); }); /* src/input.cpp:130-133 */
+    const char *const *hit = std::find(AVERAGE_NAMES, AVERAGE_NAMES + 5, s);
+    if (hit == AVERAGE_NAMES + 5) { err = "average_fields: unknown field " + s; return 1; }
+    if (hit - AVERAGE_NAMES == HFX_AVG_W && n_dims != 3) { err = "average_fields: w_average in a two-dimensional run"; return 1; }
+  }
+  if ((int)lower.size() > HFX_MAX_AVERAGE_FIELDS) { err = "average_fields: too many fields"; return 1; }
+  average_fields.swap(lower);
+  n_average_fields = (int)average_fields.size();
+  return 0;
+}
+
+int input::average_code(int i) const
+{
+  return (int)(std::find(AVERAGE_NAMES, AVERAGE_NAMES + 5, average_fields[i]) - AVERAGE_NAMES);
 }
 
 void input::fill(hfx_params &p) const

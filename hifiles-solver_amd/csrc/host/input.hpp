@@ -41,6 +41,17 @@ struct input
   double C_s = 0.0, filter_ratio = 1.0, Kappa = 0.41, prandtl_t = 0.9;
   // ---- plotting: points per edge (src/input.cpp:110; the reference's default is 2)
   int p_res = 2;
+  // ---- time-averaged fields (src/input.cpp:115-133): names of rho_average, u_average, v_average, w_average, e_average, lower-cased;
+  // spinup_time: the time of the first step of the run, where the averages begin (src/HiFiLES.cpp:242-243)
+  std::vector<std::string> average_fields;
+  int n_average_fields = 0;
+  double spinup_time = 0.0;
+  // the names -> average_fields (lower-cased as src/input.cpp:130-133 does) and n_average_fields.  A name outside the five is refused
+  // (the reference's CalcTimeAverageQuantities would average an uninitialised value, src/eles.cpp:5632-5674), and so is
+  // w_average when n_dims is 2; a refusal leaves the fields as they were
+  int set_average_fields(const std::vector<std::string> &names, int n_dims, std::string &err);
+  // HFX_AVG_* of average_fields(i)
+  int average_code(int i) const;
   // ---- element parameters
   int upts_type_hexa = 0, vcjh_scheme_hexa = 1;
   double eta_hexa = 0.0;

@@ -425,6 +425,7 @@ int read_restart_ascii(solution *S, const std::string &dir, int in_file_num, int
       }
     }
   S->run_input.time = S->time;
+  S->i_steps = 0; // a restarted reference run counts its steps, and so weighs its averages, from zero again (src/HiFiLES.cpp:99)
   return 0;
 }
 
@@ -588,6 +589,16 @@ static int advance_ramp(solution *FlowSol)
   return 0;
 }
 
+// src/HiFiLES.cpp:223,241-245 behind `time += dt`: the step counter, the spin-up time at the first step, the time averages
+static void count_step_and_average(solution *FlowSol)
+{
+  FlowSol->i_steps++;
+  if (FlowSol->i_steps == 1) FlowSol->run_input.spinup_time = FlowSol->time;
+  if (FlowSol->run_input.n_average_fields)
+    for (int j = 0; j < FlowSol->n_ele_types; j++)
+      if (FlowSol->mesh_eles(j)) FlowSol->mesh_eles(j)->CalcTimeAverageQuantities(FlowSol->time);
+}
+
 int RunSteps(solution *FlowSol, int n_steps)
 {
   const int RKSteps = FlowSol->run_input.n_rk_stages();
@@ -606,6 +617,7 @@ int RunSteps(solution *FlowSol, int n_steps)
     FlowSol->time += FlowSol->run_input.dt;
     FlowSol->run_input.time = FlowSol->time;
     if (advance_ramp(FlowSol)) return 1;
+    count_step_and_average(FlowSol);
   }
   // (deferred execution: the last stage's record is still pending here, on purpose -- what the caller asks for next decides how
   // it runs: the state alone -> the fused stage; the gradient arrays, as the reference's CopyGPUCPU does before its
@@ -716,19 +728,21 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
   if (FlowSol->comm)
   {
     // the whole loop inside the library: phases, RCCL exchanges on its communication stream, calc_time_step with the
-    // all-reduce, ramp counters.  With CFL steps the host follows step by step to keep `time` (the library recomputes dt).
-    const int chunk = (in.dt_type == 0) ? n_steps : 1;
-    for (int done = 0; done < n_steps; done += chunk)
+    // all-reduce, ramp counters, and -- the clock handed over before and read back after -- time, the step counter, the spin-up
+    // time and the time averages (with CFL steps too: the library's clock adds every step's own dt)
+    if (hfx_ctx_set_clock(FlowSol->ctx, FlowSol->time, FlowSol->i_steps) || hfx_ctx_set_spinup_time(FlowSol->ctx, in.spinup_time))
     {
-      if (hfx_run_steps_partitioned(E->device(), fi.data(), (int)fi.size(), fm.data(), (int)fm.size(), FlowSol->comm, chunk))
-      {
-        FlowSol->err = hfx_last_error();
-        return 1;
-      }
-      if (in.dt_type != 0 && hfx_ctx_get_dt(FlowSol->ctx, &in.dt)) { FlowSol->err = hfx_last_error(); return 1; }
-      FlowSol->time += chunk * in.dt;
-      if (in.pressure_ramp) in.ramp_counter += chunk; // the library advanced its boundary blocks' counters
+      FlowSol->err = hfx_last_error();
+      return 1;
     }
+    if (hfx_run_steps_partitioned(E->device(), fi.data(), (int)fi.size(), fm.data(), (int)fm.size(), FlowSol->comm, n_steps))
+    {
+      FlowSol->err = hfx_last_error();
+      return 1;
+    }
+    if (in.dt_type != 0 && hfx_ctx_get_dt(FlowSol->ctx, &in.dt)) { FlowSol->err = hfx_last_error(); return 1; }
+    if (hfx_ctx_get_clock(FlowSol->ctx, &FlowSol->time, &FlowSol->i_steps, &in.spinup_time)) { FlowSol->err = hfx_last_error(); return 1; }
+    if (in.pressure_ramp) in.ramp_counter += n_steps; // the library advanced its boundary blocks' counters
     in.time = FlowSol->time;
     return 0;
   }
@@ -767,6 +781,7 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
     FlowSol->time += in.dt;
     in.time = FlowSol->time;
     if (advance_ramp(FlowSol)) return 1;
+    count_step_and_average(FlowSol);
   }
   // the exchange started after the last stage belongs to a stage that is not run: complete it so that
   // no request is left in flight (a following call starts over with `first`)

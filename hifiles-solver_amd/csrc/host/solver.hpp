@@ -14,6 +14,7 @@ struct solution
 {
   int rank = 0, nproc = 1;
   double time = 0.0;
+  int i_steps = 0; // time steps of this run (src/HiFiLES.cpp:99,223): step 1 sets run_input.spinup_time; a restart read resets it
   int n_ele_types = 5; // 0 tri, 1 quad, 2 tet, 3 pri, 4 hex (src/geometry.cpp:135)
   int n_dims = 0;
   int num_cells_global = 0, ini_iter = 0;

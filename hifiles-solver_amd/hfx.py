@@ -22,6 +22,11 @@ ip = C.POINTER(C.c_int)
  DISUF_UPTS, LU, LE) = range(18)
 
 
+# hfx_average_field: the reference's average_fields names in the order of their codes
+AVG_RHO, AVG_U, AVG_V, AVG_W, AVG_E = range(5)
+AVERAGE_NAMES = ("rho_average", "u_average", "v_average", "w_average", "e_average")
+
+
 class Les(C.Structure):
     _fields_ = [("sgs_model", C.c_int), ("pad", C.c_int), ("C_s", C.c_double), ("filter_ratio", C.c_double),
                 ("Kappa", C.c_double), ("prandtl_t", C.c_double)]
@@ -153,6 +158,19 @@ class Context:
     def synchronize(self):
         check(lib().hfx_ctx_synchronize(self.h))
 
+    def set_clock(self, time, i_steps=0):
+        """hands FlowSol.time and i_steps to the library: its step loops then advance them and update the time averages"""
+        check(lib().hfx_ctx_set_clock(self.h, C.c_double(time), C.c_int(i_steps)))
+
+    def set_spinup_time(self, spinup_time):
+        check(lib().hfx_ctx_set_spinup_time(self.h, C.c_double(spinup_time)))
+
+    def get_clock(self):
+        """(time, i_steps, spinup_time)"""
+        t, n, s = C.c_double(0), C.c_int(0), C.c_double(0)
+        check(lib().hfx_ctx_get_clock(self.h, C.byref(t), C.byref(n), C.byref(s)))
+        return t.value, n.value, s.value
+
     def flush(self):
         """deferred execution: run what has been recorded (no-op otherwise)"""
         check(lib().hfx_ctx_flush(self.h))
@@ -232,6 +250,31 @@ class Eles:
     def calc_disu_ppts(self):
         out = np.zeros((self.n_ppts, self.n_eles, self.n_fields), dtype=np.float64, order="F")
         check(lib().hfx_eles_calc_disu_ppts(self.h, out.ctypes.data_as(dp)))
+        return out
+
+    def set_average_fields(self, fields):
+        """fields: AVG_* codes or the reference's names (rho_average ...), in the order of the input file; [] drops them"""
+        codes = [AVERAGE_NAMES.index(f.lower()) if isinstance(f, str) else int(f) for f in fields]
+        a = (C.c_int * max(1, len(codes)))(*codes)
+        check(lib().hfx_eles_set_average_fields(self.h, C.c_int(len(codes)), a))
+        self.n_average_fields = len(codes)
+
+    def upload_average(self, a):
+        a = _f(a)
+        assert a.shape == (self.n_upts, self.n_eles, getattr(self, "n_average_fields", 0)), a.shape
+        check(lib().hfx_eles_upload_average(self.h, a.ctypes.data_as(dp)))
+
+    def download_average(self):
+        a = np.zeros((self.n_upts, self.n_eles, getattr(self, "n_average_fields", 0)), dtype=np.float64, order="F")
+        check(lib().hfx_eles_download_average(self.h, a.ctypes.data_as(dp)))
+        return a
+
+    def CalcTimeAverageQuantities(self, time, spinup_time):
+        self._call("hfx_eles_CalcTimeAverageQuantities", C.c_double(time), C.c_double(spinup_time))
+
+    def calc_time_average_ppts(self):
+        out = np.zeros((self.n_ppts, self.n_eles, self.n_average_fields), dtype=np.float64, order="F")
+        check(lib().hfx_eles_calc_time_average_ppts(self.h, out.ctypes.data_as(dp)))
         return out
 
     def extrapolate_solution(self): self._call("hfx_eles_extrapolate_solution")

@@ -337,6 +337,39 @@ class Case:
     def sync_host(self):
         check(lib().hfxh_case_sync_host(self.h))
 
+    def set_average_fields(self, names):
+        """run_input.average_fields: names out of rho_average, u_average, v_average, w_average, e_average (any letter case)"""
+        a = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        check(lib().hfxh_case_set_average_fields(self.h, C.c_int(len(names)), a))
+
+    def average_fields(self):
+        """the stored (lower-cased) names; their number is run_input.n_average_fields"""
+        n = C.c_int(0)
+        names = (C.c_char_p * 16)()
+        check(lib().hfxh_case_get_average_fields(self.h, C.byref(n), names))
+        return [names[i].decode() for i in range(n.value)]
+
+    def _average_array(self, fn):
+        ptr = dp()
+        dims = (C.c_int * 3)()
+        check(fn(self.h, C.byref(ptr), dims))
+        n = dims[0] * dims[1] * dims[2]
+        return np.ctypeslib.as_array(ptr, shape=(n,)).reshape(tuple(dims), order="F").copy()
+
+    def averages(self):
+        """disu_average_upts from the device: (n_upts, n_eles, n_average_fields)"""
+        return self._average_array(lib().hfxh_case_get_averages)
+
+    def calc_time_average_ppts(self):
+        """eles::calc_time_average_ppts for every element: (n_ppts, n_eles, n_average_fields)"""
+        return self._average_array(lib().hfxh_case_calc_time_average_ppts)
+
+    def clock(self):
+        """(time, i_steps, spinup_time) of the mirrored main loop"""
+        t, n, s = C.c_double(0), C.c_int(0), C.c_double(0)
+        check(lib().hfxh_case_get_clock(self.h, C.byref(t), C.byref(n), C.byref(s)))
+        return t.value, n.value, s.value
+
     def close(self):
         if self.h:
             lib().hfxh_case_destroy(self.h)

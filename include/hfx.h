@@ -177,6 +177,20 @@ int hfx_ctx_flush(hfx_ctx *ctx); /* run what has been recorded (asynchronously, 
 int hfx_ctx_deferred_stats(hfx_ctx *ctx, long *n_fused, long *n_replayed, const char **why_last_replay);
 /* run_input.dt as the last calc_time_step left it (dt_type 1), or as set (dt_type 0) */
 int hfx_ctx_get_dt(hfx_ctx *ctx, double *dt);
+/* ---- the clock of the step loops (src/HiFiLES.cpp:221-245) ----------------------------------------------------------
+ * The caller keeps FlowSol.time and i_steps; hfx_ctx_set_clock hands both to the library.  From then on the four loops
+ * hfx_run_steps, hfx_run_steps_blocks, hfx_run_steps_partitioned and hfx_run_steps_partitioned_blocks do after EVERY time step
+ * what the reference's main loop does there: time += run_input.dt; i_steps++; if (i_steps == 1) spinup_time = time; and then
+ * eles::CalcTimeAverageQuantities of every block that registered average fields (hfx_eles_set_average_fields) -- one more
+ * kernel per such block and step on the compute stream, nothing at all for a context without average fields.  A context
+ * whose clock was never set is the caller's to time: its loops touch neither the clock nor the averages, and the caller calls
+ * hfx_eles_CalcTimeAverageQuantities itself where the reference does.  spinup_time is kept across calls (0 in a new
+ * context); setting i_steps = 0 makes the next step the one that sets it, which restarts the averages' weights as a restarted
+ * reference run does.  The hfx_time_* entry points never touch the clock. */
+int hfx_ctx_set_clock(hfx_ctx *ctx, double time, int i_steps);
+int hfx_ctx_get_clock(hfx_ctx *ctx, double *time, int *i_steps, double *spinup_time); /* any pointer may be NULL */
+/* run_input.spinup_time of a run that is continued with i_steps > 0 in another context than the one that made its first step */
+int hfx_ctx_set_spinup_time(hfx_ctx *ctx, double spinup_time);
 /* runs what has been recorded and waits for the context's stream and for the communication stream of every hfx_comm of the
  * context that has a solution message in flight */
 int hfx_ctx_synchronize(hfx_ctx *ctx);
@@ -302,6 +316,40 @@ int hfx_eles_set_opp_p(hfx_eles *e, int n_ppts, const double *opp_p);
  * disu_ppts (n_ppts,n_eles,n_fields) = opp_p . disu_upts(0), written to the HOST array the plot writer reads
  * (output::write_vtu loops the elements, src/output.cpp) */
 int hfx_eles_calc_disu_ppts(hfx_eles *e, double *disu_ppts_host);
+
+/* ---- time-averaged fields (run_input.average_fields, src/input.cpp:115-133) -------------------------------------------
+ * The running time averages the reference's main loop updates after every time step (run_output.CalcTimeAverageQuantities,
+ * src/HiFiLES.cpp:240-245) and every output writer takes to the plot points. */
+enum hfx_average_field
+{
+  HFX_AVG_RHO = 0, /* "rho_average": density */
+  HFX_AVG_U = 1,   /* "u_average": field 1 / density */
+  HFX_AVG_V = 2,   /* "v_average": field 2 / density */
+  HFX_AVG_W = 3,   /* "w_average": field 3 / density (three-dimensional blocks only) */
+  HFX_AVG_E = 4    /* "e_average": field n_dims + 1 / density -- field 3 in 2-D, 4 in 3-D (src/eles.cpp:5664-5674) */
+};
+#define HFX_MAX_AVERAGE_FIELDS 16
+/* Registers run_input.average_fields of one block: codes[n] in the order of the input file, names may repeat.  Allocates
+ * disu_average_upts (n_upts, n_eles, n) on the device, zeroed as the reference does (src/eles.cpp:124-127).  n = 0 drops the
+ * array; registering again replaces it (zeroed).  HFX_AVG_W on a two-dimensional block is refused. */
+int hfx_eles_set_average_fields(hfx_eles *e, int n, const int *codes);
+/* host <-> device copies of disu_average_upts (n_upts, n_eles, n_average_fields): what a run that is to be continued saves
+ * and restores (together with the clock) */
+int hfx_eles_upload_average(hfx_eles *e, const double *host);
+int hfx_eles_download_average(hfx_eles *e, double *host);
+/* eles::CalcTimeAverageQuantities (src/eles.cpp:5630-5702): ONE update of every registered field from disu_upts(0),
+ *   average = a * average + b * current,   a = 0, b = 1 when time == spinup_time,
+ *   else a = (time - spinup_time - dt) / (time - spinup_time), b = dt / (time - spinup_time)
+ * with dt = run_input.dt (dt_type 0 / 1: a and b are evaluated once, on the host) or dt_local(ele) (dt_type 2: per element,
+ * in the kernel, from HFX_DT_LOCAL, which must exist).  One streaming kernel; with deferred execution a recorded stage runs
+ * first.  The reference's abort on a NaN average (src/eles.cpp:5698) is NOT built: a NaN average means a NaN state, and that
+ * is what hfx_eles_check_nan already reports.  The step loops call this themselves once the clock is theirs
+ * (hfx_ctx_set_clock). */
+int hfx_eles_CalcTimeAverageQuantities(hfx_eles *e, double time, double spinup_time);
+/* eles::calc_time_average_ppts (src/eles.cpp:3820-3846) for every element at once: disu_average_ppts
+ * (n_ppts, n_eles, n_average_fields) = opp_p . disu_average_upts, with the operator of hfx_eles_set_opp_p and the
+ * contraction of hfx_eles_calc_disu_ppts, written to the HOST array the plot writer reads */
+int hfx_eles_calc_time_average_ppts(hfx_eles *e, double *disu_average_ppts_host);
 
 /* ---- CFL time stepping (calc_time_step, src/solver.cpp:484-549) ---------- */
 int hfx_eles_set_h_ref(hfx_eles *e, const double *h_ref); /* eles::h_ref (n_eles), src/eles.cpp:3985 */

@@ -194,6 +194,22 @@ int hfxh_case_calc_time_step(hfxh_case *c, double *dt);
 int hfxh_case_calc_disu_ppts(hfxh_case *c, const double **out, int dims[3]);
 int hfxh_case_sync_host(hfxh_case *c);        /* cp_*_gpu_cpu of state, divergence, gradient */
 
+/* ---- time-averaged fields (run_input.average_fields, src/input.cpp:115-133) ---------------------------------------------
+ * names[n] out of rho_average, u_average, v_average, w_average, e_average in any letter case (stored lower-cased, as the
+ * reference does); a name outside the five, and w_average in a two-dimensional case, are refused and leave the case as it
+ * was.  Host only; a case that is on the device also registers them there (zeroed averages), hfxh_case_to_device does so
+ * otherwise.  hfxh_case_run and hfxh_case_run_partitioned then update the averages after every time step
+ * (src/HiFiLES.cpp:240-245). */
+int hfxh_case_set_average_fields(hfxh_case *c, int n, const char *const *names);
+/* run_input.n_average_fields and the stored names (names may be NULL) */
+int hfxh_case_get_average_fields(hfxh_case *c, int *n, const char *names[HFX_MAX_AVERAGE_FIELDS]);
+/* disu_average_upts downloaded: out (n_upts, n_eles, n_average_fields) */
+int hfxh_case_get_averages(hfxh_case *c, const double **out, int dims[3]);
+/* eles::calc_time_average_ppts for every element: out (n_ppts, n_eles, n_average_fields) */
+int hfxh_case_calc_time_average_ppts(hfxh_case *c, const double **out, int dims[3]);
+/* FlowSol.time, i_steps (time steps of this run; a restart read resets it) and run_input.spinup_time; any pointer may be NULL */
+int hfxh_case_get_clock(hfxh_case *c, double *time, int *i_steps, double *spinup_time);
+
 #ifdef __cplusplus
 }
 #endif
