@@ -543,19 +543,8 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
       // the consistent switch of src/inters.cpp:568-581 on the LEFT normal (exact zero tests);
       // only the sign decision is stored
       const double n[3] = {norm[il], norm[il + plane_f], nd == 3 ? norm[il + 2 * plane_f] : 0.0};
-      double bt = 1.0;
-      if (n[0] < 0.)
-        bt = -bt;
-      else if (n[0] == 0.)
-      {
-        if ((n[0] + n[1]) < 0.)
-          bt = -bt;
-        else if ((n[0] + n[1]) == 0)
-        {
-          if (nd == 3 && (n[0] + n[2]) < 0.) bt = -bt;
-        }
-      }
-      const unsigned char flip = (bt < 0) ? 2 : 0;
+      const double n2[2] = {n[0], n[1]};
+      const unsigned char flip = ((nd == 3 ? ldg_switch<3>(1.0, n) : ldg_switch<2>(1.0, n2)) < 0) ? 2 : 0;
       meta[il] = flip;
       meta[ir] = flip | 1;
     }
@@ -785,24 +774,11 @@ static void stage_args(Args &a, const hfx_eles *e, int in_step, bool write_div)
 }
 
 // the pairs of one interior-face block for a pairwise kernel; false: none
-template <class Args>
-static bool face_pairs(Args &a, const hfx_inters *f)
+static bool face_pairs(FacePairArgs &a, const hfx_inters *f)
 {
   a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
   a.L = f->L; a.R = f->R;
   return a.npairs > 0;
-}
-
-// f(RS) with the Riemann solver of a pairwise common-flux kernel (face_flux_kernel, face_flux2_kernel) as a constant
-template <class F>
-static void with_riemann_solver(int riemann, F f)
-{
-  if (riemann == 0)
-    f(std::integral_constant<int, 0>{});
-  else if (riemann == 2)
-    f(std::integral_constant<int, 2>{});
-  else
-    f(std::integral_constant<int, 3>{});
 }
 
 // Over-integration folded into the divergence (src/solver.cpp:82-91): the sum-factorised kernel hands the loader-wave flux kernel
@@ -840,20 +816,22 @@ struct SplitStageT final : SplitStage
   const int flux_per_cu = e->ctx->opt.flux_grid_per_cu > 0 ? e->ctx->opt.flux_grid_per_cu : per_cu;
   Split2Args e2{};      // variant 3
   SplitEleArgs ea{};    // variant 2
-  SplitFaceArgs fa{};   // face_delta_kernel, face_flux_kernel: all but the block's pairs (face_pairs)
-  Split2FaceArgs fa2{}; // face_flux2_kernel: likewise
+  FacePairArgs fa{};    // the pairwise kernels: the block's arrays on both sides, all but a face block's pairs (face_pairs)
   SplitStageT(hfx_eles *e_, hfx_inters *const *faces_, int nfb_, const SplitPlan &pl_) : SplitStage(e_, faces_, nfb_, pl_) {}
 
   int init(int in_step, bool write_div) override
   {
     HFX_CHECK(V3 || pl.variant == 2, "split variant 3 does not fit %d-D elements with %d points per direction: run variant 2", ND, N);
     const long plane_f = (long)e->n_fpts * e->n_eles;
-    fa.meta = F->meta; fa.plane_f = plane_f;
-    fa.disu = e->arr[HFX_DISU_FPTS]; fa.grad = e->arr[HFX_GRAD_DISU_FPTS]; fa.fnorm = e->norm_fpts; fa.tdA = e->tdA_fpts;
-    fa.delta = e->arr[HFX_DELTA_DISU_FPTS]; fa.tconf = e->arr[HFX_NORM_TCONF_FPTS];
-    fa.sgsf = (e->les_ready && pl.variant == 2) ? e->arr[HFX_SGSF_FPTS] : nullptr;
-    fa.jac_fpts = e->Jacobian_fpts; fa.detjac_fpts = e->detjac_fpts;
-    fa.P = P;
+    FaceSide s{};
+    s.plane = plane_f;
+    s.disu = e->arr[HFX_DISU_FPTS]; s.grad = e->arr[HFX_GRAD_DISU_FPTS]; s.tdA = e->tdA_fpts;
+    s.delta = e->arr[HFX_DELTA_DISU_FPTS]; s.tconf = e->arr[HFX_NORM_TCONF_FPTS];
+    // (variant 2: the SGS flux at the flux points arrives in reference space)
+    s.sgsf = (e->les_ready && pl.variant == 2) ? e->arr[HFX_SGSF_FPTS] : nullptr;
+    s.jac = e->Jacobian_fpts; s.detjac = e->detjac_fpts;
+    fa.meta = F->meta; fa.norm = e->norm_fpts;
+    fa.l = fa.r = s;
     if (pl.variant == 2)
     {
       stage_args(ea, e, in_step, write_div);
@@ -889,8 +867,7 @@ struct SplitStageT final : SplitStage
     e2.nbr = pl.gather ? F->nbr.get() : nullptr;
     e2.disu = e->arr[HFX_DISU_FPTS];
     e2.aff_rec = pl.affine ? F->aff_rec.get() : nullptr;
-    fa2.meta = F->meta; fa2.plane_f = plane_f;
-    fa2.disu = fa.disu; fa2.fn = F->fn_fpts; fa2.fnorm = fa.fnorm; fa2.tdA = fa.tdA; fa2.tconf = fa.tconf; fa2.P = P;
+    fa.l.fn = fa.r.fn = F->fn_fpts;
     return 0;
   }
 
@@ -907,7 +884,7 @@ struct SplitStageT final : SplitStage
       }
       if (!pl.face_delta) continue; // (the flux kernel reads the partner's flux-point solution itself)
       if (!face_pairs(fa, faces[b])) continue;
-      hipLaunchKernelGGL((face_delta_kernel<ND>), dim3((unsigned)((fa.npairs + 255) / 256)), dim3(256), 0, st, fa);
+      hipLaunchKernelGGL((face_delta_kernel<ND>), dim3((unsigned)((fa.npairs + 255) / 256)), dim3(256), 0, st, fa, P);
     }
     HFX_HIP(hipGetLastError());
     return 0;
@@ -1015,12 +992,9 @@ struct SplitStageT final : SplitStage
       if (faces[b]->is_bdy || !face_pairs(fa, faces[b])) continue;
       const dim3 nb((unsigned)((fa.npairs + 255) / 256));
       if (pl.variant == 3)
-      {
-        face_pairs(fa2, faces[b]);
-        with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL((face_flux2_kernel<ND, decltype(RS)::value>), nb, dim3(256), 0, st, fa2); });
-      }
+        with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL((face_flux2_kernel<ND, decltype(RS)::value>), nb, dim3(256), 0, st, FaceBlockArgs(fa), P); });
       else
-        with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL((face_flux_kernel<ND, decltype(RS)::value>), nb, dim3(256), 0, st, fa); });
+        with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL((face_flux_kernel<ND, decltype(RS)::value>), nb, dim3(256), 0, st, fa, P); });
     }
     if (beside && side_stream_wait(e->ctx)) return 1;
     HFX_HIP(hipGetLastError());

@@ -7,7 +7,7 @@
 // Here the stage is cut at the two places where data must cross elements, exactly like the split stage of the
 // tensor-product classes (fused_hex.hip, fused = 3), and is FOUR launches per element block and stage:
 //
-//   gface_delta_kernel   thread per interior flux-point pair: LDG common solution -> delta_disu_fpts (both sides, which
+//   face_delta_kernel    thread per interior flux-point pair: LDG common solution -> delta_disu_fpts (both sides, which
 //                        may belong to different element blocks: prism | tetrahedron faces)
 //   general_flux_kernel  workgroup per batch of 16 elements: corrected gradient at the solution points
 //                        (opp_4, opp_5), its extrapolation to the flux points (opp_6), both point physics blocks, the
@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "general.hpp"
+#include "face_kernels.hpp" // the pairwise kernels (face_delta_kernel<3>, gface_flux_multi_kernel are instantiated here)
 
 namespace hfx
 {
@@ -246,7 +247,7 @@ __global__ __launch_bounds__(64 * W, 2) void general_flux_kernel(const GenArgs a
 #pragma unroll
         for (int i = 0; i < MAXQ_D; i++)
         {
-          const double beta = (w[i] & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
+          const double beta = ldg_beta(w[i], a.P);
 #pragma unroll
           for (int f = 0; f < NF; f++)
           {
@@ -847,124 +848,8 @@ __global__ __launch_bounds__(64 * W) void general_update_kernel(const GenArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// pairwise face kernels; the two sides of a block may belong to different element blocks
-// ---------------------------------------------------------------------------------------------------------------
-struct GFaceArgs
-{
-  long npairs;
-  const int *L, *R;
-  const unsigned char *meta_l; // bit1 of the LEFT point: beta sign flipped (the switch of src/inters.cpp:568-581,620-633)
-  long plane_l, plane_r;
-  const double *disu_l, *disu_r, *fn_l, *fn_r, *norm_l, *tdA_l, *tdA_r;
-  double *delta_l, *delta_r, *tconf_l, *tconf_r;
-  Phys P;
-};
-
-__global__ __launch_bounds__(256) void gface_delta_kernel(const GFaceArgs a)
-{
-  constexpr int NF = 5;
-  const long q = (long)blockIdx.x * 256 + threadIdx.x;
-  if (q >= a.npairs) return;
-  const long il = a.L[q], ir = a.R[q];
-  const double beta = (a.meta_l[il] & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
-  // every load before the first store (a load behind a store to memory that may overlap it waits for the store)
-  double ul[NF], ur[NF];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu_l[il + k * a.plane_l];
-    ur[k] = a.disu_r[ir + k * a.plane_r];
-  }
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    const double uc = 0.5 * (ul[k] + ur[k]) - beta * (ul[k] - ur[k]); // src/inters.cpp:637
-    a.delta_l[il + k * a.plane_l] = uc - ul[k];
-    a.delta_r[ir + k * a.plane_r] = uc - ur[k];
-  }
-}
-
-// Riemann + LDG common flux of the interior pairs from u and Fn of both sides -> norm_tconf of both sides.
-// ALL interior-face blocks of a stage in ONE launch.  A mixed mesh has one block per (left class, right
-// class, face type) -- the channel four --, each a few tens of microseconds of work: launched one after the other every one
-// pays its own ramp-up and tail (4 x 45 us for 208 MB, i.e. 1.2 TB/s).  Workgroups are dealt to the blocks in whole numbers
-// (wg_start), so the block of a workgroup is uniform and its arguments come through scalar loads.
-constexpr int GFACE_MAX_BLOCKS = 8;
-struct GFaceMulti
-{
-  int nb;
-  unsigned wg_start[GFACE_MAX_BLOCKS + 1];
-  GFaceArgs blk[GFACE_MAX_BLOCKS];
-};
-
-template <int RS>
-__global__ __launch_bounds__(256) void gface_flux_multi_kernel(const GFaceMulti m)
-{
-  constexpr int NF = 5, ND = 3;
-  int b = 0;
-  while (b + 1 < m.nb && blockIdx.x >= m.wg_start[b + 1]) b++;
-  const GFaceArgs &a = m.blk[b];
-  const long q = (long)(blockIdx.x - m.wg_start[b]) * 256 + threadIdx.x;
-  if (q >= a.npairs) return;
-  const long il = a.L[q], ir = a.R[q];
-  double ul[NF], ur[NF], n[ND], fn[NF];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu_l[il + k * a.plane_l];
-    ur[k] = a.disu_r[ir + k * a.plane_r];
-  }
-#pragma unroll
-  for (int mm = 0; mm < ND; mm++) n[mm] = a.norm_l[il + mm * a.plane_l];
-  const double tl = a.tdA_l[il], tr = a.tdA_r[ir];
-  double fl[NF], fr[NF];
-  const unsigned char mt = a.meta_l[il];
-  const bool viscous = a.P.viscous;
-  if (viscous)
-  {
-#pragma unroll
-    for (int k = 0; k < NF; k++)
-    {
-      fl[k] = a.fn_l[il + k * a.plane_l];
-      fr[k] = a.fn_r[ir + k * a.plane_r];
-    }
-  }
-  riemann_flux_t<ND, RS, true>(a.P, ul, ur, n, fn);
-  const double beta = (mt & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    double fv = 0.0;
-    if (viscous)
-    {
-      fv = (0.5 + beta) * fl[k] - (0.5 - beta) * fr[k];
-      fv -= a.P.ldg_tau * (ur[k] - ul[k]);
-    }
-    a.tconf_l[il + k * a.plane_l] = viscous ? fn[k] * tl + fv * tl : fn[k] * tl;
-    a.tconf_r[ir + k * a.plane_r] = viscous ? -fn[k] * tr + -fv * tr : -fn[k] * tr;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-// the consistent switch of src/inters.cpp:568-581 on the LEFT normal (exact zero tests), as physics.hpp's ldg_switch
-static double ldg_switch_host(double beta, const double (&n)[3])
-{
-  if (n[0] < 0.0)
-    beta = -beta;
-  else if (n[0] == 0.0)
-  {
-    if ((n[0] + n[1]) < 0.0)
-      beta = -beta;
-    else if ((n[0] + n[1]) == 0.0)
-    {
-      if ((n[0] + n[2]) < 0.0) beta = -beta;
-    }
-  }
-  return beta;
-}
-
 static int padded_operator(DevBuf<double> &dst, const Operator &op, int M, int K)
 {
   HFX_CHECK(op.present(), "general fused stage: an operator is missing");
@@ -1066,7 +951,7 @@ static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_ele
         const int il = f->hL[q];
         owned[il] = 1;
         const double n[3] = {norm[il], norm[il + plane_f], norm[il + 2 * plane_f]};
-        if (ldg_switch_host(1.0, n) < 0) meta[il] |= 2;
+        if (ldg_switch<3>(1.0, n) < 0) meta[il] |= 2;
       }
     if (f->right == e)
       for (long q = 0; q < np; q++) owned[f->hR[q]] = 1;
@@ -1103,7 +988,7 @@ static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_ele
         else
         {
           const double n[3] = {nl[il], nl[il + plane_l], nl[il + 2 * plane_l]};
-          flip = ldg_switch_host(1.0, n) < 0 ? 2 : 0;
+          flip = ldg_switch<3>(1.0, n) < 0 ? 2 : 0;
         }
         if (f->left == e) nbr[il] = (ir << 4) | (br << 2) | flip;
         if (f->right == e) nbr[ir] = (il << 4) | (bl << 2) | flip | 1;
@@ -1181,20 +1066,20 @@ static GenArgs gen_args(hfx_eles *e, const GeneralPlan &pl, int in_step)
   return a;
 }
 
-static GFaceArgs gface_args(hfx_inters *f)
+// the pairs of an interior-face block; its two sides may belong to different element blocks
+static FacePairArgs gface_args(hfx_inters *f)
 {
-  hfx_eles *l = f->left, *r = f->right;
-  GeneralData *gl = l->general.get(), *gr = r->general.get();
-  GFaceArgs a{};
+  auto side = [](hfx_eles *x) {
+    FaceSide s{};
+    s.plane = (long)x->n_fpts * x->n_eles;
+    s.disu = x->arr[HFX_DISU_FPTS]; s.fn = x->general->fn_fpts; s.tdA = x->tdA_fpts;
+    s.delta = x->arr[HFX_DELTA_DISU_FPTS]; s.tconf = x->arr[HFX_NORM_TCONF_FPTS];
+    return s;
+  };
+  FacePairArgs a{};
   a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
-  a.L = f->L; a.R = f->R; a.meta_l = gl->meta;
-  a.plane_l = (long)l->n_fpts * l->n_eles; a.plane_r = (long)r->n_fpts * r->n_eles;
-  a.disu_l = l->arr[HFX_DISU_FPTS]; a.disu_r = r->arr[HFX_DISU_FPTS];
-  a.fn_l = gl->fn_fpts; a.fn_r = gr->fn_fpts;
-  a.norm_l = l->norm_fpts; a.tdA_l = l->tdA_fpts; a.tdA_r = r->tdA_fpts;
-  a.delta_l = l->arr[HFX_DELTA_DISU_FPTS]; a.delta_r = r->arr[HFX_DELTA_DISU_FPTS];
-  a.tconf_l = l->arr[HFX_NORM_TCONF_FPTS]; a.tconf_r = r->arr[HFX_NORM_TCONF_FPTS];
-  a.P = l->ctx->phys();
+  a.L = f->L; a.R = f->R; a.meta = f->left->general->meta; a.norm = f->left->norm_fpts;
+  a.l = side(f->left); a.r = side(f->right);
   return a;
 }
 
@@ -1250,9 +1135,9 @@ int GeneralStage::interior_ldg() const
     if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], 0, 1)) return 1; // ghost state -> inviscid common flux, LDG common solution
     if (faces[b]->is_bdy || faces[b]->is_mpi) continue;
     if (gathers(faces[b]->left) && gathers(faces[b]->right)) continue; // both sides' flux kernels form these corrections themselves
-    const GFaceArgs a = gface_args(faces[b]);
+    const FacePairArgs a = gface_args(faces[b]);
     if (a.npairs == 0) continue;
-    hipLaunchKernelGGL(gface_delta_kernel, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, ctx->stream, a);
+    hipLaunchKernelGGL(face_delta_kernel<3>, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, ctx->stream, a, ctx->phys());
   }
   HFX_HIP(hipGetLastError());
   return 0;
@@ -1283,17 +1168,17 @@ int GeneralStage::common_fluxes() const
   if (beside && side_stream_join(ctx)) return 1;
   // all interior-face blocks in one launch (groups of GFACE_MAX_BLOCKS)
   GFaceMulti m{};
-  const auto kernel = P.riemann == 0 ? gface_flux_multi_kernel<0> : P.riemann == 2 ? gface_flux_multi_kernel<2> : gface_flux_multi_kernel<3>;
   auto flush = [&]() {
-    if (m.nb > 0) hipLaunchKernelGGL(kernel, dim3(m.wg_start[m.nb]), dim3(256), 0, ctx->stream, m);
+    if (m.nb > 0)
+      with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL(gface_flux_multi_kernel<decltype(RS)::value>, dim3(m.wg_start[m.nb]), dim3(256), 0, ctx->stream, m); });
     m.nb = 0;
   };
   for (int b = 0; b < nfb; b++)
   {
     if (faces[b]->is_bdy || faces[b]->is_mpi) continue;
-    const GFaceArgs a = gface_args(faces[b]);
+    const FacePairArgs a = gface_args(faces[b]);
     if (a.npairs == 0) continue;
-    m.blk[m.nb] = a;
+    m.blk[m.nb] = {a, P};
     m.wg_start[m.nb + 1] = m.wg_start[m.nb] + (unsigned)((a.npairs + 255) / 256);
     if (++m.nb == GFACE_MAX_BLOCKS) flush();
   }

@@ -93,7 +93,7 @@ struct GeneralStage
   std::vector<GeneralPlan> plans; // per element block, as
   std::vector<GenArgs> args;
   GeneralStage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step);
-  // viscous: boundary ghost states (-> inviscid common flux, LDG common solution); gface_delta_kernel unless BOTH sides' plans `gather`
+  // viscous: boundary ghost states (-> inviscid common flux, LDG common solution); face_delta_kernel unless BOTH sides' plans `gather`
   int interior_ldg() const;
   int flux_kernels() const; // behind the over-integration contraction where the block registered it
   // boundary viscous fluxes (option bdy_beside: on the side stream, beside the pairwise launch); all interior-face blocks in one launch

@@ -1601,22 +1601,22 @@ int hfx_stage_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, 
   }
 }
 
-static FaceArgs face_args(hfx_inters *f)
+// the pairs of an interior-face block for the per-method kernels (which apply ldg_switch themselves: no meta bytes)
+static FacePairArgs face_args(hfx_inters *f)
 {
-  FaceArgs a;
-  hfx_eles *l = f->left, *r = f->right;
+  const bool les = f->left->les_ready && f->right->les_ready;
+  auto side = [&](hfx_eles *x) {
+    FaceSide s{};
+    s.plane = (long)x->n_fpts * x->n_eles;
+    s.disu = x->arr[HFX_DISU_FPTS]; s.grad = x->arr[HFX_GRAD_DISU_FPTS]; s.tdA = x->tdA_fpts;
+    s.sgsf = les ? x->arr[HFX_SGSF_FPTS] : nullptr; // (physical: no jac / detjac)
+    s.delta = x->arr[HFX_DELTA_DISU_FPTS]; s.tconf = x->arr[HFX_NORM_TCONF_FPTS];
+    return s;
+  };
+  FacePairArgs a{};
   a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
-  a.L = f->L; a.R = f->R;
-  a.plane_l = (long)l->n_fpts * l->n_eles; a.plane_r = (long)r->n_fpts * r->n_eles;
-  a.disu_l = l->arr[HFX_DISU_FPTS]; a.disu_r = r->arr[HFX_DISU_FPTS];
-  a.norm_l = l->norm_fpts;
-  a.tdA_l = l->tdA_fpts; a.tdA_r = r->tdA_fpts;
-  a.tconf_l = l->arr[HFX_NORM_TCONF_FPTS]; a.tconf_r = r->arr[HFX_NORM_TCONF_FPTS];
-  a.delta_l = l->arr[HFX_DELTA_DISU_FPTS]; a.delta_r = r->arr[HFX_DELTA_DISU_FPTS];
-  a.grad_l = l->arr[HFX_GRAD_DISU_FPTS]; a.grad_r = r->arr[HFX_GRAD_DISU_FPTS];
-  const bool les = l->les_ready && r->les_ready;
-  a.sgsf_l = les ? l->arr[HFX_SGSF_FPTS] : nullptr;
-  a.sgsf_r = les ? r->arr[HFX_SGSF_FPTS] : nullptr;
+  a.L = f->L; a.R = f->R; a.norm = f->left->norm_fpts;
+  a.l = side(f->left); a.r = side(f->right);
   return a;
 }
 
@@ -1627,7 +1627,7 @@ int hfx_int_inters_calculate_common_invFlux(hfx_inters *f)
   HFX_CHECK(f->ctx->have_params, "parameters not set");
   HFX_DEFER(f->ctx, DM_INT_COMMON_INVFLUX, nullptr, f, nullptr, 0, 0);
   for (hfx_eles *x : {f->left, f->right}) x->stale &= ~((1u << HFX_NORM_TCONF_FPTS) | (1u << HFX_DELTA_DISU_FPTS));
-  const FaceArgs a = face_args(f);
+  const FacePairArgs a = face_args(f);
   const Phys P = f->ctx->phys();
   with_dims(f->left->n_dims, [&](auto ND) { launch_points(common_invflux_kernel<ND()>, a.npairs, f->ctx->stream, a, P); });
   HFX_HIP(hipGetLastError());
@@ -1640,7 +1640,7 @@ int hfx_int_inters_calculate_common_viscFlux(hfx_inters *f)
   if (f->n_inters == 0) return 0;
   HFX_CHECK(f->ctx->have_params, "parameters not set");
   HFX_DEFER(f->ctx, DM_INT_COMMON_VISCFLUX, nullptr, f, nullptr, 0, 0);
-  const FaceArgs a = face_args(f);
+  const FacePairArgs a = face_args(f);
   const Phys P = f->ctx->phys();
   with_dims(f->left->n_dims, [&](auto ND) { launch_points(common_viscflux_kernel<ND()>, a.npairs, f->ctx->stream, a, P); });
   HFX_HIP(hipGetLastError());
@@ -1813,7 +1813,7 @@ int hfx_time_general_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *
   HFX_CHECK(eles && neb > 0 && ms && names && reps > 0, "hfx_time_general_kernels: bad argument");
   HFX_IMMEDIATE(eles[0]->ctx, 0);
   HFX_CHECK(eles[0]->ctx->have_params, "parameters not set");
-  snprintf(names, 256, "gface_delta_kernel,general_flux_kernel,gface_flux_multi_kernel,general_update_kernel");
+  snprintf(names, 256, "face_delta_kernel,general_flux_kernel,gface_flux_multi_kernel,general_update_kernel");
   return general_time_kernels(eles, neb, faces, nfb, reps, ms);
 }
 

@@ -9,7 +9,7 @@
 #pragma once
 #include "../../include/hfx.h"
 #include "hfx_internal.hpp"
-#include "physics.hpp"
+#include "face_physics.hpp"
 
 namespace hfx
 {
@@ -332,10 +332,8 @@ __global__ __launch_bounds__(256) void bdy_invflux_kernel(const BdyArgs a)
   const long il = a.L[q];
   const hfx_bc bc = a.bcs[a.boundary_id[i]];
   double ul[NF], ur[NF], n[ND], fn[NF];
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.norm[il + m * a.plane];
-#pragma unroll
-  for (int k = 0; k < NF; k++) ul[k] = a.disu[il + k * a.plane];
+  gather_plane(a.norm, il, a.plane, n);
+  gather_plane(a.disu, il, a.plane, ul);
   bc_state<ND>(0, bc, ul, n, a.P.gamma, a.R_ref, a.ramp_counter, ur);
   if (bc.flag == HFX_BC_SLIP_WALL_DUAL)
   {
@@ -350,19 +348,12 @@ __global__ __launch_bounds__(256) void bdy_invflux_kernel(const BdyArgs a)
     }
   }
   else if (FAST)
-  {
-    if (a.P.riemann == 0)
-      riemann_flux_t<ND, 0, true>(a.P, ul, ur, n, fn);
-    else if (a.P.riemann == 2)
-      riemann_flux_t<ND, 2, true>(a.P, ul, ur, n, fn);
-    else
-      riemann_flux_t<ND, 3, true>(a.P, ul, ur, n, fn);
-  }
+    riemann_flux_fast<ND>(a.P, ul, ur, n, fn);
   else
     riemann_flux<ND>(a.P, ul, ur, n, fn);
   const double tl = a.tdA[il];
 #pragma unroll
-  for (int k = 0; k < NF; k++) a.tconf[il + k * a.plane] = fn[k] * tl;
+  for (int k = 0; k < NF; k++) store_flux_left(a.tconf[il + k * a.plane], tl, fn[k]);
   if (a.P.viscous)
   {
     if (bc_is_wall(bc.flag)) bc_state<ND>(1, bc, ul, n, a.P.gamma, a.R_ref, a.ramp_counter, ur);
@@ -384,12 +375,9 @@ __global__ __launch_bounds__(256) void bdy_viscflux_kernel(const BdyArgs a)
   const hfx_bc bc = a.bcs[a.boundary_id[i]];
   if (bc.flag == HFX_BC_SLIP_WALL) return;
   double ul[NF], ur[NF], n[ND], gl[NG], gr[NG], fr[NG];
-#pragma unroll
-  for (int k = 0; k < NF; k++) ul[k] = a.disu[il + k * a.plane];
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.norm[il + m * a.plane];
-#pragma unroll
-  for (int s = 0; s < NG; s++) gl[s] = a.grad[il + s * a.plane];
+  gather_plane(a.disu, il, a.plane, ul);
+  gather_plane(a.norm, il, a.plane, n);
+  gather_plane(a.grad, il, a.plane, gl);
   bc_state<ND>(1, bc, ul, n, a.P.gamma, a.R_ref, a.ramp_counter, ur);
   bc_gradients<ND>(bc.flag, ur, gl, n, gr);
   calc_visf<ND, FAST>(a.P, ur, gr, fr);
@@ -401,8 +389,8 @@ __global__ __launch_bounds__(256) void bdy_viscflux_kernel(const BdyArgs a)
     double fn = 0.0;
 #pragma unroll
     for (int l = 0; l < ND; l++) fn += fr[k + NF * l] * n[l];
-    fn -= a.P.ldg_tau * (ur[k] - ul[k]);
-    a.tconf[il + k * a.plane] += fn * tl;
+    fn -= ldg_penalty(a.P, ul[k], ur[k]);
+    store_flux_left<true>(a.tconf[il + k * a.plane], tl, fn);
   }
 }
 

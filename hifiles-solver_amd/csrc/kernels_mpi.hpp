@@ -6,6 +6,7 @@
 // ranks evaluate the common flux from their own side as "left"; the results agree to rounding.
 #pragma once
 #include "hfx_internal.hpp"
+#include "face_physics.hpp"
 
 namespace hfx
 {
@@ -99,37 +100,20 @@ __global__ __launch_bounds__(256) void mpi_common_invflux_kernel(const MpiArgs a
   const long il = a.L[q];
   const int jr = a.Rlut[q];
   double ul[NF], ur[NF], n[ND], fn[NF];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu[il + k * a.plane];
-    ur[k] = a.in_disu[jr + (long)a.nfpi * (k + NF * i)];
-  }
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.norm[il + m * a.plane];
+  gather_pair_record(a.disu, il, a.plane, a.in_disu, jr, a.nfpi, i, ul, ur);
+  gather_plane(a.norm, il, a.plane, n);
   if (FAST)
-  {
-    if (a.P.riemann == 0)
-      riemann_flux_t<ND, 0, true>(a.P, ul, ur, n, fn);
-    else if (a.P.riemann == 2)
-      riemann_flux_t<ND, 2, true>(a.P, ul, ur, n, fn);
-    else
-      riemann_flux_t<ND, 3, true>(a.P, ul, ur, n, fn);
-  }
+    riemann_flux_fast<ND>(a.P, ul, ur, n, fn);
   else
     riemann_flux<ND>(a.P, ul, ur, n, fn);
   const double tl = a.tdA[il];
 #pragma unroll
-  for (int k = 0; k < NF; k++) a.tconf[il + k * a.plane] = fn[k] * tl;
+  for (int k = 0; k < NF; k++) store_flux_left(a.tconf[il + k * a.plane], tl, fn[k]);
   if (a.P.viscous && a.delta != nullptr)
   {
     const double beta = ldg_switch<ND>(a.P.ldg_beta, n);
 #pragma unroll
-    for (int k = 0; k < NF; k++)
-    {
-      const double uc = 0.5 * (ul[k] + ur[k]) - beta * (ul[k] - ur[k]);
-      a.delta[il + k * a.plane] = uc - ul[k];
-    }
+    for (int k = 0; k < NF; k++) a.delta[il + k * a.plane] = ldg_common_solution(beta, ul[k], ur[k]);
   }
 }
 
@@ -144,16 +128,15 @@ __global__ __launch_bounds__(256) void mpi_delta_kernel(const MpiArgs a)
   const long il = a.L[q];
   const int jr = a.Rlut[q];
   double n[ND];
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.norm[il + m * a.plane];
+  gather_plane(a.norm, il, a.plane, n);
   const double beta = ldg_switch<ND>(a.P.ldg_beta, n);
+  // (field by field: a handful of registers)
 #pragma unroll
   for (int k = 0; k < NF; k++)
   {
     const double ul = a.disu[il + k * a.plane];
     const double ur = a.in_disu[jr + (long)a.nfpi * (k + NF * i)];
-    const double uc = 0.5 * (ul + ur) - beta * (ul - ur);
-    a.delta[il + k * a.plane] = uc - ul;
+    a.delta[il + k * a.plane] = ldg_common_solution(beta, ul, ur);
   }
 }
 
@@ -168,6 +151,7 @@ __global__ __launch_bounds__(256) void mpi_common_viscflux_kernel(const MpiArgs 
   const long il = a.L[q];
   const int jr = a.Rlut[q];
   double ul[NF], ur[NF], gl[NG], gr[NG], fl[NG], fr[NG], n[ND];
+  // (written out: through gather_pair_record the same loads take six more registers at ND = 2)
 #pragma unroll
   for (int k = 0; k < NF; k++)
   {
@@ -180,8 +164,7 @@ __global__ __launch_bounds__(256) void mpi_common_viscflux_kernel(const MpiArgs 
     gl[s] = a.grad[il + s * a.plane];
     gr[s] = a.in_grad[jr + (long)a.nfpi * (s + NG * i)];
   }
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.norm[il + m * a.plane];
+  gather_plane(a.norm, il, a.plane, n);
   calc_visf<ND, FAST>(a.P, ul, gl, fl);
   calc_visf<ND, FAST>(a.P, ur, gr, fr);
   if (a.sgsf != nullptr) // src/mpi_inters.cpp:536-551: the physical SGS flux of both sides joins the viscous flux
@@ -198,18 +181,7 @@ __global__ __launch_bounds__(256) void mpi_common_viscflux_kernel(const MpiArgs 
   const double beta = ldg_switch<ND>(a.P.ldg_beta, n);
   const double tl = a.tdA[il];
 #pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    double fn = 0.0;
-#pragma unroll
-    for (int l = 0; l < ND; l++)
-    {
-      const double fc = (0.5 + beta) * fl[k + NF * l] + (0.5 - beta) * fr[k + NF * l];
-      fn += fc * n[l];
-    }
-    fn -= a.P.ldg_tau * (ur[k] - ul[k]);
-    a.tconf[il + k * a.plane] += fn * tl;
-  }
+  for (int k = 0; k < NF; k++) store_flux_left<true>(a.tconf[il + k * a.plane], tl, ldg_flux_reference<ND>(a.P, beta, ul[k], ur[k], fl, fr, n, k));
 }
 
 // ---- split variant 3: the neighbour sends its projected viscous flux Fn = F_v(u,grad).n_own (n_fields
@@ -239,37 +211,25 @@ __global__ __launch_bounds__(256) void mpi_common_flux2_kernel(const MpiArgs a)
   const long il = a.L[q];
   const int jr = a.Rlut[q];
   double ul[NF], ur[NF], n[ND], fn[NF];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu[il + k * a.plane];
-    ur[k] = a.in_disu[jr + (long)a.nfpi * (k + NF * i)];
-  }
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.norm[il + m * a.plane];
-  if (a.P.riemann == 0)
-    riemann_flux_t<ND, 0, true>(a.P, ul, ur, n, fn);
-  else if (a.P.riemann == 2)
-    riemann_flux_t<ND, 2, true>(a.P, ul, ur, n, fn);
-  else
-    riemann_flux_t<ND, 3, true>(a.P, ul, ur, n, fn);
+  gather_pair_record(a.disu, il, a.plane, a.in_disu, jr, a.nfpi, i, ul, ur);
+  gather_plane(a.norm, il, a.plane, n);
+  riemann_flux_fast<ND>(a.P, ul, ur, n, fn);
   const double tl = a.tdA[il];
   if (a.P.viscous)
   {
+    // the neighbour projected on ITS normal = -n (its record rides in the gradient buffer)
     const double beta = ldg_switch<ND>(a.P.ldg_beta, n);
 #pragma unroll
     for (int k = 0; k < NF; k++)
     {
-      // the neighbour projected on ITS normal = -n
-      double fv = (0.5 + beta) * a.fn[il + k * a.plane] - (0.5 - beta) * a.in_grad[jr + (long)a.nfpi * (k + NF * i)];
-      fv -= a.P.ldg_tau * (ur[k] - ul[k]);
-      a.tconf[il + k * a.plane] = fn[k] * tl + fv * tl;
+      const double fv = ldg_flux_projected(a.P, beta, ul[k], ur[k], a.fn[il + k * a.plane], a.in_grad[jr + (long)a.nfpi * (k + NF * i)]);
+      store_flux_left(a.tconf[il + k * a.plane], tl, fn[k], fv);
     }
   }
   else
   {
 #pragma unroll
-    for (int k = 0; k < NF; k++) a.tconf[il + k * a.plane] = fn[k] * tl;
+    for (int k = 0; k < NF; k++) store_flux_left(a.tconf[il + k * a.plane], tl, fn[k]);
   }
 }
 

@@ -15,6 +15,7 @@
 // 4.6 kB run.
 #pragma once
 #include "hfx_internal.hpp"
+#include "face_kernels.hpp" // FacePairArgs (no kernel of that header is instantiated here)
 
 namespace hfx
 {
@@ -236,108 +237,57 @@ __global__ __launch_bounds__(PT_BLOCK) void sgsf_to_physical_kernel(long plane, 
 }
 
 // ---- int_inters::calculate_common_invFlux ------------------------------------
-struct FaceArgs
-{
-  long npairs; // n_fpts_per_inter * n_inters
-  const int *L, *R;
-  long plane_l, plane_r; // n_fpts*n_eles of the left / right element block
-  const double *disu_l, *disu_r;
-  const double *norm_l; // left block norm_fpts (fpt,ele,dim)
-  const double *tdA_l, *tdA_r;
-  double *tconf_l, *tconf_r;
-  double *delta_l, *delta_r;
-  const double *grad_l, *grad_r;
-  const double *sgsf_l, *sgsf_r; // LES: physical SGS flux at the flux points (NULL: off)
-};
-
 template <int ND>
-__global__ __launch_bounds__(PT_BLOCK) void common_invflux_kernel(const FaceArgs a, const Phys P)
+__global__ __launch_bounds__(PT_BLOCK) void common_invflux_kernel(const FacePairArgs a, const Phys P)
 {
   constexpr int NF = ND + 2;
   const long q = (long)blockIdx.x * PT_BLOCK + threadIdx.x;
   if (q >= a.npairs) return;
   const long il = a.L[q], ir = a.R[q];
   double ul[NF], ur[NF], n[ND], fn[NF];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu_l[il + k * a.plane_l];
-    ur[k] = a.disu_r[ir + k * a.plane_r];
-  }
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.norm_l[il + m * a.plane_l];
+  gather_pair(a.l.disu, il, a.l.plane, a.r.disu, ir, a.r.plane, ul, ur);
+  gather_plane(a.norm, il, a.l.plane, n);
   riemann_flux<ND>(P, ul, ur, n, fn);
-  const double tl = a.tdA_l[il], tr = a.tdA_r[ir];
+  const double tl = a.l.tdA[il], tr = a.r.tdA[ir];
 #pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    a.tconf_l[il + k * a.plane_l] = fn[k] * tl;
-    a.tconf_r[ir + k * a.plane_r] = -fn[k] * tr;
-  }
+  for (int k = 0; k < NF; k++) store_flux_both(a.l.tconf[il + k * a.l.plane], tl, a.r.tconf[ir + k * a.r.plane], tr, fn[k]);
   if (P.viscous)
   {
     const double beta = ldg_switch<ND>(P.ldg_beta, n);
 #pragma unroll
-    for (int k = 0; k < NF; k++)
-    {
-      const double uc = 0.5 * (ul[k] + ur[k]) - beta * (ul[k] - ur[k]);
-      a.delta_l[il + k * a.plane_l] = uc - ul[k];
-      a.delta_r[ir + k * a.plane_r] = uc - ur[k];
-    }
+    for (int k = 0; k < NF; k++) ldg_common_solution(beta, ul[k], ur[k], a.l.delta[il + k * a.l.plane], a.r.delta[ir + k * a.r.plane]);
   }
 }
 
 // ---- int_inters::calculate_common_viscFlux (LES off) ---------------------------
 template <int ND>
-__global__ __launch_bounds__(PT_BLOCK) void common_viscflux_kernel(const FaceArgs a, const Phys P)
+__global__ __launch_bounds__(PT_BLOCK) void common_viscflux_kernel(const FacePairArgs a, const Phys P)
 {
-  constexpr int NF = ND + 2;
+  constexpr int NF = ND + 2, NG = NF * ND;
   const long q = (long)blockIdx.x * PT_BLOCK + threadIdx.x;
   if (q >= a.npairs) return;
   const long il = a.L[q], ir = a.R[q];
-  double ul[NF], ur[NF], gl[NF * ND], gr[NF * ND], fl[NF * ND], fr[NF * ND], n[ND];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu_l[il + k * a.plane_l];
-    ur[k] = a.disu_r[ir + k * a.plane_r];
-  }
-#pragma unroll
-  for (int s = 0; s < NF * ND; s++)
-  {
-    gl[s] = a.grad_l[il + s * a.plane_l];
-    gr[s] = a.grad_r[ir + s * a.plane_r];
-  }
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.norm_l[il + m * a.plane_l];
+  double ul[NF], ur[NF], gl[NG], gr[NG], fl[NG], fr[NG], n[ND];
+  gather_pair(a.l.disu, il, a.l.plane, a.r.disu, ir, a.r.plane, ul, ur);
+  gather_pair(a.l.grad, il, a.l.plane, a.r.grad, ir, a.r.plane, gl, gr);
+  gather_plane(a.norm, il, a.l.plane, n);
   calc_visf<ND>(P, ul, gl, fl);
   calc_visf<ND>(P, ur, gr, fr);
-  if (a.sgsf_l != nullptr)
+  if (a.l.sgsf != nullptr)
   {
-    // src/int_inters.cpp:302-318
+    // src/int_inters.cpp:302-318 (the physical SGS flux of both sides)
 #pragma unroll
-    for (int s = 0; s < NF * ND; s++)
+    for (int s = 0; s < NG; s++)
     {
-      fl[s] += a.sgsf_l[il + s * a.plane_l];
-      fr[s] += a.sgsf_r[ir + s * a.plane_r];
+      fl[s] += a.l.sgsf[il + s * a.l.plane];
+      fr[s] += a.r.sgsf[ir + s * a.r.plane];
     }
   }
   const double beta = ldg_switch<ND>(P.ldg_beta, n);
-  const double tl = a.tdA_l[il], tr = a.tdA_r[ir];
+  const double tl = a.l.tdA[il], tr = a.r.tdA[ir];
 #pragma unroll
   for (int k = 0; k < NF; k++)
-  {
-    double fn = 0.0;
-#pragma unroll
-    for (int l = 0; l < ND; l++)
-    {
-      const double fc = (0.5 + beta) * fl[k + NF * l] + (0.5 - beta) * fr[k + NF * l];
-      fn += fc * n[l];
-    }
-    fn -= P.ldg_tau * (ur[k] - ul[k]);
-    a.tconf_l[il + k * a.plane_l] += fn * tl;
-    a.tconf_r[ir + k * a.plane_r] += -fn * tr;
-  }
+    store_flux_both<true>(a.l.tconf[il + k * a.l.plane], tl, a.r.tconf[ir + k * a.r.plane], tr, ldg_flux_reference<ND>(P, beta, ul[k], ur[k], fl, fr, n, k));
 }
 
 // ---- eles::calc_sgs_terms (src/eles.cpp:2058-2283), the two point-wise parts ----------------------------

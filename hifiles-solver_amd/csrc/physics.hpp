@@ -416,9 +416,9 @@ __device__ __forceinline__ void riemann_flux_t(const Phys &P, const double (&ul)
 }
 
 // the "consistent switch" (inters.cpp:568-581, :620-633): exact floating-point
-// zero tests on the LEFT element's unit normal.
+// zero tests on the LEFT element's unit normal.  (Host too: the fused stages decide the sign once, when they build their tables.)
 template <int ND>
-__device__ __forceinline__ double ldg_switch(double beta, const double (&n)[ND])
+__host__ __device__ __forceinline__ double ldg_switch(double beta, const double (&n)[ND])
 {
   if (beta != 0.0)
   {

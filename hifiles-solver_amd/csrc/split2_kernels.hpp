@@ -3,6 +3,7 @@
 // instantiated once)
 #pragma once
 #include "split_common.hpp"
+#include "face_kernels.hpp" // the pairwise kernels between the element kernels: face_delta_kernel, face_flux_kernel, face_flux2_kernel
 
 namespace hfx
 {
@@ -19,114 +20,6 @@ namespace hfx
 // pairwise face kernels read every flux-point datum once instead of twice, and every element
 // kernel is a thread-per-point kernel small enough to keep 3-4 workgroups resident per CU.
 // =======================================================================================
-
-struct SplitFaceArgs
-{
-  // LES: the SGS flux at the flux points in REFERENCE space (n_fpts,n_eles,n_fields,n_dims), NULL: off; the kernel takes
-  // it to physical space with |J|^-1 J (second half of eles::extrapolate_sgsFlux, src/eles.cpp:2862-2893)
-  const double *sgsf, *jac_fpts, *detjac_fpts;
-
-  long npairs;
-  const int *L, *R;
-  const unsigned char *meta; // bit1 of the LEFT point: beta sign flipped
-  long plane_f;
-  const double *disu, *grad, *fnorm, *tdA;
-  double *delta, *tconf;
-  Phys P;
-};
-
-template <int ND>
-__global__ __launch_bounds__(256) void face_delta_kernel(const SplitFaceArgs a)
-{
-  constexpr int NF = ND + 2;
-  const long q = (long)blockIdx.x * 256 + threadIdx.x;
-  if (q >= a.npairs) return;
-  const long il = a.L[q], ir = a.R[q];
-  const double beta = (a.meta[il] & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
-  // every load before the first store (the compiler must assume that delta and disu overlap: a load behind a store waits)
-  double ul[NF], ur[NF];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu[il + k * a.plane_f];
-    ur[k] = a.disu[ir + k * a.plane_f];
-  }
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    const double uc = 0.5 * (ul[k] + ur[k]) - beta * (ul[k] - ur[k]); // src/inters.cpp:637
-    a.delta[il + k * a.plane_f] = uc - ul[k];
-    a.delta[ir + k * a.plane_f] = uc - ur[k];
-  }
-}
-
-template <int ND, int RS>
-__global__ __launch_bounds__(256) void face_flux_kernel(const SplitFaceArgs a)
-{
-  constexpr int NF = ND + 2, NG = NF * ND;
-  const long q = (long)blockIdx.x * 256 + threadIdx.x;
-  if (q >= a.npairs) return;
-  const long il = a.L[q], ir = a.R[q];
-  double ul[NF], ur[NF], n[ND], fn[NF];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu[il + k * a.plane_f];
-    ur[k] = a.disu[ir + k * a.plane_f];
-  }
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.fnorm[il + m * a.plane_f];
-  const double tl = a.tdA[il], tr = a.tdA[ir];
-  riemann_flux_t<ND, RS, true>(a.P, ul, ur, n, fn);
-  if (a.P.viscous)
-  {
-    const double beta = (a.meta[il] & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
-    double pl[NF];
-    {
-      double gq[NG], fq[NG];
-#pragma unroll
-      for (int s = 0; s < NG; s++) gq[s] = a.grad[il + s * a.plane_f];
-      calc_visf<ND, true>(a.P, ul, gq, fq);
-      if (a.sgsf) add_sgs_flux<ND>(a.sgsf, a.jac_fpts, a.detjac_fpts, il, a.plane_f, fq); // src/int_inters.cpp:302-318
-#pragma unroll
-      for (int k = 0; k < NF; k++)
-      {
-        double s = 0.0;
-#pragma unroll
-        for (int l = 0; l < ND; l++) s += ((0.5 + beta) * fq[k + NF * l]) * n[l];
-        pl[k] = s;
-      }
-    }
-    {
-      double gq[NG], fq[NG];
-#pragma unroll
-      for (int s = 0; s < NG; s++) gq[s] = a.grad[ir + s * a.plane_f];
-      calc_visf<ND, true>(a.P, ur, gq, fq);
-      if (a.sgsf) add_sgs_flux<ND>(a.sgsf, a.jac_fpts, a.detjac_fpts, ir, a.plane_f, fq);
-#pragma unroll
-      for (int k = 0; k < NF; k++)
-      {
-        double s = 0.0;
-#pragma unroll
-        for (int l = 0; l < ND; l++) s += ((0.5 - beta) * fq[k + NF * l]) * n[l];
-        double fv = pl[k] + s;
-        fv -= a.P.ldg_tau * (ur[k] - ul[k]);
-        // norm_tconf_l = fn*tdA_l + fv*tdA_l ; norm_tconf_r = -fn*tdA_r + -fv*tdA_r   (int_inters.cpp:217-220,329-332)
-        a.tconf[il + k * a.plane_f] = fn[k] * tl + fv * tl;
-        a.tconf[ir + k * a.plane_f] = -fn[k] * tr + -fv * tr;
-      }
-    }
-  }
-  else
-  {
-#pragma unroll
-    for (int k = 0; k < NF; k++)
-    {
-      a.tconf[il + k * a.plane_f] = fn[k] * tl;
-      a.tconf[ir + k * a.plane_f] = -fn[k] * tr;
-    }
-  }
-}
 
 struct SplitEleArgs
 {

@@ -1647,71 +1647,6 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
 }
 
 
-struct Split2FaceArgs
-{
-  long npairs;
-  const int *L, *R;
-  const unsigned char *meta;
-  long plane_f;
-  const double *disu, *fn, *fnorm, *tdA;
-  double *tconf;
-  Phys P;
-};
-
-template <int ND, int RS>
-__global__ __launch_bounds__(256) void face_flux2_kernel(const Split2FaceArgs a)
-{
-  constexpr int NF = ND + 2;
-  const long q = (long)blockIdx.x * 256 + threadIdx.x;
-  if (q >= a.npairs) return;
-  const long il = a.L[q], ir = a.R[q];
-  double ul[NF], ur[NF], n[ND], fn[NF];
-#pragma unroll
-  for (int k = 0; k < NF; k++)
-  {
-    ul[k] = a.disu[il + k * a.plane_f];
-    ur[k] = a.disu[ir + k * a.plane_f];
-  }
-#pragma unroll
-  for (int m = 0; m < ND; m++) n[m] = a.fnorm[il + m * a.plane_f];
-  const double tl = a.tdA[il], tr = a.tdA[ir];
-  // (every load before the first store: tconf may overlap the inputs as far as the compiler knows)
-  double fl[NF], fr[NF];
-  const unsigned char mt = a.meta[il]; // with the other loads, not behind the Riemann solver
-  if (a.P.viscous)
-  {
-#pragma unroll
-    for (int k = 0; k < NF; k++)
-    {
-      fl[k] = a.fn[il + k * a.plane_f];
-      fr[k] = a.fn[ir + k * a.plane_f];
-    }
-  }
-  riemann_flux_t<ND, RS, true>(a.P, ul, ur, n, fn);
-  if (a.P.viscous)
-  {
-    const double beta = (mt & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
-#pragma unroll
-    for (int k = 0; k < NF; k++)
-    {
-      // (1/2+b) F_L.n + (1/2-b) F_R.n - tau (u_R - u_L), n the left normal = -(right normal)
-      double fv = (0.5 + beta) * fl[k] - (0.5 - beta) * fr[k];
-      fv -= a.P.ldg_tau * (ur[k] - ul[k]);
-      a.tconf[il + k * a.plane_f] = fn[k] * tl + fv * tl;
-      a.tconf[ir + k * a.plane_f] = -fn[k] * tr + -fv * tr;
-    }
-  }
-  else
-  {
-#pragma unroll
-    for (int k = 0; k < NF; k++)
-    {
-      a.tconf[il + k * a.plane_f] = fn[k] * tl;
-      a.tconf[ir + k * a.plane_f] = -fn[k] * tr;
-    }
-  }
-}
-
 // div_tdisf + opp_3 (norm_tconf - norm_tdisf) -> RK update -> disu_fpts of the new state: a streaming kernel
 // (after the sum-factorised flux kernel: (div_tdisf - opp_3 norm_tdisf) + opp_3 norm_tconf, norm_tdisf is not read)
 #ifndef HFX_UPD_WAVES

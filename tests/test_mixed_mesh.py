@@ -151,15 +151,13 @@ def test_run_steps_blocks_vs_reference():
     ctx.close()
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("name", MIXED)
-def test_general_fused_stage_on_mixed_mesh_vs_reference(name):
-    """hfx_run_steps_blocks(..., fused = 4): the fused stage for general element classes (csrc/general.hip: four launches
-    per block and stage, FP64-MFMA contractions over batches of 16 elements) on the mixed channel -- prism | tetrahedron
-    face pairs, walls on the prisms -- against the genuine reference after every time step"""
+def general_fused_vs_reference(name, options=()):
+    """one time step after the other on the general fused stage, against the genuine reference after every step"""
     import hfx
     d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
     ctx = hfx.Context(0)
+    for k, v in options:
+        ctx.set_option(k, v)
     classes, E, F = build_gpu(ctx, d)
     nstage = int(d["c2_sizes"][7])
     steps = sorted({int(k.split("_")[2][4:]) for k in d if k.startswith("c2_u_step")})
@@ -174,6 +172,22 @@ def test_general_fused_stage_on_mixed_mesh_vs_reference(name):
     for c in classes:
         E[c].close()
     ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", MIXED)
+def test_general_fused_stage_on_mixed_mesh_vs_reference(name):
+    """hfx_run_steps_blocks(..., fused = 4): the fused stage for general element classes (csrc/general.hip: four launches
+    per block and stage, FP64-MFMA contractions over batches of 16 elements) on the mixed channel -- prism | tetrahedron
+    face pairs, walls on the prisms -- against the genuine reference after every time step"""
+    general_fused_vs_reference(name)
+
+
+@pytest.mark.gpu
+def test_general_fused_stage_face_delta_kernel_vs_reference():
+    """the same with gather_delta off: the flux kernels do not form the LDG corrections themselves, so face_delta_kernel<3>
+    writes them for every interior face block, those between prisms and tetrahedra (two planes, two array sets) included"""
+    general_fused_vs_reference("mixed_p3_channel", [("gather_delta", 0)])
 
 
 @pytest.mark.gpu
