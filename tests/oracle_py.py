@@ -316,51 +316,73 @@ class PartitionedCase(Case):
 
     # kinds of exchange: 0 solution, 1 corrected gradient, 2 SGS flux (LES; src/mpi_inters.cpp:339-397)
 
-    def CalcResidual(self):
+    def residual_points(self):
+        """CalcResidual as a generator: yields (kind, phase) where the reference starts (phase 0) or awaits (phase 1) a
+        message -- four points, six with an LES closure -- and returns calculate_corrected_divergence's value.  A caller that
+        runs several parts in one thread advances every part to the same point and moves the records in between."""
         o = load()
         e, (f, nb), m, p = self.c_eles(), self.c_faces(), self.c_mpi(), self.params
         E, M, P = C.byref(e), C.byref(m), C.byref(p)
+        bd, nbd = self.c_bdy() if self.bdy else (None, 0)
         have = m.n_inters > 0
         o.orc_extrapolate_solution(E)
         if have:
             o.orc_mpi_pack_solution(M, E)
-            self.exchange(0, 0)
+            yield (0, 0)
         if p.viscous:
             o.orc_calculate_gradient(E)
         o.orc_evaluate_invFlux(E, C.byref(p))
         for b in range(nb):
             o.orc_int_calculate_common_invFlux(C.byref(f[b]), E, P)
+        for b in range(nbd):
+            o.orc_bdy_evaluate_boundaryConditions_invFlux(C.byref(bd[b]), E, P)
         if have:
-            self.exchange(0, 1)
+            yield (0, 1)
             o.orc_mpi_calculate_common_invFlux(M, E, P)
         if p.viscous:
             o.orc_correct_gradient(E)
             if have:
                 o.orc_mpi_pack_corrected_gradient(M, E)
-                self.exchange(1, 0)
+                yield (1, 0)
             o.orc_evaluate_viscFlux(E, P)
             if self.les:  # src/solver.cpp:162-178
                 o.orc_extrapolate_sgsFlux(E)
                 if have:
                     o.orc_mpi_pack_sgsf(M, E)
-                    self.exchange(2, 0)
+                    yield (2, 0)
         o.orc_extrapolate_totalFlux(E)
         o.orc_calculate_divergence(E)
         if p.viscous:
             for b in range(nb):
                 o.orc_int_calculate_common_viscFlux(C.byref(f[b]), E, P)
+            for b in range(nbd):
+                o.orc_bdy_evaluate_boundaryConditions_viscFlux(C.byref(bd[b]), E, P)
             if have:
-                self.exchange(1, 1)
+                yield (1, 1)
                 if self.les:  # src/solver.cpp:203-206
-                    self.exchange(2, 1)
+                    yield (2, 1)
                 o.orc_mpi_calculate_common_viscFlux(M, E, P)
         return o.orc_calculate_corrected_divergence(E)
 
-    def rk_step(self):
+    def rk_step_points(self):
+        """one time step as a generator over the same points (every stage's CalcResidual, then AdvanceSolution)"""
         o = load()
         for s in range(self.params.n_rk if self.params.adv_type else 1):
             if s == 0 and self.les and self.les["sgs_model"] >= 2:  # src/solver.cpp:55-62
                 assert o.orc_calc_sgs_terms(C.byref(self.c_eles())) < 0
-            bad = self.CalcResidual()
+            bad = yield from self.residual_points()
             assert bad < 0, "NaN at %d" % bad
             o.orc_AdvanceSolution(C.byref(self._e), C.byref(self.params), C.c_int(s))
+
+    def _drive(self, points):
+        try:
+            while True:
+                self.exchange(*next(points))
+        except StopIteration as stop:
+            return stop.value
+
+    def CalcResidual(self):
+        return self._drive(self.residual_points())
+
+    def rk_step(self):
+        self._drive(self.rk_step_points())

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import mixed_util as MU
+from ragged_partition import self_partition
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MIXED = ["mixed_p2_channel", "mixed_p3_channel"]
@@ -460,31 +461,7 @@ def test_general_les_stage_at_bench_size_properties():
 
 
 # ---- the mixed channel on PARTITIONED element blocks ----------------------------------------------------------------------
-def self_partition(ctx, E, faces):
-    """Every second face of every interior block that joins a class to ITSELF becomes a pair of one-sided partition faces whose
-    neighbour is the rank itself: -> (remaining interior blocks as (a, b, L, R), [hfx.MpiInters]).  The partition-face block
-    of a (class, face type) lists the left sides A_0..A_n-1, then the right sides B_0..B_n-1 (in the order of their own
-    offsets); Rlut is the slot of the partner's point in the mate's record; the two halves are each other's neighbour segment."""
-    import hfx
-    rest, mpi = [], []
-    for a, b, L, R in faces:
-        if a != b or L.shape[1] < 4:
-            rest.append((a, b, L, R))
-            continue
-        pick = np.zeros(L.shape[1], dtype=bool)
-        pick[::2] = True
-        rest.append((a, b, np.asfortranarray(L[:, ~pick]), np.asfortranarray(R[:, ~pick])))
-        La, Ra = L[:, pick], R[:, pick]
-        n = La.shape[1]
-        order = np.argsort(Ra, axis=0)            # order[j', i]: the A-point j whose partner is B's j'-th point
-        rank = np.argsort(order, axis=0)          # rank[j, i]: the slot of A-point j's partner in B's record
-        Lb = np.take_along_axis(Ra, order, axis=0)
-        Lm = np.asfortranarray(np.concatenate([La, Lb], axis=1).astype(np.int32))
-        Rlut = np.asfortranarray(np.concatenate([rank, order], axis=1).astype(np.int32))
-        f = hfx.MpiInters(ctx, E[a], Lm, Rlut)
-        f.set_neighbours([(0, 0, n, n), (0, n, 0, n)])
-        mpi.append(f)
-    return rest, mpi
+# (self_partition: ragged_partition.cut_faces_self with the rule "every second face")
 
 
 @pytest.mark.gpu
