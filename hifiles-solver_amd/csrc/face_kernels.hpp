@@ -143,11 +143,19 @@ __global__ __launch_bounds__(256) void face_flux2_kernel(const FaceBlockArgs b, 
   // (every load before the first store: tconf may overlap the inputs as far as the compiler knows)
   double fl[NF], fr[NF];
   const unsigned char mt = a.meta[il]; // with the other loads, not behind the Riemann solver
-  if (P.viscous) gather_pair(a.l.fn, il, a.l.plane, a.r.fn, ir, a.r.plane, fl, fr);
+  const double beta = ldg_beta(mt, P);
+  // (one-sided LDG: only the side whose weight is not zero -- the affine flux kernel did not write the other; quads: both, as the
+  // 2-D flux kernels write both -- the one register more of the selected load costs this kernel's 2-D form a resident wave)
+  if (P.viscous)
+  {
+    if constexpr (ND == 3)
+      gather_pair_needed(P, beta, a.l.fn, il, a.l.plane, a.r.fn, ir, a.r.plane, fl, fr);
+    else
+      gather_pair(a.l.fn, il, a.l.plane, a.r.fn, ir, a.r.plane, fl, fr);
+  }
   riemann_flux_t<ND, RS, true>(P, ul, ur, n, fn);
   if (P.viscous)
   {
-    const double beta = ldg_beta(mt, P);
 #pragma unroll
     for (int k = 0; k < NF; k++)
     {
@@ -196,9 +204,9 @@ __global__ __launch_bounds__(256) void gface_flux_multi_kernel(const GFaceMulti 
   double fl[NF], fr[NF];
   const unsigned char mt = a.meta[il];
   const bool viscous = P.viscous;
-  if (viscous) gather_pair(a.l.fn, il, a.l.plane, a.r.fn, ir, a.r.plane, fl, fr);
-  riemann_flux_t<ND, RS, true>(P, ul, ur, n, fn);
   const double beta = ldg_beta(mt, P);
+  if (viscous) gather_pair_needed(P, beta, a.l.fn, il, a.l.plane, a.r.fn, ir, a.r.plane, fl, fr);
+  riemann_flux_t<ND, RS, true>(P, ul, ur, n, fn);
 #pragma unroll
   for (int k = 0; k < NF; k++)
   {

@@ -136,6 +136,36 @@ __device__ __forceinline__ double ldg_flux_projected(const Phys &P, double beta,
   return fv;
 }
 
+// One-sided LDG: with |ldg_beta| = 1/2 one of the two weights of every pair is exactly 0.0 and the common viscous flux is the Fn of
+// ONE side (which one: the pair's sign bit).  The flux kernels that know their points' partners do not write an Fn whose weight is
+// zero (split3_kernels.hpp, fn_needed), so the pairwise kernels must not read it: `both` -- uniform, from the run's ldg_beta --
+// says whether both sides enter; if not, the one load per field goes to the side with the non-zero weight and the other side is 0.0
+// (w * Fn - 0.0 * 0.0: the result of the full formula for finite data).
+__device__ __forceinline__ bool ldg_both_sides(const Phys &P) { return (0.5 + P.ldg_beta) != 0.0 && (0.5 - P.ldg_beta) != 0.0; }
+
+template <int S>
+__device__ __forceinline__ void gather_pair_needed(const Phys &P, double beta, const double *pl, long il, long plane_l, const double *pr, long ir,
+                                                   long plane_r, double (&vl)[S], double (&vr)[S])
+{
+  if (ldg_both_sides(P))
+  {
+    gather_pair(pl, il, plane_l, pr, ir, plane_r, vl, vr);
+    return;
+  }
+  double wl, wr;
+  ldg_weights(beta, wl, wr);
+  const bool left = wl != 0.0;
+  const double *p = left ? pl + il : pr + ir;
+  const long plane = left ? plane_l : plane_r;
+#pragma unroll
+  for (int s = 0; s < S; s++)
+  {
+    const double x = p[s * plane];
+    vl[s] = left ? x : 0.0;
+    vr[s] = left ? 0.0 : x;
+  }
+}
+
 // ---- the fused paths' Riemann solver (reciprocal-multiply physics) where the solver is not a template argument of the kernel
 template <int ND>
 __device__ __forceinline__ void riemann_flux_fast(const Phys &P, const double (&ul)[ND + 2], const double (&ur)[ND + 2], const double (&n)[ND],

@@ -578,6 +578,9 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
     // (partner offset << 2) | beta-sign flipped << 1 | this point is the right side;  -1: boundary or partition-face point
     std::vector<int> nbr(plane_f, -1);
     bool fits = plane_f < (1L << 29);
+    F->n_interior_fpts = 0;
+    for (int b = 0; b < nfb; b++)
+      if (!faces[b]->is_bdy) F->n_interior_fpts += 2L * faces[b]->n_inters * faces[b]->n_fpts_per_inter;
     for (int b = 0; b < nfb && fits; b++)
     {
       hfx_inters *f = faces[b];
@@ -769,7 +772,8 @@ static void stage_args(Args &a, const hfx_eles *e, int in_step, bool write_div)
   a.adv_type = p.adv_type; a.in_step = in_step; a.dt_local_on = p.dt_type == 2; a.dt = p.dt;
   a.rk_a = (p.adv_type >= 3) ? p.RK_a[in_step] : 0.0;
   a.rk_b = (p.adv_type >= 3) ? p.RK_b[in_step] : 0.0;
-  a.need_u1 = (p.adv_type >= 3) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
+  // (low-storage schemes: a stage whose RK_a is 0.0 -- the first of a step -- takes 0.0 for the register instead of reading it)
+  a.need_u1 = (p.adv_type >= 3 && a.rk_a != 0.0) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
   a.write_div = write_div ? 1 : 0;
 }
 
@@ -1246,6 +1250,20 @@ void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant)
       // a partner word per point; the pairwise LDG kernel is not launched
       bytes[0] = 0.0;
       bytes[1] += ne * 4.0 * nfp;
+    }
+    if (e->fused && e->fused->built)
+    {
+      // One-sided LDG (|ldg_beta| = 1/2): of every interior pair one side's Fn enters the common flux.  The face kernel reads that
+      // side alone, and the flux kernel that knows its points' partners (gather) writes that side alone.  bytes[5]: the flux points
+      // whose Fn is needed -- one per pair, every boundary and partition-face point; every point with another beta, without
+      // viscosity, or in 2-D, where the stage is as it was --, bytes[6]: the bytes per stage that are not moved for the others: the face
+      // kernel's reads, and the flux kernel's writes in its affine form.  (bytes[1] and bytes[2] keep the count of every point: they
+      // price the two kernels as if all were needed.)
+      const Phys P = e->ctx->phys();
+      const bool one_sided = P.viscous && nd == 3 && ((0.5 + P.ldg_beta) == 0.0 || (0.5 - P.ldg_beta) == 0.0);
+      const double idle = one_sided ? 0.5 * (double)e->fused->n_interior_fpts : 0.0;
+      bytes[5] = nfp * ne - idle;
+      bytes[6] = 8.0 * nf * idle * (pl.affine ? 2.0 : 1.0);
     }
     if (pl.affine)
     {

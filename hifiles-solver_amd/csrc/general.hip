@@ -1057,7 +1057,8 @@ static GenArgs gen_args(hfx_eles *e, const GeneralPlan &pl, int in_step)
   a.adv_type = p.adv_type; a.in_step = in_step; a.dt_local_on = p.dt_type == 2; a.dt = p.dt;
   a.rk_a = (p.adv_type >= 3) ? p.RK_a[in_step] : 0.0;
   a.rk_b = (p.adv_type >= 3) ? p.RK_b[in_step] : 0.0;
-  a.need_u1 = (p.adv_type >= 3) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
+  // (low-storage schemes: a stage whose RK_a is 0.0 -- the first of a step -- takes 0.0 for the register instead of reading it)
+  a.need_u1 = (p.adv_type >= 3 && a.rk_a != 0.0) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
   if (e->ctx->opt.flux_stamps) (void)g->stamps.ensure_zeroed(16 * 16); // (diagnostics: without the buffer the kernel takes none)
   a.stamps = g->stamps;
   a.les = e->les; a.les_len2 = g->les_len2; a.tdA_fpts = e->tdA_fpts;

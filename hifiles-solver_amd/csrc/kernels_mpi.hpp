@@ -213,16 +213,29 @@ __global__ __launch_bounds__(256) void mpi_common_flux2_kernel(const MpiArgs a)
   double ul[NF], ur[NF], n[ND], fn[NF];
   gather_pair_record(a.disu, il, a.plane, a.in_disu, jr, a.nfpi, i, ul, ur);
   gather_plane(a.norm, il, a.plane, n);
-  riemann_flux_fast<ND>(a.P, ul, ur, n, fn);
   const double tl = a.tdA[il];
+  // the neighbour projected on ITS normal = -n (its record rides in the gradient buffer).  Only the side or sides whose LDG weight
+  // is not zero are loaded (one-sided LDG, |ldg_beta| = 1/2: one of them), before the Riemann solver and the first store
+  const double beta = ldg_switch<ND>(a.P.ldg_beta, n);
+  double fl[NF], fr[NF];
   if (a.P.viscous)
   {
-    // the neighbour projected on ITS normal = -n (its record rides in the gradient buffer)
-    const double beta = ldg_switch<ND>(a.P.ldg_beta, n);
+    double wl, wr;
+    ldg_weights(beta, wl, wr);
 #pragma unroll
     for (int k = 0; k < NF; k++)
     {
-      const double fv = ldg_flux_projected(a.P, beta, ul[k], ur[k], a.fn[il + k * a.plane], a.in_grad[jr + (long)a.nfpi * (k + NF * i)]);
+      fl[k] = (wl != 0.0) ? a.fn[il + k * a.plane] : 0.0;
+      fr[k] = (wr != 0.0) ? a.in_grad[jr + (long)a.nfpi * (k + NF * i)] : 0.0;
+    }
+  }
+  riemann_flux_fast<ND>(a.P, ul, ur, n, fn);
+  if (a.P.viscous)
+  {
+#pragma unroll
+    for (int k = 0; k < NF; k++)
+    {
+      const double fv = ldg_flux_projected(a.P, beta, ul[k], ur[k], fl[k], fr[k]);
       store_flux_left(a.tconf[il + k * a.plane], tl, fn[k], fv);
     }
   }

@@ -917,6 +917,15 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
     // Jacobian of this flux point
     [[maybe_unused]] double tsg[LES ? NG : 1], tdA_f = 1.0, len2 = 0.0;
     double accg[GA ? ROUNDS : 1][N]; // GA: the pencils' D . u, formed in A0 while the partner values are waited for
+    // One-sided LDG (|ldg_beta| = 1/2): the common viscous flux of an interior pair is the Fn of ONE side -- the other side's weight
+    // 1/2 -+ beta is exactly 0.0 -- and the pairwise kernel loads that side alone (face_physics.hpp, gather_pair_needed).  A point
+    // whose Fn is not needed stores none; boundary and partition-face points (partner word -1) and every point of a run with another
+    // beta are needed.  One bit per lane, a lane mask in scalar registers.  ONE_SIDED: the affine form on hexahedra, which has the
+    // partner word (GA) and the registers -- the other loader-wave forms sit at 256 VGPRs with spills, where the mask and the branch
+    // below cost them more spills (LES: 11 -> 32 VGPRs), and keep writing every Fn: the pairwise kernel skips what it does not need
+    // either way.  (Quads: P3 lost a resident wave to it, 167 -> 171 VGPRs; the 2-D stage is as it was, face kernel included.)
+    constexpr bool ONE_SIDED = GA && AFF && ND == 3;
+    bool fn_needed = true;
     if constexpr (GA)
     {
       // first the part of phase A that needs no correction -- the 1-D derivative of the pencils' state: the wait for the
@@ -961,6 +970,8 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
       }
       const int nb = nb_cur;
       const double beta = (nb & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
+      if constexpr (ONE_SIDED)
+        fn_needed = nb < 0 || ((nb & 1) ? 0.5 - beta : 0.5 + beta) != 0.0 || (a.grad_fpts != nullptr && a.meta == nullptr);
 #pragma unroll
       for (int k = 0; k < NF; k++)
       {
@@ -1227,7 +1238,7 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
           if (is_f) sd[k * NFP + tf] = s;
         }
       }
-      else if (is_f)
+      else if (is_f && fn_needed)
       {
 #pragma unroll
         for (int k = 0; k < NF; k++)
@@ -1297,6 +1308,12 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
     else if (LW && viscous)
     {
       // ---- a wave without solution points: the flux-point physics alone, metrics from the slot into registers first (2b)
+      // (one-sided LDG: when none of its points' Fn is needed -- the points of one face, which a conforming mesh pairs as a whole --
+      // the wave takes a uniform branch around all of it; every barrier is outside the branch)
+      // (ONE_SIDED is an AFF form: no barrier 2b inside the branch)
+      const bool wave_fn = !ONE_SIDED || __builtin_amdgcn_ballot_w64(fn_needed && is_f) != 0;
+      if (wave_fn)
+      {
       double JFl[NQ], nl[ND], grf[NG], fq[NG];
       double inv_df;
       if constexpr (AFF)
@@ -1356,9 +1373,10 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
         {
           if (is_f) sd[k * NFP + tf] = s; // (parked: the extrapolated SGS flux joins it behind phase C)
         }
-        else if (is_f)
+        else if (is_f && fn_needed)
           g_fn.st(ef + k * plane_f, lf, s);
       }
+      } // (wave_fn)
     }
     else
     {

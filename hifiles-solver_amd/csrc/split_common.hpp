@@ -33,6 +33,7 @@ struct FusedData
   DevBuf<double> tab_g, tab_r; // value tables (MAX_TAB doubles)
   DevBuf<int> o1m_dim;                       // (n_fpts) dimension slab of the merged opp_1 row
   DevBuf<int> nbr;                           // (n_fpts, n_eles) partner of every interior flux point (split3_kernels.hpp, Split2Args::nbr)
+  long n_interior_fpts = 0;                  // flux points with a partner in a registered interior face (two per pair)
   // partitioned blocks: the elements that own a flux point without a registered face (= a partition-face point), and the rest
   DevBuf<int> upd_list_b, upd_list_i;
   long n_list_b = 0, n_list_i = 0;

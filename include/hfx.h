@@ -545,7 +545,11 @@ int hfx_time_methods(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, i
 /* The same for the kernels of the fused path: ms[8] (unused entries 0), names = comma-separated
  * kernel names (buffer of 256 chars); the state advances by reps stages. */
 int hfx_time_fused_kernels(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int reps, double ms[8], char names[256]);
-/* ALGORITHMIC HBM bytes per launch of each fused kernel (same order), see DESIGN.md */
+/* ALGORITHMIC HBM bytes per launch of each fused kernel (same order), see DESIGN.md.  Variant 3, once the block's fused tables are
+ * built: bytes[5] is the number of flux points whose projected viscous flux Fn the stage needs (one-sided LDG, |ldg_beta| = 1/2, hexahedra: one
+ * point of every interior pair and every boundary / partition-face point; otherwise every point), bytes[6] the bytes per stage that
+ * the flux kernel does not write and the face kernel does not read for the others (bytes[1] and bytes[2] count every point: the two
+ * kernels together move bytes[6] less). */
 int hfx_fused_kernel_bytes(hfx_eles *e, double bytes[8]);
 /* The launches of the persistent element kernels since the block's last split fused stage began, in launch order: slot[i] is the
  * kernel's entry in hfx_time_fused_kernels (1 flux / gradient kernel, 3 update / residual kernel, 4 over-integration kernel) or 5 for the
