@@ -444,6 +444,9 @@ static int run_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int,
   for (int s = 0; n_stages_total >= 0 ? done < n_stages_total : s < n_steps; s++)
   {
     if (calc_time_step(e, comm)) return 1; /* src/HiFiLES.cpp:198 */
+    // the mass-flux body force (src/solver.cpp:96-109; not for hfx_time_partitioned): its integrals are summed over the ranks.  It reads
+    // disu_upts(0) and writes src_upts on the compute stream; the solution exchange in flight reads the packed flux-point values
+    if (n_stages_total < 0 && begin_of_step(&e, 1, comm)) return 1;
     for (int rk = 0; rk < nst && (n_stages_total < 0 || done < n_stages_total); rk++, done++)
     {
       if (partitioned_stage(e, int_faces, n_int, mpi_faces, n_mpi, comm, rk, first, T)) return 1;
@@ -684,6 +687,7 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   for (int i = 0; i < n_ele_blocks; i++) start = start || !sent_over(eles[i], comm);
   for (int s = 0; s < n_steps; s++)
   {
+    if (begin_of_step(eles, n_ele_blocks, comm)) return 1; /* src/solver.cpp:96-109 */
     for (int rk = 0; rk < nst; rk++)
     {
       if (rk == 0 && first_stage_closure_filter(eles, n_ele_blocks, false)) return 1;

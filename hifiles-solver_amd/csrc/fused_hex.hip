@@ -1116,6 +1116,7 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
   for (int s = 0; s < n_steps; s++)
   {
     if (calc_time_step(e, nullptr)) return 1; /* src/HiFiLES.cpp:198 */
+    if (begin_of_step(&e, 1, nullptr)) return 1; /* src/solver.cpp:96-109 */
     for (int rk = 0; rk < nst; rk++)
     {
       // (the SVV closure replaces the state, whose flux-point values the previous stage's update kernel has already written)

@@ -1256,6 +1256,7 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
   for (int s = 0; s < n_steps; s++)
   {
     if (calc_time_step_blocks(eles, neb)) return 1; /* src/HiFiLES.cpp:198 */
+    if (begin_of_step(eles, neb, nullptr)) return 1; /* src/solver.cpp:96-109 */
     for (int rk = 0; rk < nst; rk++)
     {
       if (rk == 0 && first_stage_closure_filter(eles, neb, true)) return 1;

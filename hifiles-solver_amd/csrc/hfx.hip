@@ -1723,6 +1723,7 @@ int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *face
   for (int s = 0; s < n_steps; s++)
   {
     if (calc_time_step_blocks(eles, neb)) return 1; /* src/HiFiLES.cpp:198 */
+    if (begin_of_step(eles, neb, nullptr)) return 1; /* src/solver.cpp:96-109 */
     for (int rk = 0; rk < nst; rk++)
     {
       if (rk == 0) /* src/solver.cpp:55-62 */

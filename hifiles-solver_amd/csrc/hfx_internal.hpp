@@ -275,6 +275,34 @@ struct LaunchLog
 };
 } // namespace hfx
 
+namespace hfx
+{
+// The controller of the mass-flux body force (forcing.hip; eles::evaluate_body_force, src/eles.cpp:5281-5482) as it lives on the
+// device: what the three kernels of an evaluation hand to each other and what the state queries download
+struct BodyForceRecord
+{
+  double integral[2];    // integral(0), integral(1) of the last evaluation (over all ranks)
+  double mass_flux, ubulk;
+  double force[2];       // body_force(1), body_force(4) of the last evaluation
+  double accumulated[2]; // their sums since the registration: what src_upts holds of the controller
+  long long steps;       // evaluations since the registration
+  int nan;               // a body_force(1) was NaN (src/eles.cpp:5455)
+  int fresh;             // no evaluation yet: mdot_old = mdot0 (src/eles.cpp:5398-5401)
+};
+struct BodyForce
+{
+  int n_faces = 0, n_groups = 0, capacity = 0;
+  double area = 0.0, mdot0 = 0.0;
+  bool own_src = false;            // HFX_SRC_UPTS was allocated by the first evaluation (the caller uploaded none)
+  DevBuf<double> weights;          // c (n_upts, n_faces)
+  DevBuf<int> face_ele;            // (n_faces)
+  DevBuf<double> partial;          // (2, n_groups)
+  DevBuf<BodyForceRecord> record;  // one
+  DevBuf<double> ring;             // (3, capacity): mass_flux, ubulk, body_force(1) of the last `capacity` evaluations
+  double h_integral[2] = {};       // several ranks: the integrals on their way through the all-reduce
+};
+} // namespace hfx
+
 struct hfx_eles
 {
   hfx_ctx *ctx = nullptr;
@@ -302,6 +330,8 @@ struct hfx_eles
   int n_average_fields = 0;
   int average_codes[HFX_MAX_AVERAGE_FIELDS] = {};
   hfx::DevBuf<double> disu_average_upts, disu_average_ppts;
+  // mass-flux body force (hfx_eles_set_body_force); null: none registered
+  std::unique_ptr<hfx::BodyForce> body_force;
   // over-integration (hfx_eles_set_over_int)
   bool over_int_ready = false;
   int n_cubpts = 0;
@@ -419,6 +449,12 @@ void advance_ramp_counters(hfx_inters *const *faces, int nfb);
 // clock is the library's: time += dt, i_steps++, spinup_time at step 1, then the time averages of every block that has average
 // fields (averages.hip).  Nothing for a context without a clock; no launch for a block without average fields
 int end_of_step(hfx_eles *const *eles, int neb);
+// the `forcing == 1` branch at the first RK stage of a step (src/solver.cpp:96-109): eles::evaluate_body_force of every block that
+// has a body force registered (forcing.hip) -- three launches per such block and, without `comm`, nothing else: no copy, no
+// synchronisation.  With `comm` (the partitioned loops) the two integrals are summed over its ranks between the first and the
+// second kernel by the path of hfx_comm_allreduce: one host round trip per step.  Called behind the loop's calc_time_step: the
+// controller takes params.dt of this step.  Nothing, and no launch, for blocks without a body force
+int begin_of_step(hfx_eles *const *eles, int neb, hfx_comm *comm);
 // RK stages per time step of adv_type (src/HiFiLES.cpp:143-150)
 inline int n_rk_stages(int adv_type) { return (adv_type == 0) ? 1 : (adv_type <= 2) ? 4 : (adv_type == 3) ? 5 : 14; }
 inline int n_rk_stages(const hfx_params &p) { return n_rk_stages(p.adv_type); }

@@ -61,6 +61,9 @@ extern "C" int hfxh_case_create(const hfxh_case_desc *d, hfxh_case **out)
     in.loc_1d_upts_override.setup(d->order + 1);
     for (int i = 0; i <= d->order; i++) in.loc_1d_upts_override(i) = d->loc_1d_upts[i];
   }
+  in.forcing = d->body_forcing;
+  if (d->forcing_area != 0.0) in.forcing_area = d->forcing_area;
+  if (d->forcing_mdot0 != 0.0) in.forcing_mdot0 = d->forcing_mdot0;
   if (in.setup_params(g_err)) { delete c; return 1; }
   for (int i = 0; i < d->n_bcs; i++)
   {
@@ -172,6 +175,21 @@ extern "C" int hfxh_case_get_array(hfxh_case *c, const char *name, const double 
   else if (n == "div_tconf_upts") a = &E->div_tconf_upts(0);
   else if (n == "grad_disu_upts") a = &E->grad_disu_upts;
   else if (n == "h_ref") a = &E->h_ref;
+  // surface cubature of local face l (body forcing): <name>_<l>
+  else if (n.size() > 2 && n[n.size() - 2] == '_' && E->n_cubpts_per_inter.get_dim(0) == E->n_inters_per_ele)
+  {
+    const int l = n.back() - '0';
+    const std::string base = n.substr(0, n.size() - 2);
+    if (l >= 0 && l < E->n_inters_per_ele)
+    {
+      if (base == "opp_inters_cubpts") a = &E->opp_inters_cubpts(l);
+      else if (base == "weight_inters_cubpts") a = &E->weight_inters_cubpts(l);
+      else if (base == "loc_inters_cubpts") a = &E->loc_inters_cubpts(l);
+      else if (base == "tnorm_inters_cubpts") a = &E->tnorm_inters_cubpts(l);
+      else if (base == "inter_detjac_inters_cubpts") a = &E->inter_detjac_inters_cubpts(l);
+      else if (base == "norm_inters_cubpts") a = &E->norm_inters_cubpts(l);
+    }
+  }
   if (!a) { g_err = "hfxh_case_get_array: unknown array " + n; return 1; }
   *ptr = a->get_ptr_cpu();
   for (int i = 0; i < 4; i++) dims[i] = a->get_dim(i);
@@ -415,6 +433,59 @@ extern "C" int hfxh_case_get_clock(hfxh_case *c, double *time, int *i_steps, dou
   if (time) *time = c->S.time;
   if (i_steps) *i_steps = c->S.i_steps;
   if (spinup_time) *spinup_time = c->S.run_input.spinup_time;
+  return 0;
+}
+
+// ---- mass-flux body force ------------------------------------------------------------------------------------------------
+extern "C" int hfxh_case_get_forcing(hfxh_case *c, int *body_forcing, double *forcing_area, double *forcing_mdot0)
+{
+  const input &in = c->S.run_input;
+  if (body_forcing) *body_forcing = in.forcing;
+  if (forcing_area) *forcing_area = in.forcing_area;
+  if (forcing_mdot0) *forcing_mdot0 = in.forcing_mdot0;
+  return 0;
+}
+
+extern "C" int hfxh_case_set_forcing(hfxh_case *c, double forcing_area, double forcing_mdot0)
+{
+  input &in = c->S.run_input;
+  if (in.forcing != 1 || c->S.n_dims != 3) { g_err = "hfxh_case_set_forcing: the case was not made with body_forcing 1 in three dimensions"; return 1; }
+  in.forcing_area = forcing_area;
+  in.forcing_mdot0 = forcing_mdot0;
+  eles *E = the_eles(c);
+  if (E->register_body_force()) { g_err = E->last_error(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_set_reduce_sum(hfxh_case *c, hfxh_reduce_sum_cb fn, void *user)
+{
+  SetReduceSum(&c->S, fn, user);
+  return 0;
+}
+
+extern "C" int hfxh_case_get_inflow_faces(hfxh_case *c, const int **ele, const int **inter, int *n_faces)
+{
+  eles *E = the_eles(c);
+  *ele = E->inflow_ele.data();
+  *inter = E->inflow_inter.data();
+  *n_faces = (int)E->inflow_ele.size();
+  return 0;
+}
+
+extern "C" int hfxh_case_body_force_state(hfxh_case *c, double *mass_flux, double *ubulk, double *body_force_x, double accumulated[2],
+                                          double integral[2], long *n_steps)
+{
+  eles *E = the_eles(c);
+  if (!E->device()) { g_err = "case is not on the device"; return 1; }
+  if (hfx_eles_body_force_state(E->device(), mass_flux, ubulk, body_force_x, accumulated, integral, n_steps)) { g_err = hfx_last_error(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_body_force_history(hfxh_case *c, int max_rows, double *rows, int *n_rows)
+{
+  eles *E = the_eles(c);
+  if (!E->device()) { g_err = "case is not on the device"; return 1; }
+  if (hfx_eles_body_force_history(E->device(), max_rows, rows, n_rows)) { g_err = hfx_last_error(); return 1; }
   return 0;
 }
 

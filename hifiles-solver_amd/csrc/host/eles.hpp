@@ -60,6 +60,29 @@ public:
   void calc_time_average_ppts(int in_ele, hf_array<double> &out_disu_average_ppts); // src/eles.cpp:3820, the per-element accessor
   hf_array<double> disu_average_upts, disu_average_ppts;
   double compute_res_upts(int in_norm_type, int in_field);
+  // ---- surface cubature and the mass-flux body force (run_input->forcing; csrc/host/eles_forcing.cpp).  Built by set_transforms
+  // only when forcing is on, like the reference (src/eles.cpp:4023); for EVERY element, where the reference keeps them for its
+  // boundary elements only (bdy_ele2ele): the second index of the per-element arrays is the element
+  hf_array<int> n_cubpts_per_inter;
+  hf_array<hf_array<double>> loc_inters_cubpts, weight_inters_cubpts, tnorm_inters_cubpts; // (n_dims, n_cubpts) | (n_cubpts) | (n_dims, n_cubpts)
+  hf_array<hf_array<double>> opp_inters_cubpts;                                            // (n_cubpts, n_upts)
+  hf_array<hf_array<double>> inter_detjac_inters_cubpts, norm_inters_cubpts;               // (n_cubpts, n_eles) | (n_cubpts, n_eles, n_dims)
+  virtual int set_inters_cubpts();                // the class's face cubature rule (src/eles_hexas.cpp:284-373); hexahedra only here
+  void set_opp_inters_cubpts();                   // src/eles.cpp:3635-3665
+  void set_transforms_inters_cubpts();            // src/eles.cpp:4480-4595
+  virtual double compute_inter_detjac_inters_cubpts(int in_inter, const hf_array<double> &d_pos) { return 0.0; }
+  // cyclic_inter(ele, l) = 1: local face l of the element lies on a cyclic boundary group of the mesh (set by the mesh setup: the
+  // reference asks run_input.bc_list(bcid(ele, l)), src/eles.cpp:5322)
+  hf_array<int> cyclic_inter;
+  // the reference's inflow rule (src/eles.cpp:5312-5338): cyclic, and the x-component of the unit normal at the first cubature
+  // point == -1 exactly -> inflow_ele / inflow_inter, elements ascending, local faces ascending
+  void set_inflow_inters();
+  std::vector<int> inflow_ele, inflow_inter;
+  int register_body_force();                 // -> hfx_eles_set_body_force with run_input's forcing_area / forcing_mdot0 (resets the controller)
+  void evaluate_body_force(int in_file_num); // src/eles.cpp:5281: one evaluation on the device
+  // its two halves around the sum over the ranks (src/eles.cpp:5375-5385), for the transports of solution::comm / reduce_sum
+  int body_force_integrals(double integral[2]);
+  int body_force_apply(const double integral[2]);
 
   // ---- getters used by face wiring (src/eles.cpp:4638-4949 return pointers; here: offsets)
   int get_n_eles() const { return n_eles; }
@@ -149,6 +172,10 @@ protected:
 
 class eles_hexas : public eles
 {
+public:
+  int set_inters_cubpts() override;
+  double compute_inter_detjac_inters_cubpts(int in_inter, const hf_array<double> &d_pos) override; // src/eles_hexas.cpp:395
+
 protected:
   int setup_ele_type_specific() override;
   double eval_nodal_basis(int in_index, const hf_array<double> &in_loc) override;

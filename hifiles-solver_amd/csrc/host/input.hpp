@@ -52,6 +52,12 @@ struct input
   int set_average_fields(const std::vector<std::string> &names, int n_dims, std::string &err);
   // HFX_AVG_* of average_fields(i)
   int average_code(int i) const;
+  // ---- mass-flux body force of periodic channels (`body_forcing`, src/input.cpp:312).  forcing_area and forcing_mdot0 are keys of
+  // this mirror: the inflow area and the target mass flux, which the reference hard-codes to 9.162 both (src/eles.cpp:5393-5395);
+  // forcing_history: evaluations whose massflux.dat columns the device keeps
+  int forcing = 0;
+  double forcing_area = 9.162, forcing_mdot0 = 9.162;
+  int forcing_history = 4096;
   // ---- element parameters
   int upts_type_hexa = 0, vcjh_scheme_hexa = 1;
   double eta_hexa = 0.0;

@@ -165,6 +165,23 @@ int GeoPreprocess_box(solution *S, const box_mesh &mesh)
             }
       }
   if (E->set_transforms()) { S->err = E->last_error(); return 1; }
+  // the faces on a cyclic boundary group of the mesh: those whose neighbour lies beyond an end of the GLOBAL box in a periodic
+  // direction; then the inflow faces of the mass-flux body force (src/eles.cpp:5312-5338)
+  if (in.forcing == 1 && dims == 3)
+  {
+    const int nnc[3] = {nx, ny, nz};
+    E->cyclic_inter.setup(E->n_eles, nfaces_loc);
+    for (int k = 0; k < nz; k++)
+      for (int j = 0; j < ny; j++)
+        for (int i = 0; i < nx; i++)
+          for (int f = 0; f < nfaces_loc; f++)
+          {
+            const int d = hex_face[f][0], c[3] = {i, j, k};
+            const int gc = c[d] + mesh.pcoord[d] * nnc[d] + hex_face[f][1];
+            E->cyclic_inter(i + nx * (j + ny * k), f) = periodic[d] && (gc < 0 || gc >= nnc[d] * mesh.pgrid[d]);
+          }
+    E->set_inflow_inters();
+  }
   // global element numbers (src/geometry.cpp: ele2global_ele): x-fastest over the GLOBAL box
   E->ele2global_ele.setup(E->n_eles);
   {
@@ -465,10 +482,46 @@ int SetDeferred(solution *S, bool on)
   return 0;
 }
 
+// eles::evaluate_body_force of every class (src/solver.cpp:105-108).  One rank: on the device from end to end.  Several: each
+// class's integrals are summed over the ranks (src/eles.cpp:5375-5385) by the library's communicator or the caller's hook
+static bool forcing_on(const solution *FlowSol)
+{
+  return FlowSol->run_input.forcing == 1 && FlowSol->run_input.equation == 0 && FlowSol->n_dims == 3;
+}
+static int forcing_has_transport(solution *FlowSol, const char *who)
+{
+  if (!forcing_on(FlowSol) || FlowSol->nproc == 1 || FlowSol->comm || FlowSol->reduce_sum) return 0;
+  FlowSol->err = std::string(who) + ": the body force on more than one rank needs a SUM reduction over the ranks (SetComm or SetReduceSum)";
+  return 1;
+}
+static void evaluate_body_force_all(int in_file_num, solution *FlowSol)
+{
+  for (int i = 0; i < FlowSol->n_ele_types; i++)
+  {
+    eles *E = FlowSol->mesh_eles(i);
+    if (!E) continue;
+    if (FlowSol->nproc == 1) { E->evaluate_body_force(in_file_num); continue; }
+    double v[2];
+    if (E->body_force_integrals(v)) continue;
+    if (FlowSol->comm)
+    {
+      if (hfx_comm_allreduce(FlowSol->comm, v, 2, 2)) { FlowSol->err = hfx_last_error(); continue; }
+    }
+    else if (FlowSol->reduce_sum)
+      FlowSol->reduce_sum(FlowSol->reduce_sum_user, v, 2);
+    E->body_force_apply(v);
+  }
+}
+
 // ---- the stage scheduler: same call order as the reference --------------------------------
-void CalcResidual(int /*in_file_num*/, int in_rk_stage, solution *FlowSol)
+void CalcResidual(int in_file_num, int in_rk_stage, solution *FlowSol)
 {
   int i;
+  // the mass-flux body force of periodic channels (src/solver.cpp:96-109), under the reference's condition but at the TOP of the
+  // stage: nothing between here and the reference's position changes disu_upts(0) or src_upts, and with deferred execution the
+  // call then makes exactly the previous, complete stage run instead of cutting this one in half.  (The SVV closure, which
+  // replaces the state below, would be the exception: the force then sees the unfiltered state.)
+  if (forcing_on(FlowSol) && in_rk_stage == 0) evaluate_body_force_all(in_file_num, FlowSol);
   // 0: closures that filter the solution do so once per time step, at its first stage (src/solver.cpp:55-62)
   if (FlowSol->run_input.LES && FlowSol->run_input.SGS_model >= 2 && in_rk_stage == 0)
     for (i = 0; i < FlowSol->n_ele_types; i++)
@@ -602,6 +655,7 @@ static void count_step_and_average(solution *FlowSol)
 int RunSteps(solution *FlowSol, int n_steps)
 {
   const int RKSteps = FlowSol->run_input.n_rk_stages();
+  if (forcing_has_transport(FlowSol, "RunSteps")) return 1;
   for (int i_steps = 0; i_steps < n_steps; i_steps++)
   {
     if (calc_time_step(FlowSol)) return 1; /* src/HiFiLES.cpp:198 */
@@ -654,6 +708,12 @@ void SetExchange(solution *FlowSol, hfxh_exchange_fn fn, void *user)
   FlowSol->exchange = fn;
   FlowSol->exchange_user = user;
   for (int j = 0; j < FlowSol->n_mpi_inter_types; j++) FlowSol->mesh_mpi_inters(j).set_exchange(fn, user);
+}
+
+void SetReduceSum(solution *FlowSol, void (*fn)(void *user, double *v, int n), void *user)
+{
+  FlowSol->reduce_sum = fn;
+  FlowSol->reduce_sum_user = user;
 }
 
 void SetReduceMin(solution *FlowSol, double (*fn)(void *user, double v), void *user)
@@ -746,6 +806,7 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
     in.time = FlowSol->time;
     return 0;
   }
+  if (forcing_has_transport(FlowSol, "RunStepsPartitionedFused")) return 1;
   const int RKSteps = in.n_rk_stages();
   const bool ex = !fm.empty() && FlowSol->exchange;
   auto phase = [&](int ph, int stage, int first) {
@@ -759,6 +820,12 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
   for (int i_steps = 0; i_steps < n_steps; i_steps++)
   {
     if (calc_time_step(FlowSol)) return 1; /* src/HiFiLES.cpp:198 */
+    if (forcing_on(FlowSol)) /* src/solver.cpp:96-109 */
+    {
+      evaluate_body_force_all(FlowSol->ini_iter + i_steps, FlowSol);
+      if (E->failed()) { FlowSol->err = E->last_error(); return 1; }
+      if (!FlowSol->err.empty()) return 1;
+    }
     for (int i = 0; i < RKSteps; i++)
     {
       if (first)

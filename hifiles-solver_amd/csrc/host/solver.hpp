@@ -1,7 +1,7 @@
 // solver.hpp -- `struct solution`, the stage scheduler CalcResidual and the box-mesh setup.
 //
 // struct solution mirrors /root/reference/include/solution.h:44-96; CalcResidual has the
-// call order of /root/reference/src/solver.cpp:50-223 (single rank, LES / RANS / forcing off)
+// call order of /root/reference/src/solver.cpp:50-223 (RANS off)
 // and calls only the public eles / int_inters methods, like the reference's.
 #pragma once
 #include <string>
@@ -35,6 +35,8 @@ struct solution
   void *exchange_user = nullptr;
   double (*reduce_min)(void *user, double v) = nullptr; // MPI_Allreduce(MIN) of calc_time_step, supplied by the caller
   void *reduce_user = nullptr;
+  void (*reduce_sum)(void *user, double *v, int n) = nullptr; // MPI_Allreduce(SUM) of the body force's integrals, supplied by the caller
+  void *reduce_sum_user = nullptr;
   hfx_comm *comm = nullptr; // the library's RCCL transport (SetComm); takes the place of `exchange` and `reduce_min`
   // deferred execution (include/hfx.h): the method calls of CalcResidual + AdvanceSolution below are recorded by libhfx and
   // a whole stage runs as one fused stage -- the call sequence itself is the reference's, unchanged.  On by default.
@@ -90,6 +92,7 @@ int RunSteps(solution *FlowSol, int n_steps);
 int RunStepsPartitionedFused(solution *FlowSol, int n_steps);
 void SetExchange(solution *FlowSol, hfxh_exchange_fn fn, void *user);
 void SetReduceMin(solution *FlowSol, double (*fn)(void *user, double v), void *user);
+void SetReduceSum(solution *FlowSol, void (*fn)(void *user, double *v, int n), void *user);
 // collective: the library's communicator for this rank (id from hfx_comm_get_unique_id on rank 0)
 int SetComm(solution *FlowSol, const char *unique_id);
 // per-phase / per-exchange times of the partitioned fused stage (hfx_time_partitioned)

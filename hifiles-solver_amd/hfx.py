@@ -129,6 +129,23 @@ def fused_launch_grids(eles_handle):
     return [(slot[i], grid[i], work[i]) for i in range(min(n.value, 16))]
 
 
+def body_force_state_of(call):
+    """call(mass_flux*, ubulk*, body_force_x*, accumulated*, integral*, n_steps*) -> the record as a dict"""
+    m, u, f, n = C.c_double(0), C.c_double(0), C.c_double(0), C.c_long(0)
+    acc, integ = (C.c_double * 2)(), (C.c_double * 2)()
+    call(C.byref(m), C.byref(u), C.byref(f), acc, integ, C.byref(n))
+    return {"mass_flux": m.value, "ubulk": u.value, "body_force_x": f.value, "accumulated": np.array(list(acc)),
+            "integral": np.array(list(integ)), "n_steps": n.value}
+
+
+def body_force_history_of(call, max_rows):
+    """call(max_rows, rows*, n_rows*) -> (n, 3) array of (mass_flux, ubulk, body_force(1)), oldest first"""
+    rows = np.zeros((3, max(1, max_rows)), dtype=np.float64, order="F")
+    n = C.c_int(0)
+    call(C.c_int(max_rows), rows.ctypes.data_as(dp), C.byref(n))
+    return rows[:, :n.value].T.copy()
+
+
 class Context:
     def __init__(self, device=0):
         self.h = C.c_void_p()
@@ -276,6 +293,44 @@ class Eles:
         out = np.zeros((self.n_ppts, self.n_eles, self.n_average_fields), dtype=np.float64, order="F")
         check(lib().hfx_eles_calc_time_average_ppts(self.h, out.ctypes.data_as(dp)))
         return out
+
+    def set_body_force(self, face_ele, face_inter, opp_inters_cubpts, weight_inters_cubpts, inter_detjac_inters_cubpts, area, mdot0,
+                       history_capacity=64):
+        """hfx_eles_set_body_force.  face_ele, face_inter: the inflow faces as (element, local face); opp_inters_cubpts[l]
+        (n_cubpts, n_upts) and weight_inters_cubpts[l] (n_cubpts) per local face l (None for faces nobody names);
+        inter_detjac_inters_cubpts: one array of n_cubpts values per listed face, in list order."""
+        fe = np.ascontiguousarray(np.array(face_ele, dtype=np.int32).ravel())
+        fl = np.ascontiguousarray(np.array(face_inter, dtype=np.int32).ravel())
+        nl = len(opp_inters_cubpts)
+        opp = [None if a is None else _f(a) for a in opp_inters_cubpts]
+        wgt = [None if a is None else np.ascontiguousarray(np.array(a, dtype=np.float64).ravel()) for a in weight_inters_cubpts]
+        ncub = (C.c_int * max(1, nl))(*[0 if a is None else a.shape[0] for a in opp])
+        po = (dp * max(1, nl))(*[None if a is None else a.ctypes.data_as(dp) for a in opp])
+        pw = (dp * max(1, nl))(*[None if a is None else a.ctypes.data_as(dp) for a in wgt])
+        dj = np.ascontiguousarray(np.concatenate([np.array(a, dtype=np.float64).ravel() for a in inter_detjac_inters_cubpts])
+                                  if len(fe) else np.zeros(1))
+        check(lib().hfx_eles_set_body_force(self.h, C.c_int(len(fe)), fe.ctypes.data_as(ip), fl.ctypes.data_as(ip), C.c_int(nl), ncub,
+                                            po, pw, dj.ctypes.data_as(dp), C.c_double(area), C.c_double(mdot0),
+                                            C.c_int(history_capacity)))
+
+    def clear_body_force(self): self._call("hfx_eles_clear_body_force")
+    def evaluate_body_force(self): self._call("hfx_eles_evaluate_body_force")
+
+    def body_force_integrals(self):
+        v = (C.c_double * 2)()
+        check(lib().hfx_eles_body_force_integrals(self.h, v))
+        return [v[0], v[1]]
+
+    def body_force_apply(self, integral):
+        check(lib().hfx_eles_body_force_apply(self.h, (C.c_double * 2)(*[float(x) for x in integral])))
+
+    def body_force_state(self):
+        """dict(mass_flux, ubulk, body_force_x, accumulated (2), integral (2), n_steps); raises on the NaN flag"""
+        return body_force_state_of(lambda *a: check(lib().hfx_eles_body_force_state(self.h, *a)))
+
+    def body_force_history(self, max_rows=64):
+        """(n, 3): mass_flux, ubulk, body_force(1) of the newest evaluations, oldest first"""
+        return body_force_history_of(lambda *a: check(lib().hfx_eles_body_force_history(self.h, *a)), max_rows)
 
     def extrapolate_solution(self): self._call("hfx_eles_extrapolate_solution")
     def calculate_gradient(self): self._call("hfx_eles_calculate_gradient")

@@ -29,7 +29,8 @@ class CaseDesc(C.Structure):
                 ("over_int", C.c_int), ("over_int_order", C.c_int), ("shock_cap", C.c_int), ("shock_det_field", C.c_int),
                 ("s0", C.c_double), ("expf_fac", C.c_double), ("expf_order", C.c_int), ("expf_cutoff", C.c_int),
                 ("LES", C.c_int), ("SGS_model", C.c_int), ("C_s", C.c_double), ("filter_ratio", C.c_double),
-                ("prandtl_t", C.c_double), ("p_res", C.c_int), ("self_partition", C.c_int * 3), ("filter_type", C.c_int)]
+                ("prandtl_t", C.c_double), ("p_res", C.c_int), ("self_partition", C.c_int * 3), ("filter_type", C.c_int),
+                ("body_forcing", C.c_int), ("forcing_area", C.c_double), ("forcing_mdot0", C.c_double)]
 
 
 class BcDesc(C.Structure):
@@ -46,6 +47,7 @@ SIDES2 = ("y-", "x+", "y+", "x-")
 
 EXCHANGE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int)
 REDUCE_MIN_CB = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double)
+REDUCE_SUM_CB = C.CFUNCTYPE(None, C.c_void_p, dp, C.c_int)
 
 
 # the shipped Taylor-Green case (/root/reference/testcases/navier-stokes/Taylor_Green_vortex/input_TGV_SD_hex)
@@ -369,6 +371,41 @@ class Case:
         t, n, s = C.c_double(0), C.c_int(0), C.c_double(0)
         check(lib().hfxh_case_get_clock(self.h, C.byref(t), C.byref(n), C.byref(s)))
         return t.value, n.value, s.value
+
+    def forcing(self):
+        """(body_forcing, forcing_area, forcing_mdot0) as the case holds them"""
+        on, a, m = C.c_int(0), C.c_double(0), C.c_double(0)
+        check(lib().hfxh_case_get_forcing(self.h, C.byref(on), C.byref(a), C.byref(m)))
+        return on.value, a.value, m.value
+
+    def set_forcing(self, area, mdot0):
+        """new inflow area and target mass flux; on the device this registers again and resets the controller"""
+        check(lib().hfxh_case_set_forcing(self.h, C.c_double(area), C.c_double(mdot0)))
+
+    def set_reduce_sum(self, fn):
+        """fn(list of n doubles) -> their sums over the ranks: the body force's MPI_Allreduce(SUM) when the transport is the caller's"""
+        def cb(user, v, n):
+            out = fn([v[i] for i in range(n)])
+            for i in range(n):
+                v[i] = float(out[i])
+        self._scb = REDUCE_SUM_CB(cb)
+        check(lib().hfxh_case_set_reduce_sum(self.h, self._scb, None))
+
+    def inflow_faces(self):
+        """(elements, local faces) the reference's inflow rule selects"""
+        e, l, n = ip(), ip(), C.c_int(0)
+        check(lib().hfxh_case_get_inflow_faces(self.h, C.byref(e), C.byref(l), C.byref(n)))
+        if n.value == 0:
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
+        return (np.ctypeslib.as_array(e, shape=(n.value,)).copy(), np.ctypeslib.as_array(l, shape=(n.value,)).copy())
+
+    def body_force_state(self):
+        """the controller's record: dict(mass_flux, ubulk, body_force_x, accumulated (2), integral (2), n_steps)"""
+        return hfx.body_force_state_of(lambda *a: check(lib().hfxh_case_body_force_state(self.h, *a)))
+
+    def body_force_history(self, max_rows=4096):
+        """rows (n, 3) of (mass_flux, ubulk, body_force(1)), oldest first: the columns of the reference's massflux.dat"""
+        return hfx.body_force_history_of(lambda *a: check(lib().hfxh_case_body_force_history(self.h, *a)), max_rows)
 
     def close(self):
         if self.h:

@@ -351,6 +351,66 @@ int hfx_eles_CalcTimeAverageQuantities(hfx_eles *e, double time, double spinup_t
  * contraction of hfx_eles_calc_disu_ppts, written to the HOST array the plot writer reads */
 int hfx_eles_calc_time_average_ppts(hfx_eles *e, double *disu_average_ppts_host);
 
+/* ---- mass-flux body force of driven periodic channels (run_input.forcing, src/input.cpp:312) ---------------------------
+ * The `forcing == 1` branch of CalcResidual (src/solver.cpp:96-109): at the first RK stage of every time step
+ * eles::evaluate_body_force (src/eles.cpp:5281-5482) integrates density and x-momentum over the cyclic inflow plane, turns the
+ * mass-flux defect into a streamwise momentum force and an energy force and ADDS them to src_upts (HFX_SRC_UPTS), which every
+ * AdvanceSolution scheme subtracts from the residual.  Here the integral, the controller and the addition are three small
+ * kernels on the compute stream; on one rank an evaluation makes no copy and no host synchronisation.
+ *
+ * hfx_eles_set_body_force registers (src/eles.cpp:5312-5373, 5393-5395):
+ *   face_ele[n_faces], face_inter[n_faces]   the block's inflow faces as (element, local face) pairs -- the faces the reference
+ *       flags at :5312-5338 (cyclic group, x-component of the unit normal at the first cubature point == -1).  n_faces == 0 is
+ *       legal: the block (or rank) then only receives the force
+ *   n_inters_per_ele, and per local face l: n_cubpts_per_inter[l], opp_inters_cubpts[l] (n_cubpts, n_upts),
+ *       weight_inters_cubpts[l] (n_cubpts) -- eles::set_opp_inters_cubpts (src/eles.cpp:3635-3665) and the class's
+ *       set_inters_cubpts; entries of local faces no listed face names may be NULL
+ *   inter_detjac_inters_cubpts   per listed face, in list order, the n_cubpts values of its local face (packed)
+ *       (set_transforms_inters_cubpts, src/eles.cpp:4480-4595)
+ *   area, mdot0   the reference hard-codes 9.162 for both (:5393-5395)
+ *   history_capacity   evaluations whose (mass_flux, ubulk, body_force(1)) -- the columns of massflux.dat -- are kept
+ * The three arrays are folded into one weight per solution point and face, c(k, face) = sum_j w_j detjac(j, face) opp(j, k),
+ * so an evaluation costs a dot product of length n_upts per face and field.  Registering again replaces everything and resets
+ * the controller: what it had added to src_upts is taken out, and the next evaluation uses mdot_old = mdot0, as a fresh or
+ * restarted reference run does (:5398-5403).  Refused: two-dimensional blocks and n_fields != 5 (the reference runs the branch
+ * for n_dims == 3, equation == 0 only), a face outside the block. */
+int hfx_eles_set_body_force(hfx_eles *e, int n_faces, const int *face_ele, const int *face_inter, int n_inters_per_ele,
+                            const int *n_cubpts_per_inter, const double *const *opp_inters_cubpts,
+                            const double *const *weight_inters_cubpts, const double *inter_detjac_inters_cubpts, double area,
+                            double mdot0, int history_capacity);
+/* drops the registration and takes its contribution out of src_upts; no-op without one */
+int hfx_eles_clear_body_force(hfx_eles *e);
+/* eles::evaluate_body_force (src/eles.cpp:5281-5482), ONE evaluation on this rank's faces alone, for callers that drive the stages
+ * themselves (at the first RK stage, before it: nothing between the top of the stage and src/solver.cpp:96 changes
+ * disu_upts(0) or src_upts).  integral(0), integral(1) over the registered faces (fields 2 and 3, which the reference integrates
+ * and never reads, are not) in a fixed summation order -- the same state gives the same bits --, then :5411-5428 with dt =
+ * hfx_params.dt:  ubulk = integral(0) == 0 ? 0 : integral(1) / integral(0);  mass_flux = ubulk * integral(0);
+ * body_force(1) = 1 / area / dt * (mdot0 - 2 mass_flux + mdot_old);  body_force(4) = body_force(1) * ubulk;  mdot_old = mdot0
+ * at the first evaluation after a registration, the previous mass_flux afterwards; then src_upts(., ., k) += body_force(k),
+ * k = 1, 4.  HFX_SRC_UPTS is allocated (zeroed) by the first evaluation when the caller uploaded none; an uploaded source
+ * term keeps its values and the force adds on top (upload it BEFORE the registration: an upload of HFX_SRC_UPTS replaces the
+ * whole array, the controller's contribution included).  dt_type 2 is refused with the reference's message (:5409).
+ * Immediate: with deferred execution the recorded stage runs first.  hfx_run_steps, hfx_run_steps_blocks,
+ * hfx_run_steps_partitioned and hfx_run_steps_partitioned_blocks evaluate every registered block themselves, behind their
+ * calc_time_step and before the first stage of every step; the partitioned ones sum the two integrals over the communicator
+ * (the MPI_Allreduce of :5375-5385; one host round trip per step).  The hfx_time_* entry points never evaluate it. */
+int hfx_eles_evaluate_body_force(hfx_eles *e);
+/* The two halves of an evaluation for a caller whose transport sums over the ranks (the MPI_Allreduce of src/eles.cpp:5375-5385):
+ * hfx_eles_body_force_integrals returns THIS rank's integral(0), integral(1) (zeros for a rank without inflow faces; waits for
+ * the compute stream), the caller adds them over the ranks, hfx_eles_body_force_apply runs the controller and the addition to
+ * src_upts from the sums.  Immediate, like hfx_eles_evaluate_body_force, which is the two in one without leaving the device. */
+int hfx_eles_body_force_integrals(hfx_eles *e, double integral[2]);
+int hfx_eles_body_force_apply(hfx_eles *e, const double integral[2]);
+/* The controller's record after the last evaluation (waits for the compute stream): mass_flux, ubulk, body_force(1),
+ * accumulated[2] = the sums of body_force(1) and body_force(4) since the registration (what src_upts holds of the controller),
+ * integral[2] = integral(0), integral(1) (over all ranks), n_steps = evaluations since the registration.  Any pointer may be
+ * NULL.  Fails with the reference's "ERROR: NaN body force, exiting" (src/eles.cpp:5455-5458) once a body_force(1) was NaN. */
+int hfx_eles_body_force_state(hfx_eles *e, double *mass_flux, double *ubulk, double *body_force_x, double accumulated[2],
+                              double integral[2], long *n_steps);
+/* the newest min(max_rows, history_capacity, n_steps) rows (mass_flux, ubulk, body_force(1)) -- what the reference appends to
+ * massflux.dat (src/eles.cpp:5445-5451) --, oldest first: rows (3, *n_rows).  max_rows == 0 asks for the number alone */
+int hfx_eles_body_force_history(hfx_eles *e, int max_rows, double *rows, int *n_rows);
+
 /* ---- CFL time stepping (calc_time_step, src/solver.cpp:484-549) ---------- */
 int hfx_eles_set_h_ref(hfx_eles *e, const double *h_ref); /* eles::h_ref (n_eles), src/eles.cpp:3985 */
 /* dt_local(ic) = eles::calc_dt_local(ic) (src/eles.cpp:1267-1356) for every element -> HFX_DT_LOCAL, and the
@@ -407,7 +467,9 @@ int hfx_bdy_inters_evaluate_boundaryConditions_viscFlux(hfx_inters *f, double ti
 
 /* ---- the caller contract ---------------------------------------------- */
 /* CalcResidual (src/solver.cpp:50-223) for one element block and its interior and boundary
- * face blocks (any mix, in `faces`), LES / RANS / forcing off; same call order as the reference. */
+ * face blocks (any mix, in `faces`), RANS off; same call order as the reference.  The `forcing == 1` branch
+ * (src/solver.cpp:96-109) is not in here: a caller that drives the stages itself calls hfx_eles_evaluate_body_force at the
+ * first RK stage of a step, the hfx_run_steps* loops do so themselves (see "mass-flux body force" above). */
 int hfx_CalcResidual(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks);
 /* The same for a MIXED mesh: several element blocks (the reference's mesh_eles(i), one per element class) and face blocks
  * whose left and right sides may belong to different element blocks (int_inters::set_interior is called with
@@ -542,6 +604,10 @@ int hfx_time_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, h
  * The state advances by reps stages (stage index cycles through the scheme). */
 #define HFX_N_TIMED_METHODS 11
 int hfx_time_methods(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int reps, double ms[HFX_N_TIMED_METHODS]);
+/* The three kernels of one evaluation of the body force (hfx_eles_evaluate_body_force), each between two HIP events:
+ * ms[0] mass_flux_kernel, ms[1] body_force_kernel, ms[2] add_body_force_kernel, averaged over `reps` evaluations -- which do
+ * take place: the controller and src_upts advance by reps evaluations. */
+int hfx_time_body_force_kernels(hfx_eles *e, int reps, double ms[3]);
 /* The same for the kernels of the fused path: ms[8] (unused entries 0), names = comma-separated
  * kernel names (buffer of 256 chars); the state advances by reps stages. */
 int hfx_time_fused_kernels(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int reps, double ms[8], char names[256]);

@@ -86,6 +86,14 @@ typedef struct hfxh_case_desc
    * filter_type 0 high-order-commuting Vasilyev, 1 discrete Gaussian, 2 modal, other: average (src/input.cpp:173,
    * src/eles_hexas.cpp:583-790, src/eles_quads.cpp:428-622; the mirror builds filter_upts in csrc/host/eles_modal.cpp) */
   int filter_type;
+  /* the mass-flux body force of periodic channels: `body_forcing` (src/input.cpp:312; 1: on, three-dimensional cases), and two
+   * keys of this mirror, forcing_area and forcing_mdot0 -- the inflow area and the target mass flux, which the reference
+   * hard-codes (src/eles.cpp:5393-5395); 0: its value, 9.162.  The mirror then builds the surface cubature of the hexahedra
+   * (set_inters_cubpts, set_opp_inters_cubpts, set_transforms_inters_cubpts), selects the inflow faces by the reference's rule
+   * (cyclic group, x-component of the unit normal at the first cubature point == -1; src/eles.cpp:5312-5338), registers them
+   * with hfx_eles_set_body_force, and CalcResidual evaluates the force at the first RK stage of every step. */
+  int body_forcing;
+  double forcing_area, forcing_mdot0;
 } hfxh_case_desc;
 
 const char *hfxh_last_error(void);
@@ -209,6 +217,24 @@ int hfxh_case_get_averages(hfxh_case *c, const double **out, int dims[3]);
 int hfxh_case_calc_time_average_ppts(hfxh_case *c, const double **out, int dims[3]);
 /* FlowSol.time, i_steps (time steps of this run; a restart read resets it) and run_input.spinup_time; any pointer may be NULL */
 int hfxh_case_get_clock(hfxh_case *c, double *time, int *i_steps, double *spinup_time);
+
+/* ---- mass-flux body force (hfxh_case_desc.body_forcing) ------------------------------------------------------------------
+ * the surface cubature is read with hfxh_case_get_array: opp_inters_cubpts_<l>, weight_inters_cubpts_<l>, loc_inters_cubpts_<l>,
+ * tnorm_inters_cubpts_<l>, inter_detjac_inters_cubpts_<l> (n_cubpts, n_eles), norm_inters_cubpts_<l> (n_cubpts, n_eles, n_dims)
+ * for local face l -- per ELEMENT, where the reference keeps them per boundary element */
+int hfxh_case_get_forcing(hfxh_case *c, int *body_forcing, double *forcing_area, double *forcing_mdot0);
+/* new forcing_area / forcing_mdot0; a case on the device registers again, which resets its controller (hfx_eles_set_body_force) */
+int hfxh_case_set_forcing(hfxh_case *c, double forcing_area, double forcing_mdot0);
+/* MPI_Allreduce(SUM) hook of eles::evaluate_body_force (src/eles.cpp:5375-5385) on more than one rank when the transport is
+ * the caller's: fn(user, v, n) replaces v[n] by its sum over the ranks.  With hfxh_case_set_comm the library's communicator sums. */
+typedef void (*hfxh_reduce_sum_cb)(void *user, double *v, int n);
+int hfxh_case_set_reduce_sum(hfxh_case *c, hfxh_reduce_sum_cb fn, void *user);
+/* the inflow faces the reference's rule selects, elements ascending: (element, local face) */
+int hfxh_case_get_inflow_faces(hfxh_case *c, const int **ele, const int **inter, int *n_faces);
+/* hfx_eles_body_force_state / hfx_eles_body_force_history of the case's block */
+int hfxh_case_body_force_state(hfxh_case *c, double *mass_flux, double *ubulk, double *body_force_x, double accumulated[2],
+                               double integral[2], long *n_steps);
+int hfxh_case_body_force_history(hfxh_case *c, int max_rows, double *rows, int *n_rows);
 
 #ifdef __cplusplus
 }
