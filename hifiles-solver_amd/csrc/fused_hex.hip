@@ -595,6 +595,27 @@ static int fused_build(hfx_eles *e, hfx_inters *const *faces, int nfb, bool allo
     }
     F->nbr.reset();
     if (fits && F->nbr.upload(nbr)) return 1;
+    // two-wave flux kernel: what every local face's would-be left-over points ask of Fn (FusedData::tw_need)
+    F->tw_counted = false;
+    const int n_left = nfp - 128, npf = nfp / (2 * nd);
+    if (fits && nd == 3 && n_left > 0 && n_left <= npf)
+    {
+      for (auto &row : F->tw_need)
+        for (long &c : row) c = 0;
+      for (long el = 0; el < e->n_eles; el++)
+        for (int face = 0; face < 2 * nd; face++)
+        {
+          int code = 0;
+          for (int j = 0; j < n_left; j++)
+          {
+            const int nb = nbr[(long)nfp * el + npf * face + j];
+            // weight of this side's Fn: 1/2 + beta on the pair's left side, 1/2 - beta on its right, beta's sign flipped with bit1
+            code |= nb < 0 ? 1 : ((((nb & 1) ^ ((nb >> 1) & 1)) == 0) ? 2 : 4);
+          }
+          F->tw_need[face][code]++;
+        }
+      F->tw_counted = true;
+    }
   }
   if (F->disu_alt.ensure((size_t)plane_f * e->n_fields)) return 1;
   F->built = true;
@@ -648,6 +669,45 @@ struct LoaderWaveLaunch<ND, N, OI, GA, LES, true, AFF>
     hipLaunchKernelGGL((split_flux_tensor_kernel<ND, N, 2, true, OI, true, GA, LES, AFF>), dim3(grid), dim3(TB), 0, st, e2, coef, idx);
   }
 };
+
+// Two-wave flux kernel: how many elements of the block need the projected viscous flux of one of the left-over points when these
+// lie on local face f (need[f], from the partner words counted in fused_build and the run's ldg_beta: the kernel's own test of
+// `needed`), and the face that asks least often (the lowest of equals) -- the left-over points go there
+static int two_wave_face(const FusedData *F, double ldg_beta, long need[6])
+{
+  int best = 0;
+  for (int f = 0; f < 6; f++)
+  {
+    need[f] = 0;
+    for (int code = 1; code < 8; code++)
+      if ((code & 1) || ((code & 2) && 0.5 + ldg_beta != 0.0) || ((code & 4) && 0.5 - ldg_beta != 0.0)) need[f] += F->tw_need[f][code];
+    if (need[f] < need[best]) best = f;
+  }
+  return best;
+}
+
+// launch of the two-wave form, instantiated only for the element size it is written for (TwoWave::fits)
+template <int ND, int N, bool FITS>
+struct TwoWaveLaunch
+{
+  static void go(const hfx_eles *, int, hipStream_t, const Split2Args &, const double *, const int *, int) {}
+};
+template <int ND, int N>
+struct TwoWaveLaunch<ND, N, true>
+{
+  static void go(const hfx_eles *e, int per_cu, hipStream_t st, const Split2Args &e2, const double *coef, const int *idx, int face)
+  {
+    constexpr int TB = TwoWave<ND, N>::TB;
+    int grid = element_grid<split_flux_two_wave_kernel<ND, N>>(e, TB, per_cu);
+    if (e2.ele_list != nullptr) grid = (int)std::max<long>(1, std::min<long>(grid, e2.n_list));
+    grid = persistent_grid(e, SLOT_ELEMENT, e2.ele_list != nullptr ? e2.n_list : (long)e->n_eles, grid);
+    hipLaunchKernelGGL((split_flux_two_wave_kernel<ND, N>), dim3(grid), dim3(TB), 0, st, e2, coef, idx, TwoWave<ND, N>::rotation(face));
+  }
+};
+static bool two_wave_fits_rt(int nd, int N)
+{
+  return nd == 3 && N == 5 && TwoWave<3, 5>::fits;
+}
 
 // The squared length scale of the eddy-viscosity closures at every solution point (les_len2_upload, hfx.hip): the flux kernel
 // reads it instead of evaluating a cube root per point and stage.
@@ -724,6 +784,8 @@ SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int r
   // LES closure) has an AFF instantiation for every element size the loader wave fits; the update kernel follows it.
   // Every other form keeps the per-point metrics.
   p.affine = v3 && F && F->affine && opt.affine_metrics && p.flux == FluxForm::loader_wave && p.gather && !oi && !p.les;
+  // ... and on P4 hexahedra, whose loader-wave form has four waves, the affine form runs as two-wave workgroups
+  p.two_wave = p.affine && opt.flux_two_wave && two_wave_fits_rt(e->n_dims, N) && F->tw_counted;
 
   // a partitioned block: variant 3 sends the projected viscous flux; element lists for the flux kernel without over-integration
   // (which runs on all elements first), for the update without shock capturing (whose filter follows the whole update)
@@ -741,7 +803,7 @@ SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int r
   else if (F && F->affine)
     // (no launch of its own: the flux and update kernels read the per-element metric record | the block was found affine, but the form
     // that runs keeps the per-point metrics)
-    p.extra_names = p.affine ? ",affine_metrics" : ",affine_block";
+    p.extra_names = p.two_wave ? ",affine_metrics,two_wave" : p.affine ? ",affine_metrics" : ",affine_block";
   return p;
 }
 
@@ -907,7 +969,12 @@ struct SplitStageT final : SplitStage
   {
     constexpr bool fits = loader_wave_fits<ND, N>();
     static_assert(!fits || loader_wave_fits<ND, N, true>(), "the affine form fits wherever the loader wave does");
-    if (pl.affine)
+    if (pl.two_wave)
+    {
+      long need[6];
+      if constexpr (!OI && !LES) TwoWaveLaunch<ND, N, TwoWave<ND, N>::fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx, two_wave_face(F, P.ldg_beta, need));
+    }
+    else if (pl.affine)
     {
       if constexpr (!OI && !LES) LoaderWaveLaunch<ND, N, false, true, false, fits, true>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx);
     }
@@ -1206,6 +1273,15 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
     fprintf(stderr, "   (wait state | bar1 | issue state, wait metrics | bar2 | bar3 | issue metrics | bar4)  total %lld\n", h[3 * 16 + 7] - h[3 * 16]);
   }
   snprintf(names, names_len, "%s%s", pl.names, pl.extra_names);
+  return 0;
+}
+
+int split_two_wave_face(hfx_eles *e, hfx_inters *const *faces, int nfb, int variant, int *face, long need[6])
+{
+  if (ensure_fused_tables(e, faces, nfb, false)) return 1;
+  const SplitPlan pl = split_plan(e, faces, nfb, variant);
+  for (int f = 0; f < 6; f++) need[f] = 0;
+  *face = pl.two_wave ? two_wave_face(e->fused.get(), e->ctx->params.ldg_beta, need) : -1;
   return 0;
 }
 

@@ -12,6 +12,9 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
 // average duration (ms, HIP events on the context stream) of each kernel of the stage over `reps` stages
 int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps, double *ms, char *names, int names_len,
                        int variant = 2);
+// the local face that holds the left-over flux points of the two-wave flux kernel on this block (-1: the form does not run), and
+// per local face the elements that would need the projected viscous flux of a left-over point there
+int split_two_wave_face(hfx_eles *e, hfx_inters *const *faces, int nfb, int variant, int *face, long need[6]);
 // algorithmic HBM bytes per launch of each kernel, same order
 void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant = 2);
 // what the split stage runs on a block when `requested_variant` (2 or 3) is asked for (split_common.hpp): its .variant is 2

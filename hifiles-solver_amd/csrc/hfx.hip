@@ -512,6 +512,7 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value)
   else if (n == "split_flux") o.split_flux = value != 0;
   else if (n == "flux_stamps") o.flux_stamps = value;
   else if (n == "simd_roles") o.simd_roles = value != 0;
+  else if (n == "flux_two_wave") o.flux_two_wave = value != 0;
   else if (n == "les_flux_kernel") o.les_flux_kernel = value != 0;
   else if (n == "bdy_beside") o.bdy_beside = value != 0;
   else if (n == "light_wave_short") o.light_wave_short = value != 0;
@@ -1830,6 +1831,14 @@ int hfx_fused_kernel_bytes(hfx_eles *e, double bytes[8])
   HFX_CHECK(e && bytes, "hfx_fused_kernel_bytes: bad argument");
   split_kernel_bytes(e, bytes, e->ctx->fused_mode);
   return 0;
+}
+
+int hfx_flux_two_wave_face(hfx_eles *e, hfx_inters *const *faces, int nfb, int *face, long need[6])
+{
+  HFX_CHECK(e && face && need, "hfx_flux_two_wave_face: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  HFX_CHECK(e->ctx->have_params, "parameters not set");
+  return split_two_wave_face(e, faces, nfb, e->ctx->fused_mode, face, need);
 }
 
 int hfx_fused_launch_grids(hfx_eles *e, int max_launches, int *slot, int *grid, long *work, int *n_launches)

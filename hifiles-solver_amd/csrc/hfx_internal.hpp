@@ -234,6 +234,7 @@ struct hfx_ctx
     int bdy_beside = 0;         // 1: the fused stages' viscous boundary-face kernels run on a side stream beside the interior-face kernel (measured neutral: off)
     int les_flux_kernel = 1;    // 1: the LES closure is evaluated in the flux kernel of split variant 3 where its loader-wave form runs
     int affine_metrics = 1;     // 1: on an affine block (every element a parallelepiped) the split stage's flux and update kernels read a 34-double metric record per element in place of most per-point metric arrays
+    int flux_two_wave = 1;      // 1: the affine flux kernel of P4 hexahedra as two-wave workgroups, four resident per CU (0: its loader-wave form)
     int general_waves = 0;      // waves per workgroup of the general flux kernel: 0 by the LDS image (4 or 8), else 3, 4 or 8
   } opt;
   hfx::Deferred defer;

@@ -1664,6 +1664,553 @@ __global__ __launch_bounds__((SGeo<ND, N>::TB + (LW ? 64 : 0)), WV) void split_f
   }
 }
 
+// =======================================================================================
+// TWO-WAVE form of the affine flux kernel (P4 hexahedra: the size whose loader-wave form has four waves).
+// The loader-wave form allocates 255 VGPRs for all four of its waves, so a SIMD holds two waves -- and one of the two is
+// a loader or a light wave that issues next to nothing: half of the register file idles.  Here a workgroup is the two
+// HEAVY waves alone (128 threads) and FOUR workgroups are resident per CU: every SIMD carries two heavy waves of
+// different elements, each filling the other's dependency stalls.
+//   * wave w runs the paired point physics on solution points 64 w .. and on 64 flux points; wave 0 also issues the
+//     LDS-DMA of the next element (state, metric record), wave 1 the NLEFT = NFP - 128 flux points without a partner lane
+//     as an extra pass on its lanes 0 .. NLEFT-1: phase A0 (extrapolated solution, LDG correction) always, phase B (the
+//     unpaired flux-point block) under the wave-uniform one-sided-LDG branch.
+//   * lane t owns flux point (t + rot) mod NFP, the left-over ones are (128 + j + rot) mod NFP: the host picks `rot` so
+//     that they are the first NLEFT points of the local face whose Fn the block needs least often (two_wave_face,
+//     fused_hex.hip) -- on a periodic box with |ldg_beta| = 1/2 a face that no element needs, and the pass in phase B is
+//     never taken.
+//   * LDS (<= 40 kB, four workgroups in 160 KiB): ONE state slot, refilled behind the barrier that ends phase A (the last
+//     reader of u) and waited for by wave 0 before barrier 4 -- a lead of phases B and C; the correction region aliases
+//     the work region sA (idle from barrier 4 to barrier 2 of the next element); the 272-byte record, read throughout
+//     phase B, is double-buffered.  Four barriers per element: 1b (corrections written), 2, 3, 4 as in the loader-wave
+//     form; barrier 4 also publishes the next element's slot.
+//   * the 375 pencil items are three rounds of 128, round r = direction r (compile-time strides); phase C takes them in
+//     two batches (the three folded matrices at once would not fit the registers).
+// =======================================================================================
+template <int ND, int N>
+struct TwoWave
+{
+  using G = Geo<ND, N>;
+  static constexpr int TB = 128;
+  static constexpr int NLEFT = G::NFP - TB;      // flux points without a partner lane
+  static constexpr int NPF = G::NFP / (2 * ND);  // flux points of a local face (faces are runs of NPF points)
+  static constexpr int XSTRIDE = NLEFT > 0 ? NLEFT : 1;
+  static constexpr bool fits = ND == 3 && TGeo<ND, N>::SP == TB && G::NU <= TB && NLEFT > 0 && NLEFT <= NPF && NLEFT <= 64 &&
+                               loader_wave_fits<ND, N, true>();
+  // lane -> flux-point rotation that makes the first NLEFT points of local face `face` the left-over ones
+  static constexpr int rotation(int face) { return (NPF * face + NLEFT) % G::NFP; }
+  // LDS doubles: work regions | state slot | two records | 1-D tables (D, Dc, c5, Lf) | parked left-over solution
+  static constexpr int NUS = (G::NU + 1) & ~1, NN2 = (N * N + 1) & ~1, NP = (N + 1) & ~1;
+  static constexpr int S_TOT = NN2 + ND * NN2 + 2 * ND * 2 * NP;
+  static constexpr long lds_bytes = 8L * (2 * ((G::NF * ND * G::NU + 1) & ~1) + G::NF * NUS + 2 * AffRec::SIZE + S_TOT + G::NF * XSTRIDE);
+};
+
+template <int ND, int N>
+__global__ __launch_bounds__(128, 2) void split_flux_two_wave_kernel(const Split2Args a, const double *coef_g, const int *tidx, const int rot)
+{
+  using G = Geo<ND, N>;
+  using T = TGeo<ND, N>;
+  using W2 = TwoWave<ND, N>;
+  constexpr int NF = G::NF, NU = G::NU, NFP = G::NFP, NG = NF * ND, NQ = ND * ND, L = T::L;
+  constexpr int TB = W2::TB, NLEFT = W2::NLEFT, NPF = W2::NPF, NUS = W2::NUS, NN2 = W2::NN2, NP = W2::NP;
+  static_assert(W2::fits, "the two-wave form: P4 hexahedra");
+  static_assert(W2::lds_bytes <= 40960, "four workgroups must fit the CU's 160 KiB of LDS");
+  static_assert(NF * NFP <= NG * NU, "the correction region aliases the work region");
+  constexpr int S_D = 0, S_DC = NN2, S_C5 = S_DC + ND * NN2, S_LF = S_C5 + ND * 2 * NP, S_TOT = W2::S_TOT;
+  __shared__ __attribute__((aligned(16))) double sA[NG * NU]; // sd (corrections), later st
+  __shared__ __attribute__((aligned(16))) double sB[NG * NU]; // sg, later the per-direction parts of the divergence
+  __shared__ __attribute__((aligned(16))) double s_u[NF * NUS];
+  __shared__ __attribute__((aligned(16))) double s_rec[2 * AffRec::SIZE];
+  __shared__ __attribute__((aligned(16))) double s_coef[S_TOT];
+  __shared__ double s_x[NF * NLEFT]; // the left-over points' extrapolated solution, from A0 to their pass in phase B
+  double *const sd = sA, *const st = sA, *const sg = sB, *const sp = sB;
+  // the 1-D tables of the pencil phases (as the loader-wave form makes them), and the extrapolation rows Lf for the extra pass
+  for (int i = threadIdx.x; i < S_TOT; i += TB)
+  {
+    double v = 0.0;
+    if (i < S_DC)
+      v = (i < N * N) ? coef_g[T::C_D + i] : 0.0;
+    else if (i < S_C5)
+    {
+      const int d = (i - S_DC) / NN2, q = (i - S_DC) - d * NN2;
+      if (q < N * N)
+      {
+        const int mp = q / N, m = q - mp * N;
+        const double ta = coef_g[T::C_3 + (d * 2 + 0) * N + mp] * (coef_g[T::C_L1 + (d * 2 + 0) * N] * coef_g[T::C_LF + (d * 2 + 0) * N + m]);
+        const double tb = coef_g[T::C_3 + (d * 2 + 1) * N + mp] * (coef_g[T::C_L1 + (d * 2 + 1) * N] * coef_g[T::C_LF + (d * 2 + 1) * N + m]);
+        v = coef_g[T::C_D + q] - ta - tb;
+      }
+    }
+    else
+    {
+      const int row = (i - S_C5) / NP, mp = (i - S_C5) - row * NP; // c5 rows, then Lf rows
+      const int src = row < ND * 2 ? T::C_5 + row * N : T::C_LF + (row - ND * 2) * N;
+      v = (mp < N) ? coef_g[src + mp] : 0.0;
+    }
+    s_coef[i] = v;
+  }
+  auto table = [&](int off, auto &out) {
+    typedef double hfx_d2 __attribute__((ext_vector_type(2)));
+    constexpr int CNT = sizeof(out) / sizeof(double);
+#pragma unroll
+    for (int i = 0; i < CNT / 2; i++)
+    {
+      const hfx_d2 v = *(const volatile __attribute__((address_space(3))) hfx_d2 *)(&s_coef[off + 2 * i]);
+      out[2 * i] = v.x;
+      out[2 * i + 1] = v.y;
+    }
+  };
+  const int t = threadIdx.x, lane = t & 63;
+  const bool wave_x = __builtin_amdgcn_readfirstlane(t >> 6) != 0; // wave 1: the extra pass; wave 0: the DMA
+  const int tu = t < NU ? t : NU - 1;
+  const bool is_u = t < NU, is_x = wave_x && lane < NLEFT;
+  int tf = t + rot, tx = TB + (lane < NLEFT ? lane : NLEFT - 1) + rot;
+  if (tf >= NFP) tf -= NFP;
+  if (tx >= NFP) tx -= NFP;
+  const long ne = a.n_eles, plane_u = (long)NU * ne, plane_f = (long)NFP * ne;
+
+  // flux-point role: the 1-D extrapolation row of this point and its pencil; the left-over point's row is read from LDS at its use
+  const int dq = tidx[T::I_FDQ + tf], d_f = dq >> 1;
+  const int bf = tidx[T::I_FB + tf], sf = (d_f == 0) ? 1 : (d_f == 1 ? N : N * N);
+  // (the left-over point's number, pencil base and extrapolation row in one word, unpacked at its uses)
+  const unsigned pk_x = (unsigned)tx | (unsigned)tidx[T::I_FB + tx] << 8 | (unsigned)tidx[T::I_FDQ + tx] << 16;
+  static_assert(NFP <= 256 && NU <= 256, "a packed point number has 8 bits");
+  // pencil role: item (field kq, pencil `line`) of direction r in round r.  What is loop invariant here is kept in few registers
+  // and unpacked at its use in every element (the kernel sits at its 256 registers): the pencil's two flux points of the three
+  // rounds in one word each (10 bits a round), the pencils' bases derived from `line`
+  const int kq = is_u ? t / L : 0, line = is_u ? t - (t / L) * L : 0;
+  static_assert(NF * NFP <= 1024, "a packed correction index has 10 bits");
+  unsigned pk_fa = 0, pk_fb = 0;
+#pragma unroll
+  for (int r = 0; r < ND; r++)
+  {
+    pk_fa |= (unsigned)(kq * NFP + tidx[T::I_PF + (r * L + line) * 2 + 0]) << (10 * r);
+    pk_fb |= (unsigned)(kq * NFP + tidx[T::I_PF + (r * L + line) * 2 + 1]) << (10 * r);
+  }
+
+  const long tot_u = plane_u * NF, tot_f = plane_f * NF;
+  const GArr<true> g_u0(a.u0, tot_u), g_JGu(a.JGinv_upts, plane_u * NQ), g_gf(a.grad_fpts, plane_f * NG), g_fn(a.fn_fpts, tot_f),
+      g_div(a.div, tot_u), g_rec(a.aff_rec, (long)AffRec::SIZE * ne);
+  const unsigned lu = tu, lf = tf;
+  const EleOrder order(ne, a.xcd_order != 0, a.ele_list, a.n_list);
+#define HFX_VMCNT(n_) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n_) : "memory")
+  // wave 0: the state (one run per field, 16 bytes per lane) and the record of element e into the slot / record buffer `which`
+  constexpr int L_U = (NU + 1) / 2;
+  auto issue = [&](long e, int which) {
+    dma16_region(g_rec, (lds_dp)s_rec + which * AffRec::SIZE, AffRec::SIZE / 2, lane, (unsigned)((long)AffRec::SIZE * e) * 8u);
+#pragma unroll
+    for (int k = 0; k < NF; k++) dma16_region(g_u0, (lds_dp)s_u + k * NUS, L_U, lane, (unsigned)((long)NU * e + k * plane_u) * 8u);
+  };
+  // what a flux point needs for its LDG correction (the partner's flux-point solution, or at a boundary / partition-face point
+  // the correction its one-sided kernel left in `delta`): requested a whole element ahead for the lane's own point, the partner
+  // words another element ahead; for the left-over point in phase C of the element before (fewer registers across phase B)
+  double pv[NF], pvx[NF];
+  int nb_cur = -1, nb_next = -1, nb_nn = -1, nbx_cur = -1, nbx_next = -1;
+  auto request_partner = [&](long e_of, int nb, int point, double (&out)[NF]) {
+    const double *src = (nb < 0) ? a.delta + ((long)NFP * e_of + point) : a.disu + (nb >> 2);
+#pragma unroll
+    for (int k = 0; k < NF; k++) out[k] = src[k * plane_f];
+  };
+#pragma unroll
+  for (int k = 0; k < NF; k++) pvx[k] = 0.0;
+  long e = order.at(0);
+  if (e >= 0)
+  {
+    if (!wave_x) issue(e, 0);
+    nb_cur = a.nbr[(long)NFP * e + tf];
+    request_partner(e, nb_cur, tf, pv);
+    if (order.at(1) >= 0) nb_next = a.nbr[(long)NFP * order.at(1) + tf];
+    if (is_x)
+    {
+      nbx_cur = a.nbr[(long)NFP * e + (int)(pk_x & 255u)];
+      request_partner(e, nbx_cur, (int)(pk_x & 255u), pvx);
+    }
+  }
+  if (!wave_x) HFX_VMCNT(0);
+  __syncthreads(); // the tables, the first element's slot and record
+
+  for (long kk = 0, e_next; e >= 0; kk++, e = e_next)
+  {
+    e_next = order.at(kk + 1);
+    const long eu = (long)NU * e, ef = (long)NFP * e;
+    const double *rec = s_rec + (kk & 1) * AffRec::SIZE;
+    // (the pencil addresses of the flux-point role rebuilt from an opaque copy: see the loader-wave form)
+    int am[N];
+    {
+      int bfo = bf;
+      asm volatile("" : "+v"(bfo));
+#pragma unroll
+      for (int m = 0; m < N; m++) am[m] = bfo + m * sf;
+    }
+    int it_b[ND];
+    {
+      int lo = line;
+      asm volatile("" : "+v"(lo));
+#pragma unroll
+      for (int r = 0; r < ND; r++) it_b[r] = r == 0 ? N * lo : (r == 1 ? (lo % N) + N * N * (lo / N) : lo);
+    }
+    // this flux point's 1-D extrapolation row, from the table (a register per entry across the element loop otherwise)
+    double Lrow[N];
+#pragma unroll
+    for (int m = 0; m < N; m++) Lrow[m] = ldsv(&s_coef[S_LF + dq * NP + m]);
+    double u[NF], uf[NF], accg[ND][N];
+    // ---- A0, first the part of phase A that needs no correction: the 1-D derivative of the pencils' state
+    {
+      double xa[ND][N], Dm[NN2];
+      table(S_D, Dm);
+#pragma unroll
+      for (int r = 0; r < ND; r++)
+      {
+        const double *su_p = s_u + kq * NUS + it_b[r];
+#pragma unroll
+        for (int m = 0; m < N; m++) xa[r][m] = ldsv(su_p + m * ipow(N, r));
+      }
+#pragma unroll
+      for (int r = 0; r < ND; r++)
+      {
+#pragma unroll
+        for (int mp = 0; mp < N; mp++) accg[r][mp] = 0.0;
+#pragma unroll
+        for (int m = 0; m < N; m++)
+#pragma unroll
+          for (int mp = 0; mp < N; mp++) accg[r][mp] += Dm[mp * N + m] * xa[r][m];
+      }
+    }
+    // ---- A0: this flux point's solution and its LDG correction delta = u_common - u_own (src/inters.cpp:637) -> sd
+#pragma unroll
+    for (int k = 0; k < NF; k++) uf[k] = 0.0;
+#pragma unroll
+    for (int m = 0; m < N; m++)
+    {
+      double x[NF];
+#pragma unroll
+      for (int k = 0; k < NF; k++) x[k] = ldsv(&s_u[k * NUS + am[m]]);
+#pragma unroll
+      for (int k = 0; k < NF; k++) uf[k] += Lrow[m] * x[k];
+    }
+    // one-sided LDG: is this point's Fn needed? (see the loader-wave form)
+    auto needed = [&](int nb) {
+      const double beta = (nb & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
+      return nb < 0 || ((nb & 1) ? 0.5 - beta : 0.5 + beta) != 0.0 || (a.grad_fpts != nullptr && a.meta == nullptr);
+    };
+    auto correction = [&](int nb, const double (&part)[NF], const double (&own)[NF], int point) {
+      const double beta = (nb & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
+#pragma unroll
+      for (int k = 0; k < NF; k++)
+      {
+        const double ul = (nb & 1) ? part[k] : own[k], ur = (nb & 1) ? own[k] : part[k];
+        const double uc = 0.5 * (ul + ur) - beta * (ul - ur);
+        sd[k * NFP + point] = (nb < 0) ? part[k] : uc - own[k];
+      }
+    };
+    const bool fn_needed = needed(nb_cur);
+    correction(nb_cur, pv, uf, tf);
+    // the next element's partner values, and the word of the one after (rotated at the END of the iteration)
+    if (e_next >= 0) request_partner(e_next, nb_next, tf, pv);
+    {
+      const long e_nn = order.at(kk + 2);
+      nb_nn = a.nbr[(long)NFP * (e_nn >= 0 ? e_nn : e) + tf];
+    }
+    if (wave_x)
+    {
+      // ---- A0 of the left-over points (lanes 0 .. NLEFT-1): the gradient needs every correction
+      if (is_x)
+      {
+        unsigned px = pk_x;
+        asm volatile("" : "+v"(px));
+        const int tx = px & 255u, bxo = (px >> 8) & 255u, dqx = px >> 16;
+        const int sfx = (dqx >> 1) == 0 ? 1 : ((dqx >> 1) == 1 ? N : N * N);
+        double ufx[NF];
+#pragma unroll
+        for (int k = 0; k < NF; k++) ufx[k] = 0.0;
+#pragma unroll
+        for (int m = 0; m < N; m++)
+        {
+          const double lm = ldsv(&s_coef[S_LF + dqx * NP + m]);
+          double x[NF];
+#pragma unroll
+          for (int k = 0; k < NF; k++) x[k] = ldsv(&s_u[k * NUS + bxo + m * sfx]);
+#pragma unroll
+          for (int k = 0; k < NF; k++) ufx[k] += lm * x[k];
+        }
+        correction(nbx_cur, pvx, ufx, tx);
+#pragma unroll
+        for (int k = 0; k < NF; k++) s_x[k * NLEFT + lane] = ufx[k];
+        nbx_next = a.nbr[(long)NFP * (e_next >= 0 ? e_next : e) + tx];
+      }
+    }
+    lds_barrier(); // 1b: the corrections are written
+
+    // ---- A: transformed gradient, pencil-wise
+    {
+      double da[ND], db[ND], c5a[ND][NP], c5b[ND][NP];
+      unsigned fa = pk_fa, fb = pk_fb;
+      asm volatile("" : "+v"(fa), "+v"(fb));
+#pragma unroll
+      for (int r = 0; r < ND; r++)
+      {
+        da[r] = ldsv(sd + ((fa >> (10 * r)) & 1023u));
+        db[r] = ldsv(sd + ((fb >> (10 * r)) & 1023u));
+      }
+#pragma unroll
+      for (int r = 0; r < ND; r++)
+      {
+        table(S_C5 + (r * 2 + 0) * NP, c5a[r]);
+        table(S_C5 + (r * 2 + 1) * NP, c5b[r]);
+      }
+#pragma unroll
+      for (int r = 0; r < ND; r++)
+      {
+#pragma unroll
+        for (int mp = 0; mp < N; mp++) accg[r][mp] += c5a[r][mp] * da[r];
+#pragma unroll
+        for (int mp = 0; mp < N; mp++) accg[r][mp] += c5b[r][mp] * db[r];
+      }
+      if (is_u)
+      {
+#pragma unroll
+        for (int r = 0; r < ND; r++)
+        {
+          double *sg_p = sg + (kq + NF * r) * NU + it_b[r];
+#pragma unroll
+          for (int mp = 0; mp < N; mp++) sg_p[mp * ipow(N, r)] = accg[r][mp];
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NF; k++) u[k] = ldsv(&s_u[k * NUS + tu]);
+    lds_barrier(); // 2: sg complete; the corrections are dead (their region becomes st) and so is the state slot
+    // the next element's state into the slot, its record into the other record buffer (last read in phase B of the element before)
+    if (!wave_x && e_next >= 0) issue(e_next, (int)((kk + 1) & 1));
+
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- B: the PAIRED point physics (see the loader-wave form): a thread's solution point and its flux point together, both
+    // on the element's JGinv and detjac from the record
+    {
+      double jg[NQ], inv, u2[2][NF], g2[2][NG], f2[2][NG], nr2[ND], jgp[NQ];
+      // the solution point's OWN JGinv for the transform of the total flux (requested here, used behind the point physics)
+#pragma unroll
+      for (int q = 0; q < NQ; q++) jgp[q] = g_JGu.ld(eu * NQ, lu * NQ + q);
+#pragma unroll
+      for (int q = 0; q < NQ; q++) jg[q] = ldsv(&rec[AffRec::JG + q]);
+      inv = 1.0 / ldsv(&rec[AffRec::DJ]);
+#pragma unroll
+      for (int k = 0; k < NF; k++)
+      {
+        u2[0][k] = u[k];
+        u2[1][k] = uf[k];
+      }
+#pragma unroll
+      for (int q = 0; q < NG; q++) g2[0][q] = ldsv(&sg[q * NU + tu]);
+#pragma unroll
+      for (int q = 0; q < NG; q++) g2[1][q] = 0.0;
+#pragma unroll
+      for (int m = 0; m < N; m++)
+      {
+        double x[NG];
+        const double lm = ldsv(&s_coef[S_LF + dq * NP + m]);
+#pragma unroll
+        for (int q = 0; q < NG; q++) x[q] = ldsv(&sg[q * NU + am[m]]);
+#pragma unroll
+        for (int q = 0; q < NG; q++) g2[1][q] += lm * x[q];
+      }
+      // to physical space (to_physical, both points per statement)
+#pragma unroll
+      for (int k = 0; k < NF; k++)
+      {
+        double cg[2][ND], tmp[2];
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+          for (int d = 0; d < ND; d++) cg[p][d] = 0.0;
+#pragma unroll
+        for (int l = 0; l < ND; l++)
+        {
+#pragma unroll
+          for (int p = 0; p < 2; p++) tmp[p] = inv * g2[p][k + NF * l];
+#pragma unroll
+          for (int d = 0; d < ND; d++)
+#pragma unroll
+            for (int p = 0; p < 2; p++) cg[p][d] += tmp[p] * jg[l + ND * d];
+        }
+#pragma unroll
+        for (int d = 0; d < ND; d++)
+#pragma unroll
+          for (int p = 0; p < 2; p++) g2[p][k + NF * d] = cg[p][d];
+      }
+      if (a.grad_fpts && (a.meta == nullptr || (a.meta[ef + tf] & 4)))
+#pragma unroll
+        for (int q = 0; q < NG; q++) g_gf.st(ef + q * plane_f, lf, g2[1][q]);
+      calc_visf_pair<ND>(a.P, u2, g2, f2);
+      {
+        int tfo = tf;
+        asm volatile("" : "+v"(tfo));
+        const int fo = AffRec::FACE + AffRec::FACE_W * (tfo / NPF);
+#pragma unroll
+        for (int l = 0; l < ND; l++) nr2[l] = ldsv(&rec[fo + l]);
+      }
+      // flux point: this side's viscous flux on its own normal
+      if (fn_needed)
+      {
+#pragma unroll
+        for (int k = 0; k < NF; k++)
+        {
+          double s = 0.0;
+#pragma unroll
+          for (int l = 0; l < ND; l++) s += f2[1][k + NF * l] * nr2[l];
+          g_fn.st(ef + k * plane_f, lf, s);
+        }
+      }
+      // solution point: total flux to reference space, on the point's own JGinv
+      if (is_u)
+      {
+        double ft[NG];
+        calc_invf<ND, true>(a.P.gamma, u, ft);
+#pragma unroll
+        for (int q = 0; q < NG; q++) ft[q] += f2[0][q];
+#pragma unroll
+        for (int k = 0; k < NF; k++)
+#pragma unroll
+          for (int l = 0; l < ND; l++)
+          {
+            double s = 0.0;
+#pragma unroll
+            for (int m = 0; m < ND; m++) s += jgp[l + ND * m] * ft[k + NF * m];
+            st[(k + NF * l) * NU + tu] = s;
+          }
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (wave_x)
+    {
+      // ---- B of the left-over points: the unpaired flux-point block, under a wave-uniform branch when none of them needs its Fn
+      // (the points of one face, which a conforming mesh pairs as a whole); every barrier is outside the branch
+      const bool fnx = needed(nbx_cur);
+      if (__builtin_amdgcn_ballot_w64(fnx && is_x) != 0)
+      {
+        double JFl[NQ], nl[ND], grf[NG], fq[NG], ufx[NF];
+        unsigned px = pk_x;
+        asm volatile("" : "+v"(px));
+        const int tx = px & 255u, bxo = (px >> 8) & 255u, dqx = px >> 16;
+        const unsigned lx = tx;
+        const int fox = AffRec::FACE + AffRec::FACE_W * (tx / NPF);
+        const int sfx = (dqx >> 1) == 0 ? 1 : ((dqx >> 1) == 1 ? N : N * N);
+#pragma unroll
+        for (int q = 0; q < NQ; q++) JFl[q] = ldsv(&rec[AffRec::JG + q]);
+        const double inv_df = 1.0 / ldsv(&rec[AffRec::DJ]);
+#pragma unroll
+        for (int k = 0; k < NF; k++) ufx[k] = ldsv(&s_x[k * NLEFT + (lane < NLEFT ? lane : NLEFT - 1)]);
+#pragma unroll
+        for (int q = 0; q < NG; q++) grf[q] = 0.0;
+#pragma unroll
+        for (int m = 0; m < N; m++)
+        {
+          const double lm = ldsv(&s_coef[S_LF + dqx * NP + m]);
+          double x[NG];
+#pragma unroll
+          for (int q = 0; q < NG; q++) x[q] = ldsv(&sg[q * NU + bxo + m * sfx]);
+#pragma unroll
+          for (int q = 0; q < NG; q++) grf[q] += lm * x[q];
+        }
+#pragma unroll
+        for (int k = 0; k < NF; k++)
+        {
+          double tg[ND], cg[ND];
+#pragma unroll
+          for (int d = 0; d < ND; d++) tg[d] = grf[k + NF * d];
+          to_physical<ND>(inv_df, JFl, tg, cg);
+#pragma unroll
+          for (int d = 0; d < ND; d++) grf[k + NF * d] = cg[d];
+        }
+        if (a.grad_fpts && is_x && (a.meta == nullptr || (a.meta[ef + tx] & 4)))
+#pragma unroll
+          for (int q = 0; q < NG; q++) g_gf.st(ef + q * plane_f, lx, grf[q]);
+        calc_visf<ND, true>(a.P, ufx, grf, fq);
+#pragma unroll
+        for (int l = 0; l < ND; l++) nl[l] = ldsv(&rec[fox + l]);
+#pragma unroll
+        for (int k = 0; k < NF; k++)
+        {
+          double s = 0.0;
+#pragma unroll
+          for (int l = 0; l < ND; l++) s += fq[k + NF * l] * nl[l];
+          if (is_x && fnx) g_fn.st(ef + k * plane_f, lx, s);
+        }
+      }
+    }
+    lds_barrier(); // 3: st complete; sg is dead: its region takes the divergence parts
+
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- C: divergence parts pencil-wise with the folded matrix of the round's direction (div_tdisf - opp_3 norm_tdisf of a pencil
+    // in N^2 FMAs), two rounds and then the third
+    if (is_x && e_next >= 0) request_partner(e_next, nbx_next, (int)(pk_x & 255u), pvx);
+#pragma unroll
+    for (int r0 = 0; r0 < ND; r0 += 2)
+    {
+      double xa[2][N], acc[2][N], Dc[2][NN2];
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        if (r0 + j < ND)
+        {
+          const double *st_p = st + (kq + NF * (r0 + j)) * NU + it_b[r0 + j];
+#pragma unroll
+          for (int m = 0; m < N; m++) xa[j][m] = ldsv(st_p + m * ipow(N, r0 + j));
+        }
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        if (r0 + j < ND) table(S_DC + (r0 + j) * NN2, Dc[j]);
+#pragma unroll
+      for (int j = 0; j < 2; j++)
+        if (r0 + j < ND)
+        {
+#pragma unroll
+          for (int mp = 0; mp < N; mp++) acc[j][mp] = 0.0;
+#pragma unroll
+          for (int m = 0; m < N; m++)
+#pragma unroll
+            for (int mp = 0; mp < N; mp++) acc[j][mp] += Dc[j][mp * N + m] * xa[j][m];
+        }
+      if (is_u)
+      {
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+          if (r0 + j < ND)
+          {
+            double *sp_p = sp + (kq + NF * (r0 + j)) * NU + it_b[r0 + j];
+#pragma unroll
+            for (int mp = 0; mp < N; mp++) sp_p[mp * ipow(N, r0 + j)] = acc[j][mp];
+          }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // wave 0: the next element's slot and record have landed (requested behind barrier 2: phases B and C ago)
+    if (!wave_x) HFX_VMCNT(0);
+    lds_barrier(); // 4: the divergence parts are complete; st is dead; the next element's slot may be read
+    if (is_u)
+    {
+      double part[ND][NF];
+#pragma unroll
+      for (int d = 0; d < ND; d++)
+#pragma unroll
+        for (int k = 0; k < NF; k++) part[d][k] = ldsv(&sp[(k + NF * d) * NU + tu]);
+#pragma unroll
+      for (int k = 0; k < NF; k++)
+      {
+        double s = part[0][k];
+        s += part[1][k];
+        s += part[ND - 1][k];
+        g_div.st(eu + k * plane_u, lu, s);
+      }
+    }
+    asm volatile("" : "+v"(nb_nn)); // (the word is needed here, not earlier)
+    nb_cur = nb_next;
+    nb_next = nb_nn;
+    nbx_cur = nbx_next;
+    // no barrier: the next iteration writes the corrections to sA (dead since barrier 4), the left-over solution to s_x (its own
+    // lanes') and sB only behind its barrier 1b
+  }
+#undef HFX_VMCNT
+}
+
 
 // div_tdisf + opp_3 (norm_tconf - norm_tdisf) -> RK update -> disu_fpts of the new state: a streaming kernel
 // (after the sum-factorised flux kernel: (div_tdisf - opp_3 norm_tdisf) + opp_3 norm_tconf, norm_tdisf is not read)

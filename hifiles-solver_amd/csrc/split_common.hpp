@@ -44,6 +44,11 @@ struct FusedData
   bool affine = false;
   double affine_tol = 0.0, affine_spread = 0.0; // the relative bound of the test and the largest spread it met (diagnostics)
   DevBuf<double> aff_rec;                       // (AffRec::SIZE, n_eles)
+  // two-wave flux kernel (split_flux_two_wave_kernel): per local face, the elements by what the face's first n_fpts - 128 points
+  // (the left-over points, were the face chosen) ask of their projected viscous flux -- bit0: a point without a partner word
+  // (always needed), bit1: a point needed unless ldg_beta = -1/2, bit2: a point needed unless ldg_beta = +1/2 (two_wave_face)
+  long tw_need[6][8] = {};
+  bool tw_counted = false;
   bool built = false;
 };
 
@@ -81,6 +86,7 @@ struct SplitPlan
   bool buf = false;             // register pipeline: BUF
   bool gather = false;          // the flux kernel forms the interior LDG corrections itself (loader wave: GA)
   bool affine = false;          // an affine block: the flux kernel (loader wave: AFF) and the update kernel read the per-element metric record
+  bool two_wave = false;        // the affine flux kernel in its two-wave form (split_flux_two_wave_kernel: P4 hexahedra, option flux_two_wave)
   bool face_delta = false;      // face_delta_kernel forms them (a viscous block without `gather`)
   bool oi_fold = false;         // the over-integration kernel hands over its result folded into the divergence
   OverInt over_int = OverInt::none;

@@ -125,7 +125,8 @@ int hfx_ctx_set_CFL(hfx_ctx *ctx, double CFL);
  * min(its usual grid, n) workgroups, so that a mesh of a few elements runs their element loops past the first iteration; results do not change,
  * hfx_fused_launch_grids reports the grids), "xcd_order" (1), "dictionary_rows" (0), "flux_waves" (2 | 3), "buffer_addressing" (1),
  * "loader_wave" (1), "fold_general" (1: the general fused stage applies opp_2 - opp_3 opp_1 and never forms norm_tdisf), "gather_delta" (1: the loader-wave flux kernel forms the interior LDG corrections itself, no pairwise
- * LDG launch), "simd_roles" (1: the flux kernel deals its waves' parts by SIMD), "comm_stream_faces" (1:
+ * LDG launch), "simd_roles" (1: the flux kernel deals its waves' parts by SIMD), "flux_two_wave" (1: on P4 hexahedra the affine flux kernel runs as
+ * two-wave workgroups, four resident per CU; 0: its loader-wave form; hfx_time_fused_kernels lists "two_wave" behind the kernels when it runs), "comm_stream_faces" (1:
  * hfx_run_steps_partitioned launches the one-sided partition-face kernels on the communication stream), "flux_stamps" (0; n >= 1: cycle
  * stamps of iteration max(n, 2) of one workgroup of the flux kernels, printed by the hfx_time_* entry points), "tensor_ops" (1),
  * "split_flux" (1: hfx_run_steps_partitioned runs the flux kernel in three launches -- half of the elements without partition-face points,
@@ -622,6 +623,12 @@ int hfx_fused_kernel_bytes(hfx_eles *e, double bytes[8]);
  * shock-capturing kernel, grid[i] its workgroups, work[i] the elements -- on a partitioned block the entries of the element list -- it walks.
  * Writes min(*n_launches, max_launches) entries; at most 16 launches are kept. */
 int hfx_fused_launch_grids(hfx_eles *e, int max_launches, int *slot, int *grid, long *work, int *n_launches);
+/* The two-wave form of the affine flux kernel (P4 hexahedra on an affine block, option "flux_two_wave"): 22 of an element's 150 flux
+ * points have no partner lane and run as an extra pass, which is skipped when none of them needs its projected viscous flux
+ * (one-sided LDG).  The library puts them on the local face whose flux the block needs least often: *face is that face (0..5; -1:
+ * the form does not run on this block), need[f] the number of elements that would take the pass with the points on face f (counted
+ * from the partner words and ldg_beta). */
+int hfx_flux_two_wave_face(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int *face, long need[6]);
 /* The same for the general fused stage (hfx_run_steps_blocks(..., fused = 4)): ms[0..3] = pairwise LDG kernels, flux
  * kernels of all element blocks, pairwise common-flux kernels, update kernels of all blocks */
 int hfx_time_general_kernels(hfx_eles *const *eles, int n_ele_blocks, hfx_inters *const *faces, int n_face_blocks, int reps,
