@@ -93,6 +93,11 @@ MIXED_KEYS = dict(
     bc_WallHi_type="adiabat_wall", bc_WallHi_w=-2.0,
 )
 
+# element-class keys of the single-class tetrahedron and prism cases
+TET_KEYS = dict(upts_type_tet=0, fpts_type_tet=0, vcjh_scheme_tet=1, eta_tet=0.0)
+PRI_KEYS = dict(upts_type_pri_tri=0, upts_type_pri_1d=0, vcjh_scheme_pri_1d=1, eta_pri=0.0, upts_type_tri=0, vcjh_scheme_tri=1,
+                c_tri=0.0)
+
 # threshold inside the widest gap of hex_p4_jet's first-stage sensor values (so that rounding cannot flip an element)
 HEX_P4_JET_S0 = 7.0e-7
 
@@ -305,6 +310,71 @@ CASES = [
          bc_OutT_type="sub_out_char", bc_OutT_p_static=P_TGV * 0.98,
          bc_InC_type="sub_in_char", bc_InC_p_total=P_TGV * 1.9, bc_InC_T_total=600.0, bc_InC_nx=0.0, bc_InC_ny=0.0,
          bc_InC_nz=1.0, **BC_KEYS),
+    # ---- the run-wide switches on every element class (tests/test_branch_census.py::test_switch_table) ----
+    # 2-D: RoeM, Sutherland's law, a penalty and an off-centre LDG switch together, on the mesh and at the Mach number of
+    # quad_p3_transonic.  Three steps: the stored state that enters the last stage is no longer isothermal
+    case("quad_p3_roem_sutherland", dims=2, n=4, amp=0.1, level=1, order=3, steps=3, Mach_c_ic=1.15, riemann_solve_type=2,
+         fix_vis=0, ldg_beta=0.25, ldg_tau=0.3, dt=5.0e-5),
+    # tetrahedra and prisms: the same four switches on the mesh of tet_p2_transonic and on prisms one cell wider in y (RoeM
+    # clips its wave speeds only where a face sees a supersonic normal Mach number; on pri_p2_transonic's 3 x 2 x 2 box six
+    # pairs clip either speed, and at Mach 1.25 the first residual has a negative pressure), and Rusanov with the penalty and the off-centre switch on
+    # the meshes of tet_p2_n2_deformed / pri_p2_n2_deformed
+    case("tet_p2_roem_sutherland", n=[3, 2, 2], amp=0.1, level=1, order=2, steps=1, tets=True, Mach_c_ic=1.25,
+         riemann_solve_type=2, fix_vis=0, ldg_beta=0.25, ldg_tau=0.3, **TET_KEYS),
+    case("pri_p2_roem_sutherland", n=[3, 3, 2], amp=0.1, level=1, order=2, steps=2, tets="prisms", Mach_c_ic=1.2,
+         riemann_solve_type=2, fix_vis=0, ldg_beta=0.25, ldg_tau=0.3, **PRI_KEYS),
+    case("tet_p2_rusanov_ldg", n=2, amp=0.1, level=1, order=2, steps=1, tets=True, riemann_solve_type=0, ldg_beta=0.25,
+         ldg_tau=0.3, **TET_KEYS),
+    case("pri_p2_rusanov_ldg", n=2, amp=0.1, level=1, order=2, steps=1, tets="prisms", riemann_solve_type=0, ldg_beta=0.25,
+         ldg_tau=0.3, **PRI_KEYS),
+    # inviscid tetrahedra and prisms (the isentropic vortex of quad_p3_vortex: the Taylor-Green state needs the viscous
+    # reference values)
+    case("tet_p2_inviscid", n=2, amp=0.1, level=1, order=2, steps=1, tets=True, viscous=0, ic_form=0, dt=0.001, rho_c_ic=1.0,
+         u_c_ic=1.0, v_c_ic=1.0, w_c_ic=0.0, p_c_ic=1.0, **TET_KEYS),
+    case("pri_p2_inviscid", n=2, amp=0.1, level=1, order=2, steps=1, tets="prisms", viscous=0, ic_form=0, dt=0.001, rho_c_ic=1.0,
+         u_c_ic=1.0, v_c_ic=1.0, w_c_ic=0.0, p_c_ic=1.0, **PRI_KEYS),
+    # 2-D boundary types that no quad fixture carried, on a viscous box in the Taylor-Green field: none of the four branches
+    # on the sign of u.n (which is zero on every side of the box)
+    case("quad_p3_bdy_inout", dims=2, n=4, amp=0.1, level=2, order=3, steps=1,
+         bcs={"y-": "InS", "y+": "Dual", "x-": "SupI", "x+": "SupO"}, **BC_KEYS),
+    # the 2-D twins of hex_p1_bdy_supersonic and hex_p2_bdy_transonic, both viscous: uniform flow at Mach 1.8 along (0.7, 0.714)
+    # (normal Mach numbers 1.26 and 1.29): "char" with supersonic inflow (x-) and outflow (x+), "sub_out_simp" with
+    # machn >= 1 (y+) and with reverse flow (y-) ...
+    case("quad_p3_bdy_supersonic", dims=2, n=4, amp=0.1, level=2, order=3, steps=1, ic_form=1, Mach_c_ic=1.8, nx_c_ic=0.7,
+         ny_c_ic=0.714, nz_c_ic=0.0,
+         bcs={"x-": "FarS2", "x+": "FarS2", "y-": "OutS3", "y+": "OutS3"},
+         bc_FarS2_type="char", bc_FarS2_p_static=P_TGV, bc_FarS2_mach=1.7, bc_FarS2_T_static=295.0, bc_FarS2_nx=0.7,
+         bc_FarS2_ny=0.714,
+         bc_OutS3_type="sub_out_simp", bc_OutS3_p_static=P_TGV * 0.99, bc_OutS3_T_total=480.0, **BC_KEYS),
+    # ... and at Mach 0.6 along (0.7, 0.714) (normal Mach number about 0.42): "char" subsonic inflow (x-) and outflow (x+),
+    # "sub_out_simp" subsonic (y+), a "sub_in_char" inlet whose total temperature clamps the ghost Mach number to 1 (y-)
+    case("quad_p3_bdy_transonic", dims=2, n=4, amp=0.1, level=2, order=3, steps=1, ic_form=1, Mach_c_ic=0.6, nx_c_ic=0.7,
+         ny_c_ic=0.714, nz_c_ic=0.0,
+         bcs={"x-": "FarT2", "x+": "FarT2", "y-": "InC2", "y+": "OutT2"},
+         bc_FarT2_type="char", bc_FarT2_p_static=P_TGV, bc_FarT2_mach=0.55, bc_FarT2_T_static=295.0, bc_FarT2_nx=0.7,
+         bc_FarT2_ny=0.714,
+         bc_InC2_type="sub_in_char", bc_InC2_p_total=P_TGV * 1.9, bc_InC2_T_total=600.0, bc_InC2_nx=0.0, bc_InC2_ny=1.0,
+         bc_OutT2_type="sub_out_simp", bc_OutT2_p_static=P_TGV * 0.98, **BC_KEYS),
+    # the viscous sweep of slip_wall_dual in 3-D (hex_p1_bdy_inviscid carries the type without one); two cells between the
+    # walls, three along the periodic directions (27 P2 hexes with every intermediate no longer fit a file of 1 MiB)
+    case("hex_p2_bdy_dual", n=[3, 3, 2], amp=0.1, level=2, order=2, steps=1, bcs={"z-": "Dual", "z+": "Dual"}, **BC_KEYS),
+    # the ramp from ramping to clamped: ramp_counter runs 1, 2, 3 over the three steps, so p_total_old + (p_total -
+    # p_total_old) * 0.4 * counter passes p_total at the third step and the temperature ramp (coefficient 0.6) at the second.
+    # Uniform flow at Mach 0.3 along x into the inlet's direction (ghost Mach number below 1, the velocity root positive),
+    # an adiabatic wall that moves along itself below
+    case("quad_p3_ramp_clamp", dims=2, n=4, amp=0.1, level=1, order=3, steps=3, ic_form=1, Mach_c_ic=0.3, nx_c_ic=1.0,
+         ny_c_ic=0.0, nz_c_ic=0.0,
+         bcs={"y-": "WallQ2", "y+": "Slip", "x-": "InR2", "x+": "Out"},
+         bc_WallQ2_type="adiabat_wall", bc_WallQ2_u=40.0,
+         bc_InR2_type="sub_in_char", bc_InR2_p_total=P_TGV * 1.064, bc_InR2_T_total=305.4, bc_InR2_nx=1.0, bc_InR2_ny=0.0,
+         bc_InR2_pressure_ramp=1, bc_InR2_p_ramp_coeff=0.4, bc_InR2_T_ramp_coeff=0.6, bc_InR2_p_total_old=P_TGV * 1.03,
+         bc_InR2_T_total_old=301.0, **BC_KEYS),
+    # the ramp switched on with p_ramp_coeff = 0: the total pressure is not ramped (src/bdy_inters.cpp:490-491)
+    case("quad_p3_ramp_zero", dims=2, n=4, amp=0.1, level=1, order=3, steps=1,
+         bcs={"y-": "WallT", "y+": "Slip", "x-": "InR0", "x+": "Out"},
+         bc_InR0_type="sub_in_char", bc_InR0_p_total=P_TGV * 1.0070, bc_InR0_T_total=300.6, bc_InR0_nx=0.0, bc_InR0_ny=1.0,
+         bc_InR0_pressure_ramp=1, bc_InR0_p_ramp_coeff=0.0, bc_InR0_T_ramp_coeff=-1.0, bc_InR0_p_total_old=P_TGV * 1.002,
+         **BC_KEYS),
 ]
 
 

@@ -36,7 +36,7 @@ def case_from_fixture(d, **over):
               viscous=kk["viscous"], ic_form=kk["ic_form"], fix_vis=kk["fix_vis"], T_c_ic=kk["T_c_ic"], rho_c_ic=kk["rho_c_ic"],
               upts_type=kk["upts_type_hexa"], vcjh_scheme=kk["vcjh_scheme_hexa"])
     for k in ("u_c_ic", "v_c_ic", "w_c_ic", "p_c_ic", "over_int", "over_int_order", "shock_cap", "shock_det_field", "s0",
-              "expf_fac", "expf_order", "expf_cutoff", "dt"):
+              "expf_fac", "expf_order", "expf_cutoff", "dt", "Mach_c_ic", "ldg_beta", "ldg_tau"):
         if k in kk:
             kw[k] = kk[k]
     if meta["dims"] == 2:

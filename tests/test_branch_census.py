@@ -12,6 +12,12 @@ clipped wave speed is a max / min), so a point that rounding moves across a swit
 margin is asked there.  The boundary ghost states are NOT continuous across theirs (sub_out_simp jumps from the back
 pressure to the interior's, "char" swaps whole Riemann invariants), so every boundary point has to stay clear of every
 switch by 1e-6 of the sound speed -- seven orders above what differently rounded arithmetic can move it.
+
+The same argument for what does not depend on the data: the run-wide switches (Riemann solver, Sutherland's law, the LDG
+penalty and switch, viscous or not) on every element class, every boundary type in 2-D and in 3-D with its viscous sweep, and
+the branches of the total-pressure ramp at the ramp counter of every stored step (test_switch_table,
+test_every_boundary_type_in_each_dimension, test_ramp_takes_every_branch).  tests/test_gpu_physics_matrix.py runs the same
+switches through every kernel family against the oracle, which is trusted where these fixtures pin it.
 """
 import os
 
@@ -22,8 +28,17 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 HLLC = ["hex_p2_transonic", "quad_p3_transonic", "tet_p2_transonic", "pri_p2_transonic", "hex_p1_bdy_supersonic",
         "hex_p2_bdy_transonic"]
 ROEM = ["hex_p2_transonic_roem"]
+# RoeM on the other element classes: each has its own face kernels, each sees both clips
+ROEM_CLASSES = ["quad_p3_roem_sutherland", "tet_p2_roem_sutherland", "pri_p2_roem_sutherland"]
+SUTHERLAND = {"quad_p3_roem_sutherland": "u_step2_stage3", "tet_p2_roem_sutherland": "u_step0_stage3",
+              "pri_p2_roem_sutherland": "u_step1_stage3"}  # fixture -> the state that enters its last stored stage
 BDY = ["hex_p1_bdy_supersonic", "hex_p2_bdy_transonic"]
+BDY2 = ["quad_p3_bdy_supersonic", "quad_p3_bdy_transonic", "quad_p3_ramp_clamp"]
 SUB_OUT_SIMP, SUB_IN_CHAR, CHAR = 1, 2, 10  # bc flags of the boundary records (include/hfx.h)
+# hfx_bc_flag by name (include/hfx.h; the reference's bc type names)
+BC_FLAGS = {"sub_in_simp": 0, "sub_out_simp": 1, "sub_in_char": 2, "sub_out_char": 3, "sup_in": 4, "sup_out": 5, "slip_wall": 6,
+            "cyclic": 7, "isotherm_wall": 8, "adiabat_wall": 9, "char": 10, "slip_wall_dual": 11}
+ELE_CLASSES = {1: "quad", 4: "hex", 2: "tet", 3: "prism"}  # sizes[6], the reference's ele_type
 MIN_POINTS = 8
 MARGIN = 1e-6
 
@@ -150,6 +165,11 @@ def bdy_census(d):
     if m.any():
         # the ghost speed from the total temperature and the outgoing invariant: root of a quadratic
         T0 = par[7][bc][m]
+        ramped = d["bc_flags"].reshape(3, -1, order="F")[1][bc][m] != 0
+        if ramped.any():  # a ramped inlet: the total temperature of the fixture's first step (src/bdy_inters.cpp:482-504)
+            counter = int(np.ravel(d["ramp_counter"])[0])
+            T_l = p[m] / (rho[m] * R_ref)
+            T0 = np.where(ramped, [ramp_totals(par[:, b], counter, t, q)[1] for b, t, q in zip(bc[m], T_l, p[m])], T0)
         dirn = par[8:8 + n.shape[1]][:, bc].T[m]
         alpha = (n[m] * dirn).sum(axis=1)
         R_plus = vn[m] + 2.0 * c[m] / gm1
@@ -166,6 +186,43 @@ def bdy_census(d):
         out["sub_in_char M2 < 1"] = int((M2 < 1).sum())
         gap = min(gap, np.abs(np.sqrt(M2) - 1.0).min())
     return out, gap
+
+
+def ramp_totals(q, counter, T_l=None, p_l=None, gamma=1.4):
+    """(p_total_temp, T_total_temp, the branches taken) of a ramped sub_in_char record at a ramp counter
+    (src/bdy_inters.cpp:482-504); q is the record's column of `bc_params`"""
+    p_total, T_total, p_coeff, T_coeff, p_old, T_old = q[6], q[7], q[11], q[12], q[13], q[14]
+    taken = []
+    if p_coeff:
+        p0 = p_old + (p_total - p_old) * p_coeff * counter
+        taken.append("p clamped" if p0 >= p_total else "p ramping")
+        p0 = min(p0, p_total)
+    else:
+        p0 = p_total
+        taken.append("p_ramp_coeff == 0")
+    if T_coeff > 0:
+        T0 = T_old + (T_total - T_old) * T_coeff * counter
+        taken.append("T clamped" if T0 >= T_total else "T ramping")
+        T0 = min(T0, T_total)
+    elif T_coeff < 0:
+        T0 = T_l * (p0 / p_l) ** ((gamma - 1.0) / gamma) if T_l is not None else None
+        taken.append("T isentropic")
+    else:
+        T0 = T_total
+        taken.append("T_ramp_coeff == 0")
+    return p0, T0, taken
+
+
+def fixtures(keep):
+    """every single-class fixture that carries a residual's inputs (name, arrays), filtered by keep(arrays)"""
+    import glob
+    for path in sorted(glob.glob(os.path.join(GOLDEN, "*.npz"))):
+        name = os.path.basename(path)[:-4]
+        if name.startswith("mixed_") or "_tgv" in name:
+            continue
+        d = np.load(path)
+        if "sizes" in d.files and "riemann_solve_type" in d.files and keep(d):
+            yield name, d
 
 
 def report(name, census):
@@ -234,3 +291,127 @@ def test_sutherland_fixture_has_a_temperature_field():
 
     assert spread(d["u_init"]) < 1e-12
     assert spread(d["u_step2_stage3"]) > 1e-2
+
+
+def test_roem_clips_both_wave_speeds_on_every_element_class():
+    """roeM_flux<ND> is compiled into the 2-D split kernels and the general stage's face kernels separately"""
+    for name in ROEM_CLASSES:
+        d = load(name)
+        assert int(np.ravel(d["riemann_solve_type"])[0]) == 2
+        c = roem_census(d)
+        report(name, c)
+        for k in ("b1_clipped", "b2_clipped", "unclipped"):
+            assert c[k] >= MIN_POINTS, (name, k, c)
+
+
+@pytest.mark.parametrize("name", sorted(SUTHERLAND))
+def test_new_sutherland_fixtures_have_a_temperature_field(name):
+    """as test_sutherland_fixture_has_a_temperature_field, on each class's fix_vis = 0 fixture"""
+    d = load(name)
+    assert int(np.ravel(d["fix_vis"])[0]) == 0
+    gamma, R_ref, nd = float(np.ravel(d["gamma"])[0]), float(np.ravel(d["R_ref"])[0]), int(d["sizes"][4])
+
+    def spread(u):
+        rho = u[..., 0]
+        p = (gamma - 1.0) * (u[..., nd + 1] - 0.5 * (u[..., 1:nd + 1] ** 2).sum(axis=-1) / rho)
+        T = p / (rho * R_ref)
+        return (T.max() - T.min()) / T.mean()
+
+    last = max(k for k in d if k.startswith("u_step") and k.endswith("stage3"))
+    assert SUTHERLAND[name] == last
+    print("%-24s T spread %.3e at the start, %.3e entering the last stored stage" % (name, spread(d["u_init"]), spread(d[last])))
+    assert spread(d["u_init"]) < 1e-12
+    assert spread(d[last]) > 1e-2
+
+
+def test_boundary_states_take_every_branch_in_two_dimensions():
+    """bc_state<2> and bc_gradients<2> are instantiations of their own: the same branches as in 3-D, the same margin"""
+    best = {}
+    for name in BDY2:
+        d = load(name)
+        assert int(d["sizes"][4]) == 2 and int(np.ravel(d["viscous"])[0]) == 1
+        c, gap = bdy_census(d)
+        report(name, c)
+        print("%-24s smallest distance from a switch: %.3e of the sound speed" % (name, gap))
+        assert gap > MARGIN, (name, gap)
+        for k, v in c.items():
+            best[k] = max(best.get(k, 0), v)
+    for k in ("sub_out_simp reverse flow", "sub_out_simp machn >= 1", "sub_out_simp subsonic", "char supersonic inflow",
+              "char supersonic outflow", "char subsonic inflow", "char subsonic outflow", "sub_in_char M2 clamped",
+              "sub_in_char M2 < 1"):
+        assert best[k] >= MIN_POINTS, (k, best)
+
+
+@pytest.mark.parametrize("nd", [2, 3])
+def test_every_boundary_type_in_each_dimension(nd):
+    """every hfx_bc_flag but `cyclic` on at least MIN_POINTS boundary flux points of some fixture, and -- the viscous sweep
+    (bdy_viscflux_kernel, bc_gradients<ND>) -- of some VISCOUS fixture; slip_wall is the one flag that sweep returns on"""
+    any_run, viscous_run = {}, {}
+    for name, d in fixtures(lambda d: "bc_flags" in d.files and int(d["sizes"][4]) == nd):
+        flags = d["bc_flags"].reshape(3, -1, order="F")[0]
+        for t in range(3):
+            if "bdy%d_L" % t in d.files:
+                n_fpts = d["bdy%d_L" % t].shape[0]
+                for fl, cnt in zip(*np.unique(flags[np.ravel(d["bdy%d_id" % t])], return_counts=True)):
+                    for table in (any_run, viscous_run) if int(np.ravel(d["viscous"])[0]) else (any_run,):
+                        if cnt * n_fpts > table.get(int(fl), (0, ""))[0]:
+                            table[int(fl)] = (int(cnt * n_fpts), name)
+    for bc, fl in BC_FLAGS.items():
+        if bc != "cyclic":
+            print("ND %d %-15s %-32s viscous: %s" % (nd, bc, any_run.get(fl), viscous_run.get(fl)))
+    for bc, fl in BC_FLAGS.items():
+        if bc != "cyclic":
+            assert any_run.get(fl, (0,))[0] >= MIN_POINTS, (nd, bc)
+            assert viscous_run.get(fl, (0,))[0] >= MIN_POINTS, (nd, bc, "viscous sweep")
+
+
+def test_ramp_takes_every_branch():
+    """the total-pressure / total-temperature ramp of sub_in_char (src/bdy_inters.cpp:482-504) at the ramp counter of every
+    stored step (the counter advances after each step, src/HiFiLES.cpp:224-225)"""
+    taken = {}
+    for name, d in fixtures(lambda d: "bc_flags" in d.files and d["bc_flags"].reshape(3, -1, order="F")[1].any()):
+        fl = d["bc_flags"].reshape(3, -1, order="F")
+        par = d["bc_params"].reshape(15, -1, order="F")
+        steps = sorted({int(k.split("_")[1][4:]) for k in d.files if k.startswith("u_step")})
+        for st in steps:
+            counter = int(np.ravel(d["ramp_counter"])[0]) + st
+            for b in np.flatnonzero(fl[1]):
+                assert fl[0][b] == SUB_IN_CHAR
+                p0, _, branches = ramp_totals(par[:, b], counter)
+                print("%-20s step %d counter %d: %s" % (name, st, counter, ", ".join(branches)))
+                for k in branches:
+                    taken.setdefault(k, set()).add(name)
+    for k in ("p ramping", "p clamped", "T ramping", "T clamped", "T isentropic", "p_ramp_coeff == 0"):
+        assert taken.get(k), (k, taken)
+
+
+# class / switch pairs that the reference itself refuses: none.  (It refuses Lax-Friedrichs on a Navier-Stokes run,
+# src/input.cpp:546, which is no row of this table.)  The tetrahedron / prism inviscid row is filled by captures
+# (tet_p2_inviscid, pri_p2_inviscid), not by an override.
+REFUSED_BY_THE_REFERENCE = set()
+SWITCHES = {
+    "RoeM": lambda s: s["riemann_solve_type"] == 2,
+    "Rusanov": lambda s: s["riemann_solve_type"] == 0,
+    "fix_vis=0": lambda s: s["viscous"] == 1 and s["fix_vis"] == 0,
+    "ldg_tau, |ldg_beta| != 1/2": lambda s: s["viscous"] == 1 and s["ldg_tau"] != 0 and abs(s["ldg_beta"]) != 0.5,
+    "viscous=0": lambda s: s["viscous"] == 0,
+}
+
+
+def test_switch_table():
+    """every run-wide switch of the face-point physics on every element class, in at least one fixture that carries stage
+    states: the pairwise kernels take the solver as a template argument, so every (class, switch) is machine code of its own"""
+    table = {}
+    for name, d in fixtures(lambda d: any(k.startswith("u_step") for k in d.files) and "detjac_upts" in d.files):
+        cls = ELE_CLASSES[int(d["sizes"][6])]
+        s = {k: float(np.ravel(d[k])[0]) for k in ("riemann_solve_type", "fix_vis", "ldg_tau", "ldg_beta", "viscous")}
+        for sw, has in SWITCHES.items():
+            if has(s):
+                table.setdefault((cls, sw), []).append(name)
+    missing = []
+    for cls in ELE_CLASSES.values():
+        for sw in SWITCHES:
+            print("%-6s %-28s %s" % (cls, sw, ", ".join(table.get((cls, sw), [])) or "-"))
+            if not table.get((cls, sw)) and (cls, sw) not in REFUSED_BY_THE_REFERENCE:
+                missing.append((cls, sw))
+    assert not missing, missing

@@ -241,7 +241,8 @@ def test_full_size_residual_norms_vs_reference_stdout():
 
 
 @pytest.mark.parametrize("mode", ["methods", 2, 3])
-@pytest.mark.parametrize("name", ["hex_p2_bdy_walls", "hex_p2_bdy_inout", "hex_p1_bdy_inviscid", "quad_p3_bdy"])
+@pytest.mark.parametrize("name", ["hex_p2_bdy_walls", "hex_p2_bdy_inout", "hex_p1_bdy_inviscid", "quad_p3_bdy", "quad_p3_bdy_inout",
+                                  "hex_p2_bdy_dual", "quad_p3_ramp_clamp", "quad_p3_ramp_zero"])
 def test_boundary_case_through_the_mirror(name, mode):
     """Boundary faces end to end: host-mirror setup (mesh sides -> bdy_inters, bc_list non-dimensionalisation)
     + the mirrored CalcResidual / the split fused paths, against the genuine reference's state after a step."""
