@@ -55,11 +55,11 @@ BASE.update(TGV_FLUID)
 
 
 def case(name, n=3, dims=3, amp=0.0, steps=1, level=1, bcs=None, restart=False, tets=False, keep_every=1, ppts=False, curve=None,
-         **over):
+         orient_seed=None, **over):
     d = dict(BASE)
     d.update(over)
     return dict(name=name, n=n, dims=dims, amp=amp, steps=steps, level=level, keys=d, bcs=bcs, restart=restart, tets=tets,
-                keep_every=keep_every, ppts=ppts, curve=curve)
+                keep_every=keep_every, ppts=ppts, curve=curve, orient_seed=orient_seed)
 
 
 # boundary groups for the bdy_inters fixtures: states near the TGV initial state (rho 8.42e-4, T 300, Mach 0.1)
@@ -375,6 +375,10 @@ CASES = [
          bc_InR0_type="sub_in_char", bc_InR0_p_total=P_TGV * 1.0070, bc_InR0_T_total=300.6, bc_InR0_nx=0.0, bc_InR0_ny=1.0,
          bc_InR0_pressure_ramp=1, bc_InR0_p_ramp_coeff=0.0, bc_InR0_T_ramp_coeff=-1.0, bc_InR0_p_total_old=P_TGV * 1.002,
          **BC_KEYS),
+    # cells of mixed orientation: every cell's vertex list rotated by a seeded proper rotation (all 24 / all 4 occur), so
+    # that the face tables the reference's own preprocessor writes pair rotated faces and unlike local faces
+    case("hex_p2_scrambled", amp=0.05, level=1, order=2, steps=1, orient_seed=1),
+    case("quad_p3_scrambled", dims=2, n=[5, 3], amp=0.05, level=1, order=3, steps=1, orient_seed=3),
 ]
 
 
@@ -408,7 +412,7 @@ def run_case(c):
         elif c.get("tets"):
             xv = write_neu_tets(os.path.join(td, "mesh.neu"), c["n"], amp=c["amp"], curve=c.get("curve"))
         else:
-            xv = write_neu(os.path.join(td, "mesh.neu"), c["n"], c["dims"], amp=c["amp"], bcs=c.get("bcs"))
+            xv = write_neu(os.path.join(td, "mesh.neu"), c["n"], c["dims"], amp=c["amp"], bcs=c.get("bcs"), orient_seed=c.get("orient_seed"))
         keys = dict(c["keys"])
         keys["n_steps"] = c["steps"]
         if c["dims"] == 2:
@@ -436,7 +440,7 @@ def run_case(c):
         arrs["restart_ascii"] = arrs["restart_ascii"].astype(np.uint8)
     arrs["xv"] = xv
     meta = dict(name=c["name"], n=c["n"], dims=c["dims"], amp=c["amp"], steps=c["steps"],
-                level=c["level"], keys=c["keys"], bcs=c.get("bcs"),
+                level=c["level"], keys=c["keys"], bcs=c.get("bcs"), orient_seed=c.get("orient_seed"),
                 generator="oracle/capture_golden.py via oracle/_ref/ref_harness (genuine reference)")
     arrs["meta_json"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
     os.makedirs(GOLDEN, exist_ok=True)

@@ -63,10 +63,44 @@ SIDES3 = ("z-", "y-", "x+", "y+", "x-", "z+")  # code faces 0..5 of a hex
 SIDES2 = ("y-", "x+", "y+", "x-")              # code faces 0..3 of a quad
 
 
-def write_neu(path, n, dims=3, length=2.0 * math.pi, amp=0.0, bcname="Cyclic", bcs=None):
+def proper_rotations(dims):
+    """the proper rotations of the reference square (4) / cube (24) as integer matrices, the identity first"""
+    import itertools
+    out = []
+    for p in itertools.permutations(range(dims)):
+        for s in itertools.product((1, -1), repeat=dims):
+            G = np.zeros((dims, dims), dtype=int)
+            for k in range(dims):
+                G[k, p[k]] = s[k]
+            if round(np.linalg.det(G)) == 1:
+                out.append(G)
+    return out
+
+
+def cell_rotations(ne, dims, seed):
+    """seeded rotation index per cell: the first 24 (4) cells get every rotation once, in a seeded order"""
+    rng = np.random.RandomState(seed)
+    n_rot = 4 if dims == 2 else 24
+    rot = rng.randint(n_rot, size=ne)
+    first = rng.permutation(n_rot)[:ne]
+    rot[:first.size] = first
+    return rot
+
+
+# outward reference normals of the code faces (SIDES3 / SIDES2) and Gambit's number of each code face
+NORMALS3 = [(0, 0, -1), (0, -1, 0), (1, 0, 0), (0, 1, 0), (-1, 0, 0), (0, 0, 1)]
+NORMALS2 = [(0, -1), (1, 0), (0, 1), (-1, 0)]
+GAMBIT3 = {0: 1, 1: 4, 2: 6, 3: 2, 4: 5, 5: 3}  # mesh_reader.cpp:336-350
+GAMBIT2 = {0: 1, 1: 2, 2: 3, 3: 4}
+
+
+def write_neu(path, n, dims=3, length=2.0 * math.pi, amp=0.0, bcname="Cyclic", bcs=None, orient_seed=None):
     """bcs: optional {side: boundary-group name} (sides "x-","x+","y-","y+","z-","z+"); sides that are not
     listed belong to the group `bcname`.  One BOUNDARY CONDITIONS section is written per group
-    (mesh_reader.cpp:310-372 reads n_bdy of them); the group's type comes from the input key bc_<name>_type."""
+    (mesh_reader.cpp:310-372 reads n_bdy of them); the group's type comes from the input key bc_<name>_type.
+    orient_seed: every cell's vertex list is written rotated by a seeded proper rotation G of the reference element (the
+    cell's reference coordinates become xi' = G xi: slot c' holds the vertex that sat at G^T xi'), still in Gambit's
+    node order, and the boundary records name the Gambit face the side lies on after the rotation."""
     if isinstance(n, int):
         n = [n] * dims
     xv = box_vertices(n, dims, length, amp)
@@ -94,37 +128,56 @@ def write_neu(path, n, dims=3, length=2.0 * math.pi, amp=0.0, bcname="Cyclic", b
         f.write("ENDOFSECTION\n      ELEMENTS/CELLS 2.3.16\n")
         bfaces = []
         e = 0
+        Gs = proper_rotations(dims)
+        rot = cell_rotations(ne, dims, orient_seed) if orient_seed is not None else np.zeros(ne, dtype=int)
+        normals, gambit = (NORMALS3, GAMBIT3) if dims == 3 else (NORMALS2, GAMBIT2)
+
+        def turned(slot, G):
+            """the slots of the rotated cell: corner c' (xi' = 2 c' - 1) holds the vertex at xi = G^T xi'"""
+            out = {}
+            for q in range(2 ** dims):
+                c = np.array([(q >> d) & 1 for d in range(dims)])
+                src = (G.T @ (2 * c - 1) + 1) // 2
+                out[q] = slot[int(sum(int(src[d]) << d for d in range(dims)))]
+            return out
+
+        def face_id(code_face, G):
+            """Gambit's number of the face that code face `code_face` of the unrotated cell has become"""
+            return gambit[normals.index(tuple(int(v) for v in G @ np.array(normals[code_face])))]
+
         for k in range(nz):
             for j in range(ny):
                 for i in range(nx):
                     e += 1
+                    G = Gs[rot[e - 1]]
                     if dims == 3:
                         slot = {}
                         for t in range(2):
                             for s in range(2):
                                 for r in range(2):
                                     slot[r + 2 * s + 4 * t] = vid(i + r, j + s, k + t)
+                        slot = turned(slot, G)
                         order = [0, 2, 4, 6, 1, 3, 5, 7]
                         nodes = [slot[o] for o in order]
                         f.write("%8d %2d %2d " % (e, 4, 8) + "".join("%8d" % v for v in nodes[:7]) + "\n")
                         f.write(" " * 15 + "%8d\n" % nodes[7])
                         # gambit face ids (mesh_reader.cpp:336-350): code face 0<-1, 3<-2, 5<-3, 1<-4, 4<-5, 2<-6
-                        if k == 0: bfaces.append((e, 4, 1, "z-"))       # z-min : code face 0
-                        if j == 0: bfaces.append((e, 4, 4, "y-"))       # y-min : code face 1
-                        if i == nx - 1: bfaces.append((e, 4, 6, "x+"))  # x-max : code face 2
-                        if j == ny - 1: bfaces.append((e, 4, 2, "y+"))  # y-max : code face 3
-                        if i == 0: bfaces.append((e, 4, 5, "x-"))       # x-min : code face 4
-                        if k == nz - 1: bfaces.append((e, 4, 3, "z+"))  # z-max : code face 5
+                        if k == 0: bfaces.append((e, 4, face_id(0, G), "z-"))       # z-min : code face 0
+                        if j == 0: bfaces.append((e, 4, face_id(1, G), "y-"))       # y-min : code face 1
+                        if i == nx - 1: bfaces.append((e, 4, face_id(2, G), "x+"))  # x-max : code face 2
+                        if j == ny - 1: bfaces.append((e, 4, face_id(3, G), "y+"))  # y-max : code face 3
+                        if i == 0: bfaces.append((e, 4, face_id(4, G), "x-"))       # x-min : code face 4
+                        if k == nz - 1: bfaces.append((e, 4, face_id(5, G), "z+"))  # z-max : code face 5
                     else:
                         # quad slots 0:(0,0) 1:(1,0) 2:(0,1) 3:(1,1); file order -> slots 0,1,3,2
-                        slot = {r + 2 * s: vid(i + r, j + s) for s in range(2) for r in range(2)}
+                        slot = turned({r + 2 * s: vid(i + r, j + s) for s in range(2) for r in range(2)}, G)
                         nodes = [slot[0], slot[1], slot[3], slot[2]]
                         f.write("%8d %2d %2d " % (e, 2, 4) + "".join("%8d" % v for v in nodes) + "\n")
                         # quad faces (eles_quads.cpp:209-248): 0: eta=-1, 1: xi=+1, 2: eta=+1, 3: xi=-1; gambit k = face+1
-                        if j == 0: bfaces.append((e, 2, 1, "y-"))
-                        if i == nx - 1: bfaces.append((e, 2, 2, "x+"))
-                        if j == ny - 1: bfaces.append((e, 2, 3, "y+"))
-                        if i == 0: bfaces.append((e, 2, 4, "x-"))
+                        if j == 0: bfaces.append((e, 2, face_id(0, G), "y-"))
+                        if i == nx - 1: bfaces.append((e, 2, face_id(1, G), "x+"))
+                        if j == ny - 1: bfaces.append((e, 2, face_id(2, G), "y+"))
+                        if i == 0: bfaces.append((e, 2, face_id(3, G), "x-"))
         f.write("ENDOFSECTION\n       ELEMENT GROUP 2.3.16\n")
         f.write("GROUP: %10d ELEMENTS: %10d MATERIAL: %10d NFLAGS: %10d\n" % (1, ne, 2, 1))
         f.write("                           fluid\n       0\n")
