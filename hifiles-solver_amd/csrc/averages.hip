@@ -150,6 +150,9 @@ int end_of_step(hfx_eles *const *eles, int neb)
   if (ctx->i_steps == 1) ctx->spinup_time = ctx->time; /* src/HiFiLES.cpp:242-243 */
   for (int i = 0; i < neb; i++)
     if (launch_time_average(eles[i], ctx->time, ctx->spinup_time)) return 1;
+  if (ctx->n_probe_fields > 0 && ctx->i_steps % ctx->probe_freq == 0) /* src/HiFiLES.cpp:289-297 */
+    for (int i = 0; i < neb; i++)
+      if (sample_probes(eles[i], ctx->time, ctx->i_steps)) return 1;
   return 0;
 }
 

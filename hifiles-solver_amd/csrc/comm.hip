@@ -667,6 +667,7 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
   HFX_CHECK(e && comm, "hfx_run_steps_partitioned: NULL argument");
   HFX_CHECK(e->ctx->have_params, "parameters not set");
   HFX_IMMEDIATE(e->ctx, 0);
+  if (probes_check_capacity(&e, 1, n_steps)) return 1;
   return run_partitioned(e, int_faces, n_int, mpi_faces, n_mpi, comm, n_steps, -1, nullptr);
 }
 
@@ -680,6 +681,7 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   HFX_CHECK(ctx->params.dt_type == 0, "hfx_run_steps_partitioned_blocks: CFL time steps (dt_type 1 / 2) over several element blocks are the caller's "
                                       "(hfx_eles_calc_dt_local per block + hfx_comm_allreduce, then one step at a time)");
   const int nst = n_rk_stages(ctx->params);
+  if (probes_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
   for (int i = 0; i < n_ele_blocks; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
   // (as run_partitioned: the solution a partitioned fused stage has posted for this state is not posted again)

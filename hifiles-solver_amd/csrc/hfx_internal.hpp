@@ -246,6 +246,11 @@ struct hfx_ctx
   double time = 0.0, spinup_time = 0.0;
   int i_steps = 0;
   bool have_clock = false;
+  // point probes (hfx_ctx_set_probes): the fields of every block's samples, the sampling frequency in steps and the samples a
+  // block's device history holds.  probe_epoch: counts the registrations; a block whose history was made for another one makes it anew
+  int n_probe_fields = 0, probe_freq = 1, probe_capacity = 0;
+  int probe_codes[HFX_MAX_PROBE_FIELDS] = {};
+  unsigned long probe_epoch = 0;
   hfx::Phys phys() const
   {
     hfx::Phys P;
@@ -304,6 +309,23 @@ struct BodyForce
 };
 } // namespace hfx
 
+namespace hfx
+{
+// The point probes of one block (probes.hip), sorted by element: position i of the sorted order is probe dest[i] of the caller
+struct Probes
+{
+  int n = 0;
+  DevBuf<double> opp;     // (n_upts, n) operator rows, sorted order
+  DevBuf<int> ele, dest;  // (n) element | the caller's index, sorted order
+  // (n_fields, n, capacity + 1): the samples in the caller's order; the last slot is the scratch of hfx_time_probes
+  DevBuf<double> history;
+  int n_fields = 0, capacity = 0; // what `history` was made for
+  unsigned long epoch = 0;        // ctx->probe_epoch it was made at
+  std::vector<double> times;      // of the stored samples; their number is the number of stored samples
+  std::vector<int> steps;
+};
+} // namespace hfx
+
 struct hfx_eles
 {
   hfx_ctx *ctx = nullptr;
@@ -331,6 +353,8 @@ struct hfx_eles
   int n_average_fields = 0;
   int average_codes[HFX_MAX_AVERAGE_FIELDS] = {};
   hfx::DevBuf<double> disu_average_upts, disu_average_ppts;
+  // point probes (hfx_eles_set_probes)
+  hfx::Probes probes;
   // mass-flux body force (hfx_eles_set_body_force); null: none registered
   std::unique_ptr<hfx::BodyForce> body_force;
   // over-integration (hfx_eles_set_over_int)
@@ -448,8 +472,14 @@ int first_stage_closure_filter(hfx_eles *const *eles, int neb, bool refresh_svv)
 void advance_ramp_counters(hfx_inters *const *faces, int nfb);
 // what the reference's main loop does between the last RK stage and the outputs (src/HiFiLES.cpp:221-245), for a context whose
 // clock is the library's: time += dt, i_steps++, spinup_time at step 1, then the time averages of every block that has average
-// fields (averages.hip).  Nothing for a context without a clock; no launch for a block without average fields
+// fields (averages.hip), then -- when i_steps % probe_freq == 0 -- one sample of every block that has probes (probes.hip).  Nothing
+// for a context without a clock; no launch for a block without average fields or probes
 int end_of_step(hfx_eles *const *eles, int neb);
+// (probes.hip) one sample of e's probes on the compute stream; nothing for a block or a context without probes
+int sample_probes(hfx_eles *e, double time, int step);
+// what every step loop asks before its first launch: can the histories of these blocks take the samples of the next n_steps steps?
+// Nothing to ask without the library's clock or without probes
+int probes_check_capacity(hfx_eles *const *eles, int neb, int n_steps);
 // the `forcing == 1` branch at the first RK stage of a step (src/solver.cpp:96-109): eles::evaluate_body_force of every block that
 // has a body force registered (forcing.hip) -- three launches per such block and, without `comm`, nothing else: no copy, no
 // synchronisation.  With `comm` (the partitioned loops) the two integrals are summed over its ranks between the first and the

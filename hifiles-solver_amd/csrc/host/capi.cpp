@@ -436,6 +436,137 @@ extern "C" int hfxh_case_get_clock(hfxh_case *c, double *time, int *i_steps, dou
   return 0;
 }
 
+// ---- point probes --------------------------------------------------------------------------------------------------------
+static int locate_points(eles *E, int n, const double *positions, int *p2c, double *loc)
+{
+  hf_array<double> pos(E->n_dims), l(E->n_dims);
+  for (int i = 0; i < n; i++)
+  {
+    for (int d = 0; d < E->n_dims; d++) pos(d) = positions[d + (size_t)E->n_dims * i];
+    p2c[i] = E->calc_p2c(pos);
+    if (p2c[i] == -2) { g_err = E->probe_error; return 1; }
+    for (int d = 0; d < E->n_dims; d++) loc[d + (size_t)E->n_dims * i] = 0.0;
+    if (p2c[i] < 0) continue;
+    if (E->pos_to_loc(pos, p2c[i], l)) { g_err = E->probe_error; return 1; }
+    for (int d = 0; d < E->n_dims; d++) loc[d + (size_t)E->n_dims * i] = l(d);
+  }
+  return 0;
+}
+
+static int loc_to_pos(eles *E, int n, const int *ele, const double *loc, double *positions)
+{
+  hf_array<double> pos(E->n_dims), l(E->n_dims);
+  for (int i = 0; i < n; i++)
+  {
+    if (ele[i] < 0 || ele[i] >= E->n_eles) { g_err = "calc_pos: element out of range"; return 1; }
+    for (int d = 0; d < E->n_dims; d++) l(d) = loc[d + (size_t)E->n_dims * i];
+    E->calc_pos_probe(l, ele[i], pos);
+    for (int d = 0; d < E->n_dims; d++) positions[d + (size_t)E->n_dims * i] = pos(d);
+  }
+  return 0;
+}
+
+static int newton_in_element(eles *E, int ele, const double *position, double *loc)
+{
+  if (ele < 0 || ele >= E->n_eles) { g_err = "pos_to_loc: element out of range"; return 1; }
+  hf_array<double> pos(E->n_dims), l(E->n_dims);
+  for (int d = 0; d < E->n_dims; d++) pos(d) = position[d];
+  if (E->pos_to_loc(pos, ele, l)) { g_err = E->probe_error; return 1; }
+  for (int d = 0; d < E->n_dims; d++) loc[d] = l(d);
+  return 0;
+}
+
+static int opp_probe_rows(eles *E, int n, const double *loc, double *opp_probe)
+{
+  hf_array<double> l(E->n_dims);
+  for (int i = 0; i < n; i++)
+  {
+    for (int d = 0; d < E->n_dims; d++) l(d) = loc[d + (size_t)E->n_dims * i];
+    E->set_opp_probe(l);
+    for (int k = 0; k < E->n_upts_per_ele; k++) opp_probe[k + (size_t)E->n_upts_per_ele * i] = E->opp_probe(k);
+  }
+  return 0;
+}
+
+extern "C" int hfxh_case_locate(hfxh_case *c, int n, const double *positions, int *p2c, double *loc) { return locate_points(the_eles(c), n, positions, p2c, loc); }
+extern "C" int hfxh_case_calc_pos(hfxh_case *c, int n, const int *ele, const double *loc, double *positions) { return loc_to_pos(the_eles(c), n, ele, loc, positions); }
+extern "C" int hfxh_case_pos_to_loc(hfxh_case *c, int ele, const double *position, double *loc) { return newton_in_element(the_eles(c), ele, position, loc); }
+extern "C" int hfxh_case_opp_probe(hfxh_case *c, int n, const double *loc, double *opp_probe) { return opp_probe_rows(the_eles(c), n, loc, opp_probe); }
+
+extern "C" int hfxh_case_set_probes(hfxh_case *c, int n, const double *positions, int n_fields, const char *const *names, int probe_freq,
+                                    int capacity)
+{
+  if (!c || n < 0 || (n > 0 && !positions) || n_fields < 0 || (n_fields > 0 && !names)) { g_err = "hfxh_case_set_probes: bad argument"; return 1; }
+  std::vector<std::string> v;
+  for (int i = 0; i < n_fields; i++) v.push_back(names[i] ? names[i] : "");
+  input check; // (the names are checked on a scratch input first: a refusal leaves the case as it was)
+  if (check.set_probe_fields(v, c->S.n_dims, probe_freq, capacity, g_err)) return 1;
+  eles *E = the_eles(c);
+  if (E->locate_probes(n_fields ? n : 0, positions)) { g_err = E->probe_error; return 1; }
+  c->S.run_input.set_probe_fields(v, c->S.n_dims, probe_freq, capacity, g_err);
+  if (RegisterProbeFields(&c->S)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  if (E->register_probes()) { g_err = E->last_error(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_get_probes(hfxh_case *c, int *n_located, const int **p2c, const int **p2t, const double **loc_probe,
+                                    const int **global_index)
+{
+  eles *E = the_eles(c);
+  static thread_local std::vector<int> type;
+  type.assign(E->probe_p2c.size(), E->ele_type); // run_probe.p2t: the element class of each probe (one class per case)
+  if (n_located) *n_located = (int)E->probe_p2c.size();
+  if (p2c) *p2c = E->probe_p2c.data();
+  if (p2t) *p2t = type.data();
+  if (loc_probe) *loc_probe = E->probe_loc.data();
+  if (global_index) *global_index = E->probe_global.data();
+  return 0;
+}
+
+extern "C" int hfxh_case_sample_probes(hfxh_case *c)
+{
+  eles *E = the_eles(c);
+  if (c->S.run_input.n_probe_fields == 0) { g_err = "hfxh_case_sample_probes: the case has no probes"; return 1; }
+  if (!E->device()) { g_err = "case is not on the device"; return 1; }
+  if (hfx_eles_sample_probes(E->device(), c->S.time, c->S.i_steps)) { g_err = hfx_last_error(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_probe_count(hfxh_case *c, int *n_samples, int *n_probes)
+{
+  eles *E = the_eles(c);
+  if (!E->device()) { g_err = "case is not on the device"; return 1; }
+  if (hfx_eles_probe_count(E->device(), n_samples, n_probes)) { g_err = hfx_last_error(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_read_probes(hfxh_case *c, int dimensional, int max_samples, double *times, int *steps, double *values,
+                                     int *n_samples)
+{
+  eles *E = the_eles(c);
+  const input &in = c->S.run_input;
+  if (!E->device()) { g_err = "case is not on the device"; return 1; }
+  if (hfx_eles_read_probes(E->device(), max_samples, times, steps, values, n_samples)) { g_err = hfx_last_error(); return 1; }
+  if (!dimensional || !in.viscous) return 0; /* src/output.cpp:1475-1535: the reference factors of a viscous run */
+  const int nf = in.n_probe_fields;
+  const size_t np = E->probe_p2c.size();
+  for (int s = 0; s < *n_samples; s++) times[s] *= in.time_ref;
+  for (int f = 0; f < nf; f++)
+  {
+    const int code = in.probe_code(f);
+    const double scale = code == HFX_PROBE_RHO ? in.rho_ref : code == HFX_PROBE_E ? in.uvw_ref * in.uvw_ref : code == HFX_PROBE_P ? in.p_ref : in.uvw_ref;
+    for (size_t i = 0; i < np * (size_t)*n_samples; i++) values[f + (size_t)nf * i] *= scale;
+  }
+  return 0;
+}
+
+extern "C" int hfxh_case_ref_values(hfxh_case *c, double ref[5])
+{
+  const input &in = c->S.run_input;
+  ref[0] = in.rho_ref; ref[1] = in.uvw_ref; ref[2] = in.p_ref; ref[3] = in.time_ref; ref[4] = in.viscous;
+  return 0;
+}
+
 // ---- mass-flux body force ------------------------------------------------------------------------------------------------
 extern "C" int hfxh_case_get_forcing(hfxh_case *c, int *body_forcing, double *forcing_area, double *forcing_mdot0)
 {
@@ -616,6 +747,11 @@ extern "C" int hfxh_simplex_get_array(hfxh_simplex *s, const char *name, const d
   for (int i = 0; i < 4; i++) dims[i] = a->get_dim(i);
   return 0;
 }
+
+extern "C" int hfxh_simplex_locate(hfxh_simplex *s, int n, const double *positions, int *p2c, double *loc) { return locate_points(s->E, n, positions, p2c, loc); }
+extern "C" int hfxh_simplex_calc_pos(hfxh_simplex *s, int n, const int *ele, const double *loc, double *positions) { return loc_to_pos(s->E, n, ele, loc, positions); }
+extern "C" int hfxh_simplex_pos_to_loc(hfxh_simplex *s, int ele, const double *position, double *loc) { return newton_in_element(s->E, ele, position, loc); }
+extern "C" int hfxh_simplex_opp_probe(hfxh_simplex *s, int n, const double *loc, double *opp_probe) { return opp_probe_rows(s->E, n, loc, opp_probe); }
 
 extern "C" int hfxh_simplex_destroy(hfxh_simplex *s)
 {

@@ -84,6 +84,23 @@ public:
   int body_force_integrals(double integral[2]);
   int body_force_apply(const double integral[2]);
 
+  // ---- point probes (csrc/host/eles_probes.cpp; run_input.probe, src/probe_input.cpp, src/output.cpp:1440-1545)
+  int calc_p2c(const hf_array<double> &in_pos); // the class's calc_p2c: the element that holds in_pos, -1 none, -2 shape not implemented (probe_error)
+  int pos_to_loc(const hf_array<double> &in_pos, int in_ele, hf_array<double> &out_loc); // src/eles.cpp:5992; non-zero: no convergence
+  void set_opp_probe(const hf_array<double> &in_loc);                                    // src/eles.cpp:3625 -> opp_probe (n_upts)
+  void calc_pos_probe(const hf_array<double> &in_loc, int in_ele, hf_array<double> &out_pos); // calc_pos, for callers outside the class
+  hf_array<double> opp_probe;
+  // the located probes of this class: element (run_probe.p2c), index in the caller's list, reference location (n_dims each),
+  // operator rows (n_upts each)
+  std::vector<int> probe_p2c, probe_global;
+  std::vector<double> probe_loc, probe_opp;
+  int locate_probes(int n, const double *positions); // locate positions (n_dims, n), keep what lies in this class (host only)
+  std::string probe_error;                           // why calc_p2c / pos_to_loc / locate_probes refused (the block itself stays usable)
+  int register_probes();                          // -> hfx_eles_set_probes (empties the device history)
+  void sample_probes(double time, int step);      // one sample on the device
+  // the shape nodes that span the plane of local face in_face (calc_p2c); returns the number of faces, -1: shape not implemented
+  virtual int face_plane_vertices(int in_n_spts, int in_face, int v[3]) const = 0;
+
   // ---- getters used by face wiring (src/eles.cpp:4638-4949 return pointers; here: offsets)
   int get_n_eles() const { return n_eles; }
   int get_n_dims() const { return n_dims; }
@@ -173,6 +190,7 @@ protected:
 class eles_hexas : public eles
 {
 public:
+  int face_plane_vertices(int in_n_spts, int in_face, int v[3]) const override;
   int set_inters_cubpts() override;
   double compute_inter_detjac_inters_cubpts(int in_inter, const hf_array<double> &d_pos) override; // src/eles_hexas.cpp:395
 
@@ -187,6 +205,9 @@ protected:
 
 class eles_quads : public eles
 {
+public:
+  int face_plane_vertices(int in_n_spts, int in_face, int v[3]) const override;
+
 protected:
   int setup_ele_type_specific() override;
   double eval_nodal_basis(int in_index, const hf_array<double> &in_loc) override;
@@ -200,6 +221,9 @@ protected:
 // metrics: csrc/host/eles_simplex.cpp.  4-node / 6-node (straight-sided) shapes.
 class eles_tets : public eles
 {
+public:
+  int face_plane_vertices(int in_n_spts, int in_face, int v[3]) const override;
+
 protected:
   int setup_ele_type_specific() override;
   double eval_nodal_basis(int in_index, const hf_array<double> &in_loc) override;
@@ -217,6 +241,7 @@ protected:
 class eles_pris : public eles
 {
 public:
+  int face_plane_vertices(int in_n_spts, int in_face, int v[3]) const override;
   eles_pris();
   ~eles_pris() override;
   int n_upts_tri = 0;

@@ -110,6 +110,32 @@ int input::average_code(int i) const
   return (int)(std::find(AVERAGE_NAMES, AVERAGE_NAMES + 5, average_fields[i]) - AVERAGE_NAMES);
 }
 
+static const char *const PROBE_NAMES[6] = {"rho", "u", "v", "w", "specific_total_energy", "pressure"}; /* src/output.cpp:1482-1522 */
+
+int input::set_probe_fields(const std::vector<std::string> &names, int n_dims, int freq, int capacity, std::string &err)
+{
+  std::vector<std::string> lower(names);
+  for (std::string &s : lower)
+  {
+    std::transform(s.begin(), s.end(), s.begin(), [](unsigned char c) { return (char)std::tolower(c); });
+    const char *const *hit = std::find(PROBE_NAMES, PROBE_NAMES + 6, s);
+    if (hit == PROBE_NAMES + 6) { err = "Probe field not implemented yet! (" + s + ")"; return 1; } /* src/output.cpp:1538 */
+    if (hit - PROBE_NAMES == HFX_PROBE_W && n_dims != 3) { err = "2 dimensional elements don't have z velocity"; return 1; } /* :1513 */
+  }
+  if ((int)lower.size() > HFX_MAX_PROBE_FIELDS) { err = "probe fields: too many fields"; return 1; }
+  if (!lower.empty() && freq < 1) { err = "probe_freq must be at least 1"; return 1; }
+  if (!lower.empty() && capacity < 1) { err = "probes: a history of at least one sample"; return 1; }
+  probe_fields.swap(lower);
+  n_probe_fields = (int)probe_fields.size();
+  if (n_probe_fields) { probe_freq = freq; probe_capacity = capacity; }
+  return 0;
+}
+
+int input::probe_code(int i) const
+{
+  return (int)(std::find(PROBE_NAMES, PROBE_NAMES + 6, probe_fields[i]) - PROBE_NAMES);
+}
+
 void input::fill(hfx_params &p) const
 {
   p.gamma = gamma; p.prandtl = prandtl; p.rt_inf = rt_inf; p.mu_inf = mu_inf; p.c_sth = c_sth; p.fix_vis = fix_vis;

@@ -52,6 +52,14 @@ struct input
   int set_average_fields(const std::vector<std::string> &names, int n_dims, std::string &err);
   // HFX_AVG_* of average_fields(i)
   int average_code(int i) const;
+  // ---- point probes (run_input.probe, src/probe_input.cpp): the field names of rho, u, v, w, specific_total_energy, pressure,
+  // lower-cased as probe_input::read_probe_input does; probe_freq in steps; probe_capacity: the samples the device history holds
+  // (a key of this mirror: the reference writes every sample to a file at once)
+  std::vector<std::string> probe_fields;
+  int n_probe_fields = 0, probe_freq = 1, probe_capacity = 0;
+  // a name outside the six, w in a two-dimensional run, probe_freq < 1 and capacity < 1 are refused and leave everything as it was
+  int set_probe_fields(const std::vector<std::string> &names, int n_dims, int freq, int capacity, std::string &err);
+  int probe_code(int i) const; // HFX_PROBE_* of probe_fields(i)
   // ---- mass-flux body force of periodic channels (`body_forcing`, src/input.cpp:312).  forcing_area and forcing_mdot0 are keys of
   // this mirror: the inflow area and the target mass flux, which the reference hard-codes to 9.162 both (src/eles.cpp:5393-5395);
   // forcing_history: evaluations whose massflux.dat columns the device keeps

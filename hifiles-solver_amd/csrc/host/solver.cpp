@@ -455,6 +455,17 @@ int InitSolution(solution *S)
   return 0;
 }
 
+// run_input's probe fields, frequency and history size -> the context (every block's history starts empty)
+int RegisterProbeFields(solution *S)
+{
+  if (!S->ctx) return 0; // (MoveToDevice registers them)
+  const input &in = S->run_input;
+  int codes[HFX_MAX_PROBE_FIELDS];
+  for (int i = 0; i < in.n_probe_fields; i++) codes[i] = in.probe_code(i);
+  if (hfx_ctx_set_probes(S->ctx, in.n_probe_fields, codes, in.probe_freq, in.probe_capacity)) { S->err = hfx_last_error(); return 1; }
+  return 0;
+}
+
 int MoveToDevice(solution *S, int device)
 {
   if (hfx_ctx_create(device, &S->ctx)) { S->err = hfx_last_error(); return 1; }
@@ -463,6 +474,7 @@ int MoveToDevice(solution *S, int device)
   if (hfx_ctx_set_params(S->ctx, &p)) { S->err = hfx_last_error(); return 1; }
   if (S->run_input.dt_type != 0 && hfx_ctx_set_CFL(S->ctx, S->run_input.CFL)) { S->err = hfx_last_error(); return 1; }
   if (hfx_ctx_set_option(S->ctx, "deferred", S->deferred ? 1 : 0)) { S->err = hfx_last_error(); return 1; }
+  if (RegisterProbeFields(S)) return 1; // (before the element blocks, which register their probes)
   for (int i = 0; i < S->n_ele_types; i++)
     if (S->mesh_eles(i) && S->mesh_eles(i)->get_n_eles() != 0)
       if (S->mesh_eles(i)->mv_all_cpu_gpu(S->ctx)) { S->err = S->mesh_eles(i)->last_error(); return 1; }
@@ -642,6 +654,16 @@ static int advance_ramp(solution *FlowSol)
   return 0;
 }
 
+// one sample of every class's probes at the solution's time and step; !always: only when i_steps % probe_freq == 0, the
+// reference's condition (src/HiFiLES.cpp:289).  Errors are left with the element class (RunSteps reports them)
+void SampleProbes(solution *FlowSol, bool always)
+{
+  const input &in = FlowSol->run_input;
+  if (in.n_probe_fields == 0 || (!always && FlowSol->i_steps % in.probe_freq != 0)) return;
+  for (int j = 0; j < FlowSol->n_ele_types; j++)
+    if (FlowSol->mesh_eles(j)) FlowSol->mesh_eles(j)->sample_probes(FlowSol->time, FlowSol->i_steps);
+}
+
 // src/HiFiLES.cpp:223,241-245 behind `time += dt`: the step counter, the spin-up time at the first step, the time averages
 static void count_step_and_average(solution *FlowSol)
 {
@@ -650,6 +672,7 @@ static void count_step_and_average(solution *FlowSol)
   if (FlowSol->run_input.n_average_fields)
     for (int j = 0; j < FlowSol->n_ele_types; j++)
       if (FlowSol->mesh_eles(j)) FlowSol->mesh_eles(j)->CalcTimeAverageQuantities(FlowSol->time);
+  SampleProbes(FlowSol, false); /* src/HiFiLES.cpp:289-297 */
 }
 
 int RunSteps(solution *FlowSol, int n_steps)
@@ -849,6 +872,7 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
     in.time = FlowSol->time;
     if (advance_ramp(FlowSol)) return 1;
     count_step_and_average(FlowSol);
+    if (E->failed()) { FlowSol->err = E->last_error(); return 1; }
   }
   // the exchange started after the last stage belongs to a stage that is not run: complete it so that
   // no request is left in flight (a following call starts over with `first`)

@@ -77,6 +77,10 @@ int GeoPreprocess_box(solution *FlowSol, const box_mesh &mesh);
 int InitSolution(solution *FlowSol);
 // move everything to the device (the reference's mv_all_cpu_gpu calls, src/geometry.cpp:310-320,552-557)
 int MoveToDevice(solution *FlowSol, int device);
+// point probes: run_input's probe fields -> the context (hfx_ctx_set_probes); one sample of every element class at the solution's
+// time and step (always, or under the reference's condition i_steps % probe_freq == 0)
+int RegisterProbeFields(solution *S);
+void SampleProbes(solution *FlowSol, bool always);
 // switch deferred execution on / off (before or after MoveToDevice)
 int SetDeferred(solution *FlowSol, bool on);
 

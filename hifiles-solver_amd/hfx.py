@@ -26,6 +26,10 @@ ip = C.POINTER(C.c_int)
 AVG_RHO, AVG_U, AVG_V, AVG_W, AVG_E = range(5)
 AVERAGE_NAMES = ("rho_average", "u_average", "v_average", "w_average", "e_average")
 
+# hfx_probe_field: the reference's probe field names (src/output.cpp:1482-1522) in the order of their codes
+PROBE_RHO, PROBE_U, PROBE_V, PROBE_W, PROBE_E, PROBE_P = range(6)
+PROBE_NAMES = ("rho", "u", "v", "w", "specific_total_energy", "pressure")
+
 
 class Les(C.Structure):
     _fields_ = [("sgs_model", C.c_int), ("pad", C.c_int), ("C_s", C.c_double), ("filter_ratio", C.c_double),
@@ -146,6 +150,28 @@ def body_force_history_of(call, max_rows):
     return rows[:, :n.value].T.copy()
 
 
+def set_probes_of(eles_handle, n_upts, ele, opp_probe):
+    el = np.ascontiguousarray(np.array(ele, dtype=np.int32).ravel())
+    opp = _f(np.array(opp_probe, dtype=np.float64).reshape((n_upts, len(el)), order="F"))
+    check(lib().hfx_eles_set_probes(eles_handle, C.c_int(len(el)), el.ctypes.data_as(ip), opp.ctypes.data_as(dp)))
+
+
+def probe_count_of(eles_handle):
+    ns, n = C.c_int(0), C.c_int(0)
+    check(lib().hfx_eles_probe_count(eles_handle, C.byref(ns), C.byref(n)))
+    return ns.value, n.value
+
+
+def read_probes_of(eles_handle, n_fields):
+    ns, n = probe_count_of(eles_handle)
+    times, steps = np.zeros(max(1, ns)), np.zeros(max(1, ns), dtype=np.int32)
+    values = np.zeros((n_fields, n, max(1, ns)), order="F")
+    got = C.c_int(0)
+    check(lib().hfx_eles_read_probes(eles_handle, C.c_int(ns), times.ctypes.data_as(dp), steps.ctypes.data_as(ip),
+                                     values.ctypes.data_as(dp), C.byref(got)))
+    return times[:got.value].copy(), steps[:got.value].copy(), values[:, :, :got.value].copy(order="F")
+
+
 class Context:
     def __init__(self, device=0):
         self.h = C.c_void_p()
@@ -187,6 +213,13 @@ class Context:
         t, n, s = C.c_double(0), C.c_int(0), C.c_double(0)
         check(lib().hfx_ctx_get_clock(self.h, C.byref(t), C.byref(n), C.byref(s)))
         return t.value, n.value, s.value
+
+    def set_probes(self, fields, probe_freq=1, capacity=1):
+        """fields: PROBE_* codes or the reference's names (rho, u, v, w, specific_total_energy, pressure); [] drops them"""
+        codes = [PROBE_NAMES.index(f.lower()) if isinstance(f, str) else int(f) for f in fields]
+        a = (C.c_int * max(1, len(codes)))(*codes)
+        check(lib().hfx_ctx_set_probes(self.h, C.c_int(len(codes)), a, C.c_int(probe_freq), C.c_int(capacity)))
+        self.n_probe_fields = len(codes)
 
     def flush(self):
         """deferred execution: run what has been recorded (no-op otherwise)"""
@@ -293,6 +326,26 @@ class Eles:
         out = np.zeros((self.n_ppts, self.n_eles, self.n_average_fields), dtype=np.float64, order="F")
         check(lib().hfx_eles_calc_time_average_ppts(self.h, out.ctypes.data_as(dp)))
         return out
+
+    def set_probes(self, ele, opp_probe):
+        """ele (n_probes): the element of each probe; opp_probe (n_upts, n_probes): its operator row as a column"""
+        return set_probes_of(self.h, self.n_upts, ele, opp_probe)
+
+    def sample_probes(self, time, step):
+        self._call("hfx_eles_sample_probes", C.c_double(time), C.c_int(step))
+
+    def probe_count(self):
+        """(stored samples, registered probes)"""
+        return probe_count_of(self.h)
+
+    def read_probes(self):
+        """(times (n_samples), steps (n_samples), values (n_fields, n_probes, n_samples)); empties the history"""
+        return read_probes_of(self.h, getattr(self.ctx, "n_probe_fields", 0))
+
+    def time_probes(self, reps=20):
+        v = C.c_double(0)
+        check(lib().hfx_time_probes(self.h, C.c_int(reps), C.byref(v)))
+        return v.value
 
     def set_body_force(self, face_ele, face_inter, opp_inters_cubpts, weight_inters_cubpts, inter_detjac_inters_cubpts, area, mdot0,
                        history_capacity=64):

@@ -76,6 +76,36 @@ def check(rc):
         raise hfx.HfxError(lib().hfxh_last_error().decode())
 
 
+def _locate(fn, handle, n_dims, positions):
+    pos = np.asfortranarray(np.array(positions, dtype=np.float64).reshape((n_dims, -1), order="F"))
+    n = pos.shape[1]
+    p2c, loc = np.zeros(max(1, n), dtype=np.int32), np.zeros((n_dims, max(1, n)), order="F")
+    check(fn(handle, C.c_int(n), pos.ctypes.data_as(dp), p2c.ctypes.data_as(ip), loc.ctypes.data_as(dp)))
+    return p2c[:n].copy(), loc[:, :n].copy(order="F")
+
+
+def _calc_pos(fn, handle, n_dims, ele, loc):
+    el = np.ascontiguousarray(np.array(ele, dtype=np.int32).ravel())
+    l = np.asfortranarray(np.array(loc, dtype=np.float64).reshape((n_dims, len(el)), order="F"))
+    pos = np.zeros((n_dims, max(1, len(el))), order="F")
+    check(fn(handle, C.c_int(len(el)), el.ctypes.data_as(ip), l.ctypes.data_as(dp), pos.ctypes.data_as(dp)))
+    return pos[:, :len(el)].copy(order="F")
+
+
+def _pos_to_loc(fn, handle, n_dims, ele, position):
+    pos = np.ascontiguousarray(np.array(position, dtype=np.float64).ravel())
+    loc = np.zeros(n_dims)
+    check(fn(handle, C.c_int(int(ele)), pos.ctypes.data_as(dp), loc.ctypes.data_as(dp)))
+    return loc
+
+
+def _opp_probe(fn, handle, n_dims, n_upts, loc):
+    l = np.asfortranarray(np.array(loc, dtype=np.float64).reshape((n_dims, -1), order="F"))
+    out = np.zeros((n_upts, max(1, l.shape[1])), order="F")
+    check(fn(handle, C.c_int(l.shape[1]), l.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    return out[:, :l.shape[1]].copy(order="F")
+
+
 class Case:
     def __init__(self, n, xv=None, loc_1d_upts=None, rank=0, pgrid=None, bcs=None, sides=None, self_partition=None, **kw):
         """n: cells per direction of THIS rank's block; pgrid: ranks per direction (None: one rank).
@@ -372,6 +402,66 @@ class Case:
         check(lib().hfxh_case_get_clock(self.h, C.byref(t), C.byref(n), C.byref(s)))
         return t.value, n.value, s.value
 
+    # ---- point probes
+    def locate(self, positions):
+        """calc_p2c + pos_to_loc of positions (n_dims, n): (p2c (n), -1 where no element holds the point; loc (n_dims, n))"""
+        return _locate(lib().hfxh_case_locate, self.h, self.n_dims, positions)
+
+    def calc_pos(self, ele, loc):
+        """physical positions (n_dims, n) of the reference locations loc (n_dims, n) in the elements ele (n)"""
+        return _calc_pos(lib().hfxh_case_calc_pos, self.h, self.n_dims, ele, loc)
+
+    def pos_to_loc(self, ele, position):
+        return _pos_to_loc(lib().hfxh_case_pos_to_loc, self.h, self.n_dims, ele, position)
+
+    def opp_probe(self, loc):
+        """eles::set_opp_probe at every column of loc (n_dims, n): (n_upts, n)"""
+        return _opp_probe(lib().hfxh_case_opp_probe, self.h, self.n_dims, self.n_upts, loc)
+
+    def set_probes(self, positions, fields, probe_freq=1, capacity=1):
+        """positions (n_dims, n) physical; fields: the reference's names (rho, u, v, w, specific_total_energy, pressure)"""
+        pos = np.asfortranarray(np.array(positions, dtype=np.float64).reshape((self.n_dims, -1), order="F"))
+        a = (C.c_char_p * max(1, len(fields)))(*[f.encode() for f in fields])
+        check(lib().hfxh_case_set_probes(self.h, C.c_int(pos.shape[1]), pos.ctypes.data_as(dp), C.c_int(len(fields)), a,
+                                         C.c_int(probe_freq), C.c_int(capacity)))
+        self.n_probe_fields = len(fields)
+
+    def probes(self):
+        """the located probes: dict(p2c, p2t, loc_probe (n_dims, n_located), global_index)"""
+        n, p2c, p2t, loc, gi = C.c_int(0), ip(), ip(), dp(), ip()
+        check(lib().hfxh_case_get_probes(self.h, C.byref(n), C.byref(p2c), C.byref(p2t), C.byref(loc), C.byref(gi)))
+        k = n.value
+        if k == 0:
+            z = np.zeros(0, dtype=np.int32)
+            return {"p2c": z, "p2t": z.copy(), "loc_probe": np.zeros((self.n_dims, 0)), "global_index": z.copy()}
+        iarr = lambda p: np.ctypeslib.as_array(p, shape=(k,)).copy()
+        return {"p2c": iarr(p2c), "p2t": iarr(p2t), "global_index": iarr(gi),
+                "loc_probe": np.ctypeslib.as_array(loc, shape=(k * self.n_dims,)).copy().reshape((self.n_dims, k), order="F")}
+
+    def sample_probes(self):
+        check(lib().hfxh_case_sample_probes(self.h))
+
+    def probe_count(self):
+        ns, n = C.c_int(0), C.c_int(0)
+        check(lib().hfxh_case_probe_count(self.h, C.byref(ns), C.byref(n)))
+        return ns.value, n.value
+
+    def read_probes(self, dimensional=False):
+        """(times, steps, values (n_fields, n_located, n_samples)); dimensional: the reference factors of a viscous case"""
+        ns, n = self.probe_count()
+        times, steps = np.zeros(max(1, ns)), np.zeros(max(1, ns), dtype=np.int32)
+        values = np.zeros((getattr(self, "n_probe_fields", 0), n, max(1, ns)), order="F")
+        got = C.c_int(0)
+        check(lib().hfxh_case_read_probes(self.h, C.c_int(1 if dimensional else 0), C.c_int(ns), times.ctypes.data_as(dp),
+                                          steps.ctypes.data_as(ip), values.ctypes.data_as(dp), C.byref(got)))
+        return times[:got.value].copy(), steps[:got.value].copy(), values[:, :, :got.value].copy(order="F")
+
+    def ref_values(self):
+        """dict(rho_ref, uvw_ref, p_ref, time_ref, viscous)"""
+        v = (C.c_double * 5)()
+        check(lib().hfxh_case_ref_values(self.h, v))
+        return dict(zip(("rho_ref", "uvw_ref", "p_ref", "time_ref", "viscous"), list(v)))
+
     def forcing(self):
         """(body_forcing, forcing_area, forcing_mdot0) as the case holds them"""
         on, a, m = C.c_int(0), C.c_double(0), C.c_double(0)
@@ -432,6 +522,7 @@ class Simplex:
         x1 = None if loc_1d_upts is None else np.ascontiguousarray(np.array(loc_1d_upts, dtype=np.float64))
         self.h = C.c_void_p()
         k = Simplex.Keys(vcjh_scheme, c, SGS_model, filter_type, filter_ratio, shock_cap, expf_fac, expf_order, expf_cutoff)
+        self.n_dims, self.n_eles = 3, shp.shape[2]
         check(lib().hfxh_simplex_create_keys(C.c_int(ele_type), C.c_int(order), C.c_int(viscous), C.c_int(shp.shape[2]),
                                              C.c_int(shp.shape[1]), shp.ctypes.data_as(dp), None if x1 is None else x1.ctypes.data_as(dp),
                                              C.byref(k), C.byref(self.h)))
@@ -445,6 +536,18 @@ class Simplex:
             dims.pop()
         n = int(np.prod(dims))
         return np.ctypeslib.as_array(p, shape=(n,)).copy().reshape(dims, order="F")
+
+    def locate(self, positions):
+        return _locate(lib().hfxh_simplex_locate, self.h, 3, positions)
+
+    def calc_pos(self, ele, loc):
+        return _calc_pos(lib().hfxh_simplex_calc_pos, self.h, 3, ele, loc)
+
+    def pos_to_loc(self, ele, position):
+        return _pos_to_loc(lib().hfxh_simplex_pos_to_loc, self.h, 3, ele, position)
+
+    def opp_probe(self, loc):
+        return _opp_probe(lib().hfxh_simplex_opp_probe, self.h, 3, self.array("loc_upts").shape[1], loc)
 
     def close(self):
         if self.h:

@@ -183,7 +183,8 @@ int hfx_ctx_get_dt(hfx_ctx *ctx, double *dt);
  * hfx_run_steps, hfx_run_steps_blocks, hfx_run_steps_partitioned and hfx_run_steps_partitioned_blocks do after EVERY time step
  * what the reference's main loop does there: time += run_input.dt; i_steps++; if (i_steps == 1) spinup_time = time; and then
  * eles::CalcTimeAverageQuantities of every block that registered average fields (hfx_eles_set_average_fields) -- one more
- * kernel per such block and step on the compute stream, nothing at all for a context without average fields.  A context
+ * kernel per such block and step on the compute stream, nothing at all for a context without average fields -- and, when
+ * i_steps % probe_freq == 0, one sample of every block that has probes (hfx_ctx_set_probes, hfx_eles_set_probes).  A context
  * whose clock was never set is the caller's to time: its loops touch neither the clock nor the averages, and the caller calls
  * hfx_eles_CalcTimeAverageQuantities itself where the reference does.  spinup_time is kept across calls (0 in a new
  * context); setting i_steps = 0 makes the next step the one that sets it, which restarts the averages' weights as a restarted
@@ -351,6 +352,49 @@ int hfx_eles_CalcTimeAverageQuantities(hfx_eles *e, double time, double spinup_t
  * (n_ppts, n_eles, n_average_fields) = opp_p . disu_average_upts, with the operator of hfx_eles_set_opp_p and the
  * contraction of hfx_eles_calc_disu_ppts, written to the HOST array the plot writer reads */
 int hfx_eles_calc_time_average_ppts(hfx_eles *e, double *disu_average_ppts_host);
+
+/* ---- point probes (run_input.probe, probe_input, output::write_probe; src/HiFiLES.cpp:287-297) --------------------------
+ * Time series of the flow at points: a probe is an element and one operator row, opp_probe(i) = eval_nodal_basis(i, loc)
+ * (src/eles.cpp:3625-3631); a sample is the state interpolated to the probe and the registered fields formed from it
+ * (src/output.cpp:1479-1538).  The history of samples lives on the device; the caller reads it when it wants to write.
+ * Values are in the library's non-dimensional units. */
+enum hfx_probe_field
+{
+  HFX_PROBE_RHO = 0, /* "rho": field 0 */
+  HFX_PROBE_U = 1,   /* "u": field 1 / rho */
+  HFX_PROBE_V = 2,   /* "v": field 2 / rho */
+  HFX_PROBE_W = 3,   /* "w": field 3 / rho (three-dimensional blocks only) */
+  HFX_PROBE_E = 4,   /* "specific_total_energy": field n_dims + 1 / rho */
+  HFX_PROBE_P = 5    /* "pressure": (gamma - 1) (E - 0.5 rho |v|^2), |v|^2 over n_dims components, E = field n_dims + 1 */
+};
+#define HFX_MAX_PROBE_FIELDS 16
+/* The probe fields of the context: codes[n_fields] in the order of the input file (names may repeat), the sampling
+ * frequency probe_freq >= 1 (steps) and the number of samples the device history of every block holds.  n_fields = 0 drops
+ * everything: no block samples any more and every block's history is emptied (its probes stay registered).  Changing the
+ * fields empties the histories of the blocks registered so far. */
+int hfx_ctx_set_probes(hfx_ctx *ctx, int n_fields, const int *codes, int probe_freq, int capacity);
+/* The probes of one block: ele[n_probes] the element of each probe (0 <= ele < n_eles, checked here), opp_probe
+ * (n_upts, n_probes) column-major.  Registering again replaces the probes and empties the history; a failed registration
+ * leaves the block as it was; n_probes = 0 removes them (a block of a mixed mesh may have none).  HFX_PROBE_W among the
+ * context's fields is refused on a two-dimensional block.  The library sorts the probes by element internally (probes of
+ * one element read the same cache lines); every result is in the caller's order.  Removing a probe that two ranks both
+ * locate on their common face is the caller's (the reference all-gathers for it). */
+int hfx_eles_set_probes(hfx_eles *e, int n_probes, const int *ele, const double *opp_probe);
+/* ONE sample: a single launch on the compute stream writes n_fields x n_probes doubles into the next free slot of the
+ * device history; the host notes `time` and `step` for that slot (no synchronisation).  With deferred execution a recorded
+ * stage runs first.  A full history is refused, nothing is overwritten.  Two samples of one state are equal bit for bit (no
+ * atomics, a fixed summation order).  Once the clock is the library's (hfx_ctx_set_clock) every step loop does this itself for
+ * every block with probes after each step with i_steps % probe_freq == 0 (src/HiFiLES.cpp:289-297), behind the time
+ * averages; such a loop first counts the samples it will take and refuses the whole call, before its first launch, when a
+ * block's history cannot hold them.  Without the clock the caller samples. */
+int hfx_eles_sample_probes(hfx_eles *e, double time, int step);
+/* the number of stored samples (no copy, no synchronisation) and of registered probes; either pointer may be NULL */
+int hfx_eles_probe_count(hfx_eles *e, int *n_samples, int *n_probes);
+/* Synchronises, copies the history -- values (n_fields, n_probes, n_samples) with the field index fastest, times and steps
+ * (n_samples) -- and empties it.  max_samples: what the caller's arrays hold; fewer than stored is refused, nothing is lost. */
+int hfx_eles_read_probes(hfx_eles *e, int max_samples, double *times, int *steps, double *values, int *n_samples);
+/* device milliseconds of one sampling launch, averaged over `reps` launches into a scratch slot (the history is untouched) */
+int hfx_time_probes(hfx_eles *e, int reps, double *ms);
 
 /* ---- mass-flux body force of driven periodic channels (run_input.forcing, src/input.cpp:312) ---------------------------
  * The `forcing == 1` branch of CalcResidual (src/solver.cpp:96-109): at the first RK stage of every time step

@@ -218,6 +218,45 @@ int hfxh_case_calc_time_average_ppts(hfxh_case *c, const double **out, int dims[
 /* FlowSol.time, i_steps (time steps of this run; a restart read resets it) and run_input.spinup_time; any pointer may be NULL */
 int hfxh_case_get_clock(hfxh_case *c, double *time, int *i_steps, double *spinup_time);
 
+/* ---- point probes (run_input.probe; src/probe_input.cpp, output::write_probe src/output.cpp:1440-1545) -------------------------
+ * positions (n_dims, n) column-major, physical; names[n_fields] out of rho, u, v, w, specific_total_energy, pressure in any letter
+ * case (stored lower-cased, as probe_input::read_probe_input does); probe_freq in steps; capacity: the samples the device
+ * history holds between two reads.  The case locates every point -- calc_p2c of the element class (the first element for which
+ * the point and the centroid lie on the same side of every face plane), then eles::pos_to_loc (Newton from 0, until the step
+ * is at most 1e-6; a point that does not converge within 50 iterations is an error, where the reference loops for ever) -- and
+ * builds each probe's operator row (eles::set_opp_probe).  A point found in no element is not this rank's and is left out, as
+ * in the reference.  A point on the face of two ranks is located by both: removing the duplicate needs the reference's
+ * all-gather and is the CALLER'S.  A refusal leaves the case as it was.  n_fields = 0 drops the probes.
+ * A case on the device registers at once (hfx_ctx_set_probes, hfx_eles_set_probes), hfxh_case_to_device does otherwise.
+ * hfxh_case_run and hfxh_case_run_partitioned then sample after every step with i_steps % probe_freq == 0, behind the time
+ * averages (src/HiFiLES.cpp:289-297). */
+int hfxh_case_set_probes(hfxh_case *c, int n, const double *positions, int n_fields, const char *const *names, int probe_freq,
+                         int capacity);
+/* the located probes: their element (run_probe.p2c), element class (p2t), reference location loc_probe (n_dims, n_located)
+ * and index in the positions given (global_index); any pointer may be NULL */
+int hfxh_case_get_probes(hfxh_case *c, int *n_located, const int **p2c, const int **p2t, const double **loc_probe,
+                         const int **global_index);
+/* one sample now, at the case's time and step (hfx_eles_sample_probes) */
+int hfxh_case_sample_probes(hfxh_case *c);
+int hfxh_case_probe_count(hfxh_case *c, int *n_samples, int *n_probes);
+/* hfx_eles_read_probes of the case's block: values (n_fields, n_located, n_samples).  dimensional != 0, and only for a viscous
+ * case: rho * rho_ref, u v w * uvw_ref, specific_total_energy * uvw_ref^2, pressure * p_ref, times * time_ref
+ * (src/output.cpp:1475-1535) */
+int hfxh_case_read_probes(hfxh_case *c, int dimensional, int max_samples, double *times, int *steps, double *values, int *n_samples);
+/* {rho_ref, uvw_ref, p_ref, time_ref, viscous} of the case */
+int hfxh_case_ref_values(hfxh_case *c, double ref[5]);
+/* the pieces, for n points at once: calc_p2c + pos_to_loc (p2c[i] = -1 and loc = 0 for a point in no element); calc_pos of
+ * (ele[i], loc(:, i)); pos_to_loc in a given element; opp_probe (n_upts, n) at loc (n_dims, n).  The _simplex_ forms: the same on
+ * the tetrahedra / prisms of an hfxh_simplex */
+int hfxh_case_locate(hfxh_case *c, int n, const double *positions, int *p2c, double *loc);
+int hfxh_case_calc_pos(hfxh_case *c, int n, const int *ele, const double *loc, double *positions);
+int hfxh_case_pos_to_loc(hfxh_case *c, int ele, const double *position, double *loc);
+int hfxh_case_opp_probe(hfxh_case *c, int n, const double *loc, double *opp_probe);
+int hfxh_simplex_locate(hfxh_simplex *s, int n, const double *positions, int *p2c, double *loc);
+int hfxh_simplex_calc_pos(hfxh_simplex *s, int n, const int *ele, const double *loc, double *positions);
+int hfxh_simplex_pos_to_loc(hfxh_simplex *s, int ele, const double *position, double *loc);
+int hfxh_simplex_opp_probe(hfxh_simplex *s, int n, const double *loc, double *opp_probe);
+
 /* ---- mass-flux body force (hfxh_case_desc.body_forcing) ------------------------------------------------------------------
  * the surface cubature is read with hfxh_case_get_array: opp_inters_cubpts_<l>, weight_inters_cubpts_<l>, loc_inters_cubpts_<l>,
  * tnorm_inters_cubpts_<l>, inter_detjac_inters_cubpts_<l> (n_cubpts, n_eles), norm_inters_cubpts_<l> (n_cubpts, n_eles, n_dims)
