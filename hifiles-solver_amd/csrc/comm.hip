@@ -268,6 +268,7 @@ int partitioned_stage(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_
   PartitionedSplit s; // the steps of this stage, and its plan
   if (s.init(e, int_faces, n_int, mpi_faces, n_mpi, rk)) return 1;
   const SplitPlan &pl = s.stage->pl; // projected: variant 3 sends the projected viscous flux
+  note_gradients(e, pl.variant != 3); // (what the stage will have left once its launches below are made; deferred.hip overrides it)
   // third message: the SGS flux (src/solver.cpp:168-178,203-206) -- variant 2 only; in variant 3 it is part of the projected flux
   const bool les = e->les_ready && !pl.projected;
   hipStream_t st = ctx->stream, cs = comm->stream;
@@ -427,6 +428,7 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
   // values of the filtered state
   if (shock && general_shock_capture(eles, neb)) return 1;
   if (mpi_all(MpiKernel::pack_solution)) return 1;
+  for (int i = 0; i < neb; i++) note_gradients(eles[i], false); // (the general stage keeps them on chip)
   return start_exchange(comm, mpi_faces, n_mpi, 0, false);
 }
 

@@ -1196,6 +1196,7 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
     if (end_of_step(&e, 1)) return 1; /* src/HiFiLES.cpp:221-245 */
   }
+  note_gradients(e, pl.variant != 3);
   return 0;
 }
 
@@ -1273,6 +1274,7 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
     fprintf(stderr, "   (wait state | bar1 | issue state, wait metrics | bar2 | bar3 | issue metrics | bar4)  total %lld\n", h[3 * 16 + 7] - h[3 * 16]);
   }
   snprintf(names, names_len, "%s%s", pl.names, pl.extra_names);
+  note_gradients(e, pl.variant != 3);
   return 0;
 }
 

@@ -1266,6 +1266,7 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
     if (end_of_step(eles, neb)) return 1; /* src/HiFiLES.cpp:221-245 */
   }
+  for (int i = 0; i < neb; i++) note_gradients(eles[i], false); // (the general stage keeps them on chip)
   return 0;
 }
 
@@ -1304,6 +1305,7 @@ int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *face
     }
   for (auto &x : ev) (void)hipEventDestroy(x);
   for (int i = 0; i < 8; i++) ms[i] = (i < 4) ? acc[i] / reps : 0.0;
+  for (int i = 0; i < neb; i++) note_gradients(eles[i], false);
   for (int i = 0; i < neb; i++)
   {
     GeneralData *g = eles[i]->general.get();

@@ -665,9 +665,7 @@ int hfx_eles_download(hfx_eles *e, int id, double *host)
   HFX_CHECK(e->arr[id], "hfx_eles_download: array %d was never uploaded", id);
   HFX_IMMEDIATE(e->ctx, 1u << id);
   // (whether or not the context defers now: the option switched off after a fused stage does not make its arrays current)
-  HFX_CHECK(!(e->stale & (1u << id)),
-            "hfx_eles_download: array %d was not materialised by the fused stage that ran last (deferred execution): read it before the "
-            "next stage begins", id);
+  HFX_CHECK_CURRENT(e, id, "hfx_eles_download");
   HFX_HIP(hipStreamSynchronize(e->ctx->stream));
   HFX_HIP(hipMemcpy(host, e->arr[id], sizeof(double) * (size_t)e->arr_len[id], hipMemcpyDeviceToHost));
   return 0;
@@ -1109,6 +1107,7 @@ int hfx_eles_set_volume_cubpts(hfx_eles *e, int n_cubpts, const double *opp_volu
   HFX_IMMEDIATE(e->ctx, 0);
   e->iq_u.reset(); // (sized by n_cubpts: allocated again by the next CalcIntegralQuantities)
   e->iq_g.reset();
+  e->n_err_cubpts = 0; // (the positions of hfx_eles_set_error_points belonged to the cubature that goes)
   e->n_vol_cubpts = n_cubpts;
   if (make_operator(e->opp_volume_cubpts, opp_volume_cubpts, n_cubpts, e->n_upts)) return 1;
   if (e->weight_volume_cubpts.upload(weight_volume_cubpts, n_cubpts)) return 1;
@@ -1598,6 +1597,7 @@ int hfx_stage_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, 
   default:
     if (v3 ? s.partition_common_fluxes(st) : (viscous && s.partition_common_viscflux(st))) return 1;
     if (s.update()) return 1; // (+ shock capturing)
+    note_gradients(e, !v3);
     return s.pack_solution(st);
   }
 }

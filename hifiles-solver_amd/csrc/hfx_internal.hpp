@@ -251,6 +251,9 @@ struct hfx_ctx
   int n_probe_fields = 0, probe_freq = 1, probe_capacity = 0;
   int probe_codes[HFX_MAX_PROBE_FIELDS] = {};
   unsigned long probe_epoch = 0;
+  // the exact solution of the error monitor (hfx_ctx_set_exact_solution): run_input.test_case and what eval_couette_flow takes
+  hfx_exact exact{};
+  bool have_exact = false;
   hfx::Phys phys() const
   {
     hfx::Phys P;
@@ -345,6 +348,10 @@ struct hfx_eles
   hfx::Operator opp_volume_cubpts;
   hfx::DevBuf<double> weight_volume_cubpts, vol_detjac_vol_cubpts, iq_u, iq_g;
   hfx::DevBuf<int> iq_ids; // the quantity ids of the call that runs
+  // exact-solution error norms (error_norm.hip): pos_volume_cubpts (n_vol_cubpts, n_eles, n_dims) of hfx_eles_set_error_points,
+  // the cubature size it was registered for, and one partial per workgroup and quantity of the call that runs
+  hfx::DevBuf<double> pos_volume_cubpts, err_partial;
+  int n_err_cubpts = 0;
   // plot-point interpolation (hfx_eles_set_opp_p)
   int n_ppts = 0;
   hfx::Operator opp_p;
@@ -522,6 +529,26 @@ int les_len2_upload(hfx_eles *e, DevBuf<double> &dst);
 #define HFX_IMMEDIATE(ctx_, need_)                \
   if (hfx::defer_flush(ctx_, need_)) return 1;    \
   hfx::DeferBusy _defer_busy(ctx_)
+
+// an entry point that reads array id_ of e_: refused when the fused stage that ran last left it with older contents
+#define HFX_CHECK_CURRENT(e_, id_, who_)                                                                                        \
+  HFX_CHECK(!((e_)->stale & (1u << (id_))),                                                                                    \
+            "%s: array %d was not materialised by the fused stage that ran last (deferred execution): read it before the "      \
+            "next stage begins", who_, id_)
+
+namespace hfx
+{
+// The corrected gradients after a fused stage that ran OUTSIDE the deferred scheduler (which keeps the account of every array itself,
+// deferred.hip).  A stage that keeps them on chip -- split variant 3, the general stage -- leaves an older stage's values in
+// grad_disu_upts / grad_disu_fpts: they are marked, and hfx_eles_download and the error monitor refuse them until something writes
+// them again.  Split variant 2 has just written them: the mark goes.  Every loop and stage entry point that runs such a stage calls this
+inline void note_gradients(hfx_eles *e, bool materialised)
+{
+  if (!e->ctx->params.viscous) return;
+  const unsigned grads = (1u << HFX_GRAD_DISU_UPTS) | (1u << HFX_GRAD_DISU_FPTS);
+  e->stale = materialised ? (e->stale & ~grads) : (e->stale | grads);
+}
+} // namespace hfx
 
 // boundary-face kernels (hfx.hip); visc 0: inviscid sweep (+ LDG common solution), 1: viscous sweep;
 // fast: the fused paths' reciprocal-multiply physics

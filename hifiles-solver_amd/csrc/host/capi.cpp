@@ -175,6 +175,12 @@ extern "C" int hfxh_case_get_array(hfxh_case *c, const char *name, const double 
   else if (n == "div_tconf_upts") a = &E->div_tconf_upts(0);
   else if (n == "grad_disu_upts") a = &E->grad_disu_upts;
   else if (n == "h_ref") a = &E->h_ref;
+  // volume cubature: exists once a test case or integral quantities are set
+  else if (n == "loc_volume_cubpts" && E->weight_volume_cubpts.get_dim(0) > 0) a = &E->loc_volume_cubpts;
+  else if (n == "weight_volume_cubpts" && E->weight_volume_cubpts.get_dim(0) > 0) a = &E->weight_volume_cubpts;
+  else if (n == "opp_volume_cubpts" && E->weight_volume_cubpts.get_dim(0) > 0) a = &E->opp_volume_cubpts;
+  else if (n == "vol_detjac_vol_cubpts" && E->weight_volume_cubpts.get_dim(0) > 0) a = &E->vol_detjac_vol_cubpts;
+  else if (n == "pos_volume_cubpts" && E->pos_volume_cubpts.get_dim(0) > 0) a = &E->pos_volume_cubpts;
   // surface cubature of local face l (body forcing): <name>_<l>
   else if (n.size() > 2 && n[n.size() - 2] == '_' && E->n_cubpts_per_inter.get_dim(0) == E->n_inters_per_ele)
   {
@@ -433,6 +439,73 @@ extern "C" int hfxh_case_get_clock(hfxh_case *c, double *time, int *i_steps, dou
   if (time) *time = c->S.time;
   if (i_steps) *i_steps = c->S.i_steps;
   if (spinup_time) *spinup_time = c->S.run_input.spinup_time;
+  return 0;
+}
+
+// ---- exact-solution error norms and integral diagnostics ----------------------------------------------------------------
+// the cubature follows run_input: built again (or dropped) on the host, registered again when the case is on the device
+static int rebuild_volume_cubature(hfxh_case *c)
+{
+  eles *E = the_eles(c);
+  if (E->set_volume_cubature() || E->register_volume_cubature()) { g_err = E->last_error(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_set_test_case(hfxh_case *c, int test_case, int error_norm_type)
+{
+  if (!c) { g_err = "hfxh_case_set_test_case: NULL case"; return 1; }
+  input &in = c->S.run_input;
+  const int old_case = in.test_case, old_norm = in.error_norm_type;
+  if (in.set_test_case(test_case, error_norm_type, g_err)) return 1;
+  if (rebuild_volume_cubature(c) || RegisterExactSolution(&c->S))
+  {
+    // a refusal leaves the case as it was: what was set before is set, built and registered again
+    if (!c->S.err.empty()) { g_err = c->S.err; c->S.err.clear(); }
+    const std::string why = g_err;
+    in.test_case = old_case;
+    in.error_norm_type = old_norm;
+    (void)rebuild_volume_cubature(c);
+    (void)RegisterExactSolution(&c->S);
+    c->S.err.clear();
+    g_err = why;
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int hfxh_case_get_test_case(hfxh_case *c, int *test_case, int *error_norm_type, double *u_wall, double *T_wall)
+{
+  if (!c) { g_err = "hfxh_case_get_test_case: NULL case"; return 1; }
+  const input &in = c->S.run_input;
+  if (test_case) *test_case = in.test_case;
+  if (error_norm_type) *error_norm_type = in.error_norm_type;
+  double u = 0.0, T = 0.0;
+  if (in.test_case == 5 && in.couette_walls(u, T, g_err)) return 1;
+  if (u_wall) *u_wall = u;
+  if (T_wall) *T_wall = T;
+  return 0;
+}
+
+extern "C" int hfxh_case_set_integral_quantities(hfxh_case *c, int n, const char *const *names)
+{
+  if (!c || n < 0 || (n > 0 && !names)) { g_err = "hfxh_case_set_integral_quantities: bad argument"; return 1; }
+  std::vector<std::string> v;
+  for (int i = 0; i < n; i++) v.push_back(names[i] ? names[i] : "");
+  if (c->S.run_input.set_integral_quantities(v, g_err)) return 1;
+  return rebuild_volume_cubature(c);
+}
+
+extern "C" int hfxh_case_compute_error(hfxh_case *c, double *error)
+{
+  if (!c || !error) { g_err = "hfxh_case_compute_error: NULL argument"; return 1; }
+  if (ComputeError(&c->S, error)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_CalcIntegralQuantities(hfxh_case *c, double *integral_quantities)
+{
+  if (!c || !integral_quantities) { g_err = "hfxh_case_CalcIntegralQuantities: NULL argument"; return 1; }
+  if (CalcIntegralQuantities(&c->S, integral_quantities)) { g_err = c->S.err; c->S.err.clear(); return 1; }
   return 0;
 }
 

@@ -463,6 +463,7 @@ int eles::mv_all_cpu_gpu(hfx_ctx *ctx)
     return 1;
   }
   if (run_input->n_average_fields && register_average_fields()) return 1;
+  if (register_volume_cubature()) return 1;
   if (!probe_p2c.empty() && register_probes()) return 1;
   if (run_input->forcing == 1 && n_dims == 3 && register_body_force()) return 1;
   if (run_input->over_int &&

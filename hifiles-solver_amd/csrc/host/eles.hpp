@@ -101,6 +101,15 @@ public:
   // the shape nodes that span the plane of local face in_face (calc_p2c); returns the number of faces, -1: shape not implemented
   virtual int face_plane_vertices(int in_n_spts, int in_face, int v[3]) const = 0;
 
+  // ---- volume cubature and the monitors over it (csrc/host/eles_error.cpp): run_input->test_case, n_integral_quantities.
+  // loc (n_dims, n_cubpts), weight (n_cubpts), opp (n_cubpts, n_upts), vol_detjac (n_cubpts, n_eles), pos (n_cubpts, n_eles, n_dims;
+  // a test case only).  Quadrilaterals and hexahedra; empty while neither monitor is asked for
+  hf_array<double> loc_volume_cubpts, weight_volume_cubpts, opp_volume_cubpts, vol_detjac_vol_cubpts, pos_volume_cubpts;
+  int set_volume_cubature();      // builds or drops the five arrays by run_input (host only)
+  int register_volume_cubature(); // -> hfx_eles_set_volume_cubpts, hfx_eles_set_error_points
+  int compute_error(int in_norm_type, double &time, hf_array<double> &error); // src/eles.cpp:5076 on the device: error (2, n_fields)
+  int CalcIntegralQuantities(int n_integral_quantities, hf_array<double> &integral_quantities); // src/eles.cpp:5485: adds to them
+
   // ---- getters used by face wiring (src/eles.cpp:4638-4949 return pointers; here: offsets)
   int get_n_eles() const { return n_eles; }
   int get_n_dims() const { return n_dims; }

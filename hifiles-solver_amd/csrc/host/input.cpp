@@ -110,6 +110,60 @@ int input::average_code(int i) const
   return (int)(std::find(AVERAGE_NAMES, AVERAGE_NAMES + 5, average_fields[i]) - AVERAGE_NAMES);
 }
 
+int input::set_test_case(int in_test_case, int in_error_norm_type, std::string &err)
+{
+  if (in_test_case >= 2 && in_test_case <= 4)
+  {
+    err = "test_case " + std::to_string(in_test_case) + " is an exact solution of the advection-diffusion equation, which is not supported (equation != 0)";
+    return 1;
+  }
+  if (in_test_case != 0 && in_test_case != 1 && in_test_case != 5) { err = "Test case not recognized in compute error, exiting"; return 1; } /* src/eles.cpp:5247 */
+  if (in_error_norm_type != 1 && in_error_norm_type != 2) { err = "Error norm not supported!"; return 1; } /* src/output.cpp:2103 */
+  if (in_test_case == 5)
+  {
+    double u_wall, T_wall;
+    if (couette_walls(u_wall, T_wall, err)) return 1;
+  }
+  test_case = in_test_case;
+  error_norm_type = in_error_norm_type;
+  return 0;
+}
+
+int input::couette_walls(double &u_wall, double &T_wall, std::string &err) const
+{
+  bool moving = false, fixed = false;
+  for (const hfx_bc &b : bc_list)
+    if (b.flag == HFX_BC_ISOTHERM_WALL)
+    {
+      if (b.velocity[0] != 0) { u_wall = b.velocity[0]; moving = true; } // moving wall
+      else { T_wall = b.T_static; fixed = true; }                        // fixed wall
+    }
+  if (!moving) { err = "test_case 5 (Couette flow): no moving isothermal wall among the boundary groups (an isothermal wall with velocity(0) != 0 gives u_wall)"; return 1; }
+  if (!fixed) { err = "test_case 5 (Couette flow): no isothermal wall at rest among the boundary groups (its T_static gives T_wall)"; return 1; }
+  return 0;
+}
+
+static const char *const INTEGRAL_NAMES[5] = {"kineticenergy", "enstropy", "pressuredilatation", "straincolonproduct", "devstraincolonproduct"}; /* src/eles.cpp:5530-5618 */
+
+int input::set_integral_quantities(const std::vector<std::string> &names, std::string &err)
+{
+  std::vector<std::string> lower(names);
+  for (std::string &s : lower)
+  {
+    std::transform(s.begin(), s.end(), s.begin(), [](unsigned char c) { return (char)std::tolower(c); }); /* src/input.cpp:146-149 */
+    if (std::find(INTEGRAL_NAMES, INTEGRAL_NAMES + 5, s) == INTEGRAL_NAMES + 5) { err = "integral diagnostic quantity not recognized"; return 1; } /* src/eles.cpp:5618 */
+  }
+  if (lower.size() > 8) { err = "integral_quantities: at most 8 quantities"; return 1; }
+  integral_quantities.swap(lower);
+  n_integral_quantities = (int)integral_quantities.size();
+  return 0;
+}
+
+int input::integral_quantity_code(int i) const
+{
+  return (int)(std::find(INTEGRAL_NAMES, INTEGRAL_NAMES + 5, integral_quantities[i]) - INTEGRAL_NAMES);
+}
+
 static const char *const PROBE_NAMES[6] = {"rho", "u", "v", "w", "specific_total_energy", "pressure"}; /* src/output.cpp:1482-1522 */
 
 int input::set_probe_fields(const std::vector<std::string> &names, int n_dims, int freq, int capacity, std::string &err)

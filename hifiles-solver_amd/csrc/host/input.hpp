@@ -60,6 +60,19 @@ struct input
   // a name outside the six, w in a two-dimensional run, probe_freq < 1 and capacity < 1 are refused and leave everything as it was
   int set_probe_fields(const std::vector<std::string> &names, int n_dims, int freq, int capacity, std::string &err);
   int probe_code(int i) const; // HFX_PROBE_* of probe_fields(i)
+  // ---- exact-solution error norms (src/input.cpp:108-109): test_case 0 none, 1 isentropic vortex, 5 Couette flow (2, 3, 4 belong to
+  // the advection-diffusion equation); error_norm_type 1 L1, 2 L2.  Refusals leave both as they were
+  int test_case = 0, error_norm_type = 2;
+  int set_test_case(int in_test_case, int in_error_norm_type, std::string &err);
+  // test case 5: velocity(0) of the moving isothermal wall and T_static of the one at rest, from bc_list by the reference's rule
+  // (src/eles.cpp:5219-5230).  The reference reads what it did not find uninitialised; here a missing wall is refused by name
+  int couette_walls(double &u_wall, double &T_wall, std::string &err) const;
+  // ---- integral diagnostics (src/input.cpp:134-149): names out of kineticenergy, enstropy, pressuredilatation, straincolonproduct,
+  // devstraincolonproduct (the reference's spelling), lower-cased; another name is refused with the reference's words
+  std::vector<std::string> integral_quantities;
+  int n_integral_quantities = 0;
+  int set_integral_quantities(const std::vector<std::string> &names, std::string &err);
+  int integral_quantity_code(int i) const; // the quantity id of hfx_eles_CalcIntegralQuantities
   // ---- mass-flux body force of periodic channels (`body_forcing`, src/input.cpp:312).  forcing_area and forcing_mdot0 are keys of
   // this mirror: the inflow area and the target mass flux, which the reference hard-codes to 9.162 both (src/eles.cpp:5393-5395);
   // forcing_history: evaluations whose massflux.dat columns the device keeps

@@ -466,6 +466,89 @@ int RegisterProbeFields(solution *S)
   return 0;
 }
 
+int RegisterExactSolution(solution *S)
+{
+  if (!S->ctx) return 0; // (MoveToDevice registers it)
+  const input &in = S->run_input;
+  if (in.test_case == 0) // none: the context forgets the one it had
+  {
+    if (hfx_ctx_set_exact_solution(S->ctx, nullptr)) { S->err = hfx_last_error(); return 1; }
+    return 0;
+  }
+  hfx_exact x{};
+  x.test_case = in.test_case;
+  if (in.test_case == 5)
+  {
+    if (in.couette_walls(x.u_wall, x.T_wall, S->err)) return 1;
+    x.p_bound = in.p_c_ic; /* src/eles.cpp:5233 */
+    x.R_ref = in.R_ref;
+    x.T_ref = in.T_ref;
+  }
+  if (hfx_ctx_set_exact_solution(S->ctx, &x)) { S->err = hfx_last_error(); return 1; }
+  return 0;
+}
+
+// the SUM over the ranks of the monitors: the library's communicator, else the caller's hook (whenever one is registered);
+// more than one rank without either is refused
+static int sum_over_ranks(solution *S, double *v, int n, const char *who)
+{
+  if (S->comm)
+  {
+    if (hfx_comm_allreduce(S->comm, v, n, 2)) { S->err = hfx_last_error(); return 1; }
+  }
+  else if (S->reduce_sum)
+    S->reduce_sum(S->reduce_sum_user, v, n);
+  else if (S->nproc > 1)
+  {
+    S->err = std::string(who) + ": more than one rank needs a SUM reduction over the ranks (SetComm or SetReduceSum)";
+    return 1;
+  }
+  return 0;
+}
+
+int ComputeError(solution *S, double *error)
+{
+  const input &in = S->run_input;
+  if (in.test_case == 0) { S->err = "compute_error: the case has no test_case"; return 1; }
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  const int n_fields = S->n_dims + 2;
+  hf_array<double> sum(2, n_fields), temp_error;
+  for (int i = 0; i < S->n_ele_types; i++)
+  {
+    eles *E = S->mesh_eles(i);
+    if (!E || E->get_n_eles() == 0) continue;
+    if (E->compute_error(in.error_norm_type, S->time, temp_error)) { S->err = E->last_error(); return 1; }
+    for (int j = 0; j < n_fields; j++)
+    {
+      sum(0, j) += temp_error(0, j);
+      if (in.viscous) sum(1, j) += temp_error(1, j);
+    }
+  }
+  if (sum_over_ranks(S, sum.get_ptr_cpu(), 2 * n_fields, "compute_error")) return 1;
+  for (int j = 0; j < n_fields; j++)
+    for (int r = 0; r < 2; r++)
+      error[r + 2 * j] = (in.error_norm_type == 2 && (r == 0 || in.viscous)) ? std::sqrt(sum(r, j)) : sum(r, j);
+  return 0;
+}
+
+int CalcIntegralQuantities(solution *S, double *integral_quantities)
+{
+  const input &in = S->run_input;
+  const int nintq = in.n_integral_quantities;
+  if (nintq == 0) { S->err = "CalcIntegralQuantities: the case has no integral_quantities"; return 1; }
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  hf_array<double> q(nintq);
+  for (int i = 0; i < S->n_ele_types; i++)
+  {
+    eles *E = S->mesh_eles(i);
+    if (!E || E->get_n_eles() == 0) continue;
+    if (E->CalcIntegralQuantities(nintq, q)) { S->err = E->last_error(); return 1; }
+  }
+  if (sum_over_ranks(S, q.get_ptr_cpu(), nintq, "CalcIntegralQuantities")) return 1;
+  for (int m = 0; m < nintq; m++) integral_quantities[m] = q(m);
+  return 0;
+}
+
 int MoveToDevice(solution *S, int device)
 {
   if (hfx_ctx_create(device, &S->ctx)) { S->err = hfx_last_error(); return 1; }
@@ -475,6 +558,7 @@ int MoveToDevice(solution *S, int device)
   if (S->run_input.dt_type != 0 && hfx_ctx_set_CFL(S->ctx, S->run_input.CFL)) { S->err = hfx_last_error(); return 1; }
   if (hfx_ctx_set_option(S->ctx, "deferred", S->deferred ? 1 : 0)) { S->err = hfx_last_error(); return 1; }
   if (RegisterProbeFields(S)) return 1; // (before the element blocks, which register their probes)
+  if (S->run_input.test_case != 0 && RegisterExactSolution(S)) return 1;
   for (int i = 0; i < S->n_ele_types; i++)
     if (S->mesh_eles(i) && S->mesh_eles(i)->get_n_eles() != 0)
       if (S->mesh_eles(i)->mv_all_cpu_gpu(S->ctx)) { S->err = S->mesh_eles(i)->last_error(); return 1; }

@@ -81,6 +81,13 @@ int MoveToDevice(solution *FlowSol, int device);
 // time and step (always, or under the reference's condition i_steps % probe_freq == 0)
 int RegisterProbeFields(solution *S);
 void SampleProbes(solution *FlowSol, bool always);
+// run_input's test case -> the context (hfx_ctx_set_exact_solution), with the walls of Couette flow from the boundary groups
+int RegisterExactSolution(solution *S);
+// output::compute_error (src/output.cpp:2052-2110) without the file: error (2, n_fields) summed over the element classes and the
+// ranks (one SUM reduction of 2 n_fields values), then the square root for error_norm_type 2, at the solution's time
+int ComputeError(solution *FlowSol, double *error);
+// output::CalcIntegralQuantities (src/output.cpp:2017-2038): run_input's integral quantities over the classes and the ranks
+int CalcIntegralQuantities(solution *FlowSol, double *integral_quantities);
 // switch deferred execution on / off (before or after MoveToDevice)
 int SetDeferred(solution *FlowSol, bool on);
 

@@ -37,6 +37,12 @@ class Les(C.Structure):
 CONTRACT_AUTO, CONTRACT_DENSE, CONTRACT_SPARSE = 0, 1, 2
 
 
+class Exact(C.Structure):
+    """hfx_exact: run_input.test_case and what the exact solution of Couette flow takes"""
+    _fields_ = [("test_case", C.c_int), ("pad", C.c_int)] + \
+               [(n, C.c_double) for n in ("u_wall", "T_wall", "p_bound", "R_ref", "T_ref")]
+
+
 class Params(C.Structure):
     _fields_ = [(n, C.c_double) for n in
                 ("gamma", "prandtl", "rt_inf", "mu_inf", "c_sth", "fix_vis", "ldg_beta", "ldg_tau", "dt")] + \
@@ -220,6 +226,11 @@ class Context:
         a = (C.c_int * max(1, len(codes)))(*codes)
         check(lib().hfx_ctx_set_probes(self.h, C.c_int(len(codes)), a, C.c_int(probe_freq), C.c_int(capacity)))
         self.n_probe_fields = len(codes)
+
+    def set_exact_solution(self, test_case, u_wall=0.0, T_wall=0.0, p_bound=0.0, R_ref=0.0, T_ref=0.0):
+        """test_case 1: isentropic vortex; 5: Couette flow, which takes the five parameters (hfx_exact)"""
+        x = Exact(int(test_case), 0, u_wall, T_wall, p_bound, R_ref, T_ref)
+        check(lib().hfx_ctx_set_exact_solution(self.h, C.byref(x)))
 
     def flush(self):
         """deferred execution: run what has been recorded (no-op otherwise)"""
@@ -431,6 +442,25 @@ class Eles:
         out = np.zeros(len(ids))
         check(lib().hfx_eles_CalcIntegralQuantities(self.h, C.c_int(len(ids)), ids.ctypes.data_as(ip), out.ctypes.data_as(dp)))
         return out
+
+    def set_error_points(self, pos_volume_cubpts):
+        """pos_volume_cubpts (n_cubpts, n_eles, n_dims): the positions of the cubature points of set_volume_cubpts"""
+        a = _f(pos_volume_cubpts)
+        assert a.ndim == 3 and a.shape[1:] == (self.n_eles, self.n_dims), a.shape
+        check(lib().hfx_eles_set_error_points(self.h, a.ctypes.data_as(dp)))
+
+    def compute_error(self, norm_type, time):
+        """eles::compute_error of this block: (2, n_fields), row 0 the solution error, row 1 the gradient error, before the
+        sum over blocks and ranks and the square root"""
+        out = np.zeros((2, self.n_fields), dtype=np.float64, order="F")
+        check(lib().hfx_eles_compute_error(self.h, C.c_int(norm_type), C.c_double(time), out.ctypes.data_as(dp)))
+        return out
+
+    def error_launch(self):
+        """(workgroups, elements per pass) of the next compute_error"""
+        g, n = C.c_int(0), C.c_int(0)
+        check(lib().hfx_eles_error_launch(self.h, C.byref(g), C.byref(n)))
+        return g.value, n.value
 
     def set_h_ref(self, h_ref):
         h = np.ascontiguousarray(np.ravel(h_ref).astype(np.float64))

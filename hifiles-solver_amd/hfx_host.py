@@ -481,6 +481,35 @@ class Case:
         self._scb = REDUCE_SUM_CB(cb)
         check(lib().hfxh_case_set_reduce_sum(self.h, self._scb, None))
 
+    # ---- exact-solution error norms and integral diagnostics
+    def set_test_case(self, test_case, error_norm_type=2):
+        """run_input.test_case (0 none, 1 isentropic vortex, 5 Couette flow) and error_norm_type (1 L1, 2 L2)"""
+        check(lib().hfxh_case_set_test_case(self.h, C.c_int(test_case), C.c_int(error_norm_type)))
+
+    def test_case(self):
+        """dict(test_case, error_norm_type, u_wall, T_wall): the walls as found among the boundary groups (test case 5)"""
+        tc, nt, u, t = C.c_int(0), C.c_int(0), C.c_double(0), C.c_double(0)
+        check(lib().hfxh_case_get_test_case(self.h, C.byref(tc), C.byref(nt), C.byref(u), C.byref(t)))
+        return dict(test_case=tc.value, error_norm_type=nt.value, u_wall=u.value, T_wall=t.value)
+
+    def set_integral_quantities(self, names):
+        """run_input.integral_quantities: names out of kineticenergy, enstropy, pressuredilatation, straincolonproduct,
+        devstraincolonproduct (any letter case)"""
+        a = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        check(lib().hfxh_case_set_integral_quantities(self.h, C.c_int(len(names)), a))
+        self.n_integral_quantities = len(names)
+
+    def compute_error(self):
+        """output::compute_error at the mirror's clock: (2, n_fields), over blocks and ranks, after the square root (norm 2)"""
+        out = np.zeros((2, self.n_fields), dtype=np.float64, order="F")
+        check(lib().hfxh_case_compute_error(self.h, out.ctypes.data_as(dp)))
+        return out
+
+    def CalcIntegralQuantities(self):
+        out = np.zeros(max(1, getattr(self, "n_integral_quantities", 0)))
+        check(lib().hfxh_case_CalcIntegralQuantities(self.h, out.ctypes.data_as(dp)))
+        return out[:getattr(self, "n_integral_quantities", 0)]
+
     def inflow_faces(self):
         """(elements, local faces) the reference's inflow rule selects"""
         e, l, n = ip(), ip(), C.c_int(0)

@@ -204,6 +204,10 @@ int hfx_eles_create(hfx_ctx *ctx, const hfx_eles_desc *desc, hfx_eles **out);
 int hfx_eles_destroy(hfx_eles *e);
 /* replaces hf_array::cp_cpu_gpu / cp_gpu_cpu (include/hf_array.h:541-580) */
 int hfx_eles_upload(hfx_eles *e, int array_id, const double *host);
+/* A download of grad_disu_upts / grad_disu_fpts is refused ("was not materialised ...") after a fused stage that keeps the
+ * corrected gradients on chip -- split variant 3, the general stage; through hfx_run_steps*, the partitioned loops,
+ * hfx_stage_partitioned, the timing entry points or deferred execution -- until a per-method stage, split variant 2 or an
+ * upload writes them again: the arrays then hold an older stage's values. */
 int hfx_eles_download(hfx_eles *e, int array_id, double *host);
 /* deferred execution: *current = 1 when the array holds the last stage's values; 2 when it does not yet but a whole stage is
  * pending that a download of this array would run call by call (and so refresh it); 0 when the fused stage that ran last did
@@ -310,6 +314,40 @@ int hfx_eles_set_volume_cubpts(hfx_eles *e, int n_cubpts, const double *opp_volu
  * 4 devstraincolonproduct) from disu_upts(0) and grad_disu_upts (the corrected gradient of the last
  * per-method / fused-mode-2 stage).  The caller adds over blocks and ranks (src/output.cpp:2017-2050). */
 int hfx_eles_CalcIntegralQuantities(hfx_eles *e, int n_quantities, const int *quantity_ids, double *integral_quantities);
+
+/* ---- exact-solution error norms (run_input.test_case, error_norm_type; output::compute_error, src/output.cpp:2052) ------
+ * The monitor a verification run ends with (src/HiFiLES.cpp:324-325): the state -- and for Couette flow the gradient --
+ * interpolated to the volume cubature points, minus the exact solution there, integrated in the L1 or L2 sense. */
+typedef struct hfx_exact
+{
+  int test_case, pad; /* run_input.test_case: 1 isentropic vortex (src/funcs.cpp:1724-1739), 5 Couette flow (src/funcs.cpp:1830-1922) */
+  /* test case 5 only: velocity(0) of the moving isothermal wall, T_static of the one at rest (src/eles.cpp:5219-5230),
+   * run_input.p_c_ic, R_ref and T_ref.  gamma and prandtl are those of hfx_params */
+  double u_wall, T_wall, p_bound, R_ref, T_ref;
+} hfx_exact;
+/* Stored as given; hfx_eles_compute_error refuses what it cannot compute.  x NULL: the context has no exact solution any more. */
+int hfx_ctx_set_exact_solution(hfx_ctx *ctx, const hfx_exact *x);
+/* pos_volume_cubpts (n_cubpts,n_eles,n_dims): the physical positions of the cubature points registered with
+ * hfx_eles_set_volume_cubpts (which comes first), what the reference recomputes with calc_pos on every call
+ * (src/eles.cpp:5095-5097).  Every hfx_eles_set_volume_cubpts drops them: the positions are registered again behind it. */
+int hfx_eles_set_error_points(hfx_eles *e, const double *pos_volume_cubpts);
+/* eles::compute_error (src/eles.cpp:5076-5136) for one block.  error (2,n_fields) column-major like hf_array is OVERWRITTEN:
+ * row 0 the solution error of every field, row 1 the gradient error; norm_type 1: the sum of |e| weight detjac (row 1: |e|
+ * summed over the dimensions first, as the reference does), 2: of e^2 weight detjac, anything else is refused with "Error norm
+ * not supported!".  The caller adds over blocks and ranks and takes the square root for norm 2 (src/output.cpp:2066-2099).
+ *   test case 1: the solution error alone.  Row 1 is zero and grad_disu_upts is never read, so the call works after any fused
+ *     stage and with a deferred stage pending (which runs first, fused as it would have).
+ *   test case 5: on a viscous context row 1 is the error of grad_disu_upts as it stands against the exact gradient, of which
+ *     the reference sets d(rho)/dy, d(rho u)/dy and dE/dy and leaves everything else zero.  A pending deferred stage is run so
+ *     that it leaves the gradient; a gradient the last fused stage did not materialise is refused with the words of
+ *     hfx_eles_download.  On an inviscid context row 1 is zero.
+ *   test cases 2, 3, 4 (advection-diffusion) and unknown ones are refused, as are a missing cubature, missing positions and
+ *     missing parameters -- all before anything is launched.
+ * One fused kernel and the copy of one partial per workgroup and quantity; no array of the size of n_cubpts x n_eles.  Two
+ * calls on one state agree bit for bit (no atomics; fixed summation order for a given grid). */
+int hfx_eles_compute_error(hfx_eles *e, int norm_type, double time, double *error);
+/* what the next hfx_eles_compute_error launches: workgroups, and the elements a workgroup takes per pass of its loop */
+int hfx_eles_error_launch(hfx_eles *e, int *n_groups, int *eles_per_pass);
 
 /* ---- plot-point interpolation (8f-3: the VTU writer's input) -------------- */
 /* opp_p (n_ppts,n_upts): the nodal basis at the plot points, eles::set_opp_p (src/eles.cpp:3600-3621) */

@@ -268,6 +268,34 @@ int hfxh_case_set_forcing(hfxh_case *c, double forcing_area, double forcing_mdot
  * the caller's: fn(user, v, n) replaces v[n] by its sum over the ranks.  With hfxh_case_set_comm the library's communicator sums. */
 typedef void (*hfxh_reduce_sum_cb)(void *user, double *v, int n);
 int hfxh_case_set_reduce_sum(hfxh_case *c, hfxh_reduce_sum_cb fn, void *user);
+
+/* ---- exact-solution error norms and integral diagnostics (run_input.test_case, error_norm_type, integral_quantities) ------
+ * Setters in the style of hfxh_case_set_average_fields: called after hfxh_case_create, before hfxh_case_to_device (a case that
+ * is on the device registers again at once).  While either is active the quadrilaterals / hexahedra of the case carry the
+ * reference's volume cubature -- loc_volume_cubpts (n_dims,n_cubpts) and weight_volume_cubpts (n_cubpts): the tensor Gauss rule
+ * with order + 1 points per direction, first direction fastest (src/eles_hexas.cpp:87,376, src/eles_quads.cpp:97,317);
+ * opp_volume_cubpts (n_cubpts,n_upts) (src/eles.cpp:3667); vol_detjac_vol_cubpts (n_cubpts,n_eles) (src/eles.cpp:4600-4633); and,
+ * for a test case, pos_volume_cubpts (n_cubpts,n_eles,n_dims) -- readable through hfxh_case_get_array and registered with the
+ * device block (hfx_eles_set_volume_cubpts, hfx_eles_set_error_points).  With neither active none of the five exists.
+ *
+ * test_case 0: none; 1: isentropic vortex; 5: Couette flow, whose u_wall is velocity(0) of the isothermal wall that moves and
+ * whose T_wall is T_static of the isothermal wall at rest (src/eles.cpp:5219-5230) -- a missing wall is refused by name, where
+ * the reference reads an uninitialised value.  2, 3, 4 (advection-diffusion) and unknown cases are refused, as is an
+ * error_norm_type other than 1 (L1) and 2 (L2, the reference's default, src/input.cpp:109).  A refusal leaves the case as it was. */
+int hfxh_case_set_test_case(hfxh_case *c, int test_case, int error_norm_type);
+/* what is set; u_wall and T_wall as found among the boundary groups (test case 5, else 0).  Any pointer may be NULL */
+int hfxh_case_get_test_case(hfxh_case *c, int *test_case, int *error_norm_type, double *u_wall, double *T_wall);
+/* names[n] out of kineticenergy, enstropy (the reference's spelling), pressuredilatation, straincolonproduct,
+ * devstraincolonproduct, any letter case; another name is refused with "integral diagnostic quantity not recognized" */
+int hfxh_case_set_integral_quantities(hfxh_case *c, int n, const char *const *names);
+/* output::compute_error (src/output.cpp:2052-2110) without the file, at the mirror's clock: error (2,n_fields) column-major, row 0
+ * the solution, row 1 the gradient (viscous cases); summed over the case's blocks, then over the ranks -- the library's
+ * communicator, else ONE call of the hook of hfxh_case_set_reduce_sum with 2 n_fields values -- then the square root for
+ * error_norm_type 2.  The case must be on the device. */
+int hfxh_case_compute_error(hfxh_case *c, double *error);
+/* output::CalcIntegralQuantities (src/output.cpp:2017-2038): integral_quantities[n_integral_quantities] over blocks and ranks,
+ * on top of hfx_eles_CalcIntegralQuantities (which reads the corrected gradient of the last per-method stage) */
+int hfxh_case_CalcIntegralQuantities(hfxh_case *c, double *integral_quantities);
 /* the inflow faces the reference's rule selects, elements ascending: (element, local face) */
 int hfxh_case_get_inflow_faces(hfxh_case *c, const int **ele, const int **inter, int *n_faces);
 /* hfx_eles_body_force_state / hfx_eles_body_force_history of the case's block */
