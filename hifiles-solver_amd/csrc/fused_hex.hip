@@ -673,7 +673,7 @@ struct LoaderWaveLaunch<ND, N, OI, GA, LES, true, AFF>
 // Two-wave flux kernel: how many elements of the block need the projected viscous flux of one of the left-over points when these
 // lie on local face f (need[f], from the partner words counted in fused_build and the run's ldg_beta: the kernel's own test of
 // `needed`), and the face that asks least often (the lowest of equals) -- the left-over points go there
-static int two_wave_face(const FusedData *F, double ldg_beta, long need[6])
+static int two_wave_face(const FusedData *F, double ldg_beta, long need[6], int forced = -1)
 {
   int best = 0;
   for (int f = 0; f < 6; f++)
@@ -683,7 +683,7 @@ static int two_wave_face(const FusedData *F, double ldg_beta, long need[6])
       if ((code & 1) || ((code & 2) && 0.5 + ldg_beta != 0.0) || ((code & 4) && 0.5 - ldg_beta != 0.0)) need[f] += F->tw_need[f][code];
     if (need[f] < need[best]) best = f;
   }
-  return best;
+  return forced >= 0 ? forced : best; // (option flux_two_wave_face)
 }
 
 // launch of the two-wave form, instantiated only for the element size it is written for (TwoWave::fits)
@@ -691,17 +691,29 @@ template <int ND, int N, bool FITS>
 struct TwoWaveLaunch
 {
   static void go(const hfx_eles *, int, hipStream_t, const Split2Args &, const double *, const int *, int) {}
+  static void go_fold(const hfx_eles *, int, hipStream_t, const Split2Args &, const double *, const int *, int) {}
 };
 template <int ND, int N>
 struct TwoWaveLaunch<ND, N, true>
 {
   static void go(const hfx_eles *e, int per_cu, hipStream_t st, const Split2Args &e2, const double *coef, const int *idx, int face)
   {
+    launch<false, 0>(e, per_cu, st, e2, coef, idx, face);
+  }
+  // the FOLD form (SplitPlan::fold_faces) with the run's Riemann solver: Rusanov, or HLLC as with_riemann_solver maps the others
+  // (the plan does not fold a RoeM run)
+  static void go_fold(const hfx_eles *e, int per_cu, hipStream_t st, const Split2Args &e2, const double *coef, const int *idx, int face)
+  {
+    e2.P.riemann == 0 ? launch<true, 0>(e, per_cu, st, e2, coef, idx, face) : launch<true, 3>(e, per_cu, st, e2, coef, idx, face);
+  }
+  template <bool FOLD, int RS>
+  static void launch(const hfx_eles *e, int per_cu, hipStream_t st, const Split2Args &e2, const double *coef, const int *idx, int face)
+  {
     constexpr int TB = TwoWave<ND, N>::TB;
-    int grid = element_grid<split_flux_two_wave_kernel<ND, N>>(e, TB, per_cu);
+    int grid = element_grid<split_flux_two_wave_kernel<ND, N, FOLD, RS>>(e, TB, per_cu);
     if (e2.ele_list != nullptr) grid = (int)std::max<long>(1, std::min<long>(grid, e2.n_list));
     grid = persistent_grid(e, SLOT_ELEMENT, e2.ele_list != nullptr ? e2.n_list : (long)e->n_eles, grid);
-    hipLaunchKernelGGL((split_flux_two_wave_kernel<ND, N>), dim3(grid), dim3(TB), 0, st, e2, coef, idx, TwoWave<ND, N>::rotation(face));
+    hipLaunchKernelGGL((split_flux_two_wave_kernel<ND, N, FOLD, RS>), dim3(grid), dim3(TB), 0, st, e2, coef, idx, TwoWave<ND, N>::rotation(face));
   }
 };
 static bool two_wave_fits_rt(int nd, int N)
@@ -786,6 +798,15 @@ SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int r
   p.affine = v3 && F && F->affine && opt.affine_metrics && p.flux == FluxForm::loader_wave && p.gather && !oi && !p.les;
   // ... and on P4 hexahedra, whose loader-wave form has four waves, the affine form runs as two-wave workgroups
   p.two_wave = p.affine && opt.flux_two_wave && two_wave_fits_rt(e->n_dims, N) && F->tw_counted;
+  // ... and with one-sided LDG (one weight of every pair exactly 0.0: ldg_both_sides, face_physics.hpp) it forms the interior
+  // pairs' common flux itself
+  {
+    const double b = e->ctx->params.ldg_beta;
+    const bool one_sided = (0.5 + b) == 0.0 || (0.5 - b) == 0.0;
+    // (not with RoeM: pow() in its dissipation costs the FOLD form 34 spilled registers, and at supersonic face states its last-bit
+    // differences from the face kernel's inlining take the residual past the oracle's bound -- that solver keeps the face kernel)
+    p.fold_faces = p.two_wave && viscous && one_sided && opt.fold_faces && e->ctx->params.riemann_solve_type != 2;
+  }
 
   // a partitioned block: variant 3 sends the projected viscous flux; element lists for the flux kernel without over-integration
   // (which runs on all elements first), for the update without shock capturing (whose filter follows the whole update)
@@ -803,7 +824,7 @@ SplitPlan split_plan(const hfx_eles *e, hfx_inters *const *faces, int nfb, int r
   else if (F && F->affine)
     // (no launch of its own: the flux and update kernels read the per-element metric record | the block was found affine, but the form
     // that runs keeps the per-point metrics)
-    p.extra_names = p.two_wave ? ",affine_metrics,two_wave" : p.affine ? ",affine_metrics" : ",affine_block";
+    p.extra_names = p.fold_faces ? ",affine_metrics,two_wave,folded_faces" : p.two_wave ? ",affine_metrics,two_wave" : p.affine ? ",affine_metrics" : ",affine_block";
   return p;
 }
 
@@ -972,7 +993,12 @@ struct SplitStageT final : SplitStage
     if (pl.two_wave)
     {
       long need[6];
-      if constexpr (!OI && !LES) TwoWaveLaunch<ND, N, TwoWave<ND, N>::fits>::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx, two_wave_face(F, P.ldg_beta, need));
+      if constexpr (!OI && !LES)
+      {
+        const int face = two_wave_face(F, P.ldg_beta, need, e->ctx->opt.flux_two_wave_face);
+        using Launch = TwoWaveLaunch<ND, N, TwoWave<ND, N>::fits>;
+        pl.fold_faces ? Launch::go_fold(e, flux_per_cu, st, e2, F->t_coef, F->t_idx, face) : Launch::go(e, flux_per_cu, st, e2, F->t_coef, F->t_idx, face);
+      }
     }
     else if (pl.affine)
     {
@@ -1061,6 +1087,7 @@ struct SplitStageT final : SplitStage
     for (int b = 0; b < nfb; b++)
     {
       if (faces[b]->is_bdy || !face_pairs(fa, faces[b])) continue;
+      if (pl.fold_faces) continue; // (the two-wave flux kernel has written the interior pairs' norm_tconf)
       const dim3 nb((unsigned)((fa.npairs + 255) / 256));
       if (pl.variant == 3)
         with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL((face_flux2_kernel<ND, decltype(RS)::value>), nb, dim3(256), 0, st, FaceBlockArgs(fa), P); });
@@ -1256,6 +1283,12 @@ int split_time_kernels(hfx_eles *e, hfx_inters *const *faces, int nfb, int reps,
     }
   for (auto &x : ev) (void)hipEventDestroy(x);
   for (int i = 0; i < 8; i++) ms[i] = acc[i] / reps;
+  // (folded faces without a boundary face: the common-flux step launched nothing -- the events still lie a few microseconds apart)
+  {
+    bool any_bdy_faces = false;
+    for (int b = 0; b < nfb; b++) any_bdy_faces = any_bdy_faces || (faces[b]->is_bdy && faces[b]->n_inters > 0);
+    if (pl.fold_faces && !any_bdy_faces) ms[2] = 0.0;
+  }
   if (e->fused->stamps)
   {
     long long h[64];
@@ -1283,7 +1316,7 @@ int split_two_wave_face(hfx_eles *e, hfx_inters *const *faces, int nfb, int vari
   if (ensure_fused_tables(e, faces, nfb, false)) return 1;
   const SplitPlan pl = split_plan(e, faces, nfb, variant);
   for (int f = 0; f < 6; f++) need[f] = 0;
-  *face = pl.two_wave ? two_wave_face(e->fused.get(), e->ctx->params.ldg_beta, need) : -1;
+  *face = pl.two_wave ? two_wave_face(e->fused.get(), e->ctx->params.ldg_beta, need, e->ctx->opt.flux_two_wave_face) : -1;
   return 0;
 }
 
@@ -1351,6 +1384,16 @@ void split_kernel_bytes(const hfx_eles *e, double *bytes, int variant)
       // update kernel the record's detjac.  The face kernel keeps the per-point normal and tdA (they multiply the pressure).
       bytes[1] += ne * 8.0 * (AffRec::SIZE + nu * nd * nd - (nu * (nd * nd + 1) + nfp * (nd * nd + 1) + nfp * nd));
       bytes[3] += ne * 8.0 * (1.0 - nu);
+    }
+    if (pl.fold_faces && e->fused && e->fused->built)
+    {
+      // The two-wave flux kernel forms the interior pairs' common flux: per pair the stage no longer moves the face kernel's reads
+      // (both disu, the needed Fn, the left normal, both tdA, the two point indices) and writes (both norm_tconf) nor the flux
+      // kernel's Fn; the flux kernel takes on the partner's disu (a re-read, expected in L2), the normal, both tdA and both
+      // norm_tconf.  bytes[7]: the difference per stage.  (bytes[1] and bytes[2] stay as they are: the roofline of the flux
+      // kernel is priced without the pairs' traffic, that of the face kernel as if it ran.)
+      const double pairs = 0.5 * (double)e->fused->n_interior_fpts;
+      bytes[7] = pairs * (8.0 * 3 * nf + 8.0);
     }
   }
 }

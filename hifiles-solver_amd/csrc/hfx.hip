@@ -513,6 +513,8 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value)
   else if (n == "flux_stamps") o.flux_stamps = value;
   else if (n == "simd_roles") o.simd_roles = value != 0;
   else if (n == "flux_two_wave") o.flux_two_wave = value != 0;
+  else if (n == "fold_faces") o.fold_faces = value != 0;
+  else if (n == "flux_two_wave_face") { HFX_CHECK(value >= -1 && value <= 5, "flux_two_wave_face must be -1 (the host's choice) or a local face 0-5"); o.flux_two_wave_face = value; }
   else if (n == "les_flux_kernel") o.les_flux_kernel = value != 0;
   else if (n == "bdy_beside") o.bdy_beside = value != 0;
   else if (n == "light_wave_short") o.light_wave_short = value != 0;

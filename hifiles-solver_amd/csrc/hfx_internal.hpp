@@ -235,6 +235,8 @@ struct hfx_ctx
     int les_flux_kernel = 1;    // 1: the LES closure is evaluated in the flux kernel of split variant 3 where its loader-wave form runs
     int affine_metrics = 1;     // 1: on an affine block (every element a parallelepiped) the split stage's flux and update kernels read a 34-double metric record per element in place of most per-point metric arrays
     int flux_two_wave = 1;      // 1: the affine flux kernel of P4 hexahedra as two-wave workgroups, four resident per CU (0: its loader-wave form)
+    int fold_faces = 1;         // 1: with one-sided LDG (|ldg_beta| = 1/2; not with RoeM) the two-wave flux kernel forms the interior pairs' common flux itself and the stage launches no face_flux2_kernel on interior faces (0: the three-launch stage)
+    int flux_two_wave_face = -1; // the local face that carries the two-wave flux kernel's left-over points: -1 the host's choice (two_wave_face), 0-5 forced (tests: reaches the left-over pass of phase B)
     int general_waves = 0;      // waves per workgroup of the general flux kernel: 0 by the LDS image (4 or 8), else 3, 4 or 8
   } opt;
   hfx::Deferred defer;

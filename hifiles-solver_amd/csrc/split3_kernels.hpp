@@ -1704,7 +1704,49 @@ struct TwoWave
   static constexpr long lds_bytes = 8L * (2 * ((G::NF * ND * G::NU + 1) & ~1) + G::NF * NUS + 2 * AffRec::SIZE + S_TOT + G::NF * XSTRIDE);
 };
 
-template <int ND, int N>
+// FOLD form of the two-wave kernel: the common flux of one interior pair, formed by the flux-point lane that holds the pair's only
+// contributing Fn (one-sided LDG: the other side's weight is exactly 0.0) -- what face_flux2_kernel does for the pair, with its
+// functions in its order: the pair oriented by the partner word nb, the partner's flux-point solution from disu_fpts (the update
+// kernel of the stage before wrote it; the lane fetched the same lines an element earlier for its LDG correction), the LEFT point's
+// normal and both points' tdA from the per-point arrays (n tdA of the common flux multiplies the free-stream pressure),
+// own solution `uo` and own projected flux `fno` from the lane's registers.  norm_tconf of BOTH points is written: the pair's
+// other lane has weight zero and stores nothing, so every entry has one writer.
+template <int ND, int RS>
+__device__ __forceinline__ void fold_pair(const Split2Args &a, int nb, long own, long plane_f, const double (&uo)[ND + 2], const double (&fno)[ND + 2])
+{
+  constexpr int NF = ND + 2;
+  const bool right = (nb & 1) != 0;
+  const long part = nb >> 2, il = right ? part : own, ir = right ? own : part;
+  const double beta = ldg_beta(nb, a.P);
+  double up[NF], n[ND];
+  gather_plane(a.disu, part, plane_f, up);
+  gather_plane(a.norm_fpts, il, plane_f, n);
+  const double tl = a.tdA_fpts[il], tr = a.tdA_fpts[ir];
+  // (norm_tconf is an input of every other kernel that takes these arguments, and they stay as they are: the FOLD = false form
+  // compiles to the code it was)
+  double *const tconf = const_cast<double *>(a.tconf);
+  double ul[NF], ur[NF], fl[NF], fr[NF], fn[NF];
+#pragma unroll
+  for (int k = 0; k < NF; k++)
+  {
+    ul[k] = right ? up[k] : uo[k];
+    ur[k] = right ? uo[k] : up[k];
+    fl[k] = right ? 0.0 : fno[k]; // (as gather_pair_needed leaves them)
+    fr[k] = right ? fno[k] : 0.0;
+  }
+  riemann_flux_t<ND, RS, true>(a.P, ul, ur, n, fn);
+#pragma unroll
+  for (int k = 0; k < NF; k++)
+  {
+    const double fv = ldg_flux_projected(a.P, beta, ul[k], ur[k], fl[k], fr[k]);
+    store_flux_both(tconf[il + k * plane_f], tl, tconf[ir + k * plane_f], tr, fn[k], fv);
+  }
+}
+
+// FOLD (SplitPlan::fold_faces: a viscous run with |ldg_beta| = 1/2, Riemann solver RS): an interior flux point whose Fn has the
+// non-zero weight forms its pair's common flux (fold_pair) instead of storing Fn, and the stage launches no face_flux2_kernel on
+// the interior faces.  Boundary and partition-face points (nb < 0) store Fn for their one-sided kernels as before.
+template <int ND, int N, bool FOLD = false, int RS = 0>
 __global__ __launch_bounds__(128, 2) void split_flux_two_wave_kernel(const Split2Args a, const double *coef_g, const int *tidx, const int rot)
 {
   using G = Geo<ND, N>;
@@ -1902,6 +1944,11 @@ __global__ __launch_bounds__(128, 2) void split_flux_two_wave_kernel(const Split
         sd[k * NFP + point] = (nb < 0) ? part[k] : uc - own[k];
       }
     };
+    // FOLD: does this point form its pair's common flux? (an interior point whose own weight is not zero)
+    auto folds = [&](int nb) {
+      const double beta = (nb & 2) ? -a.P.ldg_beta : a.P.ldg_beta;
+      return nb >= 0 && ((nb & 1) ? 0.5 - beta : 0.5 + beta) != 0.0;
+    };
     const bool fn_needed = needed(nb_cur);
     correction(nb_cur, pv, uf, tf);
     // the next element's partner values, and the word of the one after (rotated at the END of the iteration)
@@ -2049,7 +2096,27 @@ __global__ __launch_bounds__(128, 2) void split_flux_two_wave_kernel(const Split
         for (int l = 0; l < ND; l++) nr2[l] = ldsv(&rec[fo + l]);
       }
       // flux point: this side's viscous flux on its own normal
-      if (fn_needed)
+      double fno[FOLD ? NF : 1];
+      bool fold = false;
+      if constexpr (FOLD)
+      {
+        // (kept for the pair's common flux behind the solution point's transform; stored where a one-sided kernel reads it)
+        fold = folds(nb_cur);
+#pragma unroll
+        for (int k = 0; k < NF; k++)
+        {
+          double s = 0.0;
+#pragma unroll
+          for (int l = 0; l < ND; l++) s += f2[1][k + NF * l] * nr2[l];
+          fno[k] = s;
+        }
+        if (fn_needed && !fold)
+        {
+#pragma unroll
+          for (int k = 0; k < NF; k++) g_fn.st(ef + k * plane_f, lf, fno[k]);
+        }
+      }
+      else if (fn_needed)
       {
 #pragma unroll
         for (int k = 0; k < NF; k++)
@@ -2077,6 +2144,13 @@ __global__ __launch_bounds__(128, 2) void split_flux_two_wave_kernel(const Split
             for (int m = 0; m < ND; m++) s += jgp[l + ND * m] * ft[k + NF * m];
             st[(k + NF * l) * NU + tu] = s;
           }
+      }
+      if constexpr (FOLD)
+      {
+        // the pair's common flux, behind the transform (the total flux and the point's JGinv are dead: their registers take the
+        // partner's solution, the normal and the Riemann solver)
+        __builtin_amdgcn_sched_barrier(0);
+        if (fold) fold_pair<ND, RS>(a, nb_cur, ef + tf, plane_f, uf, fno);
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -2127,14 +2201,19 @@ __global__ __launch_bounds__(128, 2) void split_flux_two_wave_kernel(const Split
         calc_visf<ND, true>(a.P, ufx, grf, fq);
 #pragma unroll
         for (int l = 0; l < ND; l++) nl[l] = ldsv(&rec[fox + l]);
+        double fnxo[FOLD ? NF : 1];
+        const bool foldx = FOLD && is_x && folds(nbx_cur);
 #pragma unroll
         for (int k = 0; k < NF; k++)
         {
           double s = 0.0;
 #pragma unroll
           for (int l = 0; l < ND; l++) s += fq[k + NF * l] * nl[l];
-          if (is_x && fnx) g_fn.st(ef + k * plane_f, lx, s);
+          if constexpr (FOLD) fnxo[k] = s;
+          if (is_x && fnx && !foldx) g_fn.st(ef + k * plane_f, lx, s);
         }
+        if constexpr (FOLD)
+          if (foldx) fold_pair<ND, RS>(a, nbx_cur, ef + tx, plane_f, ufx, fnxo);
       }
     }
     lds_barrier(); // 3: st complete; sg is dead: its region takes the divergence parts

@@ -87,6 +87,7 @@ struct SplitPlan
   bool gather = false;          // the flux kernel forms the interior LDG corrections itself (loader wave: GA)
   bool affine = false;          // an affine block: the flux kernel (loader wave: AFF) and the update kernel read the per-element metric record
   bool two_wave = false;        // the affine flux kernel in its two-wave form (split_flux_two_wave_kernel: P4 hexahedra, option flux_two_wave)
+  bool fold_faces = false;      // the two-wave flux kernel forms the interior pairs' common flux (its FOLD form: viscous, |ldg_beta| = 1/2, not RoeM, option fold_faces) and no face_flux2_kernel is launched on the interior faces
   bool face_delta = false;      // face_delta_kernel forms them (a viscous block without `gather`)
   bool oi_fold = false;         // the over-integration kernel hands over its result folded into the divergence
   OverInt over_int = OverInt::none;

@@ -126,7 +126,12 @@ int hfx_ctx_set_CFL(hfx_ctx *ctx, double CFL);
  * hfx_fused_launch_grids reports the grids), "xcd_order" (1), "dictionary_rows" (0), "flux_waves" (2 | 3), "buffer_addressing" (1),
  * "loader_wave" (1), "fold_general" (1: the general fused stage applies opp_2 - opp_3 opp_1 and never forms norm_tdisf), "gather_delta" (1: the loader-wave flux kernel forms the interior LDG corrections itself, no pairwise
  * LDG launch), "simd_roles" (1: the flux kernel deals its waves' parts by SIMD), "flux_two_wave" (1: on P4 hexahedra the affine flux kernel runs as
- * two-wave workgroups, four resident per CU; 0: its loader-wave form; hfx_time_fused_kernels lists "two_wave" behind the kernels when it runs), "comm_stream_faces" (1:
+ * two-wave workgroups, four resident per CU; 0: its loader-wave form; hfx_time_fused_kernels lists "two_wave" behind the kernels when it runs), "fold_faces" (1: in a viscous run with
+ * |ldg_beta| = 1/2 and a Riemann solver other than RoeM the two-wave flux kernel forms the common flux of the interior pairs itself -- the point whose projected viscous flux has the
+ * non-zero weight writes norm_tconf of both sides -- and the stage launches no face_flux2_kernel on interior faces; hfx_time_fused_kernels then
+ * lists "folded_faces" and reports 0.0 ms for the face kernel when the step launched nothing; 0: the three-launch stage, bit for bit as before),
+ * "flux_two_wave_face" (-1: the library's choice | 0-5: the local face that carries the two-wave kernel's left-over points, reported by
+ * hfx_flux_two_wave_face; results agree to rounding, the forced face makes the left-over pass of the kernel's point physics run), "comm_stream_faces" (1:
  * hfx_run_steps_partitioned launches the one-sided partition-face kernels on the communication stream), "flux_stamps" (0; n >= 1: cycle
  * stamps of iteration max(n, 2) of one workgroup of the flux kernels, printed by the hfx_time_* entry points), "tensor_ops" (1),
  * "split_flux" (1: hfx_run_steps_partitioned runs the flux kernel in three launches -- half of the elements without partition-face points,
@@ -698,7 +703,9 @@ int hfx_time_fused_kernels(hfx_eles *e, hfx_inters *const *faces, int n_face_blo
  * built: bytes[5] is the number of flux points whose projected viscous flux Fn the stage needs (one-sided LDG, |ldg_beta| = 1/2, hexahedra: one
  * point of every interior pair and every boundary / partition-face point; otherwise every point), bytes[6] the bytes per stage that
  * the flux kernel does not write and the face kernel does not read for the others (bytes[1] and bytes[2] count every point: the two
- * kernels together move bytes[6] less). */
+ * kernels together move bytes[6] less).  bytes[7]: with folded faces (option "fold_faces"), the bytes per stage that the stage no longer
+ * moves because the flux kernel forms the interior pairs' common flux and face_flux2_kernel is not launched (0 otherwise); bytes[1]
+ * and bytes[2] do not change with it. */
 int hfx_fused_kernel_bytes(hfx_eles *e, double bytes[8]);
 /* The launches of the persistent element kernels since the block's last split fused stage began, in launch order: slot[i] is the
  * kernel's entry in hfx_time_fused_kernels (1 flux / gradient kernel, 3 update / residual kernel, 4 over-integration kernel) or 5 for the
@@ -708,7 +715,7 @@ int hfx_fused_launch_grids(hfx_eles *e, int max_launches, int *slot, int *grid, 
 /* The two-wave form of the affine flux kernel (P4 hexahedra on an affine block, option "flux_two_wave"): 22 of an element's 150 flux
  * points have no partner lane and run as an extra pass, which is skipped when none of them needs its projected viscous flux
  * (one-sided LDG).  The library puts them on the local face whose flux the block needs least often: *face is that face (0..5; -1:
- * the form does not run on this block), need[f] the number of elements that would take the pass with the points on face f (counted
+ * the form does not run on this block; the forced face with option "flux_two_wave_face"), need[f] the number of elements that would take the pass with the points on face f (counted
  * from the partner words and ldg_beta). */
 int hfx_flux_two_wave_face(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int *face, long need[6]);
 /* The same for the general fused stage (hfx_run_steps_blocks(..., fused = 4)): ms[0..3] = pairwise LDG kernels, flux
