@@ -256,6 +256,11 @@ struct hfx_ctx
   // the exact solution of the error monitor (hfx_ctx_set_exact_solution): run_input.test_case and what eval_couette_flow takes
   hfx_exact exact{};
   bool have_exact = false;
+  // the reference state of the wall-force monitor (hfx_ctx_set_force_reference) and what eles::compute_wall_forces forms from it
+  // (src/eles.cpp:5733-5743): factor = 1 / (0.5 rho |u|^2), aoa = atan2(v, u), aos = atan2(w, u)
+  hfx_force_ref force_ref{};
+  double force_factor = 0.0, force_aoa = 0.0, force_aos = 0.0;
+  bool have_force_ref = false;
   hfx::Phys phys() const
   {
     hfx::Phys P;
@@ -331,6 +336,25 @@ struct Probes
 };
 } // namespace hfx
 
+namespace hfx
+{
+// The wall faces of one block (wall_force.hip), sorted by (local face, element): position s of the sorted order is face
+// first[s] / n_cubpts of the caller's packed per-point arrays
+struct WallForces
+{
+  int n_faces = 0, n_inters = 0, max_cubpts = 0;
+  long n_points = 0;               // the sum of the faces' cubature points
+  DevBuf<int> ele, inter, dual;    // (n_faces) sorted order: element | local face | 1 = SLIP_WALL_DUAL
+  DevBuf<long> first;              // (n_faces) sorted order: where the face's points begin in detjac / norm / cp_cf
+  DevBuf<int> n_cubpts;            // (n_inters) per local face
+  DevBuf<long> opp_first, weight_first; // (n_inters) where local face l begins in opp / weight
+  DevBuf<double> opp, weight;      // the local faces' (n_cubpts, n_upts) column-major operators | weights, one behind the other
+  DevBuf<double> detjac, norm;     // the caller's packed arrays: (n_points) | per face (n_cubpts, n_dims) column-major
+  DevBuf<double> cp_cf;            // (n_points, 2): Cp and Cf of the last call, the caller's order
+  DevBuf<double> partial;          // (n_groups, 2 n_dims + 2) of the call that runs
+};
+} // namespace hfx
+
 struct hfx_eles
 {
   hfx_ctx *ctx = nullptr;
@@ -366,6 +390,8 @@ struct hfx_eles
   hfx::Probes probes;
   // mass-flux body force (hfx_eles_set_body_force); null: none registered
   std::unique_ptr<hfx::BodyForce> body_force;
+  // wall faces of the force monitor (hfx_eles_set_wall_faces); null: none registered
+  std::unique_ptr<hfx::WallForces> wall_forces;
   // over-integration (hfx_eles_set_over_int)
   bool over_int_ready = false;
   int n_cubpts = 0;

@@ -64,6 +64,16 @@ extern "C" int hfxh_case_create(const hfxh_case_desc *d, hfxh_case **out)
   in.forcing = d->body_forcing;
   if (d->forcing_area != 0.0) in.forcing_area = d->forcing_area;
   if (d->forcing_mdot0 != 0.0) in.forcing_mdot0 = d->forcing_mdot0;
+  if (d->nx_c_ic != 0.0 || d->ny_c_ic != 0.0 || d->nz_c_ic != 0.0)
+  {
+    in.nx_c_ic = d->nx_c_ic; in.ny_c_ic = d->ny_c_ic; in.nz_c_ic = d->nz_c_ic;
+  }
+  in.calc_force = d->calc_force;
+  if (d->calc_force) /* src/input.cpp:103-107 */
+  {
+    in.area_ref = d->area_ref;
+    in.monitor_cp_freq = d->monitor_cp_freq;
+  }
   if (in.setup_params(g_err)) { delete c; return 1; }
   for (int i = 0; i < d->n_bcs; i++)
   {
@@ -690,6 +700,42 @@ extern "C" int hfxh_case_body_force_history(hfxh_case *c, int max_rows, double *
   eles *E = the_eles(c);
   if (!E->device()) { g_err = "case is not on the device"; return 1; }
   if (hfx_eles_body_force_history(E->device(), max_rows, rows, n_rows)) { g_err = hfx_last_error(); return 1; }
+  return 0;
+}
+
+// ---- wall forces ---------------------------------------------------------------------------------------------------------
+extern "C" int hfxh_case_CalcForces(hfxh_case *c, double *inv_force, double *vis_force, double *cl, double *cd)
+{
+  if (!c || !inv_force || !vis_force || !cl || !cd) { g_err = "hfxh_case_CalcForces: NULL argument"; return 1; }
+  if (CalcForces(&c->S, inv_force, vis_force, cl, cd)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_get_wall_points(hfxh_case *c, int *n_faces, const int **ele, const int **inter, const int **flag,
+                                         const int **n_points, const double **pos, const double **cp, const double **cf)
+{
+  if (!c) { g_err = "hfxh_case_get_wall_points: NULL case"; return 1; }
+  if (!c->S.run_input.calc_force) { g_err = "hfxh_case_get_wall_points: the case was not made with calc_force"; return 1; }
+  eles *E = the_eles(c);
+  if (n_faces) *n_faces = (int)E->wall_ele.size();
+  if (ele) *ele = E->wall_ele.data();
+  if (inter) *inter = E->wall_inter.data();
+  if (flag) *flag = E->wall_flag.data();
+  if (n_points) *n_points = E->wall_n_points.data();
+  if (pos) *pos = E->wall_pos.data();
+  if (cp) *cp = E->wall_cp.empty() ? nullptr : E->wall_cp.data();
+  if (cf) *cf = E->wall_cf.empty() ? nullptr : E->wall_cf.data();
+  return 0;
+}
+
+extern "C" int hfxh_case_get_calc_force(hfxh_case *c, int *calc_force, double *area_ref, int *monitor_cp_freq, double ref[5])
+{
+  if (!c) { g_err = "hfxh_case_get_calc_force: NULL case"; return 1; }
+  const input &in = c->S.run_input;
+  if (calc_force) *calc_force = in.calc_force;
+  if (area_ref) *area_ref = in.area_ref;
+  if (monitor_cp_freq) *monitor_cp_freq = in.monitor_cp_freq;
+  if (ref) { ref[0] = in.rho_c_ic; ref[1] = in.u_c_ic; ref[2] = in.v_c_ic; ref[3] = in.w_c_ic; ref[4] = in.p_c_ic; }
   return 0;
 }
 

@@ -324,7 +324,7 @@ int eles::set_transforms()
   if (set_transforms_pts(0)) return 1;
   if (set_transforms_pts(1)) return 1;
   if (run_input->over_int && set_transforms_pts(2)) return 1;
-  if (run_input->forcing == 1 && n_dims == 3) /* src/eles.cpp:4023 */
+  if (run_input->calc_force != 0 || (run_input->forcing == 1 && n_dims == 3)) /* src/eles.cpp:4023 */
   {
     if (set_inters_cubpts()) return 1;
     set_transforms_inters_cubpts();
@@ -466,6 +466,7 @@ int eles::mv_all_cpu_gpu(hfx_ctx *ctx)
   if (register_volume_cubature()) return 1;
   if (!probe_p2c.empty() && register_probes()) return 1;
   if (run_input->forcing == 1 && n_dims == 3 && register_body_force()) return 1;
+  if (run_input->calc_force != 0 && register_wall_forces()) return 1;
   if (run_input->over_int &&
       hfx_eles_set_over_int(dev, loc_over_int_cubpts.get_dim(1), opp_over_int_cubpts.get_ptr_cpu(), over_int_filter.get_ptr_cpu(),
                             JGinv_over_int_cubpts.get_ptr_cpu()))

@@ -61,13 +61,13 @@ public:
   hf_array<double> disu_average_upts, disu_average_ppts;
   double compute_res_upts(int in_norm_type, int in_field);
   // ---- surface cubature and the mass-flux body force (run_input->forcing; csrc/host/eles_forcing.cpp).  Built by set_transforms
-  // only when forcing is on, like the reference (src/eles.cpp:4023); for EVERY element, where the reference keeps them for its
+  // only when forcing or calc_force is on, like the reference (src/eles.cpp:4023); for EVERY element, where the reference keeps them for its
   // boundary elements only (bdy_ele2ele): the second index of the per-element arrays is the element
   hf_array<int> n_cubpts_per_inter;
   hf_array<hf_array<double>> loc_inters_cubpts, weight_inters_cubpts, tnorm_inters_cubpts; // (n_dims, n_cubpts) | (n_cubpts) | (n_dims, n_cubpts)
   hf_array<hf_array<double>> opp_inters_cubpts;                                            // (n_cubpts, n_upts)
   hf_array<hf_array<double>> inter_detjac_inters_cubpts, norm_inters_cubpts;               // (n_cubpts, n_eles) | (n_cubpts, n_eles, n_dims)
-  virtual int set_inters_cubpts();                // the class's face cubature rule (src/eles_hexas.cpp:284-373); hexahedra only here
+  virtual int set_inters_cubpts();                // the class's face cubature rule (src/eles_hexas.cpp:284-373, src/eles_quads.cpp:251-315); quadrilaterals and hexahedra here
   void set_opp_inters_cubpts();                   // src/eles.cpp:3635-3665
   void set_transforms_inters_cubpts();            // src/eles.cpp:4480-4595
   virtual double compute_inter_detjac_inters_cubpts(int in_inter, const hf_array<double> &d_pos) { return 0.0; }
@@ -83,6 +83,22 @@ public:
   // its two halves around the sum over the ranks (src/eles.cpp:5375-5385), for the transports of solution::comm / reduce_sum
   int body_force_integrals(double integral[2]);
   int body_force_apply(const double integral[2]);
+
+  // ---- wall forces (run_input->calc_force; csrc/host/eles_forces.cpp; output::CalcForces, src/output.cpp:1915-2014).  The surface
+  // cubature above is then built for quadrilaterals and hexahedra (src/eles.cpp:4023).
+  // bcid(ele, l): the boundary group of local face l of the element, -1 none (set by the mesh setup; src/geometry.cpp:292)
+  hf_array<int> bcid;
+  // the wall faces in the reference's order (src/eles.cpp:5746-5769): elements with a boundary face ascending, local faces
+  // ascending -- those whose bcid names a slip, isothermal, adiabatic or dual-consistent slip wall, and ONLY those (the
+  // reference also reads bc_list(-1)); per face the bc flag and the number of cubature points; wall_pos (n_dims, points): calc_pos
+  // of every point, faces as walked, inside a face j DESCENDING, the row order of cp_*.dat
+  void set_wall_inters();
+  std::vector<int> wall_ele, wall_inter, wall_flag, wall_n_points;
+  std::vector<double> wall_pos;
+  int register_wall_forces(); // -> hfx_eles_set_wall_faces
+  // src/eles.cpp:5704 on the device: this class's sums; Cp and Cf of every point -> wall_cp, wall_cf in the order of wall_pos
+  int compute_wall_forces(hf_array<double> &inv_force, hf_array<double> &vis_force, double &temp_cl, double &temp_cd);
+  std::vector<double> wall_cp, wall_cf;
 
   // ---- point probes (csrc/host/eles_probes.cpp; run_input.probe, src/probe_input.cpp, src/output.cpp:1440-1545)
   int calc_p2c(const hf_array<double> &in_pos); // the class's calc_p2c: the element that holds in_pos, -1 none, -2 shape not implemented (probe_error)
@@ -216,6 +232,8 @@ class eles_quads : public eles
 {
 public:
   int face_plane_vertices(int in_n_spts, int in_face, int v[3]) const override;
+  int set_inters_cubpts() override;                                                                // src/eles_quads.cpp:251-315
+  double compute_inter_detjac_inters_cubpts(int in_inter, const hf_array<double> &d_pos) override; // src/eles_quads.cpp:333
 
 protected:
   int setup_ele_type_specific() override;

@@ -15,7 +15,8 @@
 
 int eles::set_inters_cubpts()
 {
-  fail("body force: the surface cubature is built for hexahedra (register the arrays of other classes with hfx_eles_set_body_force)");
+  fail("surface cubature: built for quadrilaterals and hexahedra (register the arrays of other classes with hfx_eles_set_body_force / "
+       "hfx_eles_set_wall_faces)");
   return 1;
 }
 
@@ -113,6 +114,18 @@ void eles::set_transforms_inters_cubpts()
         }
         else
           calc_d_pos(loc, i, d_pos);
+        if (n_dims == 2)
+        {
+          // src/eles.cpp:4529-4554
+          const double t0 = tnorm_inters_cubpts(l)(0, j), t1 = tnorm_inters_cubpts(l)(1, j);
+          const double v0 = (t0 * d_pos(1, 1)) - (t1 * d_pos(1, 0));
+          const double v1 = -(t0 * d_pos(0, 1)) + (t1 * d_pos(0, 0));
+          const double mag = std::sqrt(v0 * v0 + v1 * v1);
+          norm_inters_cubpts(l)(j, i, 0) = v0 / mag;
+          norm_inters_cubpts(l)(j, i, 1) = v1 / mag;
+          inter_detjac_inters_cubpts(l)(j, i) = compute_inter_detjac_inters_cubpts(l, d_pos);
+          continue;
+        }
         const double xr = d_pos(0, 0), xs = d_pos(0, 1), xt = d_pos(0, 2);
         const double yr = d_pos(1, 0), ys = d_pos(1, 1), yt = d_pos(1, 2);
         const double zr = d_pos(2, 0), zs = d_pos(2, 1), zt = d_pos(2, 2);

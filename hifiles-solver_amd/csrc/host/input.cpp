@@ -33,6 +33,8 @@ int input::setup_params(std::string &err)
   if (equation != 0) { err = "Equation not supported"; return 1; }
   if (riemann_solve_type == 1) { err = "Lax-Friedrich flux not supported with NS/RANS equation"; return 1; }
   if (adv_type < 0 || adv_type > 4) { err = "Time advancement scheme not implemented yet!"; return 1; }
+  if (monitor_cp_freq == 0) monitor_cp_freq = 2147483647; /* src/input.cpp:536-537 */
+  if (calc_force && !(area_ref > 0.0)) { err = "calc_force: area_ref must be given and positive (the force coefficients divide by it)"; return 1; }
 
   if (adv_type == 3)
   {
@@ -64,6 +66,7 @@ int input::setup_params(std::string &err)
     mu_inf = mu_gas / mu_ref;
     rt_inf = T_gas * R_gas / (uvw_ref * uvw_ref);
     if (dt_type == 0) dt /= time_ref;
+    if (calc_force) area_ref /= (L_ref * L_ref); /* src/input.cpp:621-622 */
     dx_cyclic /= L_ref;
     dy_cyclic /= L_ref;
     dz_cyclic /= L_ref;

@@ -79,6 +79,10 @@ struct input
   int forcing = 0;
   double forcing_area = 9.162, forcing_mdot0 = 9.162;
   int forcing_history = 4096;
+  // ---- wall forces (src/input.cpp:102-107): calc_force 1 makes output::CalcForces available; area_ref DIMENSIONAL on input (a
+  // viscous run divides it by L_ref^2, src/input.cpp:621-622); monitor_cp_freq 0 means never (src/input.cpp:536-537)
+  int calc_force = 0, monitor_cp_freq = 2147483647;
+  double area_ref = 0.0;
   // ---- element parameters
   int upts_type_hexa = 0, vcjh_scheme_hexa = 1;
   double eta_hexa = 0.0;

@@ -286,6 +286,11 @@ int GeoPreprocess_box(solution *S, const box_mesh &mesh)
   for (int t = 0; t < 3; t++) S->mesh_bdy_inters(t).setup(t == ftype ? (int)bf.size() : 0, t, &in);
   for (size_t m = 0; m < bf.size(); m++) S->mesh_bdy_inters(ftype).set_boundary((int)m, bf[m].g, etype, bf[m].e, bf[m].f, S);
   if (S->mesh_bdy_inters(ftype).failed()) { S->err = S->mesh_bdy_inters(ftype).last_error(); return 1; }
+  // bcid(ele, l) (src/geometry.cpp:292): the group of every boundary face, -1 elsewhere; then the wall faces of the force monitor
+  E->bcid.setup(E->n_eles, nfaces_loc);
+  E->bcid.initialize_to_value(-1);
+  for (size_t m = 0; m < bf.size(); m++) E->bcid(bf[m].e, bf[m].f) = bf[m].g;
+  if (in.calc_force != 0) E->set_wall_inters();
   for (int t = 0; t < 3; t++)
   {
     S->mesh_mpi_inters(t).setup(t == ftype ? S->n_mpi_inters : 0, t, &in);
@@ -328,9 +333,12 @@ int GeoPreprocess_box(solution *S, const box_mesh &mesh)
   if (S->n_mpi_inters)
   {
     mpi_inters &M = S->mesh_mpi_inters(ftype);
-    int rot_of_face[6];
+    int rot_of_face[6] = {0, 0, 0, 0, 0, 0};
+    bool face_used[6] = {false, false, false, false, false, false};
+    for (size_t m = 0; m < mf.size(); m++) face_used[mf[m].f] = true;
     for (int f = 0; f < nfaces_loc; f++)
     {
+      if (!face_used[f]) continue; // (a direction one cell thick between two walls has no such pair, and no partition face)
       const int *fd = (dims == 3) ? hex_face[f] : quad_face[f];
       const int d = fd[0];
       int c[3] = {0, 0, 0};
@@ -549,6 +557,50 @@ int CalcIntegralQuantities(solution *S, double *integral_quantities)
   return 0;
 }
 
+int RegisterForceReference(solution *S)
+{
+  if (!S->ctx) return 0; // (MoveToDevice registers it)
+  const input &in = S->run_input;
+  hfx_force_ref r{};
+  r.rho_c_ic = in.rho_c_ic; r.u_c_ic = in.u_c_ic; r.v_c_ic = in.v_c_ic; r.w_c_ic = in.w_c_ic; r.p_c_ic = in.p_c_ic;
+  r.area_ref = in.area_ref;
+  if (hfx_ctx_set_force_reference(S->ctx, &r)) { S->err = hfx_last_error(); return 1; }
+  return 0;
+}
+
+int CalcForces(solution *S, double *inv_force, double *vis_force, double *cl, double *cd)
+{
+  const input &in = S->run_input;
+  if (!in.calc_force) { S->err = "CalcForces: the case was not made with calc_force"; return 1; }
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  const int nd = S->n_dims;
+  double v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // inv_force, vis_force, coeff_lift, coeff_drag
+  hf_array<double> temp_inv_force, temp_vis_force;
+  for (int i = 0; i < S->n_ele_types; i++)
+  {
+    eles *E = S->mesh_eles(i);
+    if (!E || E->get_n_eles() == 0) continue;
+    double temp_cl = 0.0, temp_cd = 0.0;
+    if (E->compute_wall_forces(temp_inv_force, temp_vis_force, temp_cl, temp_cd)) { S->err = E->last_error(); return 1; }
+    for (int m = 0; m < nd; m++)
+    {
+      v[m] += temp_inv_force(m);
+      v[nd + m] += temp_vis_force(m);
+    }
+    v[2 * nd] += temp_cl;
+    v[2 * nd + 1] += temp_cd;
+  }
+  if (sum_over_ranks(S, v, 2 * nd + 2, "CalcForces")) return 1;
+  for (int m = 0; m < nd; m++)
+  {
+    inv_force[m] = v[m];
+    vis_force[m] = v[nd + m];
+  }
+  *cl = v[2 * nd];
+  *cd = v[2 * nd + 1];
+  return 0;
+}
+
 int MoveToDevice(solution *S, int device)
 {
   if (hfx_ctx_create(device, &S->ctx)) { S->err = hfx_last_error(); return 1; }
@@ -559,6 +611,7 @@ int MoveToDevice(solution *S, int device)
   if (hfx_ctx_set_option(S->ctx, "deferred", S->deferred ? 1 : 0)) { S->err = hfx_last_error(); return 1; }
   if (RegisterProbeFields(S)) return 1; // (before the element blocks, which register their probes)
   if (S->run_input.test_case != 0 && RegisterExactSolution(S)) return 1;
+  if (S->run_input.calc_force != 0 && RegisterForceReference(S)) return 1;
   for (int i = 0; i < S->n_ele_types; i++)
     if (S->mesh_eles(i) && S->mesh_eles(i)->get_n_eles() != 0)
       if (S->mesh_eles(i)->mv_all_cpu_gpu(S->ctx)) { S->err = S->mesh_eles(i)->last_error(); return 1; }

@@ -88,6 +88,12 @@ int RegisterExactSolution(solution *S);
 int ComputeError(solution *FlowSol, double *error);
 // output::CalcIntegralQuantities (src/output.cpp:2017-2038): run_input's integral quantities over the classes and the ranks
 int CalcIntegralQuantities(solution *FlowSol, double *integral_quantities);
+// run_input's reference state -> the context (hfx_ctx_set_force_reference): rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic, area_ref
+int RegisterForceReference(solution *S);
+// output::CalcForces (src/output.cpp:1915-2014) without the file: eles::compute_wall_forces of every element class, summed, then
+// summed over the ranks (one SUM reduction of 2 n_dims + 2 values; every rank gets the sums, where the reference's MPI_Reduce
+// gives them to rank 0)
+int CalcForces(solution *FlowSol, double *inv_force, double *vis_force, double *cl, double *cd);
 // switch deferred execution on / off (before or after MoveToDevice)
 int SetDeferred(solution *FlowSol, bool on);
 

@@ -156,6 +156,26 @@ def body_force_history_of(call, max_rows):
     return rows[:, :n.value].T.copy()
 
 
+class ForceRef(C.Structure):
+    """hfx_force_ref: the reference state of the wall-force monitor"""
+    _fields_ = [(n, C.c_double) for n in ("rho_c_ic", "u_c_ic", "v_c_ic", "w_c_ic", "p_c_ic", "area_ref")]
+
+
+def wall_forces_of(call, n_dims, n_points):
+    """call(inv_force*, vis_force*, cl*, cd*, cp*, cf*) -> dict; n_points None: no per-point values asked for"""
+    fi, fv = (C.c_double * 3)(), (C.c_double * 3)()
+    cl, cd = C.c_double(0), C.c_double(0)
+    out = {}
+    if n_points is None:
+        call(fi, fv, C.byref(cl), C.byref(cd), None, None)
+    else:
+        cp, cf = np.zeros(max(1, n_points)), np.zeros(max(1, n_points))
+        call(fi, fv, C.byref(cl), C.byref(cd), cp.ctypes.data_as(dp), cf.ctypes.data_as(dp))
+        out = {"cp": cp[:n_points], "cf": cf[:n_points]}
+    out.update(inv_force=np.array(fi[:n_dims]), vis_force=np.array(fv[:n_dims]), cl=cl.value, cd=cd.value)
+    return out
+
+
 def set_probes_of(eles_handle, n_upts, ele, opp_probe):
     el = np.ascontiguousarray(np.array(ele, dtype=np.int32).ravel())
     opp = _f(np.array(opp_probe, dtype=np.float64).reshape((n_upts, len(el)), order="F"))
@@ -231,6 +251,11 @@ class Context:
         """test_case 1: isentropic vortex; 5: Couette flow, which takes the five parameters (hfx_exact)"""
         x = Exact(int(test_case), 0, u_wall, T_wall, p_bound, R_ref, T_ref)
         check(lib().hfx_ctx_set_exact_solution(self.h, C.byref(x)))
+
+    def set_force_reference(self, rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic, area_ref):
+        """the reference state the wall forces are made coefficients with (hfx_force_ref)"""
+        r = ForceRef(rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic, area_ref)
+        check(lib().hfx_ctx_set_force_reference(self.h, C.byref(r)))
 
     def flush(self):
         """deferred execution: run what has been recorded (no-op otherwise)"""
@@ -395,6 +420,44 @@ class Eles:
     def body_force_history(self, max_rows=64):
         """(n, 3): mass_flux, ubulk, body_force(1) of the newest evaluations, oldest first"""
         return body_force_history_of(lambda *a: check(lib().hfx_eles_body_force_history(self.h, *a)), max_rows)
+
+    def set_wall_faces(self, face_ele, face_inter, face_flag, opp_inters_cubpts, weight_inters_cubpts, inter_detjac_inters_cubpts,
+                       norm_inters_cubpts):
+        """hfx_eles_set_wall_faces.  face_ele, face_inter, face_flag: the wall faces as (element, local face, BC_* flag);
+        opp_inters_cubpts[l] (n_cubpts, n_upts) and weight_inters_cubpts[l] (n_cubpts) per local face l (None for faces nobody
+        names); per listed face, in list order, inter_detjac_inters_cubpts (n_cubpts) and norm_inters_cubpts (n_cubpts, n_dims)."""
+        fe, fl, ff = [np.ascontiguousarray(np.array(a, dtype=np.int32).ravel()) for a in (face_ele, face_inter, face_flag)]
+        nl = len(opp_inters_cubpts)
+        opp = [None if a is None else _f(a) for a in opp_inters_cubpts]
+        wgt = [None if a is None else np.ascontiguousarray(np.array(a, dtype=np.float64).ravel()) for a in weight_inters_cubpts]
+        ncub = (C.c_int * max(1, nl))(*[0 if a is None else a.shape[0] for a in opp])
+        po = (dp * max(1, nl))(*[None if a is None else a.ctypes.data_as(dp) for a in opp])
+        pw = (dp * max(1, nl))(*[None if a is None else a.ctypes.data_as(dp) for a in wgt])
+        cat = lambda parts: np.ascontiguousarray(np.concatenate(parts) if len(parts) else np.zeros(1))
+        dj = cat([np.array(a, dtype=np.float64).ravel() for a in inter_detjac_inters_cubpts])
+        nm = cat([_f(a).ravel(order="F") for a in norm_inters_cubpts])
+        check(lib().hfx_eles_set_wall_faces(self.h, C.c_int(len(fe)), fe.ctypes.data_as(ip), fl.ctypes.data_as(ip), ff.ctypes.data_as(ip),
+                                            C.c_int(nl), ncub, po, pw, dj.ctypes.data_as(dp), nm.ctypes.data_as(dp)))
+        self.n_wall_points = int(sum(ncub[l] for l in fl))
+
+    def clear_wall_faces(self): self._call("hfx_eles_clear_wall_faces")
+
+    def compute_wall_forces(self, points=True):
+        """eles::compute_wall_forces of this block: dict(inv_force (n_dims), vis_force (n_dims), cl, cd) and, with `points`,
+        cp and cf (one value per listed face and cubature point, the caller's order)"""
+        return wall_forces_of(lambda *a: check(lib().hfx_eles_compute_wall_forces(self.h, *a)), self.n_dims,
+                              getattr(self, "n_wall_points", 0) if points else None)
+
+    def wall_force_launch(self):
+        """(workgroups, faces per pass) of the next compute_wall_forces"""
+        g, n = C.c_int(0), C.c_int(0)
+        check(lib().hfx_eles_wall_force_launch(self.h, C.byref(g), C.byref(n)))
+        return g.value, n.value
+
+    def time_wall_forces(self, reps=20):
+        v = C.c_double(0)
+        check(lib().hfx_time_wall_forces(self.h, C.c_int(reps), C.byref(v)))
+        return v.value
 
     def extrapolate_solution(self): self._call("hfx_eles_extrapolate_solution")
     def calculate_gradient(self): self._call("hfx_eles_calculate_gradient")

@@ -30,7 +30,9 @@ class CaseDesc(C.Structure):
                 ("s0", C.c_double), ("expf_fac", C.c_double), ("expf_order", C.c_int), ("expf_cutoff", C.c_int),
                 ("LES", C.c_int), ("SGS_model", C.c_int), ("C_s", C.c_double), ("filter_ratio", C.c_double),
                 ("prandtl_t", C.c_double), ("p_res", C.c_int), ("self_partition", C.c_int * 3), ("filter_type", C.c_int),
-                ("body_forcing", C.c_int), ("forcing_area", C.c_double), ("forcing_mdot0", C.c_double)]
+                ("body_forcing", C.c_int), ("forcing_area", C.c_double), ("forcing_mdot0", C.c_double),
+                ("nx_c_ic", C.c_double), ("ny_c_ic", C.c_double), ("nz_c_ic", C.c_double),
+                ("calc_force", C.c_int), ("area_ref", C.c_double), ("monitor_cp_freq", C.c_int)]
 
 
 class BcDesc(C.Structure):
@@ -525,6 +527,38 @@ class Case:
     def body_force_history(self, max_rows=4096):
         """rows (n, 3) of (mass_flux, ubulk, body_force(1)), oldest first: the columns of the reference's massflux.dat"""
         return hfx.body_force_history_of(lambda *a: check(lib().hfxh_case_body_force_history(self.h, *a)), max_rows)
+
+    # ---- wall forces (calc_force=1, area_ref=..., monitor_cp_freq=... among the case's keys)
+    def CalcForces(self):
+        """output::CalcForces at the mirror's clock, over blocks and ranks: dict(inv_force (n_dims), vis_force (n_dims), cl, cd)"""
+        fi, fv = (C.c_double * 3)(), (C.c_double * 3)()
+        cl, cd = C.c_double(0), C.c_double(0)
+        check(lib().hfxh_case_CalcForces(self.h, fi, fv, C.byref(cl), C.byref(cd)))
+        return dict(inv_force=np.array(fi[:self.n_dims]), vis_force=np.array(fv[:self.n_dims]), cl=cl.value, cd=cd.value)
+
+    def wall_points(self):
+        """the rows of cp_*.dat: dict(ele, inter, flag, n_points (n_faces each), pos (n_dims, points), cp, cf (points; None
+        before the first CalcForces)); faces in the reference's order, inside a face the cubature index descending"""
+        n, e, l, fl, npts = C.c_int(0), ip(), ip(), ip(), ip()
+        pos, cp, cf = dp(), dp(), dp()
+        check(lib().hfxh_case_get_wall_points(self.h, C.byref(n), C.byref(e), C.byref(l), C.byref(fl), C.byref(npts), C.byref(pos),
+                                              C.byref(cp), C.byref(cf)))
+        k = n.value
+        iarr = lambda p: np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.zeros(0, dtype=np.int32)
+        out = dict(ele=iarr(e), inter=iarr(l), flag=iarr(fl), n_points=iarr(npts))
+        tot = int(out["n_points"].sum())
+        darr = lambda p, m: np.ctypeslib.as_array(p, shape=(m,)).copy() if (m and p) else None
+        P = darr(pos, tot * self.n_dims)
+        out["pos"] = np.zeros((self.n_dims, 0)) if P is None else P.reshape((self.n_dims, tot), order="F")
+        out["cp"], out["cf"] = darr(cp, tot), darr(cf, tot)
+        return out
+
+    def calc_force(self):
+        """dict(calc_force, area_ref (non-dimensional), monitor_cp_freq, rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic)"""
+        on, a, m, r = C.c_int(0), C.c_double(0), C.c_int(0), (C.c_double * 5)()
+        check(lib().hfxh_case_get_calc_force(self.h, C.byref(on), C.byref(a), C.byref(m), r))
+        return dict(calc_force=on.value, area_ref=a.value, monitor_cp_freq=m.value, rho_c_ic=r[0], u_c_ic=r[1], v_c_ic=r[2],
+                    w_c_ic=r[3], p_c_ic=r[4])
 
     def close(self):
         if self.h:

@@ -499,6 +499,62 @@ int hfx_eles_body_force_state(hfx_eles *e, double *mass_flux, double *ubulk, dou
  * massflux.dat (src/eles.cpp:5445-5451) --, oldest first: rows (3, *n_rows).  max_rows == 0 asks for the number alone */
 int hfx_eles_body_force_history(hfx_eles *e, int max_rows, double *rows, int *n_rows);
 
+/* ---- wall forces: output::CalcForces (src/output.cpp:1915-2014), eles::compute_wall_forces (src/eles.cpp:5704-5990) ----
+ * The force on the walls of a block -- Fx, Fy(, Fz), CL, CD of history.plt (src/output.cpp:2381-2393) -- and Cp and Cf at every
+ * wall cubature point (force_files_<step>/cp_<step>_p<rank>.dat), in one fused kernel per call.
+ *
+ * The reference state, non-dimensional as run_input holds it (src/input.cpp:534-612).  The library forms from it, as
+ * src/eles.cpp:5733-5743 do, factor = 1 / (0.5 rho_c_ic (u_c_ic^2 + v_c_ic^2 + w_c_ic^2)), aoa = atan2(v_c_ic, u_c_ic),
+ * aos = atan2(w_c_ic, u_c_ic).  Refused when the speed is zero or area_ref <= 0 (the reference would divide by zero). */
+typedef struct hfx_force_ref
+{
+  double rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic, area_ref;
+} hfx_force_ref;
+int hfx_ctx_set_force_reference(hfx_ctx *ctx, const hfx_force_ref *ref);
+/* The wall faces of one block, as (element, local face, bc flag) triples in the order the caller wants its results in:
+ *   face_ele[n_faces], face_inter[n_faces], face_flag[n_faces]   face_flag is HFX_BC_SLIP_WALL, HFX_BC_ISOTHERM_WALL,
+ *       HFX_BC_ADIABAT_WALL or HFX_BC_SLIP_WALL_DUAL (the four kinds src/eles.cpp:5768-5769 take).  n_faces == 0 is legal
+ *   n_inters_per_ele, and per local face l: n_cubpts_per_inter[l], opp_inters_cubpts[l] (n_cubpts, n_upts) column-major,
+ *       weight_inters_cubpts[l] (n_cubpts), as for hfx_eles_set_body_force; entries of local faces no listed face names may be NULL
+ *   inter_detjac_inters_cubpts   per listed face, in list order, the n_cubpts values of its local face (packed)
+ *   norm_inters_cubpts           per listed face, in list order, (n_cubpts, n_dims) column-major (packed): the unit normals
+ * A face is one whose bcid names a group of one of the four kinds; the reference's loop also takes local faces of boundary
+ * elements that belong to NO group (bcid == -1, an out-of-bounds read of bc_list): those are not wall faces and are not to be
+ * listed.  The library sorts the faces by (local face, element) internally; every result is in the caller's order.
+ * Registering again replaces everything.  Refused, before anything changes: a face outside the block, an unknown flag, a local
+ * face without its operator, more than 256 cubature points on a face.  Should a device allocation fail after that, the block is
+ * left without wall faces. */
+int hfx_eles_set_wall_faces(hfx_eles *e, int n_faces, const int *face_ele, const int *face_inter, const int *face_flag,
+                            int n_inters_per_ele, const int *n_cubpts_per_inter, const double *const *opp_inters_cubpts,
+                            const double *const *weight_inters_cubpts, const double *inter_detjac_inters_cubpts,
+                            const double *norm_inters_cubpts);
+/* drops the registration; no-op without one */
+int hfx_eles_clear_wall_faces(hfx_eles *e);
+/* eles::compute_wall_forces for one block: inv_force[n_dims], vis_force[n_dims], *cl, *cd are this block's sums (the caller adds
+ * blocks and ranks, src/output.cpp:1980-2009); cp and cf, either of which may be NULL, take one value per (listed face, cubature
+ * point) in the caller's list order, faces packed as inter_detjac_inters_cubpts is; inside a face the index is the reference's j
+ * (the reference PRINTS j descending).  Per point (src/eles.cpp:5773-5986): the state -- and on a viscous context the gradient --
+ * interpolated by opp_inters_cubpts(l); the pressure, for HFX_BC_SLIP_WALL_DUAL from the momenta with their normal part removed
+ * (which the viscous part then uses too); Cp = (p - p_c_ic) factor; Finv = wgt (p - p_c_ic) n detjac factor / area_ref; on a
+ * viscous context, for walls of ALL four kinds, mu from Sutherland's law blended by fix_vis, S with its trace / 3.0 removed (in
+ * two dimensions too), taun = 2 mu S n, Cf = |taun - (taun . n) n| factor, Fvis = -wgt taun detjac factor / area_ref; cl and cd by the
+ * reference's formulas, in three dimensions cd = F0 cos(aoa) cos(aos) + F1 sin(aoa) + F2 sin(aoa) cos(aos).  On an inviscid
+ * context vis_force and cf are zero and grad_disu_upts is never touched.
+ * The gradient: a viscous context reads grad_disu_upts AS IT STANDS, like the reference, which pairs the new state with the
+ * gradient of the last RK stage.  With deferred execution a pending stage is replayed call by call so that it leaves that
+ * gradient.  After a fused stage that kept the gradient on chip (hfx_run_steps(..., 3), hfx_run_steps_blocks(..., 4)) the call is
+ * refused, as hfx_eles_download is: run hfx_CalcResidual first -- its correct_gradient writes the gradient of the CURRENT state --
+ * and the forces are then those of the current state and its own gradient.
+ * Reproducible: shuffles inside a wave, the waves in their order, one partial per workgroup, added by the host in workgroup
+ * order; no floating-point atomics, two calls on one state agree bit for bit.  Every refusal -- no registration, no force
+ * reference, a block that is not n_dims + 2 fields in two or three dimensions, a stale gradient -- comes before anything is
+ * launched; a block with zero wall faces returns zeros and launches nothing.  Waits for the compute stream. */
+int hfx_eles_compute_wall_forces(hfx_eles *e, double *inv_force, double *vis_force, double *cl, double *cd, double *cp, double *cf);
+/* what the next hfx_eles_compute_wall_forces launches: workgroups, and the consecutive faces a workgroup takes per pass */
+int hfx_eles_wall_force_launch(hfx_eles *e, int *n_groups, int *faces_per_pass);
+/* device milliseconds of the kernel of one hfx_eles_compute_wall_forces, averaged over `reps` launches */
+int hfx_time_wall_forces(hfx_eles *e, int reps, double *ms);
+
 /* ---- CFL time stepping (calc_time_step, src/solver.cpp:484-549) ---------- */
 int hfx_eles_set_h_ref(hfx_eles *e, const double *h_ref); /* eles::h_ref (n_eles), src/eles.cpp:3985 */
 /* dt_local(ic) = eles::calc_dt_local(ic) (src/eles.cpp:1267-1356) for every element -> HFX_DT_LOCAL, and the

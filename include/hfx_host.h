@@ -94,6 +94,16 @@ typedef struct hfxh_case_desc
    * with hfx_eles_set_body_force, and CalcResidual evaluates the force at the first RK stage of every step. */
   int body_forcing;
   double forcing_area, forcing_mdot0;
+  /* the direction of the initial / reference velocity of a viscous case, `nx_c_ic`, `ny_c_ic`, `nz_c_ic` (src/input.cpp:646-649);
+   * all three 0: the reference's default (1, 0, 0) */
+  double nx_c_ic, ny_c_ic, nz_c_ic;
+  /* wall forces (src/input.cpp:102-107): `calc_force` 1, `area_ref` (dimensional; must then be positive) and `monitor_cp_freq`
+   * (0: never, src/input.cpp:536-537).  The mirror then builds the surface cubature of the quadrilaterals / hexahedra (src/eles.cpp:4023),
+   * lists the wall faces, and hfxh_case_to_device registers them (hfx_eles_set_wall_faces) and the reference state
+   * rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic, area_ref (hfx_ctx_set_force_reference). */
+  int calc_force;
+  double area_ref;
+  int monitor_cp_freq;
 } hfxh_case_desc;
 
 const char *hfxh_last_error(void);
@@ -302,6 +312,28 @@ int hfxh_case_get_inflow_faces(hfxh_case *c, const int **ele, const int **inter,
 int hfxh_case_body_force_state(hfxh_case *c, double *mass_flux, double *ubulk, double *body_force_x, double accumulated[2],
                                double integral[2], long *n_steps);
 int hfxh_case_body_force_history(hfxh_case *c, int max_rows, double *rows, int *n_rows);
+
+/* ---- wall forces (hfxh_case_desc.calc_force) --------------------------------------------------------------------------------
+ * output::CalcForces (src/output.cpp:1915-2014) without the file, at the mirror's clock: inv_force[n_dims], vis_force[n_dims], *cl,
+ * *cd summed over the case's blocks, then over the ranks -- the library's communicator, else ONE call of the hook of
+ * hfxh_case_set_reduce_sum with 2 n_dims + 2 values (the MPI_Reduce of :1992-2009; every rank gets the sums).  What the
+ * reference puts into every line of history.plt (src/output.cpp:2381-2393).  The case must be on the device; a viscous case reads
+ * grad_disu_upts as it stands (hfx_eles_compute_wall_forces): behind hfxh_case_run that is the gradient of the last RK stage,
+ * the reference's pairing.
+ * The wall faces are those whose boundary group is a slip, isothermal, adiabatic or dual-consistent slip wall.  The reference's
+ * loop also reads run_input.bc_list(-1) for the local faces of a boundary element that belong to no group and may take them for
+ * walls; that defect is not reproduced. */
+int hfxh_case_CalcForces(hfxh_case *c, double *inv_force, double *vis_force, double *cl, double *cd);
+/* The rows of force_files_<step>/cp_<step>_p<rank>.dat: the wall faces in the reference's order (boundary elements ascending, local
+ * faces ascending) as ele[n_faces], inter[n_faces], flag[n_faces] (hfx_bc_flag: the label the file prints above a face's rows) and
+ * n_points[n_faces]; then, over all faces' points in file order (inside a face the cubature index DESCENDING), pos (n_dims, points)
+ * column-major -- calc_pos of the point, evaluated once when the case is made -- and cp, cf (points) of the last
+ * hfxh_case_CalcForces (NULL before the first).  Host only but for cp and cf; any pointer may be NULL. */
+int hfxh_case_get_wall_points(hfxh_case *c, int *n_faces, const int **ele, const int **inter, const int **flag, const int **n_points,
+                              const double **pos, const double **cp, const double **cf);
+/* calc_force, area_ref (non-dimensional, as the device gets it), monitor_cp_freq and the reference state as the case holds them:
+ * ref[5] = rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic.  Any pointer may be NULL */
+int hfxh_case_get_calc_force(hfxh_case *c, int *calc_force, double *area_ref, int *monitor_cp_freq, double ref[5]);
 
 #ifdef __cplusplus
 }
