@@ -153,6 +153,9 @@ int end_of_step(hfx_eles *const *eles, int neb)
   if (ctx->n_probe_fields > 0 && ctx->i_steps % ctx->probe_freq == 0) /* src/HiFiLES.cpp:289-297 */
     for (int i = 0; i < neb; i++)
       if (sample_probes(eles[i], ctx->time, ctx->i_steps)) return 1;
+  if (integral_monitor_samples(ctx, ctx->i_steps)) /* src/HiFiLES.cpp:247-266 */
+    for (int i = 0; i < neb; i++)
+      if (sample_integrals(eles[i], ctx->time, ctx->i_steps)) return 1;
   return 0;
 }
 

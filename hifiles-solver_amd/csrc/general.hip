@@ -1253,20 +1253,32 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
   // disu_fpts of the current state (the caller may have changed disu_upts since the last call)
   for (int i = 0; i < neb; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
+  // as split_run_steps: the last stage of a step the integral monitor samples with an id 1-4 runs call by call and leaves
+  // grad_disu_upts of its input state
+  hfx_ctx *ctx = eles[0]->ctx;
+  bool monitor_gradient = false, by_calls = false;
+  for (int i = 0; i < neb; i++) monitor_gradient = monitor_gradient || eles[i]->n_vol_cubpts > 0;
+  monitor_gradient = monitor_gradient && ctx->params.viscous && integral_monitor_reads_gradient(ctx);
   for (int s = 0; s < n_steps; s++)
   {
     if (calc_time_step_blocks(eles, neb)) return 1; /* src/HiFiLES.cpp:198 */
     if (begin_of_step(eles, neb, nullptr)) return 1; /* src/solver.cpp:96-109 */
+    by_calls = monitor_gradient && integral_monitor_samples(ctx, (long)ctx->i_steps + 1);
     for (int rk = 0; rk < nst; rk++)
     {
       if (rk == 0 && first_stage_closure_filter(eles, neb, true)) return 1;
+      if (by_calls && rk == nst - 1)
+      {
+        if (stage_call_by_call(eles, neb, faces, nfb, rk)) return 1;
+        continue;
+      }
       if (GeneralStage(eles, neb, faces, nfb, rk).run()) return 1;
       if (general_shock_capture(eles, neb)) return 1;
     }
     advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
     if (end_of_step(eles, neb)) return 1; /* src/HiFiLES.cpp:221-245 */
   }
-  for (int i = 0; i < neb; i++) note_gradients(eles[i], false); // (the general stage keeps them on chip)
+  for (int i = 0; i < neb; i++) note_gradients(eles[i], by_calls); // (the general stage keeps them on chip)
   return 0;
 }
 

@@ -1709,6 +1709,24 @@ int hfx_CalcResidual(hfx_eles *e, hfx_inters *const *faces, int nfb)
   return hfx_CalcResidual_blocks(&e, 1, faces, nfb);
 }
 
+} // extern "C"
+
+int hfx::stage_call_by_call(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int rk)
+{
+  const int adv = eles[0]->ctx->params.adv_type;
+  if (hfx_CalcResidual_blocks(eles, neb, faces, nfb)) return 1;
+  for (int i = 0; i < neb; i++)
+    if (hfx_eles_AdvanceSolution(eles[i], rk, adv)) return 1;
+  for (int i = 0; i < neb; i++)
+    if (eles[i]->shock_ready && hfx_eles_shock_capture(eles[i])) return 1; /* src/HiFiLES.cpp:214-216 */
+  // (the update call by call has cleared fpts_valid, DESIGN.md 3.7: the fused stage behind this one reads disu_fpts of the new state)
+  for (int i = 0; i < neb; i++)
+    if (hfx_eles_extrapolate_solution(eles[i])) return 1;
+  return 0;
+}
+
+extern "C" {
+
 int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int n_steps, int fused)
 {
   HFX_CHECK(eles && neb > 0 && eles[0], "hfx_run_steps_blocks: no element blocks");
@@ -1718,6 +1736,7 @@ int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *face
   const int adv = ctx->params.adv_type;
   const int nst = n_rk_stages(adv); /* src/HiFiLES.cpp:143-150 */
   if (probes_check_capacity(eles, neb, n_steps)) return 1;
+  if (integrals_check_capacity(eles, neb, n_steps)) return 1;
   if (fused == 4) return general_run_steps(eles, neb, faces, nfb, n_steps);
   HFX_CHECK(fused == 0 || neb == 1, "hfx_run_steps_blocks: the split fused stage (fused %d) takes one tensor-product element block; "
                                     "several blocks run per method (0) or through the general fused stage (4)", fused);

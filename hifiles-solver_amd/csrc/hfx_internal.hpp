@@ -253,6 +253,11 @@ struct hfx_ctx
   int n_probe_fields = 0, probe_freq = 1, probe_capacity = 0;
   int probe_codes[HFX_MAX_PROBE_FIELDS] = {};
   unsigned long probe_epoch = 0;
+  // the integral monitor (hfx_ctx_set_integral_monitor): run_input.integral_quantities as the ids of hfx_eles_CalcIntegralQuantities,
+  // run_input.monitor_res_freq and the samples a block's device history holds.  iq_epoch: as probe_epoch
+  int n_iq = 0, iq_freq = 1, iq_capacity = 0;
+  int iq_ids[8] = {};
+  unsigned long iq_epoch = 0;
   // the exact solution of the error monitor (hfx_ctx_set_exact_solution): run_input.test_case and what eval_couette_flow takes
   hfx_exact exact{};
   bool have_exact = false;
@@ -355,6 +360,21 @@ struct WallForces
 };
 } // namespace hfx
 
+namespace hfx
+{
+// The integral-quantity history of one block (integrals.hip)
+struct IntegralHistory
+{
+  // (n_quantities, capacity + 1): sample s at [n_quantities * s]; the last slot is the scratch of hfx_time_integral_quantities
+  DevBuf<double> history;
+  DevBuf<double> partial;         // (n_groups, n_quantities) of the sample that runs
+  int n_quantities = 0, capacity = 0; // what `history` was made for
+  unsigned long epoch = 0;        // ctx->iq_epoch it was made at
+  std::vector<double> times;      // of the stored samples; their number is the number of stored samples
+  std::vector<int> steps;
+};
+} // namespace hfx
+
 struct hfx_eles
 {
   hfx_ctx *ctx = nullptr;
@@ -374,6 +394,8 @@ struct hfx_eles
   hfx::Operator opp_volume_cubpts;
   hfx::DevBuf<double> weight_volume_cubpts, vol_detjac_vol_cubpts, iq_u, iq_g;
   hfx::DevBuf<int> iq_ids; // the quantity ids of the call that runs
+  // the samples of the context's integral monitor (hfx_ctx_set_integral_monitor)
+  hfx::IntegralHistory integrals;
   // exact-solution error norms (error_norm.hip): pos_volume_cubpts (n_vol_cubpts, n_eles, n_dims) of hfx_eles_set_error_points,
   // the cubature size it was registered for, and one partial per workgroup and quantity of the call that runs
   hfx::DevBuf<double> pos_volume_cubpts, err_partial;
@@ -507,14 +529,42 @@ int first_stage_closure_filter(hfx_eles *const *eles, int neb, bool refresh_svv)
 void advance_ramp_counters(hfx_inters *const *faces, int nfb);
 // what the reference's main loop does between the last RK stage and the outputs (src/HiFiLES.cpp:221-245), for a context whose
 // clock is the library's: time += dt, i_steps++, spinup_time at step 1, then the time averages of every block that has average
-// fields (averages.hip), then -- when i_steps % probe_freq == 0 -- one sample of every block that has probes (probes.hip).  Nothing
-// for a context without a clock; no launch for a block without average fields or probes
+// fields (averages.hip), then -- when i_steps % probe_freq == 0 -- one sample of every block that has probes (probes.hip), then -- when
+// i_steps == 1 || i_steps % monitor_res_freq == 0 -- one sample of the integral monitor for every block with a cubature
+// (integrals.hip).  Nothing for a context without a clock; no launch for a block without average fields, probes or a monitor
 int end_of_step(hfx_eles *const *eles, int neb);
 // (probes.hip) one sample of e's probes on the compute stream; nothing for a block or a context without probes
 int sample_probes(hfx_eles *e, double time, int step);
 // what every step loop asks before its first launch: can the histories of these blocks take the samples of the next n_steps steps?
 // Nothing to ask without the library's clock or without probes
 int probes_check_capacity(hfx_eles *const *eles, int neb, int n_steps);
+// ---- the integral monitor (integrals.hip) ----
+// does the reference fill the Diagnostics columns after step `step`?  i_steps == 1 || i_steps % monitor_res_freq == 0
+// (src/HiFiLES.cpp:247-266)
+inline bool integral_sample_step(long step, long freq) { return step == 1 || step % freq == 0; }
+// how many of the steps i_steps + 1 .. i_steps + n_steps are such steps
+inline long integral_samples_in(long i_steps, long n_steps, long freq)
+{
+  if (n_steps <= 0) return 0;
+  const long last = i_steps + n_steps;
+  return last / freq - i_steps / freq + ((freq > 1 && i_steps < 1 && last >= 1) ? 1 : 0);
+}
+// will the step loops sample behind the step that makes i_steps `step`?
+inline bool integral_monitor_samples(const hfx_ctx *ctx, long step)
+{
+  return ctx->have_clock && ctx->n_iq > 0 && integral_sample_step(step, ctx->iq_freq);
+}
+// does a sample read grad_disu_upts (an id 1-4)?  The last RK stage of a step that is sampled then has to leave the corrected gradient
+// of its input state in memory
+bool integral_monitor_reads_gradient(const hfx_ctx *ctx);
+// one sample of e on the compute stream; nothing for a context without a monitor or a block without a cubature
+int sample_integrals(hfx_eles *e, double time, int step);
+// what every step loop asks before its first launch, beside probes_check_capacity
+int integrals_check_capacity(hfx_eles *const *eles, int neb, int n_steps);
+// One RK stage call by call -- CalcResidual, AdvanceSolution, the shock filter where registered (hfx.hip) -- and the flux-point
+// solution of the new state, which the fused stage that follows reads: what a loop whose stages keep the gradient on chip runs as the
+// last stage of a step the monitor samples with a gradient quantity
+int stage_call_by_call(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int rk);
 // the `forcing == 1` branch at the first RK stage of a step (src/solver.cpp:96-109): eles::evaluate_body_force of every block that
 // has a body force registered (forcing.hip) -- three launches per such block and, without `comm`, nothing else: no copy, no
 // synchronisation.  With `comm` (the partitioned loops) the two integrals are summed over its ranks between the first and the

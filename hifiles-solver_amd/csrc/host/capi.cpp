@@ -501,8 +501,72 @@ extern "C" int hfxh_case_set_integral_quantities(hfxh_case *c, int n, const char
   if (!c || n < 0 || (n > 0 && !names)) { g_err = "hfxh_case_set_integral_quantities: bad argument"; return 1; }
   std::vector<std::string> v;
   for (int i = 0; i < n; i++) v.push_back(names[i] ? names[i] : "");
-  if (c->S.run_input.set_integral_quantities(v, g_err)) return 1;
-  return rebuild_volume_cubature(c);
+  input &in = c->S.run_input;
+  const std::vector<std::string> old = in.integral_quantities;
+  if (in.set_integral_quantities(v, g_err)) return 1;
+  if (rebuild_volume_cubature(c)) return 1;
+  if (RegisterIntegralMonitor(&c->S))
+  {
+    // a refusal (a gradient quantity on an inviscid case with a history) leaves the case as it was
+    const std::string why = c->S.err;
+    std::string ignore;
+    in.set_integral_quantities(old, ignore);
+    (void)rebuild_volume_cubature(c);
+    (void)RegisterIntegralMonitor(&c->S);
+    c->S.err.clear();
+    g_err = why;
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int hfxh_case_set_monitor_res_freq(hfxh_case *c, int monitor_res_freq, int capacity)
+{
+  if (!c) { g_err = "hfxh_case_set_monitor_res_freq: NULL case"; return 1; }
+  input &in = c->S.run_input;
+  const int old_freq = in.monitor_res_freq, old_capacity = in.integral_capacity;
+  if (in.set_monitor_res_freq(monitor_res_freq, capacity, g_err)) return 1;
+  if (RegisterIntegralMonitor(&c->S))
+  {
+    const std::string why = c->S.err;
+    in.monitor_res_freq = old_freq;
+    in.integral_capacity = old_capacity;
+    (void)RegisterIntegralMonitor(&c->S);
+    c->S.err.clear();
+    g_err = why;
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int hfxh_case_get_monitor_res_freq(hfxh_case *c, int *monitor_res_freq, int *capacity)
+{
+  if (!c) { g_err = "hfxh_case_get_monitor_res_freq: NULL case"; return 1; }
+  if (monitor_res_freq) *monitor_res_freq = c->S.run_input.monitor_res_freq;
+  if (capacity) *capacity = c->S.run_input.integral_capacity;
+  return 0;
+}
+
+extern "C" int hfxh_case_sample_integral_quantities(hfxh_case *c)
+{
+  if (!c) { g_err = "hfxh_case_sample_integral_quantities: NULL case"; return 1; }
+  if (!c->S.run_input.integral_monitor_on()) { g_err = "hfxh_case_sample_integral_quantities: the case has no integral monitor (integral quantities and a capacity)"; return 1; }
+  if (SampleIntegralQuantities(&c->S, true)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_integral_count(hfxh_case *c, int *n_samples)
+{
+  if (!c || !n_samples) { g_err = "hfxh_case_integral_count: NULL argument"; return 1; }
+  if (IntegralCount(&c->S, n_samples)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_read_integral_history(hfxh_case *c, int max_samples, double *times, int *steps, double *values, int *n_samples)
+{
+  if (!c || !n_samples) { g_err = "hfxh_case_read_integral_history: NULL argument"; return 1; }
+  if (ReadIntegralHistory(&c->S, max_samples, times, steps, values, n_samples)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
 }
 
 extern "C" int hfxh_case_compute_error(hfxh_case *c, double *error)

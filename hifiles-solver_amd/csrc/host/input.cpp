@@ -162,6 +162,15 @@ int input::set_integral_quantities(const std::vector<std::string> &names, std::s
   return 0;
 }
 
+int input::set_monitor_res_freq(int freq, int capacity, std::string &err)
+{
+  if (freq < 0) { err = "monitor_res_freq must not be negative"; return 1; }
+  if (capacity < 0) { err = "the integral history holds at least 0 samples"; return 1; }
+  monitor_res_freq = freq == 0 ? 1000 : freq; /* src/input.cpp:534-535 */
+  integral_capacity = capacity;
+  return 0;
+}
+
 int input::integral_quantity_code(int i) const
 {
   return (int)(std::find(INTEGRAL_NAMES, INTEGRAL_NAMES + 5, integral_quantities[i]) - INTEGRAL_NAMES);

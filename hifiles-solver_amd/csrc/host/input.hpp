@@ -73,6 +73,13 @@ struct input
   int n_integral_quantities = 0;
   int set_integral_quantities(const std::vector<std::string> &names, std::string &err);
   int integral_quantity_code(int i) const; // the quantity id of hfx_eles_CalcIntegralQuantities
+  // the frequency in steps of the history rows, default 100, 0 means 1000 (src/input.cpp:101,534-535).  integral_capacity: the samples
+  // the device history of the integral monitor holds; 0: the quantities are not sampled in the loops (the caller asks for them with
+  // CalcIntegralQuantities, as before).  A negative frequency or capacity is refused and leaves both as they were
+  int monitor_res_freq = 100, integral_capacity = 0;
+  int set_monitor_res_freq(int freq, int capacity, std::string &err);
+  bool integral_monitor_on() const { return n_integral_quantities > 0 && integral_capacity > 0; }
+  bool integral_sample_step(int i_steps) const { return i_steps == 1 || i_steps % monitor_res_freq == 0; } /* src/HiFiLES.cpp:247 */
   // ---- mass-flux body force of periodic channels (`body_forcing`, src/input.cpp:312).  forcing_area and forcing_mdot0 are keys of
   // this mirror: the inflow area and the target mass flux, which the reference hard-codes to 9.162 both (src/eles.cpp:5393-5395);
   // forcing_history: evaluations whose massflux.dat columns the device keeps

@@ -557,6 +557,106 @@ int CalcIntegralQuantities(solution *S, double *integral_quantities)
   return 0;
 }
 
+// run_input's integral quantities, monitor_res_freq and history size -> the context (every block's history starts empty); no
+// monitor while the case has no quantities or no capacity
+int RegisterIntegralMonitor(solution *S)
+{
+  if (!S->ctx) return 0; // (MoveToDevice registers it)
+  const input &in = S->run_input;
+  int ids[8] = {};
+  const int n = in.integral_monitor_on() ? in.n_integral_quantities : 0;
+  for (int m = 0; m < n; m++) ids[m] = in.integral_quantity_code(m);
+  if (hfx_ctx_set_integral_monitor(S->ctx, n, ids, in.monitor_res_freq, in.integral_capacity)) { S->err = hfx_last_error(); return 1; }
+  return 0;
+}
+
+// one sample of every class at the solution's time and step; !always: only under the reference's condition (src/HiFiLES.cpp:247)
+int SampleIntegralQuantities(solution *S, bool always)
+{
+  const input &in = S->run_input;
+  if (!in.integral_monitor_on() || (!always && !in.integral_sample_step(S->i_steps))) return 0;
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    if (hfx_eles_sample_integral_quantities(E->device(), S->time, S->i_steps)) { S->err = hfx_last_error(); return 1; }
+  }
+  return 0;
+}
+
+int IntegralCount(solution *S, int *n_samples)
+{
+  *n_samples = 0;
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    // (every class takes every sample: the first one's count is the case's)
+    if (hfx_eles_integral_count(E->device(), n_samples)) { S->err = hfx_last_error(); return 1; }
+    return 0;
+  }
+  return 0;
+}
+
+// what a call of n_steps steps asks before its first launch: do the histories hold the samples it will take?
+static int integral_history_has_room(solution *S, int n_steps)
+{
+  const input &in = S->run_input;
+  if (!in.integral_monitor_on() || !S->ctx) return 0;
+  int n_new = 0, have = 0;
+  if (hfx_integral_monitor_samples(S->i_steps, n_steps, in.monitor_res_freq, &n_new)) { S->err = hfx_last_error(); return 1; }
+  if (IntegralCount(S, &have)) return 1;
+  if (have + n_new > in.integral_capacity)
+  {
+    S->err = "integral monitor: " + std::to_string(n_steps) + " steps from step " + std::to_string(S->i_steps) + " take " +
+             std::to_string(n_new) + " samples (monitor_res_freq " + std::to_string(in.monitor_res_freq) + "), the history of " +
+             std::to_string(in.integral_capacity) + " holds " + std::to_string(have) + " already; read it or take fewer steps per call";
+    return 1;
+  }
+  return 0;
+}
+
+// the rows as HistoryOutput prints them (src/output.cpp:2390-2402): the values summed over the classes and the ranks
+// (src/output.cpp:2023-2050), raw; the time x time_ref on a viscous case
+int ReadIntegralHistory(solution *S, int max_samples, double *times, int *steps, double *values, int *n_samples)
+{
+  const input &in = S->run_input;
+  const int nq = in.n_integral_quantities;
+  if (!in.integral_monitor_on()) { S->err = "ReadIntegralHistory: the case has no integral monitor (integral quantities and a capacity)"; return 1; }
+  int n = 0;
+  if (IntegralCount(S, &n)) return 1;
+  if (n > max_samples)
+  {
+    S->err = "ReadIntegralHistory: " + std::to_string(n) + " samples are stored, the caller's arrays hold " + std::to_string(max_samples);
+    return 1;
+  }
+  std::vector<double> sum((size_t)nq * std::max(n, 1), 0.0), part(sum.size()), t(std::max(n, 1));
+  std::vector<int> st(std::max(n, 1));
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    int got = 0;
+    if (hfx_eles_read_integral_history(E->device(), n, t.data(), st.data(), part.data(), &got)) { S->err = hfx_last_error(); return 1; }
+    if (got != n) { S->err = "ReadIntegralHistory: the classes' histories differ in length"; return 1; }
+    for (size_t i = 0; i < (size_t)nq * n; i++) sum[i] += part[i];
+    for (int s = 0; s < n; s++)
+    {
+      times[s] = t[s];
+      steps[s] = st[s];
+    }
+  }
+  for (int off = 0; off < nq * n; off += 64) // (hfx_comm_allreduce takes 64 values at a time)
+    if (sum_over_ranks(S, sum.data() + off, std::min(64, nq * n - off), "ReadIntegralHistory")) return 1;
+  for (size_t i = 0; i < (size_t)nq * n; i++) values[i] = sum[i];
+  if (in.viscous)
+    for (int s = 0; s < n; s++) times[s] *= in.time_ref;
+  *n_samples = n;
+  return 0;
+}
+
 int RegisterForceReference(solution *S)
 {
   if (!S->ctx) return 0; // (MoveToDevice registers it)
@@ -610,6 +710,7 @@ int MoveToDevice(solution *S, int device)
   if (S->run_input.dt_type != 0 && hfx_ctx_set_CFL(S->ctx, S->run_input.CFL)) { S->err = hfx_last_error(); return 1; }
   if (hfx_ctx_set_option(S->ctx, "deferred", S->deferred ? 1 : 0)) { S->err = hfx_last_error(); return 1; }
   if (RegisterProbeFields(S)) return 1; // (before the element blocks, which register their probes)
+  if (RegisterIntegralMonitor(S)) return 1;
   if (S->run_input.test_case != 0 && RegisterExactSolution(S)) return 1;
   if (S->run_input.calc_force != 0 && RegisterForceReference(S)) return 1;
   for (int i = 0; i < S->n_ele_types; i++)
@@ -801,8 +902,9 @@ void SampleProbes(solution *FlowSol, bool always)
     if (FlowSol->mesh_eles(j)) FlowSol->mesh_eles(j)->sample_probes(FlowSol->time, FlowSol->i_steps);
 }
 
-// src/HiFiLES.cpp:223,241-245 behind `time += dt`: the step counter, the spin-up time at the first step, the time averages
-static void count_step_and_average(solution *FlowSol)
+// src/HiFiLES.cpp:223,241-266 behind `time += dt`: the step counter, the spin-up time at the first step, the time averages, the
+// probes, the integral quantities of a history row (whose refusal, a full history for one, ends the loop)
+static int count_step_and_average(solution *FlowSol)
 {
   FlowSol->i_steps++;
   if (FlowSol->i_steps == 1) FlowSol->run_input.spinup_time = FlowSol->time;
@@ -810,12 +912,14 @@ static void count_step_and_average(solution *FlowSol)
     for (int j = 0; j < FlowSol->n_ele_types; j++)
       if (FlowSol->mesh_eles(j)) FlowSol->mesh_eles(j)->CalcTimeAverageQuantities(FlowSol->time);
   SampleProbes(FlowSol, false); /* src/HiFiLES.cpp:289-297 */
+  return SampleIntegralQuantities(FlowSol, false); /* src/HiFiLES.cpp:247-266 */
 }
 
 int RunSteps(solution *FlowSol, int n_steps)
 {
   const int RKSteps = FlowSol->run_input.n_rk_stages();
   if (forcing_has_transport(FlowSol, "RunSteps")) return 1;
+  if (integral_history_has_room(FlowSol, n_steps)) return 1;
   for (int i_steps = 0; i_steps < n_steps; i_steps++)
   {
     if (calc_time_step(FlowSol)) return 1; /* src/HiFiLES.cpp:198 */
@@ -831,7 +935,7 @@ int RunSteps(solution *FlowSol, int n_steps)
     FlowSol->time += FlowSol->run_input.dt;
     FlowSol->run_input.time = FlowSol->time;
     if (advance_ramp(FlowSol)) return 1;
-    count_step_and_average(FlowSol);
+    if (count_step_and_average(FlowSol)) return 1;
   }
   // (deferred execution: the last stage's record is still pending here, on purpose -- what the caller asks for next decides how
   // it runs: the state alone -> the fused stage; the gradient arrays, as the reference's CopyGPUCPU does before its
@@ -967,6 +1071,7 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
     return 0;
   }
   if (forcing_has_transport(FlowSol, "RunStepsPartitionedFused")) return 1;
+  if (integral_history_has_room(FlowSol, n_steps)) return 1;
   const int RKSteps = in.n_rk_stages();
   const bool ex = !fm.empty() && FlowSol->exchange;
   auto phase = [&](int ph, int stage, int first) {
@@ -1008,7 +1113,7 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
     FlowSol->time += in.dt;
     in.time = FlowSol->time;
     if (advance_ramp(FlowSol)) return 1;
-    count_step_and_average(FlowSol);
+    if (count_step_and_average(FlowSol)) return 1;
     if (E->failed()) { FlowSol->err = E->last_error(); return 1; }
   }
   // the exchange started after the last stage belongs to a stage that is not run: complete it so that

@@ -88,6 +88,13 @@ int RegisterExactSolution(solution *S);
 int ComputeError(solution *FlowSol, double *error);
 // output::CalcIntegralQuantities (src/output.cpp:2017-2038): run_input's integral quantities over the classes and the ranks
 int CalcIntegralQuantities(solution *FlowSol, double *integral_quantities);
+// the integral monitor (hfx_ctx_set_integral_monitor): run_input's quantities, monitor_res_freq and history size -> the context;
+// one sample of every class at the solution's clock (always, or under the reference's condition i_steps == 1 || i_steps %
+// monitor_res_freq == 0, src/HiFiLES.cpp:247); the stored samples; the rows of history.plt over classes and ranks
+int RegisterIntegralMonitor(solution *FlowSol);
+int SampleIntegralQuantities(solution *FlowSol, bool always);
+int IntegralCount(solution *FlowSol, int *n_samples);
+int ReadIntegralHistory(solution *FlowSol, int max_samples, double *times, int *steps, double *values, int *n_samples);
 // run_input's reference state -> the context (hfx_ctx_set_force_reference): rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic, area_ref
 int RegisterForceReference(solution *S);
 // output::CalcForces (src/output.cpp:1915-2014) without the file: eles::compute_wall_forces of every element class, summed, then

@@ -15,6 +15,7 @@
 // 4.6 kB run.
 #pragma once
 #include "hfx_internal.hpp"
+#include "integral_point.hpp"
 #include "face_kernels.hpp" // FacePairArgs (no kernel of that header is instantiated here)
 
 namespace hfx
@@ -547,8 +548,7 @@ __global__ __launch_bounds__(64) void dt_local_kernel(int n_upts, long n_eles, c
 // ---- eles::CalcIntegralQuantities (src/eles.cpp:5485-5627) -----------------------------------
 // pointwise diagnostics at the volume cubature points (state and gradient already interpolated
 // there), weighted and reduced to one partial per workgroup per quantity (fixed tree; the host
-// adds the partials in block order)
-constexpr int IQ_MAX = 8;
+// adds the partials in block order).  The formulas themselves: integral_point.hpp
 template <int ND>
 __global__ __launch_bounds__(PT_BLOCK) void integral_quantities_kernel(int n_cub, long n_eles, const double *__restrict__ Uc,
                                                                        const double *__restrict__ Gc,
@@ -572,54 +572,12 @@ __global__ __launch_bounds__(PT_BLOCK) void integral_quantities_kernel(int n_cub
     const double irho = 1. / u[0];
     double dv[ND][ND]; // dv[i][j] = d u_i / d x_j
 #pragma unroll
-    for (int i = 0; i < ND; i++)
-#pragma unroll
-      for (int j = 0; j < ND; j++) dv[i][j] = irho * (g[(i + 1) + NF * j] - u[i + 1] * irho * g[0 + NF * j]);
-    double tke = 0.0;
-#pragma unroll
-    for (int n = 1; n < ND + 1; n++) tke += 0.5 * u[n] * u[n];
+    for (int j = 0; j < ND; j++) iq_velocity_gradient<ND>(u, irho, g + NF * j, j, dv);
+    const double tke = iq_tke<ND>(u);
     const double w = wgt[p % n_cub] * vdj[p];
     for (int m = 0; m < nq; m++)
     {
-      double diagnostic = 0.0;
-      const int id = ids[m];
-      if (id == 0)
-        diagnostic = irho * tke;
-      else if (id == 1)
-      {
-        const double wz = dv[1][0] - dv[0][1];
-        diagnostic = wz * wz;
-        if (ND == 3)
-        {
-          const double wx = dv[ND - 1][1] - dv[1][ND - 1], wy = dv[0][ND - 1] - dv[ND - 1][0];
-          diagnostic += wx * wx + wy * wy;
-        }
-        diagnostic *= 0.5 / irho;
-      }
-      else if (id == 2)
-      {
-        const double pressure = (gamma - 1.0) * (u[ND + 1] - irho * tke);
-        double dil = dv[0][0] + dv[1][1];
-        if (ND == 3) dil = dil + dv[ND - 1][ND - 1];
-        diagnostic = pressure * dil;
-      }
-      else
-      {
-        double S[ND][ND];
-#pragma unroll
-        for (int a = 0; a < ND; a++)
-#pragma unroll
-          for (int b = 0; b < ND; b++) S[a][b] = (a == b) ? dv[a][a] : (dv[a][b] + dv[b][a]) / 2.0;
-        double diag = (S[0][0] + S[1][1]) / 3.0;
-        if (ND == 3) diag += S[ND - 1][ND - 1] / 3.0;
-        if (id == 4)
-#pragma unroll
-          for (int a = 0; a < ND; a++) S[a][a] -= diag;
-#pragma unroll
-        for (int a = 0; a < ND; a++)
-#pragma unroll
-          for (int b = 0; b < ND; b++) diagnostic += S[a][b] * S[a][b];
-      }
+      const double diagnostic = iq_diagnostic<ND>(ids[m], u, irho, tke, dv, gamma);
       acc[m] += diagnostic * w;
     }
   }

@@ -198,6 +198,32 @@ def read_probes_of(eles_handle, n_fields):
     return times[:got.value].copy(), steps[:got.value].copy(), values[:, :, :got.value].copy(order="F")
 
 
+INTEGRAL_NAMES = ["kineticenergy", "enstropy", "pressuredilatation", "straincolonproduct", "devstraincolonproduct"]
+
+
+def integral_count_of(eles_handle):
+    n = C.c_int(0)
+    check(lib().hfx_eles_integral_count(eles_handle, C.byref(n)))
+    return n.value
+
+
+def read_integral_history_of(eles_handle, n_quantities):
+    ns = integral_count_of(eles_handle)
+    times, steps = np.zeros(max(1, ns)), np.zeros(max(1, ns), dtype=np.int32)
+    values = np.zeros((max(1, n_quantities), max(1, ns)), order="F")
+    got = C.c_int(0)
+    check(lib().hfx_eles_read_integral_history(eles_handle, C.c_int(ns), times.ctypes.data_as(dp), steps.ctypes.data_as(ip),
+                                               values.ctypes.data_as(dp), C.byref(got)))
+    return times[:got.value].copy(), steps[:got.value].copy(), values[:n_quantities, :got.value].copy(order="F")
+
+
+def integral_monitor_samples(i_steps, n_steps, monitor_res_freq):
+    """how many of the steps i_steps + 1 .. i_steps + n_steps the integral monitor samples (no device needed)"""
+    n = C.c_int(0)
+    check(lib().hfx_integral_monitor_samples(C.c_int(i_steps), C.c_int(n_steps), C.c_int(monitor_res_freq), C.byref(n)))
+    return n.value
+
+
 class Context:
     def __init__(self, device=0):
         self.h = C.c_void_p()
@@ -246,6 +272,14 @@ class Context:
         a = (C.c_int * max(1, len(codes)))(*codes)
         check(lib().hfx_ctx_set_probes(self.h, C.c_int(len(codes)), a, C.c_int(probe_freq), C.c_int(capacity)))
         self.n_probe_fields = len(codes)
+
+    def set_integral_monitor(self, quantities, monitor_res_freq=100, capacity=1):
+        """quantities: ids 0-4 or the reference's names (kineticenergy, enstropy, pressuredilatation, straincolonproduct,
+        devstraincolonproduct), in the order of the input file; [] drops the monitor"""
+        ids = [INTEGRAL_NAMES.index(q.lower()) if isinstance(q, str) else int(q) for q in quantities]
+        a = (C.c_int * max(1, len(ids)))(*ids)
+        check(lib().hfx_ctx_set_integral_monitor(self.h, C.c_int(len(ids)), a, C.c_int(monitor_res_freq), C.c_int(capacity)))
+        self.n_integral_quantities = len(ids)
 
     def set_exact_solution(self, test_case, u_wall=0.0, T_wall=0.0, p_bound=0.0, R_ref=0.0, T_ref=0.0):
         """test_case 1: isentropic vortex; 5: Couette flow, which takes the five parameters (hfx_exact)"""
@@ -505,6 +539,28 @@ class Eles:
         out = np.zeros(len(ids))
         check(lib().hfx_eles_CalcIntegralQuantities(self.h, C.c_int(len(ids)), ids.ctypes.data_as(ip), out.ctypes.data_as(dp)))
         return out
+
+    def sample_integral_quantities(self, time, step):
+        """one sample of the context's integral monitor into the block's device history (no synchronisation)"""
+        self._call("hfx_eles_sample_integral_quantities", C.c_double(time), C.c_int(step))
+
+    def integral_count(self):
+        return integral_count_of(self.h)
+
+    def read_integral_history(self):
+        """(times (n_samples), steps (n_samples), values (n_quantities, n_samples)); empties the history"""
+        return read_integral_history_of(self.h, getattr(self.ctx, "n_integral_quantities", 0))
+
+    def integral_launch(self):
+        """(workgroups, elements per pass) of the next sample"""
+        g, n = C.c_int(0), C.c_int(0)
+        check(lib().hfx_eles_integral_launch(self.h, C.byref(g), C.byref(n)))
+        return g.value, n.value
+
+    def time_integral_quantities(self, reps=20):
+        v = C.c_double(0)
+        check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))
+        return v.value
 
     def set_error_points(self, pos_volume_cubpts):
         """pos_volume_cubpts (n_cubpts, n_eles, n_dims): the positions of the cubature points of set_volume_cubpts"""

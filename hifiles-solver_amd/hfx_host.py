@@ -501,6 +501,35 @@ class Case:
         check(lib().hfxh_case_set_integral_quantities(self.h, C.c_int(len(names)), a))
         self.n_integral_quantities = len(names)
 
+    def set_monitor_res_freq(self, monitor_res_freq=100, capacity=0):
+        """run_input.monitor_res_freq (0 means 1000) and the samples the integral monitor's device history holds (0: no monitor)"""
+        check(lib().hfxh_case_set_monitor_res_freq(self.h, C.c_int(monitor_res_freq), C.c_int(capacity)))
+
+    def monitor_res_freq(self):
+        """(monitor_res_freq, capacity)"""
+        f, n = C.c_int(0), C.c_int(0)
+        check(lib().hfxh_case_get_monitor_res_freq(self.h, C.byref(f), C.byref(n)))
+        return f.value, n.value
+
+    def sample_integral_quantities(self):
+        check(lib().hfxh_case_sample_integral_quantities(self.h))
+
+    def integral_count(self):
+        n = C.c_int(0)
+        check(lib().hfxh_case_integral_count(self.h, C.byref(n)))
+        return n.value
+
+    def read_integral_history(self):
+        """(times, steps, values (n_integral_quantities, n_samples)): the rows of history.plt over blocks and ranks; empties the
+        histories"""
+        ns, nq = self.integral_count(), getattr(self, "n_integral_quantities", 0)
+        times, steps = np.zeros(max(1, ns)), np.zeros(max(1, ns), dtype=np.int32)
+        values = np.zeros((max(1, nq), max(1, ns)), order="F")
+        got = C.c_int(0)
+        check(lib().hfxh_case_read_integral_history(self.h, C.c_int(ns), times.ctypes.data_as(dp), steps.ctypes.data_as(ip),
+                                                    values.ctypes.data_as(dp), C.byref(got)))
+        return times[:got.value].copy(), steps[:got.value].copy(), values[:nq, :got.value].copy(order="F")
+
     def compute_error(self):
         """output::compute_error at the mirror's clock: (2, n_fields), over blocks and ranks, after the square root (norm 2)"""
         out = np.zeros((2, self.n_fields), dtype=np.float64, order="F")

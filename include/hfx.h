@@ -320,6 +320,48 @@ int hfx_eles_set_volume_cubpts(hfx_eles *e, int n_cubpts, const double *opp_volu
  * per-method / fused-mode-2 stage).  The caller adds over blocks and ranks (src/output.cpp:2017-2050). */
 int hfx_eles_CalcIntegralQuantities(hfx_eles *e, int n_quantities, const int *quantity_ids, double *integral_quantities);
 
+/* ---- the integral monitor: the Diagnostics[...] columns of history.plt sampled on the device (src/HiFiLES.cpp:247-266) ----
+ * The reference fills them at step 1 and every run_input.monitor_res_freq steps (output::CalcIntegralQuantities,
+ * src/output.cpp:2017; eles::CalcIntegralQuantities, src/eles.cpp:5485-5627).  A sample pairs disu_upts(0) as it stands with
+ * grad_disu_upts as it stands: behind a time step that is the new state and the corrected gradient of the last RK stage's INPUT
+ * state, exactly what the reference integrates.  The monitor forms no gradient of its own.  Values are per block; adding over
+ * blocks and ranks is the caller's (src/output.cpp:2023-2050). */
+#define HFX_MAX_INTEGRAL_QUANTITIES 8
+/* The quantities of the context: quantity_ids[n_quantities] as for hfx_eles_CalcIntegralQuantities (0-4, src/eles.cpp:5540-5620;
+ * anything else is refused with the reference's words, src/eles.cpp:5618), monitor_res_freq >= 1 (steps, src/input.cpp:101) and
+ * the number of samples the device history of every block holds (>= 1).  n_quantities = 0 drops the monitor and empties every
+ * block's history; changing the quantities empties the histories.  A quantity that reads the gradient (ids 1-4) is refused on an
+ * inviscid context: the reference has no grad_disu_upts there.  Parameters (hfx_ctx_set_params) come first. */
+int hfx_ctx_set_integral_monitor(hfx_ctx *ctx, int n_quantities, const int *quantity_ids, int monitor_res_freq, int capacity);
+/* ONE sample of the block (which needs hfx_eles_set_volume_cubpts) into the next free slot of its device history: one fused
+ * launch and one single-workgroup launch that adds the workgroups' partials in workgroup order; no array of the size of
+ * n_cubpts x n_eles, no synchronisation with the host, which notes `time` and `step` for the slot.  With an id 1-4 selected a
+ * pending deferred stage runs so that it leaves the gradient (as for hfx_eles_compute_wall_forces), and a gradient the last
+ * fused stage did not materialise is refused with the words of hfx_eles_download.  With the kinetic energy alone the gradient is
+ * never read: the sample works after any fused stage and on inviscid contexts.  A full history is refused, nothing is
+ * overwritten.  Two samples of one state are equal bit for bit, in any slot (no atomics, a fixed summation order for a given grid).
+ * Once the clock is the library's (hfx_ctx_set_clock) every step loop does this itself, behind the time averages and the probes,
+ * for every block with a cubature after each step with i_steps == 1 || i_steps % monitor_res_freq == 0.  Such a loop first counts
+ * the samples it will take and refuses the whole call, before its first launch, when a history cannot hold them.  With an id 1-4
+ * selected, a loop whose stages keep the gradient on chip (fused 3 on a variant-3 plan, fused 4) runs the last RK stage of every
+ * step it samples call by call -- CalcResidual, AdvanceSolution, the shock filter -- so that grad_disu_upts holds what the
+ * reference's does; the partitioned loops refuse that combination before their first launch (fused mode 2 samples everything).
+ * A loop without a monitor, or with the kinetic energy alone, launches exactly the stages it launched before. */
+int hfx_eles_sample_integral_quantities(hfx_eles *e, double time, int step);
+/* the number of stored samples (no copy, no synchronisation) */
+int hfx_eles_integral_count(hfx_eles *e, int *n_samples);
+/* Synchronises, copies the history -- values (n_quantities, n_samples) with the quantity index fastest, times and steps
+ * (n_samples) -- and empties it.  max_samples: what the caller's arrays hold; fewer than stored is refused, nothing is lost. */
+int hfx_eles_read_integral_history(hfx_eles *e, int max_samples, double *times, int *steps, double *values, int *n_samples);
+/* what the next sample launches: workgroups, and the elements a workgroup takes per pass of its loop */
+int hfx_eles_integral_launch(hfx_eles *e, int *n_groups, int *eles_per_pass);
+/* how many of the steps i_steps + 1 .. i_steps + n_steps the reference samples (step 1 and the multiples of monitor_res_freq):
+ * what the loops' capacity check counts.  Pure host arithmetic */
+int hfx_integral_monitor_samples(int i_steps, int n_steps, int monitor_res_freq, int *n_samples);
+/* device milliseconds of the launches of one sample, averaged over `reps` samples into a scratch slot (the history is untouched;
+ * grad_disu_upts is read as it stands, whichever stage wrote it) */
+int hfx_time_integral_quantities(hfx_eles *e, int reps, double *ms);
+
 /* ---- exact-solution error norms (run_input.test_case, error_norm_type; output::compute_error, src/output.cpp:2052) ------
  * The monitor a verification run ends with (src/HiFiLES.cpp:324-325): the state -- and for Couette flow the gradient --
  * interpolated to the volume cubature points, minus the exact solution there, integrated in the L1 or L2 sense. */

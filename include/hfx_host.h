@@ -306,6 +306,25 @@ int hfxh_case_compute_error(hfxh_case *c, double *error);
 /* output::CalcIntegralQuantities (src/output.cpp:2017-2038): integral_quantities[n_integral_quantities] over blocks and ranks,
  * on top of hfx_eles_CalcIntegralQuantities (which reads the corrected gradient of the last per-method stage) */
 int hfxh_case_CalcIntegralQuantities(hfxh_case *c, double *integral_quantities);
+/* ---- the integral monitor: the Diagnostics[...] columns of history.plt (src/HiFiLES.cpp:247-266) --------------------------
+ * run_input.monitor_res_freq (default 100; 0 means 1000, src/input.cpp:101,534-535) and the samples the device history holds.
+ * With integral quantities set and capacity >= 1 the case has a monitor (hfx_ctx_set_integral_monitor; registered here on a
+ * device case, by hfxh_case_to_device otherwise, and again by hfxh_case_set_integral_quantities): hfxh_case_run and
+ * hfxh_case_run_partitioned then take one sample after every step with i_steps == 1 || i_steps % monitor_res_freq == 0,
+ * behind the time averages and the probes, and refuse a call whose samples the history cannot hold before its first launch.
+ * capacity 0 (the default): no monitor.  A sample pairs the state after the step with grad_disu_upts of the last RK stage, as
+ * the reference does; with deferred execution the pending last stage then runs call by call.  A refusal -- a negative value,
+ * or a quantity that reads the gradient on an inviscid device case -- leaves the case as it was. */
+int hfxh_case_set_monitor_res_freq(hfxh_case *c, int monitor_res_freq, int capacity);
+int hfxh_case_get_monitor_res_freq(hfxh_case *c, int *monitor_res_freq, int *capacity);
+/* one sample now, at the case's time and step (hfx_eles_sample_integral_quantities of every block) */
+int hfxh_case_sample_integral_quantities(hfxh_case *c);
+int hfxh_case_integral_count(hfxh_case *c, int *n_samples);
+/* The rows as HistoryOutput prints them (src/output.cpp:2390-2402), and the histories emptied: values (n_integral_quantities,
+ * n_samples) summed over the case's blocks, then over the ranks (src/output.cpp:2023-2050) -- the library's communicator, else
+ * the hook of hfxh_case_set_reduce_sum -- and left raw; times x time_ref on a viscous case; steps the iteration column.  Fewer
+ * than stored (max_samples) is refused and nothing is lost.  Adapter for src/HiFiLES.cpp:255-258: INTEGRATION.md */
+int hfxh_case_read_integral_history(hfxh_case *c, int max_samples, double *times, int *steps, double *values, int *n_samples);
 /* the inflow faces the reference's rule selects, elements ascending: (element, local face) */
 int hfxh_case_get_inflow_faces(hfxh_case *c, const int **ele, const int **inter, int *n_faces);
 /* hfx_eles_body_force_state / hfx_eles_body_force_history of the case's block */
