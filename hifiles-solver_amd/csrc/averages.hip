@@ -156,6 +156,9 @@ int end_of_step(hfx_eles *const *eles, int neb)
   if (integral_monitor_samples(ctx, ctx->i_steps)) /* src/HiFiLES.cpp:247-266 */
     for (int i = 0; i < neb; i++)
       if (sample_integrals(eles[i], ctx->time, ctx->i_steps)) return 1;
+  if (history_monitor_samples(ctx, ctx->i_steps))
+    for (int i = 0; i < neb; i++)
+      if (sample_history(eles[i], ctx->time, ctx->i_steps)) return 1;
   return 0;
 }
 

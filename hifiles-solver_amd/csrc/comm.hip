@@ -438,13 +438,18 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
 static const char *const MONITOR_PARTITIONED =
     "partitioned step loop: the integral monitor has a quantity that reads grad_disu_upts (ids 1-4), and the stages of this loop keep the "
     "gradient on chip; run it with fused mode 2 (hfx_ctx_set_fused_mode), or monitor the kinetic energy (id 0) alone";
-static bool monitor_gradient_on_chip(hfx_eles *const *eles, int neb)
+// the same for the history monitor's viscous wall forces (history.hip)
+static const char *const HISTORY_PARTITIONED =
+    "partitioned step loop: the history monitor samples the viscous wall forces, which read grad_disu_upts, and the stages of this loop "
+    "keep the gradient on chip; run it with fused mode 2 (hfx_ctx_set_fused_mode), or monitor the residuals alone (with_forces 0)";
+// nullptr: no monitor of this loop reads the gradient; else the refusal of a loop that keeps it on chip
+static const char *monitor_gradient_on_chip(hfx_eles *const *eles, int neb)
 {
   const hfx_ctx *ctx = eles[0]->ctx;
-  if (!ctx->have_clock || !ctx->params.viscous || !integral_monitor_reads_gradient(ctx)) return false;
+  if (!ctx->have_clock || !monitor_reads_gradient(eles, neb)) return nullptr;
   for (int i = 0; i < neb; i++)
-    if (eles[i]->n_vol_cubpts > 0) return true;
-  return false;
+    if (history_monitor_reads_gradient(eles[i])) return HISTORY_PARTITIONED;
+  return MONITOR_PARTITIONED;
 }
 
 // the loop of hfx_run_steps_partitioned / hfx_time_partitioned.  n_stages_total < 0: n_steps whole time steps
@@ -686,12 +691,13 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
   HFX_IMMEDIATE(e->ctx, 0);
   if (probes_check_capacity(&e, 1, n_steps)) return 1;
   if (integrals_check_capacity(&e, 1, n_steps)) return 1;
-  if (monitor_gradient_on_chip(&e, 1))
+  if (history_check_capacity(&e, 1, n_steps)) return 1;
+  if (const char *refusal = monitor_gradient_on_chip(&e, 1))
   {
     // (a plan of variant 2 writes grad_disu_upts in every stage: everything is sampled)
     SplitPlan pl;
     if (ensure_fused_tables(e, int_faces, n_int, true) || split_stage_plan(e, int_faces, n_int, e->ctx->fused_mode, &pl)) return 1;
-    HFX_CHECK(pl.variant != 3, "%s", MONITOR_PARTITIONED);
+    HFX_CHECK(pl.variant != 3, "%s", refusal);
   }
   return run_partitioned(e, int_faces, n_int, mpi_faces, n_mpi, comm, n_steps, -1, nullptr);
 }
@@ -708,7 +714,9 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   const int nst = n_rk_stages(ctx->params);
   if (probes_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
   if (integrals_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
-  HFX_CHECK(!monitor_gradient_on_chip(eles, n_ele_blocks), "%s", MONITOR_PARTITIONED); // (the general stage keeps the gradient on chip)
+  if (history_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
+  if (const char *refusal = monitor_gradient_on_chip(eles, n_ele_blocks)) // (the general stage keeps the gradient on chip)
+    HFX_CHECK(false, "%s", refusal);
   for (int i = 0; i < n_ele_blocks; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
   // (as run_partitioned: the solution a partitioned fused stage has posted for this state is not posted again)

@@ -1207,16 +1207,16 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
   if (n_steps <= 0) return 0;
   const int nst = n_rk_stages(e->ctx->params);
   if (hfx_eles_extrapolate_solution(e)) return 1;
-  // the integral monitor pairs the state behind a step with grad_disu_upts of the last stage's input state (integrals.hip): on a
-  // plan that keeps the gradient on chip the last stage of a step it samples with an id 1-4 runs call by call
+  // a monitor that reads grad_disu_upts pairs the state behind a step with the gradient of the last stage's input state (integrals.hip,
+  // history.hip): on a plan that keeps the gradient on chip the last stage of a step such a monitor samples runs call by call
   hfx_ctx *ctx = e->ctx;
-  const bool monitor_gradient = pl.variant == 3 && ctx->params.viscous && integral_monitor_reads_gradient(ctx) && e->n_vol_cubpts > 0;
+  const bool monitor_gradient = pl.variant == 3 && monitor_reads_gradient(&e, 1);
   bool by_calls = false;
   for (int s = 0; s < n_steps; s++)
   {
     if (calc_time_step(e, nullptr)) return 1; /* src/HiFiLES.cpp:198 */
     if (begin_of_step(&e, 1, nullptr)) return 1; /* src/solver.cpp:96-109 */
-    by_calls = monitor_gradient && integral_monitor_samples(ctx, (long)ctx->i_steps + 1);
+    by_calls = monitor_gradient && monitor_samples(ctx, (long)ctx->i_steps + 1);
     for (int rk = 0; rk < nst; rk++)
     {
       // (the SVV closure replaces the state, whose flux-point values the previous stage's update kernel has already written)

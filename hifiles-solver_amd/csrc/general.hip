@@ -1253,17 +1253,16 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
   // disu_fpts of the current state (the caller may have changed disu_upts since the last call)
   for (int i = 0; i < neb; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
-  // as split_run_steps: the last stage of a step the integral monitor samples with an id 1-4 runs call by call and leaves
-  // grad_disu_upts of its input state
+  // as split_run_steps: the last stage of a step a monitor samples that reads grad_disu_upts runs call by call and leaves the
+  // gradient of its input state
   hfx_ctx *ctx = eles[0]->ctx;
-  bool monitor_gradient = false, by_calls = false;
-  for (int i = 0; i < neb; i++) monitor_gradient = monitor_gradient || eles[i]->n_vol_cubpts > 0;
-  monitor_gradient = monitor_gradient && ctx->params.viscous && integral_monitor_reads_gradient(ctx);
+  const bool monitor_gradient = monitor_reads_gradient(eles, neb);
+  bool by_calls = false;
   for (int s = 0; s < n_steps; s++)
   {
     if (calc_time_step_blocks(eles, neb)) return 1; /* src/HiFiLES.cpp:198 */
     if (begin_of_step(eles, neb, nullptr)) return 1; /* src/solver.cpp:96-109 */
-    by_calls = monitor_gradient && integral_monitor_samples(ctx, (long)ctx->i_steps + 1);
+    by_calls = monitor_gradient && monitor_samples(ctx, (long)ctx->i_steps + 1);
     for (int rk = 0; rk < nst; rk++)
     {
       if (rk == 0 && first_stage_closure_filter(eles, neb, true)) return 1;

@@ -258,6 +258,11 @@ struct hfx_ctx
   int n_iq = 0, iq_freq = 1, iq_capacity = 0;
   int iq_ids[8] = {};
   unsigned long iq_epoch = 0;
+  // the history monitor (hfx_ctx_set_history_monitor): run_input.res_norm_type, whether the rows carry the wall forces,
+  // run_input.monitor_res_freq and the rows a block's device history holds.  hist_epoch: as probe_epoch
+  bool hist_on = false, hist_forces = false;
+  int hist_norm = 2, hist_freq = 1, hist_capacity = 0;
+  unsigned long hist_epoch = 0;
   // the exact solution of the error monitor (hfx_ctx_set_exact_solution): run_input.test_case and what eval_couette_flow takes
   hfx_exact exact{};
   bool have_exact = false;
@@ -373,6 +378,18 @@ struct IntegralHistory
   std::vector<double> times;      // of the stored samples; their number is the number of stored samples
   std::vector<int> steps;
 };
+// The history rows of one block (history.hip): the residual of every field, then (the monitor with forces) the 2 n_dims + 2 values of
+// hfx_eles_compute_wall_forces
+struct HistoryRows
+{
+  // (n_res + n_force, capacity + 1): row s at [(n_res + n_force) * s]; the last slot is the scratch of hfx_time_history
+  DevBuf<double> rows;
+  DevBuf<double> partial;         // (n_groups, n_res) of the residual kernel of the sample that runs
+  int n_res = 0, n_force = 0, capacity = 0; // what `rows` was made for
+  unsigned long epoch = 0;        // ctx->hist_epoch it was made at
+  std::vector<double> times;      // of the stored rows; their number is the number of stored rows
+  std::vector<int> steps;
+};
 } // namespace hfx
 
 struct hfx_eles
@@ -396,6 +413,8 @@ struct hfx_eles
   hfx::DevBuf<int> iq_ids; // the quantity ids of the call that runs
   // the samples of the context's integral monitor (hfx_ctx_set_integral_monitor)
   hfx::IntegralHistory integrals;
+  // the rows of the context's history monitor (hfx_ctx_set_history_monitor)
+  hfx::HistoryRows history_rows;
   // exact-solution error norms (error_norm.hip): pos_volume_cubpts (n_vol_cubpts, n_eles, n_dims) of hfx_eles_set_error_points,
   // the cubature size it was registered for, and one partial per workgroup and quantity of the call that runs
   hfx::DevBuf<double> pos_volume_cubpts, err_partial;
@@ -531,7 +550,8 @@ void advance_ramp_counters(hfx_inters *const *faces, int nfb);
 // clock is the library's: time += dt, i_steps++, spinup_time at step 1, then the time averages of every block that has average
 // fields (averages.hip), then -- when i_steps % probe_freq == 0 -- one sample of every block that has probes (probes.hip), then -- when
 // i_steps == 1 || i_steps % monitor_res_freq == 0 -- one sample of the integral monitor for every block with a cubature
-// (integrals.hip).  Nothing for a context without a clock; no launch for a block without average fields, probes or a monitor
+// (integrals.hip), then -- under the same condition -- one row of the history monitor for every block (history.hip).  Nothing for a
+// context without a clock; no launch for a block without average fields, probes or a monitor
 int end_of_step(hfx_eles *const *eles, int neb);
 // (probes.hip) one sample of e's probes on the compute stream; nothing for a block or a context without probes
 int sample_probes(hfx_eles *e, double time, int step);
@@ -561,6 +581,29 @@ bool integral_monitor_reads_gradient(const hfx_ctx *ctx);
 int sample_integrals(hfx_eles *e, double time, int step);
 // what every step loop asks before its first launch, beside probes_check_capacity
 int integrals_check_capacity(hfx_eles *const *eles, int neb, int n_steps);
+// ---- the history monitor (history.hip) ----
+// will the step loops take a row behind the step that makes i_steps `step`?  The condition of the integral monitor, the reference's one
+inline bool history_monitor_samples(const hfx_ctx *ctx, long step)
+{
+  return ctx->have_clock && ctx->hist_on && integral_sample_step(step, ctx->hist_freq);
+}
+// does a row of e read grad_disu_upts: the monitor with forces, a viscous context, a block with wall faces
+bool history_monitor_reads_gradient(const hfx_eles *e);
+// one row of e on the compute stream; nothing for a context without the monitor
+int sample_history(hfx_eles *e, double time, int step);
+// what every step loop asks before its first launch, beside probes_check_capacity and integrals_check_capacity
+int history_check_capacity(hfx_eles *const *eles, int neb, int n_steps);
+// (wall_force.hip) the wall forces of a row: _prepare is everything that refuses hfx_eles_compute_wall_forces on a block with wall
+// faces and the arrays its launch needs; _launch the kernel alone, whose per-workgroup partials stay in wall_forces->partial
+int wall_force_partials_prepare(hfx_eles *e, const char *who);
+int wall_force_partials_launch(hfx_eles *e, int *n_groups);
+// ---- the one-stage rule of the step loops ----
+// does a monitor the loops sample read grad_disu_upts of one of these blocks: the integral monitor with an id 1-4 and a block with a
+// cubature, or the history monitor's viscous wall forces (history_monitor_reads_gradient)?  The last RK stage of a step that is
+// sampled then has to leave the corrected gradient of its input state in memory
+bool monitor_reads_gradient(hfx_eles *const *eles, int neb);
+// will the loops sample such a monitor behind the step that makes i_steps `step`?
+inline bool monitor_samples(const hfx_ctx *ctx, long step) { return integral_monitor_samples(ctx, step) || history_monitor_samples(ctx, step); }
 // One RK stage call by call -- CalcResidual, AdvanceSolution, the shock filter where registered (hfx.hip) -- and the flux-point
 // solution of the new state, which the fused stage that follows reads: what a loop whose stages keep the gradient on chip runs as the
 // last stage of a step the monitor samples with a gradient quantity

@@ -569,6 +569,70 @@ extern "C" int hfxh_case_read_integral_history(hfxh_case *c, int max_samples, do
   return 0;
 }
 
+// ---- the history monitor: residual and force columns of history.plt ---------------------------------------------------------
+extern "C" int hfxh_case_set_history(hfxh_case *c, int res_norm_type, int capacity)
+{
+  if (!c) { g_err = "hfxh_case_set_history: NULL case"; return 1; }
+  input &in = c->S.run_input;
+  const int old_norm = in.res_norm_type, old_capacity = in.history_capacity;
+  if (in.set_history(res_norm_type, capacity, g_err)) return 1;
+  if (RegisterHistoryMonitor(&c->S))
+  {
+    const std::string why = c->S.err;
+    in.res_norm_type = old_norm;
+    in.history_capacity = old_capacity;
+    (void)RegisterHistoryMonitor(&c->S);
+    c->S.err.clear();
+    g_err = why;
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int hfxh_case_get_history(hfxh_case *c, int *res_norm_type, int *capacity, int *n_cols)
+{
+  if (!c) { g_err = "hfxh_case_get_history: NULL case"; return 1; }
+  if (res_norm_type) *res_norm_type = c->S.run_input.res_norm_type;
+  if (capacity) *capacity = c->S.run_input.history_capacity;
+  if (n_cols) *n_cols = HistoryColumns(&c->S);
+  return 0;
+}
+
+extern "C" int hfxh_norm_residual(int res_norm_type, int n_fields, const double *sum, long n_upts, double *norm_residual)
+{
+  if (!sum || !norm_residual || n_fields < 0) { g_err = "hfxh_norm_residual: bad argument"; return 1; }
+  return NormResidual(res_norm_type, n_fields, sum, n_upts, norm_residual, g_err);
+}
+
+extern "C" int hfxh_case_CalcNormResidual(hfxh_case *c, double *norm_residual)
+{
+  if (!c || !norm_residual) { g_err = "hfxh_case_CalcNormResidual: NULL argument"; return 1; }
+  if (CalcNormResidual(&c->S, norm_residual)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_sample_history(hfxh_case *c)
+{
+  if (!c) { g_err = "hfxh_case_sample_history: NULL case"; return 1; }
+  if (!c->S.run_input.history_monitor_on()) { g_err = "hfxh_case_sample_history: the case has no history monitor (a capacity)"; return 1; }
+  if (SampleHistory(&c->S, true)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_history_count(hfxh_case *c, int *n_rows)
+{
+  if (!c || !n_rows) { g_err = "hfxh_case_history_count: NULL argument"; return 1; }
+  if (HistoryCount(&c->S, n_rows)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_read_history(hfxh_case *c, int max_rows, int *steps, double *rows, int *n_cols, int *n_rows)
+{
+  if (!c || !n_rows || (max_rows > 0 && (!steps || !rows))) { g_err = "hfxh_case_read_history: NULL argument"; return 1; }
+  if (ReadHistory(&c->S, max_rows, steps, rows, n_cols, n_rows)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
 extern "C" int hfxh_case_compute_error(hfxh_case *c, double *error)
 {
   if (!c || !error) { g_err = "hfxh_case_compute_error: NULL argument"; return 1; }

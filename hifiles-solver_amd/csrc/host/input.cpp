@@ -171,6 +171,15 @@ int input::set_monitor_res_freq(int freq, int capacity, std::string &err)
   return 0;
 }
 
+int input::set_history(int norm_type, int capacity, std::string &err)
+{
+  if (norm_type < 0 || norm_type > 2) { err = "norm_type not recognized"; return 1; } /* src/output.cpp:2241 */
+  if (capacity < 0) { err = "the history holds at least 0 rows"; return 1; }
+  res_norm_type = norm_type;
+  history_capacity = capacity;
+  return 0;
+}
+
 int input::integral_quantity_code(int i) const
 {
   return (int)(std::find(INTEGRAL_NAMES, INTEGRAL_NAMES + 5, integral_quantities[i]) - INTEGRAL_NAMES);

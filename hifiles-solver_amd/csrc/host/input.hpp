@@ -80,6 +80,12 @@ struct input
   int set_monitor_res_freq(int freq, int capacity, std::string &err);
   bool integral_monitor_on() const { return n_integral_quantities > 0 && integral_capacity > 0; }
   bool integral_sample_step(int i_steps) const { return i_steps == 1 || i_steps % monitor_res_freq == 0; } /* src/HiFiLES.cpp:247 */
+  // ---- the residual and force columns of a history row: res_norm_type 0 infinity, 1 L1, 2 L2 norm (default 2, src/input.cpp:108);
+  // anything else is refused with the reference's words (src/output.cpp:2241).  history_capacity: the rows the device history of the
+  // history monitor holds; 0: no rows are taken in the loops.  The forces of a row follow calc_force
+  int res_norm_type = 2, history_capacity = 0;
+  int set_history(int norm_type, int capacity, std::string &err);
+  bool history_monitor_on() const { return history_capacity > 0; }
   // ---- mass-flux body force of periodic channels (`body_forcing`, src/input.cpp:312).  forcing_area and forcing_mdot0 are keys of
   // this mirror: the inflow area and the target mass flux, which the reference hard-codes to 9.162 both (src/eles.cpp:5393-5395);
   // forcing_history: evaluations whose massflux.dat columns the device keeps

@@ -566,8 +566,20 @@ int RegisterIntegralMonitor(solution *S)
   int ids[8] = {};
   const int n = in.integral_monitor_on() ? in.n_integral_quantities : 0;
   for (int m = 0; m < n; m++) ids[m] = in.integral_quantity_code(m);
-  if (hfx_ctx_set_integral_monitor(S->ctx, n, ids, in.monitor_res_freq, in.integral_capacity)) { S->err = hfx_last_error(); return 1; }
-  return 0;
+  // The two monitors of a context share monitor_res_freq.  While it stays what the history monitor was registered with, that monitor
+  // and its stored rows are left alone; when it changes, the history monitor steps aside (its rows go: a new frequency empties both
+  // histories) and follows.  If the context refuses this registration the history monitor comes back as it was registered
+  const int old_freq = S->history_freq;
+  const bool move = old_freq != in.monitor_res_freq;
+  if (move && hfx_ctx_set_history_monitor(S->ctx, in.res_norm_type, 0, in.monitor_res_freq, 0)) { S->err = hfx_last_error(); return 1; }
+  if (hfx_ctx_set_integral_monitor(S->ctx, n, ids, in.monitor_res_freq, in.integral_capacity))
+  {
+    S->err = hfx_last_error();
+    if (move && old_freq > 0)
+      (void)hfx_ctx_set_history_monitor(S->ctx, in.res_norm_type, in.calc_force != 0, old_freq, in.history_capacity);
+    return 1;
+  }
+  return move ? RegisterHistoryMonitor(S) : 0;
 }
 
 // one sample of every class at the solution's time and step; !always: only under the reference's condition (src/HiFiLES.cpp:247)
@@ -657,6 +669,202 @@ int ReadIntegralHistory(solution *S, int max_samples, double *times, int *steps,
   return 0;
 }
 
+// run_input's res_norm_type, calc_force, monitor_res_freq and history size -> the context (every block's history starts empty); no
+// monitor while the case has no capacity.  Behind RegisterForceReference on a case with calc_force
+int RegisterHistoryMonitor(solution *S)
+{
+  if (!S->ctx) return 0; // (MoveToDevice registers it)
+  const input &in = S->run_input;
+  if (hfx_ctx_set_history_monitor(S->ctx, in.res_norm_type, in.calc_force != 0, in.monitor_res_freq, in.history_capacity)) { S->err = hfx_last_error(); return 1; }
+  S->history_freq = in.history_monitor_on() ? in.monitor_res_freq : 0; // (0: none registered, any frequency is free)
+  return 0;
+}
+
+// one row of every class at the solution's time and step; !always: only under the reference's condition (src/HiFiLES.cpp:247)
+int SampleHistory(solution *S, bool always)
+{
+  const input &in = S->run_input;
+  if (!in.history_monitor_on() || (!always && !in.integral_sample_step(S->i_steps))) return 0;
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    if (hfx_eles_sample_history(E->device(), S->time, S->i_steps)) { S->err = hfx_last_error(); return 1; }
+  }
+  return 0;
+}
+
+int HistoryCount(solution *S, int *n_rows)
+{
+  *n_rows = 0;
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    // (every class takes every row: the first one's count is the case's)
+    if (hfx_eles_history_count(E->device(), n_rows)) { S->err = hfx_last_error(); return 1; }
+    return 0;
+  }
+  return 0;
+}
+
+static int history_has_room(solution *S, int n_steps)
+{
+  const input &in = S->run_input;
+  if (!in.history_monitor_on() || !S->ctx) return 0;
+  int n_new = 0, have = 0;
+  if (hfx_integral_monitor_samples(S->i_steps, n_steps, in.monitor_res_freq, &n_new)) { S->err = hfx_last_error(); return 1; }
+  if (HistoryCount(S, &have)) return 1;
+  if (have + n_new > in.history_capacity)
+  {
+    S->err = "history monitor: " + std::to_string(n_steps) + " steps from step " + std::to_string(S->i_steps) + " take " +
+             std::to_string(n_new) + " rows (monitor_res_freq " + std::to_string(in.monitor_res_freq) + "), the history of " +
+             std::to_string(in.history_capacity) + " holds " + std::to_string(have) + " already; read it or take fewer steps per call";
+    return 1;
+  }
+  return 0;
+}
+
+int NormResidual(int res_norm_type, int n_fields, const double *sum, long n_upts, double *norm_residual, std::string &err)
+{
+  for (int i = 0; i < n_fields; i++)
+  {
+    if (res_norm_type == 0) norm_residual[i] = sum[i];
+    else if (res_norm_type == 1) norm_residual[i] = sum[i] / n_upts;
+    else if (res_norm_type == 2) norm_residual[i] = std::sqrt(sum[i]) / n_upts; // (the reference divides the root by n_upts)
+    else { err = "norm_type not recognized"; return 1; }
+    if (std::isnan(norm_residual[i])) { err = "NaN residual encountered. Exiting"; return 1; }
+  }
+  return 0;
+}
+
+// the max (norm type 0) or the sum over the ranks of n values, and with the sums n_upts: src/output.cpp:2217-2230
+static int residual_over_ranks(solution *S, int norm_type, double *v, int n, const char *who)
+{
+  if (norm_type != 0) return sum_over_ranks(S, v, n, who);
+  if (S->comm)
+  {
+    if (hfx_comm_allreduce(S->comm, v, n, 1)) { S->err = hfx_last_error(); return 1; }
+  }
+  else if (S->reduce_min)
+    for (int i = 0; i < n; i++) v[i] = -S->reduce_min(S->reduce_user, -v[i]); // (a NaN is whatever the hook makes of it)
+  else if (S->nproc > 1)
+  {
+    S->err = std::string(who) + ": more than one rank needs a MAX reduction over the ranks (SetComm, or SetReduceMin of the negated values)";
+    return 1;
+  }
+  return 0;
+}
+
+int CalcNormResidual(solution *S, double *norm_residual)
+{
+  const input &in = S->run_input;
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  const int n_fields = S->n_dims + 2;
+  double v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // sum[n_fields], n_upts
+  for (int i = 0; i < S->n_ele_types; i++)
+  {
+    eles *E = S->mesh_eles(i);
+    if (!E || E->get_n_eles() == 0) continue;
+    v[n_fields] += (double)E->get_n_eles() * E->n_upts_per_ele;
+    for (int j = 0; j < n_fields; j++)
+    {
+      double r = E->compute_res_upts(in.res_norm_type, j);
+      // (the per-call maximum drops a NaN, as the reference's max does; the rows of the history monitor keep it, and so does this:
+      // the L1 sum of the field is NaN exactly when a residual is)
+      if (in.res_norm_type == 0 && !E->failed())
+      {
+        const double probe = E->compute_res_upts(1, j);
+        if (probe != probe) r = probe;
+      }
+      if (E->failed()) { S->err = E->last_error(); return 1; }
+      v[j] = in.res_norm_type == 0 ? ((r > v[j] || r != r) ? r : v[j]) : v[j] + r;
+    }
+  }
+  if (residual_over_ranks(S, in.res_norm_type, v, n_fields, "CalcNormResidual")) return 1;
+  if (in.res_norm_type != 0 && sum_over_ranks(S, v + n_fields, 1, "CalcNormResidual")) return 1;
+  return NormResidual(in.res_norm_type, n_fields, v, (long)v[n_fields], norm_residual, S->err);
+}
+
+int HistoryColumns(const solution *S)
+{
+  const input &in = S->run_input;
+  return S->n_dims + 2 + (in.calc_force ? S->n_dims + 2 : 0) + (in.integral_monitor_on() ? in.n_integral_quantities : 0) + 1;
+}
+
+int ReadHistory(solution *S, int max_rows, int *steps, double *rows, int *n_cols, int *n_rows)
+{
+  const input &in = S->run_input;
+  if (!in.history_monitor_on()) { S->err = "ReadHistory: the case has no history monitor (a capacity)"; return 1; }
+  const int nd = S->n_dims, nf = nd + 2, nq = in.calc_force ? 2 * nd + 2 : 0;
+  const int niq = in.integral_monitor_on() ? in.n_integral_quantities : 0;
+  const int cols = HistoryColumns(S);
+  int n = 0;
+  if (HistoryCount(S, &n)) return 1;
+  if (n > max_rows)
+  {
+    S->err = "ReadHistory: " + std::to_string(n) + " rows are stored, the caller's arrays hold " + std::to_string(max_rows);
+    return 1;
+  }
+  if (niq)
+  {
+    int ni = 0;
+    if (IntegralCount(S, &ni)) return 1;
+    if (ni != n) { S->err = "ReadHistory: the integral monitor holds " + std::to_string(ni) + " samples, the history " + std::to_string(n) + " rows"; return 1; }
+  }
+  const size_t m = (size_t)std::max(n, 1);
+  std::vector<double> res((size_t)nf * m, 0.0), frc((size_t)std::max(nq, 1) * m, 0.0), pr(res.size()), pf(frc.size()), t(m);
+  std::vector<int> st(m);
+  double n_upts = 0.0;
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    int got = 0;
+    if (hfx_eles_read_history(E->device(), n, t.data(), st.data(), pr.data(), pf.data(), &got)) { S->err = hfx_last_error(); return 1; }
+    if (got != n) { S->err = "ReadHistory: the classes' histories differ in length"; return 1; }
+    n_upts += (double)E->get_n_eles() * E->n_upts_per_ele;
+    for (size_t i = 0; i < (size_t)nf * n; i++)
+      res[i] = in.res_norm_type == 0 ? ((pr[i] > res[i] || pr[i] != pr[i]) ? pr[i] : res[i]) : res[i] + pr[i];
+    for (size_t i = 0; i < (size_t)nq * n; i++) frc[i] += pf[i];
+    for (int s = 0; s < n; s++) steps[s] = st[s];
+  }
+  for (int off = 0; off < nf * n; off += 64) // (hfx_comm_allreduce takes 64 values at a time)
+    if (residual_over_ranks(S, in.res_norm_type, res.data() + off, std::min(64, nf * n - off), "ReadHistory")) return 1;
+  for (int off = 0; off < nq * n; off += 64)
+    if (sum_over_ranks(S, frc.data() + off, std::min(64, nq * n - off), "ReadHistory")) return 1;
+  if (in.res_norm_type != 0 && sum_over_ranks(S, &n_upts, 1, "ReadHistory")) return 1;
+  // the Diagnostics[...] columns and the times (x time_ref on a viscous case) are the integral monitor's where it is registered
+  std::vector<double> diag((size_t)std::max(niq, 1) * m), ti(m);
+  if (niq)
+  {
+    std::vector<int> si(m);
+    int got = 0;
+    if (ReadIntegralHistory(S, n, ti.data(), si.data(), diag.data(), &got)) return 1;
+  }
+  for (int s = 0; s < n; s++)
+  {
+    double *row = rows + (size_t)cols * s, norm[8];
+    if (NormResidual(in.res_norm_type, nf, res.data() + (size_t)nf * s, (long)n_upts, norm, S->err)) return 1;
+    int c = 0;
+    for (int f = 0; f < nf; f++) row[c++] = std::log10(norm[f]);
+    if (nq)
+    {
+      const double *q = frc.data() + (size_t)nq * s;
+      for (int d = 0; d < nd; d++) row[c++] = q[d] + q[nd + d]; /* src/output.cpp:2385-2390 */
+      row[c++] = q[2 * nd];
+      row[c++] = q[2 * nd + 1];
+    }
+    for (int q = 0; q < niq; q++) row[c++] = diag[(size_t)niq * s + q];
+    row[c++] = in.viscous ? t[s] * in.time_ref : t[s];
+  }
+  if (n_cols) *n_cols = cols;
+  *n_rows = n;
+  return 0;
+}
+
 int RegisterForceReference(solution *S)
 {
   if (!S->ctx) return 0; // (MoveToDevice registers it)
@@ -710,9 +918,9 @@ int MoveToDevice(solution *S, int device)
   if (S->run_input.dt_type != 0 && hfx_ctx_set_CFL(S->ctx, S->run_input.CFL)) { S->err = hfx_last_error(); return 1; }
   if (hfx_ctx_set_option(S->ctx, "deferred", S->deferred ? 1 : 0)) { S->err = hfx_last_error(); return 1; }
   if (RegisterProbeFields(S)) return 1; // (before the element blocks, which register their probes)
-  if (RegisterIntegralMonitor(S)) return 1;
+  if (S->run_input.calc_force != 0 && RegisterForceReference(S)) return 1; // (before the history monitor, whose rows carry the forces)
+  if (RegisterIntegralMonitor(S)) return 1; // (and the history monitor behind it)
   if (S->run_input.test_case != 0 && RegisterExactSolution(S)) return 1;
-  if (S->run_input.calc_force != 0 && RegisterForceReference(S)) return 1;
   for (int i = 0; i < S->n_ele_types; i++)
     if (S->mesh_eles(i) && S->mesh_eles(i)->get_n_eles() != 0)
       if (S->mesh_eles(i)->mv_all_cpu_gpu(S->ctx)) { S->err = S->mesh_eles(i)->last_error(); return 1; }
@@ -912,7 +1120,8 @@ static int count_step_and_average(solution *FlowSol)
     for (int j = 0; j < FlowSol->n_ele_types; j++)
       if (FlowSol->mesh_eles(j)) FlowSol->mesh_eles(j)->CalcTimeAverageQuantities(FlowSol->time);
   SampleProbes(FlowSol, false); /* src/HiFiLES.cpp:289-297 */
-  return SampleIntegralQuantities(FlowSol, false); /* src/HiFiLES.cpp:247-266 */
+  if (SampleIntegralQuantities(FlowSol, false)) return 1; /* src/HiFiLES.cpp:247-266 */
+  return SampleHistory(FlowSol, false);
 }
 
 int RunSteps(solution *FlowSol, int n_steps)
@@ -920,6 +1129,7 @@ int RunSteps(solution *FlowSol, int n_steps)
   const int RKSteps = FlowSol->run_input.n_rk_stages();
   if (forcing_has_transport(FlowSol, "RunSteps")) return 1;
   if (integral_history_has_room(FlowSol, n_steps)) return 1;
+  if (history_has_room(FlowSol, n_steps)) return 1;
   for (int i_steps = 0; i_steps < n_steps; i_steps++)
   {
     if (calc_time_step(FlowSol)) return 1; /* src/HiFiLES.cpp:198 */
@@ -1072,6 +1282,7 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
   }
   if (forcing_has_transport(FlowSol, "RunStepsPartitionedFused")) return 1;
   if (integral_history_has_room(FlowSol, n_steps)) return 1;
+  if (history_has_room(FlowSol, n_steps)) return 1;
   const int RKSteps = in.n_rk_stages();
   const bool ex = !fm.empty() && FlowSol->exchange;
   auto phase = [&](int ph, int stage, int first) {

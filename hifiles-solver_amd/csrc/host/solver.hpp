@@ -41,6 +41,7 @@ struct solution
   // deferred execution (include/hfx.h): the method calls of CalcResidual + AdvanceSolution below are recorded by libhfx and
   // a whole stage runs as one fused stage -- the call sequence itself is the reference's, unchanged.  On by default.
   bool deferred = true;
+  int history_freq = 0; // the monitor_res_freq the context's history monitor is registered with; 0: none (RegisterHistoryMonitor)
   std::string err;
   ~solution();
 };
@@ -95,6 +96,21 @@ int RegisterIntegralMonitor(solution *FlowSol);
 int SampleIntegralQuantities(solution *FlowSol, bool always);
 int IntegralCount(solution *FlowSol, int *n_samples);
 int ReadIntegralHistory(solution *FlowSol, int max_samples, double *times, int *steps, double *values, int *n_samples);
+// the history monitor (hfx_ctx_set_history_monitor): run_input's res_norm_type, calc_force, monitor_res_freq and history size -> the
+// context; one row of every class at the solution's clock (always, or under the reference's condition); the stored rows
+int RegisterHistoryMonitor(solution *FlowSol);
+int SampleHistory(solution *FlowSol, bool always);
+int HistoryCount(solution *FlowSol, int *n_rows);
+// the finish of output::CalcNormResidual (src/output.cpp:2236-2246) on what the classes and ranks gave: sum[n_fields] -- the max for
+// norm type 0, the sums for 1 and 2 -- and n_upts -> sum, sum / n_upts or sqrt(sum) / n_upts; a NaN norm is the reference's error
+int NormResidual(int res_norm_type, int n_fields, const double *sum, long n_upts, double *norm_residual, std::string &err);
+// output::CalcNormResidual (src/output.cpp:2166-2248) now, through eles::compute_res_upts of every class: norm_residual[n_fields]
+int CalcNormResidual(solution *FlowSol, double *norm_residual);
+// the rows as HistoryOutput writes them (src/output.cpp:2375-2402) without the computing time, the histories (the integral monitor's
+// too) emptied: per row log10(norm_residual) per field, with calc_force inv + vis force per dimension, CL, CD, the integral
+// quantities where that monitor is registered, the time (x time_ref on a viscous case)
+int HistoryColumns(const solution *FlowSol);
+int ReadHistory(solution *FlowSol, int max_rows, int *steps, double *rows, int *n_cols, int *n_rows);
 // run_input's reference state -> the context (hfx_ctx_set_force_reference): rho_c_ic, u_c_ic, v_c_ic, w_c_ic, p_c_ic, area_ref
 int RegisterForceReference(solution *S);
 // output::CalcForces (src/output.cpp:1915-2014) without the file: eles::compute_wall_forces of every element class, summed, then

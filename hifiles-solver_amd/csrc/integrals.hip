@@ -361,6 +361,10 @@ int hfx_ctx_set_integral_monitor(hfx_ctx *ctx, int n_quantities, const int *quan
     HFX_CHECK(monitor_res_freq >= 1, "hfx_ctx_set_integral_monitor: monitor_res_freq %d (at least 1)", monitor_res_freq);
     HFX_CHECK(capacity >= 1, "hfx_ctx_set_integral_monitor: a history of %d samples (at least 1)", capacity);
     HFX_CHECK(ctx->have_params, "hfx_ctx_set_integral_monitor: parameters not set");
+    // (the reference has one monitor_res_freq for the whole row: history.hip)
+    HFX_CHECK(!ctx->hist_on || ctx->hist_freq == monitor_res_freq,
+              "hfx_ctx_set_integral_monitor: monitor_res_freq %d, and the history monitor is registered with %d: a row of history.plt has one",
+              monitor_res_freq, ctx->hist_freq);
     // the reference has no grad_disu_upts on an inviscid run (src/eles.cpp:5517 reads it unconditionally)
     HFX_CHECK(!grad || ctx->params.viscous, "hfx_ctx_set_integral_monitor: a quantity that reads the gradient (ids 1-4) on an inviscid "
                                             "context, which has no grad_disu_upts; kinetic energy (id 0) alone works there");

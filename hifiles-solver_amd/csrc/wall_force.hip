@@ -330,6 +330,25 @@ static int prepare_launch(hfx_eles *e, const WallLaunch &L, bool grad, const cha
   return 0;
 }
 
+// for the rows of the history monitor (history.hip), on a block with wall faces: the call's checks and arrays ...
+int wall_force_partials_prepare(hfx_eles *e, const char *who)
+{
+  if (check_call(e, who)) return 1;
+  WallLaunch L;
+  if (plan_launch(e, L)) return 1;
+  return prepare_launch(e, L, e->ctx->params.viscous != 0, who);
+}
+
+// ... and its kernel: the partials of n_groups workgroups are left in wall_forces->partial
+int wall_force_partials_launch(hfx_eles *e, int *n_groups)
+{
+  WallLaunch L;
+  if (plan_launch(e, L)) return 1;
+  if (launch_wall_forces(e, L, e->ctx->params.viscous != 0)) return 1;
+  *n_groups = L.groups;
+  return 0;
+}
+
 } // namespace hfx
 
 using namespace hfx;

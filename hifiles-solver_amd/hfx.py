@@ -217,6 +217,24 @@ def read_integral_history_of(eles_handle, n_quantities):
     return times[:got.value].copy(), steps[:got.value].copy(), values[:n_quantities, :got.value].copy(order="F")
 
 
+def history_count_of(eles_handle):
+    n = C.c_int(0)
+    check(lib().hfx_eles_history_count(eles_handle, C.byref(n)))
+    return n.value
+
+
+def read_history_of(eles_handle, n_fields, n_forces):
+    ns = history_count_of(eles_handle)
+    times, steps = np.zeros(max(1, ns)), np.zeros(max(1, ns), dtype=np.int32)
+    res = np.zeros((n_fields, max(1, ns)), order="F")
+    forces = np.zeros((n_forces, max(1, ns)), order="F")
+    got = C.c_int(0)
+    check(lib().hfx_eles_read_history(eles_handle, C.c_int(ns), times.ctypes.data_as(dp), steps.ctypes.data_as(ip),
+                                      res.ctypes.data_as(dp), forces.ctypes.data_as(dp), C.byref(got)))
+    n = got.value
+    return times[:n].copy(), steps[:n].copy(), res[:, :n].copy(order="F"), forces[:, :n].copy(order="F")
+
+
 def integral_monitor_samples(i_steps, n_steps, monitor_res_freq):
     """how many of the steps i_steps + 1 .. i_steps + n_steps the integral monitor samples (no device needed)"""
     n = C.c_int(0)
@@ -280,6 +298,11 @@ class Context:
         a = (C.c_int * max(1, len(ids)))(*ids)
         check(lib().hfx_ctx_set_integral_monitor(self.h, C.c_int(len(ids)), a, C.c_int(monitor_res_freq), C.c_int(capacity)))
         self.n_integral_quantities = len(ids)
+
+    def set_history_monitor(self, res_norm_type=2, with_forces=False, monitor_res_freq=100, capacity=1):
+        """the residual (and, with_forces, wall-force) columns of history.plt; capacity 0 drops the monitor"""
+        check(lib().hfx_ctx_set_history_monitor(self.h, C.c_int(res_norm_type), C.c_int(1 if with_forces else 0),
+                                                C.c_int(monitor_res_freq), C.c_int(capacity)))
 
     def set_exact_solution(self, test_case, u_wall=0.0, T_wall=0.0, p_bound=0.0, R_ref=0.0, T_ref=0.0):
         """test_case 1: isentropic vortex; 5: Couette flow, which takes the five parameters (hfx_exact)"""
@@ -560,6 +583,29 @@ class Eles:
     def time_integral_quantities(self, reps=20):
         v = C.c_double(0)
         check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))
+        return v.value
+
+    def sample_history(self, time, step):
+        """one row of the context's history monitor into the block's device history (no synchronisation)"""
+        self._call("hfx_eles_sample_history", C.c_double(time), C.c_int(step))
+
+    def history_count(self):
+        return history_count_of(self.h)
+
+    def read_history(self):
+        """(times (n_rows), steps (n_rows), residuals (n_fields, n_rows), forces (2 n_dims + 2, n_rows)): the block's raw values;
+        empties the history"""
+        return read_history_of(self.h, self.n_fields, 2 * self.n_dims + 2)
+
+    def history_launch(self):
+        """(workgroups, solution points per pass) of the residual kernel of the next sample"""
+        g, n = C.c_int(0), C.c_int(0)
+        check(lib().hfx_eles_history_launch(self.h, C.byref(g), C.byref(n)))
+        return g.value, n.value
+
+    def time_history(self, reps=20):
+        v = C.c_double(0)
+        check(lib().hfx_time_history(self.h, C.c_int(reps), C.byref(v)))
         return v.value
 
     def set_error_points(self, pos_volume_cubpts):

@@ -78,6 +78,16 @@ def check(rc):
         raise hfx.HfxError(lib().hfxh_last_error().decode())
 
 
+def norm_residual(res_norm_type, sums, n_upts):
+    """the finish of output::CalcNormResidual (no device needed): the max / sums over blocks and ranks -> norm_residual; raises the
+    reference's errors for an unknown norm type and a NaN norm"""
+    s = np.ascontiguousarray(np.ravel(sums).astype(np.float64))
+    out = np.zeros(max(1, len(s)))
+    check(lib().hfxh_norm_residual(C.c_int(res_norm_type), C.c_int(len(s)), s.ctypes.data_as(dp), C.c_long(int(n_upts)),
+                                   out.ctypes.data_as(dp)))
+    return out[:len(s)]
+
+
 def _locate(fn, handle, n_dims, positions):
     pos = np.asfortranarray(np.array(positions, dtype=np.float64).reshape((n_dims, -1), order="F"))
     n = pos.shape[1]
@@ -510,6 +520,39 @@ class Case:
         f, n = C.c_int(0), C.c_int(0)
         check(lib().hfxh_case_get_monitor_res_freq(self.h, C.byref(f), C.byref(n)))
         return f.value, n.value
+
+    def set_history(self, res_norm_type=2, capacity=0):
+        """run_input.res_norm_type (0 infinity, 1 L1, 2 L2) and the rows the history monitor's device history holds (0: no monitor)"""
+        check(lib().hfxh_case_set_history(self.h, C.c_int(res_norm_type), C.c_int(capacity)))
+
+    def history(self):
+        """(res_norm_type, capacity, columns of a row)"""
+        t, n, k = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().hfxh_case_get_history(self.h, C.byref(t), C.byref(n), C.byref(k)))
+        return t.value, n.value, k.value
+
+    def CalcNormResidual(self):
+        """output::CalcNormResidual now, over blocks and ranks: norm_residual (n_fields)"""
+        out = np.zeros(self.n_fields)
+        check(lib().hfxh_case_CalcNormResidual(self.h, out.ctypes.data_as(dp)))
+        return out
+
+    def sample_history(self):
+        check(lib().hfxh_case_sample_history(self.h))
+
+    def history_count(self):
+        n = C.c_int(0)
+        check(lib().hfxh_case_history_count(self.h, C.byref(n)))
+        return n.value
+
+    def read_history(self):
+        """(steps (n_rows), rows (n_cols, n_rows)): the rows of history.plt without the computing time; empties the histories"""
+        ns, nc = self.history_count(), self.history()[2]
+        steps, rows = np.zeros(max(1, ns), dtype=np.int32), np.zeros((nc, max(1, ns)), order="F")
+        got, cols = C.c_int(0), C.c_int(0)
+        check(lib().hfxh_case_read_history(self.h, C.c_int(ns), steps.ctypes.data_as(ip), rows.ctypes.data_as(dp), C.byref(cols),
+                                           C.byref(got)))
+        return steps[:got.value].copy(), rows[:, :got.value].copy(order="F")
 
     def sample_integral_quantities(self):
         check(lib().hfxh_case_sample_integral_quantities(self.h))

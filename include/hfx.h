@@ -362,6 +362,48 @@ int hfx_integral_monitor_samples(int i_steps, int n_steps, int monitor_res_freq,
  * grad_disu_upts is read as it stands, whichever stage wrote it) */
 int hfx_time_integral_quantities(hfx_eles *e, int reps, double *ms);
 
+/* ---- the history monitor: the residual and force columns of history.plt sampled on the device (src/HiFiLES.cpp:247-266) ----
+ * In front of the Diagnostics[...] columns a row holds log10 of the residual norm of every field (output::CalcNormResidual,
+ * src/output.cpp:2166-2248) and, with calc_force, the total force, CL and CD (output::CalcForces, src/output.cpp:1915-2014).  A row
+ * of a block holds the RAW values: per field the max (norm 0) or the sum (norms 1, 2) of eles::compute_res_upts over the block's
+ * solution points -- div_tconf_upts(0) / detjac_upts - src_upts -- and the 2 n_dims + 2 values of hfx_eles_compute_wall_forces.
+ * Adding (or taking the max) over blocks and ranks, the division by n_upts, the square root and the log10 are the caller's, as for
+ * the integral monitor.  Cp and Cf per wall point (cp_*.dat, monitor_cp_freq) are not part of a row: they stay with
+ * hfx_eles_compute_wall_forces.  Blocks of other than n_dims + 2 fields (RANS, advection-diffusion) are refused. */
+/* res_norm_type 0, 1 or 2 as run_input.res_norm_type (src/input.cpp:108; anything else is refused with the reference's words,
+ * src/output.cpp:2241); with_forces != 0: the rows carry the forces, which needs hfx_ctx_set_force_reference first;
+ * monitor_res_freq >= 1; capacity >= 1: the rows the device history of every block holds.  capacity 0 drops the monitor and empties
+ * the histories; any registration empties them.  The reference has ONE monitor_res_freq: when the integral monitor is registered
+ * too the two must agree, and the second registration is refused otherwise.  Parameters (hfx_ctx_set_params) come first. */
+int hfx_ctx_set_history_monitor(hfx_ctx *ctx, int res_norm_type, int with_forces, int monitor_res_freq, int capacity);
+/* ONE row of the block into the next free slot of its device history: one launch of the residual kernel for all fields, with forces
+ * and wall faces the kernel of hfx_eles_compute_wall_forces, and one single-workgroup launch that combines the workgroups' partials
+ * of both in workgroup order.  No synchronisation with the host, which notes `time` and `step` for the slot; no floating-point
+ * atomics: two samples of one state are equal bit for bit in any slot, and the force columns are bit for bit those of
+ * hfx_eles_compute_wall_forces on the same state, gradient and grid.  A block without wall faces has zeros in its force columns.
+ * Norm 0 keeps a NaN residual (the reference stops on one, src/output.cpp:2243).
+ * div_tconf_upts must be current: a pending deferred stage runs so that it stores it, and a stale one is refused with the words of
+ * hfx_eles_compute_res_upts.  With forces on a viscous context and a block with wall faces the pending stage also leaves the gradient,
+ * and a gradient the last fused stage kept on chip is refused, exactly as for hfx_eles_compute_wall_forces.  A full history is refused.
+ * Once the clock is the library's (hfx_ctx_set_clock) every step loop does this itself, behind the sample of the integral monitor
+ * and under its condition, i_steps == 1 || i_steps % monitor_res_freq == 0, for every block, after counting the rows it will take:
+ * a call whose rows would not fit is refused before its first launch.  Every loop stores div_tconf_upts at the last stage of every
+ * step, so residuals alone, or forces on an inviscid context, leave the loop's launches and its states as they were.  With viscous
+ * forces and a block with wall faces the rule of the integral monitor's ids 1-4 applies: a loop that keeps the gradient on chip
+ * runs the last RK stage of a sampled step call by call; the partitioned loops refuse that combination before their first launch
+ * (fused mode 2, or residuals alone). */
+int hfx_eles_sample_history(hfx_eles *e, double time, int step);
+/* the number of stored rows (no copy, no synchronisation) */
+int hfx_eles_history_count(hfx_eles *e, int *n_rows);
+/* Synchronises, copies the history -- residuals (n_fields, n_rows) and forces (2 n_dims + 2, n_rows: inviscid force, viscous force,
+ * CL, CD; not touched, and may be NULL, when the monitor has no forces) with the first index fastest, times and steps (n_rows) --
+ * and empties it.  max_rows: what the caller's arrays hold; fewer than stored is refused, nothing is lost. */
+int hfx_eles_read_history(hfx_eles *e, int max_rows, double *times, int *steps, double *residuals, double *forces, int *n_rows);
+/* what the next sample launches for the residual: workgroups, and the solution points a workgroup takes per pass of its loop */
+int hfx_eles_history_launch(hfx_eles *e, int *n_groups, int *points_per_pass);
+/* device milliseconds of the launches of one sample, averaged over `reps` samples into a scratch slot (the history is untouched) */
+int hfx_time_history(hfx_eles *e, int reps, double *ms);
+
 /* ---- exact-solution error norms (run_input.test_case, error_norm_type; output::compute_error, src/output.cpp:2052) ------
  * The monitor a verification run ends with (src/HiFiLES.cpp:324-325): the state -- and for Couette flow the gradient --
  * interpolated to the volume cubature points, minus the exact solution there, integrated in the L1 or L2 sense. */

@@ -325,6 +325,36 @@ int hfxh_case_integral_count(hfxh_case *c, int *n_samples);
  * the hook of hfxh_case_set_reduce_sum -- and left raw; times x time_ref on a viscous case; steps the iteration column.  Fewer
  * than stored (max_samples) is refused and nothing is lost.  Adapter for src/HiFiLES.cpp:255-258: INTEGRATION.md */
 int hfxh_case_read_integral_history(hfxh_case *c, int max_samples, double *times, int *steps, double *values, int *n_samples);
+/* ---- the history monitor: the residual and force columns, and with them the whole row of history.plt ---------------------------
+ * run_input.res_norm_type (0 infinity, 1 L1, 2 L2 norm; default 2, src/input.cpp:108; anything else is refused with "norm_type not
+ * recognized") and the rows the device history holds; capacity 0 (the default): no monitor.  The forces of a row follow the case's
+ * calc_force, the frequency is monitor_res_freq (hfxh_case_set_monitor_res_freq).  Registered (hfx_ctx_set_history_monitor) here on
+ * a device case, by hfxh_case_to_device otherwise.  hfxh_case_run and hfxh_case_run_partitioned then take one row after every step
+ * with i_steps == 1 || i_steps % monitor_res_freq == 0, behind the sample of the integral monitor, with deferred execution on and
+ * off, and refuse a call whose rows the history cannot hold before its first launch. */
+int hfxh_case_set_history(hfxh_case *c, int res_norm_type, int capacity);
+/* n_cols: n_fields + (calc_force: n_dims + 2) + (the integral monitor: n_integral_quantities) + 1.  Any pointer may be NULL */
+int hfxh_case_get_history(hfxh_case *c, int *res_norm_type, int *capacity, int *n_cols);
+/* The finish of output::CalcNormResidual (src/output.cpp:2236-2246), host arithmetic: sum[n_fields] -- the max (type 0) or the sums
+ * (types 1, 2) of eles::compute_res_upts over blocks and ranks -- and n_upts -> sum, sum / n_upts or sqrt(sum) / n_upts (the
+ * reference does divide the root by n_upts).  A NaN norm is refused with "NaN residual encountered. Exiting" */
+int hfxh_norm_residual(int res_norm_type, int n_fields, const double *sum, long n_upts, double *norm_residual);
+/* output::CalcNormResidual (src/output.cpp:2166-2248) now: norm_residual[n_fields] over the case's blocks and the ranks -- the
+ * library's communicator, else the hooks of hfxh_case_set_reduce_sum (types 1, 2) / hfxh_case_set_reduce_min (type 0, on the negated
+ * values).  The case must be on the device */
+int hfxh_case_CalcNormResidual(hfxh_case *c, double *norm_residual);
+/* one row now, at the case's time and step (hfx_eles_sample_history of every block) */
+int hfxh_case_sample_history(hfxh_case *c);
+int hfxh_case_history_count(hfxh_case *c, int *n_rows);
+/* The rows as HistoryOutput writes them (src/output.cpp:2375-2402), and the histories -- the integral monitor's too -- emptied:
+ * rows (n_cols, n_rows) with the column index fastest, steps the iteration column.  Per row log10(norm_residual) of every field;
+ * with calc_force inv + vis force per dimension, then CL, CD; the integral quantities where that monitor is registered; the time,
+ * x time_ref on a viscous case.  The computing-time column is left out.  A NaN norm is the reference's error.  Fewer than stored
+ * (max_rows) and a case without the monitor are refused before anything is read, and nothing is lost.
+ * An error behind that -- a failed reduction over the ranks, the NaN norm, which ends the reference's run -- comes after the blocks'
+ * histories have been read and emptied: those rows are gone.  Changing monitor_res_freq (hfxh_case_set_monitor_res_freq) registers
+ * both monitors anew and empties both histories; changing the integral quantities alone leaves the history monitor's rows. */
+int hfxh_case_read_history(hfxh_case *c, int max_rows, int *steps, double *rows, int *n_cols, int *n_rows);
 /* the inflow faces the reference's rule selects, elements ascending: (element, local face) */
 int hfxh_case_get_inflow_faces(hfxh_case *c, const int **ele, const int **inter, int *n_faces);
 /* hfx_eles_body_force_state / hfx_eles_body_force_history of the case's block */
