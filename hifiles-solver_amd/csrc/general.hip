@@ -1364,3 +1364,14 @@ void general_kernel_bytes(hfx_eles *const *eles, int neb, double *bytes)
 }
 
 } // namespace hfx
+
+extern "C" int hfx_general_plan(hfx_eles *e, int out[8])
+{
+  HFX_CHECK(e && out, "hfx_general_plan: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  HFX_CHECK(e->general && e->general->built, "hfx_general_plan: no general fused stage has prepared this block (run fused 4 first)");
+  const hfx::GeneralPlan pl = hfx::general_plan(e);
+  const int v[8] = {pl.size_class, pl.flux_waves, pl.flux_batched, pl.gather, pl.les, pl.update_waves, pl.fold, (int)pl.flux_lds};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+  return 0;
+}

@@ -580,6 +580,13 @@ class Eles:
         check(lib().hfx_eles_integral_launch(self.h, C.byref(g), C.byref(n)))
         return g.value, n.value
 
+    def general_plan(self):
+        """the launch forms of the general fused stage on this block (hfx_general_plan), valid after a fused-4 call: dict of
+        size_class, flux_waves, flux_batched, gather, les, update_waves, fold, flux_lds"""
+        out = (C.c_int * 8)()
+        check(lib().hfx_general_plan(self.h, out))
+        return dict(zip(("size_class", "flux_waves", "flux_batched", "gather", "les", "update_waves", "fold", "flux_lds"), list(out)))
+
     def time_integral_quantities(self, reps=20):
         v = C.c_double(0)
         check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))

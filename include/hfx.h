@@ -863,6 +863,13 @@ int hfx_flux_two_wave_face(hfx_eles *e, hfx_inters *const *faces, int n_face_blo
 int hfx_time_general_kernels(hfx_eles *const *eles, int n_ele_blocks, hfx_inters *const *faces, int n_face_blocks, int reps,
                              double ms[8], char names[256]);
 int hfx_general_kernel_bytes(hfx_eles *const *eles, int n_ele_blocks, double bytes[8]);
+/* The launch forms the general fused stage runs on this block with the context's current options (read-only; valid once a fused-4
+ * call has prepared the block, refused before): out[0] size class (index of the kernel instantiation with compile-time sizes:
+ * 0-2 tetrahedra P1-P3, 3-5 prisms P1-P3; -1: the size-generic kernels), out[1] waves of the flux kernel (3, 4, 8), out[2] 1: its
+ * staging requests all loads up front, 0: the looped staging, out[3] 1: it forms the interior LDG corrections itself (no
+ * face_delta_kernel), out[4] 1: its LES form, out[5] waves of the update kernel (4, 8), out[6] 1: the folded correction
+ * (opp_2 - opp_3 opp_1), out[7] bytes of the flux kernel's LDS image of a batch. */
+int hfx_general_plan(hfx_eles *e, int out[8]);
 
 #ifdef __cplusplus
 }

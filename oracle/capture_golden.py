@@ -159,6 +159,11 @@ CASES = [
     case("pri_p3_n2_deformed", n=2, amp=0.1, level=1, order=3, steps=1, tets="prisms",
          upts_type_pri_tri=0, upts_type_pri_1d=0, vcjh_scheme_pri_1d=1, eta_pri=0.0, upts_type_tri=0,
          vcjh_scheme_tri=1, c_tri=0.0),
+    # the orders on either side of those: P1 tetrahedra (4, 12) and prisms (6, 18) -- the smallest kernel instantiations of the
+    # general fused stage -- and P4 tetrahedra (35, 60), which run its size-generic kernels
+    case("tet_p1_n2_deformed", n=2, amp=0.1, level=1, order=1, steps=1, tets=True, **TET_KEYS),
+    case("pri_p1_n2_deformed", n=2, amp=0.1, level=1, order=1, steps=1, tets="prisms", **PRI_KEYS),
+    case("tet_p4_n2_deformed", n=2, amp=0.1, level=1, order=4, steps=1, tets=True, **TET_KEYS),
     # LES eddy-viscosity closures: WALE on a periodic box, Smagorinsky with wall damping between two walls
     case("hex_p2_les_wale", amp=0.15, level=2, order=2, steps=1, LES=1, SGS_model=1, C_s=0.325, filter_ratio=1.0),
     case("hex_p2_les_smag", amp=0.1, level=2, order=2, steps=1, LES=1, SGS_model=0, C_s=0.17, filter_ratio=1.5,

@@ -12,6 +12,12 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def test_general_plan_query_is_part_of_the_abi():
+    # the read-only query of the general fused stage's launch forms (tests/test_gpu_general_batches.py asserts what it returns)
+    assert "hfx_general_plan" in hfx.declared_symbols()
+    assert hasattr(hfx.lib(), "hfx_general_plan") and hasattr(hfx.Eles, "general_plan")
+
+
 def test_struct_layouts_match_oracle_binding():
     # hfx_params and orc_params are declared field-for-field alike (include/hfx.h, oracle/oracle.h)
     import oracle_py as O

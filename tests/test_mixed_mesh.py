@@ -197,10 +197,14 @@ def test_general_fused_stage_face_delta_kernel_vs_reference():
                                   "tet_p3_shock", "pri_p2_shock", "tet_p2_les_wale", "pri_p2_les_wale", "tet_p3_les_wsm", "tet_p3_les_sim",
                                   "tet_p3_les_svv", "tet_p2_overint", "pri_p2_overint", "tet_p2_transonic", "pri_p2_transonic",
                                   "tet_p2_roem_sutherland", "pri_p2_roem_sutherland", "tet_p2_rusanov_ldg", "pri_p2_rusanov_ldg",
-                                  "tet_p2_inviscid", "pri_p2_inviscid"])
+                                  "tet_p2_inviscid", "pri_p2_inviscid", "tet_p1_n2_deformed", "pri_p1_n2_deformed", "tet_p4_n2_deformed"])
 def test_general_fused_stage_single_class_vs_reference(name):
-    """the same on the periodic single-class tetrahedron and prism fixtures (a last batch of fewer than 16 elements
-    included), and what it leaves in the public arrays against the per-method path"""
+    """the same on the periodic single-class tetrahedron and prism fixtures, and what it leaves in the public arrays against the
+    per-method path.  Most of these hold 48 tetrahedra or 16 prisms -- whole batches of 16; a last batch of fewer elements occurs
+    on tet_p2_transonic and tet_p2_roem_sutherland (72 elements: 8 left), pri_p2_transonic (24: 8) and pri_p2_roem_sutherland
+    (36: 4) only, all P2 in the default launch form.  Last batches of 1, 15, 16 + 1 and 32 + 1 elements on every size class, launch
+    form and feature: tests/test_gpu_general_batches.py.  (tet_p1 and pri_p1: the instantiations {4, 12} and {6, 18}; tet_p4: the
+    size-generic kernels.)"""
     import hfx
     from test_gpu_methods_vs_golden import build
     d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
