@@ -159,6 +159,9 @@ int end_of_step(hfx_eles *const *eles, int neb)
   if (history_monitor_samples(ctx, ctx->i_steps))
     for (int i = 0; i < neb; i++)
       if (sample_history(eles[i], ctx->time, ctx->i_steps)) return 1;
+  if (plot_monitor_samples(ctx, ctx->i_steps)) /* src/HiFiLES.cpp:273-285 */
+    for (int i = 0; i < neb; i++)
+      if (sample_plot(eles[i], ctx->time, ctx->i_steps)) return 1;
   return 0;
 }
 

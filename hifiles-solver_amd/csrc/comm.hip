@@ -442,6 +442,10 @@ static const char *const MONITOR_PARTITIONED =
 static const char *const HISTORY_PARTITIONED =
     "partitioned step loop: the history monitor samples the viscous wall forces, which read grad_disu_upts, and the stages of this loop "
     "keep the gradient on chip; run it with fused mode 2 (hfx_ctx_set_fused_mode), or monitor the residuals alone (with_forces 0)";
+// the same for the plot monitor's vorticity and Q criteria (plot_fields.hip)
+static const char *const PLOT_PARTITIONED =
+    "partitioned step loop: the plot monitor has a field that reads grad_disu_upts (vorticity, q_criterion, scaled_q_criterion), and the "
+    "stages of this loop keep the gradient on chip; run it with fused mode 2 (hfx_ctx_set_fused_mode), or plot gradient-free fields alone";
 // nullptr: no monitor of this loop reads the gradient; else the refusal of a loop that keeps it on chip
 static const char *monitor_gradient_on_chip(hfx_eles *const *eles, int neb)
 {
@@ -449,6 +453,8 @@ static const char *monitor_gradient_on_chip(hfx_eles *const *eles, int neb)
   if (!ctx->have_clock || !monitor_reads_gradient(eles, neb)) return nullptr;
   for (int i = 0; i < neb; i++)
     if (history_monitor_reads_gradient(eles[i])) return HISTORY_PARTITIONED;
+  for (int i = 0; i < neb; i++)
+    if (plot_monitor_reads_gradient(eles[i])) return PLOT_PARTITIONED;
   return MONITOR_PARTITIONED;
 }
 
@@ -692,6 +698,7 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
   if (probes_check_capacity(&e, 1, n_steps)) return 1;
   if (integrals_check_capacity(&e, 1, n_steps)) return 1;
   if (history_check_capacity(&e, 1, n_steps)) return 1;
+  if (plot_check_capacity(&e, 1, n_steps)) return 1;
   if (const char *refusal = monitor_gradient_on_chip(&e, 1))
   {
     // (a plan of variant 2 writes grad_disu_upts in every stage: everything is sampled)
@@ -715,6 +722,7 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   if (probes_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
   if (integrals_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
   if (history_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
+  if (plot_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
   if (const char *refusal = monitor_gradient_on_chip(eles, n_ele_blocks)) // (the general stage keeps the gradient on chip)
     HFX_CHECK(false, "%s", refusal);
   for (int i = 0; i < n_ele_blocks; i++)

@@ -1738,6 +1738,7 @@ int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *face
   if (probes_check_capacity(eles, neb, n_steps)) return 1;
   if (integrals_check_capacity(eles, neb, n_steps)) return 1;
   if (history_check_capacity(eles, neb, n_steps)) return 1;
+  if (plot_check_capacity(eles, neb, n_steps)) return 1;
   if (fused == 4) return general_run_steps(eles, neb, faces, nfb, n_steps);
   HFX_CHECK(fused == 0 || neb == 1, "hfx_run_steps_blocks: the split fused stage (fused %d) takes one tensor-product element block; "
                                     "several blocks run per method (0) or through the general fused stage (4)", fused);

@@ -12,6 +12,7 @@
 
 #include "../../include/hfx.h"
 #include "physics.hpp"
+#include "plot_point.hpp"
 
 namespace hfx
 {
@@ -263,6 +264,12 @@ struct hfx_ctx
   bool hist_on = false, hist_forces = false;
   int hist_norm = 2, hist_freq = 1, hist_capacity = 0;
   unsigned long hist_epoch = 0;
+  // the plot monitor (hfx_ctx_set_plot_monitor): run_input.diagnostic_fields as hfx_plot_field codes in the caller's order,
+  // run_input.plot_freq and the snapshots a block's device history holds.  plot_epoch: as probe_epoch
+  bool plot_on = false;
+  int n_plot_diag = 0, plot_freq = 1, plot_capacity = 0;
+  int plot_codes[16] = {};
+  unsigned long plot_epoch = 0;
   // the exact solution of the error monitor (hfx_ctx_set_exact_solution): run_input.test_case and what eval_couette_flow takes
   hfx_exact exact{};
   bool have_exact = false;
@@ -390,6 +397,17 @@ struct HistoryRows
   std::vector<double> times;      // of the stored rows; their number is the number of stored rows
   std::vector<int> steps;
 };
+// The plot-file snapshots of one block (plot_fields.hip): per plot point the conserved fields, the registered average fields and the
+// monitor's diagnostic fields, field planes apart as disu_ppts lies
+struct PlotHistory
+{
+  DevBuf<double> history;         // (n_ppts, n_eles, n_out, capacity): snapshot s at [n_ppts * n_eles * n_out * s]
+  DevBuf<double> scratch;         // one snapshot: hfx_eles_calc_plot_fields, hfx_time_plot_fields
+  int n_ppts = 0, n_average = 0, n_out = 0, capacity = 0; // what `history` was made for
+  unsigned long epoch = 0;        // ctx->plot_epoch it was made at
+  std::vector<double> times;      // of the stored snapshots; their number is the number of stored snapshots
+  std::vector<int> steps;
+};
 } // namespace hfx
 
 struct hfx_eles
@@ -415,6 +433,8 @@ struct hfx_eles
   hfx::IntegralHistory integrals;
   // the rows of the context's history monitor (hfx_ctx_set_history_monitor)
   hfx::HistoryRows history_rows;
+  // the snapshots of the context's plot monitor (hfx_ctx_set_plot_monitor)
+  hfx::PlotHistory plot;
   // exact-solution error norms (error_norm.hip): pos_volume_cubpts (n_vol_cubpts, n_eles, n_dims) of hfx_eles_set_error_points,
   // the cubature size it was registered for, and one partial per workgroup and quantity of the call that runs
   hfx::DevBuf<double> pos_volume_cubpts, err_partial;
@@ -597,13 +617,31 @@ int history_check_capacity(hfx_eles *const *eles, int neb, int n_steps);
 // faces and the arrays its launch needs; _launch the kernel alone, whose per-workgroup partials stay in wall_forces->partial
 int wall_force_partials_prepare(hfx_eles *e, const char *who);
 int wall_force_partials_launch(hfx_eles *e, int *n_groups);
+// ---- the plot monitor (plot_fields.hip) ----
+// does a snapshot of e read grad_disu_upts: a monitor with vorticity or a Q criterion, a block with plot points
+bool plot_monitor_reads_gradient(const hfx_eles *e);
+// will the step loops take a snapshot behind the step that makes i_steps `step`?  i_steps % plot_freq == 0 (src/HiFiLES.cpp:273)
+inline bool plot_monitor_samples(const hfx_ctx *ctx, long step) { return ctx->have_clock && ctx->plot_on && step % ctx->plot_freq == 0; }
+// how many of the steps i_steps + 1 .. i_steps + n_steps are such steps
+inline long plot_samples_in(long i_steps, long n_steps, long freq) { return n_steps <= 0 ? 0 : (i_steps + n_steps) / freq - i_steps / freq; }
+// one snapshot of e on the compute stream; nothing for a context without the monitor or a block without plot points
+int sample_plot(hfx_eles *e, double time, int step);
+// what every step loop asks before its first launch, beside the other three: the capacity, and everything that refuses a block
+int plot_check_capacity(hfx_eles *const *eles, int neb, int n_steps);
 // ---- the one-stage rule of the step loops ----
 // does a monitor the loops sample read grad_disu_upts of one of these blocks: the integral monitor with an id 1-4 and a block with a
-// cubature, or the history monitor's viscous wall forces (history_monitor_reads_gradient)?  The last RK stage of a step that is
-// sampled then has to leave the corrected gradient of its input state in memory
+// cubature, the history monitor's viscous wall forces (history_monitor_reads_gradient), or the plot monitor's vorticity and Q criteria
+// on a block with plot points (plot_monitor_reads_gradient)?  The last RK stage of a step that is sampled then has to leave the
+// corrected gradient of its input state in memory
 bool monitor_reads_gradient(hfx_eles *const *eles, int neb);
-// will the loops sample such a monitor behind the step that makes i_steps `step`?
-inline bool monitor_samples(const hfx_ctx *ctx, long step) { return integral_monitor_samples(ctx, step) || history_monitor_samples(ctx, step); }
+// will the loops sample such a monitor behind the step that makes i_steps `step`?  (The plot monitor has a frequency of its own: it
+// counts only where it reads the gradient, so that a plot of gradient-free fields never changes what another monitor's steps launch)
+inline bool monitor_samples(const hfx_ctx *ctx, long step)
+{
+  bool plot_gradient = false;
+  for (int m = 0; m < ctx->n_plot_diag; m++) plot_gradient = plot_gradient || pf_reads_gradient(ctx->plot_codes[m]);
+  return integral_monitor_samples(ctx, step) || history_monitor_samples(ctx, step) || (plot_gradient && plot_monitor_samples(ctx, step));
+}
 // One RK stage call by call -- CalcResidual, AdvanceSolution, the shock filter where registered (hfx.hip) -- and the flux-point
 // solution of the new state, which the fused stage that follows reads: what a loop whose stages keep the gradient on chip runs as the
 // last stage of a step the monitor samples with a gradient quantity

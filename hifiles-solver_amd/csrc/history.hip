@@ -264,7 +264,7 @@ bool monitor_reads_gradient(hfx_eles *const *eles, int neb)
   if (!ctx->params.viscous) return false;
   const bool integrals = integral_monitor_reads_gradient(ctx);
   for (int i = 0; i < neb; i++)
-    if ((integrals && eles[i]->n_vol_cubpts > 0) || history_monitor_reads_gradient(eles[i])) return true;
+    if ((integrals && eles[i]->n_vol_cubpts > 0) || history_monitor_reads_gradient(eles[i]) || plot_monitor_reads_gradient(eles[i])) return true;
   return false;
 }
 

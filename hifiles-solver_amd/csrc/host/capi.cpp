@@ -633,6 +633,79 @@ extern "C" int hfxh_case_read_history(hfxh_case *c, int max_rows, int *steps, do
   return 0;
 }
 
+// ---- the plot monitor: the rows of the plot file ----------------------------------------------------------------------------
+extern "C" int hfxh_case_set_diagnostic_fields(hfxh_case *c, int n, const char *const *names)
+{
+  if (!c || n < 0 || (n > 0 && !names)) { g_err = "hfxh_case_set_diagnostic_fields: bad argument"; return 1; }
+  std::vector<std::string> v;
+  for (int i = 0; i < n; i++) v.push_back(names[i] ? names[i] : "");
+  input &in = c->S.run_input;
+  const std::vector<std::string> old = in.diagnostic_fields;
+  if (in.set_diagnostic_fields(v, g_err)) return 1;
+  if (RegisterPlotMonitor(&c->S))
+  {
+    const std::string why = c->S.err;
+    std::string ignored;
+    (void)in.set_diagnostic_fields(old, ignored);
+    (void)RegisterPlotMonitor(&c->S);
+    c->S.err.clear();
+    g_err = why;
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int hfxh_case_set_plot(hfxh_case *c, int plot_freq, int capacity)
+{
+  if (!c) { g_err = "hfxh_case_set_plot: NULL case"; return 1; }
+  input &in = c->S.run_input;
+  const int old_freq = in.plot_freq, old_capacity = in.plot_capacity;
+  if (in.set_plot(plot_freq, capacity, g_err)) return 1;
+  if (RegisterPlotMonitor(&c->S))
+  {
+    const std::string why = c->S.err;
+    in.plot_freq = old_freq;
+    in.plot_capacity = old_capacity;
+    (void)RegisterPlotMonitor(&c->S);
+    c->S.err.clear();
+    g_err = why;
+    return 1;
+  }
+  return 0;
+}
+
+extern "C" int hfxh_case_get_plot(hfxh_case *c, int *plot_freq, int *capacity, int *n_cols, long *n_points)
+{
+  if (!c) { g_err = "hfxh_case_get_plot: NULL case"; return 1; }
+  if (plot_freq) *plot_freq = c->S.run_input.plot_freq;
+  if (capacity) *capacity = c->S.run_input.plot_capacity;
+  if (n_cols) *n_cols = PlotColumns(&c->S);
+  if (n_points) *n_points = PlotPoints(&c->S);
+  return 0;
+}
+
+extern "C" int hfxh_case_sample_plot(hfxh_case *c)
+{
+  if (!c) { g_err = "hfxh_case_sample_plot: NULL case"; return 1; }
+  if (!c->S.run_input.plot_monitor_on()) { g_err = "hfxh_case_sample_plot: the case has no plot monitor (a capacity)"; return 1; }
+  if (SamplePlot(&c->S, true)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_plot_count(hfxh_case *c, int *n_snapshots)
+{
+  if (!c || !n_snapshots) { g_err = "hfxh_case_plot_count: NULL argument"; return 1; }
+  if (PlotCount(&c->S, n_snapshots)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
+extern "C" int hfxh_case_read_plot_rows(hfxh_case *c, int max_snapshots, double *times, int *steps, double *rows, int *n_snapshots)
+{
+  if (!c || !n_snapshots || (max_snapshots > 0 && (!times || !steps || !rows))) { g_err = "hfxh_case_read_plot_rows: NULL argument"; return 1; }
+  if (ReadPlotRows(&c->S, max_snapshots, times, steps, rows, n_snapshots)) { g_err = c->S.err; c->S.err.clear(); return 1; }
+  return 0;
+}
+
 extern "C" int hfxh_case_compute_error(hfxh_case *c, double *error)
 {
   if (!c || !error) { g_err = "hfxh_case_compute_error: NULL argument"; return 1; }

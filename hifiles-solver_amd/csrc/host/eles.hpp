@@ -167,6 +167,7 @@ public:
   hf_array<double> loc_ppts, opp_p, disu_ppts; // disu_ppts (n_ppts, n_eles, n_fields): filled by calc_disu_ppts_all
   void set_loc_ppts();
   void set_opp_p();
+  void calc_pos_ppts(int in_ele, hf_array<double> &out_pos_ppts);   // src/eles.cpp:3714: (n_ppts_per_ele, n_dims) through calc_pos
   int calc_disu_ppts_all();                                         // every element at once, on the device
   void calc_disu_ppts(int in_ele, hf_array<double> &out_disu_ppts); // the reference's per-element accessor
   virtual int set_shock_capture_operators(); // set_vandermonde1D/3D, calc_norm_basis, set_exp_filter; eles_tets / eles_pris override it

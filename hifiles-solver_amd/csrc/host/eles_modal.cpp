@@ -365,6 +365,17 @@ void eles::set_opp_p()
     }
 }
 
+void eles::calc_pos_ppts(int in_ele, hf_array<double> &out_pos_ppts)
+{
+  hf_array<double> loc(n_dims), pos(n_dims);
+  for (int i = 0; i < n_ppts_per_ele; i++)
+  {
+    for (int j = 0; j < n_dims; j++) loc(j) = loc_ppts(j, i);
+    calc_pos(loc, in_ele, pos);
+    for (int j = 0; j < n_dims; j++) out_pos_ppts(i, j) = pos(j);
+  }
+}
+
 int eles::calc_disu_ppts_all()
 {
   if (!dev) { fail("element block is not on the device"); return 1; }

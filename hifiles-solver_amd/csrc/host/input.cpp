@@ -185,6 +185,37 @@ int input::integral_quantity_code(int i) const
   return (int)(std::find(INTEGRAL_NAMES, INTEGRAL_NAMES + 5, integral_quantities[i]) - INTEGRAL_NAMES);
 }
 
+static const char *const PLOT_NAMES[10] = {"u", "v", "w", "energy", "mach", "pressure", "vorticity", "q_criterion", "scaled_q_criterion",
+                                           "sensor"}; /* src/eles.cpp:3885-3983 */
+
+int input::set_diagnostic_fields(const std::vector<std::string> &names, std::string &err)
+{
+  std::vector<std::string> lower(names);
+  for (std::string &s : lower)
+  {
+    std::transform(s.begin(), s.end(), s.begin(), [](unsigned char c) { return (char)std::tolower(c); }); /* src/input.cpp:125-129 */
+    if (std::find(PLOT_NAMES, PLOT_NAMES + 10, s) == PLOT_NAMES + 10) { err = "plot_quantity = " + s + ": plot_quantity not recognized"; return 1; } /* src/eles.cpp:3993-3994 */
+  }
+  if (lower.size() > HFX_MAX_PLOT_DIAGNOSTICS) { err = "diagnostic_fields: at most " + std::to_string(HFX_MAX_PLOT_DIAGNOSTICS) + " fields"; return 1; }
+  diagnostic_fields.swap(lower);
+  n_diagnostic_fields = (int)diagnostic_fields.size();
+  return 0;
+}
+
+int input::diagnostic_code(int i) const
+{
+  return (int)(std::find(PLOT_NAMES, PLOT_NAMES + 10, diagnostic_fields[i]) - PLOT_NAMES);
+}
+
+int input::set_plot(int freq, int capacity, std::string &err)
+{
+  if (freq < 1) { err = "plot_freq must be at least 1"; return 1; }
+  if (capacity < 0) { err = "the plot history holds at least 0 snapshots"; return 1; }
+  plot_freq = freq;
+  plot_capacity = capacity;
+  return 0;
+}
+
 static const char *const PROBE_NAMES[6] = {"rho", "u", "v", "w", "specific_total_energy", "pressure"}; /* src/output.cpp:1482-1522 */
 
 int input::set_probe_fields(const std::vector<std::string> &names, int n_dims, int freq, int capacity, std::string &err)

@@ -86,6 +86,18 @@ struct input
   int res_norm_type = 2, history_capacity = 0;
   int set_history(int norm_type, int capacity, std::string &err);
   bool history_monitor_on() const { return history_capacity > 0; }
+  // ---- the plot file (src/input.cpp:98,114,125-129): run_input.diagnostic_fields out of u, v, w, energy, mach, pressure, vorticity,
+  // q_criterion, scaled_q_criterion, sensor, lower-cased; another name is refused with the reference's words (src/eles.cpp:3994).
+  // plot_freq in steps (the reference's default is INT32_MAX: never); plot_capacity: the snapshots the device history of the plot
+  // monitor holds; 0: no snapshots are taken in the loops.  Refusals leave everything as it was
+  std::vector<std::string> diagnostic_fields;
+  int n_diagnostic_fields = 0;
+  int set_diagnostic_fields(const std::vector<std::string> &names, std::string &err);
+  int diagnostic_code(int i) const; // HFX_PLOT_* of diagnostic_fields(i)
+  int plot_freq = 2147483647, plot_capacity = 0;
+  int set_plot(int freq, int capacity, std::string &err);
+  bool plot_monitor_on() const { return plot_capacity > 0; }
+  bool plot_sample_step(int i_steps) const { return i_steps % plot_freq == 0; } /* src/HiFiLES.cpp:273 */
   // ---- mass-flux body force of periodic channels (`body_forcing`, src/input.cpp:312).  forcing_area and forcing_mdot0 are keys of
   // this mirror: the inflow area and the target mass flux, which the reference hard-codes to 9.162 both (src/eles.cpp:5393-5395);
   // forcing_history: evaluations whose massflux.dat columns the device keeps

@@ -727,6 +727,139 @@ static int history_has_room(solution *S, int n_steps)
   return 0;
 }
 
+// run_input's diagnostic fields, plot_freq and history size -> the context (every block's history starts empty); no monitor while
+// the case has no capacity
+int RegisterPlotMonitor(solution *S)
+{
+  if (!S->ctx) return 0; // (MoveToDevice registers it)
+  const input &in = S->run_input;
+  int codes[HFX_MAX_PLOT_DIAGNOSTICS] = {};
+  for (int m = 0; m < in.n_diagnostic_fields; m++) codes[m] = in.diagnostic_code(m);
+  if (hfx_ctx_set_plot_monitor(S->ctx, in.n_diagnostic_fields, codes, in.plot_freq, in.plot_capacity)) { S->err = hfx_last_error(); return 1; }
+  return 0;
+}
+
+// one snapshot of every class at the solution's time and step; !always: only under the reference's condition (src/HiFiLES.cpp:273).
+// Deferred, the sample's need mask makes the pending last stage leave the gradient where a field reads it, and only then
+int SamplePlot(solution *S, bool always)
+{
+  const input &in = S->run_input;
+  if (!in.plot_monitor_on() || (!always && !in.plot_sample_step(S->i_steps))) return 0;
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    if (hfx_eles_sample_plot(E->device(), S->time, S->i_steps)) { S->err = hfx_last_error(); return 1; }
+  }
+  return 0;
+}
+
+int PlotCount(solution *S, int *n_snapshots)
+{
+  *n_snapshots = 0;
+  if (!S->ctx) { S->err = "case is not on the device"; return 1; }
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    // (every class takes every snapshot: the first one's count is the case's)
+    if (hfx_eles_plot_count(E->device(), n_snapshots)) { S->err = hfx_last_error(); return 1; }
+    return 0;
+  }
+  return 0;
+}
+
+static int plot_has_room(solution *S, int n_steps)
+{
+  const input &in = S->run_input;
+  if (!in.plot_monitor_on() || !S->ctx) return 0;
+  int n_new = 0, have = 0;
+  if (hfx_plot_monitor_samples(S->i_steps, n_steps, in.plot_freq, &n_new)) { S->err = hfx_last_error(); return 1; }
+  if (PlotCount(S, &have)) return 1;
+  if (have + n_new > in.plot_capacity)
+  {
+    S->err = "plot monitor: " + std::to_string(n_steps) + " steps from step " + std::to_string(S->i_steps) + " take " +
+             std::to_string(n_new) + " snapshots (plot_freq " + std::to_string(in.plot_freq) + "), the history of " +
+             std::to_string(in.plot_capacity) + " holds " + std::to_string(have) + " already; read it or take fewer steps per call";
+    return 1;
+  }
+  return 0;
+}
+
+int PlotColumns(const solution *S)
+{
+  const input &in = S->run_input;
+  return S->n_dims + S->n_dims + 2 + in.n_average_fields + in.n_diagnostic_fields;
+}
+
+long PlotPoints(const solution *S)
+{
+  long n = 0;
+  for (int j = 0; j < S->n_ele_types; j++)
+    if (S->mesh_eles(j)) n += (long)S->mesh_eles(j)->get_n_eles() * S->mesh_eles(j)->n_ppts_per_ele;
+  return n;
+}
+
+int ReadPlotRows(solution *S, int max_snapshots, double *times, int *steps, double *rows, int *n_snapshots)
+{
+  const input &in = S->run_input;
+  if (!in.plot_monitor_on()) { S->err = "ReadPlotRows: the case has no plot monitor (a capacity)"; return 1; }
+  int n = 0;
+  if (PlotCount(S, &n)) return 1;
+  if (n > max_snapshots)
+  {
+    S->err = "ReadPlotRows: " + std::to_string(n) + " snapshots are stored, the caller's arrays hold " + std::to_string(max_snapshots);
+    return 1;
+  }
+  const int nd = S->n_dims, n_cols = PlotColumns(S), n_out = n_cols - nd;
+  const long n_points = PlotPoints(S);
+  std::vector<double> t(std::max(n, 1));
+  std::vector<int> st(std::max(n, 1));
+  long first = 0; // the class's first row of a snapshot
+  for (int j = 0; j < S->n_ele_types; j++)
+  {
+    eles *E = S->mesh_eles(j);
+    if (!E || E->get_n_eles() == 0) continue;
+    const int npp = E->n_ppts_per_ele, ne = E->get_n_eles();
+    std::vector<double> values((size_t)npp * ne * n_out * std::max(n, 1));
+    int got = 0;
+    if (hfx_eles_read_plot_snapshots(E->device(), n, t.data(), st.data(), values.data(), &got)) { S->err = hfx_last_error(); return 1; }
+    if (got != n) { S->err = "ReadPlotRows: the classes' histories differ in length"; return 1; }
+    hf_array<double> pos(npp, nd);
+    for (int i = 0; i < ne; i++)
+    {
+      E->calc_pos_ppts(i, pos); /* src/output.cpp:368 */
+      for (int s = 0; s < n; s++)
+        for (int k = 0; k < npp; k++)
+        {
+          double *row = rows + ((size_t)s * n_points + first + (size_t)i * npp + k) * n_cols;
+          for (int l = 0; l < nd; l++) row[l] = pos(k, l);
+          for (int l = 0; l < n_out; l++)
+          {
+            const double v = values[k + (size_t)npp * (i + (size_t)ne * (l + (size_t)n_out * s))];
+            if (std::isnan(v))
+            {
+              const int m = l - (nd + 2) - in.n_average_fields;
+              S->err = m >= 0 ? "In calculation of plot_quantitiy " + in.diagnostic_fields[m] + ": NaN" /* src/eles.cpp:3996-3999 */
+                              : "Nan in tecplot file, exiting";                                          /* src/output.cpp:397 */
+              return 1;
+            }
+            row[nd + l] = v;
+          }
+        }
+    }
+    first += (long)ne * npp;
+  }
+  for (int s = 0; s < n; s++)
+  {
+    times[s] = t[s];
+    steps[s] = st[s];
+  }
+  *n_snapshots = n;
+  return 0;
+}
+
 int NormResidual(int res_norm_type, int n_fields, const double *sum, long n_upts, double *norm_residual, std::string &err)
 {
   for (int i = 0; i < n_fields; i++)
@@ -920,6 +1053,7 @@ int MoveToDevice(solution *S, int device)
   if (RegisterProbeFields(S)) return 1; // (before the element blocks, which register their probes)
   if (S->run_input.calc_force != 0 && RegisterForceReference(S)) return 1; // (before the history monitor, whose rows carry the forces)
   if (RegisterIntegralMonitor(S)) return 1; // (and the history monitor behind it)
+  if (RegisterPlotMonitor(S)) return 1;
   if (S->run_input.test_case != 0 && RegisterExactSolution(S)) return 1;
   for (int i = 0; i < S->n_ele_types; i++)
     if (S->mesh_eles(i) && S->mesh_eles(i)->get_n_eles() != 0)
@@ -1111,7 +1245,7 @@ void SampleProbes(solution *FlowSol, bool always)
 }
 
 // src/HiFiLES.cpp:223,241-266 behind `time += dt`: the step counter, the spin-up time at the first step, the time averages, the
-// probes, the integral quantities of a history row (whose refusal, a full history for one, ends the loop)
+// probes, the integral quantities of a history row (whose refusal, a full history for one, ends the loop), the plot file
 static int count_step_and_average(solution *FlowSol)
 {
   FlowSol->i_steps++;
@@ -1121,7 +1255,8 @@ static int count_step_and_average(solution *FlowSol)
       if (FlowSol->mesh_eles(j)) FlowSol->mesh_eles(j)->CalcTimeAverageQuantities(FlowSol->time);
   SampleProbes(FlowSol, false); /* src/HiFiLES.cpp:289-297 */
   if (SampleIntegralQuantities(FlowSol, false)) return 1; /* src/HiFiLES.cpp:247-266 */
-  return SampleHistory(FlowSol, false);
+  if (SampleHistory(FlowSol, false)) return 1;
+  return SamplePlot(FlowSol, false); /* src/HiFiLES.cpp:273-285 */
 }
 
 int RunSteps(solution *FlowSol, int n_steps)
@@ -1130,6 +1265,7 @@ int RunSteps(solution *FlowSol, int n_steps)
   if (forcing_has_transport(FlowSol, "RunSteps")) return 1;
   if (integral_history_has_room(FlowSol, n_steps)) return 1;
   if (history_has_room(FlowSol, n_steps)) return 1;
+  if (plot_has_room(FlowSol, n_steps)) return 1;
   for (int i_steps = 0; i_steps < n_steps; i_steps++)
   {
     if (calc_time_step(FlowSol)) return 1; /* src/HiFiLES.cpp:198 */
@@ -1283,6 +1419,7 @@ int RunStepsPartitionedFused(solution *FlowSol, int n_steps)
   if (forcing_has_transport(FlowSol, "RunStepsPartitionedFused")) return 1;
   if (integral_history_has_room(FlowSol, n_steps)) return 1;
   if (history_has_room(FlowSol, n_steps)) return 1;
+  if (plot_has_room(FlowSol, n_steps)) return 1;
   const int RKSteps = in.n_rk_stages();
   const bool ex = !fm.empty() && FlowSol->exchange;
   auto phase = [&](int ph, int stage, int first) {

@@ -101,6 +101,18 @@ int ReadIntegralHistory(solution *FlowSol, int max_samples, double *times, int *
 int RegisterHistoryMonitor(solution *FlowSol);
 int SampleHistory(solution *FlowSol, bool always);
 int HistoryCount(solution *FlowSol, int *n_rows);
+// the plot monitor (hfx_ctx_set_plot_monitor): run_input's diagnostic_fields, plot_freq and history size -> the context; one snapshot
+// of every class at the solution's clock (always, or under the reference's condition i_steps % plot_freq == 0, src/HiFiLES.cpp:273);
+// the stored snapshots; the columns of a row (n_dims + n_fields + n_average_fields + n_diagnostic_fields) and the rows of a snapshot
+// (the plot points of every class); the rows as write_tec prints them (src/output.cpp:366-427), the histories emptied: per snapshot,
+// classes in their order, per element and plot point the position, the conserved fields, the averages, the diagnostic fields.  A NaN
+// is the reference's error ("Nan in tecplot file, exiting", src/output.cpp:397; "NaN", src/eles.cpp:3999)
+int RegisterPlotMonitor(solution *FlowSol);
+int SamplePlot(solution *FlowSol, bool always);
+int PlotCount(solution *FlowSol, int *n_snapshots);
+int PlotColumns(const solution *FlowSol);
+long PlotPoints(const solution *FlowSol);
+int ReadPlotRows(solution *FlowSol, int max_snapshots, double *times, int *steps, double *rows, int *n_snapshots);
 // the finish of output::CalcNormResidual (src/output.cpp:2236-2246) on what the classes and ranks gave: sum[n_fields] -- the max for
 // norm type 0, the sums for 1 and 2 -- and n_upts -> sum, sum / n_upts or sqrt(sum) / n_upts; a NaN norm is the reference's error
 int NormResidual(int res_norm_type, int n_fields, const double *sum, long n_upts, double *norm_residual, std::string &err);

@@ -235,6 +235,52 @@ def read_history_of(eles_handle, n_fields, n_forces):
     return times[:n].copy(), steps[:n].copy(), res[:, :n].copy(order="F"), forces[:, :n].copy(order="F")
 
 
+PLOT_NAMES = ["u", "v", "w", "energy", "mach", "pressure", "vorticity", "q_criterion", "scaled_q_criterion", "sensor"]
+
+
+def plot_count_of(eles_handle):
+    n = C.c_int(0)
+    check(lib().hfx_eles_plot_count(eles_handle, C.byref(n)))
+    return n.value
+
+
+def plot_width_of(eles_handle):
+    n = C.c_int(0)
+    check(lib().hfx_eles_plot_width(eles_handle, C.byref(n)))
+    return n.value
+
+
+def read_plot_snapshots_of(eles_handle, n_ppts, n_eles):
+    """(times (n), steps (n), values (n_ppts, n_eles, n_fields + n_average + n_diag, n)); empties the history"""
+    ns, width = plot_count_of(eles_handle), plot_width_of(eles_handle)
+    times, steps = np.zeros(max(1, ns)), np.zeros(max(1, ns), dtype=np.int32)
+    values = np.zeros((n_ppts, n_eles, width, max(1, ns)), order="F")
+    got = C.c_int(0)
+    check(lib().hfx_eles_read_plot_snapshots(eles_handle, C.c_int(ns), times.ctypes.data_as(dp), steps.ctypes.data_as(ip),
+                                             values.ctypes.data_as(dp), C.byref(got)))
+    return times[:got.value].copy(), steps[:got.value].copy(), values[..., :got.value].copy(order="F")
+
+
+def plot_monitor_samples(i_steps, n_steps, plot_freq):
+    """how many of the steps i_steps + 1 .. i_steps + n_steps the plot monitor samples (no device needed)"""
+    n = C.c_int(0)
+    check(lib().hfx_plot_monitor_samples(C.c_int(i_steps), C.c_int(n_steps), C.c_int(plot_freq), C.byref(n)))
+    return n.value
+
+
+def plot_point_fields(names, u, grad, gamma, sensor=0.0):
+    """the kernel's pointwise formulas on the host at one plot point (no device needed): u (n_dims + 2), grad (n_dims + 2, n_dims) or
+    None; the fields `names` in their order"""
+    codes = [PLOT_NAMES.index(n.lower()) if isinstance(n, str) else int(n) for n in names]
+    a = (C.c_int * max(1, len(codes)))(*codes)
+    u = np.ascontiguousarray(np.array(u, dtype=np.float64))
+    g = None if grad is None else _f(grad)
+    out = np.zeros(max(1, len(codes)))
+    check(lib().hfx_plot_point_fields(C.c_int(len(u) - 2), u.ctypes.data_as(dp), None if g is None else g.ctypes.data_as(dp),
+                                      C.c_double(gamma), C.c_double(sensor), C.c_int(len(codes)), a, out.ctypes.data_as(dp)))
+    return out[:len(codes)]
+
+
 def integral_monitor_samples(i_steps, n_steps, monitor_res_freq):
     """how many of the steps i_steps + 1 .. i_steps + n_steps the integral monitor samples (no device needed)"""
     n = C.c_int(0)
@@ -303,6 +349,14 @@ class Context:
         """the residual (and, with_forces, wall-force) columns of history.plt; capacity 0 drops the monitor"""
         check(lib().hfx_ctx_set_history_monitor(self.h, C.c_int(res_norm_type), C.c_int(1 if with_forces else 0),
                                                 C.c_int(monitor_res_freq), C.c_int(capacity)))
+
+    def set_plot_monitor(self, fields, plot_freq=1, capacity=1):
+        """fields: PLOT_* codes or the reference's names (u, v, w, energy, mach, pressure, vorticity, q_criterion,
+        scaled_q_criterion, sensor), in the order of the input file; [] plots the conserved fields (and averages) alone;
+        capacity 0 drops the monitor"""
+        codes = [PLOT_NAMES.index(f.lower()) if isinstance(f, str) else int(f) for f in fields]
+        a = (C.c_int * max(1, len(codes)))(*codes)
+        check(lib().hfx_ctx_set_plot_monitor(self.h, C.c_int(len(codes)), a, C.c_int(plot_freq), C.c_int(capacity)))
 
     def set_exact_solution(self, test_case, u_wall=0.0, T_wall=0.0, p_bound=0.0, R_ref=0.0, T_ref=0.0):
         """test_case 1: isentropic vortex; 5: Couette flow, which takes the five parameters (hfx_exact)"""
@@ -590,6 +644,34 @@ class Eles:
     def time_integral_quantities(self, reps=20):
         v = C.c_double(0)
         check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))
+        return v.value
+
+    def sample_plot(self, time, step):
+        """one snapshot of the context's plot monitor into the block's device history (no synchronisation)"""
+        self._call("hfx_eles_sample_plot", C.c_double(time), C.c_int(step))
+
+    def plot_count(self):
+        return plot_count_of(self.h)
+
+    def read_plot_snapshots(self):
+        """(times (n), steps (n), values (n_ppts, n_eles, n_fields + n_average + n_diag, n)); empties the history"""
+        return read_plot_snapshots_of(self.h, self.n_ppts, self.n_eles)
+
+    def calc_plot_fields(self):
+        """one snapshot of the state as it stands, (n_ppts, n_eles, n_fields + n_average + n_diag); the history is untouched"""
+        out = np.zeros((self.n_ppts, self.n_eles, plot_width_of(self.h)), dtype=np.float64, order="F")
+        check(lib().hfx_eles_calc_plot_fields(self.h, out.ctypes.data_as(dp)))
+        return out
+
+    def plot_launch(self):
+        """(workgroups, elements per pass, plot points of an element per pass of the lanes) of the next snapshot"""
+        g, n, p = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(lib().hfx_eles_plot_launch(self.h, C.byref(g), C.byref(n), C.byref(p)))
+        return g.value, n.value, p.value
+
+    def time_plot_fields(self, reps=20):
+        v = C.c_double(0)
+        check(lib().hfx_time_plot_fields(self.h, C.c_int(reps), C.byref(v)))
         return v.value
 
     def sample_history(self, time, step):

@@ -378,6 +378,36 @@ class Case:
         n = dims[0] * dims[1] * dims[2]
         return np.ctypeslib.as_array(ptr, shape=(n,)).reshape(tuple(dims), order="F").copy()
 
+    def set_diagnostic_fields(self, names):
+        """run_input.diagnostic_fields: names out of u, v, w, energy, mach, pressure, vorticity, q_criterion, scaled_q_criterion,
+        sensor (any letter case)"""
+        a = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        check(lib().hfxh_case_set_diagnostic_fields(self.h, C.c_int(len(names)), a))
+
+    def set_plot(self, plot_freq, capacity):
+        """run_input.plot_freq and the snapshots the device history of the plot monitor holds (0: no monitor)"""
+        check(lib().hfxh_case_set_plot(self.h, C.c_int(plot_freq), C.c_int(capacity)))
+
+    def sample_plot(self):
+        check(lib().hfxh_case_sample_plot(self.h))
+
+    def plot_count(self):
+        n = C.c_int(0)
+        check(lib().hfxh_case_plot_count(self.h, C.byref(n)))
+        return n.value
+
+    def read_plot_rows(self):
+        """(times (n), steps (n), rows (n, n_points, n_cols)): per snapshot the rows as write_tec prints them; empties the history"""
+        ncol, npts = C.c_int(0), C.c_long(0)
+        check(lib().hfxh_case_get_plot(self.h, None, None, C.byref(ncol), C.byref(npts)))
+        ns = self.plot_count()
+        times, steps = np.zeros(max(1, ns)), np.zeros(max(1, ns), dtype=np.int32)
+        rows = np.zeros((max(1, ns), npts.value, ncol.value))
+        got = C.c_int(0)
+        check(lib().hfxh_case_read_plot_rows(self.h, C.c_int(ns), times.ctypes.data_as(dp), steps.ctypes.data_as(ip),
+                                             rows.ctypes.data_as(dp), C.byref(got)))
+        return times[:got.value].copy(), steps[:got.value].copy(), rows[:got.value].copy()
+
     def sync_host(self):
         check(lib().hfxh_case_sync_host(self.h))
 

@@ -446,6 +446,77 @@ int hfx_eles_set_opp_p(hfx_eles *e, int n_ppts, const double *opp_p);
  * (output::write_vtu loops the elements, src/output.cpp) */
 int hfx_eles_calc_disu_ppts(hfx_eles *e, double *disu_ppts_host);
 
+/* ---- the plot monitor: the rows of the plot file sampled on the device (src/HiFiLES.cpp:273-285) --------------------------
+ * What output::write_tec / write_vtu put into a row behind the position, every run_input.plot_freq steps: the conserved fields at
+ * the plot points (eles::calc_disu_ppts), the time averages where the block has average fields (calc_time_average_ppts,
+ * hfx_eles_set_average_fields) and run_input.diagnostic_fields (calc_grad_disu_ppts, calc_sensor_ppts and
+ * calc_diagnostic_fields_ppts, src/eles.cpp:3781-4006).  One fused launch per block and snapshot interpolates with the registered
+ * opp_p (any element class) and evaluates the fields at the plot point; nothing of the size n_ppts x n_eles x n_fields x n_dims
+ * exists in memory.  A snapshot pairs disu_upts(0) as it stands with grad_disu_upts as it stands: behind a time step that is the
+ * new state and the corrected gradient of the last RK stage's INPUT state, exactly what the reference plots.  The monitor forms no
+ * gradient of its own.  The CONSERVATIVE gradient is interpolated and the velocity gradient formed at the plot point, as the
+ * reference does.  A NaN is stored as it is (the reference stops on one, src/eles.cpp:3996: the reader looks for it). */
+enum hfx_plot_field
+{
+  HFX_PLOT_U = 0,        /* "u": field 1 / density */
+  HFX_PLOT_V = 1,        /* "v" */
+  HFX_PLOT_W = 2,        /* "w": 0 on a two-dimensional block */
+  HFX_PLOT_ENERGY = 3,   /* "energy": field n_dims + 1 */
+  HFX_PLOT_MACH = 4,     /* "mach" */
+  HFX_PLOT_PRESSURE = 5, /* "pressure" */
+  HFX_PLOT_VORTICITY = 6,          /* "vorticity": its magnitude; |dv/dx - du/dy| in 2-D.  Reads the gradient */
+  HFX_PLOT_Q_CRITERION = 7,        /* "q_criterion": (OO - SS) / 2, three-dimensional blocks only.  Reads the gradient */
+  HFX_PLOT_SCALED_Q_CRITERION = 8, /* "scaled_q_criterion": (OO - SS) / 2 / (SS + 1e-24).  Reads the gradient */
+  HFX_PLOT_SENSOR = 9    /* "sensor": sensor(ele) at every plot point; blocks with shock capturing only */
+};
+#define HFX_MAX_PLOT_DIAGNOSTICS 16
+/* The diagnostic fields of the context in the caller's order, plot_freq >= 1 as run_input.plot_freq, and the snapshots the device
+ * history of every block holds (>= 1; 0 drops the monitor).  n_diag = 0 is a monitor of the conserved fields, with the averages where
+ * registered.  Any registration empties every block's history.  Refused here, with the reference's words: an unknown code
+ * ("plot_quantity not recognized") and a field that reads the gradient on an inviscid context ("Trying to calculate diagnostic field
+ * only supported by viscous simualtion").  The context does not know its blocks, so what depends on one is refused where the block is
+ * first asked -- by hfx_eles_sample_plot, hfx_eles_calc_plot_fields and by every step loop before its first launch: a Q criterion on a
+ * two-dimensional block ("Q criterion Not implemented in 2D"), the sensor on a block without shock capturing ("Sensor unavailable")
+ * and blocks of other than n_dims + 2 fields.  Parameters (hfx_ctx_set_params) come first. */
+int hfx_ctx_set_plot_monitor(hfx_ctx *ctx, int n_diag, const int *codes, int plot_freq, int capacity);
+/* ONE snapshot of the block (which needs hfx_eles_set_opp_p) into the next free slot of its device history; no synchronisation with
+ * the host, which notes `time` and `step` for the slot.  Ordinary stores, no atomics: two snapshots of one state are equal bit for bit.
+ * With a field that reads the gradient the rule of hfx_eles_compute_wall_forces applies: a pending deferred stage runs so that it
+ * leaves grad_disu_upts, and a gradient the last fused stage kept on chip is refused with the words of hfx_eles_download, never read
+ * stale.  With gradient-free fields the gradient is never touched: the sample works after any stage and on inviscid contexts.  A
+ * full history is refused, nothing is overwritten.
+ * Once the clock is the library's (hfx_ctx_set_clock) every step loop does this itself as the last duty of a step, behind averages,
+ * probes, the integral and the history monitor (the order of src/HiFiLES.cpp:241-285: a row's averages include the step), for every
+ * block with plot points after each step with i_steps % plot_freq == 0.  Such a loop first counts the snapshots it will take and
+ * refuses the whole call, before its first launch, when a history cannot hold them.  With a field that reads the gradient the
+ * one-stage rule of the integral monitor's ids 1-4 holds: a loop whose stages keep the gradient on chip runs the last RK stage of
+ * every step it samples call by call; the partitioned loops refuse that combination before their first launch and name the remedy
+ * (fused mode 2).  With gradient-free fields every loop launches exactly the stages it launched before. */
+int hfx_eles_sample_plot(hfx_eles *e, double time, int step);
+/* the number of stored snapshots (no copy, no synchronisation) | fields per plot point: n_fields + n_average_fields + n_diag */
+int hfx_eles_plot_count(hfx_eles *e, int *n_snapshots);
+int hfx_eles_plot_width(hfx_eles *e, int *n_out);
+/* Synchronises, copies the history -- values (n_ppts, n_eles, n_fields + n_average_fields + n_diag, n_snapshots) with the first index
+ * fastest: per snapshot the conserved fields, the averages, the diagnostics, field planes apart as disu_ppts lies; times and steps
+ * (n_snapshots) -- and empties it.  max_snapshots: what the caller's arrays hold; fewer than stored is refused, nothing is lost. */
+int hfx_eles_read_plot_snapshots(hfx_eles *e, int max_snapshots, double *times, int *steps, double *values, int *n_snapshots);
+/* the same kernel on demand: one snapshot (n_ppts, n_eles, n_fields + n_average_fields + n_diag) of the state as it stands into a HOST
+ * array; the history is untouched.  Bit for bit what hfx_eles_sample_plot stores for the same state.  Refusals as hfx_eles_sample_plot */
+int hfx_eles_calc_plot_fields(hfx_eles *e, double *host);
+/* what the next snapshot launches: workgroups, the elements a workgroup takes per pass of its loop, and the plot points of an element
+ * its lanes take at a time (an element with more is taken in several passes of the lanes) */
+int hfx_eles_plot_launch(hfx_eles *e, int *n_groups, int *eles_per_pass, int *ppts_per_pass);
+/* how many of the steps i_steps + 1 .. i_steps + n_steps are multiples of plot_freq: what the loops' capacity check counts */
+int hfx_plot_monitor_samples(int i_steps, int n_steps, int plot_freq, int *n_samples);
+/* The pointwise formulas of the kernel (csrc/plot_point.hpp) on the HOST, at one plot point: u[n_dims + 2] the interpolated conserved
+ * fields, grad (n_dims + 2, n_dims) column-major their interpolated gradient (may be NULL without a gradient field), the element's
+ * sensor; out[n_diag] the fields `codes` in their order.  No device is needed: what host-side unit tests call */
+int hfx_plot_point_fields(int n_dims, const double *u, const double *grad, double gamma, double sensor, int n_diag, const int *codes,
+                          double *out);
+/* device milliseconds of one snapshot, averaged over `reps` launches into a scratch snapshot (the history is untouched;
+ * grad_disu_upts is read as it stands, whichever stage wrote it) */
+int hfx_time_plot_fields(hfx_eles *e, int reps, double *ms);
+
 /* ---- time-averaged fields (run_input.average_fields, src/input.cpp:115-133) -------------------------------------------
  * The running time averages the reference's main loop updates after every time step (run_output.CalcTimeAverageQuantities,
  * src/HiFiLES.cpp:240-245) and every output writer takes to the plot points. */

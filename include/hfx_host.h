@@ -355,6 +355,32 @@ int hfxh_case_history_count(hfxh_case *c, int *n_rows);
  * histories have been read and emptied: those rows are gone.  Changing monitor_res_freq (hfxh_case_set_monitor_res_freq) registers
  * both monitors anew and empties both histories; changing the integral quantities alone leaves the history monitor's rows. */
 int hfxh_case_read_history(hfxh_case *c, int max_rows, int *steps, double *rows, int *n_cols, int *n_rows);
+/* ---- the plot monitor: the rows of the plot file (src/HiFiLES.cpp:273-285; output::write_tec, src/output.cpp:366-427) -----------
+ * run_input.diagnostic_fields: names out of u, v, w, energy, mach, pressure, vorticity, q_criterion, scaled_q_criterion, sensor, any
+ * letter case (lower-cased as src/input.cpp:125-129 does); another name is refused with "plot_quantity not recognized".  On a device
+ * case the context's refusals (hfx_ctx_set_plot_monitor) come back and leave the fields as they were. */
+int hfxh_case_set_diagnostic_fields(hfxh_case *c, int n, const char *const *names);
+/* run_input.plot_freq (>= 1; the default is the reference's INT32_MAX: never) and the snapshots the device history holds; capacity 0
+ * (the default): no monitor.  Registered (hfx_ctx_set_plot_monitor) here on a device case, by hfxh_case_to_device otherwise.
+ * hfxh_case_run and hfxh_case_run_partitioned then take one snapshot of every block after every step with i_steps % plot_freq == 0,
+ * as the last output of the step (the averages of a row include the step), with deferred execution on and off, and refuse a call
+ * whose snapshots the history cannot hold before its first launch.  Deferred, the sample's need mask makes the pending last stage
+ * run call by call where a field reads the gradient, and only that stage; with gradient-free fields every stage runs fused. */
+int hfxh_case_set_plot(hfxh_case *c, int plot_freq, int capacity);
+/* n_cols: n_dims + n_fields + n_average_fields + n_diagnostic_fields; n_points: the plot points of all blocks, the rows of one
+ * snapshot.  Any pointer may be NULL */
+int hfxh_case_get_plot(hfxh_case *c, int *plot_freq, int *capacity, int *n_cols, long *n_points);
+/* one snapshot now, at the case's time and step (hfx_eles_sample_plot of every block) */
+int hfxh_case_sample_plot(hfxh_case *c);
+int hfxh_case_plot_count(hfxh_case *c, int *n_snapshots);
+/* The rows exactly as write_tec prints them, and the histories emptied: rows (n_cols, n_points, n_snapshots) with the column index
+ * fastest; per snapshot the blocks in class order, per element and plot point the position (eles::calc_pos_ppts), the conserved
+ * fields, the averages, the diagnostic fields.  times (FlowSol.time, what SolutionTime prints) and steps per snapshot.  A NaN is the
+ * reference's error: "Nan in tecplot file, exiting" in a conserved or averaged column (src/output.cpp:397), "NaN" with the field's
+ * name in a diagnostic one (src/eles.cpp:3996-3999); the histories have been read and emptied by then.  Fewer than stored
+ * (max_snapshots) and a case without the monitor are refused before anything is read.  The file itself -- header, connectivity --
+ * stays with the caller, as do the plot points of simplex classes. */
+int hfxh_case_read_plot_rows(hfxh_case *c, int max_snapshots, double *times, int *steps, double *rows, int *n_snapshots);
 /* the inflow faces the reference's rule selects, elements ascending: (element, local face) */
 int hfxh_case_get_inflow_faces(hfxh_case *c, const int **ele, const int **inter, int *n_faces);
 /* hfx_eles_body_force_state / hfx_eles_body_force_history of the case's block */
