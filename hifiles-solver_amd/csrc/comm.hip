@@ -699,6 +699,7 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
   if (integrals_check_capacity(&e, 1, n_steps)) return 1;
   if (history_check_capacity(&e, 1, n_steps)) return 1;
   if (plot_check_capacity(&e, 1, n_steps)) return 1;
+  if (wall_model_check_points(int_faces, n_int)) return 1;
   if (const char *refusal = monitor_gradient_on_chip(&e, 1))
   {
     // (a plan of variant 2 writes grad_disu_upts in every stage: everything is sampled)
@@ -723,6 +724,7 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   if (integrals_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
   if (history_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
   if (plot_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
+  if (wall_model_check_points(int_faces, n_int)) return 1;
   if (const char *refusal = monitor_gradient_on_chip(eles, n_ele_blocks)) // (the general stage keeps the gradient on chip)
     HFX_CHECK(false, "%s", refusal);
   for (int i = 0; i < n_ele_blocks; i++)

@@ -1359,14 +1359,18 @@ int hfx_bdy_inters_create(hfx_ctx *ctx, hfx_eles *left, int n_inters, int nfpi, 
   const long np = (long)n_inters * nfpi;
   const long pl = (long)left->n_fpts * left->n_eles;
   for (long q = 0; q < np; q++) HFX_CHECK(L[q] >= 0 && L[q] < pl, "boundary face table L[%ld] = %d out of range", q, L[q]);
+  std::vector<int> wm_faces;
   for (int i = 0; i < n_inters; i++)
   {
     HFX_CHECK(boundary_id[i] >= 0 && boundary_id[i] < n_bcs, "boundary_id[%d] = %d out of range", i, boundary_id[i]);
     const hfx_bc &b = bcs[boundary_id[i]];
     HFX_CHECK(b.flag >= HFX_BC_SUB_IN_SIMP && b.flag <= HFX_BC_SLIP_WALL_DUAL && b.flag != HFX_BC_CYCLIC,
               "Boundary condition not implemented yet (bc_flag %d)", b.flag); /* src/input.cpp:341 */
-    HFX_CHECK(!((b.flag == HFX_BC_ISOTHERM_WALL || b.flag == HFX_BC_ADIABAT_WALL) && b.use_wm),
-              "boundary group %d uses the wall model, which is not part of this path", boundary_id[i]);
+    const bool wm = (b.flag == HFX_BC_ISOTHERM_WALL || b.flag == HFX_BC_ADIABAT_WALL) && b.use_wm;
+    HFX_CHECK(!wm || ctx->wall_model != 0,
+              "boundary group %d uses the wall model, which is not part of this path (the context has none: hfx_ctx_set_wall_model)",
+              boundary_id[i]);
+    if (wm) wm_faces.push_back(i);
     HFX_CHECK(b.flag != HFX_BC_ADIABAT_WALL || ctx->params.viscous || !ctx->have_params,
               "Adiabatic wall boundary only available to viscous simulation"); /* src/input.cpp:427 */
   }
@@ -1378,6 +1382,9 @@ int hfx_bdy_inters_create(hfx_ctx *ctx, hfx_eles *left, int n_inters, int nfpi, 
   f->R_ref = R_ref;
   f->hL.assign(L, L + np);
   if (f->L.upload(f->hL) || f->boundary_id.upload(boundary_id, n_inters) || f->bcs.upload(bcs, n_bcs)) return 1;
+  f->n_wm_faces = (int)wm_faces.size();
+  if (f->n_wm_faces > 0 && f->wm_face.upload(wm_faces)) return 1;
+  f->h_wm_face = std::move(wm_faces);
   left->faces_attached.push_back(f.get());
   fused_invalidate(left);
   general_invalidate(left);
@@ -1422,11 +1429,29 @@ int hfx_bdy_launch_internal(hfx_inters *f, int visc, int fast)
   HFX_CHECK(f && f->is_bdy, "not a boundary-face block");
   HFX_CHECK(f->ctx->have_params, "parameters not set");
   if (f->n_inters == 0) return 0;
+  const bool model = visc && f->n_wm_faces > 0;
+  HFX_CHECK(!model || f->wm_points,
+            "the block has %d wall-model faces and no input points (hfx_bdy_inters_set_wall_model_points)", f->n_wm_faces);
   const BdyArgs a = bdy_args(f);
   hipStream_t st = f->ctx->bdy_stream ? f->ctx->bdy_stream : f->ctx->stream;
+  WallModelArgs w{};
+  if (model)
+  {
+    hfx_eles *l = f->left;
+    w.b = a;
+    w.npts = (long)f->n_wm_faces * f->n_fpts_per_inter;
+    w.face = f->wm_face; w.upt = f->wm_upt; w.dist = f->wm_dist;
+    w.upts = l->arr[HFX_DISU_UPTS0];
+    w.n_upts = l->n_upts; w.n_fpts = l->n_fpts;
+    w.plane_u = (long)l->n_upts * l->n_eles;
+    w.model = f->ctx->wall_model; w.prandtl_t = f->ctx->wm_prandtl_t; w.Kappa = f->ctx->wm_Kappa;
+  }
   with_dims(f->left->n_dims, [&](auto ND) {
     auto launch = [&](auto FAST) {
-      launch_points(visc ? bdy_viscflux_kernel<ND(), FAST()> : bdy_invflux_kernel<ND(), FAST()>, a.npts, st, a);
+      if (model) // one launch: the workgroups of all points, then those of the compacted wall-model faces
+        hipLaunchKernelGGL((bdy_viscflux_wm_kernel<ND(), FAST()>), dim3(nblocks(a.npts, PT_BLOCK) + nblocks(w.npts, PT_BLOCK)), dim3(PT_BLOCK), 0, st, w);
+      else
+        launch_points(visc ? bdy_viscflux_kernel<ND(), FAST()> : bdy_invflux_kernel<ND(), FAST()>, a.npts, st, a);
     };
     if (fast)
       launch(std::true_type{});
@@ -1434,6 +1459,45 @@ int hfx_bdy_launch_internal(hfx_inters *f, int visc, int fast)
       launch(std::false_type{});
   });
   HFX_HIP(hipGetLastError());
+  return 0;
+}
+
+// run_input.wall_model, prandtl_t and Kappa (src/input.cpp:666; wall_model_funcs.cpp).  Before the boundary blocks are made
+int hfx_ctx_set_wall_model(hfx_ctx *ctx, int wall_model, double prandtl_t, double Kappa)
+{
+  HFX_CHECK(ctx, "NULL ctx");
+  HFX_IMMEDIATE(ctx, 0);
+  ctx->defer.plans.clear();
+  HFX_CHECK(wall_model == 0 || wall_model == 1 || wall_model == 2, "Wall model not implemented!"); /* src/wall_model_funcs.cpp:106 */
+  HFX_CHECK(wall_model == 0 || (prandtl_t > 0.0 && Kappa > 0.0), "hfx_ctx_set_wall_model: prandtl_t and Kappa must be positive");
+  ctx->wall_model = wall_model;
+  ctx->wm_prandtl_t = prandtl_t;
+  ctx->wm_Kappa = Kappa;
+  return 0;
+}
+
+int hfx_bdy_inters_set_wall_model_points(hfx_inters *f, const int *upt, const double *dist)
+{
+  HFX_CHECK(f && f->is_bdy, "not a boundary-face block");
+  HFX_CHECK(f->n_inters == 0 || (upt && dist), "hfx_bdy_inters_set_wall_model_points: NULL argument");
+  HFX_IMMEDIATE(f->ctx, 0);
+  f->ctx->defer.plans.clear();
+  for (int i : f->h_wm_face)
+    HFX_CHECK(upt[i] >= 0 && upt[i] < f->left->n_upts, "wall-model input point upt[%d] = %d out of range (n_upts %d)", i, upt[i],
+              f->left->n_upts);
+  // entries of faces without a model are never read; they are stored as point 0 so that the table holds no stray index
+  std::vector<int> u(f->n_inters, 0);
+  std::vector<double> d(f->n_inters, 0.0);
+  for (int i : f->h_wm_face) { u[i] = upt[i]; d[i] = dist[i]; }
+  if (f->n_inters > 0 && (f->wm_upt.upload(u) || f->wm_dist.upload(d))) return 1;
+  f->wm_points = true;
+  return 0;
+}
+
+int hfx_bdy_inters_wall_model_faces(hfx_inters *f, int *n)
+{
+  HFX_CHECK(f && f->is_bdy && n, "not a boundary-face block");
+  *n = f->n_wm_faces;
   return 0;
 }
 
@@ -1449,6 +1513,8 @@ int hfx_bdy_inters_evaluate_boundaryConditions_viscFlux(hfx_inters *f, double /*
 {
   HFX_CHECK(f && f->is_bdy, "not a boundary-face block");
   if (f->n_inters == 0) return 0;
+  HFX_CHECK(f->n_wm_faces == 0 || f->wm_points,
+            "the block has %d wall-model faces and no input points (hfx_bdy_inters_set_wall_model_points)", f->n_wm_faces);
   HFX_DEFER(f->ctx, DM_BDY_VISCFLUX, nullptr, f, nullptr, 0, 0);
   return hfx_bdy_launch_internal(f, 1, 0);
 }
@@ -1575,6 +1641,7 @@ int hfx_stage_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, 
   HFX_IMMEDIATE(e->ctx, 0);
   HFX_CHECK(e->ctx->have_params, "parameters not set");
   HFX_CHECK(phase >= 0 && phase <= 4, "hfx_stage_partitioned: phase must be 0..4");
+  if (wall_model_check_points(int_faces, n_int)) return 1;
   const bool viscous = e->ctx->params.viscous != 0;
   hipStream_t st = e->ctx->stream;
   PartitionedSplit s;
@@ -1670,7 +1737,8 @@ int hfx_CalcResidual_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *f
     }
     HFX_CHECK(l && r, "face block %d refers to an element block that is not part of this call", b);
   }
-#define HFX_EACH(call)             \
+  if (wall_model_check_points(faces, nfb)) return 1;
+#define HFX_EACH(call)            \
   for (int i = 0; i < neb; i++)    \
     if (call(eles[i])) return 1
   /* the call order of src/solver.cpp:65-216, every method over all element classes */
@@ -1739,6 +1807,7 @@ int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *face
   if (integrals_check_capacity(eles, neb, n_steps)) return 1;
   if (history_check_capacity(eles, neb, n_steps)) return 1;
   if (plot_check_capacity(eles, neb, n_steps)) return 1;
+  if (wall_model_check_points(faces, nfb)) return 1;
   if (fused == 4) return general_run_steps(eles, neb, faces, nfb, n_steps);
   HFX_CHECK(fused == 0 || neb == 1, "hfx_run_steps_blocks: the split fused stage (fused %d) takes one tensor-product element block; "
                                     "several blocks run per method (0) or through the general fused stage (4)", fused);

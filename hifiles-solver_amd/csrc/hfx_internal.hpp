@@ -278,6 +278,9 @@ struct hfx_ctx
   hfx_force_ref force_ref{};
   double force_factor = 0.0, force_aoa = 0.0, force_aos = 0.0;
   bool have_force_ref = false;
+  // the wall model (hfx_ctx_set_wall_model): run_input.wall_model (0 off, 1 Werner-Wengle, 2 Breuer-Rodi), prandtl_t, Kappa
+  int wall_model = 0;
+  double wm_prandtl_t = 0.9, wm_Kappa = 0.41;
   hfx::Phys phys() const
   {
     hfx::Phys P;
@@ -534,7 +537,30 @@ struct hfx_inters
   int n_bcs = 0, ramp_counter = 0;
   bool any_ramp = false; // a group of this block ramps its total pressure: run_input.pressure_ramp (src/input.cpp:374-377)
   double R_ref = 0.0;
+  // wall-model faces (a no-slip wall group with use_wm under a context with a wall model): their indices in the block, and
+  // per face of the block the input point and its wall distance (hfx_bdy_inters_set_wall_model_points)
+  int n_wm_faces = 0;
+  bool wm_points = false;
+  std::vector<int> h_wm_face;
+  hfx::DevBuf<int> wm_face, wm_upt;
+  hfx::DevBuf<double> wm_dist;
 };
+
+namespace hfx
+{
+// what every step loop and residual asks before its first launch: do the wall-model faces of a viscous run have their input points?
+inline int wall_model_check_points(hfx_inters *const *faces, int nfb)
+{
+  for (int b = 0; b < nfb; b++)
+  {
+    const hfx_inters *f = faces[b];
+    if (!f || !f->is_bdy || f->n_wm_faces == 0 || !f->ctx->params.viscous) continue;
+    HFX_CHECK(f->wm_points, "face block %d has %d wall-model faces and no input points (hfx_bdy_inters_set_wall_model_points)", b,
+              f->n_wm_faces);
+  }
+  return 0;
+}
+} // namespace hfx
 
 // RCCL transport of the partition-face buffers (comm.hip)
 struct hfx_comm

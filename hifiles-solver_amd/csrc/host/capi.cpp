@@ -74,6 +74,13 @@ extern "C" int hfxh_case_create(const hfxh_case_desc *d, hfxh_case **out)
     in.area_ref = d->area_ref;
     in.monitor_cp_freq = d->monitor_cp_freq;
   }
+  in.wall_model = d->wall_model;
+  if (d->wall_model != 0)
+  {
+    /* src/wall_model_funcs.cpp:106 (the reference finds out at the first viscous boundary sweep) */
+    if (d->wall_model != 1 && d->wall_model != 2) { g_err = "Wall model not implemented!"; delete c; return 1; }
+    if (d->prandtl_t > 0) in.prandtl_t = d->prandtl_t;
+  }
   if (in.setup_params(g_err)) { delete c; return 1; }
   for (int i = 0; i < d->n_bcs; i++)
   {
@@ -85,6 +92,7 @@ extern "C" int hfxh_case_create(const hfxh_case_desc *d, hfxh_case **out)
     s.nx = b.nx; s.ny = b.ny; s.nz = b.nz; s.mach = b.mach;
     s.p_ramp_coeff = b.p_ramp_coeff; s.T_ramp_coeff = b.T_ramp_coeff; s.p_total_old = b.p_total_old;
     s.T_total_old = b.T_total_old; s.T_total_old_given = b.T_total_old >= 0;
+    s.use_wm = b.use_wm;
     in.bc_specs.push_back(s);
   }
   if (in.read_boundary_param(g_err)) { delete c; return 1; }
@@ -231,6 +239,19 @@ extern "C" int hfxh_case_get_bdy_faces(hfxh_case *c, const int **L, const int **
   *boundary_id = B->boundary_id.get_ptr_cpu();
   *n_fpts_per_inter = B->n_fpts_per_inter;
   *n_inters = B->n_inters;
+  return 0;
+}
+
+extern "C" int hfxh_case_get_wall_model_points(hfxh_case *c, int *wall_model, const int **upt, const double **dist, int *n_inters,
+                                               int *n_wall_model_inters)
+{
+  if (!c) { g_err = "hfxh_case_get_wall_model_points: NULL case"; return 1; }
+  bdy_inters *B = the_bdy_faces(c);
+  if (wall_model) *wall_model = c->S.run_input.wall_model;
+  if (upt) *upt = B->wm_upt.get_ptr_cpu();
+  if (dist) *dist = B->wm_dist.get_ptr_cpu();
+  if (n_inters) *n_inters = B->n_inters;
+  if (n_wall_model_inters) *n_wall_model_inters = B->n_wm_inters;
   return 0;
 }
 

@@ -70,6 +70,29 @@ int eles::get_fpt_offset(int in_ele, int in_inter, int in_fpt) const
   return fpt + n_fpts_per_ele * in_ele;
 }
 
+double eles::calc_wm_upts_dist(int in_ele, int in_local_inter, int &out_upt) const
+{
+  double dist_min = 0., dist_max = 0.;
+  const int first = get_fpt_offset(0, in_local_inter, 0);
+  out_upt = 0; // (the reference leaves it unset when no distance is positive)
+  for (int i = 0; i < n_upts_per_ele; i++)
+  {
+    for (int j = 0; j < n_fpts_per_inter(in_local_inter); j++)
+    {
+      double temp_dist = 0.;
+      for (int k = 0; k < n_dims; k++)
+        temp_dist += (pos_fpts(first + j, in_ele, k) - pos_upts(i, in_ele, k)) * norm_fpts(first + j, in_ele, k);
+      if (j == 0 || temp_dist < dist_min) dist_min = temp_dist;
+    }
+    if (dist_min > dist_max)
+    {
+      dist_max = dist_min;
+      out_upt = i;
+    }
+  }
+  return dist_max;
+}
+
 // ---- operators --------------------------------------------------------------------
 void eles::set_opp_0()
 {

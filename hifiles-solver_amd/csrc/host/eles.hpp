@@ -133,6 +133,10 @@ public:
   int get_n_fpts_per_inter(int f) const { return n_fpts_per_inter(f); }
   // offset `fpt + n_fpts*ele` of local flux point `in_fpt` of local face `in_inter` of element `in_ele`
   int get_fpt_offset(int in_ele, int in_inter, int in_fpt) const;
+  // eles::calc_wm_upts_dist (src/eles.cpp:4873-4903): the wall model's input point of local face in_local_inter -- the FIRST solution
+  // point with the strictly largest minimum, over the face's flux points, of (pos_fpt - pos_upt) . n_fpt -- and that distance.  On a
+  // mesh where several points tie (a Cartesian one: the whole far row) the pick is the first strictly larger in this arithmetic
+  double calc_wm_upts_dist(int in_ele, int in_local_inter, int &out_upt) const;
   hfx_eles *device() { return dev; }
   const std::string &last_error() const { return err; }
   bool failed() const { return !err.empty(); }

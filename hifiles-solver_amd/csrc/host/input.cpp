@@ -320,10 +320,12 @@ int input::read_boundary_param(std::string &err)
       if (!viscous) { err = "Isothermal wall boundary only available to viscous simulation"; return 1; }
       b.T_static /= T_ref;
       for (int j = 0; j < 3; j++) vel[j] /= uvw_ref;
+      if (wall_model) b.use_wm = in.use_wm; /* src/input.cpp:413-414: not read without a wall model */
       break;
     case HFX_BC_ADIABAT_WALL:
       if (!viscous) { err = "Adiabatic wall boundary only available to viscous simulation"; return 1; }
       for (int j = 0; j < 3; j++) vel[j] /= uvw_ref;
+      if (wall_model) b.use_wm = in.use_wm; /* src/input.cpp:433-434 */
       break;
     default:
       break;

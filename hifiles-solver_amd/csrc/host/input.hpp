@@ -19,6 +19,7 @@ struct bc_spec
   int pressure_ramp = 0;
   double p_ramp_coeff = 0, T_ramp_coeff = 0, p_total_old = 0, T_total_old = 0;
   bool T_total_given = false, T_total_old_given = false;
+  int use_wm = 0; // bc_<name>_use_wm: read for isotherm_wall / adiabat_wall groups, and only when wall_model != 0 (src/input.cpp:413,433)
 };
 
 struct input
@@ -39,6 +40,8 @@ struct input
   // solution with filter_upts built from filter_type / filter_ratio
   int LES = 0, SGS_model = 1, filter_type = 0;
   double C_s = 0.0, filter_ratio = 1.0, Kappa = 0.41, prandtl_t = 0.9;
+  // ---- wall model (src/input.cpp:176): 0 none, 1 Werner-Wengle, 2 Breuer-Rodi; reads prandtl_t and Kappa above
+  int wall_model = 0;
   // ---- plotting: points per edge (src/input.cpp:110; the reference's default is 2)
   int p_res = 2;
   // ---- time-averaged fields (src/input.cpp:115-133): names of rho_average, u_average, v_average, w_average, e_average, lower-cased;

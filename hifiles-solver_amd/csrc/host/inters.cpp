@@ -268,6 +268,11 @@ void bdy_inters::setup(int in_n_inters, int in_inter_type, input *in)
   n_fields = n_dims + 2;
   boundary_id.setup(n_inters);
   disu_fpts_l.setup(n_fpts_per_inter, n_inters);
+  wm_upt.setup(n_inters);
+  wm_dist.setup(n_inters);
+  wm_upt.initialize_to_zero();
+  wm_dist.initialize_to_zero();
+  n_wm_inters = 0;
 }
 
 void bdy_inters::set_boundary(int in_inter, int bc_id, int in_ele_type_l, int in_ele_l, int in_local_inter_l,
@@ -282,6 +287,14 @@ void bdy_inters::set_boundary(int in_inter, int bc_id, int in_ele_type_l, int in
   }
   eles *el = FlowSol->mesh_eles(in_ele_type_l);
   for (int j = 0; j < n_fpts_per_inter; j++) disu_fpts_l(j, in_inter) = el->get_fpt_offset(in_ele_l, in_local_inter_l, j);
+  // wall model (src/bdy_inters.cpp:141-154): the farthest solution point of the face's own element and its distance
+  if (run_input->bc_list[bc_id].use_wm)
+  {
+    int upt_idx = 0;
+    wm_dist(in_inter) = el->calc_wm_upts_dist(in_ele_l, in_local_inter_l, upt_idx);
+    wm_upt(in_inter) = upt_idx;
+    n_wm_inters++;
+  }
 }
 
 int bdy_inters::mv_all_cpu_gpu(hfx_ctx *ctx, struct solution *FlowSol)
@@ -296,6 +309,11 @@ int bdy_inters::mv_all_cpu_gpu(hfx_ctx *ctx, struct solution *FlowSol)
     return 1;
   }
   if (hfx_bdy_inters_set_ramp_counter(dev, run_input->ramp_counter))
+  {
+    err = hfx_last_error();
+    return 1;
+  }
+  if (n_wm_inters > 0 && hfx_bdy_inters_set_wall_model_points(dev, wm_upt.get_ptr_cpu(), wm_dist.get_ptr_cpu()))
   {
     err = hfx_last_error();
     return 1;

@@ -116,6 +116,11 @@ public:
   int in_ele_type = -1;
   hf_array<int> boundary_id;  // index into run_input.bc_list
   hf_array<int> disu_fpts_l;  // left offsets
+  // the wall model's input point and its wall distance per face (src/bdy_inters.cpp:141-154; the reference keeps the faces of
+  // use_wm groups alone, in face order: wm_dist, wm_disu_ptr); faces without a model hold point 0, distance 0
+  hf_array<int> wm_upt;
+  hf_array<double> wm_dist;
+  int n_wm_inters = 0;
   input *run_input = nullptr;
 
 private:

@@ -1050,6 +1050,9 @@ int MoveToDevice(solution *S, int device)
   if (hfx_ctx_set_params(S->ctx, &p)) { S->err = hfx_last_error(); return 1; }
   if (S->run_input.dt_type != 0 && hfx_ctx_set_CFL(S->ctx, S->run_input.CFL)) { S->err = hfx_last_error(); return 1; }
   if (hfx_ctx_set_option(S->ctx, "deferred", S->deferred ? 1 : 0)) { S->err = hfx_last_error(); return 1; }
+  // (before the boundary blocks, which accept use_wm groups only under a context with a wall model)
+  if (S->run_input.wall_model != 0 &&
+      hfx_ctx_set_wall_model(S->ctx, S->run_input.wall_model, S->run_input.prandtl_t, S->run_input.Kappa)) { S->err = hfx_last_error(); return 1; }
   if (RegisterProbeFields(S)) return 1; // (before the element blocks, which register their probes)
   if (S->run_input.calc_force != 0 && RegisterForceReference(S)) return 1; // (before the history monitor, whose rows carry the forces)
   if (RegisterIntegralMonitor(S)) return 1; // (and the history monitor behind it)

@@ -4,18 +4,21 @@
 // the unit normal and the boundary group's parameters (bdy_inters::set_boundary_conditions,
 // :340-1019), the right gradient a function of the left gradient (set_boundary_gradients,
 // :1138-1189).  One thread per boundary flux point; the group's record is read through the face's
-// boundary_id.  Wall models, the synthetic-eddy LES inlet and the RANS field are not part of the path
-// (LES / RANS off) and are refused at registration.
+// boundary_id.  A no-slip wall group with use_wm carries the wall model (wall_model.hpp): its faces leave the viscous sweep at
+// once and further workgroups of the same launch, which walk the compacted list of those faces, add the modelled stress.  The synthetic-eddy
+// LES inlet and the RANS field are not part of the path (RANS off) and are refused at registration.
 #pragma once
 #include "../../include/hfx.h"
 #include "hfx_internal.hpp"
 #include "face_physics.hpp"
+#include "wall_model.hpp"
 
 namespace hfx
 {
 
 // ---- ghost state -----------------------------------------------------------------------------
-// sol_spec 0: the state the inviscid Riemann problem sees, 1: the state the viscous (LDG) terms see.
+// sol_spec 0: the state the inviscid Riemann problem sees, 1: the state the viscous (LDG) terms see, 2 (use_wm groups
+// only): the no-slip wall state the wall model takes.
 // Every boundary type is a function of the left primitives (rho, v, e, p, T, v.n, c), computed once, the
 // unit normal and the group's record; the arithmetic of each type follows the cited lines operation by
 // operation (the parity tests hold the boundary sweeps to 1e-12 of the reference).
@@ -34,7 +37,8 @@ __device__ __forceinline__ double sum_sq(const double (&w)[ND])
   return s;
 }
 
-template <int ND>
+// WM false: the caller has sent its wall-model faces elsewhere (the viscous kernel) and the use_wm states are not compiled in
+template <int ND, bool WM = true>
 __device__ __forceinline__ void bc_state(const int sol_spec, const hfx_bc &bc, const double (&u_l)[ND + 2],
                                          const double (&norm)[ND], const double gamma, const double R_ref,
                                          const int ramp_counter, double (&u_r)[ND + 2])
@@ -192,9 +196,17 @@ __device__ __forceinline__ void bc_state(const int sol_spec, const hfx_bc &bc, c
     e_g = L.p / gm1 + 0.5 * rho_g * sum_sq<ND>(w);
     break;
 
-  case HFX_BC_ISOTHERM_WALL: // :704-792 (wall model off): wall velocity, wall temperature
-  case HFX_BC_ADIABAT_WALL:  // :795-860 (wall model off): wall velocity, interior pressure
+  case HFX_BC_ISOTHERM_WALL: // :704-792 wall velocity, wall temperature
+  case HFX_BC_ADIABAT_WALL:  // :795-860 wall velocity, interior pressure
     rho_g = L.rho;
+    if (WM && bc.use_wm && sol_spec != 2)
+    {
+      // wall model on (:713-750, :802-825): the slip mirror for the Riemann problem, the wall-parallel velocity for the LDG
+      // common solution; the interior pressure for both kinds of wall
+      wall_normal(sol_spec == 0 ? 2.0 : 1.0);
+      e_g = L.p / gm1 + 0.5 * rho_g * sum_sq<ND>(w);
+      break;
+    }
     if (sol_spec == 0)
     {
 #pragma unroll
@@ -363,22 +375,28 @@ __global__ __launch_bounds__(256) void bdy_invflux_kernel(const BdyArgs a)
   }
 }
 
-// bdy_inters::evaluate_boundaryConditions_viscFlux (src/bdy_inters.cpp:1024-1136), faces without wall model
+__device__ __forceinline__ bool bc_uses_wall_model(const hfx_bc &bc)
+{
+  return bc.use_wm && (bc.flag == HFX_BC_ISOTHERM_WALL || bc.flag == HFX_BC_ADIABAT_WALL);
+}
+
+// bdy_inters::evaluate_boundaryConditions_viscFlux (src/bdy_inters.cpp:1024-1094), faces without wall model: the points of
+// workgroup `block`
 template <int ND, bool FAST>
-__global__ __launch_bounds__(256) void bdy_viscflux_kernel(const BdyArgs a)
+__device__ __forceinline__ void bdy_viscflux_points(const BdyArgs &a, const unsigned block)
 {
   constexpr int NF = ND + 2, NG = NF * ND;
-  const long q = (long)blockIdx.x * 256 + threadIdx.x;
+  const long q = (long)block * 256 + threadIdx.x;
   if (q >= a.npts) return;
   const long i = q / a.nfpi;
   const long il = a.L[q];
   const hfx_bc bc = a.bcs[a.boundary_id[i]];
-  if (bc.flag == HFX_BC_SLIP_WALL) return;
+  if (bc.flag == HFX_BC_SLIP_WALL || bc_uses_wall_model(bc)) return;
   double ul[NF], ur[NF], n[ND], gl[NG], gr[NG], fr[NG];
   gather_plane(a.disu, il, a.plane, ul);
   gather_plane(a.norm, il, a.plane, n);
   gather_plane(a.grad, il, a.plane, gl);
-  bc_state<ND>(1, bc, ul, n, a.P.gamma, a.R_ref, a.ramp_counter, ur);
+  bc_state<ND, false>(1, bc, ul, n, a.P.gamma, a.R_ref, a.ramp_counter, ur);
   bc_gradients<ND>(bc.flag, ur, gl, n, gr);
   calc_visf<ND, FAST>(a.P, ur, gr, fr);
   const double tl = a.tdA[il];
@@ -392,6 +410,64 @@ __global__ __launch_bounds__(256) void bdy_viscflux_kernel(const BdyArgs a)
     fn -= ldg_penalty(a.P, ul[k], ur[k]);
     store_flux_left<true>(a.tconf[il + k * a.plane], tl, fn);
   }
+}
+
+// the wall-model faces of a block (src/bdy_inters.cpp:1095-1132): one thread per flux point of the compacted face list.  The
+// input point is one per FACE (the reference's ctr advances once per interface): solution point upt[i] of the face's own
+// element, read from disu_upts(0) in the state of the current stage; no gradient, no LDG flux, no penalty
+struct WallModelArgs
+{
+  BdyArgs b;
+  long npts;            // n_fpts_per_inter * number of wall-model faces
+  const int *face;      // (number of wall-model faces) their indices in the block
+  const int *upt;       // (n_inters) the input point of each face
+  const double *dist;   // (n_inters) its distance from the wall
+  const double *upts;   // disu_upts(0) of the left block
+  int n_upts, n_fpts;
+  long plane_u;         // n_upts * n_eles
+  int model;
+  double prandtl_t, Kappa;
+};
+
+template <int ND>
+__device__ __forceinline__ void bdy_wallmodel_points(const WallModelArgs &a, const unsigned block)
+{
+  constexpr int NF = ND + 2;
+  const long q = (long)block * 256 + threadIdx.x;
+  if (q >= a.npts) return;
+  const long i = a.face[q / a.b.nfpi];
+  const long il = a.b.L[i * a.b.nfpi + q % a.b.nfpi];
+  const hfx_bc bc = a.b.bcs[a.b.boundary_id[i]];
+  double ul[NF], uw[NF], uwm[NF], n[ND], fn[NF];
+  gather_plane(a.b.disu, il, a.b.plane, ul);
+  gather_plane(a.b.norm, il, a.b.plane, n);
+  bc_state<ND>(2, bc, ul, n, a.b.P.gamma, a.b.R_ref, a.b.ramp_counter, uw);
+  gather_plane(a.upts, (il / a.n_fpts) * a.n_upts + a.upt[i], a.plane_u, uwm);
+  const WallModelPhys W{a.b.P.gamma, a.b.P.prandtl, a.b.P.rt_inf, a.b.P.mu_inf, a.b.P.c_sth, a.b.P.fix_vis};
+  wall_stress<ND>(a.model, W, a.prandtl_t, a.Kappa, uwm, uw, a.dist[i], n, fn);
+  const double tl = a.b.tdA[il];
+#pragma unroll
+  for (int k = 0; k < NF; k++) store_flux_left<true>(a.b.tconf[il + k * a.b.plane], tl, fn[k]);
+}
+
+// a block without wall-model faces: the kernel it always had
+template <int ND, bool FAST>
+__global__ __launch_bounds__(256) void bdy_viscflux_kernel(const BdyArgs a)
+{
+  bdy_viscflux_points<ND, FAST>(a, blockIdx.x);
+}
+
+// a block with wall-model faces, one launch: the first workgroups walk all points of the block as above (model faces return at
+// once), the workgroups behind them the points of the compacted model faces.  The branch is uniform over a workgroup, and the
+// registers are those of the larger side
+template <int ND, bool FAST>
+__global__ __launch_bounds__(256) void bdy_viscflux_wm_kernel(const WallModelArgs a)
+{
+  const unsigned nb = (unsigned)((a.b.npts + 255) / 256);
+  if (blockIdx.x < nb)
+    bdy_viscflux_points<ND, FAST>(a.b, blockIdx.x);
+  else
+    bdy_wallmodel_points<ND>(a, blockIdx.x - nb);
 }
 
 } // namespace hfx

@@ -309,6 +309,10 @@ class Context:
     def set_CFL(self, CFL):
         check(lib().hfx_ctx_set_CFL(self.h, C.c_double(CFL)))
 
+    def set_wall_model(self, wall_model, prandtl_t=0.9, Kappa=0.41):
+        """run_input.wall_model (0 off, 1 Werner-Wengle, 2 Breuer-Rodi); before the boundary blocks are made"""
+        check(lib().hfx_ctx_set_wall_model(self.h, C.c_int(wall_model), C.c_double(prandtl_t), C.c_double(Kappa)))
+
     def get_dt(self):
         v = C.c_double(0)
         check(lib().hfx_ctx_get_dt(self.h, C.byref(v)))
@@ -783,6 +787,19 @@ class BdyInters:
 
     def set_ramp_counter(self, ramp_counter):
         check(lib().hfx_bdy_inters_set_ramp_counter(self.h, C.c_int(ramp_counter)))
+
+    def set_wall_model_points(self, upt, dist):
+        """the wall model's input point (a solution point of the face's own element) and its wall distance, per face"""
+        upt = np.ascontiguousarray(np.array(upt, dtype=np.int32).ravel())
+        dist = np.ascontiguousarray(np.array(dist, dtype=np.float64).ravel())
+        if len(upt) != self.n_inters or len(dist) != self.n_inters:
+            raise HfxError("set_wall_model_points: %d faces, %d points, %d distances" % (self.n_inters, len(upt), len(dist)))
+        check(lib().hfx_bdy_inters_set_wall_model_points(self.h, upt.ctypes.data_as(ip), dist.ctypes.data_as(dp)))
+
+    def wall_model_faces(self):
+        n = C.c_int(0)
+        check(lib().hfx_bdy_inters_wall_model_faces(self.h, C.byref(n)))
+        return n.value
 
     def evaluate_boundaryConditions_invFlux(self, time=0.0):
         check(lib().hfx_bdy_inters_evaluate_boundaryConditions_invFlux(self.h, C.c_double(time)))

@@ -32,14 +32,15 @@ class CaseDesc(C.Structure):
                 ("prandtl_t", C.c_double), ("p_res", C.c_int), ("self_partition", C.c_int * 3), ("filter_type", C.c_int),
                 ("body_forcing", C.c_int), ("forcing_area", C.c_double), ("forcing_mdot0", C.c_double),
                 ("nx_c_ic", C.c_double), ("ny_c_ic", C.c_double), ("nz_c_ic", C.c_double),
-                ("calc_force", C.c_int), ("area_ref", C.c_double), ("monitor_cp_freq", C.c_int)]
+                ("calc_force", C.c_int), ("area_ref", C.c_double), ("monitor_cp_freq", C.c_int), ("wall_model", C.c_int)]
 
 
 class BcDesc(C.Structure):
     """hfxh_bc_desc: one boundary group, dimensional inputs as in the reference's input file."""
     _fields_ = [("flag", C.c_int), ("pressure_ramp", C.c_int)] + \
                [(k, C.c_double) for k in ("rho", "u", "v", "w", "p_static", "T_static", "p_total", "T_total", "nx", "ny", "nz",
-                                          "mach", "p_ramp_coeff", "T_ramp_coeff", "p_total_old", "T_total_old")]
+                                          "mach", "p_ramp_coeff", "T_ramp_coeff", "p_total_old", "T_total_old")] + \
+               [("use_wm", C.c_int)]
 
 
 BC_TYPES = {"sub_in_simp": 0, "sub_out_simp": 1, "sub_in_char": 2, "sub_out_char": 3, "sup_in": 4, "sup_out": 5,
@@ -221,6 +222,17 @@ class Case:
             par[:, b] = [r.rho, r.velocity[0], r.velocity[1], r.velocity[2], r.p_static, r.T_static, r.p_total, r.T_total,
                          r.nx, r.ny, r.nz, r.p_ramp_coeff, r.T_ramp_coeff, r.p_total_old, r.T_total_old]
         return fl, par, R.value, rc.value
+
+    def wall_model_points(self):
+        """(wall_model, upt (n_inters), dist (n_inters), number of wall-model faces): the model's input point of every boundary
+        face and its wall distance (0 on faces without a model), in the order of bdy_faces()"""
+        wm, ni, nw = C.c_int(), C.c_int(), C.c_int()
+        u, d = ip(), dp()
+        check(lib().hfxh_case_get_wall_model_points(self.h, C.byref(wm), C.byref(u), C.byref(d), C.byref(ni), C.byref(nw)))
+        if ni.value == 0:
+            return wm.value, np.zeros(0, dtype=np.int32), np.zeros(0), 0
+        return (wm.value, np.ctypeslib.as_array(u, shape=(ni.value,)).copy(), np.ctypeslib.as_array(d, shape=(ni.value,)).copy(),
+                nw.value)
 
     def mpi_faces(self):
         """(L, Rlut, Nout_proc) of the partition-face block."""

@@ -757,9 +757,24 @@ typedef struct hfx_bc
 /* L(j,i): offset of the face's flux point in the left block's (fpt,ele) plane (what bdy_inters::set_boundary,
  * src/bdy_inters.cpp:75-135, stores as pointers); boundary_id(i): index into bcs (bdy_inters::boundary_id);
  * R_ref: run_input.R_ref for viscous runs, run_input.R_gas for inviscid ones (src/bdy_inters.cpp:368-369).
- * Wall-model groups (use_wm) and the LES inlet are not part of this path and are refused. */
+ * An isotherm_wall / adiabat_wall group with use_wm takes the wall model of the context (hfx_ctx_set_wall_model, which
+ * comes first); under a context without one such a group is refused, as is the LES inlet. */
 int hfx_bdy_inters_create(hfx_ctx *ctx, hfx_eles *left, int n_inters, int n_fpts_per_inter, const int *L,
                           const int *boundary_id, const hfx_bc *bcs, int n_bcs, double R_ref, hfx_inters **out);
+/* The wall model of the reference (run_input.wall_model, src/wall_model_funcs.cpp): 0 off, 1 Werner-Wengle, 2 the
+ * compressible wall function of Breuer-Rodi; anything else: "Wall model not implemented!".  prandtl_t: run_input.prandtl_t
+ * (default 0.9); Kappa: the reference's constant 0.41 (src/input.cpp:666).  At a face of a use_wm group the ghost states are
+ * the slip mirror (inviscid Riemann problem) and the wall-parallel velocity (LDG common solution), and the viscous sweep adds
+ * (0, tau_w, -q_w + v_w . tau_w) tdA from calc_wall_stress in place of the LDG flux (src/bdy_inters.cpp:1095-1132).  The
+ * Newton loop of model 2 ends after 64 iterations with a NaN flux, where the reference's would not end. */
+int hfx_ctx_set_wall_model(hfx_ctx *ctx, int wall_model, double prandtl_t, double Kappa);
+/* The model's input point of every face (n_inters entries each): upt[i] a solution point of the face's own (left) element,
+ * whose disu_upts(0) of the current stage the model reads for ALL flux points of face i, and dist[i] its distance from the
+ * wall (eles::calc_wm_upts_dist, src/eles.cpp:4873-4903: the first solution point with the strictly largest minimum over the
+ * face's flux points of (pos_fpt - pos_upt) . n_fpt).  Entries of faces without a model are ignored; upt is range-checked.
+ * A viscous sweep or step loop over a block with wall-model faces and no registered points is refused before any launch. */
+int hfx_bdy_inters_set_wall_model_points(hfx_inters *f, const int *upt, const double *dist);
+int hfx_bdy_inters_wall_model_faces(hfx_inters *f, int *n); /* the wall-model faces of the block */
 int hfx_bdy_inters_set_ramp_counter(hfx_inters *f, int ramp_counter); /* run_input.ramp_counter (pressure ramps) */
 int hfx_bdy_inters_evaluate_boundaryConditions_invFlux(hfx_inters *f, double time_bound);  /* src/bdy_inters.cpp:213 */
 int hfx_bdy_inters_evaluate_boundaryConditions_viscFlux(hfx_inters *f, double time_bound); /* src/bdy_inters.cpp:1024 */

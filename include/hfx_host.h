@@ -26,6 +26,7 @@ typedef struct hfxh_bc_desc
   int flag, pressure_ramp;
   double rho, u, v, w, p_static, T_static, p_total, T_total, nx, ny, nz, mach;
   double p_ramp_coeff, T_ramp_coeff, p_total_old, T_total_old;
+  int use_wm; /* `bc_<name>_use_wm` of an isotherm_wall / adiabat_wall group: read only when the case has a wall model */
 } hfxh_bc_desc;
 
 /* inputs are DIMENSIONAL, exactly the keys of the reference's input file
@@ -104,6 +105,11 @@ typedef struct hfxh_case_desc
   int calc_force;
   double area_ref;
   int monitor_cp_freq;
+  /* `wall_model` (src/input.cpp:176): 0 none, 1 Werner-Wengle, 2 Breuer-Rodi, anything else "Wall model not implemented!"; reads
+   * prandtl_t above (0: 0.9) and the groups' use_wm.  The mirror finds every model face's input point (eles::calc_wm_upts_dist, in
+   * the face's own element: nothing crosses ranks) and hfxh_case_to_device registers the model and the points
+   * (hfx_ctx_set_wall_model, hfx_bdy_inters_set_wall_model_points). */
+  int wall_model;
 } hfxh_case_desc;
 
 const char *hfxh_last_error(void);
@@ -122,6 +128,12 @@ int hfxh_case_get_faces(hfxh_case *c, const int **L, const int **R, int *n_fpts_
  * (what input::read_boundary_param leaves in run_input.bc_list) with R_ref and ramp_counter */
 int hfxh_case_get_bdy_faces(hfxh_case *c, const int **L, const int **boundary_id, int *n_fpts_per_inter, int *n_inters);
 int hfxh_case_get_bcs(hfxh_case *c, const hfx_bc **bcs, int *n_bcs, double *R_ref, int *ramp_counter);
+/* the wall model's input points: per boundary face (n_inters entries, the order of hfxh_case_get_bdy_faces) the solution point of
+ * the face's element and its wall distance; faces without a model hold 0.  On a mesh where several solution points tie for the
+ * largest distance (a Cartesian one: the whole far row) the point is the first strictly larger in the mirror's own arithmetic,
+ * which need not be the reference's pick.  Any pointer may be NULL */
+int hfxh_case_get_wall_model_points(hfxh_case *c, int *wall_model, const int **upt, const double **dist, int *n_inters,
+                                    int *n_wall_model_inters);
 /* partition faces (mpi_inters): left offsets L(j,i), received-record slots Rlut(j,i), and Nout_proc[nproc]
  * = faces shared with each rank; a rank's faces are contiguous and ordered by rank */
 int hfxh_case_get_mpi_faces(hfxh_case *c, const int **L, const int **Rlut, int *n_fpts_per_inter, int *n_inters,
