@@ -181,6 +181,21 @@ int hfx_ctx_set_clock(hfx_ctx *ctx, double time, int i_steps)
   return 0;
 }
 
+int hfx_flush_for_samples(hfx_eles *const *eles, int n_ele_blocks, int which)
+{
+  HFX_CHECK(eles && n_ele_blocks > 0 && eles[0], "hfx_flush_for_samples: no element blocks");
+  HFX_CHECK(which >= 0 && which < 8, "hfx_flush_for_samples: which %d (the sum of 1 integrals, 2 history, 4 plot)", which);
+  unsigned need = 0;
+  for (int i = 0; i < n_ele_blocks; i++)
+  {
+    HFX_CHECK(eles[i] && eles[i]->ctx == eles[0]->ctx, "hfx_flush_for_samples: the blocks belong to several contexts");
+    if (which & 1) need |= integral_sample_need(eles[i]);
+    if (which & 2) need |= history_sample_need(eles[i]);
+    if (which & 4) need |= plot_sample_need(eles[i]);
+  }
+  return defer_flush(eles[0]->ctx, need);
+}
+
 int hfx_ctx_set_spinup_time(hfx_ctx *ctx, double spinup_time)
 {
   HFX_CHECK(ctx, "hfx_ctx_set_spinup_time: NULL ctx");

@@ -668,6 +668,12 @@ inline bool monitor_samples(const hfx_ctx *ctx, long step)
   for (int m = 0; m < ctx->n_plot_diag; m++) plot_gradient = plot_gradient || pf_reads_gradient(ctx->plot_codes[m]);
   return integral_monitor_samples(ctx, step) || history_monitor_samples(ctx, step) || (plot_gradient && plot_monitor_samples(ctx, step));
 }
+// what one sample of each monitor asks a pending deferred stage to leave in memory (bit i = hfx_array_id i): the need mask of
+// hfx_eles_sample_integral_quantities, hfx_eles_sample_history and hfx_eles_sample_plot; 0 where the context has no such monitor
+// or the block is not equipped for it
+unsigned integral_sample_need(const hfx_eles *e);
+unsigned history_sample_need(const hfx_eles *e);
+unsigned plot_sample_need(const hfx_eles *e);
 // One RK stage call by call -- CalcResidual, AdvanceSolution, the shock filter where registered (hfx.hip) -- and the flux-point
 // solution of the new state, which the fused stage that follows reads: what a loop whose stages keep the gradient on chip runs as the
 // last stage of a step the monitor samples with a gradient quantity

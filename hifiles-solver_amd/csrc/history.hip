@@ -258,6 +258,14 @@ bool history_monitor_reads_gradient(const hfx_eles *e)
   return ctx->hist_on && ctx->hist_forces && ctx->params.viscous && block_has_walls(e);
 }
 
+unsigned history_sample_need(const hfx_eles *e)
+{
+  if (!e->ctx->hist_on) return 0;
+  unsigned need = 1u << HFX_DIV_TCONF_UPTS;
+  if (history_monitor_reads_gradient(e)) need |= (1u << HFX_DISU_UPTS0) | (1u << HFX_GRAD_DISU_UPTS);
+  return need;
+}
+
 bool monitor_reads_gradient(hfx_eles *const *eles, int neb)
 {
   const hfx_ctx *ctx = eles[0]->ctx;
@@ -342,9 +350,7 @@ int hfx_eles_sample_history(hfx_eles *e, double time, int step)
   hfx_ctx *ctx = e->ctx;
   HFX_CHECK(ctx->hist_on, "hfx_eles_sample_history: no monitor (hfx_ctx_set_history_monitor)");
   // (a pending stage runs so that it stores div_tconf_upts and, for the viscous force, leaves the gradient: hfx_eles_compute_wall_forces)
-  unsigned need = 1u << HFX_DIV_TCONF_UPTS;
-  if (history_monitor_reads_gradient(e)) need |= (1u << HFX_DISU_UPTS0) | (1u << HFX_GRAD_DISU_UPTS);
-  HFX_IMMEDIATE(ctx, need);
+  HFX_IMMEDIATE(ctx, history_sample_need(e));
   return sample_history(e, time, step);
 }
 

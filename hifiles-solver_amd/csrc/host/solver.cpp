@@ -1253,6 +1253,20 @@ static int count_step_and_average(solution *FlowSol)
 {
   FlowSol->i_steps++;
   if (FlowSol->i_steps == 1) FlowSol->run_input.spinup_time = FlowSol->time;
+  // Deferred execution: the step's last stage is still pending, and the first reader below decides how it runs.  The averages and
+  // the probes read the state alone: behind them the stage would run fused and keep on chip the gradient that a monitor further down
+  // reads.  So the monitors that sample behind this step say what they read before anyone reads
+  const input &in = FlowSol->run_input;
+  const int which = (in.integral_monitor_on() && in.integral_sample_step(FlowSol->i_steps) ? 1 : 0) |
+                    (in.history_monitor_on() && in.integral_sample_step(FlowSol->i_steps) ? 2 : 0) |
+                    (in.plot_monitor_on() && in.plot_sample_step(FlowSol->i_steps) ? 4 : 0);
+  if (which && FlowSol->ctx)
+  {
+    std::vector<hfx_eles *> blocks;
+    for (int j = 0; j < FlowSol->n_ele_types; j++)
+      if (FlowSol->mesh_eles(j) && FlowSol->mesh_eles(j)->get_n_eles() > 0) blocks.push_back(FlowSol->mesh_eles(j)->device());
+    if (!blocks.empty() && hfx_flush_for_samples(blocks.data(), (int)blocks.size(), which)) { FlowSol->err = hfx_last_error(); return 1; }
+  }
   if (FlowSol->run_input.n_average_fields)
     for (int j = 0; j < FlowSol->n_ele_types; j++)
       if (FlowSol->mesh_eles(j)) FlowSol->mesh_eles(j)->CalcTimeAverageQuantities(FlowSol->time);

@@ -301,6 +301,12 @@ static int launch_sample(hfx_eles *e, int slot)
   return 0;
 }
 
+unsigned integral_sample_need(const hfx_eles *e)
+{
+  if (e->ctx->n_iq <= 0 || e->n_vol_cubpts <= 0) return 0;
+  return integral_monitor_reads_gradient(e->ctx) ? (1u << HFX_DISU_UPTS0) | (1u << HFX_GRAD_DISU_UPTS) : (1u << HFX_DISU_UPTS0);
+}
+
 bool integral_monitor_reads_gradient(const hfx_ctx *ctx)
 {
   for (int m = 0; m < ctx->n_iq; m++)
@@ -389,7 +395,7 @@ int hfx_eles_sample_integral_quantities(hfx_eles *e, double time, int step)
   HFX_CHECK(e->n_vol_cubpts > 0 && e->opp_volume_cubpts.dense, "hfx_eles_sample_integral_quantities: hfx_eles_set_volume_cubpts was not called");
   const bool grad = integral_monitor_reads_gradient(ctx);
   // (a pending stage runs so that it leaves the gradient when a quantity reads it; with kinetic energy alone fused as it would have)
-  HFX_IMMEDIATE(ctx, grad ? (1u << HFX_DISU_UPTS0) | (1u << HFX_GRAD_DISU_UPTS) : (1u << HFX_DISU_UPTS0));
+  HFX_IMMEDIATE(ctx, integral_sample_need(e));
   if (grad) HFX_CHECK_CURRENT(e, HFX_GRAD_DISU_UPTS, "hfx_eles_sample_integral_quantities");
   return sample_integrals(e, time, step);
 }

@@ -302,6 +302,8 @@ static unsigned need_mask(const hfx_eles *e)
   return need;
 }
 
+unsigned plot_sample_need(const hfx_eles *e) { return e->ctx->plot_on && e->n_ppts > 0 ? need_mask(e) : 0; }
+
 } // namespace hfx
 
 using namespace hfx;

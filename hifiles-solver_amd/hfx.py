@@ -863,6 +863,13 @@ def run_steps_blocks(eles, faces, n_steps, fused=0):
     check(lib().hfx_run_steps_blocks(ea, C.c_int(len(eles)), fa, C.c_int(len(faces)), C.c_int(n_steps), C.c_int(int(fused))))
 
 
+def flush_for_samples(eles, integrals=False, history=False, plot=False):
+    """hfx_flush_for_samples: deferred execution, before the first reader of a step -- the pending record runs so that what the
+    named samples of these blocks read is in memory"""
+    ea = (C.c_void_p * len(eles))(*[e.h for e in eles])
+    check(lib().hfx_flush_for_samples(ea, C.c_int(len(eles)), C.c_int((1 if integrals else 0) | (2 if history else 0) | (4 if plot else 0))))
+
+
 def run_steps_partitioned_blocks(eles, int_faces, mpi_faces, comm, n_steps):
     """hfx_run_steps_partitioned_blocks: the general fused stage on partitioned element blocks"""
     ea = (C.c_void_p * len(eles))(*[e.h for e in eles])

@@ -179,6 +179,17 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value);
  * (hfx_comm_exchange_stats counts them).  An upload of the state, a device pointer to it or a closure that filters it waits for
  * such a message first and drops it; hfx_ctx_synchronize also waits for the communication streams that carry one. */
 int hfx_ctx_flush(hfx_ctx *ctx); /* run what has been recorded (asynchronously, on the context's stream); no-op otherwise */
+/* Several readers behind one step.  Every entry point that reads device state makes a pending stage run so that ITS arrays hold the
+ * reference's values: the time averages and the probes read the state alone and let the stage run fused, and a stage that has run
+ * fused cannot give a later reader -- hfx_eles_sample_integral_quantities with an id 1-4, hfx_eles_sample_history with viscous
+ * forces, hfx_eles_sample_plot with vorticity or a Q criterion -- the gradient it kept on chip: that reader is refused.  A caller
+ * that is about to take several of these samples behind the step just recorded (the main loop of src/HiFiLES.cpp:221-297 takes
+ * them all) says so BEFORE the first reader: `which` is the sum of 1 (integral quantities), 2 (history row) and 4 (plot snapshot).
+ * The pending record then runs once, so that the union of what those samples read of these blocks is in memory -- call by call
+ * where one of them reads the gradient, fused otherwise, exactly as the sample would have asked had it come first.  A monitor the
+ * context does not have, or a block without its cubature, wall faces or plot points, counts for nothing; which 0, no pending
+ * record or no deferred execution: hfx_ctx_flush.  Nothing is sampled. */
+int hfx_flush_for_samples(hfx_eles *const *eles, int n_ele_blocks, int which);
 /* stages run fused / records replayed call by call since the context was created, and why the last replay was one */
 int hfx_ctx_deferred_stats(hfx_ctx *ctx, long *n_fused, long *n_replayed, const char **why_last_replay);
 /* run_input.dt as the last calc_time_step left it (dt_type 1), or as set (dt_type 0) */

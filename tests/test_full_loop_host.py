@@ -1,0 +1,150 @@
+"""The full-loop fixtures (tests/golden/full_loop/fl_*.npz; tools/capture_full_loop.py) on the CPU: conditions 2 and 3 of the capture
+are proved again from the committed files, so that a stale or hand-edited fixture fails here, and the sampling schedule the fixtures
+pin is the one hfx_integral_monitor_samples and hfx_plot_monitor_samples count, for the whole span and for every cut of it into two
+and three calls.  No GPU.  Bars: tests/history_rows_util.py and tests/plot_rows_util.py; see tests/full_loop_util.py."""
+import numpy as np
+import pytest
+
+import full_loop_util as FU
+import hfx
+import history_rows_util as HU
+import integral_history_util as IU
+import plot_rows_util as PU
+
+# history rows and plot files per case, as the issue of this family states them
+ROWS = {"fl_hex_p2_channel": ([1, 3, 6], [2, 4, 6]), "fl_hex_p2_forced": ([1], [2]), "fl_quad_p3_walls": ([1, 2, 4], [3]),
+        "fl_tet_p2_euler": ([1, 4], [3, 6])}
+BY_CALLS = {"fl_hex_p2_channel": [1, 2, 3, 4, 6], "fl_hex_p2_forced": [1, 2], "fl_quad_p3_walls": [1, 2, 3, 4], "fl_tet_p2_euler": [1, 3, 4, 6]}
+
+
+@pytest.mark.parametrize("name", FU.FL)
+def test_every_row_the_driver_wrote_is_met(name):
+    """condition 2: the oracle in lockstep -- the state after the step with the corrected gradient of the last stage's input --
+    meets every column of every history row and every plot file; the bars the capture recorded are the ones found now"""
+    d, w = FU.reference(name)
+    sz = [int(v) for v in d["sizes"]]
+    diag, avg = PU.names_of(d, "diagnostic_fields"), PU.names_of(d, "average_fields")
+    assert [r["step"] for r in w["hist"]] == [int(v) for v in d["hist_iter"]] == ROWS[name][0]
+    assert [s["step"] for s in w["plot"]] == [int(v) for v in d["plot_iter"]] == ROWS[name][1]
+    assert d["plot_rows"].shape == (len(w["plot"]), sz[0] * d["opp_p"].shape[0], sz[4] + sz[3] + len(avg) + len(diag))
+    for k, r in enumerate(w["hist"]):
+        bars = {key: r[key] for key in ("res_bars", "force_bars", "diag_bars") if key in r}
+        print("%s history row at step %d: %s (forces in units of the row's own size: %s)" % (name, r["step"], bars, r.get("force_row_size")))
+        assert max(bars.values()) <= 1.0, (name, r["step"], bars)
+        assert ("force_bars" in r) == bool(int(d["calc_force"][0])) and ("diag_bars" in r) == bool(d["hist_diag"].shape[1])
+        assert abs(r["step"] * w["dt"] * float(d["time_ref"][0]) - d["hist_time"][k]) <= 1e-13 * d["hist_time"][k]
+    for s in w["plot"]:
+        print("%s plot file %d: %s bars" % (name, s["step"], np.array2string(s["bars"], precision=2)))
+        assert np.all(s["bars"] <= PU.bars(d)), (name, s["step"], s["bars"])
+    assert FU.worst_bars(w) <= 1.0
+    assert np.all(np.array([s["bars"] for s in w["plot"]]).max(axis=0) <= d["rows_paired_bars"] + 1e-9)
+    # the harness's own last state: the two runs of the capture are one (on the forced case: the run without the force)
+    free = w["unforced"] if FU.forced(d) else w["states"][-1]
+    assert np.abs(free - d["u_last_harness"]).max() <= 1e-11 * np.abs(d["u_last_harness"]).max()
+
+
+@pytest.mark.parametrize("name", FU.FL)
+def test_the_fixture_tells_right_from_subtly_wrong(name):
+    """condition 3: every sensitivity number exceeds 1e-6 in every row or file it is formed for, and is the one the capture stored"""
+    d, w = FU.reference(name)
+    formed = {"own_gradient_force": bool(int(d["calc_force"][0])) * len(d["hist_iter"]), "own_gradient_vorticity": len(d["plot_iter"]),
+              "previous_state_row": len(d["plot_iter"]), "unforced_state": int(FU.forced(d)),
+              "spinup_zero_average": len(d["plot_iter"]) if PU.names_of(d, "average_fields") else 0}
+    for key in FU.SENSITIVITY:
+        got, stored = np.array(w["sens"][key]), d["sens_" + key]
+        print("%s %s: %s" % (name, key, np.array2string(got, precision=2)))
+        assert len(got) == len(stored) == formed[key], key
+        assert np.all(got > FU.MARGIN), key
+        assert np.all(np.abs(got - stored) <= 1e-6 * got), key
+
+
+@pytest.mark.parametrize("name", FU.FL)
+def test_a_changed_digit_is_noticed(name):
+    """a stored row changed in its 9th significant digit misses its bar: one value of every kind of row, the largest of its column
+    (history) or of its file's column (plot), multiplied by 1 + 1e-9"""
+    d, w = FU.reference(name)
+    n_dims, n_fields = int(d["sizes"][4]), int(d["sizes"][3])
+    bump = 1.0 + 1e-9
+    r = w["hist"][-1]
+    # residual columns are log10: the 9th digit of the printed value
+    res = d["hist_res"][-1].copy()
+    res[0] *= bump
+    assert HU.log_miss(r["res"], res) > 1.0
+    if "force" in r:
+        # (the bar is 1e-11 of the UN-CANCELLED scale: a column that cancels below 1e-2 of it keeps fewer than 9 digits at that bar)
+        frc = d["hist_force"][-1].copy()
+        i = int(np.argmax(np.abs(frc) / r["force_scale"]))
+        if abs(frc[i]) >= 1e-2 * r["force_scale"][i]:
+            frc[i] *= bump
+            assert HU.value_miss(r["force"], frc, r["force_scale"]) > 1.0
+    if "diag" in r:
+        dg = d["hist_diag"][-1].copy()
+        i = int(np.argmax(np.abs(dg)))
+        dg[i] *= bump
+        assert HU.value_miss(r["diag"], dg, np.abs(d["hist_diag"][-1]).max()) > 1.0
+    s = w["plot"][-1]
+    for col in range(len(s["scales"])):
+        rows = d["plot_rows"][-1][:, n_dims:].copy()
+        i = int(np.argmax(np.abs(rows[:, col])))
+        if abs(rows[i, col]) < 1e-2 * s["scales"][col]:
+            continue  # (a column whose values all lie far below its un-cancelled scale: the bar is of the scale, not of the digits)
+        rows[i, col] *= bump
+        assert PU.miss(s["rows"], rows, s["scales"])[col] > 1.0, col
+
+
+def test_the_controller_is_the_drivers():
+    """fl_hex_p2_forced: the lockstep controller meets the lines the driver printed before every step (8 digits) at 1e-7, with the
+    reference's hard-coded target and a force in every step; fl_hex_p2_channel is the same channel without the force"""
+    d, w = FU.reference("fl_hex_p2_forced")
+    drv = d["driver_controller"]
+    assert drv.shape == (FU.meta_of(d)["steps"], 5) and np.all(drv[:, 1] == HU.FORCING_MDOT0) and np.all(drv[:, 4] != 0)
+    tie = FU.controller_tie(d, w)
+    print("controller tie %.2e" % tie)
+    assert tie <= 1e-7
+    assert not FU.forced(FU.reference("fl_hex_p2_channel")[0])
+
+
+@pytest.mark.parametrize("name", FU.FL)
+def test_sampling_schedule(name):
+    """the rows the fixtures hold are the steps the library's own rules count, from clock 0 over the whole span and over every cut
+    of the span into two and three calls; the steps whose last stage runs call by call are the union of the monitors' samples that
+    read the gradient"""
+    d, _ = FU.reference(name)
+    n = FU.meta_of(d)["steps"]
+    freq, pf = int(d["monitor_res_freq"][0]), int(d["plot_freq"][0])
+    hist, plot = ROWS[name]
+    assert freq != pf
+    assert IU.sample_steps(0, n, freq) == hist and PU.sample_steps(0, n, pf) == plot
+    assert hfx.integral_monitor_samples(0, n, freq) == len(hist) and hfx.plot_monitor_samples(0, n, pf) == len(plot)
+    sched = FU.schedule(d)
+    assert [s + 1 for s, (h, p, c) in enumerate(sched) if h] == hist and [s + 1 for s, (h, p, c) in enumerate(sched) if p] == plot
+    assert [s + 1 for s, (h, p, c) in enumerate(sched) if c] == BY_CALLS[name]
+    for parts in (2, 3):
+        if parts > n:
+            continue
+        for cut in FU.cuts(n, parts):
+            assert sum(cut) == n and min(cut) >= 1
+            at, nh, npl = 0, 0, 0
+            for k in cut:
+                a, b = hfx.integral_monitor_samples(at, k, freq), hfx.plot_monitor_samples(at, k, pf)
+                assert a == len([s for s in hist if at < s <= at + k]), (cut, at)
+                assert b == len([s for s in plot if at < s <= at + k]), (cut, at)
+                nh, npl, at = nh + a, npl + b, at + k
+            assert (nh, npl) == (len(hist), len(plot)), cut
+    assert len(FU.cuts(7, 3)) == 15 and [2, 1, 4] in FU.cuts(7, 3)
+
+
+@pytest.mark.parametrize("name", FU.FL)
+def test_probes_are_located_and_expected(name):
+    """the 8 probes lie in the elements their positions were formed in, the operator rows reproduce a linear field exactly enough
+    (their sum is 1), and the expected samples fall on the steps the probe frequency gives"""
+    d, _ = FU.reference(name)
+    P = FU.probes(name)
+    assert P["opp"].shape == (int(d["sizes"][1]), FU.N_PROBES) and sorted(P["perm"]) == list(range(FU.N_PROBES))
+    assert np.all(np.abs(P["opp"].sum(axis=0) - 1.0) <= 1e-12)
+    steps, values = FU.expected_probes(name)
+    n = FU.meta_of(d)["steps"]
+    assert steps == [s for s in range(1, n + 1) if s % FU.PROBE_FREQ[name] == 0] and len(steps) >= 1
+    assert values.shape == (len(P["names"]), FU.N_PROBES, len(steps)) and np.all(np.isfinite(values))
+    if name == "fl_hex_p2_channel":
+        assert steps == [5]  # (behind a fused step between two steps that end call by call)
