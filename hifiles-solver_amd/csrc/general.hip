@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "general.hpp"
+#include "simplex2d.hpp"
 #include "face_kernels.hpp" // the pairwise kernels (face_delta_kernel<3>, gface_flux_multi_kernel are instantiated here)
 
 namespace hfx
@@ -57,6 +58,7 @@ struct GeneralData
 void general_invalidate(hfx_eles *e)
 {
   if (e && e->general) e->general->built = false;
+  simplex2d_invalidate(e);
 }
 
 void GeneralDelete::operator()(GeneralData *p) const { delete p; }
@@ -1121,13 +1123,15 @@ static int launch_element_kernels(int waves, hfx_eles *e, const GenArgs &a, cons
 }
 
 GeneralStage::GeneralStage(hfx_eles *const *eles_, int neb_, hfx_inters *const *faces_, int nfb_, int in_step_)
-    : eles(eles_), faces(faces_), neb(neb_), nfb(nfb_)
+    : eles(eles_), faces(faces_), neb(neb_), nfb(nfb_), simplex2d(neb_ == 1 && is_simplex2d(eles_[0])), in_step(in_step_)
 {
+  if (simplex2d) return;
   for (int i = 0; i < neb; i++) args.push_back(gen_args(eles[i], plans.emplace_back(general_plan(eles[i])), in_step_));
 }
 
 int GeneralStage::interior_ldg() const
 {
+  if (simplex2d) return simplex2d_interior_ldg(eles[0], faces, nfb);
   hfx_ctx *ctx = eles[0]->ctx;
   if (!ctx->params.viscous) return 0;
   auto gathers = [&](const hfx_eles *x) { return plans[std::find(eles, eles + neb - 1, x) - eles].gather; }; // (x is a block of the call)
@@ -1146,6 +1150,7 @@ int GeneralStage::interior_ldg() const
 
 int GeneralStage::flux_kernels() const
 {
+  if (simplex2d) return simplex2d_element_kernel(eles[0], in_step);
   for (int i = 0; i < neb; i++)
   {
     // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
@@ -1157,6 +1162,7 @@ int GeneralStage::flux_kernels() const
 
 int GeneralStage::common_fluxes() const
 {
+  if (simplex2d) return simplex2d_common_fluxes(eles[0], faces, nfb);
   hfx_ctx *ctx = eles[0]->ctx;
   const Phys P = ctx->phys();
   // boundary faces beside the interior ones: both need the flux kernels' results and write norm_tconf at disjoint points
@@ -1191,6 +1197,7 @@ int GeneralStage::common_fluxes() const
 
 int GeneralStage::update_kernels() const
 {
+  if (simplex2d) return simplex2d_update_kernel(eles[0], in_step);
   for (int i = 0; i < neb; i++)
     if (launch_element_kernels(plans[i].update_waves, eles[i], args[i], plans[i], false)) return 1;
   for (int i = 0; i < neb; i++) std::swap(eles[i]->arr[HFX_DISU_FPTS], eles[i]->general->disu_alt);
@@ -1215,6 +1222,9 @@ int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, in
     }
     HFX_CHECK(l && r, "face block %d refers to an element block that is not part of this call", b);
   }
+  // a two-dimensional block of a non-tensor class (triangles): the 2-D simplex stage's tables (one block, no partition faces)
+  for (int i = 0; i < neb; i++)
+    if (is_simplex2d(eles[i])) return simplex2d_prepare(eles, neb, faces, nfb);
   for (int i = 0; i < neb; i++)
   {
     GeneralData *g = eles[i]->general.get();
@@ -1340,6 +1350,11 @@ void general_kernel_bytes(hfx_eles *const *eles, int neb, double *bytes)
   for (int i = 0; i < neb; i++)
   {
     const hfx_eles *e = eles[i];
+    if (is_simplex2d(e))
+    {
+      simplex2d_kernel_bytes(e, bytes);
+      continue;
+    }
     const double nu = e->n_upts, nfp = e->n_fpts, nf = e->n_fields, nd = e->n_dims, ne = e->n_eles;
     bytes[0] += ne * (8.0 * (2 * nfp * nf) + 4.0 * nfp + nfp * 0.5);                                        // disu r, delta w, index + meta
     bytes[1] += ne * 8.0 * (nu * nf + nfp * nf + nu * (nd * nd + 1) + nfp * (nd * nd + 1) + nfp * nd + nfp * nf // u, delta, metrics, normals, disu r

@@ -92,6 +92,9 @@ struct GeneralStage
   int neb, nfb;
   std::vector<GeneralPlan> plans; // per element block, as
   std::vector<GenArgs> args;
+  // one two-dimensional simplex block (triangles): every step is simplex2d.hip's, plans and args stay empty
+  bool simplex2d = false;
+  int in_step = 0;
   GeneralStage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step);
   // viscous: boundary ghost states (-> inviscid common flux, LDG common solution); face_delta_kernel unless BOTH sides' plans `gather`
   int interior_ldg() const;

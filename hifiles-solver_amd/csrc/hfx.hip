@@ -8,6 +8,7 @@
 
 #include "split_common.hpp"
 #include "general.hpp"
+#include "simplex2d.hpp"
 #include "tensor_ops.hpp"
 #include "hfx_internal.hpp"
 #include "kernels_ops.hpp"
@@ -1908,7 +1909,10 @@ int hfx_time_general_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *
   HFX_CHECK(eles && neb > 0 && ms && names && reps > 0, "hfx_time_general_kernels: bad argument");
   HFX_IMMEDIATE(eles[0]->ctx, 0);
   HFX_CHECK(eles[0]->ctx->have_params, "parameters not set");
-  snprintf(names, 256, "face_delta_kernel,general_flux_kernel,gface_flux_multi_kernel,general_update_kernel");
+  if (neb == 1 && is_simplex2d(eles[0]))
+    snprintf(names, 256, "face_delta_kernel,simplex2d_element_kernel,face_flux2_kernel,simplex2d_update_kernel");
+  else
+    snprintf(names, 256, "face_delta_kernel,general_flux_kernel,gface_flux_multi_kernel,general_update_kernel");
   return general_time_kernels(eles, neb, faces, nfb, reps, ms);
 }
 

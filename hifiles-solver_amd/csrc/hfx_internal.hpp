@@ -20,10 +20,12 @@ namespace hfx
 void set_error(const char *fmt, ...);
 struct FusedData;
 struct GeneralData;
+struct Simplex2dData;
 struct TensorOps;
-// (the three are complete in their own translation units only: fused_hex.hip, general.hip, tensor_ops.hip)
+// (the four are complete in their own translation units only: fused_hex.hip, general.hip, simplex2d.hip, tensor_ops.hip)
 struct FusedDelete { void operator()(FusedData *p) const; };
 struct GeneralDelete { void operator()(GeneralData *p) const; };
+struct Simplex2dDelete { void operator()(Simplex2dData *p) const; };
 struct TensorOpsDelete { void operator()(TensorOps *p) const; };
 
 #define HFX_HIP(call)                                                                          \
@@ -488,6 +490,7 @@ struct hfx_eles
   // fused-path private data (built lazily)
   std::unique_ptr<hfx::FusedData, hfx::FusedDelete> fused;
   std::unique_ptr<hfx::GeneralData, hfx::GeneralDelete> general; // the general (non-tensor-product) fused stage (general.hip)
+  std::unique_ptr<hfx::Simplex2dData, hfx::Simplex2dDelete> simplex2d; // the 2-D simplex fused stage (simplex2d.hip)
   std::vector<hfx_inters *> faces_attached;
 };
 

@@ -1,0 +1,722 @@
+// simplex2d.hip -- the fused RK stage for TWO-DIMENSIONAL SIMPLEX blocks: triangles (eles_tris of the reference).
+//
+// Reference side: the same 17 calls of CalcResidual + AdvanceSolution as everywhere (src/solver.cpp:50-223); on triangles the seven
+// operators (built by src/eles_tris.cpp) are dense and SMALL -- P1..P5: 3, 6, 10, 15, 21 solution and 6, 9, 12, 15, 18 flux points.
+// The stage is cut where the general stage (general.hip) is cut and is at most four launches per stage:
+//
+//   face_delta_kernel<2>       thread per interior flux-point pair: LDG common solution -> delta_disu_fpts (only where the element
+//                              kernel does not gather the partner values itself)
+//   simplex2d_element_kernel   corrected gradient at the solution points (opp_4, opp_5), its extrapolation (opp_6), both point physics
+//                              blocks, the discontinuous divergence (opp_2) and normal flux (opp_1); leaves div_tdisf, norm_tdisf and
+//                              each side's viscous flux projected on its own normal (Fn, 4 doubles per flux point)
+//   face_flux2_kernel<2>       thread per pair: Riemann + LDG common flux from u and Fn of both sides -> norm_tconf; the boundary kernels
+//   simplex2d_update_kernel    opp_3 (norm_tconf - norm_tdisf), RK update, opp_0 of the new state
+//
+// Form: VECTOR, not matrix cores.  The general stage's batches of 16 elements on v_mfma_f64_16x16x4_f64 pad every operator to 16
+// rows: at P1 (3 and 6 rows) and P2 (6 and 9) most of a tile would be padding.  Here one lane owns one (element, operator row):
+// item q of a group is element q / n, row q % n -- the order of the arrays in memory, so every global load and store of a phase
+// is one contiguous run per field.  A group's state lies in LDS as [row][element][field] (all fields of a point in one 32- or
+// 64-byte read, the same address for the lanes of one element: a broadcast), the operators as the dense column-major matrices the
+// block registered (consecutive rows in consecutive lanes: conflict free).  A workgroup stages the operators once and walks groups
+// grid-stride.  Ordinary stores, no atomics but the NaN flag's: bit-reproducible from run to run.
+#include <algorithm>
+#include <type_traits>
+
+#include "simplex2d.hpp"
+#include "face_kernels.hpp" // the pairwise kernels (face_delta_kernel<2>, face_flux2_kernel<2, RS> are instantiated here too)
+
+namespace hfx
+{
+
+struct Simplex2dData
+{
+  DevBuf<double> element_ops, update_ops; // the operators one behind the other, in the kernels' order (zeros where inviscid)
+  DevBuf<unsigned char> meta;             // (n_fpts, n_eles): bit1 beta sign flipped (LEFT point of a pair), bit2 boundary point
+  DevBuf<int> nbr;                        // (n_fpts, n_eles) partner word of every flux point (S2dArgs::nbr)
+  DevBuf<double> disu_alt;                // second disu_fpts buffer (the update kernel writes the new state's flux-point solution)
+  DevBuf<double> fn_fpts;                 // (n_fpts, n_eles, n_fields) viscous flux projected on the point's own normal
+  bool any_bdy = false, any_int = false;
+  bool built = false;
+};
+
+void Simplex2dDelete::operator()(Simplex2dData *p) const { delete p; }
+
+void simplex2d_invalidate(hfx_eles *e)
+{
+  if (e && e->simplex2d) e->simplex2d->built = false;
+}
+
+struct S2dArgs
+{
+  int n_eles, n_groups;
+  const double *ops;
+  const double *u0, *delta, *disu;
+  // the LDG correction of an interior flux point is formed in the element kernel from the partner's flux-point solution:
+  // (partner offset << 4) | beta sign flipped << 1 | this point is the right side; -1: a boundary point (its correction is in
+  // `delta`).  NULL: `delta` holds all of them.
+  const int *nbr;
+  const double *detjac_upts, *JGinv_upts, *detjac_fpts, *JGinv_fpts, *norm_fpts;
+  const unsigned char *meta;
+  double *div, *ntd, *fn, *grad_fpts; // grad_fpts: boundary points only (NULL: no boundary faces / inviscid)
+  Phys P;
+  // update kernel
+  double *u0w, *u1;
+  const double *tconf, *src, *dt_local;
+  double *disu_next;
+  unsigned long long *nan_flag;
+  int adv_type, in_step, dt_local_on, write_div, need_u1;
+  double dt, rk_a, rk_b;
+};
+
+constexpr int S2D_NF = 4, S2D_ND = 2, S2D_T = 64 * SIMPLEX2D_WAVES;
+
+// g_phys(d) = sum_l (inv_detjac * g_ref(l)) * JGinv(l,d)   (BLAS=NO branch of src/eles.cpp:1975-1979)
+__device__ __forceinline__ void s2d_to_physical(const double inv_detjac, const double (&JG)[4], const double (&tg)[2], double (&cg)[2])
+{
+#pragma unroll
+  for (int d = 0; d < 2; d++) cg[d] = 0.0;
+#pragma unroll
+  for (int l = 0; l < 2; l++)
+  {
+    const double temp = inv_detjac * tg[l];
+#pragma unroll
+    for (int d = 0; d < 2; d++) cg[d] += temp * JG[l + 2 * d];
+  }
+}
+
+__device__ __forceinline__ void s2d_stage_ops(double *dst, const double *src, int n, int tid)
+{
+  for (int q = tid; q < n; q += S2D_T) dst[q] = src[q];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// element kernel
+// ---------------------------------------------------------------------------------------------------------------
+template <int NU, int NFP, int G>
+__global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArgs a)
+{
+  constexpr int NF = S2D_NF, ND = S2D_ND, T = S2D_T, GP = G + 1, NC = NF * ND;
+  extern __shared__ double lds[];
+  // operators, dense column-major as registered
+  double *o4 = lds;                     // [2][NU x NU]
+  double *o5 = o4 + 2 * NU * NU;        // [2][NU x NFP]
+  double *o6 = o5 + 2 * NU * NFP;       // NFP x NU
+  double *o0 = o6 + NFP * NU;           // NFP x NU
+  double *o2 = o0 + NFP * NU;           // [2][NU x NU]
+  double *o1 = o2 + 2 * NU * NU;        // [2][NFP x NU]
+  double *U = o1 + 2 * NFP * NU;        // [NU][GP][NF]   the state
+  double *D = U + NU * GP * NF;         // [NFP][GP][NF]  delta_disu_fpts
+  double *Gr = D + NFP * GP * NF;       // [NU][GP][NC]   reference-space gradient, then the transformed total flux; c = field + NF * dim
+  static_assert(simplex2d_element_lds_bytes(NU, NFP, G) == sizeof(double) * (simplex2d_element_ops(NU, NFP) + (size_t)GP * (NU * NF + NFP * NF + NU * NC)), "LDS image");
+  const int tid = threadIdx.x;
+  const bool visc = a.P.viscous != 0;
+  const long plane_u = (long)NU * a.n_eles, plane_f = (long)NFP * a.n_eles;
+  s2d_stage_ops(lds, a.ops, (int)simplex2d_element_ops(NU, NFP), tid);
+
+  for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x)
+  {
+    const long e0 = (long)grp * G;
+    const int nval = (int)min((long)G, a.n_eles - e0);
+    const int items_u = NU * nval, items_f = NFP * nval; // (a last partial group: its elements alone; nothing is read or written past them)
+
+    // ---- P0: the state and the LDG corrections of the group -> [row][element][field]
+    for (int q = tid; q < items_u; q += T)
+    {
+      const int el = q / NU, k = q - el * NU;
+      double r[NF];
+#pragma unroll
+      for (int f = 0; f < NF; f++) r[f] = a.u0[e0 * NU + q + f * plane_u];
+#pragma unroll
+      for (int f = 0; f < NF; f++) U[(k * GP + el) * NF + f] = r[f];
+    }
+    if (visc)
+      for (int q = tid; q < items_f; q += T)
+      {
+        const int el = q / NFP, j = q - el * NFP;
+        const long o = e0 * NFP + q;
+        double r[NF];
+        if (a.nbr == nullptr)
+        {
+#pragma unroll
+          for (int f = 0; f < NF; f++) r[f] = a.delta[o + f * plane_f];
+        }
+        else
+        {
+          // delta = u_common - u_own, u_common = (u_L + u_R)/2 - beta (u_L - u_R) on the pair's orientation (src/inters.cpp:637)
+          const int w = a.nbr[o];
+          const double *pp = (w < 0) ? a.delta + o : a.disu + (w >> 4);
+          double own[NF], oth[NF];
+#pragma unroll
+          for (int f = 0; f < NF; f++)
+          {
+            own[f] = a.disu[o + f * plane_f];
+            oth[f] = pp[f * plane_f];
+          }
+          const double beta = ldg_beta(w, a.P);
+#pragma unroll
+          for (int f = 0; f < NF; f++)
+          {
+            const double ul = (w & 1) ? oth[f] : own[f], ur = (w & 1) ? own[f] : oth[f];
+            const double uc = 0.5 * (ul + ur) - beta * (ul - ur);
+            r[f] = (w < 0) ? oth[f] : uc - own[f];
+          }
+        }
+#pragma unroll
+        for (int f = 0; f < NF; f++) D[(j * GP + el) * NF + f] = r[f];
+      }
+    __syncthreads();
+
+    if (visc)
+    {
+      // ---- P1: reference-space corrected gradient at the solution points (calculate_gradient + first half of correct_gradient,
+      //          src/eles.cpp:1823,1900): Gr(f,d) = opp_4[d] U(f) + opp_5[d] D(f)
+      for (int q = tid; q < items_u; q += T)
+      {
+        const int el = q / NU, i = q - el * NU;
+        double acc[NC];
+#pragma unroll
+        for (int c = 0; c < NC; c++) acc[c] = 0.0;
+#pragma unroll 2
+        for (int k = 0; k < NU; k++)
+        {
+          const double m0 = o4[i + NU * k], m1 = o4[NU * NU + i + NU * k];
+#pragma unroll
+          for (int f = 0; f < NF; f++)
+          {
+            const double u = U[(k * GP + el) * NF + f];
+            acc[f] += m0 * u;
+            acc[f + NF] += m1 * u;
+          }
+        }
+#pragma unroll 2
+        for (int j = 0; j < NFP; j++)
+        {
+          const double m0 = o5[i + NU * j], m1 = o5[NU * NFP + i + NU * j];
+#pragma unroll
+          for (int f = 0; f < NF; f++)
+          {
+            const double dl = D[(j * GP + el) * NF + f];
+            acc[f] += m0 * dl;
+            acc[f + NF] += m1 * dl;
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < NC; c++) Gr[(i * GP + el) * NC + c] = acc[c];
+      }
+      __syncthreads();
+
+      // ---- P2: gradient at the flux points (second half of correct_gradient: opp_6, then the transform with the flux points' own
+      //          metrics, src/eles.cpp:1930,1998) and the viscous flux there, projected on the point's normal
+      for (int q = tid; q < items_f; q += T)
+      {
+        const int el = q / NFP, j = q - el * NFP;
+        const long o = e0 * NFP + q;
+        double JG[4], n[ND];
+#pragma unroll
+        for (int c = 0; c < 4; c++) JG[c] = a.JGinv_fpts[o * 4 + c];
+        const double dj = a.detjac_fpts[o];
+#pragma unroll
+        for (int m = 0; m < ND; m++) n[m] = a.norm_fpts[o + m * plane_f];
+        const bool bdy = a.grad_fpts != nullptr && (a.meta[o] & 4);
+        double acc[NC], u[NF];
+#pragma unroll
+        for (int c = 0; c < NC; c++) acc[c] = 0.0;
+#pragma unroll
+        for (int f = 0; f < NF; f++) u[f] = 0.0;
+#pragma unroll 2
+        for (int k = 0; k < NU; k++)
+        {
+          const double m6 = o6[j + NFP * k], m0 = o0[j + NFP * k];
+#pragma unroll
+          for (int c = 0; c < NC; c++) acc[c] += m6 * Gr[(k * GP + el) * NC + c];
+#pragma unroll
+          for (int f = 0; f < NF; f++) u[f] += m0 * U[(k * GP + el) * NF + f];
+        }
+        double g[NC], fv[NC];
+        const double idj = 1.0 / dj;
+#pragma unroll
+        for (int f = 0; f < NF; f++)
+        {
+          const double tg[ND] = {acc[f], acc[f + NF]};
+          double cg[ND];
+          s2d_to_physical(idj, JG, tg, cg);
+#pragma unroll
+          for (int d = 0; d < ND; d++) g[f + NF * d] = cg[d];
+        }
+        if (bdy) // boundary point: the boundary kernel reads the gradient
+#pragma unroll
+          for (int c = 0; c < NC; c++) a.grad_fpts[o + c * plane_f] = g[c];
+        calc_visf<ND, true>(a.P, u, g, fv);
+#pragma unroll
+        for (int f = 0; f < NF; f++)
+        {
+          double s = 0.0;
+#pragma unroll
+          for (int m = 0; m < ND; m++) s += fv[f + NF * m] * n[m];
+          a.fn[o + f * plane_f] = s;
+        }
+      }
+      __syncthreads();
+    }
+
+    // ---- P3: point physics at the solution points (evaluate_invFlux, the transform of correct_gradient, evaluate_viscFlux;
+    //          src/eles.cpp:1415,1973,2285): Gr(f,d) <- transformed total flux
+    for (int q = tid; q < items_u; q += T)
+    {
+      const int el = q / NU, i = q - el * NU;
+      const long o = e0 * NU + q;
+      double JG[4];
+#pragma unroll
+      for (int c = 0; c < 4; c++) JG[c] = a.JGinv_upts[o * 4 + c];
+      const double dj = visc ? a.detjac_upts[o] : 1.0;
+      double u[NF], F[NC];
+#pragma unroll
+      for (int f = 0; f < NF; f++) u[f] = U[(i * GP + el) * NF + f];
+      calc_invf<ND, true>(a.P.gamma, u, F);
+      if (visc)
+      {
+        const double idj = 1.0 / dj;
+        double g[NC], fv[NC];
+#pragma unroll
+        for (int f = 0; f < NF; f++)
+        {
+          const double tg[ND] = {Gr[(i * GP + el) * NC + f], Gr[(i * GP + el) * NC + f + NF]};
+          double cg[ND];
+          s2d_to_physical(idj, JG, tg, cg);
+#pragma unroll
+          for (int d = 0; d < ND; d++) g[f + NF * d] = cg[d];
+        }
+        calc_visf<ND, true>(a.P, u, g, fv);
+#pragma unroll
+        for (int c = 0; c < NC; c++) F[c] += fv[c];
+      }
+#pragma unroll
+      for (int f = 0; f < NF; f++)
+#pragma unroll
+        for (int l = 0; l < ND; l++)
+        {
+          double t = 0.0;
+#pragma unroll
+          for (int m = 0; m < ND; m++) t += JG[l + ND * m] * F[f + NF * m];
+          Gr[(i * GP + el) * NC + f + NF * l] = t;
+        }
+    }
+    __syncthreads();
+
+    // ---- P4: discontinuous divergence (opp_2) and normal flux at the flux points (opp_1), summed over the dimensions
+    //          (calculate_divergence, extrapolate_totalFlux; src/eles.cpp:1651,1549)
+    for (int q = tid; q < items_u + items_f; q += T)
+    {
+      const bool is_div = q < items_u;
+      const int qq = is_div ? q : q - items_u, n = is_div ? NU : NFP;
+      const int el = qq / n, r = qq - el * n;
+      const double *op = is_div ? o2 : o1;
+      double acc[NF];
+#pragma unroll
+      for (int f = 0; f < NF; f++) acc[f] = 0.0;
+#pragma unroll 2
+      for (int k = 0; k < NU; k++)
+      {
+        const double m0 = op[r + n * k], m1 = op[n * NU + r + n * k];
+#pragma unroll
+        for (int f = 0; f < NF; f++) acc[f] += m0 * Gr[(k * GP + el) * NC + f] + m1 * Gr[(k * GP + el) * NC + f + NF];
+      }
+      double *out = is_div ? a.div + e0 * NU + qq : a.ntd + e0 * NFP + qq;
+      const long plane = is_div ? plane_u : plane_f;
+#pragma unroll
+      for (int f = 0; f < NF; f++) out[f * plane] = acc[f];
+    }
+    // (the next group's P0 writes U and D, which P4 does not read; its P1 writes Gr behind a barrier every thread has passed)
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// update kernel: div_tdisf + opp_3 (norm_tconf - norm_tdisf) -> RK update -> disu_fpts of the new state
+// (calculate_corrected_divergence, AdvanceSolution, extrapolate_solution; src/eles.cpp:1738,1080,1360); as general_update_kernel
+// ---------------------------------------------------------------------------------------------------------------
+template <int NU, int NFP, int G>
+__global__ __launch_bounds__(S2D_T) void simplex2d_update_kernel_t(const S2dArgs a)
+{
+  constexpr int NF = S2D_NF, T = S2D_T, GP = G + 1;
+  extern __shared__ double lds[];
+  double *o3 = lds;              // NU x NFP
+  double *o0 = o3 + NU * NFP;    // NFP x NU
+  double *X = o0 + NFP * NU;     // [NFP][GP][NF]  norm_tconf - norm_tdisf
+  double *S = X + NFP * GP * NF; // [NU][GP][NF]   the new state
+  const int tid = threadIdx.x;
+  const long plane_u = (long)NU * a.n_eles, plane_f = (long)NFP * a.n_eles;
+  s2d_stage_ops(lds, a.ops, (int)simplex2d_update_ops(NU, NFP), tid);
+
+  for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x)
+  {
+    const long e0 = (long)grp * G;
+    const int nval = (int)min((long)G, a.n_eles - e0);
+    const int items_u = NU * nval, items_f = NFP * nval;
+    for (int q = tid; q < items_f; q += T)
+    {
+      const int el = q / NFP, j = q - el * NFP;
+      const long o = e0 * NFP + q;
+      double r[NF];
+#pragma unroll
+      for (int f = 0; f < NF; f++) r[f] = a.tconf[o + f * plane_f] + -1.0 * a.ntd[o + f * plane_f]; // the daxpy of src/eles.cpp:1746
+#pragma unroll
+      for (int f = 0; f < NF; f++) X[(j * GP + el) * NF + f] = r[f];
+    }
+    __syncthreads();
+    for (int q = tid; q < items_u; q += T)
+    {
+      const int el = q / NU, i = q - el * NU;
+      const long p = e0 * NU + q;
+      // the update's inputs are requested before the contraction
+      const double dj = a.detjac_upts[p];
+      const double dt = a.dt_local_on ? a.dt_local[e0 + el] : a.dt;
+      double dvin[NF], un[NF], u1v[NF], sv[NF];
+#pragma unroll
+      for (int f = 0; f < NF; f++)
+      {
+        const long ok = p + f * plane_u;
+        dvin[f] = a.div[ok];
+        un[f] = a.u0w[ok];
+        u1v[f] = a.need_u1 ? a.u1[ok] : 0.0;
+        sv[f] = a.src ? a.src[ok] : 0.0;
+      }
+      double acc[NF];
+#pragma unroll
+      for (int f = 0; f < NF; f++) acc[f] = 0.0;
+#pragma unroll 2
+      for (int j = 0; j < NFP; j++)
+      {
+        const double m = o3[i + NU * j];
+#pragma unroll
+        for (int f = 0; f < NF; f++) acc[f] += m * X[(j * GP + el) * NF + f];
+      }
+#pragma unroll
+      for (int f = 0; f < NF; f++)
+      {
+        const long ok = p + f * plane_u;
+        const double dv = dvin[f] + acc[f];
+        if (dv != dv) atomicMin(a.nan_flag, (unsigned long long)ok);
+        if (a.write_div) a.div[ok] = dv;
+        const double s = sv[f];
+        const double dd = dv / dj;
+        double u = un[f];
+        if (a.adv_type == 0)
+          u -= dt * (dd - s);
+        else if (a.adv_type == 1)
+        {
+          if (a.in_step == 0) a.u1[ok] = u;
+          if (a.in_step < 3)
+            u -= dt / 3.0 * (dd - s);
+          else
+          {
+            const double rhs = -dd + s;
+            u = 3.0 / 4.0 * u + 1.0 / 4.0 * u1v[f] + dt / 4.0 * rhs;
+          }
+        }
+        else if (a.adv_type == 2)
+        {
+          if (a.in_step == 0) a.u1[ok] = u;
+          if (a.in_step < 2 || a.in_step == 3)
+            u -= dt / 2.0 * (dd - s);
+          else if (a.in_step == 2)
+          {
+            const double rhs = -dd + s;
+            u = 1.0 / 3.0 * u + 2.0 / 3.0 * u1v[f] + dt / 6.0 * rhs;
+          }
+        }
+        else
+        {
+          const double rhs = -dd + s;
+          const double r1 = a.rk_a * u1v[f] + dt * rhs;
+          a.u1[ok] = r1;
+          u += a.rk_b * r1;
+        }
+        a.u0w[ok] = u;
+        S[(i * GP + el) * NF + f] = u;
+      }
+    }
+    __syncthreads();
+    for (int q = tid; q < items_f; q += T)
+    {
+      const int el = q / NFP, j = q - el * NFP;
+      double acc[NF];
+#pragma unroll
+      for (int f = 0; f < NF; f++) acc[f] = 0.0;
+#pragma unroll 2
+      for (int k = 0; k < NU; k++)
+      {
+        const double m = o0[j + NFP * k];
+#pragma unroll
+        for (int f = 0; f < NF; f++) acc[f] += m * S[(k * GP + el) * NF + f];
+      }
+#pragma unroll
+      for (int f = 0; f < NF; f++) a.disu_next[e0 * NFP + q + f * plane_f] = acc[f];
+    }
+    // (the next group's staging writes X, which the opp_0 pass does not read; its opp_3 pass writes S behind a barrier)
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+static int simplex2d_size_class(const hfx_eles *e)
+{
+  for (int i = 0; i < N_SIMPLEX2D_SIZES; i++)
+    if (e->n_upts == SIMPLEX2D_SIZES[i][0] && e->n_fpts == SIMPLEX2D_SIZES[i][1]) return i;
+  return -1;
+}
+
+// the operators of `list` one behind the other, each dense column-major as registered; an operator the run does not have: zeros
+static int packed_operators(DevBuf<double> &dst, std::initializer_list<const Operator *> list, std::initializer_list<size_t> sizes)
+{
+  std::vector<double> h;
+  auto sz = sizes.begin();
+  for (const Operator *op : list)
+  {
+    const size_t n = *sz++, at = h.size();
+    h.resize(at + n, 0.0);
+    if (!op->present()) continue;
+    HFX_CHECK((size_t)op->m * op->k == n, "2-D simplex fused stage: an operator of %d x %d where %zu entries are expected", op->m, op->k, n);
+    HFX_HIP(hipMemcpy(h.data() + at, op->dense, sizeof(double) * n, hipMemcpyDeviceToHost));
+  }
+  return dst.upload(h);
+}
+
+static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
+{
+  HFX_CHECK(e->n_fields == 4, "2-D simplex fused stage: Navier-Stokes / Euler blocks only; run per method (fused 0)");
+  HFX_CHECK(simplex2d_size_class(e) >= 0, "2-D simplex fused stage: built for triangles of orders 1..5 (%d solution, %d flux points); run per method (fused 0)",
+            e->n_upts, e->n_fpts);
+  HFX_CHECK(!e->les_ready, "2-D simplex fused stage: a registered LES closure runs per method (fused 0)");
+  HFX_CHECK(!e->over_int_ready, "2-D simplex fused stage: registered over-integration runs per method (fused 0)");
+  HFX_CHECK(!e->shock_ready, "2-D simplex fused stage: registered shock capturing runs per method (fused 0)");
+  const bool visc = e->ctx->params.viscous != 0;
+  HFX_CHECK(!visc || e->viscous_ops, "2-D simplex fused stage: viscous run but the block has no opp_4/5/6");
+  for (const Operator *op : {&e->opp_0, &e->opp_3, &e->opp_1[0], &e->opp_1[1], &e->opp_2[0], &e->opp_2[1]})
+    HFX_CHECK(op->present(), "2-D simplex fused stage: an operator is missing");
+  if (!e->simplex2d) e->simplex2d.reset(new Simplex2dData());
+  Simplex2dData *g = e->simplex2d.get();
+  const size_t nu = e->n_upts, nfp = e->n_fpts;
+  if (packed_operators(g->element_ops, {&e->opp_4[0], &e->opp_4[1], &e->opp_5[0], &e->opp_5[1], &e->opp_6, &e->opp_0, &e->opp_2[0], &e->opp_2[1], &e->opp_1[0], &e->opp_1[1]},
+                       {nu * nu, nu * nu, nu * nfp, nu * nfp, nfp * nu, nfp * nu, nu * nu, nu * nu, nfp * nu, nfp * nu}))
+    return 1;
+  if (packed_operators(g->update_ops, {&e->opp_3, &e->opp_0}, {nu * nfp, nfp * nu})) return 1;
+  // per flux point: the LDG switch of the pair it is the LEFT point of (exact tests on the left normal, decided once), whether a
+  // boundary face owns it, and its partner word; every flux point must belong to exactly one registered face
+  const long plane_f = (long)nfp * e->n_eles;
+  HFX_CHECK(plane_f < (1L << 27), "2-D simplex fused stage: %ld flux points do not fit a partner word", plane_f);
+  std::vector<unsigned char> meta(plane_f, 0);
+  std::vector<char> owned(plane_f, 0);
+  std::vector<int> nbr(plane_f, -1);
+  std::vector<double> norm((size_t)plane_f * 2);
+  HFX_HIP(hipMemcpy(norm.data(), e->norm_fpts, sizeof(double) * norm.size(), hipMemcpyDeviceToHost));
+  g->any_bdy = g->any_int = false;
+  for (int b = 0; b < nfb; b++)
+  {
+    hfx_inters *f = faces[b];
+    if (f->is_bdy)
+    {
+      g->any_bdy = g->any_bdy || f->n_inters > 0;
+      for (int o : f->hL) { meta[o] |= 4; owned[o]++; }
+      continue;
+    }
+    const long np = (long)f->n_inters * f->n_fpts_per_inter;
+    for (long q = 0; q < np; q++)
+    {
+      const int il = f->hL[q], ir = f->hR[q];
+      owned[il]++; owned[ir]++;
+      const double n[2] = {norm[il], norm[il + plane_f]};
+      const int flip = ldg_switch<2>(1.0, n) < 0 ? 2 : 0;
+      meta[il] |= flip;
+      nbr[il] = (ir << 4) | flip;
+      nbr[ir] = (il << 4) | flip | 1;
+      g->any_int = true;
+    }
+  }
+  for (long o = 0; o < plane_f; o++) HFX_CHECK(owned[o] == 1, "2-D simplex fused stage: flux point %ld belongs to %d registered faces", o, (int)owned[o]);
+  if (g->meta.upload(meta) || g->nbr.upload(nbr)) return 1;
+  if (g->disu_alt.ensure((size_t)plane_f * e->n_fields) || g->fn_fpts.ensure((size_t)plane_f * e->n_fields)) return 1;
+  g->built = true;
+  return 0;
+}
+
+int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb)
+{
+  HFX_CHECK(neb == 1, "2-D simplex fused stage: several element blocks of which one is two-dimensional (a mixed quadrilateral / triangle "
+                      "mesh) run per method (fused 0)");
+  hfx_eles *e = eles[0];
+  HFX_CHECK(e->n_eles > 0, "2-D simplex fused stage: empty element block");
+  for (int b = 0; b < nfb; b++)
+    HFX_CHECK(!faces[b]->is_mpi, "2-D simplex fused stage: partition faces on a triangle block run per method (fused 0)");
+  for (int b = 0; b < nfb; b++)
+    HFX_CHECK(faces[b]->left == e && (faces[b]->right == nullptr || faces[b]->right == e), "face block %d refers to an element block that is not part of this call", b);
+  // (what refuses a block is asked every time: a closure registered, or a context made viscous, behind the first stage must not
+  // run on the tables of the stage before)
+  HFX_CHECK(!e->ctx->params.viscous || e->viscous_ops, "2-D simplex fused stage: viscous run but the block has no opp_4/5/6");
+  if (e->simplex2d && e->simplex2d->built && !e->les_ready && !e->over_int_ready && !e->shock_ready) return 0;
+  return simplex2d_build(e, faces, nfb);
+}
+
+Simplex2dPlan simplex2d_plan(const hfx_eles *e)
+{
+  Simplex2dPlan pl;
+  pl.size_class = simplex2d_size_class(e);
+  if (pl.size_class < 0) return pl;
+  const int *s = SIMPLEX2D_SIZES[pl.size_class];
+  pl.group = s[2];
+  pl.gather = e->ctx->opt.gather_delta && e->ctx->params.viscous && e->simplex2d && e->simplex2d->any_int;
+  pl.element_lds = simplex2d_element_lds_bytes(s[0], s[1], s[2]);
+  pl.update_lds = simplex2d_update_lds_bytes(s[0], s[1], s[2]);
+  return pl;
+}
+
+static S2dArgs s2d_args(hfx_eles *e, const Simplex2dPlan &pl, int in_step)
+{
+  Simplex2dData *g = e->simplex2d.get();
+  const hfx_params &p = e->ctx->params;
+  S2dArgs a{};
+  a.n_eles = e->n_eles; a.n_groups = (e->n_eles + pl.group - 1) / pl.group;
+  a.u0 = e->arr[HFX_DISU_UPTS0]; a.delta = e->arr[HFX_DELTA_DISU_FPTS]; a.disu = e->arr[HFX_DISU_FPTS];
+  a.nbr = pl.gather ? g->nbr.get() : nullptr;
+  a.detjac_upts = e->detjac_upts; a.JGinv_upts = e->JGinv_upts; a.detjac_fpts = e->detjac_fpts; a.JGinv_fpts = e->JGinv_fpts;
+  a.norm_fpts = e->norm_fpts; a.meta = g->meta;
+  a.div = e->arr[HFX_DIV_TCONF_UPTS]; a.ntd = e->arr[HFX_NORM_TDISF_FPTS]; a.fn = g->fn_fpts;
+  a.grad_fpts = (g->any_bdy && p.viscous) ? e->arr[HFX_GRAD_DISU_FPTS].get() : nullptr;
+  a.P = e->ctx->phys();
+  a.u0w = e->arr[HFX_DISU_UPTS0]; a.u1 = e->arr[HFX_DISU_UPTS1];
+  a.tconf = e->arr[HFX_NORM_TCONF_FPTS];
+  a.src = e->src_nonzero ? e->arr[HFX_SRC_UPTS].get() : nullptr;
+  a.dt_local = e->arr[HFX_DT_LOCAL];
+  a.disu_next = g->disu_alt;
+  a.nan_flag = e->nan_flag;
+  a.adv_type = p.adv_type; a.in_step = in_step; a.dt_local_on = p.dt_type == 2; a.dt = p.dt;
+  a.rk_a = (p.adv_type >= 3) ? p.RK_a[in_step] : 0.0;
+  a.rk_b = (p.adv_type >= 3) ? p.RK_b[in_step] : 0.0;
+  // (low-storage schemes: a stage whose RK_a is 0.0 -- the first of a step -- takes 0.0 for the register instead of reading it)
+  a.need_u1 = (p.adv_type >= 3 && a.rk_a != 0.0) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
+  a.write_div = 1; // the element kernel left the discontinuous part there: always complete it (the monitors read it)
+  return a;
+}
+
+// the instantiation of the plan's size class (SIMPLEX2D_SIZES[I], I counting up)
+template <int I = 0>
+static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool element)
+{
+  if constexpr (I == N_SIMPLEX2D_SIZES)
+  {
+    HFX_CHECK(false, "2-D simplex fused stage: no kernel for this element size");
+    return 1;
+  }
+  else
+  {
+    if (pl.size_class != I) return launch_s2d<I + 1>(e, a, pl, element);
+    constexpr int NU = SIMPLEX2D_SIZES[I][0], NFP = SIMPLEX2D_SIZES[I][1], G = SIMPLEX2D_SIZES[I][2];
+    const size_t lds = element ? pl.element_lds : pl.update_lds;
+    a.ops = element ? e->simplex2d->element_ops : e->simplex2d->update_ops;
+    // as many workgroups as are resident (LDS; at most 8 of four waves), walking the groups grid-stride
+    const long per_cu = std::max<long>(1, std::min<long>(8, (long)(160 * 1024 / lds)));
+    const int grid = persistent_grid(e, element ? SLOT_ELEMENT : SLOT_UPDATE, a.n_groups, std::min<long>(a.n_groups, per_cu * e->ctx->n_cu));
+    auto launch = [&](auto kernel) -> int {
+      if (lds > 48 * 1024) HFX_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(S2D_T), lds, e->ctx->stream, a);
+      HFX_HIP(hipGetLastError());
+      return 0;
+    };
+    return element ? launch(simplex2d_element_kernel_t<NU, NFP, G>) : launch(simplex2d_update_kernel_t<NU, NFP, G>);
+  }
+}
+
+// the pairs of an interior-face block of the one element block
+static FacePairArgs s2d_face_args(hfx_inters *f)
+{
+  hfx_eles *x = f->left;
+  FaceSide s{};
+  s.plane = (long)x->n_fpts * x->n_eles;
+  s.disu = x->arr[HFX_DISU_FPTS]; s.fn = x->simplex2d->fn_fpts; s.tdA = x->tdA_fpts;
+  s.delta = x->arr[HFX_DELTA_DISU_FPTS]; s.tconf = x->arr[HFX_NORM_TCONF_FPTS];
+  FacePairArgs a{};
+  a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
+  a.L = f->L; a.R = f->R; a.meta = x->simplex2d->meta; a.norm = x->norm_fpts;
+  a.l = s; a.r = s;
+  return a;
+}
+
+int simplex2d_interior_ldg(hfx_eles *e, hfx_inters *const *faces, int nfb)
+{
+  hfx_ctx *ctx = e->ctx;
+  if (!ctx->params.viscous) return 0;
+  const bool gather = simplex2d_plan(e).gather;
+  for (int b = 0; b < nfb; b++)
+  {
+    if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], 0, 1)) return 1; // ghost state -> inviscid common flux, LDG common solution
+    if (faces[b]->is_bdy || gather) continue;
+    const FacePairArgs a = s2d_face_args(faces[b]);
+    if (a.npairs == 0) continue;
+    hipLaunchKernelGGL(face_delta_kernel<2>, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, ctx->stream, a, ctx->phys());
+  }
+  HFX_HIP(hipGetLastError());
+  return 0;
+}
+
+int simplex2d_element_kernel(hfx_eles *e, int in_step)
+{
+  const Simplex2dPlan pl = simplex2d_plan(e);
+  return launch_s2d(e, s2d_args(e, pl, in_step), pl, true);
+}
+
+int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb)
+{
+  hfx_ctx *ctx = e->ctx;
+  const Phys P = ctx->phys();
+  // (an inviscid run: the boundary faces' one sweep, which the viscous run launched before the element kernel)
+  for (int b = 0; b < nfb; b++)
+    if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], P.viscous ? 1 : 0, 1)) return 1;
+  for (int b = 0; b < nfb; b++)
+  {
+    if (faces[b]->is_bdy) continue;
+    const FacePairArgs a = s2d_face_args(faces[b]);
+    if (a.npairs == 0) continue;
+    const FaceBlockArgs blk(a);
+    with_riemann_solver(P.riemann, [&](auto RS) {
+      hipLaunchKernelGGL((face_flux2_kernel<2, decltype(RS)::value>), dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, ctx->stream, blk, P);
+    });
+  }
+  HFX_HIP(hipGetLastError());
+  return 0;
+}
+
+int simplex2d_update_kernel(hfx_eles *e, int in_step)
+{
+  const Simplex2dPlan pl = simplex2d_plan(e);
+  if (launch_s2d(e, s2d_args(e, pl, in_step), pl, false)) return 1;
+  std::swap(e->arr[HFX_DISU_FPTS], e->simplex2d->disu_alt);
+  return 0;
+}
+
+// ALGORITHMIC HBM bytes per launch of the four steps (doubles listed per element), priced from the plan
+void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes)
+{
+  const double nu = e->n_upts, nfp = e->n_fpts, nf = e->n_fields, nd = e->n_dims, ne = e->n_eles;
+  const bool visc = e->ctx->params.viscous != 0;
+  const Simplex2dPlan pl = simplex2d_plan(e);
+  if (visc && !pl.gather) bytes[0] += ne * (8.0 * (2 * nfp * nf) + 4.0 * nfp + nfp * 0.5); // disu r, delta w, index + meta
+  // u, metrics at the solution points r; div, norm_tdisf w
+  bytes[1] += ne * 8.0 * (nu * nf + nu * nd * nd + nu * nf + nfp * nf);
+  // viscous: delta (or the partner's disu and the own, and a partner word), detjac at both point sets, the flux points' metrics and normals r; Fn w
+  if (visc) bytes[1] += ne * (8.0 * ((pl.gather ? 2 : 1) * nfp * nf + nu + nfp * (nd * nd + 1) + nfp * nd + nfp * nf) + (pl.gather ? 4.0 * nfp : 0.0));
+  bytes[2] += ne * (8.0 * (nfp * nf + (visc ? nfp * nf : 0.0) + 0.5 * nfp * nd + nfp + nfp * nf) + 4.0 * nfp); // disu, Fn, normal(left), tdA r; tconf w
+  bytes[3] += ne * 8.0 * (3 * nu * nf + nu + 2 * nfp * nf + 3 * nu * nf + nfp * nf);                          // u0,u1,div,detjac,tconf,ntd r; u0,u1,div,disu w
+}
+
+} // namespace hfx
+
+extern "C" int hfx_simplex2d_plan(hfx_eles *e, int out[8])
+{
+  HFX_CHECK(e && out, "hfx_simplex2d_plan: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  HFX_CHECK(e->simplex2d && e->simplex2d->built, "hfx_simplex2d_plan: no 2-D simplex fused stage has prepared this block (run fused 4 first)");
+  const hfx::Simplex2dPlan pl = hfx::simplex2d_plan(e);
+  const int v[8] = {pl.size_class, pl.group, pl.waves, pl.gather, (int)pl.element_lds, (int)pl.update_lds, 0, 0};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+  return 0;
+}

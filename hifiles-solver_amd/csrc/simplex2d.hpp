@@ -1,0 +1,49 @@
+// simplex2d.hpp -- the fused RK stage for two-dimensional simplex blocks (triangles): a block's plan and the stage's steps
+// (simplex2d.hip).  The host side of the general stage (general.hip: general_prepare, GeneralStage, general_time_kernels,
+// general_kernel_bytes) branches here for a block with n_dims == 2 of a non-tensor class; nothing else calls these.
+#pragma once
+#include "hfx_internal.hpp"
+
+namespace hfx
+{
+// the triangle orders with kernel instantiations: solution / flux points of P1..P5 and the elements of a group.  THE list: the
+// dispatch, the plan and the byte counts read it
+constexpr int SIMPLEX2D_SIZES[][3] = {{3, 6, 64}, {6, 9, 64}, {10, 12, 32}, {15, 15, 32}, {21, 18, 16}};
+constexpr int N_SIMPLEX2D_SIZES = sizeof(SIMPLEX2D_SIZES) / sizeof(SIMPLEX2D_SIZES[0]);
+constexpr int SIMPLEX2D_WAVES = 4;
+// LDS image of a workgroup (doubles): the operators, staged once per workgroup, then a group's planes [row][element + 1 pad][.]
+constexpr size_t simplex2d_element_ops(int nu, int nfp) { return (size_t)4 * nu * nu + (size_t)6 * nu * nfp; } // o4 o5 o6 o0 o2 o1
+constexpr size_t simplex2d_update_ops(int nu, int nfp) { return (size_t)2 * nu * nfp; }                       // o3 o0
+constexpr size_t simplex2d_element_lds_bytes(int nu, int nfp, int g) { return sizeof(double) * (simplex2d_element_ops(nu, nfp) + (size_t)(g + 1) * (12 * nu + 4 * nfp)); }
+constexpr size_t simplex2d_update_lds_bytes(int nu, int nfp, int g) { return sizeof(double) * (simplex2d_update_ops(nu, nfp) + (size_t)(g + 1) * (4 * nu + 4 * nfp)); }
+constexpr bool simplex2d_sizes_fit()
+{
+  bool ok = true;
+  for (const auto &s : SIMPLEX2D_SIZES) ok = ok && simplex2d_element_lds_bytes(s[0], s[1], s[2]) <= 80 * 1024; // two workgroups per CU
+  return ok;
+}
+static_assert(simplex2d_sizes_fit(), "a group of an instantiated triangle order no longer leaves room for two workgroups per CU");
+
+// What the stage runs on one block: decided once, from the options and the block's sizes and tables
+struct Simplex2dPlan
+{
+  int size_class = -1; // index in SIMPLEX2D_SIZES (order - 1)
+  int group = 0;       // elements per group
+  int waves = SIMPLEX2D_WAVES;
+  bool gather = false; // the element kernel forms the LDG corrections of interior points itself (option gather_delta, viscous)
+  size_t element_lds = 0, update_lds = 0;
+};
+
+inline bool is_simplex2d(const hfx_eles *e) { return e && e->n_dims == 2 && e->ele_type == 0; }
+// tables for the block unless they exist; refuses (naming fused 0) what the stage is not built for
+int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb);
+void simplex2d_invalidate(hfx_eles *e);
+Simplex2dPlan simplex2d_plan(const hfx_eles *e);
+// the four steps of ONE stage on a prepared block whose disu_fpts belong to the current state (GeneralStage's, in its order)
+int simplex2d_interior_ldg(hfx_eles *e, hfx_inters *const *faces, int nfb);
+int simplex2d_element_kernel(hfx_eles *e, int in_step);
+int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb);
+int simplex2d_update_kernel(hfx_eles *e, int in_step); // then the disu_fpts buffers change places
+// algorithmic HBM bytes per step, added to bytes[0..3]
+void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes);
+} // namespace hfx

@@ -645,6 +645,13 @@ class Eles:
         check(lib().hfx_general_plan(self.h, out))
         return dict(zip(("size_class", "flux_waves", "flux_batched", "gather", "les", "update_waves", "fold", "flux_lds"), list(out)))
 
+    def simplex2d_plan(self):
+        """the form of the 2-D simplex fused stage on this block of triangles (hfx_simplex2d_plan), valid after a fused-4 call: dict of
+        size_class, group, waves, gather, element_lds, update_lds"""
+        out = (C.c_int * 8)()
+        check(lib().hfx_simplex2d_plan(self.h, out))
+        return dict(zip(("size_class", "group", "waves", "gather", "element_lds", "update_lds"), list(out)))
+
     def time_integral_quantities(self, reps=20):
         v = C.c_double(0)
         check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))
@@ -861,6 +868,23 @@ def run_steps_blocks(eles, faces, n_steps, fused=0):
     ea = (C.c_void_p * len(eles))(*[e.h for e in eles])
     fa = (C.c_void_p * max(1, len(faces)))(*[f.h for f in faces])
     check(lib().hfx_run_steps_blocks(ea, C.c_int(len(eles)), fa, C.c_int(len(faces)), C.c_int(n_steps), C.c_int(int(fused))))
+
+
+def time_general_kernels(eles, faces, reps=10):
+    """hfx_time_general_kernels: (ms[8], the comma-separated kernel names) of the fused-4 stage on these blocks"""
+    ea = (C.c_void_p * len(eles))(*[e.h for e in eles])
+    fa = (C.c_void_p * max(1, len(faces)))(*[f.h for f in faces])
+    ms, names = (C.c_double * 8)(), (C.c_char * 256)()
+    check(lib().hfx_time_general_kernels(ea, C.c_int(len(eles)), fa, C.c_int(len(faces)), C.c_int(reps), ms, names))
+    return list(ms), names.value.decode()
+
+
+def general_kernel_bytes(eles):
+    """hfx_general_kernel_bytes: algorithmic HBM bytes per launch, in the order of time_general_kernels"""
+    ea = (C.c_void_p * len(eles))(*[e.h for e in eles])
+    by = (C.c_double * 8)()
+    check(lib().hfx_general_kernel_bytes(ea, C.c_int(len(eles)), by))
+    return list(by)
 
 
 def flush_for_samples(eles, integrals=False, history=False, plot=False):

@@ -967,6 +967,12 @@ int hfx_general_kernel_bytes(hfx_eles *const *eles, int n_ele_blocks, double byt
  * face_delta_kernel), out[4] 1: its LES form, out[5] waves of the update kernel (4, 8), out[6] 1: the folded correction
  * (opp_2 - opp_3 opp_1), out[7] bytes of the flux kernel's LDS image of a batch. */
 int hfx_general_plan(hfx_eles *e, int out[8]);
+/* The same for a block of triangles, which fused 4 runs through the 2-D simplex fused stage (read-only; valid once a fused-4 call or a
+ * deferred stage has prepared the block, refused before): out[0] size class (order - 1: the kernel instantiation of P1..P5), out[1]
+ * elements per group, out[2] waves per workgroup, out[3] 1: the element kernel forms the interior LDG corrections itself (no
+ * face_delta_kernel), out[4] bytes of the element kernel's LDS image (operators + one group), out[5] the update kernel's, out[6..7] 0.
+ * hfx_time_general_kernels and hfx_general_kernel_bytes answer for such a block with the stage's four steps. */
+int hfx_simplex2d_plan(hfx_eles *e, int out[8]);
 
 #ifdef __cplusplus
 }
