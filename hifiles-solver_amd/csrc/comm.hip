@@ -19,6 +19,7 @@
 
 #include "fused_hex.hpp"
 #include "general.hpp"
+#include "simplex2d.hpp"
 #include "split_common.hpp"
 #include "hfx_internal.hpp"
 
@@ -382,6 +383,61 @@ int partitioned_stage_deferred(hfx_eles *e, hfx_inters *const *int_faces, int n_
   return partitioned_stage(e, int_faces, n_int, mpi_faces, n_mpi, comm, rk, start, nullptr);
 }
 
+// ONE RK stage of the 2-D simplex fused stage (simplex2d.hip) on ONE partitioned block of triangles, interior groups first.  The
+// kernels walk groups of G consecutive elements; a group with a partition flux point is a partition group, the others need nothing
+// from the neighbours.  `all`: the interior, boundary and partition-face blocks the tables were prepared with.
+//   [solution message in flight]   boundary ghost states; element kernel on the interior groups
+//   wait 0                         (LDG corrections at the partition faces unless the element kernel gathers them); element
+//                                  kernel on the partition groups
+//   pack Fn, start exchange 1      interior common fluxes, boundary viscous fluxes
+//   wait 1; one-sided common fluxes
+//   update kernel on the partition groups; pack the new flux-point solution, start exchange 0
+//   update kernel on the interior groups   <- beside exchange 0, as is the next stage's interior element launch
+// An inviscid run has no exchange 1 and no LDG step; the order is otherwise the same.
+static int simplex2d_partitioned_stage(hfx_eles *e, hfx_inters *const *all, int n_all, hfx_inters *const *mpi_faces, int n_mpi,
+                                       hfx_comm *comm, int rk, bool start)
+{
+  hfx_ctx *ctx = e->ctx;
+  const bool visc = ctx->params.viscous != 0;
+  hipStream_t st = ctx->stream, cs = comm->stream;
+  const Simplex2dPartitionPlan pp = simplex2d_partition_plan(e);
+  // the one-sided kernels read e->arr[HFX_DISU_FPTS] when they are LAUNCHED (mpi_launch fills its arguments then): a pack
+  // launched behind simplex2d_swap_disu_fpts sees the buffer the update kernels wrote, whatever stream it runs on
+  auto mpi_all = [&](MpiKernel k, hipStream_t s) -> int {
+    for (int b = 0; b < n_mpi; b++)
+      if (mpi_launch_general(e, mpi_faces[b], k, simplex2d_fn_fpts(e), s)) return 1;
+    return 0;
+  };
+  if (start)
+  {
+    if (mpi_all(MpiKernel::pack_solution, st)) return 1;
+    if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1;
+  }
+  if (simplex2d_interior_ldg(e, all, n_all)) return 1;
+  if (simplex2d_element_kernel(e, rk, S2dList::interior)) return 1;
+  if (wait_exchange(comm, 0, n_mpi)) return 1;
+  if (visc && !pp.gather_remote && mpi_all(MpiKernel::ldg_delta, st)) return 1;
+  if (simplex2d_element_kernel(e, rk, S2dList::partition)) return 1;
+  if (visc)
+  {
+    if (mpi_all(MpiKernel::pack_projected_flux, st)) return 1;
+    if (start_exchange(comm, mpi_faces, n_mpi, 1, true)) return 1;
+  }
+  if (simplex2d_common_fluxes(e, all, n_all)) return 1;
+  if (visc && wait_exchange(comm, 1, n_mpi)) return 1;
+  if (mpi_all(MpiKernel::common_flux_projected, st)) return 1;
+  // the partition groups first: their new flux-point solution leaves (packed on the communication stream, behind this launch
+  // alone) while the interior groups are updated
+  if (simplex2d_update_kernel(e, rk, S2dList::partition)) return 1;
+  HFX_HIP(hipEventRecord(comm->packed[0], st));
+  HFX_HIP(hipStreamWaitEvent(cs, comm->packed[0], 0));
+  if (simplex2d_update_kernel(e, rk, S2dList::interior)) return 1;
+  simplex2d_swap_disu_fpts(e); // once, behind both launches: what is packed now is the new state's
+  if (mpi_all(MpiKernel::pack_solution, cs)) return 1;
+  note_gradients(e, false); // (the stage keeps them on chip)
+  return start_exchange(comm, mpi_faces, n_mpi, 0, false, true);
+}
+
 // ONE RK stage of the GENERAL fused stage (general.hip: tetrahedra, prisms, several element blocks) on partitioned blocks: the
 // stage's four parts with the one-sided partition-face kernels and the two exchanges between them, in CalcResidual's order
 // (src/solver.cpp:68-72,131-139,148-155,197-210; mpi_inters::set_mpi takes any element class, src/mpi_inters.cpp:154):
@@ -399,7 +455,11 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
   // the blocks' tables are built with ALL face blocks (every flux point needs its face)
   std::vector<hfx_inters *> all(int_faces, int_faces + n_int);
   all.insert(all.end(), mpi_faces, mpi_faces + n_mpi);
-  if (general_prepare(eles, neb, all.data(), (int)all.size())) return 1;
+  if (general_prepare(eles, neb, all.data(), (int)all.size(), true)) return 1;
+  // one block of triangles: the 2-D simplex stage, interior groups first (nothing of it is refused past this point; LES,
+  // over-integration and shock capturing were refused by the tables)
+  if (neb == 1 && is_simplex2d(eles[0]))
+    return simplex2d_partitioned_stage(eles[0], all.data(), (int)all.size(), mpi_faces, n_mpi, comm, rk, start);
   auto mpi_all = [&](MpiKernel k) -> int {
     for (int b = 0; b < n_mpi; b++)
       if (mpi_launch_general(mpi_faces[b]->left, mpi_faces[b], k, general_fn_fpts(mpi_faces[b]->left))) return 1;
@@ -717,8 +777,8 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   hfx_ctx *ctx = eles[0]->ctx;
   HFX_CHECK(ctx->have_params, "parameters not set");
   HFX_IMMEDIATE(ctx, 0);
-  HFX_CHECK(ctx->params.dt_type == 0, "hfx_run_steps_partitioned_blocks: CFL time steps (dt_type 1 / 2) over several element blocks are the caller's "
-                                      "(hfx_eles_calc_dt_local per block + hfx_comm_allreduce, then one step at a time)");
+  const bool cfl_steps = ctx->params.dt_type == 1 || ctx->params.dt_type == 2;
+  HFX_CHECK(!cfl_steps || ctx->have_CFL, "dt_type %d needs run_input.CFL: call hfx_ctx_set_CFL", ctx->params.dt_type);
   const int nst = n_rk_stages(ctx->params);
   if (probes_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
   if (integrals_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
@@ -734,6 +794,19 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   for (int i = 0; i < n_ele_blocks; i++) start = start || !sent_over(eles[i], comm);
   for (int s = 0; s < n_steps; s++)
   {
+    // calc_time_step (src/solver.cpp:484-549, src/HiFiLES.cpp:198): per-element CFL steps (dt_type 2 keeps them), their minimum
+    // over the blocks and over the ranks.  It reads disu_upts(0) on the compute stream; the solution message in flight reads the
+    // packed flux-point values
+    if (cfl_steps)
+    {
+      if (calc_time_step_blocks(eles, n_ele_blocks)) return 1;
+      if (comm->nranks > 1)
+      {
+        double dt_min = ctx->params.dt;
+        if (hfx_comm_allreduce(comm, &dt_min, 1, 0)) return 1;
+        ctx->params.dt = dt_min;
+      }
+    }
     if (begin_of_step(eles, n_ele_blocks, comm)) return 1; /* src/solver.cpp:96-109 */
     for (int rk = 0; rk < nst; rk++)
     {

@@ -219,7 +219,7 @@ static void make_plan(hfx_ctx *ctx, const std::vector<DeferCall> &log, DeferPlan
   {
     std::vector<hfx_inters *> all = P.faces;
     all.insert(all.end(), P.mpi_faces.begin(), P.mpi_faces.end());
-    if (general_prepare(P.eles.data(), (int)P.eles.size(), all.data(), (int)all.size()))
+    if (general_prepare(P.eles.data(), (int)P.eles.size(), all.data(), (int)all.size(), mpi))
     {
       P.why = hfx_last_error();
       return;

@@ -40,8 +40,8 @@ enum class MpiKernel
   common_flux_projected, // common flux from both sides' solution and Fn
   pack_sgs_flux,         // the physical SGS flux into the send buffer
 };
-// one of them on a block of the GENERAL fused stage, whose projected viscous flux is `fn` (compute stream)
-int mpi_launch_general(hfx_eles *e, hfx_inters *f, MpiKernel k, const double *fn);
+// one of them on a block of the GENERAL fused stage, whose projected viscous flux is `fn` (st NULL: the compute stream)
+int mpi_launch_general(hfx_eles *e, hfx_inters *f, MpiKernel k, const double *fn, hipStream_t st = nullptr);
 // ---- the deferred scheduler's pieces (deferred.hip) ----
 // ONE stage of the split fused path (the variant that split_plan names for the context's fused mode) on a block whose
 // disu_fpts belongs to the current state; write_div: store div_tconf_upts; shock: shock_capture follows AdvanceSolution

@@ -1204,7 +1204,7 @@ int GeneralStage::update_kernels() const
   return 0;
 }
 
-int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb)
+int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, bool partitioned)
 {
   hfx_ctx *ctx = eles[0]->ctx;
   for (int i = 0; i < neb; i++)
@@ -1222,9 +1222,10 @@ int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, in
     }
     HFX_CHECK(l && r, "face block %d refers to an element block that is not part of this call", b);
   }
-  // a two-dimensional block of a non-tensor class (triangles): the 2-D simplex stage's tables (one block, no partition faces)
+  // a two-dimensional block of a non-tensor class (triangles): the 2-D simplex stage's tables (one block; partition faces in
+  // the partitioned stage alone)
   for (int i = 0; i < neb; i++)
-    if (is_simplex2d(eles[i])) return simplex2d_prepare(eles, neb, faces, nfb);
+    if (is_simplex2d(eles[i])) return simplex2d_prepare(eles, neb, faces, nfb, partitioned);
   for (int i = 0; i < neb; i++)
   {
     GeneralData *g = eles[i]->general.get();
@@ -1240,7 +1241,11 @@ int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, in
   return 0;
 }
 
-const double *general_fn_fpts(const hfx_eles *e) { return e->general ? e->general->fn_fpts : nullptr; }
+const double *general_fn_fpts(const hfx_eles *e)
+{
+  if (is_simplex2d(e)) return simplex2d_fn_fpts(e);
+  return e->general ? e->general->fn_fpts : nullptr;
+}
 
 // eles::shock_capture behind a general fused stage (src/HiFiLES.cpp:214-216): the modal filter changes the state of the elements
 // the sensor marks, so the flux-point values the update kernel left for the next stage are extrapolated again

@@ -114,12 +114,13 @@ int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
 int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int reps, double *ms);
 // algorithmic HBM bytes per step, same order; every block priced from its own plan
 void general_kernel_bytes(hfx_eles *const *eles, int neb, double *bytes);
-// tables for these blocks unless they exist (non-zero when a block does not qualify); `faces` may hold partition-face blocks
-int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb);
+// tables for these blocks unless they exist (non-zero when a block does not qualify); `faces` may hold partition-face blocks.
+// partitioned: the caller is the partitioned stage (a triangle block takes partition-face blocks from it alone)
+int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, bool partitioned = false);
 // the general fused stage on partitioned element blocks (comm.hip)
 int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces,
                               int n_mpi, hfx_comm *comm, int rk, bool start, bool shock);
-// the projected viscous flux array of a block
+// the projected viscous flux array of a block (a triangle block: the 2-D simplex stage's)
 const double *general_fn_fpts(const hfx_eles *e);
 // eles::shock_capture of the blocks that registered it, and the flux-point values of the filtered state
 int general_shock_capture(hfx_eles *const *eles, int neb);

@@ -1544,6 +1544,7 @@ int hfx_mpi_inters_create(hfx_ctx *ctx, hfx_eles *left, int n_inters, int nfpi, 
   if (f->L.upload(f->hL) || f->R.upload(f->hR)) return 1;
   const size_t nd = (size_t)std::max<long>(np, 1) * left->n_fields, ng = nd * left->n_dims;
   if (f->out_disu.alloc(nd) || f->in_disu.alloc_zeroed(nd) || f->out_grad.alloc(ng) || f->in_grad.alloc_zeroed(ng)) return 1;
+  simplex2d_invalidate(left); // (a triangle block's partner words address a partition-face block's receive record)
   *out = f.release();
   return 0;
 }

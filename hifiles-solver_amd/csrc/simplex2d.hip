@@ -36,6 +36,14 @@ struct Simplex2dData
   DevBuf<double> disu_alt;                // second disu_fpts buffer (the update kernel writes the new state's flux-point solution)
   DevBuf<double> fn_fpts;                 // (n_fpts, n_eles, n_fields) viscous flux projected on the point's own normal
   bool any_bdy = false, any_int = false;
+  // partitioned blocks: the groups (of the size class's G consecutive elements) with and without a partition flux point, ascending
+  DevBuf<int> partition_groups, interior_groups;
+  int n_partition_groups = 0, n_interior_groups = 0;
+  bool any_mpi = false;
+  // the ONE partition-face block whose receive record the partner words of partition points address (their remote bit); NULL:
+  // partition points carry the word -1 and mpi_delta_kernel<2> writes their corrections
+  const hfx_inters *remote_face = nullptr;
+  std::vector<const hfx_inters *> built_with; // the face blocks the tables were made from
   bool built = false;
 };
 
@@ -52,9 +60,16 @@ struct S2dArgs
   const double *ops;
   const double *u0, *delta, *disu;
   // the LDG correction of an interior flux point is formed in the element kernel from the partner's flux-point solution:
-  // (partner offset << 4) | beta sign flipped << 1 | this point is the right side; -1: a boundary point (its correction is in
-  // `delta`).  NULL: `delta` holds all of them.
+  // (partner offset << 4) | remote << 2 | beta sign flipped << 1 | this point is the right side; -1: a boundary point (its
+  // correction is in `delta`).  NULL: `delta` holds all of them.  remote: a partition point whose partner lies in the receive
+  // record `in_disu` of the block's partition faces -- the offset is that of the partner's slot in its face's record (Rlut), the
+  // stride from field to field `nfpi` instead of the plane, and the point is the LEFT side with its own switch bit
   const int *nbr;
+  const double *in_disu;
+  int nfpi;
+  // the groups this launch walks: groups[0 .. n_list); NULL: all n_groups, in order
+  const int *groups;
+  int n_list;
   const double *detjac_upts, *JGinv_upts, *detjac_fpts, *JGinv_fpts, *norm_fpts;
   const unsigned char *meta;
   double *div, *ntd, *fn, *grad_fpts; // grad_fpts: boundary points only (NULL: no boundary faces / inviscid)
@@ -113,8 +128,10 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
   const long plane_u = (long)NU * a.n_eles, plane_f = (long)NFP * a.n_eles;
   s2d_stage_ops(lds, a.ops, (int)simplex2d_element_ops(NU, NFP), tid);
 
-  for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x)
+  const int n_walk = a.groups ? a.n_list : a.n_groups;
+  for (int it = blockIdx.x; it < n_walk; it += gridDim.x)
   {
+    const int grp = a.groups ? a.groups[it] : it; // (within a group nothing changes: one contiguous run per field)
     const long e0 = (long)grp * G;
     const int nval = (int)min((long)G, a.n_eles - e0);
     const int items_u = NU * nval, items_f = NFP * nval; // (a last partial group: its elements alone; nothing is read or written past them)
@@ -144,13 +161,15 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
         {
           // delta = u_common - u_own, u_common = (u_L + u_R)/2 - beta (u_L - u_R) on the pair's orientation (src/inters.cpp:637)
           const int w = a.nbr[o];
-          const double *pp = (w < 0) ? a.delta + o : a.disu + (w >> 4);
+          const bool remote = w >= 0 && (w & 4); // the partner of a partition point: in the receive record
+          const double *pp = (w < 0) ? a.delta + o : (remote ? a.in_disu : a.disu) + (w >> 4);
+          const long stride = remote ? (long)a.nfpi : plane_f;
           double own[NF], oth[NF];
 #pragma unroll
           for (int f = 0; f < NF; f++)
           {
             own[f] = a.disu[o + f * plane_f];
-            oth[f] = pp[f * plane_f];
+            oth[f] = pp[f * stride];
           }
           const double beta = ldg_beta(w, a.P);
 #pragma unroll
@@ -347,8 +366,10 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_update_kernel_t(const S2dArgs
   const long plane_u = (long)NU * a.n_eles, plane_f = (long)NFP * a.n_eles;
   s2d_stage_ops(lds, a.ops, (int)simplex2d_update_ops(NU, NFP), tid);
 
-  for (int grp = blockIdx.x; grp < a.n_groups; grp += gridDim.x)
+  const int n_walk = a.groups ? a.n_list : a.n_groups;
+  for (int it = blockIdx.x; it < n_walk; it += gridDim.x)
   {
+    const int grp = a.groups ? a.groups[it] : it;
     const long e0 = (long)grp * G;
     const int nval = (int)min((long)G, a.n_eles - e0);
     const int items_u = NU * nval, items_f = NFP * nval;
@@ -510,10 +531,40 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
   std::vector<int> nbr(plane_f, -1);
   std::vector<double> norm((size_t)plane_f * 2);
   HFX_HIP(hipMemcpy(norm.data(), e->norm_fpts, sizeof(double) * norm.size(), hipMemcpyDeviceToHost));
-  g->any_bdy = g->any_int = false;
+  g->any_bdy = g->any_int = g->any_mpi = false;
+  // partition faces (the partitioned stage): a partition point is owned by its face like every other point and carries no boundary
+  // bit; its common flux comes from the one-sided kernels of kernels_mpi.hpp.  Its LDG correction: with ONE partition-face block
+  // the element kernel reads the partner from that block's receive record (remote word; the switch from the point's OWN normal, as
+  // mpi_delta_kernel<2> decides it); with several blocks the word stays -1 and mpi_delta_kernel<2> writes delta_disu_fpts
+  int n_mpi_blocks = 0;
+  for (int b = 0; b < nfb; b++) n_mpi_blocks += faces[b]->is_mpi && faces[b]->n_inters > 0;
+  g->remote_face = nullptr;
+  const int G = SIMPLEX2D_SIZES[simplex2d_size_class(e)][2];
+  const int n_groups = (e->n_eles + G - 1) / G;
+  std::vector<char> partition_group(n_groups, 0);
   for (int b = 0; b < nfb; b++)
   {
     hfx_inters *f = faces[b];
+    if (f->is_mpi)
+    {
+      const long np = (long)f->n_inters * f->n_fpts_per_inter;
+      const bool remote = n_mpi_blocks == 1 && np * e->n_fields < (1L << 27);
+      if (remote && np > 0) g->remote_face = f;
+      for (long q = 0; q < np; q++)
+      {
+        const int il = f->hL[q];
+        owned[il]++;
+        partition_group[(il / (int)nfp) / G] = 1;
+        g->any_mpi = true;
+        if (!remote) continue;
+        const double n[2] = {norm[il], norm[il + plane_f]};
+        const int flip = ldg_switch<2>(1.0, n) < 0 ? 2 : 0;
+        const long i = q / f->n_fpts_per_inter;
+        const long slot = f->hR[q] + (long)f->n_fpts_per_inter * e->n_fields * i; // field 0 of the partner in the record of face i
+        nbr[il] = (int)(slot << 4) | 4 | flip;
+      }
+      continue;
+    }
     if (f->is_bdy)
     {
       g->any_bdy = g->any_bdy || f->n_inters > 0;
@@ -536,24 +587,41 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
   for (long o = 0; o < plane_f; o++) HFX_CHECK(owned[o] == 1, "2-D simplex fused stage: flux point %ld belongs to %d registered faces", o, (int)owned[o]);
   if (g->meta.upload(meta) || g->nbr.upload(nbr)) return 1;
   if (g->disu_alt.ensure((size_t)plane_f * e->n_fields) || g->fn_fpts.ensure((size_t)plane_f * e->n_fields)) return 1;
+  {
+    // the two group lists of the partitioned stage (the last partial group is on the list its elements put it on)
+    std::vector<int> part, inter;
+    for (int grp = 0; grp < n_groups; grp++) (partition_group[grp] ? part : inter).push_back(grp);
+    g->n_partition_groups = (int)part.size();
+    g->n_interior_groups = (int)inter.size();
+    g->partition_groups.reset();
+    g->interior_groups.reset();
+    if (!part.empty() && g->partition_groups.upload(part)) return 1;
+    if (!inter.empty() && g->interior_groups.upload(inter)) return 1;
+  }
+  g->built_with.assign(faces, faces + nfb);
   g->built = true;
   return 0;
 }
 
-int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb)
+int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, bool partitioned)
 {
   HFX_CHECK(neb == 1, "2-D simplex fused stage: several element blocks of which one is two-dimensional (a mixed quadrilateral / triangle "
                       "mesh) run per method (fused 0)");
   hfx_eles *e = eles[0];
   HFX_CHECK(e->n_eles > 0, "2-D simplex fused stage: empty element block");
-  for (int b = 0; b < nfb; b++)
-    HFX_CHECK(!faces[b]->is_mpi, "2-D simplex fused stage: partition faces on a triangle block run per method (fused 0)");
+  if (!partitioned)
+    for (int b = 0; b < nfb; b++)
+      HFX_CHECK(!faces[b]->is_mpi, "2-D simplex fused stage: partition faces on a triangle block run in the partitioned loop "
+                                   "(hfx_run_steps_partitioned_blocks) or per method (fused 0)");
   for (int b = 0; b < nfb; b++)
     HFX_CHECK(faces[b]->left == e && (faces[b]->right == nullptr || faces[b]->right == e), "face block %d refers to an element block that is not part of this call", b);
   // (what refuses a block is asked every time: a closure registered, or a context made viscous, behind the first stage must not
   // run on the tables of the stage before)
   HFX_CHECK(!e->ctx->params.viscous || e->viscous_ops, "2-D simplex fused stage: viscous run but the block has no opp_4/5/6");
-  if (e->simplex2d && e->simplex2d->built && !e->les_ready && !e->over_int_ready && !e->shock_ready) return 0;
+  const Simplex2dData *g = e->simplex2d.get();
+  if (g && g->built && !e->les_ready && !e->over_int_ready && !e->shock_ready && g->built_with.size() == (size_t)nfb &&
+      std::equal(g->built_with.begin(), g->built_with.end(), faces))
+    return 0;
   return simplex2d_build(e, faces, nfb);
 }
 
@@ -564,20 +632,43 @@ Simplex2dPlan simplex2d_plan(const hfx_eles *e)
   if (pl.size_class < 0) return pl;
   const int *s = SIMPLEX2D_SIZES[pl.size_class];
   pl.group = s[2];
-  pl.gather = e->ctx->opt.gather_delta && e->ctx->params.viscous && e->simplex2d && e->simplex2d->any_int;
+  pl.gather = e->ctx->opt.gather_delta && e->ctx->params.viscous && e->simplex2d && (e->simplex2d->any_int || e->simplex2d->remote_face);
   pl.element_lds = simplex2d_element_lds_bytes(s[0], s[1], s[2]);
   pl.update_lds = simplex2d_update_lds_bytes(s[0], s[1], s[2]);
   return pl;
 }
 
-static S2dArgs s2d_args(hfx_eles *e, const Simplex2dPlan &pl, int in_step)
+Simplex2dPartitionPlan simplex2d_partition_plan(const hfx_eles *e)
+{
+  Simplex2dPartitionPlan pp;
+  const Simplex2dData *g = e->simplex2d.get();
+  if (!g || !g->built) return pp;
+  pp.partition_groups = g->n_partition_groups;
+  pp.interior_groups = g->n_interior_groups;
+  pp.gather_remote = simplex2d_plan(e).gather && g->remote_face != nullptr;
+  return pp;
+}
+
+const double *simplex2d_fn_fpts(const hfx_eles *e) { return e->simplex2d ? e->simplex2d->fn_fpts.get() : nullptr; }
+
+static S2dArgs s2d_args(hfx_eles *e, const Simplex2dPlan &pl, int in_step, S2dList list = S2dList::all)
 {
   Simplex2dData *g = e->simplex2d.get();
   const hfx_params &p = e->ctx->params;
   S2dArgs a{};
   a.n_eles = e->n_eles; a.n_groups = (e->n_eles + pl.group - 1) / pl.group;
+  if (list != S2dList::all)
+  {
+    a.groups = list == S2dList::partition ? g->partition_groups.get() : g->interior_groups.get();
+    a.n_list = list == S2dList::partition ? g->n_partition_groups : g->n_interior_groups;
+  }
   a.u0 = e->arr[HFX_DISU_UPTS0]; a.delta = e->arr[HFX_DELTA_DISU_FPTS]; a.disu = e->arr[HFX_DISU_FPTS];
   a.nbr = pl.gather ? g->nbr.get() : nullptr;
+  if (g->remote_face)
+  {
+    a.in_disu = g->remote_face->in_disu;
+    a.nfpi = g->remote_face->n_fpts_per_inter;
+  }
   a.detjac_upts = e->detjac_upts; a.JGinv_upts = e->JGinv_upts; a.detjac_fpts = e->detjac_fpts; a.JGinv_fpts = e->JGinv_fpts;
   a.norm_fpts = e->norm_fpts; a.meta = g->meta;
   a.div = e->arr[HFX_DIV_TCONF_UPTS]; a.ntd = e->arr[HFX_NORM_TDISF_FPTS]; a.fn = g->fn_fpts;
@@ -615,7 +706,8 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
     a.ops = element ? e->simplex2d->element_ops : e->simplex2d->update_ops;
     // as many workgroups as are resident (LDS; at most 8 of four waves), walking the groups grid-stride
     const long per_cu = std::max<long>(1, std::min<long>(8, (long)(160 * 1024 / lds)));
-    const int grid = persistent_grid(e, element ? SLOT_ELEMENT : SLOT_UPDATE, a.n_groups, std::min<long>(a.n_groups, per_cu * e->ctx->n_cu));
+    const long work = a.groups ? a.n_list : a.n_groups; // the groups this launch walks
+    const int grid = persistent_grid(e, element ? SLOT_ELEMENT : SLOT_UPDATE, work, std::min<long>(work, per_cu * e->ctx->n_cu));
     auto launch = [&](auto kernel) -> int {
       if (lds > 48 * 1024) HFX_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(S2D_T), lds, e->ctx->stream, a);
@@ -649,7 +741,7 @@ int simplex2d_interior_ldg(hfx_eles *e, hfx_inters *const *faces, int nfb)
   for (int b = 0; b < nfb; b++)
   {
     if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], 0, 1)) return 1; // ghost state -> inviscid common flux, LDG common solution
-    if (faces[b]->is_bdy || gather) continue;
+    if (faces[b]->is_bdy || faces[b]->is_mpi || gather) continue; // (partition faces: the partitioned stage's one-sided kernels)
     const FacePairArgs a = s2d_face_args(faces[b]);
     if (a.npairs == 0) continue;
     hipLaunchKernelGGL(face_delta_kernel<2>, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, ctx->stream, a, ctx->phys());
@@ -658,10 +750,18 @@ int simplex2d_interior_ldg(hfx_eles *e, hfx_inters *const *faces, int nfb)
   return 0;
 }
 
-int simplex2d_element_kernel(hfx_eles *e, int in_step)
+// an empty list launches nothing (its device buffer does not exist, and a NULL list means ALL groups to the kernels)
+static bool s2d_list_empty(const hfx_eles *e, S2dList list)
 {
+  const Simplex2dData *g = e->simplex2d.get();
+  return (list == S2dList::partition && g->n_partition_groups == 0) || (list == S2dList::interior && g->n_interior_groups == 0);
+}
+
+int simplex2d_element_kernel(hfx_eles *e, int in_step, S2dList list)
+{
+  if (s2d_list_empty(e, list)) return 0;
   const Simplex2dPlan pl = simplex2d_plan(e);
-  return launch_s2d(e, s2d_args(e, pl, in_step), pl, true);
+  return launch_s2d(e, s2d_args(e, pl, in_step, list), pl, true);
 }
 
 int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb)
@@ -673,7 +773,7 @@ int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb)
     if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], P.viscous ? 1 : 0, 1)) return 1;
   for (int b = 0; b < nfb; b++)
   {
-    if (faces[b]->is_bdy) continue;
+    if (faces[b]->is_bdy || faces[b]->is_mpi) continue;
     const FacePairArgs a = s2d_face_args(faces[b]);
     if (a.npairs == 0) continue;
     const FaceBlockArgs blk(a);
@@ -685,13 +785,16 @@ int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb)
   return 0;
 }
 
-int simplex2d_update_kernel(hfx_eles *e, int in_step)
+int simplex2d_update_kernel(hfx_eles *e, int in_step, S2dList list)
 {
+  if (s2d_list_empty(e, list)) return 0;
   const Simplex2dPlan pl = simplex2d_plan(e);
-  if (launch_s2d(e, s2d_args(e, pl, in_step), pl, false)) return 1;
-  std::swap(e->arr[HFX_DISU_FPTS], e->simplex2d->disu_alt);
+  if (launch_s2d(e, s2d_args(e, pl, in_step, list), pl, false)) return 1;
+  if (list == S2dList::all) simplex2d_swap_disu_fpts(e);
   return 0;
 }
+
+void simplex2d_swap_disu_fpts(hfx_eles *e) { std::swap(e->arr[HFX_DISU_FPTS], e->simplex2d->disu_alt); }
 
 // ALGORITHMIC HBM bytes per launch of the four steps (doubles listed per element), priced from the plan
 void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes)
@@ -718,5 +821,15 @@ extern "C" int hfx_simplex2d_plan(hfx_eles *e, int out[8])
   const hfx::Simplex2dPlan pl = hfx::simplex2d_plan(e);
   const int v[8] = {pl.size_class, pl.group, pl.waves, pl.gather, (int)pl.element_lds, (int)pl.update_lds, 0, 0};
   for (int i = 0; i < 8; i++) out[i] = v[i];
+  return 0;
+}
+
+extern "C" int hfx_simplex2d_partition_plan(hfx_eles *e, int out[4])
+{
+  HFX_CHECK(e && out, "hfx_simplex2d_partition_plan: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  HFX_CHECK(e->simplex2d && e->simplex2d->built, "hfx_simplex2d_partition_plan: no 2-D simplex fused stage has prepared this block");
+  const hfx::Simplex2dPartitionPlan pp = hfx::simplex2d_partition_plan(e);
+  out[0] = pp.partition_groups; out[1] = pp.interior_groups; out[2] = pp.gather_remote; out[3] = 0;
   return 0;
 }

@@ -34,16 +34,35 @@ struct Simplex2dPlan
   size_t element_lds = 0, update_lds = 0;
 };
 
+// The partitioned stage's side of the plan (general_partitioned_stage, comm.hip): the kernels walk GROUPS of `group` consecutive
+// elements, and a group is a partition group when one of its elements owns a partition flux point
+struct Simplex2dPartitionPlan
+{
+  int partition_groups = 0, interior_groups = 0;
+  // the element kernel reads the partners of partition points from the receive record itself (gather, ONE partition-face block);
+  // else mpi_delta_kernel<2> writes their corrections to delta_disu_fpts
+  bool gather_remote = false;
+};
+// which groups a launch of the element / update kernel walks
+enum class S2dList { all, interior, partition };
+
 inline bool is_simplex2d(const hfx_eles *e) { return e && e->n_dims == 2 && e->ele_type == 0; }
-// tables for the block unless they exist; refuses (naming fused 0) what the stage is not built for
-int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb);
+// tables for the block unless they exist; refuses (naming fused 0) what the stage is not built for.  partitioned: the call comes
+// from the partitioned stage, which alone takes partition-face blocks
+int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, bool partitioned);
 void simplex2d_invalidate(hfx_eles *e);
 Simplex2dPlan simplex2d_plan(const hfx_eles *e);
+Simplex2dPartitionPlan simplex2d_partition_plan(const hfx_eles *e);
 // the four steps of ONE stage on a prepared block whose disu_fpts belong to the current state (GeneralStage's, in its order)
 int simplex2d_interior_ldg(hfx_eles *e, hfx_inters *const *faces, int nfb);
-int simplex2d_element_kernel(hfx_eles *e, int in_step);
+int simplex2d_element_kernel(hfx_eles *e, int in_step, S2dList list = S2dList::all); // an empty list launches nothing
 int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb);
-int simplex2d_update_kernel(hfx_eles *e, int in_step); // then the disu_fpts buffers change places
+// S2dList::all: then the disu_fpts buffers change places; a launch on a list leaves that to simplex2d_swap_disu_fpts, called once
+// behind both lists' launches
+int simplex2d_update_kernel(hfx_eles *e, int in_step, S2dList list = S2dList::all);
+void simplex2d_swap_disu_fpts(hfx_eles *e);
+// the projected viscous flux array of the block (what a partition face sends)
+const double *simplex2d_fn_fpts(const hfx_eles *e);
 // algorithmic HBM bytes per step, added to bytes[0..3]
 void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes);
 } // namespace hfx

@@ -46,11 +46,14 @@ static int mpi_launch(hfx_eles *e, hfx_inters *f, MpiKernel k, bool sgs_ref, hip
   return 0;
 }
 
-// the one-sided partition-face kernels for a block of the general fused stage (three-dimensional; fn: that block's projected flux).
+// the one-sided partition-face kernels for a block of the general fused stage (fn: that block's projected flux) on stream `st`
+// (NULL: the compute stream).  Triangles take the two-dimensional instantiations (no closure there: no SGS buffers).
 // (sgs_ref as the SPLIT plan of the block's fused mode would have it: it decides whether a block with a closure gets SGS buffers)
-int mpi_launch_general(hfx_eles *e, hfx_inters *f, MpiKernel k, const double *fn)
+int mpi_launch_general(hfx_eles *e, hfx_inters *f, MpiKernel k, const double *fn, hipStream_t st)
 {
-  return mpi_launch<3>(e, f, k, split_plan(e, nullptr, 0, e->ctx->fused_mode).variant == 2, e->ctx->stream, fn);
+  if (!st) st = e->ctx->stream;
+  if (e->n_dims == 2) return mpi_launch<2>(e, f, k, false, st, fn);
+  return mpi_launch<3>(e, f, k, split_plan(e, nullptr, 0, e->ctx->fused_mode).variant == 2, st, fn);
 }
 
 int PartitionedSplit::init(hfx_eles *e_, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces_, int n_mpi_, int in_step_)

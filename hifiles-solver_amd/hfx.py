@@ -652,6 +652,13 @@ class Eles:
         check(lib().hfx_simplex2d_plan(self.h, out))
         return dict(zip(("size_class", "group", "waves", "gather", "element_lds", "update_lds"), list(out)))
 
+    def simplex2d_partition_plan(self):
+        """what the partitioned loop runs on this block of triangles (hfx_simplex2d_partition_plan): dict of partition_groups,
+        interior_groups, gather_remote"""
+        out = (C.c_int * 4)()
+        check(lib().hfx_simplex2d_partition_plan(self.h, out))
+        return dict(zip(("partition_groups", "interior_groups", "gather_remote"), list(out)))
+
     def time_integral_quantities(self, reps=20):
         v = C.c_double(0)
         check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))

@@ -904,10 +904,16 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
  * stage (hfx_run_steps_blocks(..., 4)) on partitioned blocks.  A partition-face block belongs to one element block
  * (mpi_inters::set_mpi takes any in_ele_type_l, src/mpi_inters.cpp:154); int_faces holds the interior blocks (whose two sides may
  * lie in different element blocks) and the boundary blocks.  Each stage: LDG corrections and common fluxes of the partition faces
- * by the one-sided kernels, the flux-point solution and each side's projected viscous flux Fn as the two messages.  Fixed time
- * step (dt_type 0) only; three-dimensional blocks as hfx_run_steps_blocks(..., 4) takes them -- an LES closure is evaluated in the
+ * by the one-sided kernels, the flux-point solution and each side's projected viscous flux Fn as the two messages.  With dt_type
+ * 1 / 2 every step starts with calc_time_step (src/solver.cpp:484-549, src/HiFiLES.cpp:198): hfx_eles_calc_dt_local of every
+ * block, the minimum over the blocks, all-reduce MIN over the ranks (h_ref and run_input.CFL must have been set).
+ * Three-dimensional blocks as hfx_run_steps_blocks(..., 4) takes them -- an LES closure is evaluated in the
  * flux kernel (its F_sgs . n travels inside Fn: no third message; the SVV closure is refused here), over-integration feeds it,
  * shock capturing follows the update before the next solution message is packed.
+ * ONE block of triangles (orders 1-5; no LES, over-integration or shock capturing) runs the 2-D simplex fused stage, interior
+ * groups first: the element and the update kernel walk the groups without a partition flux point beside the solution message, the
+ * groups with one behind it (hfx_simplex2d_partition_plan); with one partition-face block the element kernel reads the partners
+ * of partition points from the receive record itself.  hfx_run_steps_blocks(..., 4) keeps refusing a partition-face block.
  * With deferred execution the mirrored CalcResidual of such a mesh runs this stage when its send_* / receive_* name one hfx_comm. */
 int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hfx_inters *const *int_faces, int n_int,
                                      hfx_inters *const *mpi_faces, int n_mpi, hfx_comm *comm, int n_steps);
@@ -973,6 +979,13 @@ int hfx_general_plan(hfx_eles *e, int out[8]);
  * face_delta_kernel), out[4] bytes of the element kernel's LDS image (operators + one group), out[5] the update kernel's, out[6..7] 0.
  * hfx_time_general_kernels and hfx_general_kernel_bytes answer for such a block with the stage's four steps. */
 int hfx_simplex2d_plan(hfx_eles *e, int out[8]);
+/* What the partitioned loop (hfx_run_steps_partitioned_blocks, or the deferred stage) runs on a block of triangles (read-only; valid
+ * once a stage has prepared the block, refused before).  The kernels walk groups of out[1] of hfx_simplex2d_plan consecutive
+ * elements: out[0] partition groups (an element of the group owns a partition flux point), out[1] interior groups (launched
+ * first, beside the solution message), out[2] 1: the element kernel reads the partners of partition points from the receive
+ * record itself (option gather_delta, one partition-face block), 0: mpi_delta_kernel writes their LDG corrections, out[3] 0.
+ * A block prepared by hfx_run_steps_blocks(..., 4) has no partition groups. */
+int hfx_simplex2d_partition_plan(hfx_eles *e, int out[4]);
 
 #ifdef __cplusplus
 }
