@@ -394,8 +394,13 @@ int partitioned_stage_deferred(hfx_eles *e, hfx_inters *const *int_faces, int n_
 //   update kernel on the partition groups; pack the new flux-point solution, start exchange 0
 //   update kernel on the interior groups   <- beside exchange 0, as is the next stage's interior element launch
 // An inviscid run has no exchange 1 and no LDG step; the order is otherwise the same.
+// shock: eles::shock_capture follows the stage.  Folded into the update kernel (Simplex2dPlan::fold_shock) nothing changes in the
+// order above: the update on the partition groups writes the FILTERED state's flux-point solution of those groups (an element's
+// filter reads that element alone), the event `packed[0]` is recorded behind that launch, and the pack on the communication stream
+// waits for it -- what leaves is the filtered state's.  Not folded (option fold_shock 0) the filter and the extrapolation of the
+// filtered state run behind BOTH update launches and the pack waits for them: nothing is hidden behind the interior groups then.
 static int simplex2d_partitioned_stage(hfx_eles *e, hfx_inters *const *all, int n_all, hfx_inters *const *mpi_faces, int n_mpi,
-                                       hfx_comm *comm, int rk, bool start)
+                                       hfx_comm *comm, int rk, bool start, bool shock)
 {
   hfx_ctx *ctx = e->ctx;
   const bool visc = ctx->params.viscous != 0;
@@ -428,11 +433,21 @@ static int simplex2d_partitioned_stage(hfx_eles *e, hfx_inters *const *all, int 
   if (mpi_all(MpiKernel::common_flux_projected, st)) return 1;
   // the partition groups first: their new flux-point solution leaves (packed on the communication stream, behind this launch
   // alone) while the interior groups are updated
-  if (simplex2d_update_kernel(e, rk, S2dList::partition)) return 1;
-  HFX_HIP(hipEventRecord(comm->packed[0], st));
-  HFX_HIP(hipStreamWaitEvent(cs, comm->packed[0], 0));
-  if (simplex2d_update_kernel(e, rk, S2dList::interior)) return 1;
+  const bool filter_behind = shock && e->shock_ready && !simplex2d_folds_shock(e);
+  if (simplex2d_update_kernel(e, rk, S2dList::partition, shock)) return 1;
+  if (!filter_behind)
+  {
+    HFX_HIP(hipEventRecord(comm->packed[0], st));
+    HFX_HIP(hipStreamWaitEvent(cs, comm->packed[0], 0));
+  }
+  if (simplex2d_update_kernel(e, rk, S2dList::interior, shock)) return 1;
   simplex2d_swap_disu_fpts(e); // once, behind both launches: what is packed now is the new state's
+  if (filter_behind)
+  {
+    if (general_shock_capture(&e, 1)) return 1; // (the filter, then disu_fpts of the filtered state)
+    HFX_HIP(hipEventRecord(comm->packed[0], st));
+    HFX_HIP(hipStreamWaitEvent(cs, comm->packed[0], 0));
+  }
   if (mpi_all(MpiKernel::pack_solution, cs)) return 1;
   note_gradients(e, false); // (the stage keeps them on chip)
   return start_exchange(comm, mpi_faces, n_mpi, 0, false, true);
@@ -457,9 +472,9 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
   all.insert(all.end(), mpi_faces, mpi_faces + n_mpi);
   if (general_prepare(eles, neb, all.data(), (int)all.size(), true)) return 1;
   // one block of triangles: the 2-D simplex stage, interior groups first (nothing of it is refused past this point; LES,
-  // over-integration and shock capturing were refused by the tables)
+  // over-integration and shock capturing of another form than the triangle's own were refused by the tables)
   if (neb == 1 && is_simplex2d(eles[0]))
-    return simplex2d_partitioned_stage(eles[0], all.data(), (int)all.size(), mpi_faces, n_mpi, comm, rk, start);
+    return simplex2d_partitioned_stage(eles[0], all.data(), (int)all.size(), mpi_faces, n_mpi, comm, rk, start, shock);
   auto mpi_all = [&](MpiKernel k) -> int {
     for (int b = 0; b < n_mpi; b++)
       if (mpi_launch_general(mpi_faces[b]->left, mpi_faces[b], k, general_fn_fpts(mpi_faces[b]->left))) return 1;

@@ -296,7 +296,8 @@ static int run_fused(hfx_ctx *ctx, const DeferPlan &P, int in_step, bool write_d
     break;
   case DeferPlan::Kind::general:
     if (general_prepare(P.eles.data(), (int)P.eles.size(), faces, nfb)) return 1; // (no-op unless the registration changed)
-    if (GeneralStage(P.eles.data(), (int)P.eles.size(), faces, nfb, in_step).run()) return 1; // (completes div_tconf_upts at every stage)
+    // (completes div_tconf_upts at every stage; a recorded shock_capture is part of the stage: folded on a triangle block)
+    if (GeneralStage(P.eles.data(), (int)P.eles.size(), faces, nfb, in_step, P.shock).run()) return 1;
     if (P.shock && general_shock_capture(P.eles.data(), (int)P.eles.size())) return 1;
     break;
   case DeferPlan::Kind::general_partitioned:

@@ -1122,8 +1122,8 @@ static int launch_element_kernels(int waves, hfx_eles *e, const GenArgs &a, cons
                                                                               : launch_element_kernels<8>(e, a, pl, flux);
 }
 
-GeneralStage::GeneralStage(hfx_eles *const *eles_, int neb_, hfx_inters *const *faces_, int nfb_, int in_step_)
-    : eles(eles_), faces(faces_), neb(neb_), nfb(nfb_), simplex2d(neb_ == 1 && is_simplex2d(eles_[0])), in_step(in_step_)
+GeneralStage::GeneralStage(hfx_eles *const *eles_, int neb_, hfx_inters *const *faces_, int nfb_, int in_step_, bool shock_)
+    : eles(eles_), faces(faces_), neb(neb_), nfb(nfb_), simplex2d(neb_ == 1 && is_simplex2d(eles_[0])), in_step(in_step_), shock(shock_)
 {
   if (simplex2d) return;
   for (int i = 0; i < neb; i++) args.push_back(gen_args(eles[i], plans.emplace_back(general_plan(eles[i])), in_step_));
@@ -1197,7 +1197,7 @@ int GeneralStage::common_fluxes() const
 
 int GeneralStage::update_kernels() const
 {
-  if (simplex2d) return simplex2d_update_kernel(eles[0], in_step);
+  if (simplex2d) return simplex2d_update_kernel(eles[0], in_step, S2dList::all, shock);
   for (int i = 0; i < neb; i++)
     if (launch_element_kernels(plans[i].update_waves, eles[i], args[i], plans[i], false)) return 1;
   for (int i = 0; i < neb; i++) std::swap(eles[i]->arr[HFX_DISU_FPTS], eles[i]->general->disu_alt);
@@ -1252,7 +1252,7 @@ const double *general_fn_fpts(const hfx_eles *e)
 int general_shock_capture(hfx_eles *const *eles, int neb)
 {
   for (int i = 0; i < neb; i++)
-    if (eles[i]->shock_ready)
+    if (eles[i]->shock_ready && !simplex2d_folds_shock(eles[i])) // (a triangle stage that folded the filter left the sensor, the filtered state and its disu_fpts)
     {
       if (hfx_eles_shock_capture(eles[i])) return 1;
       if (hfx_eles_extrapolate_solution(eles[i])) return 1;

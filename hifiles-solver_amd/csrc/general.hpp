@@ -95,7 +95,10 @@ struct GeneralStage
   // one two-dimensional simplex block (triangles): every step is simplex2d.hip's, plans and args stay empty
   bool simplex2d = false;
   int in_step = 0;
-  GeneralStage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step);
+  // eles::shock_capture follows this stage where a block registered it: a triangle block whose plan folds the filter
+  // (Simplex2dPlan::fold_shock) runs it inside its update kernel, and general_shock_capture behind the stage passes that block by
+  bool shock = true;
+  GeneralStage(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int in_step, bool shock = true);
   // viscous: boundary ghost states (-> inviscid common flux, LDG common solution); face_delta_kernel unless BOTH sides' plans `gather`
   int interior_ldg() const;
   int flux_kernels() const; // behind the over-integration contraction where the block registered it

@@ -515,6 +515,7 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value)
   else if (n == "simd_roles") o.simd_roles = value != 0;
   else if (n == "flux_two_wave") o.flux_two_wave = value != 0;
   else if (n == "fold_faces") o.fold_faces = value != 0;
+  else if (n == "fold_shock") o.fold_shock = value != 0;
   else if (n == "flux_two_wave_face") { HFX_CHECK(value >= -1 && value <= 5, "flux_two_wave_face must be -1 (the host's choice) or a local face 0-5"); o.flux_two_wave_face = value; }
   else if (n == "les_flux_kernel") o.les_flux_kernel = value != 0;
   else if (n == "bdy_beside") o.bdy_beside = value != 0;
@@ -1308,6 +1309,9 @@ int hfx_eles_set_shock_capture(hfx_eles *e, const double *inv_vandermonde, const
     num[j] = high_modes[j] ? norm_basis_persson[j] : 0.0;
   }
   if (e->persson_num.upload(num) || e->persson_den.upload(den)) return 1;
+  e->h_persson_num = num;
+  e->h_persson_den = den;
+  e->shock_serial++;
   e->s0 = s0;
   e->shock_det_field = shock_det_field;
   e->shock_ready = true;

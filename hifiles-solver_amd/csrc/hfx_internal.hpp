@@ -241,6 +241,7 @@ struct hfx_ctx
     int fold_faces = 1;         // 1: with one-sided LDG (|ldg_beta| = 1/2; not with RoeM) the two-wave flux kernel forms the interior pairs' common flux itself and the stage launches no face_flux2_kernel on interior faces (0: the three-launch stage)
     int flux_two_wave_face = -1; // the local face that carries the two-wave flux kernel's left-over points: -1 the host's choice (two_wave_face), 0-5 forced (tests: reaches the left-over pass of phase B)
     int general_waves = 0;      // waves per workgroup of the general flux kernel: 0 by the LDS image (4 or 8), else 3, 4 or 8
+    int fold_shock = 1;         // 1: the 2-D simplex stage's update kernel carries a triangle block's shock filter (sensor of eles_tris::shock_det_persson); 0: the per-method filter behind the stage, as on tetrahedra and prisms
   } opt;
   hfx::Deferred defer;
   std::vector<hfx_comm *> comms; // the live communicators of this context (hfx_ctx_synchronize waits for their streams)
@@ -467,6 +468,10 @@ struct hfx_eles
   bool shock_ready = false;
   hfx::Operator inv_vandermonde, exp_filter;
   hfx::DevBuf<double> persson_num, persson_den; // (n_upts) weights of the sensor's two sums
+  // the same as registered, on the host (the 2-D simplex stage checks the sensor's form without a download), and the number of
+  // the registration (0: none yet; tables made from an earlier one are rebuilt)
+  std::vector<double> h_persson_num, h_persson_den;
+  unsigned shock_serial = 0;
   double s0 = 0.0;
   int shock_det_field = 0;
   hfx::Operator opp_0, opp_1[3], opp_2[3], opp_3, opp_4[3], opp_5[3], opp_6;

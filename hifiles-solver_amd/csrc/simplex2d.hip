@@ -31,6 +31,11 @@ namespace hfx
 struct Simplex2dData
 {
   DevBuf<double> element_ops, update_ops; // the operators one behind the other, in the kernels' order (zeros where inviscid)
+  // shock capturing registered in the triangle's own form (shock_form_refusal): update_ops + inv_vandermonde + exp_filter for the
+  // update kernel's SHOCK instantiation, and the registration (hfx_eles::shock_serial) the tables were made from
+  DevBuf<double> update_shock_ops;
+  bool shock = false;
+  unsigned shock_serial = 0;
   DevBuf<unsigned char> meta;             // (n_fpts, n_eles): bit1 beta sign flipped (LEFT point of a pair), bit2 boundary point
   DevBuf<int> nbr;                        // (n_fpts, n_eles) partner word of every flux point (S2dArgs::nbr)
   DevBuf<double> disu_alt;                // second disu_fpts buffer (the update kernel writes the new state's flux-point solution)
@@ -81,6 +86,10 @@ struct S2dArgs
   unsigned long long *nan_flag;
   int adv_type, in_step, dt_local_on, write_div, need_u1;
   double dt, rk_a, rk_b;
+  // update kernel with the shock filter folded in (SHOCK): the sensor's field (0 or n_dims + 1), the threshold and sensor(n_eles)
+  int sens_field;
+  double s0;
+  double *sensor;
 };
 
 constexpr int S2D_NF = 4, S2D_ND = 2, S2D_T = 64 * SIMPLEX2D_WAVES;
@@ -352,19 +361,39 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
 // ---------------------------------------------------------------------------------------------------------------
 // update kernel: div_tdisf + opp_3 (norm_tconf - norm_tdisf) -> RK update -> disu_fpts of the new state
 // (calculate_corrected_divergence, AdvanceSolution, extrapolate_solution; src/eles.cpp:1738,1080,1360); as general_update_kernel
+//
+// SHOCK: eles::shock_capture (src/eles.cpp:2918-2959) with the triangle's own sensor (eles_tris::shock_det_persson,
+// src/eles_tris.cpp:472-524) between the RK update and the opp_0 pass, on the group's new state in LDS:
+//   modal   lane (element, mode m): u^_m = sum_k inv_vandermonde(m, k) S[k][element][field], ascending k; u^_m^2 -> M
+//   sensor  one lane per element: tail (m >= NHI = p (p + 1) / 2) and all modes summed in ascending order (accumulate), divided,
+//           stored to sensor(n_eles) and kept in LDS.  Every mode norm is one; nothing crosses lanes: bit-reproducible
+//   filter  the lanes of an element with sensor >= s0 (a NaN compares false) form exp_filter . S for the four fields in registers,
+//           the others take their own point; behind a barrier every lane stores its point ONCE to disu_upts(0), the filtered
+//           ones to S as well, so that the opp_0 pass extrapolates the filtered state
+// With SHOCK false the kernel is the code without any of it.
 // ---------------------------------------------------------------------------------------------------------------
-template <int NU, int NFP, int G>
+template <int NU, int NFP, int G, bool SHOCK>
 __global__ __launch_bounds__(S2D_T) void simplex2d_update_kernel_t(const S2dArgs a)
 {
   constexpr int NF = S2D_NF, T = S2D_T, GP = G + 1;
+  constexpr int NHI = simplex2d_first_high_mode(NU);
+  constexpr int TRIPS = (NU * G + T - 1) / T; // points of a group per lane
   extern __shared__ double lds[];
   double *o3 = lds;              // NU x NFP
   double *o0 = o3 + NU * NFP;    // NFP x NU
-  double *X = o0 + NFP * NU;     // [NFP][GP][NF]  norm_tconf - norm_tdisf
+  double *iv = o0 + NFP * NU;    // NU x NU  inv_vandermonde  (SHOCK)
+  double *ef = iv + NU * NU;     // NU x NU  exp_filter       (SHOCK)
+  double *X = o0 + NFP * NU + (SHOCK ? 2 * NU * NU : 0); // [NFP][GP][NF]  norm_tconf - norm_tdisf
   double *S = X + NFP * GP * NF; // [NU][GP][NF]   the new state
+  double *M = S + NU * GP * NF;  // [GP][NU]       squared modal coefficients of the sensor field (SHOCK)
+  double *Sen = M + NU * GP;     // [GP]           the group's sensors (SHOCK)
+  static_assert(simplex2d_update_lds_bytes(NU, NFP, G, SHOCK) ==
+                    sizeof(double) * (simplex2d_update_ops(NU, NFP, SHOCK) + (size_t)GP * (NU * NF + NFP * NF + (SHOCK ? NU + 1 : 0))), "LDS image");
+  static_assert(simplex2d_update_lds_bytes(NU, NFP, G, SHOCK) <= SIMPLEX2D_LDS_BUDGET, "LDS budget");
+  static_assert(G <= T, "one lane per element in the sensor pass");
   const int tid = threadIdx.x;
   const long plane_u = (long)NU * a.n_eles, plane_f = (long)NFP * a.n_eles;
-  s2d_stage_ops(lds, a.ops, (int)simplex2d_update_ops(NU, NFP), tid);
+  s2d_stage_ops(lds, a.ops, (int)simplex2d_update_ops(NU, NFP, SHOCK), tid);
 
   const int n_walk = a.groups ? a.n_list : a.n_groups;
   for (int it = blockIdx.x; it < n_walk; it += gridDim.x)
@@ -452,11 +481,80 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_update_kernel_t(const S2dArgs
           a.u1[ok] = r1;
           u += a.rk_b * r1;
         }
-        a.u0w[ok] = u;
+        if constexpr (!SHOCK) a.u0w[ok] = u; // (SHOCK: stored once, behind the filter)
         S[(i * GP + el) * NF + f] = u;
       }
     }
     __syncthreads();
+    if constexpr (SHOCK)
+    {
+      // ---- modal coefficients of the sensor field, squared
+      for (int q = tid; q < items_u; q += T)
+      {
+        const int el = q / NU, m = q - el * NU;
+        double acc = 0.0;
+#pragma unroll 2
+        for (int k = 0; k < NU; k++) acc += iv[m + NU * k] * S[(k * GP + el) * NF + a.sens_field];
+        M[q] = acc * acc;
+      }
+      __syncthreads();
+      // ---- the sensor, one lane per element of the group (a padded element of the last group has none)
+      if (tid < nval)
+      {
+        double hi = 0.0, all = 0.0;
+        for (int m = NHI; m < NU; m++) hi += M[tid * NU + m];
+        for (int m = 0; m < NU; m++) all = all + M[tid * NU + m];
+        const double sen = hi / all;
+        a.sensor[e0 + tid] = sen;
+        Sen[tid] = sen;
+      }
+      __syncthreads();
+      // ---- the filter where the sensor fires; every point reaches disu_upts(0) from here
+      double r[TRIPS][NF];
+      bool filt[TRIPS];
+#pragma unroll
+      for (int t = 0; t < TRIPS; t++)
+      {
+        const int q = tid + t * T;
+        filt[t] = false;
+        if (q < items_u)
+        {
+          const int el = q / NU, i = q - el * NU;
+          filt[t] = Sen[el] >= a.s0;
+          if (filt[t])
+          {
+#pragma unroll
+            for (int f = 0; f < NF; f++) r[t][f] = 0.0;
+#pragma unroll 2
+            for (int k = 0; k < NU; k++)
+            {
+              const double m = ef[i + NU * k];
+#pragma unroll
+              for (int f = 0; f < NF; f++) r[t][f] += m * S[(k * GP + el) * NF + f];
+            }
+          }
+          else
+#pragma unroll
+            for (int f = 0; f < NF; f++) r[t][f] = S[(i * GP + el) * NF + f];
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int t = 0; t < TRIPS; t++)
+      {
+        const int q = tid + t * T;
+        if (q < items_u)
+        {
+          const int el = q / NU, i = q - el * NU;
+#pragma unroll
+          for (int f = 0; f < NF; f++) a.u0w[e0 * NU + q + f * plane_u] = r[t][f];
+          if (filt[t])
+#pragma unroll
+            for (int f = 0; f < NF; f++) S[(i * GP + el) * NF + f] = r[t][f];
+        }
+      }
+      __syncthreads();
+    }
     for (int q = tid; q < items_f; q += T)
     {
       const int el = q / NFP, j = q - el * NFP;
@@ -503,6 +601,20 @@ static int packed_operators(DevBuf<double> &dst, std::initializer_list<const Ope
   return dst.upload(h);
 }
 
+// The update kernel hard-codes the sensor of eles_tris::shock_det_persson (src/eles_tris.cpp:472-524): every mode norm one, the
+// numerator's modes exactly those of total degree p, j >= p (p + 1) / 2.  nullptr: the registration (as hfx_eles_set_shock_capture
+// kept it on the host) has that form; else what differs
+static const char *shock_form_refusal(const hfx_eles *e)
+{
+  const int nu = e->n_upts, first = simplex2d_first_high_mode(nu);
+  if ((int)e->h_persson_den.size() != nu || (int)e->h_persson_num.size() != nu) return "no registration is kept on the host";
+  for (int j = 0; j < nu; j++)
+    if (e->h_persson_den[j] != 1.0) return "a norm_basis_persson entry is not 1";
+  for (int j = 0; j < nu; j++)
+    if ((e->h_persson_num[j] != 0.0) != (j >= first)) return "high_modes is not the set of the modes of total degree p, j >= p (p + 1) / 2";
+  return nullptr;
+}
+
 static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
 {
   HFX_CHECK(e->n_fields == 4, "2-D simplex fused stage: Navier-Stokes / Euler blocks only; run per method (fused 0)");
@@ -510,18 +622,31 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
             e->n_upts, e->n_fpts);
   HFX_CHECK(!e->les_ready, "2-D simplex fused stage: a registered LES closure runs per method (fused 0)");
   HFX_CHECK(!e->over_int_ready, "2-D simplex fused stage: registered over-integration runs per method (fused 0)");
-  HFX_CHECK(!e->shock_ready, "2-D simplex fused stage: registered shock capturing runs per method (fused 0)");
+  if (e->shock_ready)
+  {
+    const char *why = shock_form_refusal(e);
+    HFX_CHECK(!why, "2-D simplex fused stage: registered shock capturing that is not the triangle's own sensor (eles_tris::shock_det_persson: %s) "
+                    "runs per method (fused 0)", why);
+    HFX_CHECK(e->inv_vandermonde.present() && e->exp_filter.present(), "2-D simplex fused stage: shock capturing without its operators");
+  }
   const bool visc = e->ctx->params.viscous != 0;
   HFX_CHECK(!visc || e->viscous_ops, "2-D simplex fused stage: viscous run but the block has no opp_4/5/6");
   for (const Operator *op : {&e->opp_0, &e->opp_3, &e->opp_1[0], &e->opp_1[1], &e->opp_2[0], &e->opp_2[1]})
     HFX_CHECK(op->present(), "2-D simplex fused stage: an operator is missing");
   if (!e->simplex2d) e->simplex2d.reset(new Simplex2dData());
   Simplex2dData *g = e->simplex2d.get();
+  g->built = false; // (until every table below is this registration's)
   const size_t nu = e->n_upts, nfp = e->n_fpts;
   if (packed_operators(g->element_ops, {&e->opp_4[0], &e->opp_4[1], &e->opp_5[0], &e->opp_5[1], &e->opp_6, &e->opp_0, &e->opp_2[0], &e->opp_2[1], &e->opp_1[0], &e->opp_1[1]},
                        {nu * nu, nu * nu, nu * nfp, nu * nfp, nfp * nu, nfp * nu, nu * nu, nu * nu, nfp * nu, nfp * nu}))
     return 1;
   if (packed_operators(g->update_ops, {&e->opp_3, &e->opp_0}, {nu * nfp, nfp * nu})) return 1;
+  g->shock = false;
+  g->update_shock_ops.reset();
+  if (e->shock_ready && packed_operators(g->update_shock_ops, {&e->opp_3, &e->opp_0, &e->inv_vandermonde, &e->exp_filter}, {nu * nfp, nfp * nu, nu * nu, nu * nu}))
+    return 1;
+  g->shock = e->shock_ready;
+  g->shock_serial = e->shock_serial;
   // per flux point: the LDG switch of the pair it is the LEFT point of (exact tests on the left normal, decided once), whether a
   // boundary face owns it, and its partner word; every flux point must belong to exactly one registered face
   const long plane_f = (long)nfp * e->n_eles;
@@ -619,7 +744,9 @@ int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
   // run on the tables of the stage before)
   HFX_CHECK(!e->ctx->params.viscous || e->viscous_ops, "2-D simplex fused stage: viscous run but the block has no opp_4/5/6");
   const Simplex2dData *g = e->simplex2d.get();
-  if (g && g->built && !e->les_ready && !e->over_int_ready && !e->shock_ready && g->built_with.size() == (size_t)nfb &&
+  // (shock capturing: the tables are those of the registration they were made from; a later one, conforming or not, rebuilds them)
+  if (g && g->built && !e->les_ready && !e->over_int_ready && g->shock == e->shock_ready && g->shock_serial == e->shock_serial &&
+      g->built_with.size() == (size_t)nfb &&
       std::equal(g->built_with.begin(), g->built_with.end(), faces))
     return 0;
   return simplex2d_build(e, faces, nfb);
@@ -635,8 +762,13 @@ Simplex2dPlan simplex2d_plan(const hfx_eles *e)
   pl.gather = e->ctx->opt.gather_delta && e->ctx->params.viscous && e->simplex2d && (e->simplex2d->any_int || e->simplex2d->remote_face);
   pl.element_lds = simplex2d_element_lds_bytes(s[0], s[1], s[2]);
   pl.update_lds = simplex2d_update_lds_bytes(s[0], s[1], s[2]);
+  pl.update_shock_lds = simplex2d_update_lds_bytes(s[0], s[1], s[2], true);
+  const Simplex2dData *g = e->simplex2d.get();
+  pl.fold_shock = e->ctx->opt.fold_shock && e->shock_ready && g && g->built && g->shock && g->shock_serial == e->shock_serial;
   return pl;
 }
+
+bool simplex2d_folds_shock(const hfx_eles *e) { return is_simplex2d(e) && simplex2d_plan(e).fold_shock; }
 
 Simplex2dPartitionPlan simplex2d_partition_plan(const hfx_eles *e)
 {
@@ -686,12 +818,15 @@ static S2dArgs s2d_args(hfx_eles *e, const Simplex2dPlan &pl, int in_step, S2dLi
   // (low-storage schemes: a stage whose RK_a is 0.0 -- the first of a step -- takes 0.0 for the register instead of reading it)
   a.need_u1 = (p.adv_type >= 3 && a.rk_a != 0.0) || (p.adv_type == 1 && in_step == 3) || (p.adv_type == 2 && in_step == 2);
   a.write_div = 1; // the element kernel left the discontinuous part there: always complete it (the monitors read it)
+  a.sens_field = e->shock_det_field == 0 ? 0 : e->n_dims + 1;
+  a.s0 = e->s0;
+  a.sensor = e->arr[HFX_SENSOR];
   return a;
 }
 
 // the instantiation of the plan's size class (SIMPLEX2D_SIZES[I], I counting up)
 template <int I = 0>
-static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool element)
+static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool element, bool shock = false)
 {
   if constexpr (I == N_SIMPLEX2D_SIZES)
   {
@@ -700,10 +835,12 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
   }
   else
   {
-    if (pl.size_class != I) return launch_s2d<I + 1>(e, a, pl, element);
+    if (pl.size_class != I) return launch_s2d<I + 1>(e, a, pl, element, shock);
     constexpr int NU = SIMPLEX2D_SIZES[I][0], NFP = SIMPLEX2D_SIZES[I][1], G = SIMPLEX2D_SIZES[I][2];
-    const size_t lds = element ? pl.element_lds : pl.update_lds;
-    a.ops = element ? e->simplex2d->element_ops : e->simplex2d->update_ops;
+    const size_t lds = element ? pl.element_lds : shock ? pl.update_shock_lds : pl.update_lds;
+    HFX_CHECK(lds <= SIMPLEX2D_LDS_BUDGET, "2-D simplex fused stage: an LDS image of %zu bytes exceeds the budget of %zu", lds, SIMPLEX2D_LDS_BUDGET);
+    a.ops = element ? e->simplex2d->element_ops : shock ? e->simplex2d->update_shock_ops : e->simplex2d->update_ops;
+    HFX_CHECK(a.ops && (!shock || a.sensor), "2-D simplex fused stage: a table of the launch is missing");
     // as many workgroups as are resident (LDS; at most 8 of four waves), walking the groups grid-stride
     const long per_cu = std::max<long>(1, std::min<long>(8, (long)(160 * 1024 / lds)));
     const long work = a.groups ? a.n_list : a.n_groups; // the groups this launch walks
@@ -714,7 +851,9 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
       HFX_HIP(hipGetLastError());
       return 0;
     };
-    return element ? launch(simplex2d_element_kernel_t<NU, NFP, G>) : launch(simplex2d_update_kernel_t<NU, NFP, G>);
+    return element ? launch(simplex2d_element_kernel_t<NU, NFP, G>)
+           : shock ? launch(simplex2d_update_kernel_t<NU, NFP, G, true>)
+                   : launch(simplex2d_update_kernel_t<NU, NFP, G, false>);
   }
 }
 
@@ -785,11 +924,13 @@ int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb)
   return 0;
 }
 
-int simplex2d_update_kernel(hfx_eles *e, int in_step, S2dList list)
+int simplex2d_update_kernel(hfx_eles *e, int in_step, S2dList list, bool shock)
 {
   if (s2d_list_empty(e, list)) return 0;
   const Simplex2dPlan pl = simplex2d_plan(e);
-  if (launch_s2d(e, s2d_args(e, pl, in_step, list), pl, false)) return 1;
+  const bool fold = shock && pl.fold_shock;
+  if (launch_s2d(e, s2d_args(e, pl, in_step, list), pl, false, fold)) return 1;
+  if (fold) e->stale &= ~(1u << HFX_SENSOR); // (both lists of a partitioned stage together write every element's)
   if (list == S2dList::all) simplex2d_swap_disu_fpts(e);
   return 0;
 }
@@ -809,6 +950,7 @@ void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes)
   if (visc) bytes[1] += ne * (8.0 * ((pl.gather ? 2 : 1) * nfp * nf + nu + nfp * (nd * nd + 1) + nfp * nd + nfp * nf) + (pl.gather ? 4.0 * nfp : 0.0));
   bytes[2] += ne * (8.0 * (nfp * nf + (visc ? nfp * nf : 0.0) + 0.5 * nfp * nd + nfp + nfp * nf) + 4.0 * nfp); // disu, Fn, normal(left), tdA r; tconf w
   bytes[3] += ne * 8.0 * (3 * nu * nf + nu + 2 * nfp * nf + 3 * nu * nf + nfp * nf);                          // u0,u1,div,detjac,tconf,ntd r; u0,u1,div,disu w
+  if (pl.fold_shock) bytes[3] += ne * 8.0; // the folded shock filter: sensor w (the state it filters is the group's in LDS)
 }
 
 } // namespace hfx
@@ -821,6 +963,21 @@ extern "C" int hfx_simplex2d_plan(hfx_eles *e, int out[8])
   const hfx::Simplex2dPlan pl = hfx::simplex2d_plan(e);
   const int v[8] = {pl.size_class, pl.group, pl.waves, pl.gather, (int)pl.element_lds, (int)pl.update_lds, 0, 0};
   for (int i = 0; i < 8; i++) out[i] = v[i];
+  return 0;
+}
+
+extern "C" int hfx_simplex2d_shock_plan(hfx_eles *e, int out[4])
+{
+  HFX_CHECK(e && out, "hfx_simplex2d_shock_plan: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  HFX_CHECK(e->simplex2d && e->simplex2d->built, "hfx_simplex2d_shock_plan: no 2-D simplex fused stage has prepared this block (run fused 4 first)");
+  const hfx::Simplex2dPlan pl = hfx::simplex2d_plan(e);
+  out[0] = pl.fold_shock;
+  out[1] = (int)(pl.fold_shock ? pl.update_shock_lds : pl.update_lds);
+  out[2] = hfx::simplex2d_first_high_mode(e->n_upts);
+  // behind a stage that does not fold a registered filter (general_shock_capture): two dense contractions, the sensor and the
+  // selection kernel, and the extrapolation of the filtered state
+  out[3] = (e->shock_ready && !pl.fold_shock) ? 5 : 0;
   return 0;
 }
 

@@ -13,13 +13,28 @@ constexpr int N_SIMPLEX2D_SIZES = sizeof(SIMPLEX2D_SIZES) / sizeof(SIMPLEX2D_SIZ
 constexpr int SIMPLEX2D_WAVES = 4;
 // LDS image of a workgroup (doubles): the operators, staged once per workgroup, then a group's planes [row][element + 1 pad][.]
 constexpr size_t simplex2d_element_ops(int nu, int nfp) { return (size_t)4 * nu * nu + (size_t)6 * nu * nfp; } // o4 o5 o6 o0 o2 o1
-constexpr size_t simplex2d_update_ops(int nu, int nfp) { return (size_t)2 * nu * nfp; }                       // o3 o0
+// (shock: the update kernel with the shock filter folded in stages inv_vandermonde and exp_filter behind them)
+constexpr size_t simplex2d_update_ops(int nu, int nfp, bool shock = false) { return (size_t)2 * nu * nfp + (shock ? (size_t)2 * nu * nu : 0); } // o3 o0 [iv ef]
 constexpr size_t simplex2d_element_lds_bytes(int nu, int nfp, int g) { return sizeof(double) * (simplex2d_element_ops(nu, nfp) + (size_t)(g + 1) * (12 * nu + 4 * nfp)); }
-constexpr size_t simplex2d_update_lds_bytes(int nu, int nfp, int g) { return sizeof(double) * (simplex2d_update_ops(nu, nfp) + (size_t)(g + 1) * (4 * nu + 4 * nfp)); }
+// (shock: + the squared modal coefficients [element + 1 pad][mode] and the group's sensors)
+constexpr size_t simplex2d_update_lds_bytes(int nu, int nfp, int g, bool shock = false)
+{
+  return sizeof(double) * (simplex2d_update_ops(nu, nfp, shock) + (size_t)(g + 1) * (4 * nu + 4 * nfp + (shock ? nu + 1 : 0)));
+}
+constexpr size_t SIMPLEX2D_LDS_BUDGET = 80 * 1024; // two workgroups per CU
+// the first mode of total degree p on a triangle of order p with nu = (p + 1)(p + 2) / 2 solution points: p (p + 1) / 2 -- the
+// modes the sensor of eles_tris::shock_det_persson sums in its numerator
+constexpr int simplex2d_first_high_mode(int nu)
+{
+  int p = 0;
+  while ((p + 1) * (p + 2) / 2 < nu) p++;
+  return p * (p + 1) / 2;
+}
 constexpr bool simplex2d_sizes_fit()
 {
   bool ok = true;
-  for (const auto &s : SIMPLEX2D_SIZES) ok = ok && simplex2d_element_lds_bytes(s[0], s[1], s[2]) <= 80 * 1024; // two workgroups per CU
+  for (const auto &s : SIMPLEX2D_SIZES)
+    ok = ok && simplex2d_element_lds_bytes(s[0], s[1], s[2]) <= SIMPLEX2D_LDS_BUDGET && simplex2d_update_lds_bytes(s[0], s[1], s[2], true) <= SIMPLEX2D_LDS_BUDGET;
   return ok;
 }
 static_assert(simplex2d_sizes_fit(), "a group of an instantiated triangle order no longer leaves room for two workgroups per CU");
@@ -32,6 +47,10 @@ struct Simplex2dPlan
   int waves = SIMPLEX2D_WAVES;
   bool gather = false; // the element kernel forms the LDG corrections of interior points itself (option gather_delta, viscous)
   size_t element_lds = 0, update_lds = 0;
+  // the block registered shock capturing in the form of eles_tris::shock_det_persson and option fold_shock is on: a stage that
+  // eles::shock_capture follows runs the update kernel's SHOCK instantiation (LDS image update_shock_lds) and no filter behind it
+  bool fold_shock = false;
+  size_t update_shock_lds = 0;
 };
 
 // The partitioned stage's side of the plan (general_partitioned_stage, comm.hip): the kernels walk GROUPS of `group` consecutive
@@ -59,7 +78,10 @@ int simplex2d_element_kernel(hfx_eles *e, int in_step, S2dList list = S2dList::a
 int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb);
 // S2dList::all: then the disu_fpts buffers change places; a launch on a list leaves that to simplex2d_swap_disu_fpts, called once
 // behind both lists' launches
-int simplex2d_update_kernel(hfx_eles *e, int in_step, S2dList list = S2dList::all);
+// shock: eles::shock_capture follows this stage (folded into the launch where the plan says fold_shock; else the caller runs it)
+int simplex2d_update_kernel(hfx_eles *e, int in_step, S2dList list = S2dList::all, bool shock = true);
+// the stage's update kernel carries the block's shock filter: nothing runs behind the stage for it
+bool simplex2d_folds_shock(const hfx_eles *e);
 void simplex2d_swap_disu_fpts(hfx_eles *e);
 // the projected viscous flux array of the block (what a partition face sends)
 const double *simplex2d_fn_fpts(const hfx_eles *e);

@@ -659,6 +659,13 @@ class Eles:
         check(lib().hfx_simplex2d_partition_plan(self.h, out))
         return dict(zip(("partition_groups", "interior_groups", "gather_remote"), list(out)))
 
+    def simplex2d_shock_plan(self):
+        """shock capturing on this block of triangles in the 2-D simplex fused stage (hfx_simplex2d_shock_plan), valid after a fused-4
+        call: dict of folded, update_lds (of the update kernel that runs), first_high_mode, launches_behind"""
+        out = (C.c_int * 4)()
+        check(lib().hfx_simplex2d_shock_plan(self.h, out))
+        return dict(zip(("folded", "update_lds", "first_high_mode", "launches_behind"), list(out)))
+
     def time_integral_quantities(self, reps=20):
         v = C.c_double(0)
         check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))
@@ -973,6 +980,53 @@ def CalcResidual(eles, faces):
 
 def run_steps(eles, faces, n_steps, fused=False):
     check(lib().hfx_run_steps(eles.h, _face_array(faces), C.c_int(len(faces)), C.c_int(n_steps), C.c_int(int(fused))))
+
+
+def _jacobi_normalized(x, alpha, beta, n):
+    """the orthonormal Jacobi polynomial P_n^(alpha, beta) at x by its three-term recurrence (eval_jacobi, src/funcs.cpp:1245)"""
+    import math
+    x = np.asarray(x, dtype=np.float64)
+    g = lambda m: float(math.factorial(m - 1))  # (Gamma at a positive integer: eval_gamma)
+    p0 = math.sqrt(2.0 ** (-alpha - beta - 1) * g(alpha + beta + 2) / (g(alpha + 1) * g(beta + 1))) * np.ones_like(x)
+    if n == 0:
+        return p0
+    p1 = 0.5 * p0 * math.sqrt((alpha + beta + 3.0) / ((alpha + 1.0) * (beta + 1.0))) * (x * (alpha + beta + 2) + (alpha - beta))
+
+    def a(m):
+        return 2.0 / (2 * m + alpha + beta) * math.sqrt(m * (m + alpha + beta) * (m + alpha) * (m + beta) / ((2 * m + alpha + beta - 1.0) * (2 * m + alpha + beta + 1.0)))
+
+    for m in range(2, n + 1):
+        b = -(alpha * alpha - beta * beta) / ((2 * (m - 1) + alpha + beta) * (2 * (m - 1) + alpha + beta + 2.0))
+        p0, p1 = p1, ((x - b) * p1 - a(m - 1) * p0) / a(m)
+    return p1
+
+
+def tri_shock_operators(loc_upts, order, expf_fac, expf_order, expf_cutoff):
+    """What a block of triangles registers for shock capturing (Eles.set_shock_capture), built as eles_tris does (set_vandermonde,
+    set_exp_filter, shock_det_persson; src/eles_tris.cpp:432-524) from the solution points loc_upts (2, n_upts) of the reference
+    triangle: the orthonormal Dubiner basis (eval_dubiner_basis_2d, src/funcs.cpp:1318), modes by total degree k = 0..order and
+    within k by j = 0..k (i = k - j); sigma = 1 for k / order <= expf_cutoff / order, else exp(-expf_fac ((eta - eta_c) / (1 - eta_c))
+    ^ expf_order).  -> (inv_vandermonde, exp_filter, norm_basis_persson (ones), high_modes (1 for the modes of degree `order`)).
+    Host set-up only: nothing on the stepping path calls it."""
+    r, s = np.asarray(loc_upts, dtype=np.float64).reshape(2, -1)
+    nu = (order + 1) * (order + 2) // 2
+    assert r.size == nu, (r.size, nu)
+    a = np.where(s == 1.0, -1.0, 2.0 * (1.0 + r) / np.where(s == 1.0, 1.0, 1.0 - s) - 1.0)  # rs_to_ab
+    V = np.zeros((nu, nu))
+    sigma = np.zeros(nu)
+    high = np.zeros(nu, dtype=np.int32)
+    eta_c = float(expf_cutoff) / float(order)
+    mode = 0
+    for k in range(order + 1):
+        for j in range(k + 1):
+            i = k - j
+            V[:, mode] = np.sqrt(2.0) * _jacobi_normalized(a, 0, 0, i) * _jacobi_normalized(s, 2 * i + 1, 0, j) * (1.0 - s) ** i
+            eta = float(k) / float(order)
+            sigma[mode] = 1.0 if eta <= eta_c else np.exp(-expf_fac * ((eta - eta_c) / (1.0 - eta_c)) ** expf_order)
+            high[mode] = int(k == order)
+            mode += 1
+    Vinv = np.linalg.inv(V)
+    return np.asfortranarray(Vinv), np.asfortranarray(V @ (sigma[:, None] * Vinv)), np.ones(nu), high
 
 
 def params_from(data):

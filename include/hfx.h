@@ -741,7 +741,12 @@ int hfx_eles_evaluate_invFlux_over_int(hfx_eles *e); /* eles::evaluate_invFlux_o
 /* Registers what eles_hexas / eles_quads build when run_input.shock_cap == 1 (src/eles_hexas.cpp:74-85):
  * inv_vandermonde (n_upts,n_upts), exp_filter (n_upts,n_upts), norm_basis_persson (n_upts), and
  * high_modes(j) = 1 where a 1-D index of Legendre mode j equals the order (the set summed in
- * shock_det_persson, src/eles_hexas.cpp:1042-1047); s0 and shock_det_field are run_input's. */
+ * shock_det_persson, src/eles_hexas.cpp:1042-1047); s0 and shock_det_field are run_input's.
+ * A block of TRIANGLES registers what eles_tris builds (src/eles_tris.cpp:432-469): inv_vandermonde of the orthonormal Dubiner
+ * basis at the solution points (modes by total degree k, within k by j = 0..k), exp_filter = V sigma V^-1, norm_basis_persson all
+ * ones and high_modes(j) = 1 exactly for j >= p (p + 1) / 2, the modes of total degree p (eles_tris::shock_det_persson,
+ * src/eles_tris.cpp:472-524).  The 2-D simplex fused stage folds exactly this form into its update kernel
+ * (hfx_simplex2d_shock_plan); the per-method call below takes any registration. */
 int hfx_eles_set_shock_capture(hfx_eles *e, const double *inv_vandermonde, const double *exp_filter,
                                const double *norm_basis_persson, const int *high_modes, double s0, int shock_det_field);
 /* eles::shock_capture (src/eles.cpp:2918-2959), shock_det 0 (Persson) + shock_cap 1 (exponential modal
@@ -822,6 +827,10 @@ int hfx_run_steps(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int 
  * calc_sgs_terms before the first stage of a step), over-integration forms tdisf_upts by the dense contractions and the flux kernel
  * takes it, shock capturing follows every stage (the filter, then disu_fpts of the filtered state); a closure TOGETHER with
  * over-integration is refused (run fused 0).
+ * ONE block of triangles (orders 1-5; no LES or over-integration) runs the 2-D simplex fused stage (csrc/simplex2d.hip), at most
+ * four launches per stage.  Shock capturing registered in the form of eles_tris::shock_det_persson (below) runs INSIDE its update
+ * kernel: sensor, filter and the flux-point solution of the filtered state in the stage's last launch (option "fold_shock" 0: the
+ * per-method filter behind the stage, as on tetrahedra); any other registration is refused before the first launch (run fused 0).
  * A block with one element class may of course be passed alone (hfx_run_steps(e, ..., 4) is the same call). */
 int hfx_run_steps_blocks(hfx_eles *const *eles, int n_ele_blocks, hfx_inters *const *faces, int n_face_blocks, int n_steps,
                          int fused);
@@ -910,7 +919,8 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
  * Three-dimensional blocks as hfx_run_steps_blocks(..., 4) takes them -- an LES closure is evaluated in the
  * flux kernel (its F_sgs . n travels inside Fn: no third message; the SVV closure is refused here), over-integration feeds it,
  * shock capturing follows the update before the next solution message is packed.
- * ONE block of triangles (orders 1-5; no LES, over-integration or shock capturing) runs the 2-D simplex fused stage, interior
+ * ONE block of triangles (orders 1-5; no LES or over-integration; shock capturing in the triangle's own form is folded into the
+ * update kernel, so the partition groups' filtered flux-point solution is what is packed) runs the 2-D simplex fused stage, interior
  * groups first: the element and the update kernel walk the groups without a partition flux point beside the solution message, the
  * groups with one behind it (hfx_simplex2d_partition_plan); with one partition-face block the element kernel reads the partners
  * of partition points from the receive record itself.  hfx_run_steps_blocks(..., 4) keeps refusing a partition-face block.
@@ -986,6 +996,13 @@ int hfx_simplex2d_plan(hfx_eles *e, int out[8]);
  * record itself (option gather_delta, one partition-face block), 0: mpi_delta_kernel writes their LDG corrections, out[3] 0.
  * A block prepared by hfx_run_steps_blocks(..., 4) has no partition groups. */
 int hfx_simplex2d_partition_plan(hfx_eles *e, int out[4]);
+/* Shock capturing on a block of triangles behind / inside the 2-D simplex fused stage (read-only; valid once a fused-4 call or a
+ * deferred stage has prepared the block, refused before): out[0] 1: the update kernel carries the filter (the registration has the
+ * form of eles_tris::shock_det_persson and option "fold_shock" is 1), out[1] bytes of the LDS image of the update kernel that runs
+ * (with the filter: + inv_vandermonde, exp_filter, a group's squared modal coefficients and sensors), out[2] the first mode the
+ * sensor's numerator sums, p (p + 1) / 2, out[3] per-method launches behind every stage for the filter (0 when folded or nothing is
+ * registered; else the two dense contractions, the sensor and the selection kernel and extrapolate_solution). */
+int hfx_simplex2d_shock_plan(hfx_eles *e, int out[4]);
 
 #ifdef __cplusplus
 }
