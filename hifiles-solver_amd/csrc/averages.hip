@@ -9,7 +9,7 @@
 // Not built: the reference stops with "NaN in average value" (src/eles.cpp:5698).  An average is a * average + b * current of
 // a zero-initialised array, so a NaN average means a NaN state, and the residual's scan already reports that
 // (hfx_eles_check_nan); the kernel stays free of a flag and of the atomic that sets it.
-#include "hfx_internal.hpp"
+#include "step_loop.hpp"
 
 namespace hfx
 {
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void time_average_kernel(const AverageArgs A)
 }
 
 // one update of e's averages on the compute stream
-static int launch_time_average(hfx_eles *e, double time, double spinup_time)
+int launch_time_average(hfx_eles *e, double time, double spinup_time)
 {
   hfx_ctx *ctx = e->ctx;
   if (e->n_average_fields == 0 || e->n_eles == 0) return 0;
@@ -138,30 +138,6 @@ static int launch_time_average(hfx_eles *e, double time, double spinup_time)
   else
     hipLaunchKernelGGL(time_average_kernel<1>, grid, block, 0, ctx->stream, A);
   HFX_HIP(hipGetLastError());
-  return 0;
-}
-
-int end_of_step(hfx_eles *const *eles, int neb)
-{
-  hfx_ctx *ctx = eles[0]->ctx;
-  if (!ctx->have_clock) return 0;
-  ctx->time += ctx->params.dt; /* src/HiFiLES.cpp:221-223 */
-  ctx->i_steps++;
-  if (ctx->i_steps == 1) ctx->spinup_time = ctx->time; /* src/HiFiLES.cpp:242-243 */
-  for (int i = 0; i < neb; i++)
-    if (launch_time_average(eles[i], ctx->time, ctx->spinup_time)) return 1;
-  if (ctx->n_probe_fields > 0 && ctx->i_steps % ctx->probe_freq == 0) /* src/HiFiLES.cpp:289-297 */
-    for (int i = 0; i < neb; i++)
-      if (sample_probes(eles[i], ctx->time, ctx->i_steps)) return 1;
-  if (integral_monitor_samples(ctx, ctx->i_steps)) /* src/HiFiLES.cpp:247-266 */
-    for (int i = 0; i < neb; i++)
-      if (sample_integrals(eles[i], ctx->time, ctx->i_steps)) return 1;
-  if (history_monitor_samples(ctx, ctx->i_steps))
-    for (int i = 0; i < neb; i++)
-      if (sample_history(eles[i], ctx->time, ctx->i_steps)) return 1;
-  if (plot_monitor_samples(ctx, ctx->i_steps)) /* src/HiFiLES.cpp:273-285 */
-    for (int i = 0; i < neb; i++)
-      if (sample_plot(eles[i], ctx->time, ctx->i_steps)) return 1;
   return 0;
 }
 

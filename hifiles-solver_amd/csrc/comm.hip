@@ -21,7 +21,7 @@
 #include "general.hpp"
 #include "simplex2d.hpp"
 #include "split_common.hpp"
-#include "hfx_internal.hpp"
+#include "step_loop.hpp"
 
 namespace hfx
 {
@@ -193,26 +193,6 @@ static void mark_drained(hfx_eles *const *eles, int n)
     eles[i]->fpts_sent = false;
     eles[i]->sent_on = 0;
   }
-}
-
-// calc_time_step (src/solver.cpp:484-549): per-element CFL steps, minimum over the block and over the ranks
-int calc_time_step(hfx_eles *e, hfx_comm *comm)
-{
-  hfx_ctx *ctx = e->ctx;
-  if (ctx->params.dt_type != 1 && ctx->params.dt_type != 2) return 0;
-  HFX_CHECK(ctx->have_CFL, "dt_type %d needs run_input.CFL: call hfx_ctx_set_CFL", ctx->params.dt_type);
-  double dt_min = 0.0;
-  if (hfx_eles_calc_dt_local(e, ctx->CFL, &dt_min)) return 1;
-  if (comm && comm->nranks > 1 && hfx_comm_allreduce(comm, &dt_min, 1, 0)) return 1;
-  ctx->params.dt = dt_min;
-  return 0;
-}
-
-// run_input.ramp_counter++ after a time step when a boundary group ramps (src/HiFiLES.cpp:224-225)
-void advance_ramp_counters(hfx_inters *const *faces, int nfb)
-{
-  for (int b = 0; b < nfb; b++)
-    if (faces[b]->is_bdy && faces[b]->any_ramp) faces[b]->ramp_counter++;
 }
 
 struct StageTimers
@@ -507,64 +487,32 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
   return start_exchange(comm, mpi_faces, n_mpi, 0, false);
 }
 
-// The integral monitor inside a partitioned loop: a quantity that reads grad_disu_upts would need the last stage of a sampled step run
-// call by call with messages in flight, which is not built.  Asked before the first launch: does the loop sample (the clock is the
-// library's) a block that has a cubature with an id 1-4?
-static const char *const MONITOR_PARTITIONED =
-    "partitioned step loop: the integral monitor has a quantity that reads grad_disu_upts (ids 1-4), and the stages of this loop keep the "
-    "gradient on chip; run it with fused mode 2 (hfx_ctx_set_fused_mode), or monitor the kinetic energy (id 0) alone";
-// the same for the history monitor's viscous wall forces (history.hip)
-static const char *const HISTORY_PARTITIONED =
-    "partitioned step loop: the history monitor samples the viscous wall forces, which read grad_disu_upts, and the stages of this loop "
-    "keep the gradient on chip; run it with fused mode 2 (hfx_ctx_set_fused_mode), or monitor the residuals alone (with_forces 0)";
-// the same for the plot monitor's vorticity and Q criteria (plot_fields.hip)
-static const char *const PLOT_PARTITIONED =
-    "partitioned step loop: the plot monitor has a field that reads grad_disu_upts (vorticity, q_criterion, scaled_q_criterion), and the "
-    "stages of this loop keep the gradient on chip; run it with fused mode 2 (hfx_ctx_set_fused_mode), or plot gradient-free fields alone";
-// nullptr: no monitor of this loop reads the gradient; else the refusal of a loop that keeps it on chip
-static const char *monitor_gradient_on_chip(hfx_eles *const *eles, int neb)
+// the exchange started after the last stage belongs to a stage that is not run: the compute stream waits for it so that nothing is in
+// flight when the caller reads or changes the state (a following call starts over with a first stage that posts)
+static int drain(hfx_eles *const *eles, int neb, hfx_comm *comm, int n_mpi)
 {
-  const hfx_ctx *ctx = eles[0]->ctx;
-  if (!ctx->have_clock || !monitor_reads_gradient(eles, neb)) return nullptr;
-  for (int i = 0; i < neb; i++)
-    if (history_monitor_reads_gradient(eles[i])) return HISTORY_PARTITIONED;
-  for (int i = 0; i < neb; i++)
-    if (plot_monitor_reads_gradient(eles[i])) return PLOT_PARTITIONED;
-  return MONITOR_PARTITIONED;
+  if (wait_exchange(comm, 0, n_mpi)) return 1;
+  mark_drained(eles, neb);
+  return 0;
 }
 
-// the loop of hfx_run_steps_partitioned / hfx_time_partitioned.  n_stages_total < 0: n_steps whole time steps
-static int run_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi,
-                           hfx_comm *comm, int n_steps, int n_stages_total, StageTimers *T)
+// the stages of hfx_time_partitioned: `reps` stages of consecutive time steps with the timers, calc_time_step in front of every step and
+// the ramp counters behind it (behind a partial last one too); no body force, no clock, no samples
+static int time_partitioned_stages(hfx_eles *e, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces, int n_mpi,
+                                   hfx_comm *comm, int reps, StageTimers *T)
 {
-  hfx_ctx *ctx = e->ctx;
   if (check_partition_blocks(&e, 1, mpi_faces, n_mpi, comm)) return 1;
-  const int nst = n_rk_stages(ctx->params);
-  // a partitioned fused stage of the deferred path may have left this state's flux-point solution on its way already: the
-  // first stage takes it instead of posting it again (the messages a rank posts follow its calls, not what ran deferred)
-  bool first = !sent_over(e, comm);
-  int done = 0;
-  for (int s = 0; n_stages_total >= 0 ? done < n_stages_total : s < n_steps; s++)
+  const int nst = n_rk_stages(e->ctx->params);
+  bool first = !sent_over(e, comm); // (as hfx_run_steps_partitioned)
+  for (int done = 0; done < reps; done++)
   {
-    if (calc_time_step(e, comm)) return 1; /* src/HiFiLES.cpp:198 */
-    // the mass-flux body force (src/solver.cpp:96-109; not for hfx_time_partitioned): its integrals are summed over the ranks.  It reads
-    // disu_upts(0) and writes src_upts on the compute stream; the solution exchange in flight reads the packed flux-point values
-    if (n_stages_total < 0 && begin_of_step(&e, 1, comm)) return 1;
-    for (int rk = 0; rk < nst && (n_stages_total < 0 || done < n_stages_total); rk++, done++)
-    {
-      if (partitioned_stage(e, int_faces, n_int, mpi_faces, n_mpi, comm, rk, first, T)) return 1;
-      first = false;
-    }
-    advance_ramp_counters(int_faces, n_int);
-    // the clock and the time averages (src/HiFiLES.cpp:221-245; not for hfx_time_partitioned).  The update kernel reads disu_upts(0)
-    // alone, on the compute stream: the solution exchange the stage left in flight reads the packed flux-point values
-    if (n_stages_total < 0 && end_of_step(&e, 1)) return 1;
+    const int rk = done % nst;
+    if (rk == 0 && calc_time_step_blocks(&e, 1, comm)) return 1;
+    if (partitioned_stage(e, int_faces, n_int, mpi_faces, n_mpi, comm, rk, first, T)) return 1;
+    first = false;
+    if (rk == nst - 1 || done == reps - 1) advance_ramp_counters(int_faces, n_int);
   }
-  // the exchange started after the last stage belongs to a stage that is not run: the compute stream waits for it so
-  // that nothing is in flight when the caller reads or changes the state (a following call starts over with `first`)
-  if (wait_exchange(comm, 0, n_mpi)) return 1;
-  mark_drained(&e, 1);
-  return 0;
+  return drain(&e, 1, comm, n_mpi);
 }
 
 } // namespace hfx
@@ -770,11 +718,7 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
   HFX_CHECK(e && comm, "hfx_run_steps_partitioned: NULL argument");
   HFX_CHECK(e->ctx->have_params, "parameters not set");
   HFX_IMMEDIATE(e->ctx, 0);
-  if (probes_check_capacity(&e, 1, n_steps)) return 1;
-  if (integrals_check_capacity(&e, 1, n_steps)) return 1;
-  if (history_check_capacity(&e, 1, n_steps)) return 1;
-  if (plot_check_capacity(&e, 1, n_steps)) return 1;
-  if (wall_model_check_points(int_faces, n_int)) return 1;
+  if (step_loop_check(&e, 1, int_faces, n_int, n_steps)) return 1;
   if (const char *refusal = monitor_gradient_on_chip(&e, 1))
   {
     // (a plan of variant 2 writes grad_disu_upts in every stage: everything is sampled)
@@ -782,7 +726,20 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
     if (ensure_fused_tables(e, int_faces, n_int, true) || split_stage_plan(e, int_faces, n_int, e->ctx->fused_mode, &pl)) return 1;
     HFX_CHECK(pl.variant != 3, "%s", refusal);
   }
-  return run_partitioned(e, int_faces, n_int, mpi_faces, n_mpi, comm, n_steps, -1, nullptr);
+  if (check_partition_blocks(&e, 1, mpi_faces, n_mpi, comm)) return 1;
+  // a partitioned fused stage of the deferred path may have left this state's flux-point solution on its way already: the
+  // first stage takes it instead of posting it again (the messages a rank posts follow its calls, not what ran deferred)
+  bool first = !sent_over(e, comm);
+  // (closure none: the stage's first phase filters at stage 0 itself, split_partitioned.hpp.  The body force, the time step and the
+  // samples read disu_upts(0) on the compute stream; the solution exchange a stage leaves in flight reads the packed flux-point values)
+  StepLoop loop{&e, 1, int_faces, n_int, [&](int rk) {
+                  const bool start = first;
+                  first = false;
+                  return partitioned_stage(e, int_faces, n_int, mpi_faces, n_mpi, comm, rk, start, nullptr);
+                }};
+  loop.comm = comm;
+  if (run_step_loop(loop, n_steps)) return 1;
+  return drain(&e, 1, comm, n_mpi); // (after zero steps too)
 }
 
 int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hfx_inters *const *int_faces, int n_int,
@@ -794,51 +751,23 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   HFX_IMMEDIATE(ctx, 0);
   const bool cfl_steps = ctx->params.dt_type == 1 || ctx->params.dt_type == 2;
   HFX_CHECK(!cfl_steps || ctx->have_CFL, "dt_type %d needs run_input.CFL: call hfx_ctx_set_CFL", ctx->params.dt_type);
-  const int nst = n_rk_stages(ctx->params);
-  if (probes_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
-  if (integrals_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
-  if (history_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
-  if (plot_check_capacity(eles, n_ele_blocks, n_steps)) return 1;
-  if (wall_model_check_points(int_faces, n_int)) return 1;
+  if (step_loop_check(eles, n_ele_blocks, int_faces, n_int, n_steps)) return 1;
   if (const char *refusal = monitor_gradient_on_chip(eles, n_ele_blocks)) // (the general stage keeps the gradient on chip)
     HFX_CHECK(false, "%s", refusal);
   for (int i = 0; i < n_ele_blocks; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
-  // (as run_partitioned: the solution a partitioned fused stage has posted for this state is not posted again)
+  // (as hfx_run_steps_partitioned: the solution a partitioned fused stage has posted for this state is not posted again)
   bool start = false;
   for (int i = 0; i < n_ele_blocks; i++) start = start || !sent_over(eles[i], comm);
-  for (int s = 0; s < n_steps; s++)
-  {
-    // calc_time_step (src/solver.cpp:484-549, src/HiFiLES.cpp:198): per-element CFL steps (dt_type 2 keeps them), their minimum
-    // over the blocks and over the ranks.  It reads disu_upts(0) on the compute stream; the solution message in flight reads the
-    // packed flux-point values
-    if (cfl_steps)
-    {
-      if (calc_time_step_blocks(eles, n_ele_blocks)) return 1;
-      if (comm->nranks > 1)
-      {
-        double dt_min = ctx->params.dt;
-        if (hfx_comm_allreduce(comm, &dt_min, 1, 0)) return 1;
-        ctx->params.dt = dt_min;
-      }
-    }
-    if (begin_of_step(eles, n_ele_blocks, comm)) return 1; /* src/solver.cpp:96-109 */
-    for (int rk = 0; rk < nst; rk++)
-    {
-      if (rk == 0 && first_stage_closure_filter(eles, n_ele_blocks, false)) return 1;
-      if (general_partitioned_stage(eles, n_ele_blocks, int_faces, n_int, mpi_faces, n_mpi, comm, rk, start, true)) return 1;
-      start = false;
-    }
-    advance_ramp_counters(int_faces, n_int);
-    if (end_of_step(eles, n_ele_blocks)) return 1; /* src/HiFiLES.cpp:221-245 */
-  }
-  // (nothing in flight when the caller reads or changes the state)
-  if (n_steps > 0)
-  {
-    if (wait_exchange(comm, 0, n_mpi)) return 1;
-    mark_drained(eles, n_ele_blocks);
-  }
-  return 0;
+  StepLoop loop{eles, n_ele_blocks, int_faces, n_int, [&](int rk) {
+                  const bool post = start;
+                  start = false;
+                  return general_partitioned_stage(eles, n_ele_blocks, int_faces, n_int, mpi_faces, n_mpi, comm, rk, post, true);
+                }};
+  loop.closure = ClosureFilter::filtering; // (partitioned blocks refuse SVV)
+  loop.comm = comm;
+  if (run_step_loop(loop, n_steps)) return 1;
+  return n_steps > 0 ? drain(eles, n_ele_blocks, comm, n_mpi) : 0; // (a call without steps leaves what is in flight as it found it)
 }
 
 int hfx_comm_exchange_stats(hfx_comm *c, long posted[3], long waited[3], int *in_flight, int *stream_busy)
@@ -867,7 +796,7 @@ int hfx_time_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_int, h
   HFX_IMMEDIATE(e->ctx, 0);
   StageTimers T;
   if (T.create()) return 1;
-  const int rc = run_partitioned(e, int_faces, n_int, mpi_faces, n_mpi, comm, 0, reps, &T);
+  const int rc = time_partitioned_stages(e, int_faces, n_int, mpi_faces, n_mpi, comm, reps, &T);
   T.destroy();
   if (rc) return 1;
   for (int i = 0; i < 8; i++) ms[i] = T.acc[i] / reps;

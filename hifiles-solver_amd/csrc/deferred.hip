@@ -25,7 +25,7 @@
 #include "fused_hex.hpp"
 #include "general.hpp"
 #include "split_common.hpp"
-#include "hfx_internal.hpp"
+#include "step_loop.hpp"
 
 namespace hfx
 {

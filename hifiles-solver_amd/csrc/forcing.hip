@@ -10,7 +10,7 @@
 //   add_body_force_kernel src_upts(j, i, k) += body_force(k) for k = 1 and 4, the force read from the record
 // c(k, face) = sum_j weight(j) detjac(j, face) opp_inters_cubpts(j, k) is folded once, at registration, so the per-step integral
 // is a dot product of length n_upts per face and field whatever the cubature.
-#include "hfx_internal.hpp"
+#include "step_loop.hpp"
 
 #include <cmath>
 #include <cstddef>
@@ -269,9 +269,8 @@ static int apply_integrals(hfx_eles *e, const double integral[2])
   return launch_add(e, B.record, 0.0, 0.0);
 }
 
-// eles::evaluate_body_force for one block.  comm: a partitioned loop's communicator -- the integrals are summed over its ranks
-// (src/eles.cpp:5375-5385) by the path of hfx_comm_allreduce, one host round trip; without one nothing leaves the device
-static int evaluate_body_force(hfx_eles *e, hfx_comm *comm)
+// eles::evaluate_body_force for one block, which the step loop calls in front of a step's first stage (step_loop.hpp has the contract)
+int evaluate_body_force(hfx_eles *e, hfx_comm *comm)
 {
   if (!e->body_force || e->n_eles == 0) return 0; /* :5285 */
   if (comm)
@@ -282,13 +281,6 @@ static int evaluate_body_force(hfx_eles *e, hfx_comm *comm)
   }
   if (integrate_inflow(e) || launch_control(e, BF_SUM | BF_CONTROL)) return 1;
   return launch_add(e, e->body_force->record, 0.0, 0.0);
-}
-
-int begin_of_step(hfx_eles *const *eles, int neb, hfx_comm *comm)
-{
-  for (int i = 0; i < neb; i++)
-    if (eles[i]->body_force && evaluate_body_force(eles[i], comm)) return 1;
-  return 0;
 }
 
 // the record of e's controller on the host (waits for the compute stream)

@@ -21,6 +21,7 @@
 // ascending-column order as the reference dgemm (src/funcs.cpp:110-117).
 #include <vector>
 #include "fused_hex.hpp"
+#include "step_loop.hpp"
 #include "tensor_ops.hpp"
 
 #include <algorithm>
@@ -1204,36 +1205,20 @@ int split_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps,
   // (an LES closure that variant 3 cannot evaluate in its flux kernel, and element sizes it does not fit, run variant 2)
   SplitPlan pl;
   if (ensure_fused_tables(e, faces, nfb, false) || split_stage_plan(e, faces, nfb, variant, &pl)) return 1;
-  if (n_steps <= 0) return 0;
+  if (n_steps <= 0) return 0; // (a call without steps prepares the tables and the plan, and leaves the state alone)
   const int nst = n_rk_stages(e->ctx->params);
   if (hfx_eles_extrapolate_solution(e)) return 1;
-  // a monitor that reads grad_disu_upts pairs the state behind a step with the gradient of the last stage's input state (integrals.hip,
-  // history.hip): on a plan that keeps the gradient on chip the last stage of a step such a monitor samples runs call by call
-  hfx_ctx *ctx = e->ctx;
-  const bool monitor_gradient = pl.variant == 3 && monitor_reads_gradient(&e, 1);
+  StepLoop loop{&e, 1, faces, nfb, [&](int rk) {
+                  const auto stage = SplitStage::make(e, faces, nfb, rk, rk == nst - 1, pl);
+                  if (!stage || stage->run()) return 1;
+                  // the filter changes disu_upts(0) after the stage: redo the flux-point solution of the new state
+                  return e->shock_ready ? shock_capture_keep_fpts(e) : 0;
+                }};
+  loop.closure = ClosureFilter::filtering_refresh_svv;
+  // on a plan that keeps the gradient on chip the last stage of a step a gradient-reading monitor samples runs call by call
+  loop.by_calls = pl.variant == 3 && monitor_reads_gradient(&e, 1);
   bool by_calls = false;
-  for (int s = 0; s < n_steps; s++)
-  {
-    if (calc_time_step(e, nullptr)) return 1; /* src/HiFiLES.cpp:198 */
-    if (begin_of_step(&e, 1, nullptr)) return 1; /* src/solver.cpp:96-109 */
-    by_calls = monitor_gradient && monitor_samples(ctx, (long)ctx->i_steps + 1);
-    for (int rk = 0; rk < nst; rk++)
-    {
-      // (the SVV closure replaces the state, whose flux-point values the previous stage's update kernel has already written)
-      if (rk == 0 && first_stage_closure_filter(&e, 1, true)) return 1;
-      if (by_calls && rk == nst - 1)
-      {
-        if (stage_call_by_call(&e, 1, faces, nfb, rk)) return 1;
-        continue;
-      }
-      const auto stage = SplitStage::make(e, faces, nfb, rk, rk == nst - 1, pl);
-      if (!stage || stage->run()) return 1;
-      // the filter changes disu_upts(0) after the stage: redo the flux-point solution of the new state
-      if (e->shock_ready && shock_capture_keep_fpts(e)) return 1;
-    }
-    advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
-    if (end_of_step(&e, 1)) return 1; /* src/HiFiLES.cpp:221-245 */
-  }
+  if (run_step_loop(loop, n_steps, &by_calls)) return 1;
   note_gradients(e, pl.variant != 3 || by_calls);
   return 0;
 }

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "general.hpp"
+#include "step_loop.hpp"
 #include "simplex2d.hpp"
 #include "face_kernels.hpp" // the pairwise kernels (face_delta_kernel<3>, gface_flux_multi_kernel are instantiated here)
 
@@ -1263,35 +1264,16 @@ int general_shock_capture(hfx_eles *const *eles, int neb)
 int general_run_steps(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int n_steps)
 {
   if (general_prepare(eles, neb, faces, nfb)) return 1;
-  if (n_steps <= 0) return 0;
-  const int nst = n_rk_stages(eles[0]->ctx->params);
+  if (n_steps <= 0) return 0; // (a call without steps prepares the blocks' tables and leaves the state alone)
   // disu_fpts of the current state (the caller may have changed disu_upts since the last call)
   for (int i = 0; i < neb; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
-  // as split_run_steps: the last stage of a step a monitor samples that reads grad_disu_upts runs call by call and leaves the
-  // gradient of its input state
-  hfx_ctx *ctx = eles[0]->ctx;
-  const bool monitor_gradient = monitor_reads_gradient(eles, neb);
+  StepLoop loop{eles, neb, faces, nfb, [&](int rk) { return GeneralStage(eles, neb, faces, nfb, rk).run() || general_shock_capture(eles, neb); }};
+  loop.closure = ClosureFilter::filtering_refresh_svv;
+  // the stage keeps the gradient on chip: the last stage of a step a gradient-reading monitor samples runs call by call
+  loop.by_calls = monitor_reads_gradient(eles, neb);
   bool by_calls = false;
-  for (int s = 0; s < n_steps; s++)
-  {
-    if (calc_time_step_blocks(eles, neb)) return 1; /* src/HiFiLES.cpp:198 */
-    if (begin_of_step(eles, neb, nullptr)) return 1; /* src/solver.cpp:96-109 */
-    by_calls = monitor_gradient && monitor_samples(ctx, (long)ctx->i_steps + 1);
-    for (int rk = 0; rk < nst; rk++)
-    {
-      if (rk == 0 && first_stage_closure_filter(eles, neb, true)) return 1;
-      if (by_calls && rk == nst - 1)
-      {
-        if (stage_call_by_call(eles, neb, faces, nfb, rk)) return 1;
-        continue;
-      }
-      if (GeneralStage(eles, neb, faces, nfb, rk).run()) return 1;
-      if (general_shock_capture(eles, neb)) return 1;
-    }
-    advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
-    if (end_of_step(eles, neb)) return 1; /* src/HiFiLES.cpp:221-245 */
-  }
+  if (run_step_loop(loop, n_steps, &by_calls)) return 1;
   for (int i = 0; i < neb; i++) note_gradients(eles[i], by_calls); // (the general stage keeps them on chip)
   return 0;
 }

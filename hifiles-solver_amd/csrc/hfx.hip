@@ -10,7 +10,7 @@
 #include "general.hpp"
 #include "simplex2d.hpp"
 #include "tensor_ops.hpp"
-#include "hfx_internal.hpp"
+#include "step_loop.hpp"
 #include "kernels_ops.hpp"
 #include "kernels_bdy.hpp"
 #include "kernels_mpi.hpp"
@@ -380,29 +380,6 @@ int les_len2_upload(hfx_eles *e, DevBuf<double> &dst)
     len2[p] = l2;
   }
   return dst.upload(len2);
-}
-
-int calc_time_step_blocks(hfx_eles *const *eles, int neb)
-{
-  hfx_ctx *ctx = eles[0]->ctx;
-  if (ctx->params.dt_type != 1 && ctx->params.dt_type != 2) return 0;
-  double dt_min = 1e12;
-  for (int i = 0; i < neb; i++)
-  {
-    if (calc_time_step(eles[i], nullptr)) return 1;
-    dt_min = std::min(dt_min, ctx->params.dt);
-  }
-  ctx->params.dt = dt_min;
-  return 0;
-}
-
-int first_stage_closure_filter(hfx_eles *const *eles, int neb, bool refresh_svv)
-{
-  for (int i = 0; i < neb; i++)
-    if (eles[i]->les_ready && eles[i]->les.sgs_model >= 2 &&
-        (hfx_eles_calc_sgs_terms(eles[i]) || (refresh_svv && eles[i]->les.sgs_model == 3 && hfx_eles_extrapolate_solution(eles[i]))))
-      return 1;
-  return 0;
 }
 } // namespace hfx
 
@@ -1783,62 +1760,30 @@ int hfx_CalcResidual(hfx_eles *e, hfx_inters *const *faces, int nfb)
   return hfx_CalcResidual_blocks(&e, 1, faces, nfb);
 }
 
-} // extern "C"
-
-int hfx::stage_call_by_call(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int rk)
-{
-  const int adv = eles[0]->ctx->params.adv_type;
-  if (hfx_CalcResidual_blocks(eles, neb, faces, nfb)) return 1;
-  for (int i = 0; i < neb; i++)
-    if (hfx_eles_AdvanceSolution(eles[i], rk, adv)) return 1;
-  for (int i = 0; i < neb; i++)
-    if (eles[i]->shock_ready && hfx_eles_shock_capture(eles[i])) return 1; /* src/HiFiLES.cpp:214-216 */
-  // (the update call by call has cleared fpts_valid, DESIGN.md 3.7: the fused stage behind this one reads disu_fpts of the new state)
-  for (int i = 0; i < neb; i++)
-    if (hfx_eles_extrapolate_solution(eles[i])) return 1;
-  return 0;
-}
-
-extern "C" {
-
 int hfx_run_steps_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, int n_steps, int fused)
 {
   HFX_CHECK(eles && neb > 0 && eles[0], "hfx_run_steps_blocks: no element blocks");
   HFX_IMMEDIATE(eles[0]->ctx, 0);
   hfx_ctx *ctx = eles[0]->ctx;
   HFX_CHECK(ctx->have_params, "parameters not set");
-  const int adv = ctx->params.adv_type;
-  const int nst = n_rk_stages(adv); /* src/HiFiLES.cpp:143-150 */
-  if (probes_check_capacity(eles, neb, n_steps)) return 1;
-  if (integrals_check_capacity(eles, neb, n_steps)) return 1;
-  if (history_check_capacity(eles, neb, n_steps)) return 1;
-  if (plot_check_capacity(eles, neb, n_steps)) return 1;
-  if (wall_model_check_points(faces, nfb)) return 1;
+  if (step_loop_check(eles, neb, faces, nfb, n_steps)) return 1;
   if (fused == 4) return general_run_steps(eles, neb, faces, nfb, n_steps);
   HFX_CHECK(fused == 0 || neb == 1, "hfx_run_steps_blocks: the split fused stage (fused %d) takes one tensor-product element block; "
                                     "several blocks run per method (0) or through the general fused stage (4)", fused);
   HFX_CHECK(fused == 0 || fused == 2 || fused == 3, "hfx_run_steps: fused must be 0 (per-method), 2 or 3 (split fused stage), 4 (general fused "
                                                     "stage); the gather-style variant 1 of earlier versions has been retired");
   if (fused) return split_run_steps(eles[0], faces, nfb, n_steps, fused);
-  for (int s = 0; s < n_steps; s++)
-  {
-    if (calc_time_step_blocks(eles, neb)) return 1; /* src/HiFiLES.cpp:198 */
-    if (begin_of_step(eles, neb, nullptr)) return 1; /* src/solver.cpp:96-109 */
-    for (int rk = 0; rk < nst; rk++)
-    {
-      if (rk == 0) /* src/solver.cpp:55-62 */
-        for (int i = 0; i < neb; i++)
-          if (eles[i]->les_ready && hfx_eles_calc_sgs_terms(eles[i])) return 1;
-      if (hfx_CalcResidual_blocks(eles, neb, faces, nfb)) return 1;
-      for (int i = 0; i < neb; i++)
-        if (hfx_eles_AdvanceSolution(eles[i], rk, adv)) return 1;
-      for (int i = 0; i < neb; i++)
-        if (eles[i]->shock_ready && hfx_eles_shock_capture(eles[i])) return 1; /* src/HiFiLES.cpp:214-216 */
-    }
-    advance_ramp_counters(faces, nfb); /* src/HiFiLES.cpp:224-225 */
-    if (end_of_step(eles, neb)) return 1; /* src/HiFiLES.cpp:221-245 */
-  }
-  return 0;
+  // per method: every stage writes the gradient, nothing before or after the loop
+  StepLoop loop{eles, neb, faces, nfb, [&](int rk) {
+                  if (hfx_CalcResidual_blocks(eles, neb, faces, nfb)) return 1;
+                  for (int i = 0; i < neb; i++)
+                    if (hfx_eles_AdvanceSolution(eles[i], rk, ctx->params.adv_type)) return 1;
+                  for (int i = 0; i < neb; i++)
+                    if (eles[i]->shock_ready && hfx_eles_shock_capture(eles[i])) return 1; /* src/HiFiLES.cpp:214-216 */
+                  return 0;
+                }};
+  loop.closure = ClosureFilter::filtering;
+  return run_step_loop(loop, n_steps);
 }
 
 int hfx_run_steps(hfx_eles *e, hfx_inters *const *faces, int nfb, int n_steps, int fused)

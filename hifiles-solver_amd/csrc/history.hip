@@ -22,7 +22,7 @@
 //
 // Which gradient the viscous force reads: grad_disu_upts as it stands, as for the integral monitor (integrals.hip).  The step loops
 // see to it that it is what the last RK stage left (stage_call_by_call); the monitor forms no gradient of its own.
-#include "hfx_internal.hpp"
+#include "step_loop.hpp"
 
 #include <cstdint>
 
@@ -264,16 +264,6 @@ unsigned history_sample_need(const hfx_eles *e)
   unsigned need = 1u << HFX_DIV_TCONF_UPTS;
   if (history_monitor_reads_gradient(e)) need |= (1u << HFX_DISU_UPTS0) | (1u << HFX_GRAD_DISU_UPTS);
   return need;
-}
-
-bool monitor_reads_gradient(hfx_eles *const *eles, int neb)
-{
-  const hfx_ctx *ctx = eles[0]->ctx;
-  if (!ctx->params.viscous) return false;
-  const bool integrals = integral_monitor_reads_gradient(ctx);
-  for (int i = 0; i < neb; i++)
-    if ((integrals && eles[i]->n_vol_cubpts > 0) || history_monitor_reads_gradient(eles[i]) || plot_monitor_reads_gradient(eles[i])) return true;
-  return false;
 }
 
 int sample_history(hfx_eles *e, double time, int step)

@@ -17,7 +17,7 @@
 // Which gradient: grad_disu_upts as it stands, like the reference and like the integral monitor.  Behind a step that is what the last
 // stage's correct_gradient left -- the gradient of that stage's INPUT state, paired with the state after the step.  The step loops see
 // to it that the array holds exactly that when they sample (stage_call_by_call); the monitor forms no gradient of its own.
-#include "hfx_internal.hpp"
+#include "step_loop.hpp"
 #include "plot_point.hpp"
 
 namespace hfx

@@ -9,7 +9,7 @@
 // forms the registered fields and stores them into the sample's slot of the device history.  No atomics, no order that depends
 // on timing: a probe's value is a function of its operator row, its element's state and nothing else -- not of the probes
 // registered beside it, nor of its place among them.
-#include "hfx_internal.hpp"
+#include "step_loop.hpp"
 
 namespace hfx
 {

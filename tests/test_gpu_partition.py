@@ -231,6 +231,41 @@ def test_gpu_time_partitioned_and_allreduce(tmp_path):
     assert list(v[8:]) == [3.0, -1.5, 2.0]
 
 
+def _timing_loop_worker(rank, world, port, outdir, kw):
+    import torch
+    import hfx
+    import hfx_host as H
+    torch.cuda.set_device(0)
+    out = []
+    for timed in (True, False):
+        c = H.Case([3, 3, 3], order=2, amp=0.05, self_partition=[1, 0, 0], **kw)
+        c.to_device(0)
+        c.set_comm(hfx.comm_unique_id())
+        nst = c.n_stages
+        assert nst == 5  # RK45
+        if timed:
+            c.time_partitioned(2 * nst)
+        else:
+            c.run_partitioned(2)  # (what partition_util.gpu_worker calls in mode "fused" with transport "rccl")
+        c.sync_host()
+        out.append(c.array("disu_upts0").copy())
+        c.close()
+    np.save(outdir + "/timed.npy", out[0])
+    np.save(outdir + "/stepped.npy", out[1])
+
+
+@pytest.mark.parametrize("kw", [dict(dt_type=0), dict(dt_type=1, CFL=0.3)], ids=["dt_type0", "dt_type1"])
+def test_gpu_time_partitioned_advances_as_the_step_loop(tmp_path, kw):
+    """hfx_time_partitioned (bench.py reports from it) over 2 * nst stages against two steps of hfx_run_steps_partitioned on the
+    same self-partitioned box, RK45, no averages, probes or monitors: the timing loop takes calc_time_step every nst stages and
+    launches the same kernels in the same order -- the same bits."""
+    PU.spawn(_timing_loop_worker, 1, (str(tmp_path), kw))
+    timed, stepped = np.load(str(tmp_path / "timed.npy")), np.load(str(tmp_path / "stepped.npy"))
+    assert np.isfinite(timed).all() and np.abs(timed).max() > 0.0
+    print("timing loop against step loop: rel %.3e" % rel(timed, stepped))
+    assert np.array_equal(timed, stepped)
+
+
 def _nccl_self_worker(rank, world, port, outdir):
     import torch
     import hfx
