@@ -145,7 +145,8 @@ int main(int argc, char *argv[])
   int n_eles = E->n_eles, n_upts = E->n_upts_per_ele, n_fpts = E->n_fpts_per_ele;
   int n_fields = E->n_fields, n_dims = E->n_dims;
   if (mixed && (run_input.LES || run_input.n_integral_quantities != 0 || run_input.over_int || run_input.shock_cap ||
-                run_input.dt_type != 0 || getenv("HFX_DUMP_PPTS") || getenv("HFX_DUMP_RESTART")))
+                run_input.dt_type != 0 || getenv("HFX_DUMP_PPTS") || getenv("HFX_DUMP_RESTART") ||
+                getenv("HFX_DUMP_INTERS_CUBPTS")))
   {
     fprintf(stderr, "harness: mixed meshes are dumped for the plain Navier-Stokes / Euler path only\n");
     return 1;
@@ -467,6 +468,37 @@ int main(int argc, char *argv[])
         for (int j = 0; j < npp; j++) pp[j + (size_t)npp * (i + (size_t)n_eles * k)] = one(j, k);
     }
     put_d("disu_ppts", pp.data(), {npp, n_eles, nf});
+  }
+  if (getenv("HFX_DUMP_INTERS_CUBPTS") && run_input.calc_force)
+  {
+    // the surface cubature of every local face (eles::set_opp_inters_cubpts src/eles.cpp:3635, set_transforms_inters_cubpts
+    // :4480), for the element classes the host mirror does not build: the operator (n_cubpts, n_upts), the weights (n_cubpts),
+    // and the face Jacobian (n_cubpts, n_eles) and unit normal (n_cubpts, n_eles, n_dims) per ELEMENT -- the reference keeps the
+    // two per boundary element (bdy_ele2ele); an element without a boundary face carries zeros.  With them the reference state
+    // and area of eles::compute_wall_forces (src/eles.cpp:5734-5743, :5960-5990) after input::setup's non-dimensionalisation
+    put_scalar("u_c_ic", run_input.u_c_ic);
+    put_scalar("v_c_ic", run_input.v_c_ic);
+    put_scalar("w_c_ic", run_input.w_c_ic);
+    put_scalar("area_ref", run_input.area_ref);
+    for (int l = 0; l < E->n_inters_per_ele; l++)
+    {
+      const string s = "_" + to_string(l);
+      const int nc = E->n_cubpts_per_inter(l);
+      put_arr("opp_inters_cubpts" + s, E->opp_inters_cubpts(l));
+      put_arr("weight_inters_cubpts" + s, E->weight_inters_cubpts(l));
+      vector<double> dj((size_t)nc * n_eles, 0.0), nm((size_t)nc * n_eles * n_dims, 0.0);
+      for (int b = 0; b < E->n_bdy_eles; b++)
+      {
+        const int i = E->bdy_ele2ele(b);
+        for (int j = 0; j < nc; j++)
+        {
+          dj[j + (size_t)nc * i] = E->inter_detjac_inters_cubpts(l)(j, b);
+          for (int m = 0; m < n_dims; m++) nm[j + (size_t)nc * (i + (size_t)n_eles * m)] = E->norm_inters_cubpts(l)(j, b, m);
+        }
+      }
+      put_d("inter_detjac_inters_cubpts" + s, dj.data(), {nc, n_eles});
+      put_d("norm_inters_cubpts" + s, nm.data(), {nc, n_eles, n_dims});
+    }
   }
 
   // wall clock of the RK loop alone (setup excluded): what bench.py's cpu_baseline leg reports for the genuine reference

@@ -12,6 +12,11 @@ history_rows_util and plot_rows_util; the probes take the bar of a plotted conse
 largest magnitude over the probes (the same operation: a row of an interpolation operator applied to the state, then the pointwise
 field), a field that is zero at every probe exactly.
 
+Triangles (fl_tri_p3_*): the host mirror builds none, so the wall faces and their surface cubature (force_setup) come from the arrays
+the reference itself formed and the fixture holds, and the probes sit at plot points, where a probe operator is a row of opp_p; that
+gives a check of the probes against the DRIVER's plot rows (probes_against_plot_rows).  The shock filter of fl_tri_p3_shock runs
+behind every stage in plot_rows_util.Run; its counts come from tri_shock_util's lockstep (filtered_counts).
+
 Sensitivity numbers (condition 3 of the capture; each must exceed 1e-6, the margin of tests/test_gpu_physics_matrix.py):
   own_gradient_force      per history row: the viscous force formed with the sampled state's OWN gradient, miss of the driver's
                           viscous part relative to that part's largest component
@@ -34,11 +39,16 @@ import plot_rows_util as PU
 import probe_util
 
 FL_DIR = os.path.join(PU.GOLDEN, "full_loop")
-FL = ["fl_hex_p2_channel", "fl_hex_p2_forced", "fl_quad_p3_walls", "fl_tet_p2_euler"]
+FL = ["fl_hex_p2_channel", "fl_hex_p2_forced", "fl_quad_p3_walls", "fl_tet_p2_euler", "fl_tri_p3_walls", "fl_tri_p3_shock"]
 SENSITIVITY = ["own_gradient_force", "own_gradient_vorticity", "previous_state_row", "unforced_state", "spinup_zero_average"]
 MARGIN = 1e-6
-PROBE_FREQ = {"fl_hex_p2_channel": 5, "fl_hex_p2_forced": 1, "fl_quad_p3_walls": 1, "fl_tet_p2_euler": 1}
+PROBE_FREQ = {"fl_hex_p2_channel": 5, "fl_hex_p2_forced": 1, "fl_quad_p3_walls": 1, "fl_tet_p2_euler": 1, "fl_tri_p3_walls": 1,
+              "fl_tri_p3_shock": 1}
 N_PROBES = 8
+TRIANGLES = 0  # (sizes[6] of a triangle block: the class the host mirror does not build)
+# the virtual parts of fl_tri_p3_walls in the partitioned loop (test_tris_partition_oracle.grow_parts: weights, seed): parts of 31, 6
+# and 3 elements whose 22 partition faces all lie in the first group of 32 -- one partition group, and the ragged group of 8 interior
+TRI_PARTS = ([10, 2, 1], 11)
 
 
 def load(name):
@@ -103,10 +113,49 @@ class Run(PU.Run):
         return np.array(self.ctl.rows) if self.ctl is not None else np.zeros((0, 2))
 
 
+def fixture_wall_faces(d):
+    """(ele, local face, flag) of every face in a wall group, from the fixture's boundary tables alone: a table entry is
+    fpt + n_fpts * ele, the flux points of local face l are l (order + 1) ... (l + 1)(order + 1) - 1 (tests/tri_util.py).  In the
+    order of eles::compute_wall_forces (src/eles.cpp:5746-5769): ascending by element, then by local face"""
+    import wall_force_util as W
+    n_fpts, order = int(d["sizes"][2]), int(d["sizes"][5])
+    flags = np.asarray(d["bc_flags"]).reshape(3, -1, order="F")[0]
+    faces = []
+    for t in range(3):
+        if "bdy%d_L" % t in d:
+            L, ids = np.asarray(d["bdy%d_L" % t]), np.ravel(d["bdy%d_id" % t])
+            for i in range(L.shape[1]):
+                ele, l = int(L[0, i]) // n_fpts, (int(L[0, i]) % n_fpts) // (order + 1)
+                assert np.array_equal(L[:, i] // n_fpts, np.full(L.shape[0], ele)) and int(L[-1, i]) % n_fpts == (l + 1) * (order + 1) - 1
+                if int(flags[ids[i]]) in W.WALL_FLAGS:
+                    faces.append((ele, l, int(flags[ids[i]])))
+    faces.sort()
+    return tuple(np.array(c, dtype=np.int32) for c in zip(*faces))
+
+
+def fixture_device_arrays(d):
+    """test_wall_force_host.device_arrays from the arrays the reference itself formed (eles_tris::set_inters_cubpts,
+    eles::set_opp_inters_cubpts, set_transforms_inters_cubpts) and the harness dumped into the fixture, in the mirror's shapes:
+    per local face opp (n_cubpts, n_upts), weight (n_cubpts), detjac (n_cubpts, n_eles), norm (n_cubpts, n_eles, n_dims)"""
+    ele, inter, flag = fixture_wall_faces(d)
+    n_inters = len([k for k in d if k.startswith("opp_inters_cubpts_")])
+    opp = [np.asarray(d["opp_inters_cubpts_%d" % l]) for l in range(n_inters)]
+    weight = [np.ravel(d["weight_inters_cubpts_%d" % l]) for l in range(n_inters)]
+    detjac = [np.asarray(d["inter_detjac_inters_cubpts_%d" % l])[:, e] for e, l in zip(ele, inter)]
+    norm = [np.asarray(d["norm_inters_cubpts_%d" % l])[:, e, :] for e, l in zip(ele, inter)]
+    return dict(face_ele=ele, face_inter=inter, face_flag=flag, opp=opp, weight=weight, detjac=detjac, norm=norm)
+
+
 def force_setup(d):
-    """the wall faces the host mirror builds for the fixture (no device): dict(A, phys, ref), or None without calc_force"""
+    """the wall faces of the fixture (no device): dict(A, phys, ref), or None without calc_force.  From the host mirror, except on
+    triangles, which the mirror does not build: there from the surface cubature the fixture holds"""
     if not int(d["calc_force"][0]):
         return None
+    if int(d["sizes"][6]) == TRIANGLES:
+        phys = {k: PU.scalar(d, k) for k in ("gamma", "rt_inf", "mu_inf", "c_sth", "fix_vis")}
+        phys["viscous"] = int(PU.scalar(d, "viscous"))
+        ref = {k: PU.scalar(d, k) for k in ("rho_c_ic", "u_c_ic", "v_c_ic", "w_c_ic", "p_c_ic", "area_ref")}
+        return dict(A=fixture_device_arrays(d), phys=phys, ref=ref)
     from test_wall_force_host import device_arrays, mirror_case, phys_of, ref_of
     mc, _ = mirror_case(d)
     out = dict(A=device_arrays(mc), phys=phys_of(mc), ref=ref_of(mc))
@@ -169,7 +218,8 @@ def walk(d):
                 own = PU.rows_of(PU.fixture_fields(d, run, grad=run.own_gradient())[0])
                 out["sens"]["own_gradient_vorticity"].append(float(rel_columns(own, drv)[col]))
             grad = run.grad if PU.reads_gradient(diag) else None
-            before = PU.fields(diag, d["opp_p"], prev, grad, PU.scalar(d, "gamma"), average=run.average if na else None)[0]
+            before = PU.fields(diag, d["opp_p"], prev, grad, PU.scalar(d, "gamma"), average=run.average if na else None,
+                               sensor=run.sensor)[0]
             out["sens"]["previous_state_row"].append(float(rel_columns(PU.rows_of(before), drv).max()))
             if na:
                 zero = np.einsum("jk,kif->jif", d["opp_p"], run.average0)
@@ -183,7 +233,36 @@ def walk(d):
             free.step()
         out["unforced"] = free.u.copy(order="F")
         out["sens"]["unforced_state"].append(float(np.abs(free.u - run.u).max() / np.abs(run.u).max()))
+    if shock(d):
+        # the harness does not dump a triangle run with shock_cap 1 (tools/capture_tris_shock.py): it ran without the filter, and
+        # the run without the filter is what its last state is tied to
+        free = Run(dict(d, shock_cap=np.array([0], dtype=np.int32)))
+        for _ in range(steps):
+            free.step()
+        out["unfiltered"] = free.u.copy(order="F")
     return out
+
+
+def shock(d):
+    return bool("shock_cap" in d and int(np.ravel(d["shock_cap"])[0]))
+
+
+def harness_state(d, w):
+    """the lockstep state the harness's own last state is tied to: of the run without the body force or without the shock filter
+    where the harness ran without it, else the run's"""
+    return w["unforced"] if forced(d) else w["unfiltered"] if shock(d) else w["states"][-1]
+
+
+def filtered_counts(d):
+    """the shock filter of a fixture with shock_cap 1 through tri_shock_util's lockstep: (per stage (n_steps, n_stages) the number
+    of filtered elements, per step the number of elements some stage of the step filtered, the smallest distance of a sensor value of
+    any stage from s0 relative to s0)"""
+    import tri_shock_util as TS
+    steps, n_stages, s0 = meta_of(d)["steps"], int(d["sizes"][7]), TS.scalar(d, "s0")
+    sens = TS.lockstep(d, steps)["stage_sensors"]
+    per_stage = np.array(TS.filtered_counts(sens, s0)).reshape(steps, n_stages)
+    per_step = np.array([int((sens[s * n_stages:(s + 1) * n_stages] >= s0).any(axis=0).sum()) for s in range(steps)])
+    return per_stage, per_step, TS.closest(sens, s0)
 
 
 def worst_bars(w):
@@ -250,8 +329,19 @@ def probes(name):
     dict(pos (n_dims, 8), ele (8), opp (n_upts, 8), perm: the scrambled order of registration, names: the probe fields)"""
     d = load(name)
     n_dims, n_eles, et = int(d["sizes"][4]), int(d["sizes"][0]), int(d["sizes"][6])
-    m = probe_mirror(d)
     ele = np.array([0, 1, n_eles // 3, n_eles // 2, n_eles // 2, (2 * n_eles) // 3, n_eles - 2, n_eles - 1], dtype=np.int32)
+    if et == TRIANGLES:
+        # no mirror: the probes sit at plot points strictly inside their elements, dealt in turn over the elements, and a probe's
+        # operator is the row of opp_p of its plot point (the nodal basis there).  pos: as the driver printed it in its plot file
+        loc = np.asarray(d["loc_ppts"])
+        inside = np.nonzero((loc[0] > -1 + 1e-6) & (loc[1] > -1 + 1e-6) & (loc[0] + loc[1] < -1e-6))[0]
+        assert len(inside) >= 2, "p_res %d has no two plot points strictly inside a triangle" % int(d["p_res"][0])
+        ppt = inside[np.arange(N_PROBES) % len(inside)]
+        assert len(set(zip(ele.tolist(), ppt.tolist()))) == N_PROBES
+        pos = d["plot_rows"][0][ele * loc.shape[1] + ppt, :n_dims].T.copy(order="F")
+        return dict(pos=pos, ele=ele, opp=np.asarray(d["opp_p"])[ppt, :].T.copy(order="F"), perm=np.array(PROBE_PERM),
+                    names=probe_util.field_names(n_dims), ppt=ppt)
+    m = probe_mirror(d)
     loc = probe_util.random_interior_locs(et, N_PROBES, 20261020)
     pos = m.calc_pos(ele, loc)
     p2c, found = m.locate(pos)
@@ -269,6 +359,28 @@ def expected_probes(name):
     vals = [probe_util.probe_fields(probe_util.interpolate(P["opp"], P["ele"], w["states"][s - 1]), P["names"], PU.scalar(d, "gamma"))
             for s in steps]
     return steps, np.stack(vals, axis=2)
+
+
+def probes_against_plot_rows(name, steps, values):
+    """probes registered at plot points (triangles) against the DRIVER's plot files, independent of the lockstep: at every step that
+    both sample, the conserved state of the probe samples `values` (n_fields, 8, n_samples; taken at `steps`) against the file's
+    rows at those plot points, the largest miss in units of the plot bar (plot_rows_util.miss).  None where the probes sit elsewhere"""
+    d, w = reference(name)
+    P = probes(name)
+    if "ppt" not in P:
+        return None
+    nd, nf, n_ppts = int(d["sizes"][4]), int(d["sizes"][3]), d["opp_p"].shape[0]
+    assert nd == 2
+    at = {n: i for i, n in enumerate(P["names"])}
+    worst, steps = None, list(steps)
+    for k, s in enumerate(int(v) for v in d["plot_iter"]):
+        if s in steps:
+            v = values[:, :, steps.index(s)]
+            rho = v[at["rho"]]
+            cons = np.stack([rho, rho * v[at["u"]], rho * v[at["v"]], rho * v[at["specific_total_energy"]]], axis=1)
+            rows = d["plot_rows"][k][P["ele"] * n_ppts + P["ppt"], nd:nd + nf]
+            worst = max(worst or 0.0, float(PU.miss(cons, rows, w["plot"][k]["scales"][:nf]).max()))
+    return worst
 
 
 def probe_miss(got, want):

@@ -13,8 +13,10 @@ import plot_rows_util as PU
 
 # history rows and plot files per case, as the issue of this family states them
 ROWS = {"fl_hex_p2_channel": ([1, 3, 6], [2, 4, 6]), "fl_hex_p2_forced": ([1], [2]), "fl_quad_p3_walls": ([1, 2, 4], [3]),
-        "fl_tet_p2_euler": ([1, 4], [3, 6])}
-BY_CALLS = {"fl_hex_p2_channel": [1, 2, 3, 4, 6], "fl_hex_p2_forced": [1, 2], "fl_quad_p3_walls": [1, 2, 3, 4], "fl_tet_p2_euler": [1, 3, 4, 6]}
+        "fl_tet_p2_euler": ([1, 4], [3, 6]), "fl_tri_p3_walls": ([1, 2, 4], [3]), "fl_tri_p3_shock": ([1, 2, 4], [3])}
+BY_CALLS = {"fl_hex_p2_channel": [1, 2, 3, 4, 6], "fl_hex_p2_forced": [1, 2], "fl_quad_p3_walls": [1, 2, 3, 4], "fl_tet_p2_euler": [1, 3, 4, 6],
+            "fl_tri_p3_walls": [1, 2, 3, 4], "fl_tri_p3_shock": [1, 2, 3, 4]}
+TRI = ["fl_tri_p3_walls", "fl_tri_p3_shock"]
 
 
 @pytest.mark.parametrize("name", FU.FL)
@@ -38,8 +40,9 @@ def test_every_row_the_driver_wrote_is_met(name):
         assert np.all(s["bars"] <= PU.bars(d)), (name, s["step"], s["bars"])
     assert FU.worst_bars(w) <= 1.0
     assert np.all(np.array([s["bars"] for s in w["plot"]]).max(axis=0) <= d["rows_paired_bars"] + 1e-9)
-    # the harness's own last state: the two runs of the capture are one (on the forced case: the run without the force)
-    free = w["unforced"] if FU.forced(d) else w["states"][-1]
+    # the harness's own last state: the two runs of the capture are one (on the forced case: the run without the force; on the
+    # triangle case with shock capturing: the run without the filter)
+    free = FU.harness_state(d, w)
     assert np.abs(free - d["u_last_harness"]).max() <= 1e-11 * np.abs(d["u_last_harness"]).max()
 
 
@@ -148,3 +151,86 @@ def test_probes_are_located_and_expected(name):
     assert values.shape == (len(P["names"]), FU.N_PROBES, len(steps)) and np.all(np.isfinite(values))
     if name == "fl_hex_p2_channel":
         assert steps == [5]  # (behind a fused step between two steps that end call by call)
+
+
+# ---- triangles: what the host mirror does not build comes from the fixture ---------------------------------------------------------
+@pytest.mark.parametrize("name", TRI)
+def test_triangle_wall_faces_and_surface_cubature(name):
+    """the wall list derived from the boundary tables and the surface cubature the harness dumped: 4 faces on either wall of the
+    4 x 5 box, the isothermal ones on y-, every local face among them (the node lists are rotated), 4 points per face; weights that
+    sum to the reference side's length 2, unit normals that point down on y- and up on y+, face Jacobians that sum to the wall's
+    length within the deformation; an element without a face in any boundary group carries zeros"""
+    import wall_force_util as W
+    d, _ = FU.reference(name)
+    n_eles, n_upts, order = int(d["sizes"][0]), int(d["sizes"][1]), int(d["sizes"][5])
+    assert int(d["sizes"][6]) == FU.TRIANGLES and n_eles == 40
+    F = FU.force_setup(d)
+    A = F["A"]
+    assert len(A["face_ele"]) == 8 and sorted(A["face_flag"].tolist()) == [W.ISOTHERM_WALL] * 4 + [W.ADIABAT_WALL] * 4
+    assert np.all(np.diff(A["face_ele"]) > 0) and set(A["face_inter"].tolist()) == {0, 1, 2}
+    assert len(A["opp"]) == 3 and F["phys"]["viscous"] == 1 and F["ref"]["area_ref"] > 0
+    length = {W.ISOTHERM_WALL: 0.0, W.ADIABAT_WALL: 0.0}
+    for f, (e, l, flag) in enumerate(zip(A["face_ele"], A["face_inter"], A["face_flag"])):
+        assert A["opp"][l].shape == (order + 1, n_upts) and np.all(np.abs(A["opp"][l].sum(axis=1) - 1.0) <= 1e-12)
+        nm = A["norm"][f]
+        assert nm.shape == (order + 1, 2) and np.all(np.abs((nm * nm).sum(axis=1) - 1.0) <= 1e-13)
+        assert np.all(nm[:, 1] < -0.9) if flag == W.ISOTHERM_WALL else np.all(nm[:, 1] > 0.9)
+        assert np.all(A["detjac"][f] > 0)
+        length[int(flag)] += float((A["weight"][l] * A["detjac"][f]).sum())
+    for v in length.values():  # (a wall is the deformed image of a side of 2 pi)
+        assert 2.0 * np.pi - 1e-12 <= v <= 1.1 * 2.0 * np.pi
+    walls = set(A["face_ele"].tolist())
+    for l in range(3):
+        dj = np.asarray(d["inter_detjac_inters_cubpts_%d" % l])
+        assert dj.shape == (order + 1, n_eles) and np.asarray(d["norm_inters_cubpts_%d" % l]).shape == (order + 1, n_eles, 2)
+        # the reference forms them for every element with a face in ANY group, the cyclic ones included (bdy_ele2ele): 4 + 4 on the
+        # walls, 5 + 5 on the x sides, two corner triangles counted twice
+        has = dj.all(axis=0)
+        assert np.array_equal(has, dj.any(axis=0)) and has.sum() == 16 and has[sorted(walls)].all()
+
+
+@pytest.mark.parametrize("name", TRI)
+def test_triangle_probes_sit_at_interior_plot_points_and_meet_the_plot_file(name):
+    """the 8 probes are plot points strictly inside their elements, spread over the usual element choices; at the step both a probe
+    sample and a plot file fall on, the lockstep's probe samples give the DRIVER's conserved plot rows at those points at the plot
+    bar -- and the samples of the neighbouring steps do not (the check can tell the step)"""
+    d, w = FU.reference(name)
+    P = FU.probes(name)
+    n = int(d["sizes"][0])
+    assert P["ele"].tolist() == [0, 1, n // 3, n // 2, n // 2, (2 * n) // 3, n - 2, n - 1] and P["perm"].tolist() == FU.PROBE_PERM
+    loc = np.asarray(d["loc_ppts"])[:, P["ppt"]]
+    assert np.all(loc > -1 + 1e-3) and np.all(loc.sum(axis=0) < -1e-3)
+    steps, values = FU.expected_probes(name)
+    worst = FU.probes_against_plot_rows(name, steps, values)
+    print("%s: probes against the driver's plot rows %.3g bars" % (name, worst))
+    assert worst is not None and worst <= 1.0
+    assert FU.probes_against_plot_rows(name, steps, np.roll(values, 1, axis=2)) > 1e3
+
+
+def test_triangle_virtual_parts_offer_both_kinds_of_group():
+    """FU.TRI_PARTS on fl_tri_p3_walls: three virtual parts, six directed segments, every flux point in exactly one face table, and of
+    the two groups of the fused 2-D simplex stage (32 + 8 elements at P3) one has partition faces and one has none"""
+    from test_tris_partition_oracle import grow_parts, group_census, virtual_tables
+    d, _ = FU.reference("fl_tri_p3_walls")
+    reg, L, Rlut, seg = virtual_tables(d, grow_parts(d, *FU.TRI_PARTS))
+    ne, nfp = int(d["sizes"][0]), int(d["sizes"][2])
+    assert len(seg) == 6 and L.shape[1] > 0 and np.array_equal(reg["bdy0_L"], d["bdy0_L"])
+    seen = [np.ravel(L)] + [np.ravel(reg[k]) for k in reg if k.startswith(("int", "bdy")) and k.endswith(("_L", "_R"))]
+    assert np.array_equal(np.sort(np.concatenate(seen)), np.arange(nfp * ne))
+    assert group_census(reg, L) == (1, 1, True, False)
+
+
+def test_triangle_shock_filter_counts():
+    """fl_tri_p3_shock: in every step the filter takes at least one element and not all, no sensor value of any stage lies within
+    tri_shock_util.MARGIN of s0, and the counts are the ones the capture stored; without the filter the run ends elsewhere"""
+    import tri_shock_util as TS
+    d, w = FU.reference("fl_tri_p3_shock")
+    n = int(d["sizes"][0])
+    per_stage, per_step, gap = FU.filtered_counts(d)
+    print("filtered per stage %s, per step %s of %d, closest %.1e" % (per_stage.tolist(), per_step.tolist(), n, gap))
+    assert np.all((per_step >= 1) & (per_step <= n - 1)) and gap > TS.MARGIN
+    assert np.array_equal(per_stage, d["filtered_per_stage"]) and np.array_equal(per_step, d["filtered_per_step"])
+    assert "sensor" in PU.names_of(d, "diagnostic_fields") and FU.shock(d) and not FU.shock(FU.reference("fl_tri_p3_walls")[0])
+    moved = np.abs(w["unfiltered"] - w["states"][-1]).max() / np.abs(w["states"][-1]).max()
+    print("the filter moves the final state by %.2e" % moved)
+    assert moved > FU.MARGIN

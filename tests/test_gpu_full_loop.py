@@ -10,6 +10,10 @@ column's un-cancelled scale (plot_rows_util.miss, bars); probes 1e-11 of the fie
 (full_loop_util); the controller 1e-7 of the driver's printed 8 digits; the averages 1e-11 of each plane's largest value; the state
 1e-11 of its largest value.  What each run prints: the worst of each in units of its bar.
 
+Triangles (fl_tri_p3_walls, fl_tri_p3_shock: 40 P3 triangles, one whole group of the fused 2-D simplex stage and a ragged one) run the
+per-method loop and fused 4; every fused-4 run asserts hfx_simplex2d_plan, the shock case that the filter is folded.  Their probes sit
+at plot points, so a sample on the step of a plot file is also held against the driver's rows there ("probes on plot rows").
+
 The plan of a P2 block reports neither folded faces nor the two-wave flux kernel (both are forms of P4 hexahedra on affine blocks,
 tests/test_gpu_folded_faces.py, tests/test_gpu_flux_two_wave.py): the legs with fold_faces 0 and flux_two_wave 0 are left out.
 """
@@ -29,8 +33,9 @@ from test_gpu_methods_vs_golden import build
 
 pytestmark = pytest.mark.gpu
 
-HEX, DRIVEN, QUAD, TET = FU.FL
+HEX, DRIVEN, QUAD, TET, TRI, TRI_SHOCK = FU.FL
 HISTORIES = ["probes", "integral", "history", "plot"]
+G_P3 = 32  # (elements per group of the fused 2-D simplex stage at P3: the 40 triangles are one whole group and a ragged one of 8)
 
 
 @functools.lru_cache(maxsize=None)
@@ -45,6 +50,7 @@ def setup(name):
              probe_steps=FU.expected_probes(name)[0], probe_values=FU.expected_probes(name)[1])
     s["need"] = dict(probes=len(s["probe_steps"]), integral=len(d["hist_iter"]), history=len(d["hist_iter"]), plot=len(d["plot_iter"]))
     s["free_diag"] = [n for n in s["diag"] if n not in PU.GRADIENT]
+    s["tri"], s["shock"] = int(d["sizes"][6]) == FU.TRIANGLES, FU.shock(d)
     return s
 
 
@@ -75,8 +81,22 @@ def register(ctx, e, s, monitors="all", caps=None):
 
 def make(ctx, s, monitors="all", caps=None):
     e, faces = build(ctx, s["d"])
+    e.triangles, e.folds_shock, e.fixture = s["tri"], s["shock"], s["d"]
     register(ctx, e, s, monitors, caps)
     return e, faces
+
+
+def assert_simplex_stage(e):
+    """a block of triangles behind a fused-4 call: the 2-D simplex stage prepared it (the query is refused otherwise), and where the
+    block has shock capturing the filter is folded into its update kernel -- a silent per-method loop cannot pass"""
+    from test_gpu_tris import expected_plan
+    plan, want = e.simplex2d_plan(), expected_plan(e.fixture)
+    assert plan["group"] == G_P3 and e.n_eles == G_P3 + 8
+    assert all(plan[k] == want[k] for k in ("size_class", "group", "waves", "gather", "element_lds")), plan
+    if e.folds_shock:
+        assert e.simplex2d_shock_plan()["folded"] == 1
+    else:
+        assert plan == want, plan
 
 
 def close(e, faces, ctx=None):
@@ -90,6 +110,8 @@ def close(e, faces, ctx=None):
 def run_loop(e, faces, n, fused):
     if fused == 4:
         hfx.run_steps_blocks([e], faces, n, fused=4)
+        if getattr(e, "triangles", False):
+            assert_simplex_stage(e)
     else:
         hfx.run_steps(e, faces, n, fused=fused)
 
@@ -150,6 +172,12 @@ def check(s, got, what, free=False):
     assert list(got["probe_steps"]) == s["probe_steps"], what
     assert np.allclose(got["probe_time"], dt * np.array(s["probe_steps"]), rtol=1e-14, atol=0)
     worst["probes"] = max(FU.probe_miss(got["probes"], s["probe_values"])) / 1e-11
+    # triangles: the probes sit at plot points, and where a probe sample and a plot file fall on one step the conserved state of the
+    # samples is the DRIVER's rows at those points, at the plot bar
+    on_rows = FU.probes_against_plot_rows(s["name"], got["probe_steps"], got["probes"])
+    assert (on_rows is not None) == s["tri"], what
+    if on_rows is not None:
+        worst["probes on plot rows"] = on_rows
     # the controller against the lines the driver printed before every step (8 decimals)
     if got["ctl"] is not None:
         drv = d["driver_controller"][:, 3:]
@@ -189,7 +217,8 @@ def same_bits(a, b):
 
 
 # ---- 1. through the C ABI, one call of all steps ------------------------------------------------------------------------------
-ONE_CALL = [(n, f) for n in (HEX, DRIVEN, QUAD) for f in (0, 2, 3)] + [(HEX, 4), (TET, 0), (TET, 4)]
+ONE_CALL = [(n, f) for n in (HEX, DRIVEN, QUAD) for f in (0, 2, 3)] + [(HEX, 4), (TET, 0), (TET, 4)] + \
+    [(n, f) for n in (TRI, TRI_SHOCK) for f in (0, 4)]
 
 
 @pytest.mark.parametrize("name,fused", ONE_CALL)
@@ -201,12 +230,16 @@ def test_one_call(name, fused):
 CUTS = [(HEX, (2, 1, 4)), (HEX, (1,) * 7), (QUAD, (1, 4)), (DRIVEN, (1, 1))]
 
 
-@pytest.mark.parametrize("fused", [0, 3])
-@pytest.mark.parametrize("name,cut", CUTS, ids=["%s-%s" % (n, "+".join(map(str, c))) for n, c in CUTS])
+CUT_LEGS = [(n, c, f) for n, c in CUTS for f in (0, 3)] + [(TRI, c, f) for c in ((2, 3), (1,) * 5) for f in (0, 4)] + [(TRI_SHOCK, (1,) * 5, 4)]
+
+
+@pytest.mark.parametrize("name,cut,fused", CUT_LEGS, ids=["%s-%s-%d" % (n, "+".join(map(str, c)), f) for n, c, f in CUT_LEGS])
 def test_cut_into_calls(name, cut, fused):
     """i_steps carries across the calls and "step 1" happens once; the histories are read once at the end.  fused 0: every device
-    result is the one-call run's, bit for bit (the per-method loop launches the same kernels either way).  fused 3: the fixture at the
-    bars; in a cut into single steps the library's own report shows which form the step's last stage took"""
+    result is the one-call run's, bit for bit (the per-method loop launches the same kernels either way).  fused 3, and fused 4 on the
+    triangles: the fixture at the bars; in a cut into single steps the library's own report shows which form the step's last stage
+    took.  On the triangles with shock capturing every step but the last ends call by call -- the per-method filter and a fresh
+    extrapolation -- between stages of the folded kernel"""
     s = setup(name)
     ctx = hfx.Context(0)
     e, faces = make(ctx, s)
@@ -216,7 +249,7 @@ def test_cut_into_calls(name, cut, fused):
         run_loop(e, faces, n, fused)
         done += n
         assert ctx.get_clock()[1] == done
-        if fused == 3 and n == 1:
+        if fused in (3, 4) and n == 1:
             # behind a step whose last stage ran call by call the gradient is in memory; behind a fused one it stayed on chip, and a
             # download is refused.  A loop that quietly ran everything call by call would report 1 throughout
             assert is_current(e, hfx.GRAD_DISU_UPTS) == int(by_calls[done - 1]), (name, done)
@@ -234,13 +267,14 @@ def test_cut_into_calls(name, cut, fused):
 
 
 # ---- 3. against no monitors --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", [HEX, QUAD])
-def test_state_with_and_without_the_duties(name):
-    """fused 3: with the monitors that read no gradient the loop launches what it launched before and the final state is bit-equal to
-    a run without any; with the full set the sampled steps end call by call and the state agrees to 1e-12, the bound of DESIGN 6i"""
+@pytest.mark.parametrize("name,fused", [(HEX, 3), (QUAD, 3), (TRI, 4)], ids=[HEX, QUAD, TRI])
+def test_state_with_and_without_the_duties(name, fused):
+    """fused 3, and fused 4 on the triangles: with the monitors that read no gradient the loop launches what it launched before and
+    the final state is bit-equal to a run without any; with the full set the sampled steps end call by call and the state agrees to
+    1e-12, the bound of DESIGN 6i.  (Not the triangles with shock capturing: a sensor at its threshold may legitimately flip)"""
     s = setup(name)
-    none, free, full = one_call(name, 3, "none"), one_call(name, 3, "free"), one_call(name, 3)
-    check(s, free, "%s fused 3, gradient-free monitors" % name, free=True)
+    none, free, full = one_call(name, fused, "none"), one_call(name, fused, "free"), one_call(name, fused)
+    check(s, free, "%s fused %d, gradient-free monitors" % (name, fused), free=True)
     assert np.array_equal(free["u"], none["u"])
     err = np.abs(full["u"] - none["u"]).max() / np.abs(none["u"]).max()
     print("%s: state with every duty against none %.3e" % (name, err))
@@ -248,18 +282,24 @@ def test_state_with_and_without_the_duties(name):
 
 
 # ---- 4. atomic refusal -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("fused", [0, 3])
+@pytest.mark.parametrize("fused", [0, 3, 4])
 def test_a_call_one_history_refuses_leaves_everything_untouched(fused):
     """every history has room for the whole run but one, each in turn: the call is refused before any launch -- the clock, all four
-    counts and the state are as they were -- and once that history has room the same context runs and meets the fixture"""
-    s = setup(HEX)
+    counts and the state are as they were -- and once that history has room the same context runs and meets the fixture.  fused 4: on
+    the triangles"""
+    name = TRI if fused == 4 else HEX
+    s = setup(name)
     for which in HISTORIES:
         ctx = hfx.Context(0)
         e, faces = make(ctx, s, caps={which: s["need"][which] - 1} if s["need"][which] > 1 else None)
         if s["need"][which] == 1:
             # (one sample in the whole run: a capacity of 0 would drop the monitor; fill the history's only place by hand instead)
-            assert which == "probes"
-            e.sample_probes(0.0, 0)
+            assert which == "probes" or (name == TRI and which == "plot")
+            if which == "probes":
+                e.sample_probes(0.0, 0)
+            else:  # (the triangles' one plot file; its vorticity reads a gradient: a residual of the initial state leaves one)
+                hfx.CalcResidual(e, faces)
+                e.sample_plot(0.0, 0)
         u0 = e.download(hfx.DISU_UPTS0)
         before = counts(e)
         with pytest.raises(hfx.HfxError):
@@ -272,15 +312,19 @@ def test_a_call_one_history_refuses_leaves_everything_untouched(fused):
         register(ctx, e, s)
         assert counts(e) == dict.fromkeys(HISTORIES, 0)
         run_loop(e, faces, s["steps"], fused)
-        check(s, collect(ctx, e, s), "%s fused %d after a refusal by the %s history" % (HEX, fused, which))
+        check(s, collect(ctx, e, s), "%s fused %d after a refusal by the %s history" % (name, fused, which))
         close(e, faces, ctx)
 
 
-@pytest.mark.parametrize("fused", [0, 3])
+@pytest.mark.parametrize("fused", [0, 3, 4])
 def test_a_refused_call_leaves_the_controller_untouched(fused):
     """the driven channel after its two steps, nothing read: a further call finds each history full in turn (the others read empty) and
-    is refused before the controller evaluates -- its record, the clock, the counts, src_upts and the state are as they were"""
-    s = setup(DRIVEN)
+    is refused before the controller evaluates -- its record, the clock, the counts, src_upts and the state are as they were.
+    fused 4: the triangles after their five steps.  There is no driven triangle case (the reference's body force is three-dimensional,
+    tools/capture_full_loop.py), so that leg has no controller: the clock, the counts, the averages and the state"""
+    s = setup(TRI if fused == 4 else DRIVEN)
+    driven = s["forcing"] is not None
+    assert driven == (fused != 4)
     for which in HISTORIES:
         ctx = hfx.Context(0)
         e, faces = make(ctx, s)
@@ -288,16 +332,19 @@ def test_a_refused_call_leaves_the_controller_untouched(fused):
         for other in HISTORIES:
             if other != which:
                 dict(probes=e.read_probes, integral=e.read_integral_history, history=e.read_history, plot=e.read_plot_snapshots)[other]()
-        before, clock, state = counts(e), ctx.get_clock(), e.body_force_state()
-        u0, src0, rows0 = e.download(hfx.DISU_UPTS0), e.download(hfx.SRC_UPTS), e.body_force_history()
+        before, clock = counts(e), ctx.get_clock()
+        u0, avg0 = e.download(hfx.DISU_UPTS0), e.download_average()
+        if driven:
+            state, src0, rows0 = e.body_force_state(), e.download(hfx.SRC_UPTS), e.body_force_history()
         assert before == {k: (s["need"][k] if k == which else 0) for k in HISTORIES}
         with pytest.raises(hfx.HfxError):
-            run_loop(e, faces, 2, fused)  # (steps 3 and 4: every monitor samples, and would have room had it been read)
-        after = e.body_force_state()
+            run_loop(e, faces, 2, fused)  # (the next two steps: every monitor samples, and would have room had it been read)
         assert ctx.get_clock() == clock and counts(e) == before, which
-        assert all(np.array_equal(state[k], after[k]) for k in state), which
-        assert np.array_equal(e.body_force_history(), rows0) and np.array_equal(e.download(hfx.SRC_UPTS), src0), which
-        assert np.array_equal(e.download(hfx.DISU_UPTS0), u0), which
+        if driven:
+            after = e.body_force_state()
+            assert all(np.array_equal(state[k], after[k]) for k in state), which
+            assert np.array_equal(e.body_force_history(), rows0) and np.array_equal(e.download(hfx.SRC_UPTS), src0), which
+        assert np.array_equal(e.download(hfx.DISU_UPTS0), u0) and np.array_equal(e.download_average(), avg0), which
         close(e, faces, ctx)
 
 
@@ -443,6 +490,61 @@ def test_the_first_reader_decides_how_a_pending_stage_runs(announce):
     close(e, faces, ctx)
 
 
+@pytest.mark.parametrize("announce", [False, True])
+def test_the_first_reader_decides_how_a_pending_triangle_stage_runs(announce):
+    """the triangle counterpart: the calls of one RK45 step on fl_tri_p3_walls with `deferred` 1, every whole stage planned as the 2-D
+    simplex stage.  A probe sample and the time averages read the state alone: behind them the pending last stage has run fused, and
+    the integral sample of the same step is refused, never served an older gradient.  With the step's samples announced first that
+    one stage is replayed call by call, and the history row, the integral row and the wall forces are the driver's row of step 1.
+    Either way the state is the lockstep's after step 1 and the probes are its probes"""
+    from test_gpu_deferred import calc_residual_calls, tag
+    s = setup(TRI)
+    d, w = s["d"], s["w"]
+    ctx = hfx.Context(0)
+    ctx.set_option("deferred", 1)
+    e, faces = make(ctx, s)
+    tag(e, d)
+    n_stages = int(d["sizes"][7])
+    for rk in range(n_stages):
+        calc_residual_calls([e], faces, True, rk)
+        e.AdvanceSolution(rk, 3)
+    dt = w["dt"]
+    if announce:
+        hfx.flush_for_samples([e], integrals=True, history=True, plot=True)
+    e.sample_probes(dt, 1)
+    e.CalcTimeAverageQuantities(dt, dt)
+    if not announce:
+        assert ctx.deferred_stats()[:2] == (n_stages, 0), ctx.deferred_stats()[2]
+        with pytest.raises(hfx.HfxError, match="was not materialised by the fused stage that ran last"):
+            e.sample_integral_quantities(dt, 1)
+        with pytest.raises(hfx.HfxError):  # (the viscous wall forces read the same gradient)
+            e.sample_history(dt, 1)
+        assert e.integral_count() == 0 and e.history_count() == 0
+    else:
+        e.sample_integral_quantities(dt, 1)
+        e.sample_history(dt, 1)
+        e.sample_plot(dt, 1)
+        assert ctx.deferred_stats()[:2] == (n_stages - 1, 1), ctx.deferred_stats()[2]
+        nd, r = e.n_dims, w["hist"][0]
+        _, _, res, frc = e.read_history()
+        log = np.log10(HU.norm_residual(s["norm"], res[:, 0], e.n_upts * e.n_eles))
+        force = np.concatenate([frc[:nd, 0] + frc[nd:2 * nd, 0], frc[2 * nd:, 0]])
+        integ = e.read_integral_history()[2][:, 0]
+        miss = (HU.log_miss(log, d["hist_res"][0]), HU.value_miss(force, d["hist_force"][0], r["force_scale"]),
+                HU.value_miss(integ, d["hist_diag"][0], np.abs(d["hist_diag"][0]).max()))
+        print("triangles, row of step 1 behind the announced flush: residual %.3g, force %.3g, integral %.3g bars" % miss)
+        assert max(miss) <= 1.0
+    assert_simplex_stage(e)
+    assert np.array_equal(e.download_average()[:, :, 0], e.download(hfx.DISU_UPTS0)[:, :, 0])  # (step 1: a = 0, b = 1)
+    probes = e.read_probes()[2][:, np.argsort(s["P"]["perm"]), :]
+    assert s["probe_steps"][0] == 1
+    miss = (max(FU.probe_miss(probes, s["probe_values"][:, :, :1])) / 1e-11,
+            float(np.abs(e.download(hfx.DISU_UPTS0) - w["states"][0]).max() / np.abs(w["states"][0]).max()) / 1e-11)
+    print("triangles deferred, announce %d: probes %.3g, state %.3g bars" % ((announce,) + miss))
+    assert max(miss) <= 1.0
+    close(e, faces, ctx)
+
+
 # ---- 7. partitioned ---------------------------------------------------------------------------------------------------------------------
 def _partitioned_worker(rank, world, port, outdir):
     import faulthandler
@@ -500,3 +602,44 @@ def test_partitioned(tmp_path):
         got.setdefault("avg", None)
         check(s, got, "%s partitioned, %s" % (HEX, "fused mode 3, gradient-free monitors" if tag == "free" else "fused mode 2"),
               free=tag == "free")
+
+
+REFUSALS = ["the history monitor samples the viscous wall forces", "the plot monitor has a field that reads grad_disu_upts",
+            "the integral monitor has a quantity that reads grad_disu_upts"]
+
+
+def test_partitioned_triangles():
+    """fl_tri_p3_walls cut into three virtual parts of one rank (FU.TRI_PARTS: one partition group, one interior group) through
+    hfx_run_steps_partitioned_blocks, whose stages keep the gradient on chip.  With the full monitor set the call is refused before the
+    first launch, for the history monitor's wall forces first, then -- that monitor on the residuals alone -- for the plot monitor's
+    vorticity, then for the integral monitor's enstrophy; each time the state, the clock, the averages and all four counts are as they
+    were.  The gradient-free set then runs on the same blocks and meets the driver's rows"""
+    from test_tris_partition_oracle import grow_parts, virtual_tables
+    s = setup(TRI)
+    d = s["d"]
+    reg, L, Rlut, seg = virtual_tables(d, grow_parts(d, *FU.TRI_PARTS))
+    ctx = hfx.Context(0)
+    e, faces = build(ctx, reg)
+    m = hfx.MpiInters(ctx, e, L, Rlut)
+    m.set_neighbours(seg)
+    comm = hfx.Comm(ctx.h, hfx.comm_unique_id(), 1, 0)
+    register(ctx, e, s)
+    u0 = e.download(hfx.DISU_UPTS0)
+    for k, words in enumerate(REFUSALS):
+        if k == 1:
+            ctx.set_history_monitor(s["norm"], False, s["freq"], capacity=s["need"]["history"])
+        if k == 2:
+            ctx.set_plot_monitor(s["free_diag"], plot_freq=s["plot_freq"], capacity=s["need"]["plot"])
+        with pytest.raises(hfx.HfxError, match=words):
+            hfx.run_steps_partitioned_blocks([e], faces, [m], comm, s["steps"])
+        assert ctx.get_clock()[:2] == (0.0, 0) and counts(e) == dict.fromkeys(HISTORIES, 0), words
+        assert np.array_equal(e.download(hfx.DISU_UPTS0), u0) and not e.download_average().any(), words
+    register(ctx, e, s, "free")
+    hfx.run_steps_partitioned_blocks([e], faces, [m], comm, s["steps"])
+    pp = e.simplex2d_partition_plan()
+    assert (pp["partition_groups"], pp["interior_groups"]) == (1, 1), pp
+    assert e.simplex2d_plan()["group"] == G_P3
+    got = collect(ctx, e, s)
+    comm.close()
+    close(e, faces + [m], ctx)
+    check(s, got, "%s partitioned, three virtual parts, gradient-free monitors" % TRI, free=True)

@@ -129,6 +129,29 @@ def test_other_element_classes_with_seven_points_per_face(ctx, name, n_inters):
     close(e, faces)
 
 
+@pytest.mark.parametrize("fix_vis", [1, 0])
+def test_triangle_wall_faces_from_the_reference(ctx, fix_vis):
+    """fl_tri_p3_walls (tests/golden/full_loop): 40 P3 triangles between an isothermal and an adiabatic wall, the 8 wall faces and the
+    surface cubature as the reference itself formed them (the harness's dump; the host mirror builds no triangles) -- 4 points per
+    face, all 3 local faces among the walls, node lists rotated.  After one hfx_CalcResidual, with the constant viscosity and with
+    Sutherland's law, against the restatement on the downloaded state and gradient at its derived bar"""
+    import full_loop_util as FU
+    d = FU.load("fl_tri_p3_walls")
+    F = FU.force_setup(d)
+    A = F["A"]
+    assert len(A["face_ele"]) == 8 and set(A["face_inter"].tolist()) == {0, 1, 2} and A["opp"][0].shape == (4, 10)
+    e, faces = build(ctx, d)
+    p = hfx.params_from(d)
+    p.fix_vis = float(fix_vis)
+    ctx.set_params(p)
+    ctx.set_force_reference(**F["ref"])
+    register(e, A)
+    hfx.CalcResidual(e, faces)
+    grad = e.download(hfx.GRAD_DISU_UPTS)
+    check_device(e, A, d["u_init"], grad, dict(F["phys"], fix_vis=float(fix_vis)), F["ref"], "fl_tri_p3_walls fix_vis %d" % fix_vis)
+    close(e, faces)
+
+
 @functools.lru_cache(maxsize=None)
 def p4_channel():
     """18 P4 hexahedra between an isothermal and a dual-consistent slip wall, from the host mirror: 36 wall faces of 5 x 5 points"""

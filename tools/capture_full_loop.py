@@ -21,6 +21,12 @@ Conditions enforced before a file is written, on the CPU, through tests/full_loo
      tests/plot_rows_util.py, with the reference's pairing: the state after the step, the corrected gradient of the last stage's input;
   3. the fixture can tell right from subtly wrong: the sensitivity numbers of tests/full_loop_util.py, each stored in the file, each
      more than 1e-6 in every row or file it is formed for.  dt is the neighbouring hr_* case's; no case needed a larger one.
+The triangle cases (see TRI_MESH below) also hold what the host mirror cannot give: the surface cubature of every local face as the
+reference formed it (HFX_DUMP_INTERS_CUBPTS: opp_, weight_, inter_detjac_ and norm_inters_cubpts_l in the mirror's shapes, and the
+reference state of the wall forces); the wall list is derived from the boundary tables in tests/full_loop_util.py.  On the triangle
+case with shock capturing the harness runs without the filter, as on the forced case it runs without the force: condition 1 ties the
+oracle WITHOUT the filter to it, condition 2 the oracle WITH it to every row of the driver, the sensor column among them, and the
+file holds how many elements the filter took per stage and per step -- in every step at least one and not all.
 
 Nothing under oracle/ is written: everything runs in a temporary directory, and no bytecode cache is left.  The archive is written
 with fixed member times, so that a second capture gives the same bytes.
@@ -31,6 +37,7 @@ with fixed member times, so that a second capture gives the same bytes.
 import glob
 import json
 import os
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -43,19 +50,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import capture_history_rows as CH  # noqa: E402  (puts oracle/, tests/ and the package on the path)
 import capture_plot_rows as CP  # noqa: E402
+import capture_tris_shock as CTS  # noqa: E402
 from capture_golden import read_dump, write_neu, write_neu_tets  # noqa: E402
+from gen_neu_mesh import box_vertices  # noqa: E402
 import full_loop_util as FU  # noqa: E402
+import hfx  # noqa: E402
 import integral_history_util as IU  # noqa: E402
 import plot_rows_util as PU  # noqa: E402
+import tri_shock_util as TS  # noqa: E402
+import tri_util as T  # noqa: E402
 
 GOLDEN = FU.FL_DIR
 MAX_BYTES = CH.MAX_BYTES
+CTS_SHOCK = CTS.SHOCK  # (shock_cap 1, expf_fac 36, expf_order 4, expf_cutoff 1, shock_det_field 0: the keys of ts_p3_n4)
 
 
-def derive(base, name, steps, forced=False, **over):
-    """the case `base` of tools/capture_history_rows.py with other steps and input keys; forced: the driver runs with body_forcing 1"""
+def derive(base, name, steps, forced=False, mesh=None, **over):
+    """the case `base` of tools/capture_history_rows.py with other steps and input keys; forced: the driver runs with body_forcing 1;
+    mesh: other entries of the case itself (n, tris, orient_seed, shock)"""
     b = next(c for c in CH.CASES if c["name"] == base)
-    c = dict(b, name=name, steps=steps, forced=forced, keys=dict(b["keys"]))
+    c = dict(b, name=name, steps=steps, forced=forced, keys=dict(b["keys"]), **(mesh or {}))
     c["keys"].pop("pairing", None)
     c["keys"].pop("forced", None)
     c["keys"].update(over)
@@ -87,6 +101,31 @@ CASES = [
            average_fields="1 rho_average"),
 ]
 
+# TRIANGLES.  The box of fl_quad_p3_walls with 4 x 5 squares, each cut into two deformed P3 triangles (tests/tri_util.py:
+# write_neu_tris): 40 elements, at G = 32 one whole group of the fused 2-D simplex stage and a ragged one of 8; node lists rotated,
+# cyclic in x, an isothermal wall on y-, an adiabatic one on y+.  The keys of fl_quad_p3_walls (viscous, RK45, dt_type 0,
+# calc_force 1, its dt) and the time averages; p_res 5, the smallest with more than one plot point strictly inside a triangle: the
+# probes of tests/full_loop_util.py sit there.  The host mirror builds no triangles: the harness dumps the surface cubature of the
+# wall forces itself (HFX_DUMP_INTERS_CUBPTS)
+TRI_MESH = dict(n=[4, 5], tris=True, orient_seed=5)
+TRI_KEYS = dict(upts_type_tri=0, fpts_type_tri=0, vcjh_scheme_tri=1, c_tri=0.0, monitor_res_freq=2,
+                integral_quantities="2 kineticenergy enstropy", plot_freq=3, p_res=5, average_fields="3 rho_average u_average e_average")
+CASES += [
+    derive("hr_quad_p3_walls", "fl_tri_p3_walls", steps=5, mesh=TRI_MESH, diagnostic_fields="2 mach vorticity", **TRI_KEYS),
+    # the same with shock_cap 1 for the DRIVER and the sensor among the plotted fields.  The harness does not dump a triangle run
+    # with the filter (tools/capture_tris_shock.py): it runs with shock_cap 0 and gives the arrays; the filter's operators are rebuilt
+    # in numpy (hfx.tri_shock_operators).  Condition 1 is split as on a forced case: the oracle WITHOUT the filter is tied to the
+    # harness's last state, the oracle WITH it to every row the driver wrote, the sensor column among them.  s0: the first of
+    # tri_shock_util.choose_s0's gaps of the first stage's sensors for which no sensor value of any stage of the run lies within
+    # tri_shock_util.MARGIN of it and in EVERY step at least one element and not all are filtered; the mesh amplitude is the base's
+    derive("hr_quad_p3_walls", "fl_tri_p3_shock", steps=5, mesh=dict(TRI_MESH, shock=dict(CTS_SHOCK)),
+           diagnostic_fields="3 mach vorticity sensor", **TRI_KEYS),
+    # NO fl_tri_p3_forced: the reference's body force exists in three dimensions only.  Its CalcResidual evaluates the mass-flux
+    # controller under `FlowSol->n_dims == 3` (src/solver.cpp:97), so the genuine driver with body_forcing 1 on this box IS the run
+    # of fl_tri_p3_walls -- it prints no controller line and adds no source -- and there is nothing of the driver's to compare a
+    # forced triangle block with; hfx_eles_set_body_force refuses a two-dimensional block for the same reason
+]
+
 
 def save_npz(path, arrays):
     """np.savez_compressed with the members' times fixed: the same arrays give the same bytes"""
@@ -98,12 +137,47 @@ def save_npz(path, arrays):
                 np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
 
 
+def run(cmd, td, env, name):
+    r = subprocess.run(cmd, cwd=td, env=env, capture_output=True, text=True)
+    if r.returncode != 0:
+        sys.stderr.write(r.stdout[-3000:] + r.stderr[-3000:])
+        raise SystemExit("%s failed for %s" % (os.path.basename(cmd[0]), name))
+    return r.stdout
+
+
+def shock_arrays(c, arrs):
+    """the filter of a triangle case: the operators of eles_tris rebuilt from the harness's loc_upts, and s0 (see the case)"""
+    sh = c["shock"]
+    n_eles, order = int(arrs["sizes"][0]), int(arrs["sizes"][5])
+    iv, ef, norm, high = hfx.tri_shock_operators(arrs["loc_upts"], order, sh["expf_fac"], sh["expf_order"], sh["expf_cutoff"])
+    out = dict(shock_cap=np.array([1], dtype=np.int32), inv_vandermonde=iv, exp_filter=ef, norm_basis_persson=norm,
+               persson_high_modes=high, shock_det_field=np.array([sh["shock_det_field"]], dtype=np.int32),
+               expf_fac=np.array([sh["expf_fac"]]), expf_order=np.array([sh["expf_order"]], dtype=np.int32),
+               expf_cutoff=np.array([sh["expf_cutoff"]], dtype=np.int32), s0=np.array([np.inf]))
+    block = dict(arrs, **out)
+    first = TS.lockstep(block, 1, shock=False)["stage_sensors"][0]
+    n_stages = int(arrs["sizes"][7])
+    for skip in range(12):
+        s0 = TS.choose_s0(first, skip)
+        sens = TS.lockstep(block, c["steps"], s0=s0)["stage_sensors"]
+        per_step = [int((sens[s * n_stages:(s + 1) * n_stages] >= s0).any(axis=0).sum()) for s in range(c["steps"])]
+        if TS.closest(sens, s0) > TS.MARGIN and all(0 < k < n_eles for k in per_step):
+            out["s0"] = np.array([s0])
+            return out
+        print("%s: s0 %.4e of gap %d: closest %.1e, filtered per step %s of %d -- the next-widest gap"
+              % (c["name"], s0, skip, TS.closest(sens, s0), per_step, n_eles))
+    raise SystemExit("%s: no s0 filters at least one element and not all in every step: raise the amplitude" % c["name"])
+
+
 def capture(c):
-    forced = c["forced"]
+    forced, shock = c["forced"], c.get("shock")
     with tempfile.TemporaryDirectory() as td:
         mesh = os.path.join(td, "mesh.neu")
         if c.get("tets"):
             xv = write_neu_tets(mesh, c["n"], amp=c["amp"])
+        elif c.get("tris"):
+            xv = box_vertices(c["n"], 2, amp=c["amp"])
+            T.write_neu_tris(mesh, c["n"], xv, bcs=c.get("bcs"), orient_seed=c.get("orient_seed"))
         else:
             xv = write_neu(mesh, c["n"], c["dims"], amp=c["amp"], bcs=c.get("bcs"))
         keys = dict(c["keys"])
@@ -114,19 +188,29 @@ def capture(c):
         with open(os.path.join(td, "input"), "w") as f:
             for k, v in keys.items():
                 f.write("%s %s\n" % (k, repr(v) if isinstance(v, float) else v))
-        if forced:  # (the driver's input alone)
-            with open(os.path.join(td, "input_forced"), "w") as f:
-                f.write(open(os.path.join(td, "input")).read() + "body_forcing 1\n")
         env = dict(os.environ, HIFILES_HOME=CH.REF_HOME, HFX_DUMP_PPTS="1")
-        driver_out = ""
-        for cmd in ([CH.DRIVER, "input_forced" if forced else "input"], [CH.HARNESS, "input", "dump.bin", str(c["steps"]), str(c["level"])]):
-            r = subprocess.run(cmd, cwd=td, env=env, capture_output=True, text=True)
-            if r.returncode != 0:
-                sys.stderr.write(r.stdout[-3000:] + r.stderr[-3000:])
-                raise SystemExit("%s failed for %s" % (os.path.basename(cmd[0]), c["name"]))
-            if cmd[0] == CH.DRIVER:
-                driver_out = r.stdout
-        arrs = read_dump(os.path.join(td, "dump.bin"))
+        if c.get("tris"):
+            env["HFX_DUMP_INTERS_CUBPTS"] = "1"
+        # the harness, in a directory of its own beside the driver's
+        hd = os.path.join(td, "harness")
+        os.mkdir(hd)
+        for f in ("mesh.neu", "input"):
+            shutil.copyfile(os.path.join(td, f), os.path.join(hd, f))
+        run([CH.HARNESS, "input", "dump.bin", str(c["steps"]), str(c["level"])], hd, env, c["name"])
+        arrs = read_dump(os.path.join(hd, "dump.bin"))
+        # the driver's input alone: the body force; the shock filter with the s0 the harness's arrays give
+        more = {}
+        if forced:
+            more["body_forcing"] = 1
+        if shock:
+            filt = shock_arrays(c, arrs)
+            arrs.update(filt)
+            more.update(shock, s0=float(filt["s0"][0]))
+        with open(os.path.join(td, "input_driver"), "w") as f:
+            f.write(open(os.path.join(td, "input")).read())
+            for k, v in more.items():
+                f.write("%s %s\n" % (k, repr(v) if isinstance(v, float) else v))
+        driver_out = run([CH.DRIVER, "input_driver"], td, env, c["name"])
         sz = [int(v) for v in arrs["sizes"]]
         n_eles, n_fields, n_dims, n_stages = sz[0], sz[3], sz[4], sz[7]
         calc_force = int(keys.get("calc_force", 0))
@@ -179,13 +263,15 @@ def capture(c):
             raise SystemExit("%s: the driver printed %d controller lines for %d steps" % (c["name"], len(lines), steps))
         out["driver_controller"] = np.array([[float(x) for x in l.split(":")[1].split(",")] for l in lines])
     meta = dict(name=c["name"], n=c["n"], dims=c["dims"], amp=c["amp"], steps=steps, level=c["level"], keys=c["keys"],
-                bcs=c.get("bcs"), orient_seed=None,
+                bcs=c.get("bcs"), orient_seed=c.get("orient_seed"),
                 generator="tools/capture_full_loop.py via oracle/_ref/HiFiLES_ref and oracle/_ref/ref_harness (genuine reference)")
+    if c.get("tris"):
+        meta.update(mesh="tests/tri_util.py: write_neu_tris", driver_keys=more)
     out["meta_json"] = np.frombuffer(json.dumps(meta).encode(), dtype=np.uint8)
 
     # the conditions, through the oracle
     w = FU.walk(out)
-    free = w["unforced"] if forced else w["states"][-1]
+    free = FU.harness_state(out, w)
     tie = float(np.abs(free - arrs[last]).max() / np.abs(arrs[last]).max())
     if not tie <= 1e-11:
         raise SystemExit("%s: driver and harness are not one run: the oracle's last state misses the harness's by %.2e" % (c["name"], tie))
@@ -206,6 +292,11 @@ def capture(c):
             raise SystemExit("%s: %s is %s: raise dt or the amplitude" % (c["name"], k, v))
         out["sens_" + k] = np.array(v)
     out["state_tie"] = np.array([tie])
+    if shock:
+        per_stage, per_step, gap = FU.filtered_counts(out)
+        if not (gap > TS.MARGIN and np.all((per_step >= 1) & (per_step <= sz[0] - 1))):
+            raise SystemExit("%s: filtered per step %s of %d, closest sensor value %.1e from s0" % (c["name"], per_step, sz[0], gap))
+        out["filtered_per_stage"], out["filtered_per_step"], out["closest_sensor_to_s0"] = per_stage, per_step, np.array([gap])
     out["rows_paired_bars"] = np.array([s["bars"] for s in w["plot"]]).max(axis=0)  # per column behind the position, as the pr_* files
     out["hist_paired_bars"] = np.array([max(r[k] for k in ("res_bars", "force_bars", "diag_bars") if k in r) for r in w["hist"]])
 
