@@ -266,10 +266,11 @@ def primitive_minima(u, gamma):
     return float(rho.min()), float(p.min())
 
 
-def oracle_steps(d, n_steps=N_STEPS):
+def oracle_steps(d, n_steps=N_STEPS, dt_map=None):
     """n_steps time steps of the oracle on a single-class block, in the reference's call order (tests/test_oracle_vs_golden.py:
     CFL time step, calc_sgs_terms at the first stage, CalcResidual with boundary faces, AdvanceSolution, shock capturing)
-    -> per step a dict of copies: u, div (of the last stage), sensor (shock capturing) and bad (the worst NaN report, -1: none)"""
+    -> per step a dict of copies: u, div (of the last stage), sensor (shock capturing) and bad (the worst NaN report, -1: none).
+    dt_map (dt_type 2): what a deliberately WRONG run does to the local time steps before it uses them"""
     import oracle_py as O
     o = O.load()
     c = O.Case(d)
@@ -287,6 +288,7 @@ def oracle_steps(d, n_steps=N_STEPS):
             dtl = np.array([o.orc_calc_dt_local(C.byref(e), C.byref(c.params), i, h[i], CFL, order) for i in range(c.n_eles)])
             c.params.dt = dtl.min()
             if dt_type == 2:
+                dtl = dtl if dt_map is None else np.ascontiguousarray(dt_map(dtl))
                 c._dtl = dtl
                 e.dt_local = dtl.ctypes.data_as(O.dp)
         for rk in range(nstage):

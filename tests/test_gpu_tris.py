@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 TOL_1, TOL_DIV, TOL_U, TOL_FPTS = 1e-12, 5e-11, 1e-11, 1e-12
 NAMES = T.names()
 SIZES = {(3, 6): (0, 64), (6, 9): (1, 64), (10, 12): (2, 32), (15, 15): (3, 32), (21, 18): (4, 16)}  # SIMPLEX2D_SIZES of csrc/simplex2d.hpp
-G_P3 = 32
+G_P3 = T.GROUP[3]
 relerr = T.relerr
 
 
@@ -120,8 +120,9 @@ def test_per_method_states(ctx, name):
 
 
 # ---- 2. the fused stage ----------------------------------------------------------------------------------------------------------
-def run_fused_steps(ctx, d, want, what, opts=()):
-    """one call of one step per entry of `want` (the state after that step, or None); -> the plan that ran"""
+def run_fused_steps(ctx, d, want, what, opts=(), grids=None):
+    """one call of one step per entry of `want` (the state after that step, or None); -> the plan that ran (grids: a list that
+    receives hfx.fused_launch_grids of the last stage)"""
     for k, v in opts:
         ctx.set_option(k, v)
     try:
@@ -135,9 +136,12 @@ def run_fused_steps(ctx, d, want, what, opts=()):
                 assert per_ele.max() < TOL_U, (what, st, int(per_ele.argmax()), per_ele.max())
                 if w.get("div") is not None:
                     err = relerr(e.download(hfx.DIV_TCONF_UPTS), w["div"])
+                    print("%s step %d: div_tconf_upts %.2e" % (what, st, err))
                     assert err < 10 * TOL_DIV, (what, st, err)  # (of the step's LAST stage: the bar of tests/test_gpu_general_batches.py)
             check_fpts_and_nan(e, d, "%s step %d" % (what, st))
         plan = e.simplex2d_plan()
+        if grids is not None:
+            grids.extend(hfx.fused_launch_grids(e.h))
         close(e, faces)
         return plan
     finally:

@@ -114,3 +114,49 @@ def test_cut_blocks_are_sound_inputs(n):
         moves = G.element_moves(before, u)
         assert moves.min() > 1e-6, (st, int(moves.argmin()), moves.min())
         before = u
+
+
+# ---- the blocks of tests/test_gpu_tris_orders.py: whole and later groups at every instantiated order -----------------------------
+ORDER_BLOCKS = T.order_blocks() + T.SWITCH_BLOCKS
+LOCAL_DT_BLOCKS = [(name, n) for name, n in T.SWITCH_BLOCKS if name == "tri_p2_cfl_local"]
+
+
+@pytest.mark.parametrize("name,n", ORDER_BLOCKS)
+def test_order_blocks_are_sound_inputs(name, n):
+    """every flux point belongs to one face, the oracle reports no NaN over N_STEPS steps and every element moves by more than 1e-6
+    of max |u| in every step; where the block has elements a and a + G, their final states differ by more than 1e-6 of max |u|
+    for EVERY a -- a kernel that takes group k's element for group k + 1's cannot meet the bar on any of them"""
+    g = T.group_of(name)
+    d = T.block(n, name)
+    assert int(d["sizes"][0]) == n and (G.face_census(d) == 1).all()
+    assert any(k.startswith("bdy") for k in d) and any(k.startswith("int") for k in d)
+    if name in T.KINDS:
+        fl = np.asarray(d["bc_flags"]).reshape(3, -1, order="F")
+        used = sorted({int(fl[0, i]) for t in range(3) if "bdy%d_id" % t in d for i in np.ravel(d["bdy%d_id" % t])})
+        assert used == sorted(T.KINDS[name]), used
+    ref = T.block_reference(n, name)
+    before = d["u_init"]
+    for st, r in enumerate(ref):
+        assert r["bad"] == -1 and np.isfinite(r["u"]).all(), (st, r["bad"])
+        moves = G.element_moves(before, r["u"])
+        assert moves.min() > 1e-6, (st, int(moves.argmin()), moves.min())
+        before = r["u"]
+    if n > g:
+        diff = T.offset_differences(ref[-1]["u"], g)
+        print("%s, %d elements: elements a and a + %d differ by %.1e at least" % (name, n, g, diff.min()))
+        assert diff.size == n - g and diff.min() > 1e-6, (int(diff.argmin()), diff.min())
+
+
+@pytest.mark.parametrize("name,n", LOCAL_DT_BLOCKS)
+def test_local_time_steps_of_another_group_miss(name, n):
+    """dt_type 2: the oracle with dt_local rolled by G elements, and with every group reading group 0's dt_local, misses the
+    right result by more than 1e-6 -- on elements beyond group 0 in the second case"""
+    g = T.group_of(name)
+    d = T.block(n, name)
+    assert int(np.ravel(d["dt_type"])[0]) == 2
+    right = T.block_reference(n, name)[-1]["u"]
+    rolled = G.oracle_steps(d, T.N_STEPS, dt_map=lambda dtl: np.roll(dtl, g))[-1]["u"]
+    group0 = G.oracle_steps(d, T.N_STEPS, dt_map=lambda dtl: dtl[np.arange(n) % g])[-1]["u"]
+    miss = [T.relerr(rolled, right), T.relerr(group0[:, g:], right[:, g:]), T.relerr(group0[:, :g], right[:, :g])]
+    print("%s, %d elements: rolled dt_local %.1e, group 0's dt_local %.1e beyond group 0 (%.1e inside)" % (name, n, *miss))
+    assert miss[0] > 1e-6 and miss[1] > 1e-6, miss

@@ -15,7 +15,7 @@ import ragged_partition as RP
 import tri_util as T
 
 TOL_U = 1e-11
-GROUP = {1: 64, 2: 64, 3: 32, 4: 32, 5: 16}  # elements per group by order: SIMPLEX2D_SIZES of csrc/simplex2d.hpp
+GROUP = T.GROUP                              # elements per group by order: SIMPLEX2D_SIZES of csrc/simplex2d.hpp
 CUT4 = ([10, 3, 2, 1], 13)                   # (weights, seed): four ragged parts
 VIRTUAL3 = ([3, 2, 1], 3)                    # three virtual parts of one rank (a seed whose six segments differ in size on every fixture)
 G_P3 = GROUP[3]
@@ -87,23 +87,24 @@ def virtual_tables(reg, part):
     return RP.cut_self(reg, part)
 
 
-def block_parts(n):
-    """the virtual parts of tri_util.block(n), n = 1, G - 1, G + 1, 2 G + 1 at P3.  1: nothing to cut.  G - 1: one partial group, every
-    third element a part.  G + 1: the cut lies inside the whole group and away from element G and its neighbours, so that the last
-    partial group is an interior group.  2 G + 1: three runs of consecutive elements."""
-    d = T.block(n)
+def block_parts(n, name=T.CUT_FROM):
+    """the virtual parts of tri_util.block(n, name), n = 1, G - 1, G + 1, 2 G + 1 at the fixture's G.  1: nothing to cut.  G - 1: one
+    partial group, every third element a part.  G + 1: the cut lies inside the whole group and away from element G and its
+    neighbours, so that the last partial group is an interior group.  2 G + 1: three runs of about 2 G / 3 consecutive elements."""
+    g = T.group_of(name)
+    d = T.block(n, name)
     v = np.zeros(n, dtype=np.int64)
-    if n == G_P3 - 1:
+    if n == g - 1:
         v = np.arange(n) % 3
-    elif n == G_P3 + 1:
+    elif n == g + 1:
         adj = adjacency(d)
-        near_last = {G_P3} | set(adj[G_P3])
+        near_last = {g} | set(adj[g])
         near_last |= {q for el in list(near_last) for q in adj[el]}
-        others = [el for el in range(G_P3) if el not in near_last]
+        others = [el for el in range(g) if el not in near_last]
         v[others[0::3]] = 1
         v[others[1::3]] = 2
-    elif n == 2 * G_P3 + 1:
-        v = np.arange(n) // 22
+    elif n == 2 * g + 1:
+        v = np.arange(n) // ((n + 2) // 3)  # (runs of 22 at G = 32)
     return v
 
 
@@ -202,7 +203,29 @@ def test_census_of_the_cuts():
     assert interior_present and zero_interior and partial_on_partition and partial_on_interior and part_without_free_element
 
 
+# (partition groups, interior groups) of block_parts at n = G - 1, G + 1, 2 G + 1, per fixture: what tests/test_gpu_tris_orders.py asserts
+# of hfx_simplex2d_partition_plan.  At P1 the one element of group 2 owns no partition face
+ORDER_CUTS = {"tri_p1_n4_deformed": [(1, 0), (1, 1), (2, 1)], "tri_p2_n3_deformed": [(1, 0), (1, 1), (3, 0)],
+              "tri_p3_n4_deformed": [(1, 0), (1, 1), (3, 0)], "tri_p4_n2_deformed": [(1, 0), (1, 1), (3, 0)],
+              "tri_p5_n2_deformed": [(1, 0), (1, 1), (3, 0)]}
+
+
+def order_cuts():
+    """(fixture, n, (partition groups, interior groups))"""
+    for name, want in ORDER_CUTS.items():
+        g = T.group_of(name)
+        for n, w in zip((g - 1, g + 1, 2 * g + 1), want):
+            yield name, n, w
+
+
 def test_block_cuts_are_what_the_gpu_tests_assert():
-    """the group counts tests/test_gpu_tris_partition.py expects of hfx_simplex2d_partition_plan on the four blocks"""
+    """the group counts tests/test_gpu_tris_partition.py and tests/test_gpu_tris_orders.py expect of hfx_simplex2d_partition_plan"""
     got = {n: group_census(*virtual_tables(T.block(n), block_parts(n))[:2])[:2] for n in BLOCKS}
     assert got[1] == (0, 1) and got[G_P3 - 1] == (1, 0) and got[G_P3 + 1] == (1, 1) and got[2 * G_P3 + 1][0] >= 2, got
+    assert sorted(ORDER_CUTS) == sorted(T.BY_ORDER.values())
+    for name, n, want in order_cuts():
+        reg, L, Rlut, seg = virtual_tables(T.block(n, name), block_parts(n, name))
+        nfp = int(reg["sizes"][2])
+        seen = [np.ravel(L)] + [np.ravel(reg[k]) for k in reg if k.startswith(("int", "bdy")) and k.endswith(("_L", "_R"))]
+        assert np.array_equal(np.sort(np.concatenate(seen)), np.arange(nfp * n)), (name, n)
+        assert len(seg) == 6 and group_census(reg, L)[:2] == want, (name, n, group_census(reg, L))

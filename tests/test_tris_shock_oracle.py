@@ -83,7 +83,7 @@ def partition_census(name, part):
     """per stage: (filtered elements in partition groups, in interior groups) of fixture `name` cut into the virtual parts"""
     d = TS.load(name)
     reg, L, Rlut, seg = virtual_tables(d, part)
-    ne, nfp, G = int(d["sizes"][0]), int(d["sizes"][2]), {1: 64, 2: 64, 3: 32, 4: 32, 5: 16}[int(d["sizes"][5])]
+    ne, nfp, G = int(d["sizes"][0]), int(d["sizes"][2]), T.GROUP[int(d["sizes"][5])]
     marked = np.zeros((ne + G - 1) // G, dtype=bool)
     marked[np.unique((np.ravel(L) // nfp) // G)] = True
     ref = TS.reference(name)
@@ -106,3 +106,52 @@ def test_virtual_partitions_are_sound_inputs(name):
     assert any(a > 0 for a, b in census)
     if name == "ts_p3_cylinder":
         assert n_int > 0 and any(a > 0 and b > 0 for a, b in census)
+
+
+# ---- the blocks of tests/test_gpu_tris_orders.py: the filter in whole and later groups at every instantiated order ---------------
+def group_of(name):
+    return T.group_of(bytes(TS.load(name)["based_on"]).decode())
+
+
+ORDER_BLOCKS = [(TS.BY_ORDER[p], n) for p in sorted(TS.BY_ORDER) for n in (group_of(TS.BY_ORDER[p]), 2 * group_of(TS.BY_ORDER[p]) + 1)]
+ORDER_BLOCKS.append(("ts_p2_cfl_local", 129))
+LANES = 256  # S2D_T of csrc/simplex2d.hip: a group of NU * G solution points takes ceil(NU G / 256) trips
+
+
+def second_trip_and_later_groups(name, n):
+    """per stage: (filtered elements with a point in the update kernel's second trip, filtered elements beyond group 0)"""
+    b, ref = TS.block(n, name)
+    nu, g, s0 = int(b["sizes"][1]), group_of(name), TS.scalar(b, "s0")
+    out = []
+    for s in ref["stage_sensors"]:
+        el = np.nonzero(s >= s0)[0]
+        out.append((int((((el % g) * nu + nu - 1) >= LANES).sum()), int((el >= g).sum())))
+    return out
+
+
+@pytest.mark.parametrize("name,n", ORDER_BLOCKS)
+def test_order_blocks_are_sound_inputs(name, n):
+    """conditions 3 and 4 and no NaN (inside TS.block).  Orders whose whole group takes two trips (P2 to P5): some stage filters an
+    element of the SECOND trip; every 2 G + 1 block has a stage that filters an element beyond group 0"""
+    b, ref = TS.block(n, name)
+    nu, g = int(b["sizes"][1]), group_of(name)
+    assert int(b["sizes"][0]) == n and ref["bad"] == -1 and all(np.isfinite(u).all() for u in ref["u"])
+    census = second_trip_and_later_groups(name, n)
+    print("%s, %d elements: s0 %.4e (nearest sensor %.1e away), filtered per stage %s, (second trip, beyond group 0) %s" %
+          (name, n, TS.scalar(b, "s0"), TS.closest(ref["stage_sensors"], TS.scalar(b, "s0")), TS.filtered_counts(ref["stage_sensors"], TS.scalar(b, "s0")), census))
+    trips = -(-nu * g // LANES)
+    assert trips == (1 if nu == 3 else 2)
+    if trips == 2:
+        assert any(second > 0 for second, _ in census), census
+    if n == 2 * g + 1:
+        assert any(later > 0 for _, later in census), census
+
+
+def test_local_time_steps_of_another_group_miss_under_the_filter():
+    """ts_p2_cfl_local at 129 elements: filter, local time step and second group together; dt_local rolled by G misses by > 1e-6"""
+    b, ref = TS.block(129, "ts_p2_cfl_local")
+    assert int(np.ravel(b["dt_type"])[0]) == 2
+    rolled = TS.lockstep(b, TS.N_STEPS, dt_map=lambda dtl: np.roll(dtl, 64))
+    miss = T.relerr(rolled["u"][-1], ref["u"][-1])
+    print("ts_p2_cfl_local, 129 elements: rolled dt_local %.1e" % miss)
+    assert miss > 1e-6

@@ -26,10 +26,11 @@ SHOCK_KEYS = ("shock_cap", "inv_vandermonde", "exp_filter", "norm_basis_persson"
 # results of the base fixture's run without a filter
 STALE = ("s0_", "u_step", "dt_step", "dt_local_step", "meta_json")
 CUT_FROM = "ts_p3_n4"
-G_P3 = 32
+G_P3 = T.GROUP[3]
 # the virtual parts of the GPU tests (test_tris_partition_oracle.grow_parts: weights, seed).  The cylinder's: 17 partition and 6
 # interior groups, and the stages that filter at all filter elements of both kinds (tests/test_tris_shock_oracle.py)
 PARTS = {"ts_p3_n4": ([3, 2, 1], 3), "ts_p3_cylinder": ([20, 1, 1], 1)}
+BY_ORDER = {1: "ts_p1_n4", 2: "ts_p2_n3", 3: "ts_p3_n4", 4: "ts_p4_n2", 5: "ts_p5_n2"}
 
 
 def names():
@@ -70,9 +71,10 @@ def choose_s0(sensors, skip=0):
     return float("%.4e" % (0.5 * (v[i] + v[i + 1])))
 
 
-def lockstep(d, n_steps, shock=True, s0=None):
+def lockstep(d, n_steps, shock=True, s0=None, dt_map=None):
     """the oracle on block d, the filter behind every stage (shock False: the sensor is computed and nothing is filtered)
-    -> dict of u (per step), sensor (per step: the last stage's), stage_sensors (n_steps * n_stages, n_eles), bad"""
+    -> dict of u (per step), sensor (per step: the last stage's), stage_sensors (n_steps * n_stages, n_eles), bad.
+    dt_map (dt_type 2): what a deliberately WRONG run does to the local time steps before it uses them"""
     import oracle_py as O
     o = O.load()
     d = dict(d)
@@ -94,6 +96,7 @@ def lockstep(d, n_steps, shock=True, s0=None):
             dtl = np.array([o.orc_calc_dt_local(C.byref(e), C.byref(c.params), i, h[i], CFL, order) for i in range(c.n_eles)])
             c.params.dt = dtl.min()
             if dt_type == 2:
+                dtl = dtl if dt_map is None else np.ascontiguousarray(dt_map(dtl))
                 c._dtl = dtl
                 e.dt_local = dtl.ctypes.data_as(O.dp)
         for rk in range(nstage):
@@ -142,19 +145,20 @@ def reference(name, shock=True):
     return _references[key]
 
 
-# ---- the blocks the GPU tests cut: tri_util.block(n) (the arrays of ts_p3_n4 are tri_p3_n4_deformed's) with ts_p3_n4's operators ---
+# ---- the blocks the GPU tests cut: tri_util.block(n, base) of the fixture a ts_* file is based on, with that file's operators ---------
 N_STEPS = 2
 
 
 @functools.lru_cache(maxsize=None)
-def block(n):
+def block(n, name=CUT_FROM):
     """-> (block with the shock keys, its lockstep over N_STEPS steps); s0: the middle of the widest upper-half gap of the first stage's
     oracle sensors (the next-widest where a later stage comes within MARGIN)"""
-    src = load(CUT_FROM)
-    base = T.load(bytes(src["based_on"]).decode())
-    for k in ("u_init", "opp_0", "opp_3", "detjac_upts", "int0_L"):
-        assert np.array_equal(src[k], base[k]), k  # (tri_util.block cuts tri_p3_n4_deformed: the same arrays)
-    b = dict(T.block(n))
+    src = load(name)
+    based_on = bytes(src["based_on"]).decode()
+    base = T.load(based_on)
+    for k in ("u_init", "opp_0", "opp_3", "detjac_upts", "int0_L", "sizes", "adv_type", "dt_type", "RK_a", "RK_b"):
+        assert np.array_equal(src[k], base[k]), k  # (tri_util.block cuts the fixture `name` is based on: the same arrays)
+    b = dict(T.block(n, based_on))
     for k in SHOCK_KEYS:
         b[k] = src[k]
     first = lockstep(b, 1, shock=False)["stage_sensors"][0]
@@ -164,7 +168,7 @@ def block(n):
         if closest(ref["stage_sensors"], s0) > MARGIN and (n == 1 or any(0 < c < n for c in filtered_counts(ref["stage_sensors"], s0))):
             break
     b["s0"] = np.array([s0])
-    check_conditions(ref["stage_sensors"], s0, "block of %d" % n)
+    check_conditions(ref["stage_sensors"], s0, "block of %d of %s" % (n, name))
     assert ref["bad"] == -1
     return b, ref
 

@@ -220,13 +220,32 @@ def failures(errs):
 # ---- the blocks the GPU tests run: any element count, cut faces become boundary faces ------------------------------------------
 CUT_FROM, BC_FROM = "tri_p3_n4_deformed", "tri_p3_bdy"
 N_STEPS = 2
+GROUP = {1: 64, 2: 64, 3: 32, 4: 32, 5: 16}  # elements per group by order: SIMPLEX2D_SIZES of csrc/simplex2d.hpp
+BY_ORDER = {1: "tri_p1_n4_deformed", 2: "tri_p2_n3_deformed", 3: "tri_p3_n4_deformed", 4: "tri_p4_n2_deformed", 5: "tri_p5_n2_deformed"}
+# the boundary records are scaled for the Taylor-Green state of their fixture; on the isentropic vortex of the inviscid fixture the
+# oracle itself returns NaN with the characteristic outflow (type 3) and the far field (type 10) among the cut faces, and the
+# library refuses the adiabatic wall (type 9) without viscous terms, as the reference does (src/input.cpp:427): its cut faces
+# are isothermal walls (type 8) alone, whose inviscid state is all an inviscid run uses (tests/test_tris_oracle.py runs the
+# oracle on every block)
+KINDS = {"tri_p2_inviscid": (8,)}
+
+
+def group_of(name):
+    """elements per group of the fused stage at the fixture's order"""
+    return GROUP[int(_load(name)["sizes"][5])]
+
+
+def edge_counts(name):
+    """G - 1, G, G + 1, 2 G + 1"""
+    g = group_of(name)
+    return [g - 1, g, g + 1, 2 * g + 1]
 
 
 @functools.lru_cache(maxsize=None)
-def block(n, name=CUT_FROM):
+def block(n, name=CUT_FROM, kinds=None):
     """n elements of the fixture (tiled first where it has fewer than 2 n), picked and ordered by a seeded permutation; the cut
     faces carry the boundary records of tri_p3_bdy without a pressure ramp (isothermal and adiabatic wall, far field, characteristic
-    outflow) in a seeded order"""
+    outflow) in a seeded order; kinds: only the records of these types (bc_flags row 0; None: KINDS of the fixture, or all)"""
     import general_util as G
     d = load(name)
     ne = int(d["sizes"][0])
@@ -236,11 +255,32 @@ def block(n, name=CUT_FROM):
     keep = rng.permutation(int(d["sizes"][0]))[:n]
     bc = load(BC_FROM)
     fl = np.asarray(bc["bc_flags"]).reshape(3, -1, order="F")
+    kinds = KINDS.get(name) if kinds is None else kinds
     # (not the ramping inlet: the step loops advance its counter after every step, general_util.oracle_steps does not)
-    return G.cut(d, keep, bc, rng.permutation([i for i in range(fl.shape[1]) if fl[1, i] == 0]))
+    ids = rng.permutation([i for i in range(fl.shape[1]) if fl[1, i] == 0])
+    return G.cut(d, keep, bc, [i for i in ids if kinds is None or fl[0, i] in kinds])
 
+
+def order_blocks():
+    """(fixture, n): blocks of G - 1, G, G + 1 and 2 G + 1 elements at every instantiated order"""
+    return [(BY_ORDER[p], n) for p in sorted(BY_ORDER) for n in edge_counts(BY_ORDER[p])]
+
+
+# the run-wide switches past group 0 (P2: G = 64); dt_type 2 also with a second group of ONE element
+SWITCH_BLOCKS = [("tri_p2_roem_sutherland", 129), ("tri_p2_rusanov_ldg", 129), ("tri_p2_inviscid", 129), ("tri_p2_cfl_local", 129),
+                 ("tri_p2_cfl_local", 65)]
 
 _references = {}
+
+
+def block_reference(n, name=CUT_FROM):
+    """the oracle's N_STEPS steps on block(n, name), computed once and shared (read-only)"""
+    return reference(("block", n) if name == CUT_FROM else ("block", n, name), block(n, name))
+
+
+def offset_differences(u, g):
+    """per element a < n - g: max |u[a] - u[a + g]| relative to max |u| (a state that takes element a + g for element a shows)"""
+    return np.abs(u[:, :-g] - u[:, g:]).max(axis=(0, 2)) / np.abs(u).max()
 
 
 def reference(key, d, n_steps=N_STEPS):
