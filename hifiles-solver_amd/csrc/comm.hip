@@ -399,6 +399,9 @@ static int simplex2d_partitioned_stage(hfx_eles *e, hfx_inters *const *all, int 
     if (start_exchange(comm, mpi_faces, n_mpi, 0, false)) return 1;
   }
   if (simplex2d_interior_ldg(e, all, n_all)) return 1;
+  // (over-integration folded into the element kernel: nothing here; option fold_over_int 0: the per-method launches on the whole
+  // block, on the compute stream beside the solution message -- they read the solution points alone)
+  if (simplex2d_over_int_unfolded(e)) return 1;
   if (simplex2d_element_kernel(e, rk, S2dList::interior)) return 1;
   if (wait_exchange(comm, 0, n_mpi)) return 1;
   if (visc && !pp.gather_remote && mpi_all(MpiKernel::ldg_delta, st)) return 1;
@@ -451,8 +454,8 @@ int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const 
   std::vector<hfx_inters *> all(int_faces, int_faces + n_int);
   all.insert(all.end(), mpi_faces, mpi_faces + n_mpi);
   if (general_prepare(eles, neb, all.data(), (int)all.size(), true)) return 1;
-  // one block of triangles: the 2-D simplex stage, interior groups first (nothing of it is refused past this point; LES,
-  // over-integration and shock capturing of another form than the triangle's own were refused by the tables)
+  // one block of triangles: the 2-D simplex stage, interior groups first (nothing of it is refused past this point; LES
+  // and shock capturing of another form than the triangle's own were refused by the tables)
   if (neb == 1 && is_simplex2d(eles[0]))
     return simplex2d_partitioned_stage(eles[0], all.data(), (int)all.size(), mpi_faces, n_mpi, comm, rk, start, shock);
   auto mpi_all = [&](MpiKernel k) -> int {

@@ -1151,7 +1151,8 @@ int GeneralStage::interior_ldg() const
 
 int GeneralStage::flux_kernels() const
 {
-  if (simplex2d) return simplex2d_element_kernel(eles[0], in_step);
+  // (a triangle block's over-integration: inside the element kernel, or -- option fold_over_int 0 -- per method in front of it)
+  if (simplex2d) return simplex2d_over_int_unfolded(eles[0]) || simplex2d_element_kernel(eles[0], in_step);
   for (int i = 0; i < neb; i++)
   {
     // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
@@ -1286,17 +1287,27 @@ int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *face
   // one set of events per repetition and ONE synchronisation at the end: a host synchronisation per stage let the queue
   // run dry, and the first kernel after it (the flux kernel) then measured 10 % slower than in the running pipeline
   std::vector<hipEvent_t> ev((size_t)reps * 5);
+  // a triangle block whose over-integration runs per method in front of the element kernel: its own slot (SLOT_OVER_INT)
+  const bool oi_slot = neb == 1 && is_simplex2d(eles[0]) && simplex2d_plan(eles[0]).over_int && !simplex2d_plan(eles[0]).fold_over_int;
+  std::vector<hipEvent_t> ev_oi(oi_slot ? (size_t)reps : 0);
+  for (auto &x : ev_oi) HFX_HIP(hipEventCreate(&x));
   for (auto &x : ev) HFX_HIP(hipEventCreate(&x));
   for (int i = 0; i < neb; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
-  double acc[4] = {0, 0, 0, 0};
+  double acc[4] = {0, 0, 0, 0}, acc_oi = 0.0;
   for (int r = 0; r < reps; r++)
   {
     const GeneralStage stage(eles, neb, faces, nfb, r % nst);
     HFX_HIP(hipEventRecord(ev[5 * r], st));
     if (stage.interior_ldg()) return 1;
     HFX_HIP(hipEventRecord(ev[5 * r + 1], st));
-    if (stage.flux_kernels()) return 1;
+    if (oi_slot)
+    {
+      if (simplex2d_over_int_unfolded(eles[0])) return 1;
+      HFX_HIP(hipEventRecord(ev_oi[r], st));
+      if (simplex2d_element_kernel(eles[0], r % nst)) return 1;
+    }
+    else if (stage.flux_kernels()) return 1;
     HFX_HIP(hipEventRecord(ev[5 * r + 2], st));
     if (stage.common_fluxes()) return 1;
     HFX_HIP(hipEventRecord(ev[5 * r + 3], st));
@@ -1311,8 +1322,17 @@ int general_time_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *face
       HFX_HIP(hipEventElapsedTime(&t, ev[5 * r + w], ev[5 * r + w + 1]));
       acc[w] += t;
     }
+  for (int r = 0; r < reps && oi_slot; r++)
+  {
+    float t = 0;
+    HFX_HIP(hipEventElapsedTime(&t, ev[5 * r + 1], ev_oi[r]));
+    acc_oi += t;
+    acc[1] -= t;
+  }
   for (auto &x : ev) (void)hipEventDestroy(x);
+  for (auto &x : ev_oi) (void)hipEventDestroy(x);
   for (int i = 0; i < 8; i++) ms[i] = (i < 4) ? acc[i] / reps : 0.0;
+  if (oi_slot) ms[SLOT_OVER_INT] = acc_oi / reps;
   for (int i = 0; i < neb; i++) note_gradients(eles[i], false);
   for (int i = 0; i < neb; i++)
   {

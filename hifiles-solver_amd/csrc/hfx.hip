@@ -493,6 +493,7 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value)
   else if (n == "flux_two_wave") o.flux_two_wave = value != 0;
   else if (n == "fold_faces") o.fold_faces = value != 0;
   else if (n == "fold_shock") o.fold_shock = value != 0;
+  else if (n == "fold_over_int") o.fold_over_int = value != 0;
   else if (n == "flux_two_wave_face") { HFX_CHECK(value >= -1 && value <= 5, "flux_two_wave_face must be -1 (the host's choice) or a local face 0-5"); o.flux_two_wave_face = value; }
   else if (n == "les_flux_kernel") o.les_flux_kernel = value != 0;
   else if (n == "bdy_beside") o.bdy_beside = value != 0;
@@ -1232,6 +1233,7 @@ int hfx_eles_set_over_int(hfx_eles *e, int n_cubpts, const double *opp_over_int_
   if (e->JGinv_over_int_cubpts.upload(JGinv_over_int_cubpts, pc * e->n_dims * e->n_dims)) return 1;
   if (e->u_cub.alloc(pc * e->n_fields) || e->t_cub.alloc(pc * e->n_fields * e->n_dims)) return 1;
   e->over_int_ready = true;
+  e->over_int_serial++;
   fused_invalidate(e);
   general_invalidate(e); // (the general stage takes the closure / the de-aliased flux from the registration too)
   // tensor-product elements: 1-D factors of the two matrices for the sum-factorised kernel (tensor_ops.hip)
@@ -1859,11 +1861,17 @@ int hfx_time_general_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *
   HFX_CHECK(eles && neb > 0 && ms && names && reps > 0, "hfx_time_general_kernels: bad argument");
   HFX_IMMEDIATE(eles[0]->ctx, 0);
   HFX_CHECK(eles[0]->ctx->have_params, "parameters not set");
+  if (general_time_kernels(eles, neb, faces, nfb, reps, ms)) return 1;
   if (neb == 1 && is_simplex2d(eles[0]))
-    snprintf(names, 256, "face_delta_kernel,simplex2d_element_kernel,face_flux2_kernel,simplex2d_update_kernel");
+  {
+    // (slot 4, SLOT_OVER_INT: a registered over-integration that the element kernel does not fold -- option fold_over_int 0)
+    const hfx::Simplex2dPlan pl = hfx::simplex2d_plan(eles[0]);
+    snprintf(names, 256, "face_delta_kernel,simplex2d_element_kernel,face_flux2_kernel,simplex2d_update_kernel%s",
+             pl.over_int && !pl.fold_over_int ? ",evaluate_invFlux_over_int" : "");
+  }
   else
     snprintf(names, 256, "face_delta_kernel,general_flux_kernel,gface_flux_multi_kernel,general_update_kernel");
-  return general_time_kernels(eles, neb, faces, nfb, reps, ms);
+  return 0;
 }
 
 int hfx_general_kernel_bytes(hfx_eles *const *eles, int neb, double bytes[8])

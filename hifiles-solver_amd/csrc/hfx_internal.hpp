@@ -241,6 +241,7 @@ struct hfx_ctx
     int fold_faces = 1;         // 1: with one-sided LDG (|ldg_beta| = 1/2; not with RoeM) the two-wave flux kernel forms the interior pairs' common flux itself and the stage launches no face_flux2_kernel on interior faces (0: the three-launch stage)
     int flux_two_wave_face = -1; // the local face that carries the two-wave flux kernel's left-over points: -1 the host's choice (two_wave_face), 0-5 forced (tests: reaches the left-over pass of phase B)
     int general_waves = 0;      // waves per workgroup of the general flux kernel: 0 by the LDS image (4 or 8), else 3, 4 or 8
+    int fold_over_int = 1;      // 1: the 2-D simplex stage's element kernel carries a triangle block's over-integration (its OVERINT instantiation); 0: hfx_eles_evaluate_invFlux_over_int in front of the element kernel, which reads tdisf_upts
     int fold_shock = 1;         // 1: the 2-D simplex stage's update kernel carries a triangle block's shock filter (sensor of eles_tris::shock_det_persson); 0: the per-method filter behind the stage, as on tetrahedra and prisms
   } opt;
   hfx::Deferred defer;
@@ -462,6 +463,7 @@ struct hfx_eles
   // over-integration (hfx_eles_set_over_int)
   bool over_int_ready = false;
   int n_cubpts = 0;
+  unsigned over_int_serial = 0; // counts hfx_eles_set_over_int calls (the 2-D simplex stage's tables are one registration's)
   hfx::Operator opp_over_int_cubpts, over_int_filter;
   hfx::DevBuf<double> JGinv_over_int_cubpts, u_cub, t_cub;
   // shock capturing (hfx_eles_set_shock_capture)

@@ -8,7 +8,8 @@
 //                              kernel does not gather the partner values itself)
 //   simplex2d_element_kernel   corrected gradient at the solution points (opp_4, opp_5), its extrapolation (opp_6), both point physics
 //                              blocks, the discontinuous divergence (opp_2) and normal flux (opp_1); leaves div_tdisf, norm_tdisf and
-//                              each side's viscous flux projected on its own normal (Fn, 4 doubles per flux point)
+//                              each side's viscous flux projected on its own normal (Fn, 4 doubles per flux point); where the block
+//                              registered over-integration, the de-aliased inviscid flux too (OVERINT, below)
 //   face_flux2_kernel<2>       thread per pair: Riemann + LDG common flux from u and Fn of both sides -> norm_tconf; the boundary kernels
 //   simplex2d_update_kernel    opp_3 (norm_tconf - norm_tdisf), RK update, opp_0 of the new state
 //
@@ -36,6 +37,12 @@ struct Simplex2dData
   DevBuf<double> update_shock_ops;
   bool shock = false;
   unsigned shock_serial = 0;
+  // over-integration (hfx_eles_set_over_int): opp_over_int_cubpts and over_int_filter one behind the other for the element kernel's
+  // OVERINT instantiation, and the registration (hfx_eles::over_int_serial) they were made from
+  DevBuf<double> overint_ops;
+  bool over_int = false;
+  unsigned over_int_serial = 0;
+  int n_cub = 0;
   DevBuf<unsigned char> meta;             // (n_fpts, n_eles): bit1 beta sign flipped (LEFT point of a pair), bit2 boundary point
   DevBuf<int> nbr;                        // (n_fpts, n_eles) partner word of every flux point (S2dArgs::nbr)
   DevBuf<double> disu_alt;                // second disu_fpts buffer (the update kernel writes the new state's flux-point solution)
@@ -90,7 +97,15 @@ struct S2dArgs
   int sens_field;
   double s0;
   double *sensor;
+  // element kernel with over-integration (S2dOverInt::folded): opp_over_int_cubpts (n_cub x NU) and over_int_filter (NU x n_cub) one
+  // behind the other, dense column-major; JGinv_over_int_cubpts (l, n, m, ele).  S2dOverInt::unfolded: tdisf_upts as
+  // hfx_eles_evaluate_invFlux_over_int left it (the transformed inviscid flux at the solution points)
+  const double *oi_ops, *JG_oi, *tdisf_in;
+  int n_cub;
 };
+
+// how the element kernel takes the inviscid flux at the solution points of a block that registered over-integration
+enum class S2dOverInt { none, folded, unfolded };
 
 constexpr int S2D_NF = 4, S2D_ND = 2, S2D_T = 64 * SIMPLEX2D_WAVES;
 
@@ -116,10 +131,24 @@ __device__ __forceinline__ void s2d_stage_ops(double *dst, const double *src, in
 // ---------------------------------------------------------------------------------------------------------------
 // element kernel
 // ---------------------------------------------------------------------------------------------------------------
-template <int NU, int NFP, int G>
+//
+// OVERINT folded: eles::evaluate_invFlux_over_int (src/eles.cpp:1480-1545) between the staging of U and of D, with D and Gr as
+// scratch.  The cubature points are walked in chunks of CH = NU:
+//   stage   the chunk's rows of opp_over_int_cubpts (A, [point][k], point fastest) and columns of over_int_filter (Fl, as in memory)
+//           -> the D region
+//   flux    lane (element, cubature point m): u_m = sum_k A(m, k) U[k], ascending k; calc_invf; the transform with the point's OWN
+//           four entries of JGinv_over_int_cubpts -> Gr[m - m0][element][field + NF * l]
+//   filter  lane (element, solution point j): its TRIPS points' 8 accumulators += sum_m Fl(j, m) Gr[m - m0], ascending m
+// The accumulators stay in registers until P3, which adds the transformed viscous flux to them and never calls calc_invf.
+// OVERINT unfolded: P3 reads the transformed inviscid flux from tdisf_upts instead (hfx_eles_evaluate_invFlux_over_int ran before
+// the launch).  OVERINT none is the code without any of it.
+template <int NU, int NFP, int G, S2dOverInt OVERINT>
 __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArgs a)
 {
   constexpr int NF = S2D_NF, ND = S2D_ND, T = S2D_T, GP = G + 1, NC = NF * ND;
+  constexpr int CH = NU;                      // cubature points per chunk
+  constexpr int TRIPS = (NU * G + T - 1) / T; // solution points of a group per lane
+  static_assert(2 * CH * NU <= NFP * GP * NF, "a chunk's operator slices fit the D region");
   extern __shared__ double lds[];
   // operators, dense column-major as registered
   double *o4 = lds;                     // [2][NU x NU]
@@ -154,6 +183,75 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
       for (int f = 0; f < NF; f++) r[f] = a.u0[e0 * NU + q + f * plane_u];
 #pragma unroll
       for (int f = 0; f < NF; f++) U[(k * GP + el) * NF + f] = r[f];
+    }
+    [[maybe_unused]] double oi[TRIPS][NC]; // (folded: the de-aliased transformed inviscid flux of the lane's solution points)
+    if constexpr (OVERINT == S2dOverInt::folded)
+    {
+      __syncthreads(); // (U is complete; every lane has left the P4 of the group before, which read Gr)
+      double *A = D, *Fl = D + CH * NU;
+      const int n_cub = a.n_cub;
+      const double *JGo = a.JG_oi + (size_t)4 * n_cub * e0;
+#pragma unroll
+      for (int t = 0; t < TRIPS; t++)
+#pragma unroll
+        for (int c = 0; c < NC; c++) oi[t][c] = 0.0;
+      for (int m0 = 0; m0 < n_cub; m0 += CH)
+      {
+        const int ch = min(CH, n_cub - m0);
+        for (int q = tid; q < CH * NU; q += T)
+        {
+          const int k = q / CH, mm = q - k * CH;
+          if (mm < ch) A[q] = a.oi_ops[m0 + mm + (size_t)n_cub * k];
+        }
+        for (int q = tid; q < NU * ch; q += T) Fl[q] = a.oi_ops[(size_t)n_cub * NU + (size_t)NU * m0 + q];
+        __syncthreads();
+        for (int q = tid; q < CH * nval; q += T)
+        {
+          const int el = q / CH, mm = q - el * CH;
+          if (mm >= ch) continue;
+          double JG[4];
+#pragma unroll
+          for (int c = 0; c < 4; c++) JG[c] = JGo[((size_t)el * n_cub + m0 + mm) * 4 + c];
+          double u[NF], F[NC];
+#pragma unroll
+          for (int f = 0; f < NF; f++) u[f] = 0.0;
+#pragma unroll 2
+          for (int k = 0; k < NU; k++)
+          {
+            const double m = A[mm + CH * k];
+#pragma unroll
+            for (int f = 0; f < NF; f++) u[f] += m * U[(k * GP + el) * NF + f];
+          }
+          calc_invf<ND, true>(a.P.gamma, u, F);
+#pragma unroll
+          for (int f = 0; f < NF; f++)
+#pragma unroll
+            for (int l = 0; l < ND; l++)
+            {
+              double t = 0.0;
+#pragma unroll
+              for (int n = 0; n < ND; n++) t += JG[l + ND * n] * F[f + NF * n];
+              Gr[(mm * GP + el) * NC + f + NF * l] = t;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < TRIPS; t++)
+        {
+          const int q = tid + t * T;
+          if (q < items_u)
+          {
+            const int el = q / NU, j = q - el * NU;
+            for (int mm = 0; mm < ch; mm++)
+            {
+              const double m = Fl[j + NU * mm];
+#pragma unroll
+              for (int c = 0; c < NC; c++) oi[t][c] += m * Gr[(mm * GP + el) * NC + c];
+            }
+          }
+        }
+        __syncthreads(); // (the next chunk's slices, or the corrections, overwrite D; the next chunk's fluxes Gr)
+      }
     }
     if (visc)
       for (int q = tid; q < items_f; q += T)
@@ -289,45 +387,98 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
 
     // ---- P3: point physics at the solution points (evaluate_invFlux, the transform of correct_gradient, evaluate_viscFlux;
     //          src/eles.cpp:1415,1973,2285): Gr(f,d) <- transformed total flux
-    for (int q = tid; q < items_u; q += T)
+    if constexpr (OVERINT == S2dOverInt::none)
     {
-      const int el = q / NU, i = q - el * NU;
-      const long o = e0 * NU + q;
-      double JG[4];
-#pragma unroll
-      for (int c = 0; c < 4; c++) JG[c] = a.JGinv_upts[o * 4 + c];
-      const double dj = visc ? a.detjac_upts[o] : 1.0;
-      double u[NF], F[NC];
-#pragma unroll
-      for (int f = 0; f < NF; f++) u[f] = U[(i * GP + el) * NF + f];
-      calc_invf<ND, true>(a.P.gamma, u, F);
-      if (visc)
+      for (int q = tid; q < items_u; q += T)
       {
-        const double idj = 1.0 / dj;
-        double g[NC], fv[NC];
+        const int el = q / NU, i = q - el * NU;
+        const long o = e0 * NU + q;
+        double JG[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) JG[c] = a.JGinv_upts[o * 4 + c];
+        const double dj = visc ? a.detjac_upts[o] : 1.0;
+        double u[NF], F[NC];
+#pragma unroll
+        for (int f = 0; f < NF; f++) u[f] = U[(i * GP + el) * NF + f];
+        calc_invf<ND, true>(a.P.gamma, u, F);
+        if (visc)
+        {
+          const double idj = 1.0 / dj;
+          double g[NC], fv[NC];
+#pragma unroll
+          for (int f = 0; f < NF; f++)
+          {
+            const double tg[ND] = {Gr[(i * GP + el) * NC + f], Gr[(i * GP + el) * NC + f + NF]};
+            double cg[ND];
+            s2d_to_physical(idj, JG, tg, cg);
+#pragma unroll
+            for (int d = 0; d < ND; d++) g[f + NF * d] = cg[d];
+          }
+          calc_visf<ND, true>(a.P, u, g, fv);
+#pragma unroll
+          for (int c = 0; c < NC; c++) F[c] += fv[c];
+        }
 #pragma unroll
         for (int f = 0; f < NF; f++)
-        {
-          const double tg[ND] = {Gr[(i * GP + el) * NC + f], Gr[(i * GP + el) * NC + f + NF]};
-          double cg[ND];
-          s2d_to_physical(idj, JG, tg, cg);
 #pragma unroll
-          for (int d = 0; d < ND; d++) g[f + NF * d] = cg[d];
-        }
-        calc_visf<ND, true>(a.P, u, g, fv);
+          for (int l = 0; l < ND; l++)
+          {
+            double t = 0.0;
 #pragma unroll
-        for (int c = 0; c < NC; c++) F[c] += fv[c];
+            for (int m = 0; m < ND; m++) t += JG[l + ND * m] * F[f + NF * m];
+            Gr[(i * GP + el) * NC + f + NF * l] = t;
+          }
       }
+    }
+    else
+    {
+      // (over-integration: the transformed inviscid flux is the de-aliased one -- the lane's accumulators, or tdisf_upts -- and the
+      // transformed viscous flux is added to it as eles::evaluate_viscFlux does; calc_invf is not called here)
 #pragma unroll
-      for (int f = 0; f < NF; f++)
-#pragma unroll
-        for (int l = 0; l < ND; l++)
+      for (int t = 0; t < TRIPS; t++)
+      {
+        const int q = tid + t * T;
+        if (q < items_u)
         {
-          double t = 0.0;
+          const int el = q / NU, i = q - el * NU;
+          const long o = e0 * NU + q;
+          double td[NC];
 #pragma unroll
-          for (int m = 0; m < ND; m++) t += JG[l + ND * m] * F[f + NF * m];
-          Gr[(i * GP + el) * NC + f + NF * l] = t;
+          for (int c = 0; c < NC; c++)
+          {
+            if constexpr (OVERINT == S2dOverInt::folded) td[c] = oi[t][c];
+            else td[c] = a.tdisf_in[o + c * plane_u];
+          }
+          if (visc)
+          {
+            double JG[4];
+#pragma unroll
+            for (int c = 0; c < 4; c++) JG[c] = a.JGinv_upts[o * 4 + c];
+            const double idj = 1.0 / a.detjac_upts[o];
+            double u[NF], g[NC], fv[NC];
+#pragma unroll
+            for (int f = 0; f < NF; f++) u[f] = U[(i * GP + el) * NF + f];
+#pragma unroll
+            for (int f = 0; f < NF; f++)
+            {
+              const double tg[ND] = {Gr[(i * GP + el) * NC + f], Gr[(i * GP + el) * NC + f + NF]};
+              double cg[ND];
+              s2d_to_physical(idj, JG, tg, cg);
+#pragma unroll
+              for (int d = 0; d < ND; d++) g[f + NF * d] = cg[d];
+            }
+            calc_visf<ND, true>(a.P, u, g, fv);
+#pragma unroll
+            for (int f = 0; f < NF; f++)
+#pragma unroll
+              for (int l = 0; l < ND; l++)
+#pragma unroll
+                for (int m = 0; m < ND; m++) td[f + NF * l] += JG[l + ND * m] * fv[f + NF * m];
+          }
+#pragma unroll
+          for (int c = 0; c < NC; c++) Gr[(i * GP + el) * NC + c] = td[c];
         }
+      }
     }
     __syncthreads();
 
@@ -621,7 +772,16 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
   HFX_CHECK(simplex2d_size_class(e) >= 0, "2-D simplex fused stage: built for triangles of orders 1..5 (%d solution, %d flux points); run per method (fused 0)",
             e->n_upts, e->n_fpts);
   HFX_CHECK(!e->les_ready, "2-D simplex fused stage: a registered LES closure runs per method (fused 0)");
-  HFX_CHECK(!e->over_int_ready, "2-D simplex fused stage: registered over-integration runs per method (fused 0)");
+  HFX_CHECK(!(e->les_ready && e->over_int_ready), "2-D simplex fused stage: an LES closure beside over-integration runs per method (fused 0)");
+  if (e->over_int_ready)
+  {
+    // (eles_tris::set_over_int, src/eles_tris.cpp:674-700: the cubature rule of over_int_order o = 0..7 has (o + 1)(o + 2) / 2 points)
+    HFX_CHECK(simplex2d_cubature_order(e->n_cubpts) >= 0, "2-D simplex fused stage: registered over-integration with %d cubature points, "
+              "which no triangle rule of over_int_order 0..7 has ((o + 1)(o + 2) / 2: 1..36), runs per method (fused 0)", e->n_cubpts);
+    HFX_CHECK(e->opp_over_int_cubpts.present() && e->over_int_filter.present(), "2-D simplex fused stage: over-integration without its operators");
+    HFX_CHECK(e->JGinv_over_int_cubpts.size() == (size_t)4 * e->n_cubpts * e->n_eles,
+              "2-D simplex fused stage: JGinv_over_int_cubpts holds %zu doubles where 4 x %d x %d are expected", e->JGinv_over_int_cubpts.size(), e->n_cubpts, e->n_eles);
+  }
   if (e->shock_ready)
   {
     const char *why = shock_form_refusal(e);
@@ -647,6 +807,13 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
     return 1;
   g->shock = e->shock_ready;
   g->shock_serial = e->shock_serial;
+  g->over_int = false;
+  g->overint_ops.reset();
+  if (e->over_int_ready && packed_operators(g->overint_ops, {&e->opp_over_int_cubpts, &e->over_int_filter}, {(size_t)e->n_cubpts * nu, nu * (size_t)e->n_cubpts}))
+    return 1;
+  g->over_int = e->over_int_ready;
+  g->over_int_serial = e->over_int_serial;
+  g->n_cub = e->over_int_ready ? e->n_cubpts : 0;
   // per flux point: the LDG switch of the pair it is the LEFT point of (exact tests on the left normal, decided once), whether a
   // boundary face owns it, and its partner word; every flux point must belong to exactly one registered face
   const long plane_f = (long)nfp * e->n_eles;
@@ -745,7 +912,9 @@ int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
   HFX_CHECK(!e->ctx->params.viscous || e->viscous_ops, "2-D simplex fused stage: viscous run but the block has no opp_4/5/6");
   const Simplex2dData *g = e->simplex2d.get();
   // (shock capturing: the tables are those of the registration they were made from; a later one, conforming or not, rebuilds them)
-  if (g && g->built && !e->les_ready && !e->over_int_ready && g->shock == e->shock_ready && g->shock_serial == e->shock_serial &&
+  // (over-integration likewise: over_int_serial)
+  if (g && g->built && !e->les_ready && g->shock == e->shock_ready && g->shock_serial == e->shock_serial &&
+      g->over_int == e->over_int_ready && g->over_int_serial == e->over_int_serial &&
       g->built_with.size() == (size_t)nfb &&
       std::equal(g->built_with.begin(), g->built_with.end(), faces))
     return 0;
@@ -765,6 +934,10 @@ Simplex2dPlan simplex2d_plan(const hfx_eles *e)
   pl.update_shock_lds = simplex2d_update_lds_bytes(s[0], s[1], s[2], true);
   const Simplex2dData *g = e->simplex2d.get();
   pl.fold_shock = e->ctx->opt.fold_shock && e->shock_ready && g && g->built && g->shock && g->shock_serial == e->shock_serial;
+  pl.over_int = e->over_int_ready && g && g->built && g->over_int && g->over_int_serial == e->over_int_serial;
+  pl.fold_over_int = pl.over_int && e->ctx->opt.fold_over_int;
+  pl.n_cubpts = pl.over_int ? g->n_cub : 0;
+  pl.over_int_chunk = s[0];
   return pl;
 }
 
@@ -821,6 +994,11 @@ static S2dArgs s2d_args(hfx_eles *e, const Simplex2dPlan &pl, int in_step, S2dLi
   a.sens_field = e->shock_det_field == 0 ? 0 : e->n_dims + 1;
   a.s0 = e->s0;
   a.sensor = e->arr[HFX_SENSOR];
+  if (pl.over_int)
+  {
+    a.oi_ops = g->overint_ops; a.JG_oi = e->JGinv_over_int_cubpts; a.n_cub = pl.n_cubpts;
+    a.tdisf_in = e->arr[HFX_TDISF_UPTS];
+  }
   return a;
 }
 
@@ -841,6 +1019,8 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
     HFX_CHECK(lds <= SIMPLEX2D_LDS_BUDGET, "2-D simplex fused stage: an LDS image of %zu bytes exceeds the budget of %zu", lds, SIMPLEX2D_LDS_BUDGET);
     a.ops = element ? e->simplex2d->element_ops : shock ? e->simplex2d->update_shock_ops : e->simplex2d->update_ops;
     HFX_CHECK(a.ops && (!shock || a.sensor), "2-D simplex fused stage: a table of the launch is missing");
+    const bool oi = element && pl.over_int;
+    HFX_CHECK(!oi || (pl.fold_over_int ? a.oi_ops && a.JG_oi && a.n_cub > 0 : a.tdisf_in != nullptr), "2-D simplex fused stage: a table of over-integration is missing");
     // as many workgroups as are resident (LDS; at most 8 of four waves), walking the groups grid-stride
     const long per_cu = std::max<long>(1, std::min<long>(8, (long)(160 * 1024 / lds)));
     const long work = a.groups ? a.n_list : a.n_groups; // the groups this launch walks
@@ -851,7 +1031,9 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
       HFX_HIP(hipGetLastError());
       return 0;
     };
-    return element ? launch(simplex2d_element_kernel_t<NU, NFP, G>)
+    return oi      ? (pl.fold_over_int ? launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::folded>)
+                                       : launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::unfolded>))
+           : element ? launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::none>)
            : shock ? launch(simplex2d_update_kernel_t<NU, NFP, G, true>)
                    : launch(simplex2d_update_kernel_t<NU, NFP, G, false>);
   }
@@ -894,6 +1076,13 @@ static bool s2d_list_empty(const hfx_eles *e, S2dList list)
 {
   const Simplex2dData *g = e->simplex2d.get();
   return (list == S2dList::partition && g->n_partition_groups == 0) || (list == S2dList::interior && g->n_interior_groups == 0);
+}
+
+int simplex2d_over_int_unfolded(hfx_eles *e)
+{
+  const Simplex2dPlan pl = simplex2d_plan(e);
+  if (!pl.over_int || pl.fold_over_int) return 0;
+  return hfx_eles_evaluate_invFlux_over_int(e);
 }
 
 int simplex2d_element_kernel(hfx_eles *e, int in_step, S2dList list)
@@ -951,6 +1140,15 @@ void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes)
   bytes[2] += ne * (8.0 * (nfp * nf + (visc ? nfp * nf : 0.0) + 0.5 * nfp * nd + nfp + nfp * nf) + 4.0 * nfp); // disu, Fn, normal(left), tdA r; tconf w
   bytes[3] += ne * 8.0 * (3 * nu * nf + nu + 2 * nfp * nf + 3 * nu * nf + nfp * nf);                          // u0,u1,div,detjac,tconf,ntd r; u0,u1,div,disu w
   if (pl.fold_shock) bytes[3] += ne * 8.0; // the folded shock filter: sensor w (the state it filters is the group's in LDS)
+  if (pl.fold_over_int) bytes[1] += ne * 8.0 * (nd * nd * pl.n_cubpts); // the folded over-integration: the cubature points' metrics r
+  else if (pl.over_int)
+  {
+    // unfolded: the per-method kernels (u r, u_cub w | u_cub, metrics r, t_cub w | t_cub r, tdisf_upts w) in their own slot, and
+    // the element kernel reads tdisf_upts
+    const double nc = pl.n_cubpts;
+    bytes[SLOT_OVER_INT] += ne * 8.0 * (nu * nf + nc * nf + nc * nf + nc * nd * nd + nc * nf * nd + nc * nf * nd + nu * nf * nd);
+    bytes[1] += ne * 8.0 * (nu * nf * nd);
+  }
 }
 
 } // namespace hfx
@@ -978,6 +1176,21 @@ extern "C" int hfx_simplex2d_shock_plan(hfx_eles *e, int out[4])
   // behind a stage that does not fold a registered filter (general_shock_capture): two dense contractions, the sensor and the
   // selection kernel, and the extrapolation of the filtered state
   out[3] = (e->shock_ready && !pl.fold_shock) ? 5 : 0;
+  return 0;
+}
+
+extern "C" int hfx_simplex2d_over_int_plan(hfx_eles *e, int out[8])
+{
+  HFX_CHECK(e && out, "hfx_simplex2d_over_int_plan: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  HFX_CHECK(e->simplex2d && e->simplex2d->built, "hfx_simplex2d_over_int_plan: no 2-D simplex fused stage has prepared this block (run fused 4 first)");
+  const hfx::Simplex2dPlan pl = hfx::simplex2d_plan(e);
+  const int chunks = pl.over_int ? (pl.n_cubpts + pl.over_int_chunk - 1) / pl.over_int_chunk : 0;
+  // in front of a stage that does not fold a registered over-integration (hfx_eles_evaluate_invFlux_over_int): the interpolation
+  // to the cubature points, the flux there and the projection back
+  const int v[8] = {pl.fold_over_int, pl.n_cubpts, pl.over_int ? pl.over_int_chunk : 0, chunks, (int)pl.element_lds,
+                    (pl.over_int && !pl.fold_over_int) ? 3 : 0, 0, 0};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
   return 0;
 }
 

@@ -30,6 +30,13 @@ constexpr int simplex2d_first_high_mode(int nu)
   while ((p + 1) * (p + 2) / 2 < nu) p++;
   return p * (p + 1) / 2;
 }
+// over_int_order of a triangle cubature rule with n points, (o + 1)(o + 2) / 2 for o = 0..7; -1: no such rule
+constexpr int simplex2d_cubature_order(int n)
+{
+  for (int o = 0; o <= 7; o++)
+    if ((o + 1) * (o + 2) / 2 == n) return o;
+  return -1;
+}
 constexpr bool simplex2d_sizes_fit()
 {
   bool ok = true;
@@ -51,6 +58,12 @@ struct Simplex2dPlan
   // eles::shock_capture follows runs the update kernel's SHOCK instantiation (LDS image update_shock_lds) and no filter behind it
   bool fold_shock = false;
   size_t update_shock_lds = 0;
+  // the block registered over-integration (hfx_eles_set_over_int): n_cubpts cubature points, walked by the element kernel's OVERINT
+  // instantiation in chunks of over_int_chunk (= the order's solution points) where fold_over_int -- option fold_over_int, every
+  // instantiated order -- and else formed by hfx_eles_evaluate_invFlux_over_int in front of the element kernel, which then reads
+  // tdisf_upts.  The element kernel's LDS image is element_lds in every form
+  bool over_int = false, fold_over_int = false;
+  int n_cubpts = 0, over_int_chunk = 0;
 };
 
 // The partitioned stage's side of the plan (general_partitioned_stage, comm.hip): the kernels walk GROUPS of `group` consecutive
@@ -74,6 +87,9 @@ Simplex2dPlan simplex2d_plan(const hfx_eles *e);
 Simplex2dPartitionPlan simplex2d_partition_plan(const hfx_eles *e);
 // the four steps of ONE stage on a prepared block whose disu_fpts belong to the current state (GeneralStage's, in its order)
 int simplex2d_interior_ldg(hfx_eles *e, hfx_inters *const *faces, int nfb);
+// the unfolded form of a registered over-integration (plan: over_int, not fold_over_int): hfx_eles_evaluate_invFlux_over_int on the
+// whole block, ONCE per stage in front of the element launches; nothing in every other form
+int simplex2d_over_int_unfolded(hfx_eles *e);
 int simplex2d_element_kernel(hfx_eles *e, int in_step, S2dList list = S2dList::all); // an empty list launches nothing
 int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb);
 // S2dList::all: then the disu_fpts buffers change places; a launch on a list leaves that to simplex2d_swap_disu_fpts, called once

@@ -666,6 +666,13 @@ class Eles:
         check(lib().hfx_simplex2d_shock_plan(self.h, out))
         return dict(zip(("folded", "update_lds", "first_high_mode", "launches_behind"), list(out)))
 
+    def simplex2d_over_int_plan(self):
+        """over-integration on this block of triangles in the 2-D simplex fused stage (hfx_simplex2d_over_int_plan), valid after a
+        fused-4 call: dict of folded, n_cubpts, chunk, chunks, element_lds, launches_in_front"""
+        out = (C.c_int * 8)()
+        check(lib().hfx_simplex2d_over_int_plan(self.h, out))
+        return dict(zip(("folded", "n_cubpts", "chunk", "chunks", "element_lds", "launches_in_front"), list(out)))
+
     def time_integral_quantities(self, reps=20):
         v = C.c_double(0)
         check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))

@@ -138,7 +138,8 @@ int hfx_ctx_set_CFL(hfx_ctx *ctx, double CFL);
  * those with, the other half -- so that both exchanges run beside element work), "split_update" (1: hfx_run_steps_partitioned updates the elements with partition-face points in a first launch, so that their exchange
  * runs beside the update of the others), "light_wave_short" (1: a flux-kernel wave without solution points runs the flux-point physics alone), "les_flux_kernel" (1: the LES
  * closure inside the flux kernel of variant 3), "over_int_fold" (1: the sum-factorised over-integration kernel hands the loader-wave flux kernel its
- * contribution to the divergence, n_fields values per solution point, instead of tdisf_upts), "bdy_beside" (0; 1: the fused stages' viscous boundary-face kernels on a side stream
+ * contribution to the divergence, n_fields values per solution point, instead of tdisf_upts), "fold_over_int" (1: the 2-D simplex
+ * stage's element kernel carries a triangle block's registered over-integration; 0: the per-method launches in front of it), "bdy_beside" (0; 1: the fused stages' viscous boundary-face kernels on a side stream
  * beside the interior-face kernel), "affine_metrics" (1: on a block whose elements are all parallelepipeds -- metrics constant inside an
  * element up to rounding, detected when the fused tables are made -- the split stage's flux and update kernels read one 34-double metric record per element in place of
  * the per-point metric arrays (all but JGinv at the solution points); results agree with 0 to rounding, hfx_time_fused_kernels then lists "affine_metrics" behind the kernels), "general_waves" (0 = by LDS image | 3 | 4 | 8), "general_update_waves" (0 = by the staging registers | 4 | 8), "dense_waves" (0 = by the operator's rows | 4 | 8) and "dense_split" (0 | 1 | 2 | 4:
@@ -827,8 +828,10 @@ int hfx_run_steps(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int 
  * calc_sgs_terms before the first stage of a step), over-integration forms tdisf_upts by the dense contractions and the flux kernel
  * takes it, shock capturing follows every stage (the filter, then disu_fpts of the filtered state); a closure TOGETHER with
  * over-integration is refused (run fused 0).
- * ONE block of triangles (orders 1-5; no LES or over-integration) runs the 2-D simplex fused stage (csrc/simplex2d.hip), at most
- * four launches per stage.  Shock capturing registered in the form of eles_tris::shock_det_persson (below) runs INSIDE its update
+ * ONE block of triangles (orders 1-5; no LES closure) runs the 2-D simplex fused stage (csrc/simplex2d.hip), at most
+ * four launches per stage.  Registered over-integration (a triangle rule of over_int_order 0..7: 1..36 cubature points) runs INSIDE
+ * its element kernel, which walks the cubature points in chunks and keeps the de-aliased flux in registers (option "fold_over_int"
+ * 0: hfx_eles_evaluate_invFlux_over_int in front of the element kernel, which then reads tdisf_upts; hfx_simplex2d_over_int_plan).  Shock capturing registered in the form of eles_tris::shock_det_persson (below) runs INSIDE its update
  * kernel: sensor, filter and the flux-point solution of the filtered state in the stage's last launch (option "fold_shock" 0: the
  * per-method filter behind the stage, as on tetrahedra); any other registration is refused before the first launch (run fused 0).
  * A block with one element class may of course be passed alone (hfx_run_steps(e, ..., 4) is the same call). */
@@ -919,7 +922,8 @@ int hfx_run_steps_partitioned(hfx_eles *e, hfx_inters *const *int_faces, int n_i
  * Three-dimensional blocks as hfx_run_steps_blocks(..., 4) takes them -- an LES closure is evaluated in the
  * flux kernel (its F_sgs . n travels inside Fn: no third message; the SVV closure is refused here), over-integration feeds it,
  * shock capturing follows the update before the next solution message is packed.
- * ONE block of triangles (orders 1-5; no LES or over-integration; shock capturing in the triangle's own form is folded into the
+ * ONE block of triangles (orders 1-5; no LES closure; over-integration inside the element kernel on either group list, or with
+ * "fold_over_int" 0 per method on the compute stream in front of the interior groups' element launch; shock capturing in the triangle's own form is folded into the
  * update kernel, so the partition groups' filtered flux-point solution is what is packed) runs the 2-D simplex fused stage, interior
  * groups first: the element and the update kernel walk the groups without a partition flux point beside the solution message, the
  * groups with one behind it (hfx_simplex2d_partition_plan); with one partition-face block the element kernel reads the partners
@@ -1003,6 +1007,16 @@ int hfx_simplex2d_partition_plan(hfx_eles *e, int out[4]);
  * sensor's numerator sums, p (p + 1) / 2, out[3] per-method launches behind every stage for the filter (0 when folded or nothing is
  * registered; else the two dense contractions, the sensor and the selection kernel and extrapolate_solution). */
 int hfx_simplex2d_shock_plan(hfx_eles *e, int out[4]);
+/* Over-integration (hfx_eles_set_over_int) on a block of triangles inside / in front of the 2-D simplex fused stage (read-only; valid
+ * once a fused-4 call or a deferred stage has prepared the block, refused before): out[0] 1: the element kernel carries it (something
+ * is registered and option "fold_over_int" is 1; every instantiated order P1..P5 folds), out[1] cubature points of the registration (0:
+ * none), out[2] cubature points per chunk the element kernel walks (the order's solution points), out[3] chunks, out[4] bytes of the
+ * element kernel's LDS image (the same in every form: a chunk lives in the regions of the LDG corrections and the gradient), out[5]
+ * per-method launches in front of every stage (0 when folded or nothing is registered; else the three of
+ * hfx_eles_evaluate_invFlux_over_int, after which the element kernel reads tdisf_upts), out[6..7] 0.  In the unfolded form
+ * hfx_time_general_kernels reports those launches in slot 4 (name evaluate_invFlux_over_int) and hfx_general_kernel_bytes their bytes
+ * there; folded, slot 4 stays 0 and the element kernel's bytes grow by the cubature points' metrics. */
+int hfx_simplex2d_over_int_plan(hfx_eles *e, int out[8]);
 
 #ifdef __cplusplus
 }
