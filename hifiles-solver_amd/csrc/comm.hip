@@ -444,6 +444,8 @@ static int simplex2d_partitioned_stage(hfx_eles *e, hfx_inters *const *all, int 
 //   pack each side's projected viscous flux Fn, exchange       interior common fluxes, boundary viscous fluxes
 //   wait; common fluxes at the partition faces                 update kernels (new flux-point solution)
 //   pack the new flux-point solution, exchange (for the next stage)
+// (the prepare below is what a deferred stage relies on; hfx_run_steps_partitioned_blocks has prepared the same tables before its loop
+// -- for EVERY element class, so that whatever they refuse is refused before the state is touched -- and finds it a no-op here)
 int general_partitioned_stage(hfx_eles *const *eles, int neb, hfx_inters *const *int_faces, int n_int, hfx_inters *const *mpi_faces,
                               int n_mpi, hfx_comm *comm, int rk, bool start, bool shock)
 {
@@ -757,6 +759,15 @@ int hfx_run_steps_partitioned_blocks(hfx_eles *const *eles, int n_ele_blocks, hf
   if (step_loop_check(eles, n_ele_blocks, int_faces, n_int, n_steps)) return 1;
   if (const char *refusal = monitor_gradient_on_chip(eles, n_ele_blocks)) // (the general stage keeps the gradient on chip)
     HFX_CHECK(false, "%s", refusal);
+  // (what the blocks' tables refuse is refused HERE, before the state is touched: the closure filter of a step's first stage -- SVV
+  // replaces the state -- runs in front of the stage that would prepare them)
+  if (n_steps > 0)
+  {
+    if (check_partition_blocks(eles, n_ele_blocks, mpi_faces, n_mpi, comm)) return 1;
+    std::vector<hfx_inters *> all(int_faces, int_faces + n_int);
+    all.insert(all.end(), mpi_faces, mpi_faces + n_mpi);
+    if (general_prepare(eles, n_ele_blocks, all.data(), (int)all.size(), true)) return 1;
+  }
   for (int i = 0; i < n_ele_blocks; i++)
     if (hfx_eles_extrapolate_solution(eles[i])) return 1;
   // (as hfx_run_steps_partitioned: the solution a partitioned fused stage has posted for this state is not posted again)

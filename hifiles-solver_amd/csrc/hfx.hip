@@ -974,6 +974,7 @@ int hfx_eles_set_les(hfx_eles *e, const hfx_les *les, const double *wall_distanc
   for (int id : {HFX_SGSF_UPTS, HFX_SGSF_FPTS})
     if (e->arr[id].ensure_zeroed(e->arr_len[id])) return 1;
   e->les_ready = true;
+  e->les_serial++;
   fused_invalidate(e);
   general_invalidate(e); // (the general stage takes the closure / the de-aliased flux from the registration too)
   return 0;
@@ -990,6 +991,7 @@ int hfx_eles_set_les_filter(hfx_eles *e, const double *filter_upts)
   if (e->sgs_uu.ensure(e->arr_len[HFX_LU]) || e->sgs_ue.ensure(e->arr_len[HFX_LE])) return 1;
   e->les.Lu = e->arr[HFX_LU];
   e->les.Le = e->arr[HFX_LE];
+  e->les_serial++;
   return 0;
 }
 

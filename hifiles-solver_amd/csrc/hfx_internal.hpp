@@ -426,6 +426,7 @@ struct hfx_eles
   hfx::DevBuf<double> h_ref; // (n_eles) eles::h_ref for calc_dt_local
   // LES closure (hfx_eles_set_les)
   bool les_ready = false;
+  unsigned les_serial = 0; // counts hfx_eles_set_les / hfx_eles_set_les_filter calls (the 2-D simplex stage's tables are one registration's)
   hfx::LesParams les{};
   hfx::DevBuf<double> wall_distance, Jacobian_fpts;
   // similarity-type closures (sgs_model 2, 3, 4): the filter matrix and the work arrays of calc_sgs_terms

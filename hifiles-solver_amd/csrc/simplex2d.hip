@@ -9,7 +9,8 @@
 //   simplex2d_element_kernel   corrected gradient at the solution points (opp_4, opp_5), its extrapolation (opp_6), both point physics
 //                              blocks, the discontinuous divergence (opp_2) and normal flux (opp_1); leaves div_tdisf, norm_tdisf and
 //                              each side's viscous flux projected on its own normal (Fn, 4 doubles per flux point); where the block
-//                              registered over-integration, the de-aliased inviscid flux too (OVERINT, below)
+//                              registered over-integration, the de-aliased inviscid flux too (OVERINT, below); where it registered
+//                              an LES closure, the SGS flux too, and Fn carries F_sgs . n (LES, below)
 //   face_flux2_kernel<2>       thread per pair: Riemann + LDG common flux from u and Fn of both sides -> norm_tconf; the boundary kernels
 //   simplex2d_update_kernel    opp_3 (norm_tconf - norm_tdisf), RK update, opp_0 of the new state
 //
@@ -21,6 +22,7 @@
 // block registered (consecutive rows in consecutive lanes: conflict free).  A workgroup stages the operators once and walks groups
 // grid-stride.  Ordinary stores, no atomics but the NaN flag's: bit-reproducible from run to run.
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 
 #include "simplex2d.hpp"
@@ -43,6 +45,11 @@ struct Simplex2dData
   bool over_int = false;
   unsigned over_int_serial = 0;
   int n_cub = 0;
+  // an LES closure with an SGS flux (sgs_model 0, 1, 2, 4; les_jacobian_residual): its squared length scale (n_upts, n_eles;
+  // les_len2_upload) for the element kernel's LES instantiation, and the registration (hfx_eles::les_serial) it was made from
+  DevBuf<double> les_len2;
+  bool les = false;
+  unsigned les_serial = 0;
   DevBuf<unsigned char> meta;             // (n_fpts, n_eles): bit1 beta sign flipped (LEFT point of a pair), bit2 boundary point
   DevBuf<int> nbr;                        // (n_fpts, n_eles) partner word of every flux point (S2dArgs::nbr)
   DevBuf<double> disu_alt;                // second disu_fpts buffer (the update kernel writes the new state's flux-point solution)
@@ -102,6 +109,10 @@ struct S2dArgs
   // hfx_eles_evaluate_invFlux_over_int left it (the transformed inviscid flux at the solution points)
   const double *oi_ops, *JG_oi, *tdisf_in;
   int n_cub;
+  // element kernel with an LES closure (LES): the closure (Lu / Le of the step's calc_sgs_terms are read through it), its squared
+  // length scale les_len2 (n_upts, n_eles) and tdA_fpts, which takes the projected transformed SGS flux back to physical space
+  LesParams les;
+  const double *les_len2, *tdA_fpts;
 };
 
 // how the element kernel takes the inviscid flux at the solution points of a block that registered over-integration
@@ -142,12 +153,28 @@ __device__ __forceinline__ void s2d_stage_ops(double *dst, const double *src, in
 // The accumulators stay in registers until P3, which adds the transformed viscous flux to them and never calls calc_invf.
 // OVERINT unfolded: P3 reads the transformed inviscid flux from tdisf_upts instead (hfx_eles_evaluate_invFlux_over_int ran before
 // the launch).  OVERINT none is the code without any of it.
-template <int NU, int NFP, int G, S2dOverInt OVERINT>
+//
+// LES: the eddy-viscosity / similarity closure of an LES run (eles::calc_sgsf_upts, src/eles.cpp:2395-2650; sgs_model 0, 1, 2, 4 on
+// a viscous run, OVERINT none).  The reference adds F_sgs to the total flux at the solution points (src/eles.cpp:2360-2392) and, at
+// the flux points, extrapolates the TRANSFORMED SGS flux (opp_0), takes it back to physical space with Jacobian_fpts and adds it to
+// each side's viscous flux in the common-flux sweep (src/eles.cpp:2817-2893, src/int_inters.cpp:299-313).  What the face kernels
+// need of that is F_sgs . n = (F~_sgs . n~) / tdA = (sum_d opp_1[d] F~_sgs,d) / tdA (the identity of general.hip's LESG form, which
+// holds where Jacobian_fpts belongs to the block's own metrics: les_jacobian_residual), so Fn carries it and no sgsf array exists:
+//   P2   forms Fn as ever but KEEPS a lane's flux points (TRIPS_F x 4 doubles) in registers instead of storing them
+//   P3   calc_sgsf_fast on the physical gradient the point physics holds; the transformed inviscid + viscous flux stays in
+//        registers (TRIPS x 8 doubles), the transformed SGS flux ALONE goes to the lane's Gr point
+//   P3b  lane (element, flux point j) -- the q -> (element, flux point) map of P2, so the lane holds Fn of the point --:
+//        s = sum_k opp_1[0](j, k) Gr[k](f) + opp_1[1](j, k) Gr[k](f + NF), ascending k; Fn += s / tdA_fpts: the ONE store of Fn
+//   then every lane adds its register flux to its Gr point, and P4 runs on the total flux as ever.
+// With LES false the kernel is the code without any of it.
+template <int NU, int NFP, int G, S2dOverInt OVERINT, bool LES = false>
 __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArgs a)
 {
+  static_assert(!LES || OVERINT == S2dOverInt::none, "the LES form is not built beside over-integration");
   constexpr int NF = S2D_NF, ND = S2D_ND, T = S2D_T, GP = G + 1, NC = NF * ND;
   constexpr int CH = NU;                      // cubature points per chunk
   constexpr int TRIPS = (NU * G + T - 1) / T; // solution points of a group per lane
+  constexpr int TRIPS_F = (NFP * G + T - 1) / T; // flux points of a group per lane
   static_assert(2 * CH * NU <= NFP * GP * NF, "a chunk's operator slices fit the D region");
   extern __shared__ double lds[];
   // operators, dense column-major as registered
@@ -292,6 +319,7 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
       }
     __syncthreads();
 
+    [[maybe_unused]] double fnr[LES ? TRIPS_F : 1][NF]; // (LES: the projected viscous flux of the lane's flux points, P2 to P3b)
     if (visc)
     {
       // ---- P1: reference-space corrected gradient at the solution points (calculate_gradient + first half of correct_gradient,
@@ -333,7 +361,11 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
 
       // ---- P2: gradient at the flux points (second half of correct_gradient: opp_6, then the transform with the flux points' own
       //          metrics, src/eles.cpp:1930,1998) and the viscous flux there, projected on the point's normal
-      for (int q = tid; q < items_f; q += T)
+      // (LES: trip t takes the lane's ONE point tid + t T -- the inner loop runs at most once -- so that its Fn stays in fnr[t])
+      constexpr int P2_TRIPS = LES ? TRIPS_F : 1, P2_STEP = LES ? T * TRIPS_F : T;
+#pragma unroll
+      for (int t = 0; t < P2_TRIPS; t++)
+      for (int q = tid + t * T; q < items_f; q += P2_STEP)
       {
         const int el = q / NFP, j = q - el * NFP;
         const long o = e0 * NFP + q;
@@ -379,7 +411,8 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
           double s = 0.0;
 #pragma unroll
           for (int m = 0; m < ND; m++) s += fv[f + NF * m] * n[m];
-          a.fn[o + f * plane_f] = s;
+          if constexpr (LES) fnr[t][f] = s; // (stored once, by P3b)
+          else a.fn[o + f * plane_f] = s;
         }
       }
       __syncthreads();
@@ -387,7 +420,92 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
 
     // ---- P3: point physics at the solution points (evaluate_invFlux, the transform of correct_gradient, evaluate_viscFlux;
     //          src/eles.cpp:1415,1973,2285): Gr(f,d) <- transformed total flux
-    if constexpr (OVERINT == S2dOverInt::none)
+    if constexpr (LES)
+    {
+      double tiv[TRIPS][NC]; // transformed inviscid + viscous flux of the lane's solution points
+#pragma unroll
+      for (int t = 0; t < TRIPS; t++)
+      {
+        const int q = tid + t * T;
+        if (q < items_u)
+        {
+          const int el = q / NU, i = q - el * NU;
+          const long o = e0 * NU + q;
+          double JG[4];
+#pragma unroll
+          for (int c = 0; c < 4; c++) JG[c] = a.JGinv_upts[o * 4 + c];
+          const double idj = 1.0 / a.detjac_upts[o], len2 = a.les_len2[o];
+          double u[NF], F[NC], g[NC], fv[NC], sg[NC];
+#pragma unroll
+          for (int f = 0; f < NF; f++) u[f] = U[(i * GP + el) * NF + f];
+          calc_invf<ND, true>(a.P.gamma, u, F);
+#pragma unroll
+          for (int f = 0; f < NF; f++)
+          {
+            const double tg[ND] = {Gr[(i * GP + el) * NC + f], Gr[(i * GP + el) * NC + f + NF]};
+            double cg[ND];
+            s2d_to_physical(idj, JG, tg, cg);
+#pragma unroll
+            for (int d = 0; d < ND; d++) g[f + NF * d] = cg[d];
+          }
+          calc_visf<ND, true>(a.P, u, g, fv);
+          calc_sgsf_fast<ND>(a.P, a.les, u, g, len2, o, plane_u, sg);
+#pragma unroll
+          for (int f = 0; f < NF; f++)
+#pragma unroll
+            for (int l = 0; l < ND; l++)
+            {
+              double tt = 0.0, ts = 0.0;
+#pragma unroll
+              for (int m = 0; m < ND; m++)
+              {
+                tt += JG[l + ND * m] * (F[f + NF * m] + fv[f + NF * m]);
+                ts += JG[l + ND * m] * sg[f + NF * m];
+              }
+              tiv[t][f + NF * l] = tt;
+              Gr[(i * GP + el) * NC + f + NF * l] = ts;
+            }
+        }
+      }
+      __syncthreads();
+      // ---- P3b: F~_sgs . n~ at the flux points (opp_1) joins the Fn of P2, which is stored here
+#pragma unroll
+      for (int t = 0; t < TRIPS_F; t++)
+      {
+        const int q = tid + t * T;
+        if (q < items_f)
+        {
+          const int el = q / NFP, j = q - el * NFP;
+          const long o = e0 * NFP + q;
+          const double tdA = a.tdA_fpts[o];
+          double acc[NF];
+#pragma unroll
+          for (int f = 0; f < NF; f++) acc[f] = 0.0;
+#pragma unroll 2
+          for (int k = 0; k < NU; k++)
+          {
+            const double m0 = o1[j + NFP * k], m1 = o1[NFP * NU + j + NFP * k];
+#pragma unroll
+            for (int f = 0; f < NF; f++) acc[f] += m0 * Gr[(k * GP + el) * NC + f] + m1 * Gr[(k * GP + el) * NC + f + NF];
+          }
+#pragma unroll
+          for (int f = 0; f < NF; f++) a.fn[o + f * plane_f] = fnr[t][f] + acc[f] / tdA;
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int t = 0; t < TRIPS; t++)
+      {
+        const int q = tid + t * T;
+        if (q < items_u)
+        {
+          const int el = q / NU, i = q - el * NU;
+#pragma unroll
+          for (int c = 0; c < NC; c++) Gr[(i * GP + el) * NC + c] += tiv[t][c];
+        }
+      }
+    }
+    else if constexpr (OVERINT == S2dOverInt::none)
     {
       for (int q = tid; q < items_u; q += T)
       {
@@ -766,13 +884,66 @@ static const char *shock_form_refusal(const hfx_eles *e)
   return nullptr;
 }
 
+// The element kernel's LES form projects the SGS flux with the block's OWN metrics (opp_1, tdA_fpts) and never reads the registered
+// Jacobian_fpts, with which hfx_eles_extrapolate_sgsFlux takes the extrapolated flux back to physical space: the two agree where
+// sum_k Jacobian_fpts(i, k) JGinv_fpts(k, j) = detjac_fpts delta_ij at every flux point.  -> the largest miss, relative to
+// max |detjac_fpts| (checked once per registration, on the host, a chunk of flux points at a time)
+static int les_jacobian_residual(const hfx_eles *e, double *residual)
+{
+  const size_t plane_f = (size_t)e->n_fpts * e->n_eles, CHUNK = (size_t)1 << 18; // (flux points copied at a time: 18 MiB of host vectors)
+  HFX_CHECK(e->Jacobian_fpts && e->JGinv_fpts && e->detjac_fpts, "2-D simplex fused stage: an LES closure without the flux points' metrics");
+  std::vector<double> J(4 * std::min(plane_f, CHUNK)), JG(J.size()), dj(J.size() / 4);
+  double miss = 0.0, scale = 0.0;
+  for (size_t p0 = 0; p0 < plane_f; p0 += CHUNK)
+  {
+    const size_t n = std::min(CHUNK, plane_f - p0);
+    HFX_HIP(hipMemcpy(J.data(), e->Jacobian_fpts.get() + 4 * p0, sizeof(double) * 4 * n, hipMemcpyDeviceToHost));
+    HFX_HIP(hipMemcpy(JG.data(), e->JGinv_fpts.get() + 4 * p0, sizeof(double) * 4 * n, hipMemcpyDeviceToHost));
+    HFX_HIP(hipMemcpy(dj.data(), e->detjac_fpts.get() + p0, sizeof(double) * n, hipMemcpyDeviceToHost));
+    for (size_t p = 0; p < n; p++)
+    {
+      scale = std::max(scale, std::fabs(dj[p]));
+      for (int i = 0; i < 2; i++)
+        for (int j = 0; j < 2; j++)
+        {
+          double s = (i == j) ? -dj[p] : 0.0;
+          for (int k = 0; k < 2; k++) s += J[4 * p + i + 2 * k] * JG[4 * p + k + 2 * j];
+          miss = std::max(miss, std::fabs(s));
+          if (s != s) miss = HUGE_VAL; // (a NaN in the registration conforms to nothing)
+        }
+    }
+  }
+  *residual = scale > 0.0 ? miss / scale : HUGE_VAL;
+  return 0;
+}
+
 static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
 {
   HFX_CHECK(e->n_fields == 4, "2-D simplex fused stage: Navier-Stokes / Euler blocks only; run per method (fused 0)");
   HFX_CHECK(simplex2d_size_class(e) >= 0, "2-D simplex fused stage: built for triangles of orders 1..5 (%d solution, %d flux points); run per method (fused 0)",
             e->n_upts, e->n_fpts);
-  HFX_CHECK(!e->les_ready, "2-D simplex fused stage: a registered LES closure runs per method (fused 0)");
   HFX_CHECK(!(e->les_ready && e->over_int_ready), "2-D simplex fused stage: an LES closure beside over-integration runs per method (fused 0)");
+  // (a conforming closure beside a conforming shock registration: the LES element kernel and the SHOCK update kernel -- or, with
+  // option fold_shock 0, the filter behind the stage -- each as it runs alone)
+  if (e->les_ready)
+  {
+    const int model = e->les.sgs_model;
+    HFX_CHECK(e->ctx->params.viscous, "2-D simplex fused stage: an LES closure on an inviscid context runs per method (fused 0)");
+    HFX_CHECK(model != 0 || e->wall_distance, "2-D simplex fused stage: an LES closure of the Smagorinsky model without wall_distance runs per method (fused 0)");
+    HFX_CHECK(model < 2 || (e->filter_upts.present() && e->les.Lu && e->les.Le),
+              "2-D simplex fused stage: an LES closure of model %d without filter_upts (hfx_eles_set_les_filter) runs per method (fused 0)", model);
+    // (SVV filters the state after its flux-point values have left for the neighbours, as on the general stage)
+    for (int b = 0; b < nfb; b++)
+      HFX_CHECK(!faces[b]->is_mpi || model != 3, "2-D simplex fused stage: the SVV LES closure on partitioned blocks runs per method (fused 0)");
+    if (model != 3)
+    {
+      double residual = 0.0;
+      if (les_jacobian_residual(e, &residual)) return 1;
+      HFX_CHECK(residual <= 1e-9, "2-D simplex fused stage: a registered LES closure whose Jacobian_fpts is not the block's own (Jacobian_fpts . JGinv_fpts "
+                                  "misses detjac_fpts by %.3g of its largest value; the stage projects the SGS flux with tdA_fpts and opp_1) runs per method (fused 0)",
+                residual);
+    }
+  }
   if (e->over_int_ready)
   {
     // (eles_tris::set_over_int, src/eles_tris.cpp:674-700: the cubature rule of over_int_order o = 0..7 has (o + 1)(o + 2) / 2 points)
@@ -814,6 +985,12 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
   g->over_int = e->over_int_ready;
   g->over_int_serial = e->over_int_serial;
   g->n_cub = e->over_int_ready ? e->n_cubpts : 0;
+  g->les = false;
+  g->les_len2.reset();
+  const bool les = e->les_ready && e->les.sgs_model != 3; // (SVV has no SGS flux: the plain kernels behind the step loop's filter)
+  if (les && les_len2_upload(e, g->les_len2)) return 1;
+  g->les = les;
+  g->les_serial = e->les_serial;
   // per flux point: the LDG switch of the pair it is the LEFT point of (exact tests on the left normal, decided once), whether a
   // boundary face owns it, and its partner word; every flux point must belong to exactly one registered face
   const long plane_f = (long)nfp * e->n_eles;
@@ -912,8 +1089,11 @@ int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
   HFX_CHECK(!e->ctx->params.viscous || e->viscous_ops, "2-D simplex fused stage: viscous run but the block has no opp_4/5/6");
   const Simplex2dData *g = e->simplex2d.get();
   // (shock capturing: the tables are those of the registration they were made from; a later one, conforming or not, rebuilds them)
-  // (over-integration likewise: over_int_serial)
-  if (g && g->built && !e->les_ready && g->shock == e->shock_ready && g->shock_serial == e->shock_serial &&
+  // (over-integration likewise: over_int_serial; an LES closure: les_serial -- and what refuses a closure depends on the context and
+  // on the face blocks, so a block with a closure is rebuilt unless it is the one the tables took, on a viscous context)
+  const bool les_same = g && (e->les_ready ? g->les_serial == e->les_serial && g->les == (e->les.sgs_model != 3) && e->ctx->params.viscous != 0 && !e->over_int_ready
+                                           : !g->les);
+  if (g && g->built && les_same && g->shock == e->shock_ready && g->shock_serial == e->shock_serial &&
       g->over_int == e->over_int_ready && g->over_int_serial == e->over_int_serial &&
       g->built_with.size() == (size_t)nfb &&
       std::equal(g->built_with.begin(), g->built_with.end(), faces))
@@ -938,6 +1118,9 @@ Simplex2dPlan simplex2d_plan(const hfx_eles *e)
   pl.fold_over_int = pl.over_int && e->ctx->opt.fold_over_int;
   pl.n_cubpts = pl.over_int ? g->n_cub : 0;
   pl.over_int_chunk = s[0];
+  pl.sgs_model = e->les_ready ? e->les.sgs_model : -1;
+  pl.les = e->les_ready && e->les.sgs_model != 3 && e->ctx->params.viscous && g && g->built && g->les && g->les_serial == e->les_serial;
+  pl.les_terms = pl.les && (e->les.sgs_model == 2 || e->les.sgs_model == 4);
   return pl;
 }
 
@@ -999,6 +1182,10 @@ static S2dArgs s2d_args(hfx_eles *e, const Simplex2dPlan &pl, int in_step, S2dLi
     a.oi_ops = g->overint_ops; a.JG_oi = e->JGinv_over_int_cubpts; a.n_cub = pl.n_cubpts;
     a.tdisf_in = e->arr[HFX_TDISF_UPTS];
   }
+  if (pl.les)
+  {
+    a.les = e->les; a.les_len2 = g->les_len2; a.tdA_fpts = e->tdA_fpts;
+  }
   return a;
 }
 
@@ -1021,6 +1208,8 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
     HFX_CHECK(a.ops && (!shock || a.sensor), "2-D simplex fused stage: a table of the launch is missing");
     const bool oi = element && pl.over_int;
     HFX_CHECK(!oi || (pl.fold_over_int ? a.oi_ops && a.JG_oi && a.n_cub > 0 : a.tdisf_in != nullptr), "2-D simplex fused stage: a table of over-integration is missing");
+    const bool les = element && pl.les;
+    HFX_CHECK(!les || (!oi && a.les_len2 && a.tdA_fpts && (!pl.les_terms || (a.les.Lu && a.les.Le))), "2-D simplex fused stage: a table of the LES closure is missing");
     // as many workgroups as are resident (LDS; at most 8 of four waves), walking the groups grid-stride
     const long per_cu = std::max<long>(1, std::min<long>(8, (long)(160 * 1024 / lds)));
     const long work = a.groups ? a.n_list : a.n_groups; // the groups this launch walks
@@ -1033,6 +1222,7 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
     };
     return oi      ? (pl.fold_over_int ? launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::folded>)
                                        : launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::unfolded>))
+           : les     ? launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::none, true>)
            : element ? launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::none>)
            : shock ? launch(simplex2d_update_kernel_t<NU, NFP, G, true>)
                    : launch(simplex2d_update_kernel_t<NU, NFP, G, false>);
@@ -1140,6 +1330,8 @@ void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes)
   bytes[2] += ne * (8.0 * (nfp * nf + (visc ? nfp * nf : 0.0) + 0.5 * nfp * nd + nfp + nfp * nf) + 4.0 * nfp); // disu, Fn, normal(left), tdA r; tconf w
   bytes[3] += ne * 8.0 * (3 * nu * nf + nu + 2 * nfp * nf + 3 * nu * nf + nfp * nf);                          // u0,u1,div,detjac,tconf,ntd r; u0,u1,div,disu w
   if (pl.fold_shock) bytes[3] += ne * 8.0; // the folded shock filter: sensor w (the state it filters is the group's in LDS)
+  // the LES form: len2 per solution point, tdA per flux point and, for the similarity models, Lu (3) and Le (2) per solution point r
+  if (pl.les) bytes[1] += ne * (8.0 * nu + 8.0 * nfp + (pl.les_terms ? 40.0 * nu : 0.0));
   if (pl.fold_over_int) bytes[1] += ne * 8.0 * (nd * nd * pl.n_cubpts); // the folded over-integration: the cubature points' metrics r
   else if (pl.over_int)
   {
@@ -1190,6 +1382,21 @@ extern "C" int hfx_simplex2d_over_int_plan(hfx_eles *e, int out[8])
   // to the cubature points, the flux there and the projection back
   const int v[8] = {pl.fold_over_int, pl.n_cubpts, pl.over_int ? pl.over_int_chunk : 0, chunks, (int)pl.element_lds,
                     (pl.over_int && !pl.fold_over_int) ? 3 : 0, 0, 0};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+  return 0;
+}
+
+extern "C" int hfx_simplex2d_les_plan(hfx_eles *e, int out[8])
+{
+  HFX_CHECK(e && out, "hfx_simplex2d_les_plan: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  HFX_CHECK(e->simplex2d && e->simplex2d->built, "hfx_simplex2d_les_plan: no 2-D simplex fused stage has prepared this block (run fused 4 first)");
+  const hfx::Simplex2dPlan pl = hfx::simplex2d_plan(e);
+  // kernels in front of a step's FIRST stage of a closure that filters the solution (hfx_eles_calc_sgs_terms): the filter and the
+  // products kernel; the similarity models: and the two contractions of the products and the Leonard kernel; SVV: and, behind the
+  // copy of the filtered state, its extrapolation (ClosureFilter::filtering_refresh_svv)
+  const int in_front = pl.sgs_model < 2 ? 0 : pl.sgs_model == 3 ? 3 : 5;
+  const int v[8] = {pl.les, pl.sgs_model, pl.les_terms, in_front, (int)pl.element_lds, 0, 0, 0};
   for (int i = 0; i < 8; i++) out[i] = v[i];
   return 0;
 }

@@ -64,6 +64,12 @@ struct Simplex2dPlan
   // tdisf_upts.  The element kernel's LDS image is element_lds in every form
   bool over_int = false, fold_over_int = false;
   int n_cubpts = 0, over_int_chunk = 0;
+  // the block registered an LES closure with an SGS flux (sgs_model 0, 1, 2, 4) whose Jacobian_fpts is the block's own, on a viscous
+  // context: the element kernel's LES instantiation evaluates it and Fn carries F_sgs . n (LDS image element_lds).  les_terms: the
+  // similarity models (2, 4) read Lu / Le, which hfx_eles_calc_sgs_terms leaves in front of a step's first stage
+  // (first_stage_closure_filter).  sgs_model: of the registration, -1 without one (3, SVV: the plain kernels)
+  bool les = false, les_terms = false;
+  int sgs_model = -1;
 };
 
 // The partitioned stage's side of the plan (general_partitioned_stage, comm.hip): the kernels walk GROUPS of `group` consecutive
@@ -99,7 +105,7 @@ int simplex2d_update_kernel(hfx_eles *e, int in_step, S2dList list = S2dList::al
 // the stage's update kernel carries the block's shock filter: nothing runs behind the stage for it
 bool simplex2d_folds_shock(const hfx_eles *e);
 void simplex2d_swap_disu_fpts(hfx_eles *e);
-// the projected viscous flux array of the block (what a partition face sends)
+// the projected viscous flux array of the block (what a partition face sends; with an LES closure it carries F_sgs . n as well)
 const double *simplex2d_fn_fpts(const hfx_eles *e);
 // algorithmic HBM bytes per step, added to bytes[0..3]
 void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes);

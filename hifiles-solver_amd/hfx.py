@@ -673,6 +673,14 @@ class Eles:
         check(lib().hfx_simplex2d_over_int_plan(self.h, out))
         return dict(zip(("folded", "n_cubpts", "chunk", "chunks", "element_lds", "launches_in_front"), list(out)))
 
+    def simplex2d_les_plan(self):
+        """an LES closure on this block of triangles in the 2-D simplex fused stage (hfx_simplex2d_les_plan), valid after a fused-4
+        call: dict of les (the element kernel's LES form runs), sgs_model (-1: none), reads_leonard (Lu / Le), launches_in_front (of a
+        step's first stage: those of calc_sgs_terms), element_lds"""
+        out = (C.c_int * 8)()
+        check(lib().hfx_simplex2d_les_plan(self.h, out))
+        return dict(zip(("les", "sgs_model", "reads_leonard", "launches_in_front", "element_lds"), list(out)))
+
     def time_integral_quantities(self, reps=20):
         v = C.c_double(0)
         check(lib().hfx_time_integral_quantities(self.h, C.c_int(reps), C.byref(v)))
@@ -871,6 +879,8 @@ class MpiInters:
     def receive_solution(self, comm): check(lib().hfx_mpi_inters_receive_solution(self.h, comm.h))
     def send_corrected_gradient(self, comm): check(lib().hfx_mpi_inters_send_corrected_gradient(self.h, comm.h))
     def receive_corrected_gradient(self, comm): check(lib().hfx_mpi_inters_receive_corrected_gradient(self.h, comm.h))
+    def send_sgsf_fpts(self, comm): check(lib().hfx_mpi_inters_send_sgsf_fpts(self.h, comm.h))
+    def receive_sgsf_fpts(self, comm): check(lib().hfx_mpi_inters_receive_sgsf_fpts(self.h, comm.h))
 
     def close(self):
         if self.h:

@@ -828,8 +828,9 @@ int hfx_run_steps(hfx_eles *e, hfx_inters *const *faces, int n_face_blocks, int 
  * calc_sgs_terms before the first stage of a step), over-integration forms tdisf_upts by the dense contractions and the flux kernel
  * takes it, shock capturing follows every stage (the filter, then disu_fpts of the filtered state); a closure TOGETHER with
  * over-integration is refused (run fused 0).
- * ONE block of triangles (orders 1-5; no LES closure) runs the 2-D simplex fused stage (csrc/simplex2d.hip), at most
- * four launches per stage.  Registered over-integration (a triangle rule of over_int_order 0..7: 1..36 cubature points) runs INSIDE
+ * ONE block of triangles (orders 1-5) runs the 2-D simplex fused stage (csrc/simplex2d.hip), at most
+ * four launches per stage.  A registered LES closure is evaluated INSIDE its element kernel (hfx_simplex2d_les_plan; not beside
+ * over-integration, and only with the block's own Jacobian_fpts).  Registered over-integration (a triangle rule of over_int_order 0..7: 1..36 cubature points) runs INSIDE
  * its element kernel, which walks the cubature points in chunks and keeps the de-aliased flux in registers (option "fold_over_int"
  * 0: hfx_eles_evaluate_invFlux_over_int in front of the element kernel, which then reads tdisf_upts; hfx_simplex2d_over_int_plan).  Shock capturing registered in the form of eles_tris::shock_det_persson (below) runs INSIDE its update
  * kernel: sensor, filter and the flux-point solution of the filtered state in the stage's last launch (option "fold_shock" 0: the
@@ -1017,6 +1018,19 @@ int hfx_simplex2d_shock_plan(hfx_eles *e, int out[4]);
  * hfx_time_general_kernels reports those launches in slot 4 (name evaluate_invFlux_over_int) and hfx_general_kernel_bytes their bytes
  * there; folded, slot 4 stays 0 and the element kernel's bytes grow by the cubature points' metrics. */
 int hfx_simplex2d_over_int_plan(hfx_eles *e, int out[8]);
+
+/* An LES closure on a block of triangles in the 2-D simplex fused stage (valid once a fused-4 call or a deferred stage has prepared
+ * the block, refused before): out[0] 1: the element kernel's LES form evaluates the closure and the projected viscous flux carries
+ * F_sgs . n (sgs_model 0, 1, 2, 4 on a viscous context, registered with the block's own Jacobian_fpts: sum_k Jacobian_fpts(i,k)
+ * JGinv_fpts(k,j) = detjac_fpts delta_ij to 1e-9 of max |detjac_fpts|; any other registration is refused before the first launch, run
+ * fused 0), out[1] sgs_model of the registration (-1: none; 3, SVV, has no SGS flux: the plain kernels run behind the step loop's
+ * filter, and partitioned blocks refuse it), out[2] 1: the kernel reads Lu / Le (the similarity models 2 and 4), out[3] per-method
+ * kernels in front of a step's FIRST stage (0 for the eddy-viscosity models; the 5 of hfx_eles_calc_sgs_terms for models 2 and 4; 3
+ * for SVV: filter, products, and the extrapolation of the filtered state), 0 in front of every other stage, out[4] bytes of the
+ * element kernel's LDS image (the same in every form), out[5..7] 0.  hfx_general_kernel_bytes counts the added reads of the element
+ * kernel per stage: 8 B per solution point (the squared length scale), 8 B per flux point (tdA_fpts) and, for models 2 and 4, 40 B
+ * per solution point (Lu, Le). */
+int hfx_simplex2d_les_plan(hfx_eles *e, int out[8]);
 
 #ifdef __cplusplus
 }
