@@ -128,11 +128,15 @@ struct FaceBlockArgs
 // loop in either arm.  gface_flux_multi_kernel below is the same point with the choice inside its one store per side and field
 // (two sets of stores behind a branch cost that kernel a wave at RoeM); both are written out, every formula a call into
 // face_physics.hpp -- behind a shared point function either shape was allocated up to six more registers.
-template <int ND, int RS>
-__global__ __launch_bounds__(256) void face_flux2_kernel(const FaceBlockArgs b, const Phys P)
+// (Args = FacePairArgs: the two-sided form, for a block whose sides are DIFFERENT element blocks -- the 2-D stage's cross blocks)
+__device__ __forceinline__ FacePairArgs face_pair_args(const FaceBlockArgs &b) { return b.pair(); }
+__device__ __forceinline__ const FacePairArgs &face_pair_args(const FacePairArgs &a) { return a; }
+
+template <int ND, int RS, class Args = FaceBlockArgs>
+__global__ __launch_bounds__(256) void face_flux2_kernel(const Args b, const Phys P)
 {
   constexpr int NF = ND + 2;
-  const FacePairArgs a = b.pair();
+  const FacePairArgs a = face_pair_args(b);
   const long q = (long)blockIdx.x * 256 + threadIdx.x;
   if (q >= a.npairs) return;
   const long il = a.L[q], ir = a.R[q];

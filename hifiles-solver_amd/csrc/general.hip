@@ -873,7 +873,8 @@ static int general_size_class(const hfx_eles *e)
 
 static int general_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_eles *const *eles, int neb)
 {
-  HFX_CHECK(e->n_dims == 3 && e->n_fields == 5, "general fused stage: three-dimensional Navier-Stokes / Euler blocks only");
+  HFX_CHECK(e->n_dims == 3 && e->n_fields == 5, "general fused stage: three-dimensional Navier-Stokes / Euler blocks only; a two-dimensional "
+            "block runs per method (fused 0), quadrilaterals of orders 1..4 also through the 2-D simplex stage with option blocks_2d 1");
   // (shock capturing follows the stage as its own step: general_shock_capture; an LES closure is evaluated in the flux kernel;
   // over-integration: the de-aliased flux is formed by the dense contractions before the flux kernel, which takes it in P3)
   HFX_CHECK(!(e->les_ready && e->over_int_ready), "general fused stage: an LES closure together with over-integration runs per method");
@@ -1124,7 +1125,7 @@ static int launch_element_kernels(int waves, hfx_eles *e, const GenArgs &a, cons
 }
 
 GeneralStage::GeneralStage(hfx_eles *const *eles_, int neb_, hfx_inters *const *faces_, int nfb_, int in_step_, bool shock_)
-    : eles(eles_), faces(faces_), neb(neb_), nfb(nfb_), simplex2d(neb_ == 1 && is_simplex2d(eles_[0])), in_step(in_step_), shock(shock_)
+    : eles(eles_), faces(faces_), neb(neb_), nfb(nfb_), simplex2d(simplex2d_stage_call(eles_, neb_)), in_step(in_step_), shock(shock_)
 {
   if (simplex2d) return;
   for (int i = 0; i < neb; i++) args.push_back(gen_args(eles[i], plans.emplace_back(general_plan(eles[i])), in_step_));
@@ -1152,7 +1153,13 @@ int GeneralStage::interior_ldg() const
 int GeneralStage::flux_kernels() const
 {
   // (a triangle block's over-integration: inside the element kernel, or -- option fold_over_int 0 -- per method in front of it)
-  if (simplex2d) return simplex2d_over_int_unfolded(eles[0]) || simplex2d_element_kernel(eles[0], in_step);
+  // (several blocks, option blocks_2d: one launch per block; none of them registered over-integration)
+  if (simplex2d)
+  {
+    for (int i = 0; i < neb; i++)
+      if (simplex2d_over_int_unfolded(eles[i]) || simplex2d_element_kernel(eles[i], in_step)) return 1;
+    return 0;
+  }
   for (int i = 0; i < neb; i++)
   {
     // polynomial de-aliasing (src/solver.cpp:82-91): tdisf_upts = over_int_filter . F(opp_over_int_cubpts . u)
@@ -1199,7 +1206,12 @@ int GeneralStage::common_fluxes() const
 
 int GeneralStage::update_kernels() const
 {
-  if (simplex2d) return simplex2d_update_kernel(eles[0], in_step, S2dList::all, shock);
+  if (simplex2d)
+  {
+    for (int i = 0; i < neb; i++) // (each launch, then that block's disu_fpts buffers change places; no block reads another's here)
+      if (simplex2d_update_kernel(eles[i], in_step, S2dList::all, shock)) return 1;
+    return 0;
+  }
   for (int i = 0; i < neb; i++)
     if (launch_element_kernels(plans[i].update_waves, eles[i], args[i], plans[i], false)) return 1;
   for (int i = 0; i < neb; i++) std::swap(eles[i]->arr[HFX_DISU_FPTS], eles[i]->general->disu_alt);
@@ -1225,9 +1237,8 @@ int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, in
     HFX_CHECK(l && r, "face block %d refers to an element block that is not part of this call", b);
   }
   // a two-dimensional block of a non-tensor class (triangles): the 2-D simplex stage's tables (one block; partition faces in
-  // the partitioned stage alone)
-  for (int i = 0; i < neb; i++)
-    if (is_simplex2d(eles[i])) return simplex2d_prepare(eles, neb, faces, nfb, partitioned);
+  // the partitioned stage alone).  Option blocks_2d: several two-dimensional blocks, or one of quadrilaterals, likewise
+  if (simplex2d_takes(eles, neb, partitioned)) return simplex2d_prepare(eles, neb, faces, nfb, partitioned);
   for (int i = 0; i < neb; i++)
   {
     GeneralData *g = eles[i]->general.get();
@@ -1245,7 +1256,7 @@ int general_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, in
 
 const double *general_fn_fpts(const hfx_eles *e)
 {
-  if (is_simplex2d(e)) return simplex2d_fn_fpts(e);
+  if (simplex2d_runs(e)) return simplex2d_fn_fpts(e);
   return e->general ? e->general->fn_fpts : nullptr;
 }
 
@@ -1357,7 +1368,7 @@ void general_kernel_bytes(hfx_eles *const *eles, int neb, double *bytes)
   for (int i = 0; i < neb; i++)
   {
     const hfx_eles *e = eles[i];
-    if (is_simplex2d(e))
+    if (simplex2d_runs(e))
     {
       simplex2d_kernel_bytes(e, bytes);
       continue;

@@ -92,7 +92,8 @@ struct GeneralStage
   int neb, nfb;
   std::vector<GeneralPlan> plans; // per element block, as
   std::vector<GenArgs> args;
-  // one two-dimensional simplex block (triangles): every step is simplex2d.hip's, plans and args stay empty
+  // this call runs the 2-D stage (one block of triangles; option blocks_2d: several two-dimensional blocks, or one of
+  // quadrilaterals -- simplex2d_stage_call): every step is simplex2d.hip's, plans and args stay empty
   bool simplex2d = false;
   int in_step = 0;
   // eles::shock_capture follows this stage where a block registered it: a triangle block whose plan folds the filter

@@ -494,6 +494,7 @@ int hfx_ctx_set_option(hfx_ctx *ctx, const char *name, int value)
   else if (n == "fold_faces") o.fold_faces = value != 0;
   else if (n == "fold_shock") o.fold_shock = value != 0;
   else if (n == "fold_over_int") o.fold_over_int = value != 0;
+  else if (n == "blocks_2d") o.blocks_2d = value != 0;
   else if (n == "flux_two_wave_face") { HFX_CHECK(value >= -1 && value <= 5, "flux_two_wave_face must be -1 (the host's choice) or a local face 0-5"); o.flux_two_wave_face = value; }
   else if (n == "les_flux_kernel") o.les_flux_kernel = value != 0;
   else if (n == "bdy_beside") o.bdy_beside = value != 0;
@@ -1864,7 +1865,7 @@ int hfx_time_general_kernels(hfx_eles *const *eles, int neb, hfx_inters *const *
   HFX_IMMEDIATE(eles[0]->ctx, 0);
   HFX_CHECK(eles[0]->ctx->have_params, "parameters not set");
   if (general_time_kernels(eles, neb, faces, nfb, reps, ms)) return 1;
-  if (neb == 1 && is_simplex2d(eles[0]))
+  if (simplex2d_stage_call(eles, neb))
   {
     // (slot 4, SLOT_OVER_INT: a registered over-integration that the element kernel does not fold -- option fold_over_int 0)
     const hfx::Simplex2dPlan pl = hfx::simplex2d_plan(eles[0]);

@@ -243,6 +243,7 @@ struct hfx_ctx
     int general_waves = 0;      // waves per workgroup of the general flux kernel: 0 by the LDS image (4 or 8), else 3, 4 or 8
     int fold_over_int = 1;      // 1: the 2-D simplex stage's element kernel carries a triangle block's over-integration (its OVERINT instantiation); 0: hfx_eles_evaluate_invFlux_over_int in front of the element kernel, which reads tdisf_upts
     int fold_shock = 1;         // 1: the 2-D simplex stage's update kernel carries a triangle block's shock filter (sensor of eles_tris::shock_det_persson); 0: the per-method filter behind the stage, as on tetrahedra and prisms
+    int blocks_2d = 0;          // 1: the 2-D simplex stage (fused 4) takes several two-dimensional blocks -- a mixed quadrilateral / triangle mesh, several triangle blocks -- and a block of quadrilaterals of orders 1..4 (its plain kernels; cross blocks' LDG corrections by face_delta_kernel); 0: those calls are refused as ever
   } opt;
   hfx::Deferred defer;
   std::vector<hfx_comm *> comms; // the live communicators of this context (hfx_ctx_synchronize waits for their streams)

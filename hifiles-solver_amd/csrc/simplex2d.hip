@@ -21,6 +21,12 @@
 // 64-byte read, the same address for the lanes of one element: a broadcast), the operators as the dense column-major matrices the
 // block registered (consecutive rows in consecutive lanes: conflict free).  A workgroup stages the operators once and walks groups
 // grid-stride.  Ordinary stores, no atomics but the NaN flag's: bit-reproducible from run to run.
+//
+// Option blocks_2d: the same stage over SEVERAL two-dimensional blocks (a mixed quadrilateral / triangle mesh, several triangle
+// blocks) and over a block of quadrilaterals -- the dense kernels' plain forms on a second size table (QUAD2D_SIZES, P1..P4).  Each
+// block has its own tables and its own element and update launch; an interior-face block between two element blocks (a cross block)
+// takes each side's arrays from its own block (face_flux2_kernel's two-sided form), and its LDG corrections are face_delta_kernel's:
+// a partner word addresses the block's own flux points only (simplex2d_prepare_blocks, simplex2d_build).
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -54,7 +60,11 @@ struct Simplex2dData
   DevBuf<int> nbr;                        // (n_fpts, n_eles) partner word of every flux point (S2dArgs::nbr)
   DevBuf<double> disu_alt;                // second disu_fpts buffer (the update kernel writes the new state's flux-point solution)
   DevBuf<double> fn_fpts;                 // (n_fpts, n_eles, n_fields) viscous flux projected on the point's own normal
-  bool any_bdy = false, any_int = false;
+  bool any_bdy = false, any_int = false; // any_int: pairs INSIDE the block (the partner words address them)
+  // points on cross blocks (an interior-face block between this block and another one of the call): their partner word is -1 and
+  // face_delta_kernel<2> writes their corrections
+  long n_cross_pts = 0;
+  std::vector<const hfx_eles *> built_blocks; // the element blocks of the call the tables were made for
   // partitioned blocks: the groups (of the size class's G consecutive elements) with and without a partition flux point, ascending
   DevBuf<int> partition_groups, interior_groups;
   int n_partition_groups = 0, n_interior_groups = 0;
@@ -175,7 +185,7 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_element_kernel_t(const S2dArg
   constexpr int CH = NU;                      // cubature points per chunk
   constexpr int TRIPS = (NU * G + T - 1) / T; // solution points of a group per lane
   constexpr int TRIPS_F = (NFP * G + T - 1) / T; // flux points of a group per lane
-  static_assert(2 * CH * NU <= NFP * GP * NF, "a chunk's operator slices fit the D region");
+  static_assert(OVERINT != S2dOverInt::folded || 2 * CH * NU <= NFP * GP * NF, "a chunk's operator slices fit the D region");
   extern __shared__ double lds[];
   // operators, dense column-major as registered
   double *o4 = lds;                     // [2][NU x NU]
@@ -849,9 +859,35 @@ __global__ __launch_bounds__(S2D_T) void simplex2d_update_kernel_t(const S2dArgs
 // ---------------------------------------------------------------------------------------------------------------
 static int simplex2d_size_class(const hfx_eles *e)
 {
-  for (int i = 0; i < N_SIMPLEX2D_SIZES; i++)
-    if (e->n_upts == SIMPLEX2D_SIZES[i][0] && e->n_fpts == SIMPLEX2D_SIZES[i][1]) return i;
+  const int first = e->ele_type == 1 ? N_SIMPLEX2D_SIZES : 0, last = e->ele_type == 1 ? N_S2D_CLASSES : N_SIMPLEX2D_SIZES;
+  for (int i = first; i < last; i++)
+    if (e->n_upts == s2d_class_row(i)[0] && e->n_fpts == s2d_class_row(i)[1]) return i;
   return -1;
+}
+
+static bool is_block2d(const hfx_eles *e) { return e && e->n_dims == 2 && (e->ele_type == 0 || e->ele_type == 1); }
+
+bool simplex2d_runs(const hfx_eles *e)
+{
+  return is_simplex2d(e) || (is_block2d(e) && e->ctx->opt.blocks_2d && e->simplex2d && e->simplex2d->built);
+}
+
+bool simplex2d_stage_call(hfx_eles *const *eles, int neb)
+{
+  for (int i = 0; i < neb; i++)
+    if (!simplex2d_runs(eles[i])) return false;
+  return neb > 0;
+}
+
+bool simplex2d_takes(hfx_eles *const *eles, int neb, bool partitioned)
+{
+  bool tri = false, any2d = false;
+  for (int i = 0; i < neb; i++)
+  {
+    tri = tri || is_simplex2d(eles[i]);
+    any2d = any2d || eles[i]->n_dims == 2;
+  }
+  return tri || (any2d && eles[0]->ctx->opt.blocks_2d && !(partitioned && neb == 1));
 }
 
 // the operators of `list` one behind the other, each dense column-major as registered; an operator the run does not have: zeros
@@ -917,11 +953,11 @@ static int les_jacobian_residual(const hfx_eles *e, double *residual)
   return 0;
 }
 
-static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
+static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb, hfx_eles *const *blocks, int neb)
 {
   HFX_CHECK(e->n_fields == 4, "2-D simplex fused stage: Navier-Stokes / Euler blocks only; run per method (fused 0)");
-  HFX_CHECK(simplex2d_size_class(e) >= 0, "2-D simplex fused stage: built for triangles of orders 1..5 (%d solution, %d flux points); run per method (fused 0)",
-            e->n_upts, e->n_fpts);
+  HFX_CHECK(simplex2d_size_class(e) >= 0, "2-D simplex fused stage: built for triangles of orders 1..5 and quadrilaterals of orders 1..4 (%d solution, "
+            "%d flux points on element class %d); run per method (fused 0)", e->n_upts, e->n_fpts, e->ele_type);
   HFX_CHECK(!(e->les_ready && e->over_int_ready), "2-D simplex fused stage: an LES closure beside over-integration runs per method (fused 0)");
   // (a conforming closure beside a conforming shock registration: the LES element kernel and the SHOCK update kernel -- or, with
   // option fold_shock 0, the filter behind the stage -- each as it runs alone)
@@ -1001,6 +1037,7 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
   std::vector<double> norm((size_t)plane_f * 2);
   HFX_HIP(hipMemcpy(norm.data(), e->norm_fpts, sizeof(double) * norm.size(), hipMemcpyDeviceToHost));
   g->any_bdy = g->any_int = g->any_mpi = false;
+  g->n_cross_pts = 0;
   // partition faces (the partitioned stage): a partition point is owned by its face like every other point and carries no boundary
   // bit; its common flux comes from the one-sided kernels of kernels_mpi.hpp.  Its LDG correction: with ONE partition-face block
   // the element kernel reads the partner from that block's receive record (remote word; the switch from the point's OWN normal, as
@@ -1008,12 +1045,13 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
   int n_mpi_blocks = 0;
   for (int b = 0; b < nfb; b++) n_mpi_blocks += faces[b]->is_mpi && faces[b]->n_inters > 0;
   g->remote_face = nullptr;
-  const int G = SIMPLEX2D_SIZES[simplex2d_size_class(e)][2];
+  const int G = s2d_class_row(simplex2d_size_class(e))[2];
   const int n_groups = (e->n_eles + G - 1) / G;
   std::vector<char> partition_group(n_groups, 0);
   for (int b = 0; b < nfb; b++)
   {
     hfx_inters *f = faces[b];
+    if (f->left != e && f->right != e) continue; // (a face block of the call's other element blocks)
     if (f->is_mpi)
     {
       const long np = (long)f->n_inters * f->n_fpts_per_inter;
@@ -1041,6 +1079,27 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
       continue;
     }
     const long np = (long)f->n_inters * f->n_fpts_per_inter;
+    if (f->left != f->right)
+    {
+      // a cross block: its left points are this block's where it is the left one (with the pair's switch bit, from the left
+      // normal), its right points where it is the right one; the partner word stays -1 (the partner lies in another block's
+      // arrays) and face_delta_kernel<2> writes the correction
+      const bool is_left = f->left == e;
+      const std::vector<int> &mine = is_left ? f->hL : f->hR;
+      for (long q = 0; q < np; q++)
+      {
+        const int o = mine[q];
+        HFX_CHECK(o >= 0 && o < plane_f, "2-D simplex fused stage: a face block addresses flux point %d of a block with %ld", o, plane_f);
+        owned[o]++;
+        if (is_left)
+        {
+          const double n[2] = {norm[o], norm[o + plane_f]};
+          meta[o] |= ldg_switch<2>(1.0, n) < 0 ? 2 : 0;
+        }
+      }
+      g->n_cross_pts += np;
+      continue;
+    }
     for (long q = 0; q < np; q++)
     {
       const int il = f->hL[q], ir = f->hR[q];
@@ -1068,14 +1127,48 @@ static int simplex2d_build(hfx_eles *e, hfx_inters *const *faces, int nfb)
     if (!inter.empty() && g->interior_groups.upload(inter)) return 1;
   }
   g->built_with.assign(faces, faces + nfb);
+  g->built_blocks.assign(blocks, blocks + neb);
   g->built = true;
+  return 0;
+}
+
+// Several two-dimensional blocks, or one block of quadrilaterals (option blocks_2d): each block its own tables, made from the face
+// blocks that touch it.  Only the plain stage: whatever a block has registered beyond it is refused here, before anything is launched
+static int simplex2d_prepare_blocks(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb)
+{
+  for (int i = 0; i < neb; i++)
+  {
+    const hfx_eles *e = eles[i];
+    HFX_CHECK(e->n_dims == 2, "2-D simplex fused stage: a three-dimensional block beside a two-dimensional one runs per method (fused 0)");
+    HFX_CHECK(is_block2d(e), "2-D simplex fused stage: element class %d is neither triangles nor quadrilaterals; run per method (fused 0)", e->ele_type);
+    HFX_CHECK(e->n_eles > 0, "2-D simplex fused stage: empty element block");
+    HFX_CHECK(e->order == eles[0]->order, "2-D simplex fused stage: element blocks of different order (%d beside %d) run per method (fused 0)",
+              e->order, eles[0]->order);
+    HFX_CHECK(!e->les_ready, "2-D simplex fused stage: a registered LES closure on one of several blocks, or on quadrilaterals, runs per method (fused 0)");
+    HFX_CHECK(!e->over_int_ready, "2-D simplex fused stage: registered over-integration on one of several blocks, or on quadrilaterals, runs per method (fused 0)");
+    HFX_CHECK(!e->shock_ready, "2-D simplex fused stage: registered shock capturing on one of several blocks, or on quadrilaterals, runs per method (fused 0)");
+    HFX_CHECK(!e->ctx->params.viscous || e->viscous_ops, "2-D simplex fused stage: viscous run but a block has no opp_4/5/6");
+  }
+  for (int b = 0; b < nfb; b++)
+    HFX_CHECK(!faces[b]->is_mpi, "2-D simplex fused stage: a partition-face block on several two-dimensional blocks, or on quadrilaterals, runs per method (fused 0)");
+  for (int i = 0; i < neb; i++)
+  {
+    const Simplex2dData *g = eles[i]->simplex2d.get();
+    if (g && g->built && !g->shock && !g->over_int && !g->les && g->built_with.size() == (size_t)nfb && std::equal(g->built_with.begin(), g->built_with.end(), faces) &&
+        g->built_blocks.size() == (size_t)neb && std::equal(g->built_blocks.begin(), g->built_blocks.end(), eles))
+      continue;
+    if (simplex2d_build(eles[i], faces, nfb, eles, neb)) return 1;
+  }
   return 0;
 }
 
 int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, bool partitioned)
 {
-  HFX_CHECK(neb == 1, "2-D simplex fused stage: several element blocks of which one is two-dimensional (a mixed quadrilateral / triangle "
-                      "mesh) run per method (fused 0)");
+  const bool blocks_2d = eles[0]->ctx->opt.blocks_2d != 0;
+  HFX_CHECK(neb == 1 || (blocks_2d && !partitioned),
+            "2-D simplex fused stage: several element blocks of which one is two-dimensional (a mixed quadrilateral / triangle mesh) run per method "
+            "(fused 0)%s", partitioned ? " in the partitioned loop" : "; hfx_run_steps_blocks takes them with option blocks_2d 1");
+  if (neb > 1 || !is_simplex2d(eles[0])) return simplex2d_prepare_blocks(eles, neb, faces, nfb);
   hfx_eles *e = eles[0];
   HFX_CHECK(e->n_eles > 0, "2-D simplex fused stage: empty element block");
   if (!partitioned)
@@ -1096,9 +1189,9 @@ int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, 
   if (g && g->built && les_same && g->shock == e->shock_ready && g->shock_serial == e->shock_serial &&
       g->over_int == e->over_int_ready && g->over_int_serial == e->over_int_serial &&
       g->built_with.size() == (size_t)nfb &&
-      std::equal(g->built_with.begin(), g->built_with.end(), faces))
+      std::equal(g->built_with.begin(), g->built_with.end(), faces) && g->built_blocks.size() == 1 && g->built_blocks[0] == e)
     return 0;
-  return simplex2d_build(e, faces, nfb);
+  return simplex2d_build(e, faces, nfb, eles, 1);
 }
 
 Simplex2dPlan simplex2d_plan(const hfx_eles *e)
@@ -1106,7 +1199,7 @@ Simplex2dPlan simplex2d_plan(const hfx_eles *e)
   Simplex2dPlan pl;
   pl.size_class = simplex2d_size_class(e);
   if (pl.size_class < 0) return pl;
-  const int *s = SIMPLEX2D_SIZES[pl.size_class];
+  const int *s = s2d_class_row(pl.size_class);
   pl.group = s[2];
   pl.gather = e->ctx->opt.gather_delta && e->ctx->params.viscous && e->simplex2d && (e->simplex2d->any_int || e->simplex2d->remote_face);
   pl.element_lds = simplex2d_element_lds_bytes(s[0], s[1], s[2]);
@@ -1124,7 +1217,7 @@ Simplex2dPlan simplex2d_plan(const hfx_eles *e)
   return pl;
 }
 
-bool simplex2d_folds_shock(const hfx_eles *e) { return is_simplex2d(e) && simplex2d_plan(e).fold_shock; }
+bool simplex2d_folds_shock(const hfx_eles *e) { return simplex2d_runs(e) && simplex2d_plan(e).fold_shock; }
 
 Simplex2dPartitionPlan simplex2d_partition_plan(const hfx_eles *e)
 {
@@ -1189,11 +1282,11 @@ static S2dArgs s2d_args(hfx_eles *e, const Simplex2dPlan &pl, int in_step, S2dLi
   return a;
 }
 
-// the instantiation of the plan's size class (SIMPLEX2D_SIZES[I], I counting up)
+// the instantiation of the plan's size class (s2d_class_row(I), I counting up; the quadrilateral classes: the plain kernels alone)
 template <int I = 0>
 static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool element, bool shock = false)
 {
-  if constexpr (I == N_SIMPLEX2D_SIZES)
+  if constexpr (I == N_S2D_CLASSES)
   {
     HFX_CHECK(false, "2-D simplex fused stage: no kernel for this element size");
     return 1;
@@ -1201,7 +1294,7 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
   else
   {
     if (pl.size_class != I) return launch_s2d<I + 1>(e, a, pl, element, shock);
-    constexpr int NU = SIMPLEX2D_SIZES[I][0], NFP = SIMPLEX2D_SIZES[I][1], G = SIMPLEX2D_SIZES[I][2];
+    constexpr int NU = s2d_class_row(I)[0], NFP = s2d_class_row(I)[1], G = s2d_class_row(I)[2];
     const size_t lds = element ? pl.element_lds : shock ? pl.update_shock_lds : pl.update_lds;
     HFX_CHECK(lds <= SIMPLEX2D_LDS_BUDGET, "2-D simplex fused stage: an LDS image of %zu bytes exceeds the budget of %zu", lds, SIMPLEX2D_LDS_BUDGET);
     a.ops = element ? e->simplex2d->element_ops : shock ? e->simplex2d->update_shock_ops : e->simplex2d->update_ops;
@@ -1220,6 +1313,12 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
       HFX_HIP(hipGetLastError());
       return 0;
     };
+    if constexpr (I >= N_SIMPLEX2D_SIZES)
+    {
+      HFX_CHECK(!oi && !les && !shock, "2-D simplex fused stage: quadrilaterals run the plain kernels only");
+      return element ? launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::none>) : launch(simplex2d_update_kernel_t<NU, NFP, G, false>);
+    }
+    else
     return oi      ? (pl.fold_over_int ? launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::folded>)
                                        : launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::unfolded>))
            : les     ? launch(simplex2d_element_kernel_t<NU, NFP, G, S2dOverInt::none, true>)
@@ -1229,32 +1328,39 @@ static int launch_s2d(hfx_eles *e, S2dArgs a, const Simplex2dPlan &pl, bool elem
   }
 }
 
-// the pairs of an interior-face block of the one element block
+// the pairs of an interior-face block: each side the arrays of its own element block, switch bit and normal the left block's
 static FacePairArgs s2d_face_args(hfx_inters *f)
 {
+  auto side = [](hfx_eles *x) {
+    FaceSide s{};
+    s.plane = (long)x->n_fpts * x->n_eles;
+    s.disu = x->arr[HFX_DISU_FPTS]; s.fn = x->simplex2d->fn_fpts; s.tdA = x->tdA_fpts;
+    s.delta = x->arr[HFX_DELTA_DISU_FPTS]; s.tconf = x->arr[HFX_NORM_TCONF_FPTS];
+    return s;
+  };
   hfx_eles *x = f->left;
-  FaceSide s{};
-  s.plane = (long)x->n_fpts * x->n_eles;
-  s.disu = x->arr[HFX_DISU_FPTS]; s.fn = x->simplex2d->fn_fpts; s.tdA = x->tdA_fpts;
-  s.delta = x->arr[HFX_DELTA_DISU_FPTS]; s.tconf = x->arr[HFX_NORM_TCONF_FPTS];
   FacePairArgs a{};
   a.npairs = (long)f->n_inters * f->n_fpts_per_inter;
   a.L = f->L; a.R = f->R; a.meta = x->simplex2d->meta; a.norm = x->norm_fpts;
-  a.l = s; a.r = s;
+  a.l = side(x); a.r = f->right == x ? a.l : side(f->right);
   return a;
 }
+
+static bool s2d_interior(const hfx_inters *f) { return !f->is_bdy && !f->is_mpi && (long)f->n_inters * f->n_fpts_per_inter > 0; }
+static bool s2d_cross(const hfx_inters *f) { return f->left != f->right; }
+// face_delta_kernel<2> writes the corrections of this interior-face block: a cross block always, a block inside one element block
+// unless that block's element kernel gathers
+static bool s2d_needs_delta(const hfx_inters *f) { return s2d_cross(f) || !simplex2d_plan(f->left).gather; }
 
 int simplex2d_interior_ldg(hfx_eles *e, hfx_inters *const *faces, int nfb)
 {
   hfx_ctx *ctx = e->ctx;
   if (!ctx->params.viscous) return 0;
-  const bool gather = simplex2d_plan(e).gather;
   for (int b = 0; b < nfb; b++)
   {
     if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], 0, 1)) return 1; // ghost state -> inviscid common flux, LDG common solution
-    if (faces[b]->is_bdy || faces[b]->is_mpi || gather) continue; // (partition faces: the partitioned stage's one-sided kernels)
+    if (!s2d_interior(faces[b]) || !s2d_needs_delta(faces[b])) continue; // (partition faces: the partitioned stage's one-sided kernels)
     const FacePairArgs a = s2d_face_args(faces[b]);
-    if (a.npairs == 0) continue;
     hipLaunchKernelGGL(face_delta_kernel<2>, dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, ctx->stream, a, ctx->phys());
   }
   HFX_HIP(hipGetLastError());
@@ -1291,13 +1397,18 @@ int simplex2d_common_fluxes(hfx_eles *e, hfx_inters *const *faces, int nfb)
     if (faces[b]->is_bdy && hfx_bdy_launch_internal(faces[b], P.viscous ? 1 : 0, 1)) return 1;
   for (int b = 0; b < nfb; b++)
   {
-    if (faces[b]->is_bdy || faces[b]->is_mpi) continue;
+    if (!s2d_interior(faces[b])) continue;
     const FacePairArgs a = s2d_face_args(faces[b]);
-    if (a.npairs == 0) continue;
-    const FaceBlockArgs blk(a);
-    with_riemann_solver(P.riemann, [&](auto RS) {
-      hipLaunchKernelGGL((face_flux2_kernel<2, decltype(RS)::value>), dim3((unsigned)((a.npairs + 255) / 256)), dim3(256), 0, ctx->stream, blk, P);
-    });
+    const dim3 grid((unsigned)((a.npairs + 255) / 256));
+    if (s2d_cross(faces[b])) // (each side its own block's arrays: the kernel's two-sided form)
+      with_riemann_solver(P.riemann, [&](auto RS) {
+        hipLaunchKernelGGL((face_flux2_kernel<2, decltype(RS)::value, FacePairArgs>), grid, dim3(256), 0, ctx->stream, a, P);
+      });
+    else
+    {
+      const FaceBlockArgs blk(a);
+      with_riemann_solver(P.riemann, [&](auto RS) { hipLaunchKernelGGL((face_flux2_kernel<2, decltype(RS)::value>), grid, dim3(256), 0, ctx->stream, blk, P); });
+    }
   }
   HFX_HIP(hipGetLastError());
   return 0;
@@ -1323,6 +1434,7 @@ void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes)
   const bool visc = e->ctx->params.viscous != 0;
   const Simplex2dPlan pl = simplex2d_plan(e);
   if (visc && !pl.gather) bytes[0] += ne * (8.0 * (2 * nfp * nf) + 4.0 * nfp + nfp * 0.5); // disu r, delta w, index + meta
+  else if (visc && e->simplex2d) bytes[0] += (double)e->simplex2d->n_cross_pts * (8.0 * (2 * nf) + 4.0 + 0.5); // (the cross blocks' points alone)
   // u, metrics at the solution points r; div, norm_tdisf w
   bytes[1] += ne * 8.0 * (nu * nf + nu * nd * nd + nu * nf + nfp * nf);
   // viscous: delta (or the partner's disu and the own, and a partner word), detjac at both point sets, the flux points' metrics and normals r; Fn w
@@ -1343,7 +1455,43 @@ void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes)
   }
 }
 
+Simplex2dStagePlan simplex2d_stage_plan(hfx_eles *const *eles, int neb)
+{
+  Simplex2dStagePlan sp;
+  sp.blocks = neb;
+  const bool visc = eles[0]->ctx->params.viscous != 0;
+  int bdy = 0;
+  for (const hfx_inters *f : eles[0]->simplex2d->built_with) // (every block's tables were made from the call's whole face list)
+  {
+    bdy += f->is_bdy && f->n_inters > 0;
+    if (!s2d_interior(f)) continue;
+    sp.interior_face_blocks++;
+    sp.cross_face_blocks += s2d_cross(f);
+    sp.delta_launches += visc && s2d_needs_delta(f);
+  }
+  // boundary sweeps: viscous runs one in front of the element kernels and one behind, inviscid runs the one behind
+  sp.launches = (visc ? 2 : 1) * bdy + sp.delta_launches + neb + sp.interior_face_blocks + neb;
+  return sp;
+}
+
 } // namespace hfx
+
+extern "C" int hfx_simplex2d_stage_plan(hfx_eles *const *eles, int neb, int out[8])
+{
+  HFX_CHECK(eles && neb > 0 && eles[0] && out, "hfx_simplex2d_stage_plan: bad argument");
+  HFX_IMMEDIATE(eles[0]->ctx, 0);
+  for (int i = 0; i < neb; i++)
+  {
+    const hfx::Simplex2dData *g = eles[i] ? eles[i]->simplex2d.get() : nullptr;
+    HFX_CHECK(g && g->built && hfx::simplex2d_runs(eles[i]), "hfx_simplex2d_stage_plan: no 2-D simplex fused stage has prepared block %d (run fused 4 first)", i);
+    HFX_CHECK(g->built_blocks.size() == (size_t)neb && std::equal(g->built_blocks.begin(), g->built_blocks.end(), eles),
+              "hfx_simplex2d_stage_plan: block %d was prepared in another call's list of blocks", i);
+  }
+  const hfx::Simplex2dStagePlan sp = hfx::simplex2d_stage_plan(eles, neb);
+  const int v[8] = {sp.blocks, sp.interior_face_blocks, sp.cross_face_blocks, sp.delta_launches, sp.launches, 0, 0, 0};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+  return 0;
+}
 
 extern "C" int hfx_simplex2d_plan(hfx_eles *e, int out[8])
 {

@@ -1,6 +1,7 @@
 // simplex2d.hpp -- the fused RK stage for two-dimensional simplex blocks (triangles): a block's plan and the stage's steps
 // (simplex2d.hip).  The host side of the general stage (general.hip: general_prepare, GeneralStage, general_time_kernels,
-// general_kernel_bytes) branches here for a block with n_dims == 2 of a non-tensor class; nothing else calls these.
+// general_kernel_bytes) branches here for a block with n_dims == 2 of a non-tensor class -- and, with option blocks_2d, for several
+// two-dimensional blocks or a block of quadrilaterals (simplex2d_takes, simplex2d_runs); nothing else calls these.
 #pragma once
 #include "hfx_internal.hpp"
 
@@ -11,6 +12,14 @@ namespace hfx
 constexpr int SIMPLEX2D_SIZES[][3] = {{3, 6, 64}, {6, 9, 64}, {10, 12, 32}, {15, 15, 32}, {21, 18, 16}};
 constexpr int N_SIMPLEX2D_SIZES = sizeof(SIMPLEX2D_SIZES) / sizeof(SIMPLEX2D_SIZES[0]);
 constexpr int SIMPLEX2D_WAVES = 4;
+// the quadrilateral orders P1..P4 on the same dense kernels (option blocks_2d: a quadrilateral block beside triangles, or alone): the
+// PLAIN element and update kernels only.  Size classes N_SIMPLEX2D_SIZES + 0..3; P5 (36 and 24 points) does not fit: its element
+// operators alone are 82 944 bytes
+constexpr int QUAD2D_SIZES[][3] = {{4, 8, 64}, {9, 12, 32}, {16, 16, 16}, {25, 20, 8}};
+constexpr int N_QUAD2D_SIZES = sizeof(QUAD2D_SIZES) / sizeof(QUAD2D_SIZES[0]);
+constexpr int N_S2D_CLASSES = N_SIMPLEX2D_SIZES + N_QUAD2D_SIZES;
+// row {solution points, flux points, elements of a group} of a size class of either table
+constexpr const int *s2d_class_row(int i) { return i < N_SIMPLEX2D_SIZES ? SIMPLEX2D_SIZES[i] : QUAD2D_SIZES[i - N_SIMPLEX2D_SIZES]; }
 // LDS image of a workgroup (doubles): the operators, staged once per workgroup, then a group's planes [row][element + 1 pad][.]
 constexpr size_t simplex2d_element_ops(int nu, int nfp) { return (size_t)4 * nu * nu + (size_t)6 * nu * nfp; } // o4 o5 o6 o0 o2 o1
 // (shock: the update kernel with the shock filter folded in stages inv_vandermonde and exp_filter behind them)
@@ -42,14 +51,17 @@ constexpr bool simplex2d_sizes_fit()
   bool ok = true;
   for (const auto &s : SIMPLEX2D_SIZES)
     ok = ok && simplex2d_element_lds_bytes(s[0], s[1], s[2]) <= SIMPLEX2D_LDS_BUDGET && simplex2d_update_lds_bytes(s[0], s[1], s[2], true) <= SIMPLEX2D_LDS_BUDGET;
+  for (const auto &s : QUAD2D_SIZES) // (the plain forms alone; at most two points of a group per lane)
+    ok = ok && simplex2d_element_lds_bytes(s[0], s[1], s[2]) <= SIMPLEX2D_LDS_BUDGET && simplex2d_update_lds_bytes(s[0], s[1], s[2]) <= SIMPLEX2D_LDS_BUDGET &&
+         s[0] * s[2] <= 2 * 64 * SIMPLEX2D_WAVES;
   return ok;
 }
-static_assert(simplex2d_sizes_fit(), "a group of an instantiated triangle order no longer leaves room for two workgroups per CU");
+static_assert(simplex2d_sizes_fit(), "a group of an instantiated triangle or quadrilateral order no longer leaves room for two workgroups per CU");
 
 // What the stage runs on one block: decided once, from the options and the block's sizes and tables
 struct Simplex2dPlan
 {
-  int size_class = -1; // index in SIMPLEX2D_SIZES (order - 1)
+  int size_class = -1; // triangles: index in SIMPLEX2D_SIZES (order - 1); quadrilaterals: N_SIMPLEX2D_SIZES + index in QUAD2D_SIZES
   int group = 0;       // elements per group
   int waves = SIMPLEX2D_WAVES;
   bool gather = false; // the element kernel forms the LDG corrections of interior points itself (option gather_delta, viscous)
@@ -84,14 +96,23 @@ struct Simplex2dPartitionPlan
 // which groups a launch of the element / update kernel walks
 enum class S2dList { all, interior, partition };
 
-inline bool is_simplex2d(const hfx_eles *e) { return e && e->n_dims == 2 && e->ele_type == 0; }
+inline bool is_simplex2d(const hfx_eles *e) { return e && e->n_dims == 2 && e->ele_type == 0; } // a block of triangles
+// this block's tables are the 2-D stage's and the stage runs it: a triangle block, or -- option blocks_2d -- a quadrilateral block the
+// stage has prepared.  What dispatches a STAGE asks here, what is specific to triangles asks is_simplex2d
+bool simplex2d_runs(const hfx_eles *e);
+// a call over these blocks runs the 2-D stage (every one of them simplex2d_runs)
+bool simplex2d_stage_call(hfx_eles *const *eles, int neb);
+// is this call for simplex2d_prepare?  One triangle block, as ever; with option blocks_2d any call with a two-dimensional block but
+// the partitioned loop's over ONE quadrilateral block (the split stage's)
+bool simplex2d_takes(hfx_eles *const *eles, int neb, bool partitioned);
 // tables for the block unless they exist; refuses (naming fused 0) what the stage is not built for.  partitioned: the call comes
 // from the partitioned stage, which alone takes partition-face blocks
 int simplex2d_prepare(hfx_eles *const *eles, int neb, hfx_inters *const *faces, int nfb, bool partitioned);
 void simplex2d_invalidate(hfx_eles *e);
 Simplex2dPlan simplex2d_plan(const hfx_eles *e);
 Simplex2dPartitionPlan simplex2d_partition_plan(const hfx_eles *e);
-// the four steps of ONE stage on a prepared block whose disu_fpts belong to the current state (GeneralStage's, in its order)
+// the four steps of ONE stage on prepared blocks whose disu_fpts belong to the current state (GeneralStage's, in its order).  The
+// two face steps walk ALL face blocks of the call (e: any block of it), the element and update kernels are launched block by block
 int simplex2d_interior_ldg(hfx_eles *e, hfx_inters *const *faces, int nfb);
 // the unfolded form of a registered over-integration (plan: over_int, not fold_over_int): hfx_eles_evaluate_invFlux_over_int on the
 // whole block, ONCE per stage in front of the element launches; nothing in every other form
@@ -109,4 +130,13 @@ void simplex2d_swap_disu_fpts(hfx_eles *e);
 const double *simplex2d_fn_fpts(const hfx_eles *e);
 // algorithmic HBM bytes per step, added to bytes[0..3]
 void simplex2d_kernel_bytes(const hfx_eles *e, double *bytes);
+// What ONE stage over the prepared blocks launches (hfx_simplex2d_stage_plan): counted by the predicates the launches use
+struct Simplex2dStagePlan
+{
+  int blocks = 0;
+  int interior_face_blocks = 0, cross_face_blocks = 0; // (non-empty ones; cross: left != right)
+  int delta_launches = 0;                              // face_delta_kernel<2> per stage
+  int launches = 0;                                    // all of a stage: boundary sweeps, delta, element, face flux, update
+};
+Simplex2dStagePlan simplex2d_stage_plan(hfx_eles *const *eles, int neb);
 } // namespace hfx

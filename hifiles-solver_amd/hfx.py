@@ -901,6 +901,15 @@ def run_steps_blocks(eles, faces, n_steps, fused=0):
     check(lib().hfx_run_steps_blocks(ea, C.c_int(len(eles)), fa, C.c_int(len(faces)), C.c_int(n_steps), C.c_int(int(fused))))
 
 
+def simplex2d_stage_plan(eles):
+    """hfx_simplex2d_stage_plan: what one stage of the 2-D simplex fused stage launches over these blocks (the list of the fused-4 call
+    that prepared them): dict of blocks, interior_face_blocks, cross_face_blocks, delta_launches, launches"""
+    ea = (C.c_void_p * len(eles))(*[e.h for e in eles])
+    out = (C.c_int * 8)()
+    check(lib().hfx_simplex2d_stage_plan(ea, C.c_int(len(eles)), out))
+    return dict(zip(("blocks", "interior_face_blocks", "cross_face_blocks", "delta_launches", "launches"), list(out)))
+
+
 def time_general_kernels(eles, faces, reps=10):
     """hfx_time_general_kernels: (ms[8], the comma-separated kernel names) of the fused-4 stage on these blocks"""
     ea = (C.c_void_p * len(eles))(*[e.h for e in eles])

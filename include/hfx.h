@@ -139,7 +139,8 @@ int hfx_ctx_set_CFL(hfx_ctx *ctx, double CFL);
  * runs beside the update of the others), "light_wave_short" (1: a flux-kernel wave without solution points runs the flux-point physics alone), "les_flux_kernel" (1: the LES
  * closure inside the flux kernel of variant 3), "over_int_fold" (1: the sum-factorised over-integration kernel hands the loader-wave flux kernel its
  * contribution to the divergence, n_fields values per solution point, instead of tdisf_upts), "fold_over_int" (1: the 2-D simplex
- * stage's element kernel carries a triangle block's registered over-integration; 0: the per-method launches in front of it), "bdy_beside" (0; 1: the fused stages' viscous boundary-face kernels on a side stream
+ * stage's element kernel carries a triangle block's registered over-integration; 0: the per-method launches in front of it), "blocks_2d" (0; 1: fused 4 takes several two-dimensional
+ * blocks -- a mixed quadrilateral / triangle mesh -- and a block of quadrilaterals of orders 1-4 on the 2-D simplex stage, see hfx_simplex2d_stage_plan), "bdy_beside" (0; 1: the fused stages' viscous boundary-face kernels on a side stream
  * beside the interior-face kernel), "affine_metrics" (1: on a block whose elements are all parallelepipeds -- metrics constant inside an
  * element up to rounding, detected when the fused tables are made -- the split stage's flux and update kernels read one 34-double metric record per element in place of
  * the per-point metric arrays (all but JGinv at the solution points); results agree with 0 to rounding, hfx_time_fused_kernels then lists "affine_metrics" behind the kernels), "general_waves" (0 = by LDS image | 3 | 4 | 8), "general_update_waves" (0 = by the staging registers | 4 | 8), "dense_waves" (0 = by the operator's rows | 4 | 8) and "dense_split" (0 | 1 | 2 | 4:
@@ -992,8 +993,24 @@ int hfx_general_plan(hfx_eles *e, int out[8]);
  * deferred stage has prepared the block, refused before): out[0] size class (order - 1: the kernel instantiation of P1..P5), out[1]
  * elements per group, out[2] waves per workgroup, out[3] 1: the element kernel forms the interior LDG corrections itself (no
  * face_delta_kernel), out[4] bytes of the element kernel's LDS image (operators + one group), out[5] the update kernel's, out[6..7] 0.
- * hfx_time_general_kernels and hfx_general_kernel_bytes answer for such a block with the stage's four steps. */
+ * hfx_time_general_kernels and hfx_general_kernel_bytes answer for such a block with the stage's four steps. 
+ * With option "blocks_2d" 1 it answers for every block the stage has prepared; a block of quadrilaterals of order p has size class
+ * 5 + (p - 1) (orders 1-4: 4/8, 9/12, 16/16, 25/20 solution / flux points, 64, 32, 16, 8 elements per group). */
 int hfx_simplex2d_plan(hfx_eles *e, int out[8]);
+/* With option "blocks_2d" 1 (default 0: every call below is refused as ever) hfx_run_steps_blocks(..., 4), hfx_time_general_kernels
+ * and the deferred stage run the 2-D simplex fused stage over SEVERAL two-dimensional blocks -- a mixed quadrilateral / triangle mesh,
+ * several triangle blocks -- and over one block of quadrilaterals: triangles of orders 1-5, quadrilaterals of orders 1-4 on the same
+ * dense kernels (plain forms; hfx_simplex2d_plan answers for each block, a quadrilateral block with size class 5 + (order - 1)),
+ * all blocks of one order.  An interior-face block between two element blocks (a cross block) takes each side's arrays from its own
+ * block; its LDG corrections are face_delta_kernel's (no partner word crosses blocks).  Refused before the first launch, naming
+ * fused 0: a block with a registered LES closure, over-integration or shock capturing, a partition-face block, blocks of different
+ * order, a three-dimensional block beside a two-dimensional one, quadrilaterals of order 5 and above;
+ * hfx_run_steps_partitioned_blocks keeps refusing several two-dimensional blocks.  A single block of triangles runs as with 0.
+ * What ONE stage over the prepared blocks launches (read-only; the list of blocks of the fused-4 call that prepared them, refused
+ * otherwise): out[0] element blocks, out[1] non-empty interior-face blocks, out[2] how many of them are cross blocks, out[3]
+ * face_delta_kernel launches per stage, out[4] all launches per stage (boundary sweeps, face_delta_kernel, one element and one update
+ * kernel per block, one face_flux2_kernel per interior-face block), out[5..7] 0. */
+int hfx_simplex2d_stage_plan(hfx_eles *const *eles, int n_ele_blocks, int out[8]);
 /* What the partitioned loop (hfx_run_steps_partitioned_blocks, or the deferred stage) runs on a block of triangles (read-only; valid
  * once a stage has prepared the block, refused before).  The kernels walk groups of out[1] of hfx_simplex2d_plan consecutive
  * elements: out[0] partition groups (an element of the group owns a partition flux point), out[1] interior groups (launched
