@@ -1237,6 +1237,7 @@ int hfx_eles_set_over_int(hfx_eles *e, int n_cubpts, const double *opp_over_int_
   if (e->u_cub.alloc(pc * e->n_fields) || e->t_cub.alloc(pc * e->n_fields * e->n_dims)) return 1;
   e->over_int_ready = true;
   e->over_int_serial++;
+  e->over_int_form_run = -1;
   fused_invalidate(e);
   general_invalidate(e); // (the general stage takes the closure / the de-aliased flux from the registration too)
   // tensor-product elements: 1-D factors of the two matrices for the sum-factorised kernel (tensor_ops.hip)
@@ -1253,6 +1254,7 @@ int hfx_eles_evaluate_invFlux_over_int(hfx_eles *e)
   HFX_DEFER(ctx, DM_EVALUATE_INVFLUX, e, nullptr, nullptr, 1, 0);
   e->stale &= ~(1u << HFX_TDISF_UPTS);
   if (tensor_over_int_available(e) && ctx->contract_mode != HFX_CONTRACT_DENSE) return tensor_over_int_launch(e);
+  e->over_int_form_run = 0;
   // interpolate the solution to the over-integration cubature points
   {
     const Operator *ops[1] = {&e->opp_over_int_cubpts};
@@ -1294,6 +1296,7 @@ int hfx_eles_set_shock_capture(hfx_eles *e, const double *inv_vandermonde, const
   e->h_persson_num = num;
   e->h_persson_den = den;
   e->shock_serial++;
+  e->shock_form_run = -1;
   e->s0 = s0;
   e->shock_det_field = shock_det_field;
   e->shock_ready = true;
@@ -1310,6 +1313,7 @@ int hfx_eles_shock_capture(hfx_eles *e)
   if (invalidate_fpts(e)) return 1;
   e->stale &= ~(1u << HFX_SENSOR);
   if (tensor_shock_available(e) && ctx->contract_mode != HFX_CONTRACT_DENSE) return tensor_shock_launch(e);
+  e->shock_form_run = 0;
   const long plane = (long)e->n_upts * e->n_eles;
   double *scratch = e->arr[HFX_TDISF_UPTS]; // free between AdvanceSolution and the next stage's evaluate_invFlux
   double *u = e->arr[HFX_DISU_UPTS0];

@@ -496,6 +496,9 @@ struct hfx_eles
   hfx::DevBuf<double> red_buf;            // device partial sums for reductions
   int red_blocks = 0;
   std::unique_ptr<hfx::TensorOps, hfx::TensorOpsDelete> tensor_ops; // 1-D factors of the over-integration / shock-capturing matrices
+  // the form the last over-integration / shock capturing of this block ran (hfx_eles_tensor_ops_plan): 1 sum-factorised, 0 dense,
+  // -1 none yet
+  int over_int_form_run = -1, shock_form_run = -1;
   // fused-path private data (built lazily)
   std::unique_ptr<hfx::FusedData, hfx::FusedDelete> fused;
   std::unique_ptr<hfx::GeneralData, hfx::GeneralDelete> general; // the general (non-tensor-product) fused stage (general.hip)

@@ -15,6 +15,7 @@ struct hfxh_case
   box_mesh mesh;
   std::vector<hfx_inters *> faces;
   std::string err;
+  hf_array<double> high_modes_d;
 };
 
 static thread_local std::string g_err;
@@ -168,6 +169,14 @@ extern "C" int hfxh_case_get_array(hfxh_case *c, const char *name, const double 
   else if (n == "vandermonde") a = &E->vandermonde;
   else if (n == "exp_filter") a = &E->exp_filter;
   else if (n == "norm_basis_persson") a = &E->norm_basis_persson;
+  else if (n == "persson_high_modes" && E->persson_high_modes.get_dim(0) > 0)
+  {
+    // (an int array: handed out as doubles through this double-typed getter)
+    hf_array<int> &hm = E->persson_high_modes;
+    c->high_modes_d.setup(hm.get_dim(0));
+    for (int i = 0; i < hm.get_dim(0); i++) c->high_modes_d(i) = hm(i);
+    a = &c->high_modes_d;
+  }
   else if (n == "opp_over_int_cubpts") a = &E->opp_over_int_cubpts;
   else if (n == "over_int_filter") a = &E->over_int_filter;
   else if (n == "filter_upts") a = &E->filter_upts;

@@ -528,6 +528,7 @@ int tensor_over_int_launch(hfx_eles *e, bool folded)
   // (folded: n_fields values per solution point, in the first n_fields planes of tdisf_upts)
   a.tdisf = e->arr[HFX_TDISF_UPTS];
   a.gamma = e->ctx->params.gamma;
+  e->over_int_form_run = 1;
   // two regions of n_fields * Nc^nd doubles and the projection's intermediate, n_fields * N * Nc^(nd-1)
   const size_t lds = sizeof(double) * (size_t)e->n_fields * (2 * (size_t)e->n_cubpts + (size_t)T->N * (e->n_cubpts / T->Nc));
   const int per_cu = std::max(1, (int)((160 * 1024) / lds));
@@ -692,6 +693,7 @@ int tensor_shock_launch(hfx_eles *e, bool refresh_disu_fpts)
   a.W1 = T->W1; a.E1 = T->E1; a.wnum = T->wnum; a.wden = T->wden;
   a.sensor = e->arr[HFX_SENSOR];
   a.s0 = e->s0;
+  e->shock_form_run = 1;
   if (refresh_disu_fpts)
   {
     a.disu_fpts = e->arr[HFX_DISU_FPTS];
@@ -702,3 +704,14 @@ int tensor_shock_launch(hfx_eles *e, bool refresh_disu_fpts)
 }
 
 } // namespace hfx
+
+extern "C" int hfx_eles_tensor_ops_plan(hfx_eles *e, int out[8])
+{
+  HFX_CHECK(e && out, "hfx_eles_tensor_ops_plan: bad argument");
+  HFX_IMMEDIATE(e->ctx, 0);
+  const hfx::TensorOps *T = e->tensor_ops.get();
+  const bool oi = T && T->over_int && e->over_int_ready, sh = T && T->shock && e->shock_ready;
+  const int v[8] = {oi, oi ? T->N : 0, oi ? T->Nc : 0, oi && T->folded, sh, sh ? T->N : 0, e->over_int_form_run, e->shock_form_run};
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+  return 0;
+}

@@ -645,6 +645,13 @@ class Eles:
         check(lib().hfx_general_plan(self.h, out))
         return dict(zip(("size_class", "flux_waves", "flux_batched", "gather", "les", "update_waves", "fold", "flux_lds"), list(out)))
 
+    def tensor_ops_plan(self):
+        """over-integration and shock capturing on this block (hfx_eles_tensor_ops_plan): dict of over_int (1: factored), N, Nc,
+        folded, shock (1: factored), shock_N, over_int_ran, shock_ran (the form of the last call: 1 sum-factorised, 0 dense, -1 none)"""
+        out = (C.c_int * 8)()
+        check(lib().hfx_eles_tensor_ops_plan(self.h, out))
+        return dict(zip(("over_int", "N", "Nc", "folded", "shock", "shock_N", "over_int_ran", "shock_ran"), list(out)))
+
     def simplex2d_plan(self):
         """the form of the 2-D simplex fused stage on this block of triangles (hfx_simplex2d_plan), valid after a fused-4 call: dict of
         size_class, group, waves, gather, element_lds, update_lds"""

@@ -340,6 +340,19 @@ class Case:
             d["Jacobian_fpts"] = self.array("Jacobian_fpts")
             if int(self.cfg.get("SGS_model", 0)) >= 2:
                 d["filter_upts"] = self.array("filter_upts")
+        if self.cfg.get("over_int", 0):
+            # over-integration in the fixtures' form (oracle_py.Case, hfx.Eles.set_over_int)
+            d["over_int"] = np.array([1.0])
+            for k in ("opp_over_int_cubpts", "over_int_filter", "JGinv_over_int_cubpts"):
+                d[k] = self.array(k)
+        if self.cfg.get("shock_cap", 0):
+            # shock capturing likewise (oracle_py.Case, hfx.Eles.set_shock_capture)
+            d["shock_cap"] = np.array([float(self.cfg["shock_cap"])])
+            for k in ("inv_vandermonde", "exp_filter", "norm_basis_persson"):
+                d[k] = self.array(k)
+            d["persson_high_modes"] = self.array("persson_high_modes").astype(np.int32)
+            d["s0"] = np.array([float(self.cfg.get("s0", 0.0))])
+            d["shock_det_field"] = np.array([int(self.cfg.get("shock_det_field", 0))], dtype=np.int32)
         return d
 
     def to_device(self, device=0):

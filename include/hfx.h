@@ -989,6 +989,15 @@ int hfx_general_kernel_bytes(hfx_eles *const *eles, int n_ele_blocks, double byt
  * face_delta_kernel), out[4] 1: its LES form, out[5] waves of the update kernel (4, 8), out[6] 1: the folded correction
  * (opp_2 - opp_3 opp_1), out[7] bytes of the flux kernel's LDS image of a batch. */
 int hfx_general_plan(hfx_eles *e, int out[8]);
+/* Over-integration and shock capturing on this block: what the registered matrices allow and what ran last (read-only; valid at
+ * any time).  out[0] 1: opp_over_int_cubpts and over_int_filter were recognised as Kronecker powers of 1-D matrices (the
+ * sum-factorised kernel can run), 0: not (or none registered); out[1], out[2] their 1-D extents N (solution points) and Nc
+ * (cubature points), 0 where out[0] is 0; out[3] 1: the matrices of the form folded into the divergence are set (a split fused
+ * stage made them); out[4] 1: inv_vandermonde and exp_filter were recognised, out[5] their N.  out[6]: the form the last
+ * hfx_eles_evaluate_invFlux_over_int of this block ran, per method or inside a stage (1 sum-factorised, 0 dense, -1 none since
+ * the registration); out[7] the same for hfx_eles_shock_capture.  Option "tensor_ops" 0 and HFX_CONTRACT_DENSE leave out[0..5] as
+ * they are and show in out[6..7]. */
+int hfx_eles_tensor_ops_plan(hfx_eles *e, int out[8]);
 /* The same for a block of triangles, which fused 4 runs through the 2-D simplex fused stage (read-only; valid once a fused-4 call or a
  * deferred stage has prepared the block, refused before): out[0] size class (order - 1: the kernel instantiation of P1..P5), out[1]
  * elements per group, out[2] waves per workgroup, out[3] 1: the element kernel forms the interior LDG corrections itself (no

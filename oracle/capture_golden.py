@@ -55,11 +55,12 @@ BASE.update(TGV_FLUID)
 
 
 def case(name, n=3, dims=3, amp=0.0, steps=1, level=1, bcs=None, restart=False, tets=False, keep_every=1, ppts=False, curve=None,
-         orient_seed=None, **over):
+         orient_seed=None, tdisf_inv=False, last_stage_only=False, **over):
     d = dict(BASE)
     d.update(over)
     return dict(name=name, n=n, dims=dims, amp=amp, steps=steps, level=level, keys=d, bcs=bcs, restart=restart, tets=tets,
-                keep_every=keep_every, ppts=ppts, curve=curve, orient_seed=orient_seed)
+                keep_every=keep_every, ppts=ppts, curve=curve, orient_seed=orient_seed, tdisf_inv=tdisf_inv,
+                last_stage_only=last_stage_only)
 
 
 # boundary groups for the bdy_inters fixtures: states near the TGV initial state (rho 8.42e-4, T 300, Mach 0.1)
@@ -100,6 +101,9 @@ PRI_KEYS = dict(upts_type_pri_tri=0, upts_type_pri_1d=0, vcjh_scheme_pri_1d=1, e
 
 # threshold inside the widest gap of hex_p4_jet's first-stage sensor values (so that rounding cannot flip an element)
 HEX_P4_JET_S0 = 7.0e-7
+# the sides of hex_p4_jet, and of its 2-D twin (a subsonic inlet: the supersonic one points along z)
+JET_SIDES = {"z-": "SupI", "z+": "SupO", "x-": "Out", "x+": "Out", "y-": "Slip", "y+": "Slip"}
+JET_SIDES_2D = {"x-": "InS", "x+": "Out", "y-": "Slip", "y+": "Slip"}
 
 CASES = [
     # full dump of every intermediate of one residual on a deformed mesh
@@ -249,6 +253,27 @@ CASES = [
     case("hex_p4_jet", n=2, amp=0.12, level=1, order=4, steps=1, riemann_solve_type=3, over_int=1, over_int_order=6,
          shock_cap=1, shock_det=0, s0=HEX_P4_JET_S0, expf_fac=36.0, expf_order=4, expf_cutoff=1, shock_det_field=0,
          bcs={"z-": "SupI", "z+": "SupO", "x-": "Out", "x+": "Out", "y-": "Slip", "y+": "Slip"}, **BC_KEYS),
+    # the corners of the instantiation table of the sum-factorised over-integration and shock-capturing kernels (csrc/tensor_ops.hip:
+    # N = 2..6 solution points per direction, N <= Nc <= 10 cubature points): both ingredients together on a box of two cells per
+    # direction between boundaries, one step, the de-aliased flux of the first residual kept (tdisf_inv); s0 in the widest gap of
+    # the first stage's sensors.  P1 with expf_cutoff 0: with cutoff 1 = order no mode is damped and the filter is the identity.
+    # The P5 hexahedra keep the state after the step's last stage only: with every stage the file passes 1 MiB.
+    case("hex_p1_overint_shock_min", n=2, amp=0.12, level=1, order=1, steps=1, tdisf_inv=True, over_int=1, over_int_order=1,
+         shock_cap=1, shock_det=0, s0=5.0e-8, expf_fac=36.0, expf_order=4, expf_cutoff=0, shock_det_field=0, bcs=JET_SIDES, **BC_KEYS),
+    case("hex_p1_overint_shock_max", n=2, amp=0.12, level=1, order=1, steps=1, tdisf_inv=True, over_int=1, over_int_order=9,
+         shock_cap=1, shock_det=0, s0=5.0e-8, expf_fac=36.0, expf_order=4, expf_cutoff=0, shock_det_field=0, bcs=JET_SIDES, **BC_KEYS),
+    case("hex_p5_overint_shock", n=2, amp=0.12, level=1, order=5, steps=1, tdisf_inv=True, last_stage_only=True, over_int=1,
+         over_int_order=5, shock_cap=1, shock_det=0, s0=1.0e-8, expf_fac=36.0, expf_order=4, expf_cutoff=1, shock_det_field=0,
+         bcs=JET_SIDES, **BC_KEYS),
+    case("quad_p1_overint_shock", dims=2, n=2, amp=0.1, level=1, order=1, steps=1, tdisf_inv=True, over_int=1, over_int_order=1,
+         shock_cap=1, shock_det=0, s0=8.0e-8, expf_fac=36.0, expf_order=4, expf_cutoff=0, shock_det_field=0, bcs=JET_SIDES_2D,
+         **BC_KEYS),
+    case("quad_p5_overint_shock", dims=2, n=2, amp=0.1, level=1, order=5, steps=1, tdisf_inv=True, over_int=1, over_int_order=9,
+         shock_cap=1, shock_det=0, s0=8.0e-10, expf_fac=36.0, expf_order=4, expf_cutoff=1, shock_det_field=0, bcs=JET_SIDES_2D,
+         **BC_KEYS),
+    case("quad_p2_overint_shock", dims=2, n=2, amp=0.1, level=1, order=2, steps=1, tdisf_inv=True, over_int=1, over_int_order=4,
+         shock_cap=1, shock_det=0, s0=2.018e-5, expf_fac=36.0, expf_order=4, expf_cutoff=0, shock_det_field=1, bcs=JET_SIDES_2D,
+         **BC_KEYS),
     # boundary faces (bdy_inters): every ghost-state branch that the shipped cases use
     case("hex_p2_bdy_walls", amp=0.1, level=2, order=2, steps=1,
          bcs={"z-": "In", "z+": "Out", "y-": "WallT", "y+": "WallQ", "x-": "Far", "x+": "Slip"}, **BC_KEYS),
@@ -430,6 +455,10 @@ def run_case(c):
             env["HFX_DUMP_RESTART"] = "1"
         if c.get("ppts"):
             env["HFX_DUMP_PPTS"] = "1"
+        if c.get("tdisf_inv"):
+            env["HFX_DUMP_TDISF_INV"] = "1"
+        if c.get("last_stage_only"):
+            env["HFX_DUMP_LAST_STAGE_ONLY"] = "1"
         r = subprocess.run([HARNESS, "input", "dump.bin", str(c["steps"]), str(c["level"])],
                            cwd=td, env=env, capture_output=True, text=True)
         if r.returncode != 0:

@@ -553,7 +553,8 @@ int main(int argc, char *argv[])
           for (i = 0; i < FlowSol.n_ele_types; i++) FlowSol.mesh_eles(i)->evaluate_invFlux_over_int();
         else
           for (i = 0; i < FlowSol.n_ele_types; i++) FlowSol.mesh_eles(i)->evaluate_invFlux();
-        if (level >= 2) put_all("s0_tdisf_upts_inv", [](eles *X) -> hf_array<double> & { return X->tdisf_upts; });
+        // (HFX_DUMP_TDISF_INV: a level-1 fixture that still holds the inviscid flux, for the over-integration cases)
+        if (level >= 2 || getenv("HFX_DUMP_TDISF_INV")) put_all("s0_tdisf_upts_inv", [](eles *X) -> hf_array<double> & { return X->tdisf_upts; });
         for (i = 0; i < FlowSol.n_int_inter_types; i++) FlowSol.mesh_int_inters(i).calculate_common_invFlux();
         for (i = 0; i < FlowSol.n_bdy_inter_types; i++)
           FlowSol.mesh_bdy_inters(i).evaluate_boundaryConditions_invFlux(&FlowSol, FlowSol.time);
@@ -629,7 +630,7 @@ int main(int argc, char *argv[])
         if (step == 0 && rk == 0) put_arr("s0_sensor", E->sensor);
       }
 
-      if (level >= 1 || rk == RKSteps - 1)
+      if ((level >= 1 && !getenv("HFX_DUMP_LAST_STAGE_ONLY")) || rk == RKSteps - 1)
       {
         char nm[64];
         snprintf(nm, sizeof nm, "u_step%d_stage%d", step, rk);

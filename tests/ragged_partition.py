@@ -21,7 +21,7 @@ import numpy as np
 
 # arrays of a registration dict that carry an element axis, and which one: (pt, ele, ...) or (dim, dim, pt, ele)
 ELEMENT_AXIS = {"detjac_upts": 1, "detjac_fpts": 1, "tdA_fpts": 1, "norm_fpts": 1, "u_init": 1, "wall_distance": 1,
-                "JGinv_upts": 3, "JGinv_fpts": 3, "Jacobian_fpts": 3}
+                "JGinv_upts": 3, "JGinv_fpts": 3, "Jacobian_fpts": 3, "JGinv_over_int_cubpts": 3}
 
 
 def F32(a):

@@ -11,6 +11,9 @@ are those of the input; per element
 
     arrays over points           permuted along the point axis, values copied (norm_fpts keeps its rounding noise bit for bit)
     JGinv_*  (ref, phys, pt, e)  permuted; |J| dxi'/dx = G |J| dxi/dx (csrc/host/eles.cpp, set_transforms_pts: first index reference)
+                                 (JGinv_over_int_cubpts: through the permutation of the over-integration cubature points, a tensor
+                                 Gauss set and as invariant as the solution points; the class-level matrices of over-integration and
+                                 shock capturing are those of the input)
     Jacobian_fpts (phys, ref)    permuted; dx/dxi' = dx/dxi G^T
     int*_L, int*_R, bdy*_L       renumbered through the flux-point permutation, every column sorted again so that the left side's
                                  offsets ascend (the reference's tables), the R column carried along
@@ -29,7 +32,9 @@ FPTS_ARRAYS = ("detjac_fpts", "tdA_fpts", "norm_fpts")
 # what a registration may hold besides: class-level operators, run-wide scalars, boundary groups
 CLASS_LEVEL = re.compile(r"^(sizes|opp_[0-6](_[0-2])?|gamma|prandtl|rt_inf|mu_inf|c_sth|fix_vis|ldg_beta|ldg_tau|dt|viscous|"
                          r"riemann_solve_type|vis_riemann_solve_type|adv_type|dt_type|RK_a|RK_b|bc_flags|bc_params|bc_R_ref|"
-                         r"ramp_counter|LES|SGS_model|C_s|filter_ratio|Kappa|prandtl_t|(int|bdy)[0-2]_(L|R|id))$")
+                         r"ramp_counter|LES|SGS_model|C_s|filter_ratio|Kappa|prandtl_t|(int|bdy)[0-2]_(L|R|id)|"
+                         r"over_int|opp_over_int_cubpts|over_int_filter|shock_cap|inv_vandermonde|exp_filter|norm_basis_persson|"
+                         r"persson_high_modes|s0|shock_det_field)$")
 
 _upts_perm = {}  # (n_dims, n_upts) -> (n_rot, n_upts): what `back` reads
 
@@ -72,9 +77,10 @@ def orientation_vector(n_eles, n_dims, seed):
     return rot
 
 
-def reorient(reg, rot, loc_upts, tloc_fpts):
+def reorient(reg, rot, loc_upts, tloc_fpts, loc_over_int_cubpts=None):
     """the registration dict `reg` with element e in the coordinates G_rot[e] xi; loc_upts / tloc_fpts: (n_dims, n_points)
-    reference locations of the solution and flux points (hfx_host.Case.array)"""
+    reference locations of the solution and flux points (hfx_host.Case.array); loc_over_int_cubpts: those of the over-integration
+    cubature points, needed where `reg` holds JGinv_over_int_cubpts"""
     sz = [int(v) for v in reg["sizes"]]
     ne, nu, nfp, nd = sz[0], sz[1], sz[2], sz[4]
     rot = np.asarray(rot)
@@ -86,6 +92,13 @@ def reorient(reg, rot, loc_upts, tloc_fpts):
     pu = np.stack([point_perm(G, loc_upts) for G in Gs])
     pf = np.stack([point_perm(G, tloc_fpts) for G in Gs])
     assert np.array_equal(_upts_perm.setdefault((nd, nu), pu), pu)
+    pc = None
+    oi_keys = [k in reg for k in ("over_int", "opp_over_int_cubpts", "over_int_filter", "JGinv_over_int_cubpts")]
+    assert all(oi_keys) or not any(oi_keys), "over-integration: the class-level matrices and the metrics at the cubature points go together"
+    if "JGinv_over_int_cubpts" in reg:
+        assert loc_over_int_cubpts is not None, "JGinv_over_int_cubpts needs the cubature locations"
+        assert np.shape(loc_over_int_cubpts) == (nd, np.shape(reg["JGinv_over_int_cubpts"])[2])
+        pc = np.stack([point_perm(G, loc_over_int_cubpts) for G in Gs])
     out = dict(reg)
     for k, axis in ELEMENT_AXIS.items():
         if k not in reg:
@@ -98,8 +111,8 @@ def reorient(reg, rot, loc_upts, tloc_fpts):
             rows = signed_rows(Gs[r])
             if k in UPTS_ARRAYS or k in FPTS_ARRAYS:
                 new[:, el] = a[(pu if k in UPTS_ARRAYS else pf)[r]][:, el]
-            elif k in ("JGinv_upts", "JGinv_fpts"):
-                p = (pu if k == "JGinv_upts" else pf)[r]
+            elif k in ("JGinv_upts", "JGinv_fpts", "JGinv_over_int_cubpts"):
+                p = (pu if k == "JGinv_upts" else pf if k == "JGinv_fpts" else pc)[r]
                 for k2, (k1, s) in enumerate(rows):
                     new[k2][:, :, el] = (a[k1] if s > 0 else -a[k1])[:, p][:, :, el]
             else:

@@ -18,6 +18,12 @@ def test_general_plan_query_is_part_of_the_abi():
     assert hasattr(hfx.lib(), "hfx_general_plan") and hasattr(hfx.Eles, "general_plan")
 
 
+def test_tensor_ops_plan_query_is_part_of_the_abi():
+    # which form over-integration and shock capturing ran (tests/test_gpu_tensor_ops.py asserts what it returns)
+    assert "hfx_eles_tensor_ops_plan" in hfx.declared_symbols()
+    assert hasattr(hfx.lib(), "hfx_eles_tensor_ops_plan") and hasattr(hfx.Eles, "tensor_ops_plan")
+
+
 def test_struct_layouts_match_oracle_binding():
     # hfx_params and orc_params are declared field-for-field alike (include/hfx.h, oracle/oracle.h)
     import oracle_py as O

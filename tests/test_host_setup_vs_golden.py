@@ -158,7 +158,10 @@ def test_isentropic_vortex_initial_state():
     c.close()
 
 
-MODAL = ["hex_p2_overint", "quad_p3_overint", "hex_p3_shock", "hex_p2_shock_energy", "quad_p3_shock", "hex_p4_jet"]
+MODAL = ["hex_p2_overint", "quad_p3_overint", "hex_p3_shock", "hex_p2_shock_energy", "quad_p3_shock", "hex_p4_jet",
+         # the corners of the sum-factorised kernels' instantiation table (tests/test_gpu_tensor_ops.py)
+         "hex_p1_overint_shock_min", "hex_p1_overint_shock_max", "hex_p5_overint_shock", "quad_p1_overint_shock",
+         "quad_p5_overint_shock", "quad_p2_overint_shock"]
 
 
 @pytest.mark.parametrize("name", MODAL)
